@@ -12,8 +12,13 @@ The untimed setup runs the ViT encode and the S=770 prefill (reported separately
 exactly K decode steps between barrier + synchronize pairs; rank 0 prints ONE JSON line.
 
 N > 1: tensor parallel over the N GPUs (heads/ffn sharded, RCCL all-reduce over xGMI): total work is fixed, so
-"scaling" is "strong".  `roofline` is the weight-streaming GEMV (dominant kernel, HBM-bound); `cpu_baseline`
-is the CPU oracle (oracle/emu2_ref.py) timed on this box's host cores on a bounded sample.
+"scaling" is "strong".
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the JSON line (and, with
+--dump-outputs DIR, the last timed step's logits and ids as .npy files).  With --full it also measures everything else:
+`roofline` is the weight-streaming GEMV (dominant kernel, HBM-bound; an eager replay of its own), `cpu_baseline`
+is the CPU oracle (oracle/emu2_ref.py) timed on the host cores on a bounded sample, and the fp8 / 5-beam / denoise /
+BASELINE-config legs run after the headline.
 """
 import argparse
 import json
@@ -59,7 +64,17 @@ def parse():
                    "run exactly N prefills of the S=770 prompt shape and print the algorithmic bytes of their GEMMs")
     p.add_argument("--pmc-mode", type=int, default=0, metavar="N", help="profiling aid for rocprofv3 --pmc passes: after the "
                    "prefill run exactly N eager decode steps and print the algorithmic bytes of every GEMV launch of the process")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="everything beyond the headline: ViT / prefill timings, the GEMV roofline "
+                   "replay, the fp8 / 5-beam / denoise / BASELINE-config legs, the opt-in TP prefill leg and the CPU baselines "
+                   "(the --no-* switches above still drop single legs); without it a run sets up, warms up, times the decode steps "
+                   "and prints the headline line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                   "returned (rank 0): DIR/logits.npy (float32 [1, vocab]), DIR/next_token.npy and DIR/generated_ids.npy (float64: "
+                   "the greedy ids of the current decode segment, prompt's first new token included)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def gemm_source_hash():
@@ -92,6 +107,21 @@ def gemv_source_hash():
 
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, st):
+    """What the last timed decode step handed its caller, as .npy under out_dir: its logits row (bf16 -> float32, exact), the
+    greedy id it picked and the ids of the current decode segment so far (int32 -> float64, exact).  About 130 KB in all."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(st.step_idx.item())
+    arrays = {"logits": st.logits.float().cpu().numpy().astype(np.float32),
+              "next_token": st.cur.cpu().numpy().astype(np.float64),
+              "generated_ids": st.out_ids[:n, 0].cpu().numpy().astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {tuple(v.shape)}" for k, v in arrays.items()))
 
 
 def cpu_baseline(seconds: float, ctx_len: int, vocab: int):
@@ -705,11 +735,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- untimed: ViT encode + prefill (reported separately)
+    # ---- untimed: ViT encode + prefill (reported separately under --full)
     with torch.no_grad():
-        sync(); t = time.perf_counter()
-        enc = m.encode_image(img)
-        sync(); vit_ms = (time.perf_counter() - t) * 1e3
+        if a.full:
+            sync(); t = time.perf_counter()
+            m.encode_image(img)
+            sync(); vit_ms = (time.perf_counter() - t) * 1e3
         x = m._prompt_embeds(ids, img, vcfg.n_query)
         sync(); t = time.perf_counter()
         # what generate() would allocate for this request; a run longer than the model's 2048 positions decodes in
@@ -721,16 +752,17 @@ def main():
         sync(); t = time.perf_counter()
         hidden, kstart, next_pos = lm.prefill(x.view(1, S, -1), mask, s_max)
         sync(); prefill_ms = (time.perf_counter() - t) * 1e3
-        # steady state of each (the first call includes lazy code-object loads, and a single 15 / 50 ms burst after an idle
-        # synchronisation runs on a clock that is still ramping): 4 back-to-back calls, mean -- like every other leg's W + K steps
-        sync(); t = time.perf_counter()
-        for _ in range(4):
-            m.encode_image(img)
-        sync(); vit_ms2 = (time.perf_counter() - t) * 1e3 / 4
-        sync(); t = time.perf_counter()
-        for _ in range(4):
-            hidden, kstart, next_pos = lm.prefill(x.view(1, S, -1), mask, s_max)
-        sync(); prefill_ms2 = (time.perf_counter() - t) * 1e3 / 4
+        if a.full:
+            # steady state of each (the first call includes lazy code-object loads, and a single 15 / 50 ms burst after an idle
+            # synchronisation runs on a clock that is still ramping): 4 back-to-back calls, mean -- like every other leg's W + K steps
+            sync(); t = time.perf_counter()
+            for _ in range(4):
+                m.encode_image(img)
+            sync(); vit_ms2 = (time.perf_counter() - t) * 1e3 / 4
+            sync(); t = time.perf_counter()
+            for _ in range(4):
+                hidden, kstart, next_pos = lm.prefill(x.view(1, S, -1), mask, s_max)
+            sync(); prefill_ms2 = (time.perf_counter() - t) * 1e3 / 4
         logits = lm.logits(hidden[:, -1, :])
         cur = ops.argmax(logits, suppress_id=2)
     total = min(a.warmup + a.steps + 8, seg + 8)
@@ -781,6 +813,8 @@ def main():
             step()
         sync()
         dt = time.perf_counter() - t
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, st)
     per_rank_ms = None
     if world > 1:
         # every rank's own clock around the same K steps (they end together: each step holds 2 x layers all-reduces), then MAX
@@ -793,29 +827,30 @@ def main():
         dt = float(tt.item())
     tok_s = a.steps / dt
 
-    # ---- roofline leg: HIP events around every GEMV launch of the SAME steps, replayed eagerly
-    check(lib().emu_profile_gemv(1), "emu_profile_gemv")
-    n_prof = min(8, a.steps)
-    st.reset(cur, next_pos, S)                                  # eager replay from the end of the prompt
-    with torch.no_grad():
-        for _ in range(n_prof):
-            st.step()
-    torch.cuda.synchronize()
-    ms, wb, nl = C.c_double(), C.c_double(), C.c_long()
-    check(lib().emu_profile_gemv_read(C.byref(ms), C.byref(wb), C.byref(nl)), "emu_profile_gemv_read")
-    check(lib().emu_profile_gemv(0), "emu_profile_gemv")
-    gemv_ms_per_tok = ms.value / n_prof
-    bytes_per_launch = wb.value / max(1, nl.value)
-    avg_launch_s = ms.value * 1e-3 / max(1, nl.value)
-    achieved = bytes_per_launch / avg_launch_s
-    ctx_mid = S + a.warmup + a.steps // 2
-    kv_bytes = 2 * lcfg.num_hidden_layers * (lm.plan.heads_local * lcfg.head_dim) * 2 * ctx_mid
-    ids_host = out_ids[: min(a.warmup + a.steps, total) + 1, 0].tolist()
+    if a.full:
+        # ---- roofline leg: HIP events around every GEMV launch of the SAME steps, replayed eagerly
+        check(lib().emu_profile_gemv(1), "emu_profile_gemv")
+        n_prof = min(8, a.steps)
+        st.reset(cur, next_pos, S)                                  # eager replay from the end of the prompt
+        with torch.no_grad():
+            for _ in range(n_prof):
+                st.step()
+        torch.cuda.synchronize()
+        ms, wb, nl = C.c_double(), C.c_double(), C.c_long()
+        check(lib().emu_profile_gemv_read(C.byref(ms), C.byref(wb), C.byref(nl)), "emu_profile_gemv_read")
+        check(lib().emu_profile_gemv(0), "emu_profile_gemv")
+        gemv_ms_per_tok = ms.value / n_prof
+        bytes_per_launch = wb.value / max(1, nl.value)
+        avg_launch_s = ms.value * 1e-3 / max(1, nl.value)
+        achieved = bytes_per_launch / avg_launch_s
+        ctx_mid = S + a.warmup + a.steps // 2
+        kv_bytes = 2 * lcfg.num_hidden_layers * (lm.plan.heads_local * lcfg.head_dim) * 2 * ctx_mid
+        ids_host = out_ids[: min(a.warmup + a.steps, total) + 1, 0].tolist()
 
     # ---- extra leg (never the headline): same decode loop over the fp8 e4m3 weight stream (BASELINE.json configs[5]'s
     # weight-only quantised serving mode); prefill + KV cache stay bf16
     fp8 = None
-    if not a.no_fp8 and world == 1:                             # extra legs run on one GPU only: an N > 1 run carries the headline and nothing that could stall it
+    if a.full and not a.no_fp8 and world == 1:                  # extra legs run on one GPU only: an N > 1 run carries the headline and nothing that could stall it
         try:
             t0 = time.time()
             lm.use_fp8(True)
@@ -905,7 +940,7 @@ def main():
     # ---- extra leg (never the headline): the reference's DEFAULT decoding mode, 5-beam search (emu.py:163-172), whole call
     # (prefill + KV replication + 24 beam steps, 5 activation rows per weight stream); TP=1 only
     beam = None
-    if not a.no_beam and world == 1:
+    if a.full and not a.no_beam and world == 1:
         try:
             n_new = 24
             with torch.no_grad():
@@ -940,7 +975,7 @@ def main():
 
     # ---- second half of the metric: SDXL-style UNet denoise (BASELINE.json configs[3]), replicas only across GPUs
     denoise = None
-    if not a.no_denoise:
+    if a.full and not a.no_denoise:
         # across GPUs this leg runs REPLICAS: every rank times its own loop with no collective inside (a rank that fails
         # must not leave the others in a barrier), then one all_gather_object that every rank reaches
         denoise_leg.no_fp8 = a.no_fp8 or world > 1
@@ -957,7 +992,7 @@ def main():
             denoise["scaling"] = "replicas only (independent images per GPU; value = sum over the ranks' own rates)"
 
     legs = None
-    if not a.no_legs and world == 1:
+    if a.full and not a.no_legs and world == 1:
         try:
             config_legs.no_fp8 = a.no_fp8
             legs = config_legs(m, lm, ctx, dev, vcfg, lcfg, img, getattr(denoise_leg, "engine", None))
@@ -965,7 +1000,7 @@ def main():
             legs = {"note": f"legs failed: {type(e).__name__}: {e}"}
 
     tp_prefill = None
-    if world > 1 and a.tp_prefill_leg >= 1024:
+    if a.full and world > 1 and a.tp_prefill_leg >= 1024:
         # opt-in (see --tp-prefill-leg): the same S-row prompt under both prefill schedules, every rank's clock, MAX over ranks
         try:
             Sx = a.tp_prefill_leg
@@ -993,40 +1028,42 @@ def main():
         except Exception as e:                                  # never lose the headline to an extra leg
             tp_prefill = {"note": f"leg failed: {type(e).__name__}: {e}"}
 
-    # HBM traffic of the GEMV launches comes from PMC counters (FETCH_SIZE), which a timing run cannot collect itself:
-    # the committed pass over THIS command (profiles/r03_gemv_pmc_traffic.json, gfx950-corrected) gives traffic /
-    # algorithmic bytes for the same kernels; traffic = that ratio x this run's algorithmic bytes per launch
-    traffic, traffic_src = None, "no PMC pass over the GEMV sources committed"
-    for rnd in ("r06", "r05", "r03"):                               # the newest committed pass whose kernel sources are these
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", f"{rnd}_gemv_pmc_traffic.json")))
-        except Exception:
-            continue
-        if pmc.get("source_sha256") == gemv_source_hash():
-            ratio = float(pmc["all_gemv_launches"]["traffic_over_algorithmic"])
-            traffic = ratio * bytes_per_launch
-            traffic_src = (f"profiles/{rnd}_gemv_pmc_traffic.json (same kernel sources, sha256 checked): rocprofv3 --pmc FETCH_SIZE "
-                           f"pass over `bench.py --pmc-mode`, gfx950-corrected; traffic / algorithmic = {ratio:.4f}")
-            break
-        traffic_src = f"profiles/{rnd}_gemv_pmc_traffic.json is STALE (taken on other kernel sources: re-run tools/pmc_traffic.sh); traffic not reported"
+    if a.full:
+        # HBM traffic of the GEMV launches comes from PMC counters (FETCH_SIZE), which a timing run cannot collect itself:
+        # the committed pass over THIS command (profiles/r03_gemv_pmc_traffic.json, gfx950-corrected) gives traffic /
+        # algorithmic bytes for the same kernels; traffic = that ratio x this run's algorithmic bytes per launch
+        traffic, traffic_src = None, "no PMC pass over the GEMV sources committed"
+        for rnd in ("r06", "r05", "r03"):                               # the newest committed pass whose kernel sources are these
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", f"{rnd}_gemv_pmc_traffic.json")))
+            except Exception:
+                continue
+            if pmc.get("source_sha256") == gemv_source_hash():
+                ratio = float(pmc["all_gemv_launches"]["traffic_over_algorithmic"])
+                traffic = ratio * bytes_per_launch
+                traffic_src = (f"profiles/{rnd}_gemv_pmc_traffic.json (same kernel sources, sha256 checked): rocprofv3 --pmc FETCH_SIZE "
+                               f"pass over `bench.py --pmc-mode`, gfx950-corrected; traffic / algorithmic = {ratio:.4f}")
+                break
+            traffic_src = f"profiles/{rnd}_gemv_pmc_traffic.json is STALE (taken on other kernel sources: re-run tools/pmc_traffic.sh); traffic not reported"
 
-    prefill_traffic, prefill_traffic_src = None, "no PMC pass over the GEMM sources committed"
-    for rnd in ("r06", "r05", "r04", "r03"):                        # the newest committed pass whose kernel sources are these
-        try:
-            pm = json.load(open(os.path.join(ROOT, "profiles", f"{rnd}_prefill_gemm_pmc_traffic.json")))
-        except Exception:
-            continue
-        if pm.get("source_sha256") == gemm_source_hash():
-            prefill_traffic = float(pm["traffic_over_algorithmic"]) * prefill_gemm_bytes(lcfg, S)
-            prefill_traffic_src = (f"profiles/{rnd}_prefill_gemm_pmc_traffic.json (same kernel sources, sha256 checked): traffic / algorithmic GEMM "
-                                   f"bytes = {float(pm['traffic_over_algorithmic']):.3f}")
-            break
-        prefill_traffic_src = f"profiles/{rnd}_prefill_gemm_pmc_traffic.json is STALE (other kernel sources): traffic not reported"
-    if rank == 0:
+        prefill_traffic, prefill_traffic_src = None, "no PMC pass over the GEMM sources committed"
+        for rnd in ("r06", "r05", "r04", "r03"):                        # the newest committed pass whose kernel sources are these
+            try:
+                pm = json.load(open(os.path.join(ROOT, "profiles", f"{rnd}_prefill_gemm_pmc_traffic.json")))
+            except Exception:
+                continue
+            if pm.get("source_sha256") == gemm_source_hash():
+                prefill_traffic = float(pm["traffic_over_algorithmic"]) * prefill_gemm_bytes(lcfg, S)
+                prefill_traffic_src = (f"profiles/{rnd}_prefill_gemm_pmc_traffic.json (same kernel sources, sha256 checked): traffic / algorithmic GEMM "
+                                       f"bytes = {float(pm['traffic_over_algorithmic']):.3f}")
+                break
+            prefill_traffic_src = f"profiles/{rnd}_prefill_gemm_pmc_traffic.json is STALE (other kernel sources): traffic not reported"
+    if rank == 0 and a.full:
         for what, val, src in (("roofline.traffic", traffic, traffic_src), ("prefill_roofline.traffic", prefill_traffic, prefill_traffic_src)):
             if val is None:                                     # loud, but never at the price of the line itself
                 log(f"WARNING: {what} is not reported -- {src}.  Re-run tools/pmc_traffic.sh / tools/pmc_prefill_traffic.sh on the final sources and "
                     "commit their output under profiles/.")
+    if rank == 0:
         prefill_flops = lcfg.num_hidden_layers * (2 * S * (4 * lcfg.hidden_size ** 2 + 3 * lcfg.hidden_size * lcfg.intermediate_size)
                                                    + 2 * S * S * lcfg.hidden_size)
         res = {
@@ -1049,28 +1086,31 @@ def main():
                               if world > 1 else None),
                        "launch": "hipGraph replay" if use_graph else "eager",
                        "valid": bool(a.layers == 60 and a.vit_layers == 64 and not shared and not a.gemm_tune)},
-            "roofline": {"bound": "hbm", "kernel": "gemv_kernel (weight-streaming GEMV, all epilogues)",
-                         "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK, "traffic": traffic, "traffic_source": traffic_src,
-                         "bytes_per_launch": bytes_per_launch, "avg_launch_us": avg_launch_s * 1e6,
-                         "launches_per_token": nl.value / n_prof, "gemv_ms_per_token": gemv_ms_per_tok,
-                         "measured": f"HIP events on the launch stream around each GEMV, eager replay of {n_prof} decode steps",
-                         "token_level_frac": (lm.weight_bytes_per_token() + kv_bytes) * tok_s / HBM_PEAK},
-            "extra": {"vit_encode_ms": min(vit_ms, vit_ms2), "prefill_ms": min(prefill_ms, prefill_ms2),
-                      "prefill_roofline": {"bound": "mfma", "achieved": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / 1e12,
-                                           "peak": MFMA_BF16_PEAK / 1e12, "unit": "TFLOP/s",
-                                           "frac": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / MFMA_BF16_PEAK,
-                                           "flops": prefill_flops / world, "traffic": prefill_traffic,
-                                           "traffic_source": prefill_traffic_src, "algorithmic_gemm_bytes": prefill_gemm_bytes(lcfg, S)},
-                      "vit_roofline": {"bound": "mfma", "achieved": VIT_FLOPS_PER_IMAGE / (min(vit_ms, vit_ms2) * 1e-3) / 1e12,
-                                       "peak": MFMA_BF16_PEAK / 1e12, "unit": "TFLOP/s",
-                                       "frac": VIT_FLOPS_PER_IMAGE / (min(vit_ms, vit_ms2) * 1e-3) / MFMA_BF16_PEAK,
-                                       "flops": VIT_FLOPS_PER_IMAGE, "traffic": None},
-                      "prefill_tflops": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / 1e12,
-                      "prefill_mfma_frac": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / MFMA_BF16_PEAK,
-                      "weight_bytes_per_token_per_gpu": lm.weight_bytes_per_token(), "kv_bytes_per_token_per_gpu": kv_bytes,
-                      "first_tokens": ids_host[:8]},
         }
+        if a.full:
+            res.update({
+                "roofline": {"bound": "hbm", "kernel": "gemv_kernel (weight-streaming GEMV, all epilogues)",
+                             "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK, "traffic": traffic, "traffic_source": traffic_src,
+                             "bytes_per_launch": bytes_per_launch, "avg_launch_us": avg_launch_s * 1e6,
+                             "launches_per_token": nl.value / n_prof, "gemv_ms_per_token": gemv_ms_per_tok,
+                             "measured": f"HIP events on the launch stream around each GEMV, eager replay of {n_prof} decode steps",
+                             "token_level_frac": (lm.weight_bytes_per_token() + kv_bytes) * tok_s / HBM_PEAK},
+                "extra": {"vit_encode_ms": min(vit_ms, vit_ms2), "prefill_ms": min(prefill_ms, prefill_ms2),
+                          "prefill_roofline": {"bound": "mfma", "achieved": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / 1e12,
+                                               "peak": MFMA_BF16_PEAK / 1e12, "unit": "TFLOP/s",
+                                               "frac": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / MFMA_BF16_PEAK,
+                                               "flops": prefill_flops / world, "traffic": prefill_traffic,
+                                               "traffic_source": prefill_traffic_src, "algorithmic_gemm_bytes": prefill_gemm_bytes(lcfg, S)},
+                          "vit_roofline": {"bound": "mfma", "achieved": VIT_FLOPS_PER_IMAGE / (min(vit_ms, vit_ms2) * 1e-3) / 1e12,
+                                           "peak": MFMA_BF16_PEAK / 1e12, "unit": "TFLOP/s",
+                                           "frac": VIT_FLOPS_PER_IMAGE / (min(vit_ms, vit_ms2) * 1e-3) / MFMA_BF16_PEAK,
+                                           "flops": VIT_FLOPS_PER_IMAGE, "traffic": None},
+                          "prefill_tflops": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / 1e12,
+                          "prefill_mfma_frac": prefill_flops / world / (min(prefill_ms, prefill_ms2) * 1e-3) / MFMA_BF16_PEAK,
+                          "weight_bytes_per_token_per_gpu": lm.weight_bytes_per_token(), "kv_bytes_per_token_per_gpu": kv_bytes,
+                          "first_tokens": ids_host[:8]},
+            })
         if fp8 is not None:
             res["decode_fp8_weights"] = fp8
         if beam is not None:
@@ -1079,7 +1119,7 @@ def main():
             res["denoise"] = denoise
         if legs is not None:
             res["legs"] = legs
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(a.cpu_seconds, S, VOCAB_EMU2_CHAT)
             except Exception as e:                              # never lose the GPU line to a host-side problem

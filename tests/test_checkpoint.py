@@ -1,5 +1,6 @@
 """Checkpoint ingestion on CPU: single files and Hugging Face sharded checkpoints stream the same (key, tensor) pairs;
-the reference's own index file (Emu2/emu/conf/llama_config/pytorch_model.bin.index.json) names exactly the LLaMA-33B
+the reference's own index file (Emu2/emu/conf/llama_config/pytorch_model.bin.index.json, its tensor names frozen in
+tests/golden/llama_config_ref.json) names exactly the LLaMA-33B
 tensors the engine's inventory expects."""
 import json
 import os
@@ -58,15 +59,15 @@ def test_index_missing_key_is_reported(tmp_path):
         list(iter_checkpoint(str(tmp_path)))
 
 
-def test_reference_llama_index_matches_engine_inventory():
-    """The index file the reference ships lists the base LLaMA-33B tensors; with the ``decoder.lm.`` prefix they are the
-    decoder part of the Emu state dict (plus rotary inv_freq buffers of old transformers, which the loader skips)."""
-    p = "/root/reference/Emu2/emu/conf/llama_config/pytorch_model.bin.index.json"
-    if not os.path.exists(p):
-        pytest.skip("reference checkout not present on this box")
+def test_reference_llama_index_matches_engine_inventory(golden_dir):
+    """The index file the reference ships lists the base LLaMA-33B tensors (its tensor names frozen in
+    tests/golden/llama_config_ref.json by oracle/make_golden_llama_config.py); with the ``decoder.lm.`` prefix they are the
+    decoder part of the Emu state dict (plus rotary inv_freq buffers of old transformers, which the loader skips and the
+    fixture leaves out)."""
     from emu_amd import synth
     from emu_amd.conf.emu_conf import LlamaCfg
-    wm = json.load(open(p))["weight_map"]
+    names = json.load(open(os.path.join(golden_dir, "llama_config_ref.json")))["index_tensor_names"]
     ours = {k[len("decoder.lm."):] for k in synth.llama_param_shapes(LlamaCfg(), 32000)}
-    theirs = {k for k in wm if not k.endswith("rotary_emb.inv_freq")}
+    theirs = {k for k in names if not k.endswith("rotary_emb.inv_freq")}
+    assert len(theirs) == len(names) > 0
     assert theirs == ours

@@ -564,13 +564,12 @@ def test_true_width_five_beam_step_against_oracle_and_single_rows():
 @pytest.mark.parametrize("S,pad", [(1, 0), (37, 0), (200, 13), (255, 0), (511, 0), (600, 21), (1100, 0)])
 def test_decode_attention_paths(heads, D, s_max, S, pad):
     """A cached decode step against the CPU oracle: both head dims, KV capacities with and without dead splits, left
-    padding, contexts that end inside / at the edge of a 128-key split and several splits long, batch 2."""
+    padding, contexts that end inside / at the edge of a 128-key split and several splits long, batch 2.  A prompt longer
+    than the KV capacity is refused."""
     from emu_amd import synth
     from emu_amd.conf.emu_conf import LlamaCfg
     from emu_amd.llama import EmuHipContext, LlamaEngine
     from oracle import emu2_ref as R
-    if S + 1 > s_max:
-        pytest.skip("context does not fit")
     l = LlamaCfg(hidden_size=heads * D, intermediate_size=256, num_attention_heads=heads, num_hidden_layers=2)
     vocab = 64
     W = synth.synth_state_dict(synth.llama_param_shapes(l, vocab), seed=heads + D)
@@ -583,6 +582,12 @@ def test_decode_attention_paths(heads, D, s_max, S, pad):
     mask = torch.ones(2, S, dtype=torch.long)
     if pad:
         mask[1, :pad] = 0                                                # left padding on row 1
+    if S + 1 > s_max:
+        # the prompt does not fit the cache (no case here has S == s_max): refused on the host, before any launch
+        assert S > s_max
+        with pytest.raises(ValueError, match="exceeds KV capacity"):
+            eng.prefill(x[:, :S].contiguous().cuda(), mask, s_max=s_max)
+        return
     _, kstart, pos = eng.prefill(x[:, :S].contiguous().cuda(), mask, s_max=s_max)
     cache = R.KVCache(2)
     pos_ref = (mask.cumsum(-1) - 1).masked_fill(mask == 0, 1)

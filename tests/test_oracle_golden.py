@@ -148,22 +148,20 @@ def test_generate_image(golden_dir, cached):
 
 
 def test_live_reference_bf16_matches_oracle_bf16(golden_dir):
-    """When the reference is importable (build container only) run it in bf16 on CPU and check the
-    oracle's bf16 mode reproduces its rounding points on lm.model (tolerance = 1 bf16 ulp-ish)."""
+    """The reference run in bf16 on CPU (its last hidden state frozen in tests/golden/llama_tiny_ref_bf16.npz by
+    oracle/make_golden_ref_bf16.py; re-run live where the reference is importable, build container only): the oracle's bf16 mode
+    reproduces its rounding points on lm.model (tolerance = 1 bf16 ulp-ish)."""
     from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip("reference not present on this machine")
     z = tiny.load(golden_dir, "llama_tiny.npz")
+    zr = tiny.load(golden_dir, "llama_tiny_ref_bf16.npz")
+    np.testing.assert_array_equal(zr["mask"], z["mask"])
+    ref = _t(zr["hidden_bf16"])
+    if ref_import.available():
+        from oracle.make_golden_ref_bf16 import reference_bf16_hidden
+        torch.testing.assert_close(reference_bf16_hidden(z).float(), ref, rtol=0, atol=0)
     v, l, vocab, W = tiny.weights_from(z)
     cfg = tiny.oracle_cfg(v, l, vocab)
-    d = ref_import.tiny_llama_dir(l.hidden_size, l.intermediate_size, l.num_attention_heads, l.num_hidden_layers)
-    vk = dict(image_size=v.image_size, patch_size=v.patch_size, width=v.width, layers=v.layers,
-              head_width=v.head_width, mlp_ratio=v.mlp_ratio, n_query=v.n_query, v_query=v.v_query)
-    m = ref_import.build_reference(vk, d, True, W).to(torch.bfloat16)
     embeds, mask = _t(z["embeds"]).to(torch.bfloat16), _t(z["mask"])
-    with torch.no_grad():
-        ref = m.decoder.lm.model(inputs_embeds=embeds, attention_mask=mask, output_hidden_states=True,
-                                 return_dict=True).hidden_states[-1]
     h = R.llama_model(embeds, mask, R.cast_weights(W, torch.bfloat16), cfg.llama)
     valid = mask.bool()
     torch.testing.assert_close(h[valid].float(), ref[valid].float(), rtol=2e-2, atol=2e-2)

@@ -1,11 +1,15 @@
-"""Worker of tests/test_gpu_tp_multiproc.py::test_engine_tp8_true_width_shards: EIGHT rank processes on one GPU (gloo rendezvous,
-every all-reduce through the peer-to-peer kernels) run a 2-layer decoder at the TRUE LLaMA-33B width -- 52 heads padded to 56,
-seven per rank, ffn 17920 / 8 = 2240, the wave-form o_proj / down_proj of the shards -- and must generate the greedy ids of the
-unsharded engine on the same weights wherever the unsharded run's top-2 logit margin is clear (lm_head x 8; steps behind the first
-unclear margin are not compared).  The launches, and mode 3 of emu_llama_set_decode_fused (the all-reduce in the tail of the o_proj /
-down_proj launches: only that one workgroup waits, for its peers); the fused layers of modes 1 / 2 wait inside a launch, and
-rank processes that SHARE a device can starve each other's producer workgroups of CU slots (a 20 s time-out and garbage, observed
-with eight ranks here) -- that path needs the device to itself and is covered per shard in tests/test_gpu_decode_fused.py.
+"""Worker of the true-width tensor-parallel tests in tests/test_gpu_tp_multiproc.py: WORLD_SIZE rank processes (gloo rendezvous,
+every all-reduce through the peer-to-peer kernels) run a 2-layer decoder at the TRUE LLaMA-33B width and must generate the greedy
+ids of the unsharded engine on the same weights wherever the unsharded run's top-2 logit margin is clear (lm_head x 8; steps
+behind the first unclear margin are not compared), eager and replayed from a hipGraph.
+
+Where the ranks run: EMU_TP_SHARED_GPU=1 puts every rank on cuda:0 (test_engine_tp4_true_width_shards_sharing_one_gpu: four
+ranks, 13-head shards, ffn 17920 / 4 = 4480); without it rank r uses cuda:LOCAL_RANK (test_engine_tp8_true_width_shards on an
+8-GPU node: 52 heads padded to 56, seven per rank, ffn 2240).  Both cover the wave-form o_proj / down_proj of the shards, the
+stand-alone all-reduce launches, and mode 3 of emu_llama_set_decode_fused (the all-reduce in the tail of the o_proj / down_proj
+launches: only that one workgroup waits, for its peers).  The fused layers of modes 1 / 2 wait inside a launch, and rank
+processes that SHARE a device can starve each other's producer workgroups of CU slots (a 20 s time-out and garbage, observed
+with eight ranks on one device) -- that path needs the device to itself and is covered per shard in tests/test_gpu_decode_fused.py.
 Exit code 0 = pass."""
 import os
 import sys
@@ -21,8 +25,9 @@ S, NEW, V, MARGIN = 96, 12, 2048, 0.5
 
 def main():
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda", 0)
+    local = 0 if os.environ.get("EMU_TP_SHARED_GPU") == "1" else int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from emu_amd import ops, synth
     from emu_amd.conf.emu_conf import LlamaCfg
