@@ -11,7 +11,7 @@
 // a contiguous range of tiles (weight tile reuse in its L2).  Chunks beyond K (K % 64 != 0) and implicit-GEMM conv taps
 // outside the image read a 16-byte zero buffer.
 //
-// Tile configurations (launch_v2 picks per problem): 256x256 ping-pong (gemm256.hip) for the MFMA-bound shapes,
+// Tile configurations (plan_gemm picks per problem): 256x256 ping-pong (gemm256.hip) for the MFMA-bound shapes,
 // 256(n) x 128(m), 128 x 128 (2 workgroups per CU), 128(n) x 64(m) with two k-groups of waves for few-tile problems;
 // split-K (fp32 slices + a reduce launch) when a problem has fewer tiles than the chip has CUs.
 //
@@ -656,77 +656,100 @@ long g_trace_sel = -1, g_trace_count = 0; // emu_gemm_trace_select: only the sel
 int g_force_cfg = 0;                     // emu_gemm_force_config: tests / benches pin one tile configuration
 int g_tune = 0;                          // emu_gemm_tune: A/B switches of single dispatch decisions (tools/unet_ab.py)
 
-// full_tiles whole-K workgroups followed by (tiles - full_tiles) * ksplit slice workgroups, one launch (+ the reduce)
-template <int EPI, bool CONV, class T, bool F8 = false>
-void launch_cfg(const GemmArgs& a, hipStream_t s, int full_tiles = -1, int ksplit = 1) {
-    const int tiles = ((a.M + T::BMv - 1) / T::BMv) * ((a.N + T::BNv - 1) / T::BNv);
-    GemmArgs b = a;
-    b.full_tiles = full_tiles < 0 ? tiles : full_tiles;
-    b.ksplit = ksplit;
-    b.trace = emu_gemm_trace_get();
-    b.stage = stage_ok(b) && !(g_tune & 8);
-    b.stage_vt = b.stage && stage_vt_ok(b, T::BMv, T::BNv) && !(g_tune & (1 << 14));
-    // XCD-aware 2-D tile blocks (unsplit launches whose tile count splits evenly over the 8 XCDs): block b runs on XCD b % 8 and
-    // xcd_order hands every XCD a run of tiles / 8 logical indices; a run of the column-major order covers (nearly) all rows of A
-    // when tiles_m is large (2048 x 1280 on 128 x 64 tiles: 32 x 10 tiles, 40 per XCD = all 32 row tiles x 2 weight tiles = 5.2 +
-    // 0.65 MB per L2 per GEMM, measured 50 MB fetched for 13.7 MB of operands); as an 8 x 5 block it is 1.3 + 1.6 MB
-    if (b.full_tiles == tiles && tiles % 8 == 0 && !(g_tune & 16)) {
-        const int tm = (a.M + T::BMv - 1) / T::BMv, tn = tiles / tm, per = tiles / 8;
-        const int cur_cols = (per + tm - 1) / tm + ((per % tm) ? 1 : 0);
-        long best = (long)(per < tm ? per : tm) * T::BMv + (long)(cur_cols < tn ? cur_cols : tn) * T::BNv;
-        for (int sm = 1; sm <= tm; ++sm) {
-            if (tm % sm || per % sm || tn % (per / sm)) continue;
-            const long cost = (long)sm * T::BMv + (long)(per / sm) * T::BNv;
-            if (cost < best) { best = cost; b.sup_m = sm; b.sup_n = per / sm; }
-        }
-    }
-    const int tail = tiles - b.full_tiles;
-    const int fx = gemm_fx(b);
-    if constexpr (F8) {                                 // launch_gemm_fp8: V^T / cross-attention epilogues only (EPI_NONE, unsliced)
-        if constexpr (EPI == EPI_NONE) {
-            if (fx == FX_VT && tail == 0) {
-                hipLaunchKernelGGL((gemm2_kernel<EPI, false, T, FX_VT, true>), dim3(b.full_tiles), dim3(T::THREADS), 0, s, b);
-                return;
-            }
-            if constexpr (T::MF == 1 && T::NF == 2 && T::KG == 2) {
-                if (fx == FX_CROSS && tail == 0) {
-                    hipLaunchKernelGGL((gemm2_kernel<EPI, false, T, FX_CROSS, true>), dim3(b.full_tiles), dim3(T::THREADS), 0, s, b);
-                    return;
-                }
-            }
-        }
-        hipLaunchKernelGGL((gemm2_kernel<EPI, false, T, 0, true>), dim3(b.full_tiles + tail * ksplit), dim3(T::THREADS), 0, s, b);
-        if (tail > 0)
-            hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T::BMv, T::BNv>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
-        return;
-    }
-    if (fx) {                                           // launch_gemm has checked gemm_fx_ok(epi, fx)
-        if constexpr (!CONV) {
-            gemm_fx_dispatch<EPI>(fx, [&](auto m) {
-                constexpr int FXM = decltype(m)::value;
-                hipLaunchKernelGGL((gemm2_kernel<EPI, CONV, T, FXM>), dim3(b.full_tiles + tail * ksplit), dim3(T::THREADS), 0, s, b);
-                if (tail > 0)
-                    hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T::BMv, T::BNv, FXM>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
-            });
-        }
-        return;
-    }
-    hipLaunchKernelGGL((gemm2_kernel<EPI, CONV, T>), dim3(b.full_tiles + tail * ksplit), dim3(T::THREADS), 0, s, b);
-    if (tail > 0 && b.slab_rows) launch_rows_reduce_norm(b, s);        // launch_v2: every tile sliced, slices row-major
-    else if (tail > 0)
-        hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T::BMv, T::BNv>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
-}
+// ---- planning (host arithmetic only: no global, no HIP call) ----
 
+inline bool glu_epi(int epi) { return epi == EPI_SWIGLU || epi == EPI_GEGLU; }
 inline int tiles_of(const GemmArgs& a, int bn, int bm) { return ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); }
 // k tiles (128 bytes per operand row) of a problem: 64 bf16 or 128 fp8 elements each
 inline int ktiles_of(const GemmArgs& a) { return a.a_scale ? a.K / 128 : a.K / BK; }
 
+// the arguments launch_gemm / launch_gemm_fp8 accept: 0 or -22
+int check_args(const GemmArgs& a) {
+    const int fx = gemm_fx(a);
+    const bool conv = a.conv.mode != CONV_NONE;
+    if (a.M < 1 || a.N < 1) return -22;
+    if (a.a_scale) {                                   // fp8: plain GEMM, of the fused epilogues V^T or the cross-attention
+        if (!a.w_scale || (a.K & 127) || (a.lda & 15) || (a.ldw & 15) || conv || a.epi == EPI_SILU || a.bias2 || a.norm_w ||
+            (fx != 0 && fx != FX_VT && fx != FX_CROSS)) return -22;
+    } else if ((a.K & 7) || (a.ldw & 7) || (!conv && (a.lda & 7))) {
+        return -22;
+    }
+    if (a.epi < EPI_NONE || a.epi > EPI_GEGLU || (conv && a.epi != EPI_NONE && a.epi != EPI_RESID)) return -22;
+    if (glu_epi(a.epi) && ((a.N & 1) || (a.ldc & 1))) return -22;
+    if (a.bias2 && a.rows_per_batch < 1) return -22;
+    // fused LayerNorm / V^T epilogues: whole quads only, statistics slots of LN_SLOT_COLS = 128 columns
+    if (!gemm_fx_ok(a.epi, fx)) return -22;
+    if (a.ln_c && (!a.ln_d || !a.ln_stats || a.ln_slots < 1 || a.ln_slots > LN_MAX_SLOTS || a.bias || (a.N & 3) || (a.ldc & 3) || conv)) return -22;
+    if (a.row_stats_out && ((a.N & 127) || (a.ldc & 3) || (a.epi != EPI_NONE && a.epi != EPI_RESID) ||
+                            (a.epi == EPI_RESID && (a.ldres & 3)) || conv)) return -22;
+    if (a.norm_w && (!a.norm_out || (a.norm_ld & 7) || a.norm_ld < a.N || a.bias2 || fx || conv ||
+                     (a.epi != EPI_NONE && a.epi != EPI_RESID) || (a.C && (a.ldc & 7)) || (a.epi == EPI_RESID && (a.ldres & 7)) ||
+                     (!a.C && !a.norm_b) || (a.norm_res && (!a.norm_b || (a.norm_ldres & 7)))))
+        return -22;
+    if (a.rope_cos) {                                  // RoPE + KV append + V^T epilogue of the LLaMA prefill's qkv projection
+        const int hd = a.rope_hl * 128;
+        if (!a.rope_sin || !a.rope_pos || !a.rope_slot || !a.rope_kc || !a.rope_vc || !a.vt_out || a.rope_hl < 1 || a.N != 3 * hd ||
+            (hd & 255) || a.vt_col0 != 2 * hd || a.vt_s != a.M || a.rope_smax < a.M || a.epi != EPI_NONE || a.bias || a.bias2 ||
+            a.ln_c || a.row_stats_out || a.cross_k || conv || (a.ldc & 7) || ((uintptr_t)a.C & 15) ||
+            (a.vt_spad & 7) || ((uintptr_t)a.vt_out & 15) || a.vt_spad < a.M)
+            return -22;
+    }
+    if (a.vt_out && (a.epi != EPI_NONE || conv || (a.vt_col0 & 63) || ((a.N - a.vt_col0) & 63) || a.vt_col0 < 0 ||
+                     a.vt_col0 >= a.N || a.vt_s < 1 || a.M % a.vt_s || a.vt_spad < a.vt_s || (a.ldc & 3))) return -22;
+    if (a.cross_k && (!a.cross_vt || a.epi != EPI_NONE || conv || a.bias || (a.N & 63) || (a.ldc & 3) || a.cross_n < 1 ||
+                      a.cross_n > 64 || a.cross_npad < 64 || a.cross_rows < 64 || (a.cross_rows & 63) || a.M % a.cross_rows ||
+                      (a.cross_ldk & 3) || (a.cross_npad & 3) || a.row_stats_out || a.vt_out)) return -22;
+    if (conv) {
+        const ConvGeom& g = a.conv;
+        if ((g.Cin & 63) || a.K != 9 * g.Cin || a.M % (g.Hout * g.Wout)) return -22;
+        if (g.mode == CONV_3X3 && (g.Hout != g.Hin || g.Wout != g.Win)) return -22;
+        if (g.mode == CONV_3X3_S2 && (g.Hout != (g.Hin + 1) / 2 || g.Wout != (g.Win + 1) / 2)) return -22;
+        if (g.mode == CONV_3X3_UP2 && (g.Hout != 2 * g.Hin || g.Wout != 2 * g.Win)) return -22;
+    }
+    return 0;
+}
+
+// the argument block of planned launch p of problem a: the conv gather's fast form where it applies (ConvGeom), the hybrid's
+// column range (pointer offsets only: W rows, bias, residual / output columns -- half of them for the interleaved GLU pairs), the
+// plan's fields
+GemmArgs plan_args(const GemmArgs& a, const GemmPlan& p) {
+    GemmArgs b = a;
+    const ConvGeom& g = a.conv;
+    if (g.mode != CONV_NONE) {
+        const int cpt = g.Cin / 64;
+        const long src_pixels = (long)(a.M / (g.Hout * g.Wout)) * g.Hin * g.Win;
+        if (cpt <= 64 && src_pixels < (g.mode == CONV_3X3_UP2 ? 1L << 21 : 1L << 23) && src_pixels * g.Cin * 2 < (1L << 31)) {
+            b.conv.cpt = cpt;
+            b.conv.cpt_magic = (65536 + cpt - 1) / cpt;
+        }
+    }
+    if (p.col0) {
+        b.W = a.W + (size_t)p.col0 * a.ldw;
+        if (a.bias) b.bias = a.bias + p.col0;
+        if (a.res) b.res = a.res + p.col0;
+        if (a.bias2) b.bias2 = a.bias2 + p.col0;
+        if (a.ln_c) { b.ln_c = a.ln_c + p.col0; b.ln_d = a.ln_d + p.col0; }
+        if (a.row_stats_out) b.row_stats_out = a.row_stats_out + (size_t)(p.col0 / LN_SLOT_COLS) * a.M * 2;   // slots of 128 columns
+        b.C = a.C + (glu_epi(a.epi) ? p.col0 / 2 : p.col0);
+    }
+    b.N = p.n;
+    b.full_tiles = p.full_tiles;
+    b.ksplit = p.ksplit;
+    b.sup_m = p.sup_m;
+    b.sup_n = p.sup_n;
+    b.stage = p.stage;
+    b.stage_vt = p.stage_vt;
+    b.slab_rows = p.slab_rows;
+    b.slice_rr = p.slice_rr;
+    if (p.no_prefetch) { b.pf_ptr = nullptr; b.pf_bytes = 0; }
+    return b;
+}
+
 // K-slices for a problem of `tiles` tiles (fewer than the 256 CUs) so that every CU gets about one workgroup; 0 = do
 // not split.  Needs N % 4 == 0 and a non-GLU epilogue (slices are raw fp32 quads), >= min_k k tiles per slice, and a
 // scratch that holds tiles * ksplit fp32 tiles.
-template <int EPI>
 int pick_ksplit(const GemmArgs& a, int tiles, int tile_elems, int min_k) {
-    if (EPI == EPI_SWIGLU || EPI == EPI_GEGLU || (a.N & 3) || !a.partial) return 0;
+    if (glu_epi(a.epi) || (a.N & 3) || !a.partial) return 0;
     int ksplit = 256 / tiles;
     if (ksplit > 8) ksplit = 8;
     const int nk = ktiles_of(a);
@@ -783,8 +806,8 @@ inline PpPlan pick_pp(const GemmArgs& a) {
 // Whole rounds on the 256x256 tile + the remaining weight rows on the lock-step tiles.  A problem of r * 256 + f tiles with a
 // small f (the UNet's GEGLU: 8 x 40 = 320 tiles; S=1544 gate/up: 6 x 140 = 840) pays a whole extra round for the f tiles,
 // and K-slicing them costs fp32 slabs.  Instead the first n1 tile columns (tiles_m * n1 ~ r * 256: every CU exactly r
-// tiles) go to the ping-pong kernel and columns [n1 * 256, N) are a second, independent GEMM on the same A (pointer offsets
-// only: W rows, bias, residual / output columns -- half of them for the interleaved GLU pairs).  n1 = 0: not applicable.
+// tiles) go to the ping-pong kernel and columns [n1 * 256, N) are a second, independent GEMM on the same A (plan_args).
+// n1 = 0: not applicable.
 // The heuristic takes it for f <= 3/8 of a round when the cost model would not K-slice the tail (short K): measured
 // (profiles/r02_gemm_ab_v12_hybrid.log) UNet GEGLU 608 (256x128) / 701 (256x256, two rounds) -> 747 TFLOP/s, denoise step
 // 29.1 -> 28.3 ms (same-run A/B); with long K the sliced tail stays ahead (S=1544 gate/up 1124 vs 1066) and at f = 1/2 the plain rounds do.
@@ -801,13 +824,13 @@ inline int plan_hybrid(const GemmArgs& a, bool forced) {
 
 // The lock-step tile of a problem the 256x256 ping-pong tile does not take ('S' = K-sliced 256 x 128), bf16 and fp8 alike
 // (the rules count tiles and k tiles of 128 bytes per row).
-template <int EPI, bool CONV>
 int pick_lockstep(const GemmArgs& a) {
+    const bool conv = a.conv.mode != CONV_NONE;
     const bool k64 = a.a_scale ? (a.K & 127) == 0 : (a.K & 63) == 0;
     const int tc = tiles_of(a, 256, 128);
     // (>= 24 k tiles per slice: with fewer the reduce launch costs more than the slices save -- the ViT's proj at 16 per
     // slice ran 284 TFLOP/s sliced, 381 on the 128 x 64 tile; profiles/r03_gemm_ilv_ab.log)
-    if (k64 && tc < 256 && pick_ksplit<EPI>(a, tc, 256 * 128, 24)) return 'S';
+    if (k64 && tc < 256 && pick_ksplit(a, tc, 256 * 128, 24)) return 'S';
     // 128x128 tiles are L1/TA-bandwidth-bound (64 FLOP/B needs ~64 B/clk/CU), so the largest problems take the
     // 256(n) x 128(m) tile; mid-size GEMMs 128x128 with two workgroups per CU; few-tile / long-K problems (UNet 32x32
     // level, implicit-GEMM convs, skinny ViT fc2) take 128 x 64 tiles with two k-groups of waves (intra-workgroup
@@ -818,119 +841,229 @@ int pick_lockstep(const GemmArgs& a) {
     // tiles (2048 x 1280: 160 tiles, one workgroup per CU and a two-stage ring) the 128 x 128 tile wins by 15 % on weights
     // that sit in the cache and loses in the model, where every launch finds them in HBM (same-box kernel stats: 24.7 vs 22.3
     // us); not for ragged M (the ViT's 1025 rows: a ninth row of tiles for one row)
-    if (!CONV && tiles_of(a, 128, 128) >= 200 && tiles_of(a, 128, 128) < 400 &&
-             ((a.M + 127) / 128) * 128 <= a.M + a.M / 16 && !(g_tune & 32)) return 'B';
+    if (!conv && tiles_of(a, 128, 128) >= 200 && tiles_of(a, 128, 128) < 400 &&
+             ((a.M + 127) / 128) * 128 <= a.M + a.M / 16) return 'B';
     if (tc >= 1024) return 'C';
-    if ((EPI == EPI_GEGLU || EPI == EPI_SWIGLU) && tc >= 512) return 'C';   // in situ (UNet step): 256x128 29.4, 128x128 29.4, 256x256 29.8 ms
-    if (!CONV && tc >= 180 && tc < 400) return 'C';           // ~one 256x128 tile per CU: ViT qkv
-    if (!CONV && tiles_of(a, 128, 128) >= 400) return 'B';
+    if (glu_epi(a.epi) && tc >= 512) return 'C';   // in situ (UNet step): 256x128 29.4, 128x128 29.4, 256x256 29.8 ms
+    if (!conv && tc >= 180 && tc < 400) return 'C';           // ~one 256x128 tile per CU: ViT qkv
+    if (!conv && tiles_of(a, 128, 128) >= 400) return 'B';
     return 'K';
 }
 
-template <int EPI, bool CONV>
-int launch_v2(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    if (!a.partial) { a.partial = g_splitk_scratch; a.partial_floats = g_splitk_floats; }
-    a.slice_rr = (g_tune >> 1) & 1;
-    if (g_tune & (1 << 16)) { a.pf_ptr = nullptr; a.pf_bytes = 0; }      // A/B: no successor prefetch
-    if (a.cross_k) {                                   // the cross-attention epilogue lives on the 128 x 64 tile
-        if constexpr (EPI == EPI_NONE && !CONV) { launch_cfg<EPI, CONV, CfgK>(a, s); EMU_CHECK_LAUNCH(); return 0; }
-        return -22;
+// XCD-aware 2-D tile blocks (unsplit launches whose tile count splits evenly over the 8 XCDs): block b runs on XCD b % 8 and
+// xcd_order hands every XCD a run of tiles / 8 logical indices; a run of the column-major order covers (nearly) all rows of A
+// when tiles_m is large (2048 x 1280 on 128 x 64 tiles: 32 x 10 tiles, 40 per XCD = all 32 row tiles x 2 weight tiles = 5.2 +
+// 0.65 MB per L2 per GEMM, measured 50 MB fetched for 13.7 MB of operands); as an 8 x 5 block it is 1.3 + 1.6 MB.  The block of
+// tm x tn tiles of bm x bn elements that reads the fewest operand rows.
+void pick_tile_blocks(GemmPlan& p, int tm, int tn, int bm, int bn) {
+    const int tiles = tm * tn, per = tiles / 8;
+    if (p.full_tiles != tiles || tiles % 8) return;
+    const int cur_cols = (per + tm - 1) / tm + ((per % tm) ? 1 : 0);
+    long best = (long)(per < tm ? per : tm) * bm + (long)(cur_cols < tn ? cur_cols : tn) * bn;
+    for (int sm = 1; sm <= tm; ++sm) {
+        if (tm % sm || per % sm || tn % (per / sm)) continue;
+        const long cost = (long)sm * bm + (long)(per / sm) * bn;
+        if (cost < best) { best = cost; p.sup_m = sm; p.sup_n = per / sm; }
+    }
+}
+
+// The launch of `a` on `tile` with tiles [0, full) whole-K (full < 0: all of them) and the rest in ksplit K-slices: stage flags,
+// XCD tile blocks, the four-wave kernel and the reduce launch follow from those.
+GemmPlan plan_launch(const GemmArgs& a, int tile, int full, int ksplit, int tune) {
+    GemmPlan p{};
+    p.tile = tile;
+    p.n = a.N;
+    p.ksplit = ksplit;
+    p.slab_rows = a.slab_rows;
+    p.slice_rr = (tune >> 1) & 1;
+    p.no_prefetch = (tune >> 16) & 1;                   // A/B: no successor prefetch
+    const GemmArgs b = plan_args(a, p);
+    const bool conv = a.conv.mode != CONV_NONE;
+    const int bm = tile == 256 ? 256 : tile == 'K' ? 64 : 128, bn = tile == 'B' ? 128 : 256 / (tile == 'K' ? 2 : 1);
+    const int tn = (a.N + bn - 1) / bn, tiles = tile == 256 ? gemm256_tiles(b) : tiles_of(b, bn, bm), tm = tiles / tn;
+    p.full_tiles = full < 0 ? tiles : full;
+    p.stage = stage_ok(b) && !(tune & 8);
+    p.stage_vt = p.stage && stage_vt_ok(b, bm, bn);
+    const int tail = tiles - p.full_tiles, fx = gemm_fx(b);
+    if (tile == 256) {
+        if (!(tune & (1 << 23))) p.stage |= 2;          // four-wave tile: fp32 K-slices leave through LDS too (bit 23: A/B)
+        // the implicit-GEMM convs keep the column-major strips (one weight tile of K = 9 Cin per strip is what their L2 can hold)
+        if (!conv) pick_tile_blocks(p, tm, tn, bm, bn);
+        // The main launch: the four-wave tile on its LDS ring (gemm_w4.hip) for bf16 operands; gemm256.hip's eight-wave ping-pong
+        // tile for fp8 operands and, as the A/B twin, under emu_gemm_tune bit 21.  Where the four-wave tile is taken (same-run A/B,
+        // profiles/r06_gemm_w4_*.log): plain GEMMs whose tiles all lie inside N (they leave through LDS: bf16 results and fp32
+        // K-slices alike; a tile that reaches past N takes the direct path, whose scattered stores its one wave per SIMD issues at
+        // half the ping-pong tile's rate) with a light epilogue: nothing overlaps the dependent VALU chains of an erf on one wave
+        // per SIMD, and behind a GELU / GEGLU epilogue (ViT fc1, the UNet's GEGLU with its folded LayerNorm) the faster loop loses
+        // in the model (same-run: ViT encode 15.93 vs 15.39 ms, denoise step 26.64 vs 25.11 ms with those launches on it; LLaMA
+        // prefill S = 770 49.07 vs 51.35 ms).  K-slices shorter than 16 k tiles do not amortise the ring's prologue (UNet 32^2
+        // attn-out 172 vs 198 TFLOP/s), the implicit-GEMM convs' per-row bias loads cost it more (661 vs 739).
+        // emu_gemm_tune bit 22 takes it wherever it is instantiated (tests); elsewhere the ping-pong tile stands in.
+        const bool act = a.epi == EPI_GELU || a.epi == EPI_GEGLU;
+        p.w4 = gemm_w4_ok(a.a_scale != nullptr, fx) && !(tune & (1 << 21)) &&
+               ((tune & (1 << 22)) || (!conv && (a.N & 255) == 0 && !act && !(fx & FX_LN) && (tail == 0 || (a.K >> 6) / ksplit >= 16)));
+    } else {
+        pick_tile_blocks(p, tm, tn, bm, bn);
+    }
+    if (tail > 0) p.reduce = p.slab_rows ? GEMM_REDUCE_ROWS_NORM : tile == 256 ? GEMM_REDUCE_PP : GEMM_REDUCE_SPLITK;
+    return p;
+}
+
+// The launches of a checked problem: one, or the hybrid split's two (allow_split).  0, or -95: the fused form asked for is not
+// available at this shape (the caller runs the unfused sequence).
+int plan_launches(const GemmArgs& a, int force, int tune, bool allow_split, GemmPlan* plan, int& n) {
+    const bool f8 = a.a_scale != nullptr;
+    const int fx = gemm_fx(a);
+    if (fx & FX_CROSS) {                                // the cross-attention epilogue lives on the 128 x 64 tile
+        plan[n++] = plan_launch(a, 'K', -1, 1, tune);
+        return 0;
+    }
+    if (f8 && (fx & FX_VT)) {                           // fp8 V^T epilogue: the lock-step tiles, unsliced
+        int c = force ? force : pick_lockstep(a);
+        if (c == 'C' && !force) c = 'B';
+        plan[n++] = plan_launch(a, c == 'K' || c == 'C' ? c : 'B', -1, 1, tune);
+        return 0;
     }
     if (a.rope_cos) {
         // only the 256x256 tile has this epilogue, and only whole-K tiles: -95 tells the caller to run the unfused sequence
         // (qkv GEMM, rope_kv, transpose_v) instead -- thin prompts, K-sliced tail rounds
-        if constexpr (EPI == EPI_NONE && !CONV) {
-            const PpPlan pp = pick_pp(a);
-            if (!gemm256_ok(a) || !pp.use || pp.ksplit > 1) return -95;
-            return launch_gemm256(a, s, -1, 1);
-        }
-        return -22;
+        const PpPlan pp = pick_pp(a);
+        if (!gemm256_ok(a) || !pp.use || pp.ksplit > 1) return -95;
+        plan[n++] = plan_launch(a, 256, -1, 1, tune);
+        return 0;
     }
     if (a.norm_w) {
         // slice sum + the following RMSNorm in one row-wise launch: only where the 256x256 tile K-slices EVERY tile of the problem
         // (fewer tiles than CUs: S = 770 o_proj / down_proj) and the row-major slices fit the scratch; -95 = run GEMM and rmsnorm apart
-        if constexpr ((EPI == EPI_NONE || EPI == EPI_RESID) && !CONV) {
-            if ((a.N & 7) || a.N > 16384) return -95;
-            const PpPlan pp = pick_pp(a);
-            if (gemm256_ok(a) && pp.use) {
-                if (pp.ksplit < 2 || pp.full_tiles != 0 || (size_t)pp.ksplit * a.M * a.N > a.partial_floats) return -95;
-                a.slab_rows = 1;
-                return launch_gemm256(a, s, 0, pp.ksplit);
-            }
-            // the K-sliced 256 x 128 lock-step tile (ViT fc2): all of its tiles are slices
-            if (pick_lockstep<EPI, CONV>(a) != 'S') return -95;
-            const int tc = tiles_of(a, 256, 128);
-            const int ksplit = pick_ksplit<EPI>(a, tc, 256 * 128, 24);
-            if (ksplit < 2 || (size_t)ksplit * a.M * a.N > a.partial_floats) return -95;
-            a.slab_rows = 1;
-            launch_cfg<EPI, CONV, CfgC>(a, s, 0, ksplit);
-            EMU_CHECK_LAUNCH();
+        if ((a.N & 7) || a.N > 16384) return -95;
+        GemmArgs b = a;
+        b.slab_rows = 1;
+        const PpPlan pp = pick_pp(a);
+        if (gemm256_ok(a) && pp.use) {
+            if (pp.ksplit < 2 || pp.full_tiles != 0 || (size_t)pp.ksplit * a.M * a.N > a.partial_floats) return -95;
+            plan[n++] = plan_launch(b, 256, 0, pp.ksplit, tune);
             return 0;
         }
-        return -22;
+        // the K-sliced 256 x 128 lock-step tile (ViT fc2): all of its tiles are slices
+        if (pick_lockstep(a) != 'S') return -95;
+        const int ksplit = pick_ksplit(a, tiles_of(a, 256, 128), 256 * 128, 24);
+        if (ksplit < 2 || (size_t)ksplit * a.M * a.N > a.partial_floats) return -95;
+        plan[n++] = plan_launch(b, 'C', 0, ksplit, tune);
+        return 0;
     }
-    int cfg = g_force_cfg;
-    const bool k64 = (a.K & 63) == 0;
-    if (cfg == 'S' && !k64) cfg = 0;
+    int cfg = force;
+    if (cfg == 'S' && (a.K & 63)) cfg = 0;
     if ((cfg == 'P' || cfg == 'Q') && !gemm256_ok(a)) cfg = 0;
     if (!cfg || cfg == 'H') {
-        int n1 = CONV ? 0 : plan_hybrid(a, cfg == 'H');
-        // A/B switch 1: a GLU problem the hybrid would split in two launches runs as ONE launch of 128 x 128 tiles instead
-        constexpr bool GLU_EPI = EPI == EPI_SWIGLU || EPI == EPI_GEGLU;
-        if (GLU_EPI && n1 > 0 && !cfg && (g_tune & 1) && tiles_of(a, 128, 128) >= 1024) { n1 = 0; cfg = 'B'; }
+        const int n1 = f8 || !allow_split ? 0 : plan_hybrid(a, cfg == 'H');
         if (n1 > 0) {
-            constexpr bool GLU = EPI == EPI_SWIGLU || EPI == EPI_GEGLU;
-            GemmArgs head = a, rest = a;
-            head.N = n1 * 256;
-            rest.N = a.N - head.N;
-            rest.W = a.W + (size_t)head.N * a.ldw;
-            if (a.bias) rest.bias = a.bias + head.N;
-            if (a.res) rest.res = a.res + head.N;
-            if (a.bias2) rest.bias2 = a.bias2 + head.N;
-            if (a.ln_c) { rest.ln_c = a.ln_c + head.N; rest.ln_d = a.ln_d + head.N; }
-            if (a.row_stats_out) rest.row_stats_out = a.row_stats_out + (size_t)(head.N / LN_SLOT_COLS) * a.M * 2;   // slots of 128 columns
-            rest.C = a.C + (GLU ? head.N / 2 : head.N);
-            rest.pf_ptr = nullptr; rest.pf_bytes = 0;              // the head launch prefetches for the successor
-            int st = launch_gemm256(head, s, -1, 1);
-            if (st != 0) return st;
-            const int keep = g_force_cfg;
-            g_force_cfg = 0;                                       // the remainder takes whatever the heuristic says
-            st = launch_v2<EPI, CONV>(rest, s);
-            g_force_cfg = keep;
+            GemmPlan head{}, rest{};
+            head.n = n1 * 256;
+            plan[n++] = plan_launch(plan_args(a, head), 256, -1, 1, tune);
+            // the remainder: whatever the heuristic says, without a second split (what remains is under a round of tiles below
+            // ~41 000 rows); the head launch prefetches for the successor
+            rest.col0 = head.n;
+            rest.n = a.N - head.n;
+            const int k = n;
+            const int st = plan_launches(plan_args(a, rest), 0, tune, false, plan, n);
+            plan[k].col0 = rest.col0;
+            plan[k].no_prefetch = 1;
             return st;
         }
-        if (cfg == 'H') cfg = 0;
+        cfg = 0;
     }
     if (!cfg) {
         const PpPlan pp = pick_pp(a);
-        if (pp.use) return pp.ksplit > 1 ? launch_gemm256(a, s, pp.full_tiles, pp.ksplit) : launch_gemm256(a, s, -1, 1);
+        if (pp.use) {
+            plan[n++] = plan_launch(a, 256, pp.ksplit > 1 ? pp.full_tiles : -1, pp.ksplit, tune);
+            return 0;
+        }
         // The 256x128 tile moves the fewest bytes per FLOP through L2 of the lock-step tiles (the binding resource of
         // these kernels) but runs one workgroup per CU: a 2048 x 1280 output is only 80 tiles (0.31 round).  Problems
         // with fewer tiles than CUs are cut into K-slices so they fill the CUs once: fp32 slice tiles land in a
         // scratch, a second launch sums them in order and applies the epilogue.  (Slicing only the tail round of a
         // multi-round problem measured flat: a thin last round simply runs faster.)
-        cfg = pick_lockstep<EPI, CONV>(a);
+        cfg = pick_lockstep(a);
+        // fp8: with half the LDS-DMA bytes per FLOP the 128 x 128 tile (two workgroups per CU) beats the 256 x 128 tile wherever
+        // the bf16 rules pick the latter (profiles/r04_fp8_gemm_time_*.log: UNet qkv 17.7 vs 18.6 us, GEGLU 50.8 vs 53.2, ViT qkv
+        // 17.5 vs 20.1)
+        if (f8 && cfg == 'C') cfg = 'B';
     }
     switch (cfg) {
-        case 'Q': return launch_gemm256(a, s, -1, 1);  // 256x256 ping-pong, never K-sliced (A/B)
-        case 'P': {                                   // 256x256 ping-pong with the planned K-slices, whatever the shape
+        case 'Q':                                       // 256x256, never K-sliced (A/B)
+            plan[n++] = plan_launch(a, 256, -1, 1, tune);
+            break;
+        case 'P': {                                     // 256x256 with the planned K-slices, whatever the shape
             const PpPlan pp = plan_pp(a);
-            return pp.ksplit > 1 ? launch_gemm256(a, s, pp.full_tiles, pp.ksplit) : launch_gemm256(a, s, -1, 1);
-        }
-        case 'S': {
-            const int tc = tiles_of(a, 256, 128);
-            const int ksplit = tc < 256 ? pick_ksplit<EPI>(a, tc, 256 * 128, g_force_cfg ? 8 : 24) : 0;
-            if (ksplit) launch_cfg<EPI, CONV, CfgC>(a, s, 0, ksplit);
-            else launch_cfg<EPI, CONV, CfgC>(a, s);
+            plan[n++] = plan_launch(a, 256, pp.ksplit > 1 ? pp.full_tiles : -1, pp.ksplit, tune);
             break;
         }
-        case 'C': launch_cfg<EPI, CONV, CfgC>(a, s); break;
-        case 'K': launch_cfg<EPI, CONV, CfgK>(a, s); break;
-        default:  launch_cfg<EPI, CONV, CfgB>(a, s); break;
+        case 'S': {                                     // forced: slices down to 8 k tiles (fp8: 4 of 128 elements)
+            const int tc = tiles_of(a, 256, 128);
+            const int ksplit = tc < 256 ? pick_ksplit(a, tc, 256 * 128, force ? (f8 ? 4 : 8) : 24) : 0;
+            plan[n++] = ksplit ? plan_launch(a, 'C', 0, ksplit, tune) : plan_launch(a, 'C', -1, 1, tune);
+            break;
+        }
+        case 'C': case 'K':
+            plan[n++] = plan_launch(a, cfg, -1, 1, tune);
+            break;
+        default:
+            plan[n++] = plan_launch(a, 'B', -1, 1, tune);
     }
-    EMU_CHECK_LAUNCH();
     return 0;
+}
+
+// The plan of a launch_gemm / launch_gemm_fp8 call: its status (0, -22, -95) and n (<= 2) launches.  force_cfg / tune: the values
+// of emu_gemm_force_config / emu_gemm_tune; the split-K scratch is the one in a.partial.
+int plan_gemm(const GemmArgs& a, int force_cfg, int tune, GemmPlan (&plan)[2], int& n) {
+    n = 0;
+    const int st = check_args(a);
+    if (st != 0) return st;
+    GemmPlan whole{};
+    whole.n = a.N;
+    return plan_launches(plan_args(a, whole), force_cfg, tune, true, plan, n);
+}
+
+// ---- launching ----
+
+template <class T>
+bool launch_lockstep(const GemmArgs& b, const GemmPlan& p, hipStream_t s) {
+    const int tail = tiles_of(b, T::BNv, T::BMv) - b.full_tiles;
+    return gemm_form_dispatch(b, [&](auto e, auto c, auto q, auto m) {
+        constexpr int EPI = decltype(e)::value, FX = decltype(m)::value;
+        constexpr bool CONV = decltype(c)::value, F8 = decltype(q)::value;
+        // (no RoPE epilogue here; the fp8 cross-attention form exists on the 128 x 64 tile only)
+        if constexpr ((FX & FX_ROPE) != 0 || (F8 && FX == FX_CROSS && !(T::MF == 1 && T::NF == 2 && T::KG == 2))) {
+            return false;
+        } else {
+            hipLaunchKernelGGL((gemm2_kernel<EPI, CONV, T, FX, F8>), dim3(b.full_tiles + tail * b.ksplit), dim3(T::THREADS), 0, s, b);
+            if (p.reduce == GEMM_REDUCE_ROWS_NORM) launch_rows_reduce_norm(b, s);      // every tile sliced, slices row-major
+            else if (p.reduce == GEMM_REDUCE_SPLITK)
+                hipLaunchKernelGGL((splitk_reduce_kernel<EPI, T::BMv, T::BNv, FX>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
+            return true;
+        }
+    });
+}
+
+int launch_planned(const GemmArgs& a0, hipStream_t s) {
+    GemmArgs a = a0;
+    if (!a.partial) { a.partial = g_splitk_scratch; a.partial_floats = g_splitk_floats; }
+    GemmPlan plan[2];
+    int n = 0;
+    int st = plan_gemm(a, g_force_cfg, g_tune, plan, n);
+    for (int i = 0; i < n && st == 0; ++i) {
+        GemmArgs b = plan_args(a, plan[i]);
+        b.trace = emu_gemm_trace_get();
+        if (plan[i].tile == 256) {
+            st = launch_gemm256(b, plan[i], s);
+        } else {
+            const bool ok = plan[i].tile == 'C' ? launch_lockstep<CfgC>(b, plan[i], s)
+                          : plan[i].tile == 'K' ? launch_lockstep<CfgK>(b, plan[i], s) : launch_lockstep<CfgB>(b, plan[i], s);
+            st = ok ? 0 : -22;
+            if (ok) EMU_CHECK_LAUNCH();
+        }
+    }
+    return st;
 }
 
 }  // namespace
@@ -948,150 +1081,60 @@ unsigned long long* emu_gemm_trace_get() {
 }
 int emu_gemm_tune_get() { return g_tune; }
 
-// fp8 x fp8 -> bf16: the 256x256 ping-pong tile where the bf16 rules would take it, else the lock-step tiles' fp8 form
-template <int EPI>
-static int launch_fp8_v2(const GemmArgs& a, hipStream_t s) {
-    if (a.cross_k) {                                   // the cross-attention epilogue lives on the 128 x 64 tile
-        if constexpr (EPI == EPI_NONE) { launch_cfg<EPI, false, CfgK, true>(a, s); EMU_CHECK_LAUNCH(); return 0; }
-        return -22;
-    }
-    if (a.vt_out) {                                    // V^T epilogue: the lock-step tiles, unsliced
-        if constexpr (EPI == EPI_NONE) {
-            int c = g_force_cfg ? g_force_cfg : pick_lockstep<EPI, false>(a);
-            if (c == 'C' && !g_force_cfg) c = 'B';
-            if (c == 'K') launch_cfg<EPI, false, CfgK, true>(a, s);
-            else if (c == 'C') launch_cfg<EPI, false, CfgC, true>(a, s);
-            else launch_cfg<EPI, false, CfgB, true>(a, s);
-            EMU_CHECK_LAUNCH();
-            return 0;
-        }
-        return -22;
-    }
-    int cfg = g_force_cfg;
-    if (cfg == 'H') cfg = 0;
-    if ((cfg == 'P' || cfg == 'Q') && !gemm256_ok(a)) cfg = 0;
-    if (!cfg) {
-        const PpPlan pp = pick_pp(a);
-        if (pp.use) return pp.ksplit > 1 ? launch_gemm256(a, s, pp.full_tiles, pp.ksplit) : launch_gemm256(a, s, -1, 1);
-        cfg = pick_lockstep<EPI, false>(a);
-        // with half the LDS-DMA bytes per FLOP the 128 x 128 tile (two workgroups per CU) beats the 256 x 128 tile wherever the
-        // bf16 rules pick the latter (profiles/r04_fp8_gemm_time_*.log: UNet qkv 17.7 vs 18.6 us, GEGLU 50.8 vs 53.2, ViT qkv 17.5 vs 20.1)
-        if (cfg == 'C') cfg = 'B';
-    }
-    switch (cfg) {
-        case 'Q': return launch_gemm256(a, s, -1, 1);
-        case 'P': {
-            const PpPlan pp = plan_pp(a);
-            return pp.ksplit > 1 ? launch_gemm256(a, s, pp.full_tiles, pp.ksplit) : launch_gemm256(a, s, -1, 1);
-        }
-        case 'S': {
-            const int tc = tiles_of(a, 256, 128);
-            const int ksplit = tc < 256 ? pick_ksplit<EPI>(a, tc, 256 * 128, g_force_cfg ? 4 : 24) : 0;
-            if (ksplit) launch_cfg<EPI, false, CfgC, true>(a, s, 0, ksplit);
-            else launch_cfg<EPI, false, CfgC, true>(a, s);
-            break;
-        }
-        case 'C': launch_cfg<EPI, false, CfgC, true>(a, s); break;
-        case 'K': launch_cfg<EPI, false, CfgK, true>(a, s); break;
-        default:  launch_cfg<EPI, false, CfgB, true>(a, s); break;
-    }
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
-
-static int launch_gemm_fp8_impl(const GemmArgs& a0, hipStream_t s) {
-    GemmArgs a = a0;
-    if (a.M < 1 || a.N < 1 || !a.a_scale || !a.w_scale || (a.K & 127) || (a.lda & 15) || (a.ldw & 15) || a.conv.mode != CONV_NONE) return -22;
-    if ((a.epi == EPI_SWIGLU || a.epi == EPI_GEGLU) && ((a.N & 1) || (a.ldc & 1))) return -22;
-    const int fx = gemm_fx(a);
-    if ((fx != 0 && fx != FX_VT && fx != FX_CROSS) || a.bias2) return -22;
-    if (a.vt_out && (a.epi != EPI_NONE || (a.vt_col0 & 63) || ((a.N - a.vt_col0) & 63) || a.vt_col0 < 0 || a.vt_col0 >= a.N || a.vt_s < 1 ||
-                     a.M % a.vt_s || a.vt_spad < a.vt_s || (a.ldc & 3))) return -22;
-    if (a.cross_k && (!a.cross_vt || a.epi != EPI_NONE || a.bias || (a.N & 63) || (a.ldc & 3) || a.cross_n < 1 || a.cross_n > 64 ||
-                      a.cross_npad < 64 || a.cross_rows < 64 || (a.cross_rows & 63) || a.M % a.cross_rows || (a.cross_ldk & 3) ||
-                      (a.cross_npad & 3))) return -22;
-    if (!a.partial) { a.partial = g_splitk_scratch; a.partial_floats = g_splitk_floats; }
-    a.slice_rr = (g_tune >> 1) & 1;
-    switch (a.epi) {
-        case EPI_NONE:   return launch_fp8_v2<EPI_NONE>(a, s);
-        case EPI_RESID:  return launch_fp8_v2<EPI_RESID>(a, s);
-        case EPI_SWIGLU: return launch_fp8_v2<EPI_SWIGLU>(a, s);
-        case EPI_GELU:   return launch_fp8_v2<EPI_GELU>(a, s);
-        case EPI_GEGLU:  return launch_fp8_v2<EPI_GEGLU>(a, s);
-        default: return -22;
-    }
-}
-int launch_gemm_fp8(const GemmArgs& a, hipStream_t s) {
-    if (!emu_prof_on()) return launch_gemm_fp8_impl(a, s);
+int launch_gemm(const GemmArgs& a, hipStream_t s) {
+    if (!emu_prof_on()) return launch_planned(a, s);
     emu_prof_begin(s);
-    const int st = launch_gemm_fp8_impl(a, s);
+    const int st = launch_planned(a, s);
+    if (st == 0) emu_prof_end(s, a.conv.mode != CONV_NONE ? "conv" : "gemm", a.M, a.N, a.K, a.epi | (gemm_fx(a) << 8), 2.0 * a.M * a.N * a.K);
+    else emu_prof_drop();                                  // (a -95 probe of a fused form, a refused shape: nothing was launched)
+    return st;
+}
+// fp8 x fp8 -> bf16: the 256x256 ping-pong tile where the bf16 rules would take it, else the lock-step tiles' fp8 form
+int launch_gemm_fp8(const GemmArgs& a, hipStream_t s) {
+    if (!a.a_scale) return -22;
+    if (!emu_prof_on()) return launch_planned(a, s);
+    emu_prof_begin(s);
+    const int st = launch_planned(a, s);
     if (st == 0) emu_prof_end(s, "gemm_fp8", a.M, a.N, a.K, a.epi, 2.0 * a.M * a.N * a.K);
     else emu_prof_drop();
     return st;
 }
 
-static int launch_gemm_impl(const GemmArgs& a, hipStream_t s);
-int launch_gemm(const GemmArgs& a, hipStream_t s) {
-    if (!emu_prof_on()) return launch_gemm_impl(a, s);
-    emu_prof_begin(s);
-    const int st = launch_gemm_impl(a, s);
-    if (st == 0) emu_prof_end(s, a.conv.mode != CONV_NONE ? "conv" : "gemm", a.M, a.N, a.K, a.epi | (gemm_fx(a) << 8), 2.0 * a.M * a.N * a.K);
-    else emu_prof_drop();                                  // (a -95 probe of a fused form, a refused shape: nothing was launched)
+// C-ABI test hook (include/emu_hip.h): the shape stands for an argument block on aligned, distinct buffers
+int emu_gemm_plan(const emu_gemm_shape* sh, int force_cfg, int tune, emu_gemm_plan_entry plan[2], int* entries) {
+    auto ptr = [](int i) { return reinterpret_cast<bf16_t*>((uintptr_t)i << 20); };    // addresses only, never dereferenced
+    GemmArgs a{};
+    const int rows = sh->rows ? sh->rows : sh->M;
+    a.A = ptr(1); a.W = ptr(2); a.C = ptr(3);
+    a.M = sh->M; a.N = sh->N; a.K = sh->K; a.epi = sh->epi;
+    a.lda = sh->conv_mode ? sh->Cin : sh->K; a.ldw = sh->K; a.ldc = glu_epi(sh->epi) ? sh->N / 2 : sh->N; a.ldres = sh->N;
+    if (sh->epi == EPI_RESID) a.res = ptr(4);
+    a.conv = ConvGeom{sh->conv_mode, sh->Hin, sh->Win, sh->Hout, sh->Wout, sh->Cin};
+    if (sh->scratch_floats) { a.partial = reinterpret_cast<float*>(ptr(5)); a.partial_floats = sh->scratch_floats; }
+    if (sh->fp8) { a.a_scale = reinterpret_cast<float*>(ptr(6)); a.w_scale = a.a_scale; }
+    if (sh->fx & FX_LN) { a.ln_c = a.ln_d = a.ln_stats = reinterpret_cast<float*>(ptr(7)); a.ln_slots = 1; }
+    if (sh->fx & FX_STATS) a.row_stats_out = reinterpret_cast<float*>(ptr(8));
+    if (sh->fx & (FX_VT | FX_ROPE)) {
+        a.vt_out = ptr(9);
+        a.vt_col0 = (sh->fx & FX_ROPE) ? 2 * sh->N / 3 : sh->vt_col0;
+        a.vt_s = rows;
+        a.vt_spad = (rows + 63) & ~63;
+    }
+    if (sh->fx & FX_CROSS) {
+        a.cross_k = a.cross_vt = ptr(10);
+        a.cross_ldk = sh->N; a.cross_n = 64; a.cross_npad = 64; a.cross_rows = rows;
+    }
+    if (sh->fx & FX_ROPE) {
+        a.rope_cos = a.rope_sin = a.rope_kc = a.rope_vc = ptr(11);
+        a.rope_pos = a.rope_slot = reinterpret_cast<const int32_t*>(ptr(12));
+        a.rope_hl = sh->N / 384; a.rope_smax = sh->M;
+    }
+    if (sh->fx & 32) { a.norm_w = a.norm_out = ptr(13); a.norm_ld = sh->N; }      // RMSNorm of C in the reduce
+    a.pf_ptr = ptr(14); a.pf_bytes = 1;
+    GemmPlan p[2];
+    int n = 0;
+    const int st = plan_gemm(a, force_cfg & 255, tune, p, n);
+    for (int i = 0; i < n; ++i) plan[i] = p[i];
+    *entries = n;
     return st;
-}
-static int launch_gemm_impl(const GemmArgs& a, hipStream_t s) {
-    if (a.M < 1 || a.N < 1 || (a.K & 7) || (a.ldw & 7)) return -22;
-    if ((a.epi == EPI_SWIGLU || a.epi == EPI_GEGLU) && ((a.N & 1) || (a.ldc & 1))) return -22;
-    if (a.bias2 && a.rows_per_batch < 1) return -22;
-    // fused LayerNorm / V^T epilogues: whole quads only, statistics slots of LN_SLOT_COLS = 128 columns
-    if (!gemm_fx_ok(a.epi, gemm_fx(a))) return -22;
-    if (a.ln_c && (!a.ln_d || !a.ln_stats || a.ln_slots < 1 || a.ln_slots > LN_MAX_SLOTS || a.bias || (a.N & 3) || (a.ldc & 3) || a.conv.mode != CONV_NONE)) return -22;
-    if (a.row_stats_out && ((a.N & 127) || (a.ldc & 3) || (a.epi != EPI_NONE && a.epi != EPI_RESID) ||
-                            (a.epi == EPI_RESID && (a.ldres & 3)))) return -22;
-    if (a.norm_w && (!a.norm_out || (a.norm_ld & 7) || a.norm_ld < a.N || a.bias2 || gemm_fx(a) || a.conv.mode != CONV_NONE ||
-                     (a.epi != EPI_NONE && a.epi != EPI_RESID) || (a.C && (a.ldc & 7)) || (a.epi == EPI_RESID && (a.ldres & 7)) ||
-                     (!a.C && !a.norm_b) || (a.norm_res && (!a.norm_b || (a.norm_ldres & 7)))))
-        return -22;
-    if (a.rope_cos) {                                  // RoPE + KV append + V^T epilogue of the LLaMA prefill's qkv projection
-        const int hd = a.rope_hl * 128;
-        if (!a.rope_sin || !a.rope_pos || !a.rope_slot || !a.rope_kc || !a.rope_vc || !a.vt_out || a.rope_hl < 1 || a.N != 3 * hd ||
-            (hd & 255) || a.vt_col0 != 2 * hd || a.vt_s != a.M || a.rope_smax < a.M || a.epi != EPI_NONE || a.bias || a.bias2 ||
-            a.ln_c || a.row_stats_out || a.cross_k || a.conv.mode != CONV_NONE || (a.ldc & 7) || ((uintptr_t)a.C & 15) ||
-            (a.vt_spad & 7) || ((uintptr_t)a.vt_out & 15) || a.vt_spad < a.M)
-            return -22;
-    }
-    if (a.vt_out && (a.epi != EPI_NONE || a.conv.mode != CONV_NONE || (a.vt_col0 & 63) || ((a.N - a.vt_col0) & 63) || a.vt_col0 < 0 ||
-                     a.vt_col0 >= a.N || a.vt_s < 1 || a.M % a.vt_s || a.vt_spad < a.vt_s || (a.ldc & 3))) return -22;
-    if (a.cross_k && (!a.cross_vt || a.epi != EPI_NONE || a.conv.mode != CONV_NONE || a.bias || (a.N & 63) || (a.ldc & 3) || a.cross_n < 1 ||
-                      a.cross_n > 64 || a.cross_npad < 64 || a.cross_rows < 64 || (a.cross_rows & 63) || a.M % a.cross_rows ||
-                      (a.cross_ldk & 3) || (a.cross_npad & 3) || a.row_stats_out || a.vt_out)) return -22;
-    if (a.conv.mode != CONV_NONE) {
-        const ConvGeom& g = a.conv;
-        if ((g.Cin & 63) || a.K != 9 * g.Cin || a.M % (g.Hout * g.Wout)) return -22;
-        if (g.mode == CONV_3X3 && (g.Hout != g.Hin || g.Wout != g.Win)) return -22;
-        if (g.mode == CONV_3X3_S2 && (g.Hout != (g.Hin + 1) / 2 || g.Wout != (g.Win + 1) / 2)) return -22;
-        if (g.mode == CONV_3X3_UP2 && (g.Hout != 2 * g.Hin || g.Wout != 2 * g.Win)) return -22;
-        GemmArgs b = a;
-        const int cpt = g.Cin / 64;
-        const long src_pixels = (long)(a.M / (g.Hout * g.Wout)) * g.Hin * g.Win;
-        if (cpt <= 64 && src_pixels < (g.mode == CONV_3X3_UP2 ? 1L << 21 : 1L << 23) && src_pixels * g.Cin * 2 < (1L << 31)) {
-            b.conv.cpt = cpt;
-            b.conv.cpt_magic = (65536 + cpt - 1) / cpt;
-        }
-        switch (a.epi) {
-            case EPI_NONE:  return launch_v2<EPI_NONE, true>(b, s);
-            case EPI_RESID: return launch_v2<EPI_RESID, true>(b, s);
-            default: return -22;
-        }
-    }
-    if (a.lda & 7) return -22;
-    switch (a.epi) {
-        case EPI_NONE:   return launch_v2<EPI_NONE, false>(a, s);
-        case EPI_RESID:  return launch_v2<EPI_RESID, false>(a, s);
-        case EPI_SWIGLU: return launch_v2<EPI_SWIGLU, false>(a, s);
-        case EPI_SILU:   return launch_v2<EPI_SILU, false>(a, s);
-        case EPI_GELU:   return launch_v2<EPI_GELU, false>(a, s);
-        case EPI_GEGLU:  return launch_v2<EPI_GEGLU, false>(a, s);
-        default: return -22;
-    }
 }

@@ -47,8 +47,6 @@
 
 using namespace emu_gemm;
 
-int launch_gemm_w4(const GemmArgs& b, hipStream_t s, int grid, int fx);     // gemm_w4.hip
-
 namespace {
 
 constexpr int UNIT = 128 * 128;          // 128 LDS rows of 128 bytes
@@ -106,8 +104,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs a) {
     if (b < a.full_tiles) {
         wg = xcd_order(b, a.full_tiles);
         if (a.sup_m) {
-            // 2-D blocks (launch_pp, unsliced plain GEMMs with many row tiles): an XCD's run of the logical order is one sup_m x sup_n
-            // block of tiles walked row-first, so the 32 workgroups it runs at a time share sup_m row tiles of A and a few weight
+            // 2-D blocks (unsliced plain GEMMs with many row tiles, gemm.hip::pick_tile_blocks): an XCD's run of the logical order is
+            // one sup_m x sup_n block of tiles walked row-first, so the 32 workgroups it runs at a time share sup_m row tiles of A and a few weight
             // tiles instead of one weight tile and 32 different row tiles (8192^3: 4.2 GB fetched for 0.27 GB of operands)
             const int per = a.sup_m * a.sup_n, blk = wg / per, r = wg - blk * per;
             const int bm = tiles_m / a.sup_m, bi = blk % bm, bj = blk / bm;
@@ -763,73 +761,6 @@ __global__ __launch_bounds__(256) void pp_reduce_kernel(const GemmArgs a) {
     }
 }
 
-template <int EPI, bool CONV, bool F8 = false>
-void launch_pp(const GemmArgs& a, hipStream_t s, int full_tiles, int ksplit) {
-    const int tiles = gemm256_tiles(a);
-    GemmArgs b = a;
-    b.full_tiles = full_tiles < 0 ? tiles : full_tiles;
-    b.ksplit = ksplit;
-    b.trace = emu_gemm_trace_get();
-    b.stage = stage_ok(b) && !(emu_gemm_tune_get() & 8);
-    b.stage_vt = b.stage && stage_vt_ok(b, 256, 256) && !(emu_gemm_tune_get() & (1 << 14));
-    if (!(emu_gemm_tune_get() & (1 << 23))) b.stage |= 2;            // four-wave tile: fp32 K-slices leave through LDS too (bit 23: A/B)
-    // XCD-aware 2-D tile blocks (gemm.hip::launch_cfg has the rule): unsliced plain GEMMs whose tile count splits evenly over the 8
-    // XCDs; the implicit-GEMM convs keep the column-major strips (one weight tile of K = 9 Cin per strip is what their L2 can hold)
-    b.sup_m = b.sup_n = 0;
-    if (!CONV && b.full_tiles == tiles && tiles % 8 == 0 && !(emu_gemm_tune_get() & (1 << 17)) && (tiles > 256 || !(emu_gemm_tune_get() & (1 << 18)))) {
-        int ext_rows;
-        const int tm = pp_tiles_m(a.M, true, ext_rows), tn = tiles / tm, per = tiles / 8;
-        const int cur_cols = (per + tm - 1) / tm + ((per % tm) ? 1 : 0);
-        long best = (long)(per < tm ? per : tm) + (long)(cur_cols < tn ? cur_cols : tn);
-        for (int sm = 1; sm <= tm; ++sm) {
-            if (tm % sm || per % sm || tn % (per / sm)) continue;
-            const long cost = (long)sm + (long)(per / sm);
-            if (cost < best) { best = cost; b.sup_m = sm; b.sup_n = per / sm; }
-        }
-    }
-    const int tail = tiles - b.full_tiles;
-    const int fx = gemm_fx(b);
-    // the main launch: the four-wave tile on its LDS ring (gemm_w4.hip) for bf16 operands; this file's eight-wave ping-pong tile for
-    // fp8 operands and, as the A/B twin, under emu_gemm_tune bit 21.  Same tile order, K-slices and slab layout: the reduce launches
-    // below serve both.
-    // Where the four-wave tile is taken (same-run A/B, profiles/r06_gemm_w4_*.log): plain GEMMs whose tiles all lie inside N (they
-    // leave through LDS: bf16 results and fp32 K-slices alike; a tile that reaches past N takes the direct path, whose scattered
-    // stores its one wave per SIMD issues at half the ping-pong tile's rate) with a light epilogue: nothing overlaps the dependent
-    // VALU chains of an erf on one wave per SIMD, and behind a GELU / GEGLU epilogue (ViT fc1, the UNet's GEGLU with its folded
-    // LayerNorm) the faster loop loses in the model (same-run: ViT encode 15.93 vs 15.39 ms, denoise step 26.64 vs 25.11 ms with those
-    // launches on it; LLaMA prefill S = 770 49.07 vs 51.35 ms).  K-slices shorter than 16 k tiles do not amortise the ring's prologue
-    // (UNet 32^2 attn-out 172 vs 198 TFLOP/s), the implicit-GEMM convs' per-row bias loads cost it more (661 vs 739).
-    // emu_gemm_tune bit 22 takes it wherever it is instantiated (tests).
-    constexpr bool ACT = EPI == EPI_GELU || EPI == EPI_GEGLU;
-    const int tune = emu_gemm_tune_get();
-    const bool w4 = !F8 && !(tune & (1 << 21)) &&
-                    ((tune & (1 << 22)) || (!CONV && (a.N & 255) == 0 && !ACT && !(gemm_fx(b) & FX_LN) &&
-                                            (tail == 0 || (a.K >> 6) / ksplit >= 16)));
-    const int grid = b.full_tiles + tail * ksplit;
-    if (fx & FX_ROPE) {                                 // launch_gemm: EPI_NONE, unsliced, bf16 (launch_v2 checks the plan)
-        if constexpr (!CONV && !F8 && EPI == EPI_NONE) {
-            if (w4) launch_gemm_w4(b, s, b.full_tiles, fx);
-            else hipLaunchKernelGGL((gemm_pp_kernel<EPI_NONE, false, false, FX_ROPE | FX_VT>), dim3(b.full_tiles), dim3(512), 0, s, b);
-        }
-        return;
-    }
-    if (fx) {                                           // gemm256_ok: bf16 plain GEMM; launch_gemm: an instantiated (epi, mask) pair
-        if constexpr (!CONV && !F8) {
-            gemm_fx_dispatch<EPI>(fx, [&](auto m) {
-                constexpr int FXM = decltype(m)::value;
-                if (w4) launch_gemm_w4(b, s, grid, fx);
-                else hipLaunchKernelGGL((gemm_pp_kernel<EPI, CONV, F8, FXM>), dim3(grid), dim3(512), 0, s, b);
-                if (tail > 0) hipLaunchKernelGGL((pp_reduce_kernel<EPI, FXM>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
-            });
-        }
-        return;
-    }
-    if (w4) launch_gemm_w4(b, s, grid, 0);
-    else hipLaunchKernelGGL((gemm_pp_kernel<EPI, CONV, F8>), dim3(grid), dim3(512), 0, s, b);
-    if (tail > 0 && b.slab_rows) launch_rows_reduce_norm(b, s);     // launch_v2: every tile sliced, bf16, N <= 16384 (gemm_tile.h)
-    else if (tail > 0) hipLaunchKernelGGL((pp_reduce_kernel<EPI>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
-}
-
 }  // namespace
 
 int gemm256_tiles(const GemmArgs& a) {
@@ -860,36 +791,30 @@ bool gemm256_ok(const GemmArgs& a) {
     return wb < 0x7fffffffull && ab < 0x7fffffffull;
 }
 
-// 256x256 ping-pong tile: tiles [0, full_tiles) whole-K, the rest cut into ksplit K-slices (fp32 slices of
-// EMU_GEMM256_SLICE_FLOATS each in a.partial, summed by a second launch).  full_tiles < 0: no slicing.
-int launch_gemm256(const GemmArgs& a, hipStream_t s, int full_tiles, int ksplit) {
-    if (!gemm256_ok(a)) return -22;
-    if (a.a_scale) {
-        switch (a.epi) {
-            case EPI_NONE:   launch_pp<EPI_NONE, false, true>(a, s, full_tiles, ksplit); break;
-            case EPI_RESID:  launch_pp<EPI_RESID, false, true>(a, s, full_tiles, ksplit); break;
-            case EPI_SWIGLU: launch_pp<EPI_SWIGLU, false, true>(a, s, full_tiles, ksplit); break;
-            case EPI_GELU:   launch_pp<EPI_GELU, false, true>(a, s, full_tiles, ksplit); break;
-            case EPI_GEGLU:  launch_pp<EPI_GEGLU, false, true>(a, s, full_tiles, ksplit); break;
-            default: return -22;
+// A planned launch of the 256x256 tile (gemm.hip::plan_gemm): the main launch -- this file's eight-wave ping-pong kernel, or the
+// four-wave one of gemm_w4.hip (same tile order, K-slices and slab layout) -- and the reduce that follows it: tiles [0, full_tiles)
+// whole-K, the rest in ksplit K-slices (fp32 slices of EMU_GEMM256_SLICE_FLOATS each in b.partial)
+int launch_gemm256(const GemmArgs& b, const GemmPlan& p, hipStream_t s) {
+    const int tail = gemm256_tiles(b) - b.full_tiles, grid = b.full_tiles + tail * b.ksplit;
+    const bool ok = gemm_form_dispatch(b, [&](auto e, auto c, auto q, auto m) {
+        constexpr int EPI = decltype(e)::value, FX = decltype(m)::value;
+        constexpr bool CONV = decltype(c)::value, F8 = decltype(q)::value;
+        if constexpr (F8 && FX != 0) {
+            return false;
+        } else {
+            if (p.w4) {
+                if (launch_gemm_w4(b, s, grid) != 0) return false;
+            } else {
+                hipLaunchKernelGGL((gemm_pp_kernel<EPI, CONV, F8, FX>), dim3(grid), dim3(512), 0, s, b);
+            }
+            if constexpr ((FX & FX_ROPE) == 0) {
+                if (p.reduce == GEMM_REDUCE_ROWS_NORM) launch_rows_reduce_norm(b, s);
+                else if (p.reduce == GEMM_REDUCE_PP) hipLaunchKernelGGL((pp_reduce_kernel<EPI, FX>), dim3(tail, SPLITK_RED_Y), dim3(256), 0, s, b);
+            }
+            return true;
         }
-    } else if (a.conv.mode != CONV_NONE) {
-        switch (a.epi) {
-            case EPI_NONE:  launch_pp<EPI_NONE, true>(a, s, full_tiles, ksplit); break;
-            case EPI_RESID: launch_pp<EPI_RESID, true>(a, s, full_tiles, ksplit); break;
-            default: return -22;
-        }
-    } else {
-        switch (a.epi) {
-            case EPI_NONE:   launch_pp<EPI_NONE, false>(a, s, full_tiles, ksplit); break;
-            case EPI_RESID:  launch_pp<EPI_RESID, false>(a, s, full_tiles, ksplit); break;
-            case EPI_SWIGLU: launch_pp<EPI_SWIGLU, false>(a, s, full_tiles, ksplit); break;
-            case EPI_SILU:   launch_pp<EPI_SILU, false>(a, s, full_tiles, ksplit); break;
-            case EPI_GELU:   launch_pp<EPI_GELU, false>(a, s, full_tiles, ksplit); break;
-            case EPI_GEGLU:  launch_pp<EPI_GEGLU, false>(a, s, full_tiles, ksplit); break;
-            default: return -22;
-        }
-    }
+    });
+    if (!ok) return -22;
     EMU_CHECK_LAUNCH();
     return 0;
 }

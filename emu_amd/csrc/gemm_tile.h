@@ -559,4 +559,53 @@ inline bool gemm_fx_dispatch(int fx, F&& f) {
     return false;
 }
 
+// The kernel form of a launch: calls f(EPI, CONV, F8, FX) -- std::integral_constant / std::bool_constant values of the epilogue,
+// conv, fp8 operands and feature mask -- and returns its answer; false for a form no tile has (launch_gemm's checks refuse those).
+// Every tile family passes the forms it instantiates and answers false to the rest.
+template <class F>
+inline bool gemm_form_dispatch(const GemmArgs& a, F&& f) {
+    using std::integral_constant;
+    const int fx = gemm_fx(a);
+    auto with_fx = [&](auto e, auto c, auto q) -> bool {
+        constexpr int EPI = decltype(e)::value;
+        if (fx == 0) return f(e, c, q, integral_constant<int, 0>{});
+        if constexpr (decltype(c)::value) {
+            return false;
+        } else if constexpr (decltype(q)::value) {      // fp8: the V^T and cross-attention epilogues
+            if constexpr (EPI == EPI_NONE) {
+                if (fx == FX_VT) return f(e, c, q, integral_constant<int, FX_VT>{});
+                if (fx == FX_CROSS) return f(e, c, q, integral_constant<int, FX_CROSS>{});
+            }
+            return false;
+        } else {
+            if constexpr (EPI == EPI_NONE)
+                if (fx == (FX_ROPE | FX_VT)) return f(e, c, q, integral_constant<int, FX_ROPE | FX_VT>{});
+            bool r = false;
+            gemm_fx_dispatch<EPI>(fx, [&](auto m) { r = f(e, c, q, m); });
+            return r;
+        }
+    };
+    auto with_epi = [&](auto c, auto q) -> bool {
+        constexpr bool CONV = decltype(c)::value, F8 = decltype(q)::value;
+        switch (a.epi) {
+            case EPI_NONE:  return with_fx(integral_constant<int, EPI_NONE>{}, c, q);
+            case EPI_RESID: return with_fx(integral_constant<int, EPI_RESID>{}, c, q);
+        }
+        if constexpr (!CONV) {
+            switch (a.epi) {
+                case EPI_SWIGLU: return with_fx(integral_constant<int, EPI_SWIGLU>{}, c, q);
+                case EPI_GELU:   return with_fx(integral_constant<int, EPI_GELU>{}, c, q);
+                case EPI_GEGLU:  return with_fx(integral_constant<int, EPI_GEGLU>{}, c, q);
+                case EPI_SILU:
+                    if constexpr (!F8) return with_fx(integral_constant<int, EPI_SILU>{}, c, q);
+            }
+        }
+        return false;
+    };
+    if (a.conv.mode != CONV_NONE) return !a.a_scale && with_epi(std::true_type{}, std::false_type{});
+    return a.a_scale ? with_epi(std::false_type{}, std::true_type{}) : with_epi(std::false_type{}, std::false_type{});
+}
+// the forms (of those above) the four-wave 256x256 tile instantiates (gemm_w4.hip): bf16, every mask but the cross-attention
+constexpr bool gemm_w4_ok(bool f8, int fx) { return !f8 && (fx & FX_CROSS) == 0; }
+
 }  // namespace emu_gemm

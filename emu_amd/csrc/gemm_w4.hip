@@ -1,8 +1,8 @@
 // 256(n) x 256(m) x 64(k) bf16 MFMA GEMM tile on FOUR waves -- one per SIMD, 256 fp32 accumulators each in AGPRs -- fed by a ring of
 // five 32 KiB LDS slots.  Round 6's main loop for the large, light-epilogue GEMMs of the path (LLaMA prefill: qkv with the RoPE / KV /
 // V^T epilogue, gate/up, the K-sliced o_proj / down_proj); gemm256.hip's 8-wave ping-pong tile keeps fp8 operands, the GELU / GEGLU /
-// folded-LayerNorm epilogues, convs and tiles that reach past N (launch_pp has the rule and the measurements), and is the A/B twin
-// everywhere (emu_gemm_tune bit 21; bit 22 takes this tile wherever it is instantiated).  C[m, n] = epilogue(sum_k A[m, k] W[n, k]).
+// folded-LayerNorm epilogues, convs and tiles that reach past N (gemm.hip::plan_launch has the rule and the measurements), and is the
+// A/B twin everywhere (emu_gemm_tune bit 21; bit 22 takes this tile wherever it is instantiated).  C[m, n] = epilogue(sum_k A[m, k] W[n, k]).
 //
 // Why four waves: a wave that owns 128(n) x 128(m) of the tile reads (128 + 128) x 128 B = 32 KiB of fragments per k tile, 128 KiB
 // per CU; the eight waves of the ping-pong tile (128 x 64 each) read 192 KiB, and on this chip the matrix pipe is power-limited: at
@@ -794,49 +794,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
-template <int EPI, bool CONV>
-int launch_w4_epi(const GemmArgs& b, hipStream_t s, int grid, int fx) {
-    if (fx & FX_ROPE) {
-        if constexpr (!CONV && EPI == EPI_NONE) {
-            hipLaunchKernelGGL((gemm_w4_kernel<EPI_NONE, false, FX_ROPE | FX_VT>), dim3(grid), dim3(256), 0, s, b);
-            return 0;
-        }
-        return -22;
-    }
-    if (fx) {
-        if constexpr (!CONV) {
-            const bool ok = gemm_fx_dispatch<EPI>(fx, [&](auto m) {
-                constexpr int FXM = decltype(m)::value;
-                if constexpr ((FXM & FX_CROSS) == 0) hipLaunchKernelGGL((gemm_w4_kernel<EPI, CONV, FXM>), dim3(grid), dim3(256), 0, s, b);
-            });
-            return ok && !(fx & FX_CROSS) ? 0 : -22;
-        }
-        return -22;
-    }
-    hipLaunchKernelGGL((gemm_w4_kernel<EPI, CONV>), dim3(grid), dim3(256), 0, s, b);
-    return 0;
-}
-
 }  // namespace
 
-// The main launch of a 256 x 256 run on the four-wave tile.  `b` is the fully prepared argument block of gemm256.hip::launch_pp
+// The main launch of a 256 x 256 run on the four-wave tile.  `b` is the fully prepared argument block of gemm256.hip::launch_gemm256
 // (full_tiles / ksplit / stage flags / tile blocks set); the caller launches the K-slice reduce that follows.  -22: not instantiated.
-int launch_gemm_w4(const GemmArgs& b, hipStream_t s, int grid, int fx) {
-    const bool conv = b.conv.mode != CONV_NONE;
-    if (conv) {
-        switch (b.epi) {
-            case EPI_NONE:  return launch_w4_epi<EPI_NONE, true>(b, s, grid, fx);
-            case EPI_RESID: return launch_w4_epi<EPI_RESID, true>(b, s, grid, fx);
-            default: return -22;
+int launch_gemm_w4(const GemmArgs& b, hipStream_t s, int grid) {
+    const bool ok = gemm_form_dispatch(b, [&](auto e, auto c, auto q, auto m) {
+        if constexpr (!gemm_w4_ok(decltype(q)::value, decltype(m)::value)) {
+            return false;
+        } else {
+            hipLaunchKernelGGL((gemm_w4_kernel<decltype(e)::value, decltype(c)::value, decltype(m)::value>), dim3(grid), dim3(256), 0, s, b);
+            return true;
         }
-    }
-    switch (b.epi) {
-        case EPI_NONE:   return launch_w4_epi<EPI_NONE, false>(b, s, grid, fx);
-        case EPI_RESID:  return launch_w4_epi<EPI_RESID, false>(b, s, grid, fx);
-        case EPI_SWIGLU: return launch_w4_epi<EPI_SWIGLU, false>(b, s, grid, fx);
-        case EPI_SILU:   return launch_w4_epi<EPI_SILU, false>(b, s, grid, fx);
-        case EPI_GELU:   return launch_w4_epi<EPI_GELU, false>(b, s, grid, fx);
-        case EPI_GEGLU:  return launch_w4_epi<EPI_GEGLU, false>(b, s, grid, fx);
-        default: return -22;
-    }
+    });
+    return ok ? 0 : -22;
 }

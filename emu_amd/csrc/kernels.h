@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/emu_hip.h"
+
 typedef uint16_t bf16_t;
 
 enum EmuEpilogue { EPI_NONE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_SILU = 3, EPI_GELU = 4, EPI_GEGLU = 5 };
@@ -159,9 +161,13 @@ unsigned long long* emu_gemm_trace_get();
 void emu_gemm_trace_select(long n);     // trace only the n-th GEMM launch from now on (-1: every launch)
 // fp8 x fp8 -> bf16 on the block-scaled MFMA (256x256 ping-pong tile only): K % 128 == 0, a.a_scale / a.w_scale set
 int launch_gemm_fp8(const GemmArgs& a, hipStream_t s);
-// the 256x256 ping-pong tile (gemm256.hip), dispatched by launch_gemm; tiles [0, full_tiles) whole-K, the rest in ksplit
-// K-slices of EMU_GEMM256_SLICE_FLOATS fp32 each in a.partial (full_tiles < 0: no slicing)
-int launch_gemm256(const GemmArgs& a, hipStream_t s, int full_tiles, int ksplit);
+// One planned launch of launch_gemm / launch_gemm_fp8 (gemm.hip::plan_gemm; the C-ABI test hook emu_gemm_plan returns the same).
+using GemmPlan = emu_gemm_plan_entry;
+enum GemmReduce { GEMM_REDUCE_NONE = 0, GEMM_REDUCE_SPLITK = 1, GEMM_REDUCE_PP = 2, GEMM_REDUCE_ROWS_NORM = 3 };
+// the 256x256 tile (gemm256.hip) for a planned launch: `b` carries the plan's fields; -22 if the form is not instantiated
+int launch_gemm256(const GemmArgs& b, const GemmPlan& p, hipStream_t s);
+// its four-wave main loop (gemm_w4.hip): grid workgroups, the caller launches the reduce; -22 if the form is not instantiated
+int launch_gemm_w4(const GemmArgs& b, hipStream_t s, int grid);
 int gemm256_tiles(const GemmArgs& a);           // workgroups of a whole-K launch (the last row of tiles carries M % 256 <= 32)
 bool gemm256_ok(const GemmArgs& a);             // K % 64 == 0 and operands within reach of 32-bit descriptor offsets
 constexpr size_t EMU_GEMM256_SLICE_FLOATS = 288 * 256;
@@ -171,7 +177,7 @@ constexpr size_t EMU_SPLITK_SCRATCH_FLOATS = (size_t)512 * 288 * 256;
 void emu_gemm_set_splitk_scratch(float* ptr, size_t floats);
 // test / bench hook: pin the tile configuration ('B', 'C', 'K', 'S', 'P'; 0 = heuristic)
 void emu_gemm_force_config_set(int cfg);
-// A/B switches of single dispatch decisions (bit 0: GLU GEMMs the hybrid would split run as one launch of 128 x 128 tiles)
+// A/B switches of single dispatch decisions (include/emu_hip.h: emu_gemm_tune)
 void emu_gemm_tune_set(int mask);
 int emu_gemm_tune_get();
 

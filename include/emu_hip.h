@@ -72,24 +72,45 @@ void emu_set_splitk_scratch(void* ptr, size_t bytes);
  * GEMM (where the tile count allows, else the heuristic).  The parity tests walk every configuration over the
  * bench's true shapes with it (tests/test_gpu_ops.py); production code never calls it. */
 void emu_gemm_force_config(int cfg);
-/* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bit 0: GLU GEMMs that the heuristic
- * splits into whole rounds of the 256x256 tile + a remainder GEMM run as ONE launch of 128x128 tiles.  Bit 1: the K-slice
- * workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before round 3) instead of the
- * XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip) and run on the
- * v_dot2c / register-fed MFMA kernels as before round 3; bit 3: the GEMM / conv epilogues store straight from the accumulator
- * layout (8 bytes per lane to 32 rows per instruction, as before round 4) instead of through the LDS-staged, row-contiguous
- * 16-byte form; bit 4: the lock-step tiles keep the column-major XCD runs instead of 2-D tile blocks per XCD; bit 5: no 128 x 128
- * tile for one-round problems; bit 6: the attention kernel deals its workgroups in launch order (query blocks of a head on 8
+/* CPU test hook (tests/test_gemm_plan.py): what launch_gemm / launch_gemm_fp8 would launch for a problem of this shape under
+ * force_cfg (emu_gemm_force_config) and tune (emu_gemm_tune) -- host arithmetic only, no HIP call, no global read.  The shape
+ * stands for an argument block with row-contiguous operands (lda = ldw = K, or Cin for a conv; ldc = N, N / 2 for the GLU
+ * epilogues) on aligned buffers.  fx: 1 LayerNorm folded into A (ln_*), 2 row statistics of C (row_stats_out), 4 V^T (vt_*),
+ * 8 cross-attention (cross_*), 16 RoPE + KV append (with 4), 32 RMSNorm of C in the reduce (norm_*); rows: rows per batch
+ * element of the V^T / cross-attention forms (0: M).  Fills *entries (two only for the hybrid split: whole rounds of the 256x256
+ * tile, then the remaining columns) and returns launch_gemm's status: 0, -22 (refused), -95 (fused form not available). */
+typedef struct {
+    int M, N, K, epi;
+    int conv_mode, Hin, Win, Hout, Wout, Cin;
+    int fx, rows, vt_col0, fp8;
+    size_t scratch_floats;      /* split-K scratch; 0 = none */
+} emu_gemm_shape;
+typedef struct {
+    int tile;                   /* 'B' 128x128, 'C' 256(n)x128(m), 'K' 128(n)x64(m) with two k-groups, 256: the 256x256 tile */
+    int w4;                     /* tile 256: the four-wave kernel (gemm_w4.hip) instead of the eight-wave ping-pong one */
+    int col0, n;                /* output columns [col0, col0 + n) of this launch */
+    int full_tiles, ksplit;     /* tiles [0, full_tiles) whole-K, every later tile in ksplit K-slices */
+    int sup_m, sup_n;           /* XCD tile blocks (0: column-major runs) */
+    int stage, stage_vt, slab_rows, slice_rr;   /* the GemmArgs flags of the same names */
+    int no_prefetch;            /* the successor-weight prefetch is dropped */
+    int reduce;                 /* the launch after it: 0 none, 1 split-K reduce, 2 256x256 slice reduce, 3 rows + norm */
+} emu_gemm_plan_entry;
+int emu_gemm_plan(const emu_gemm_shape* shape, int force_cfg, int tune, emu_gemm_plan_entry plan[2], int* entries);
+/* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bits 0, 4, 5, 14, 17 and 18: retired,
+ * ignored.  Bit 1: the K-slice workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before
+ * round 3) instead of the XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip)
+ * and run on the v_dot2c / register-fed MFMA kernels as before round 3; bit 3: the GEMM / conv epilogues store straight from the
+ * accumulator layout (8 bytes per lane to 32 rows per instruction, as before round 4) instead of through the LDS-staged,
+ * row-contiguous 16-byte form; bit 6: the attention kernel deals its workgroups in launch order (query blocks of a head on 8
  * different XCDs); bit 7: it stores O straight from the accumulator layout; bits 12-13: 1 / 2 = attention always on 4 / 8 waves;
- * bit 14: V^T tiles of a fused qkv projection stored straight from the accumulators instead of through the transposed staging; bit 15:
- * causal attention launches keep the (head, query block) order instead of walking every XCD's heads from the longest query block
- * down; bits 8-11: variant of the thin stream (tools/thin_ab.py); bit 16: no successor-weight prefetch from inside the GEMM kernels;
- * bit 17: the 256 x 256 tile keeps the column-major XCD runs instead of 2-D tile blocks per XCD (unsliced plain GEMMs), bit 18: blocks
- * only for launches of more than one round; bit 19 (opt-in): a short tensor-parallel shard's one-row step merges the decode
- * attention's splits in the o_proj launch's prologue instead of a combine launch ahead of it (gemv_merge.hip: bit-identical, measured level);
- * bits 21-23 (round 6, the four-wave 256x256 tile of gemm_w4.hip): 21 = never take it (the eight-wave ping-pong tile everywhere: the
- * same-run A/B twin), 22 = take it wherever it is instantiated (tests: bf16 plain GEMMs and convs of the 256x256 configuration,
- * whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of through LDS. */
+ * bit 15: causal attention launches keep the (head, query block) order instead of walking every XCD's heads from the longest query
+ * block down; bits 8-11: variant of the thin stream (tools/thin_ab.py); bit 16: no successor-weight prefetch from inside the GEMM
+ * kernels; bit 19 (opt-in): a short tensor-parallel shard's one-row step merges the decode attention's splits in the o_proj
+ * launch's prologue instead of a combine launch ahead of it (gemv_merge.hip: bit-identical, measured level);
+ * bits 21-23 (round 6, the four-wave 256x256 tile of gemm_w4.hip): 21 = never take it (the eight-wave ping-pong
+ * tile everywhere: the same-run A/B twin), 22 = take it wherever it is instantiated (tests: bf16 plain GEMMs and convs of the
+ * 256x256 configuration, whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of
+ * through LDS. */
 void emu_gemm_tune(int mask);
 
 /* Tools hook (tools/gemm_trace.py): per-workgroup timelines of the following GEMM launches -- 8 x uint64 per workgroup at

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Same-run A/B of the UNet denoise step under different launch-fusion masks (emu_unet_set_fusion): one engine, one set of
 weights, the variants alternated inside one process (box-to-box variance of the MFMA-bound legs is ~12 %, so only same-run
-comparisons are evidence).  A variant is a fusion mask, optionally followed by "t<N>" = emu_gemm_tune(N) (e.g. "3t1"), or
+comparisons are evidence).  A variant is a fusion mask, optionally followed by "t<N>" = emu_gemm_tune(N) (e.g. "3t8"), or
 "fp8" = the transformer blocks W8A8 (emu_unet_use_fp8).
 Usage: python tools/unet_ab.py [steps] [variant,variant,...] [rounds]"""
 import os, sys, time
