@@ -162,6 +162,11 @@ _PROTOS = {
     "emu_beam_advance": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "emu_llama_beam_reorder_kv": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "emu_vit_blocks": (i32, [vp, vp, i32, i32, i32, vp, sz, vp]),
+    "emu_vit_set_token_parallel": (i32, [vp, i32, i32, i32]),
+    "emu_vit_tp_create": (i32, [vp, vp]),
+    "emu_vit_tp_open": (i32, [vp, vp, i32, i32]),
+    "emu_vit_forward_tp": (i32, [vp, vp, i32, vp, vp, sz, vp]),
+    "emu_vit_tp_rows": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "emu_unet_workspace_bytes": (sz, [vp, i32, i32]),
     "emu_unet_context_bytes": (sz, [vp, i32]),
     "emu_unet_set_context": (i32, [vp, vp, i32, vp, i32, vp, sz, vp, sz, vp]),

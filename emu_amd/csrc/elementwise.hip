@@ -189,6 +189,23 @@ __global__ __launch_bounds__(256) void vit_assemble_kernel(const bf16_t* __restr
     }
 }
 
+// the same for token rows [t0, t0 + gridDim.x) of one image (token-parallel ViT: a rank assembles its own rows only)
+__global__ __launch_bounds__(256) void vit_assemble_rows_kernel(const bf16_t* __restrict__ patches, const bf16_t* __restrict__ cls,
+                                                                const bf16_t* __restrict__ pos, bf16_t* __restrict__ x, int t0, int C) {
+    const int t = t0 + blockIdx.x;
+    const bf16_t* src = t == 0 ? cls : patches + (size_t)(t - 1) * C;
+    const bf16_t* pr = pos + (size_t)t * C;
+    bf16_t* dst = x + (size_t)t * C;
+    for (int vi = threadIdx.x; vi < (C >> 3); vi += 256) {
+        float f[8], q[8];
+        unpack8(ld16(src + vi * 8), f);
+        unpack8(ld16(pr + vi * 8), q);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] += q[e];
+        st16(dst + vi * 8, pack8(f));
+    }
+}
+
 // softmax over one row per workgroup, fp32 statistics; the row is re-read from L2 for each pass.  Optional additive bias
 // (T5 relative-position bias + causal mask, bf16): logits = bf16(x * scale + bias) as the bf16 tensor add of the reference.
 __global__ __launch_bounds__(256) void softmax_rows_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ bias, int cols, int ld,
@@ -437,6 +454,12 @@ int launch_avgpool_tokens(const bf16_t* x, bf16_t* out, int B, int g, int C, int
 int launch_vit_assemble(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int B, int T, int C, hipStream_t s) {
     if (B < 1 || (C & 7)) return -22;
     hipLaunchKernelGGL(vit_assemble_kernel, dim3(B * (T + 1)), dim3(256), 0, s, patches, cls, pos, x, T, C);
+    EMU_CHECK_LAUNCH();
+    return 0;
+}
+int launch_vit_assemble_rows(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int t0, int t1, int C, hipStream_t s) {
+    if (t0 < 0 || t1 <= t0 || (C & 7)) return -22;
+    hipLaunchKernelGGL(vit_assemble_rows_kernel, dim3(t1 - t0), dim3(256), 0, s, patches, cls, pos, x, t0, C);
     EMU_CHECK_LAUNCH();
     return 0;
 }

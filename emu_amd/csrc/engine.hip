@@ -1264,6 +1264,13 @@ struct emu_vit {
     bool fp8 = false;
     bool fuse_vt = true;                             // emu_vit_set_fusion bit 0: V^T out of the qkv projection's epilogue (one image)
     bool fuse_norm = true;                           // bit 1: fc2's K-slice sum applies bias + LayerNorm + residual (post-norm blocks)
+    // token-parallel encode of one image (emu_vit_set_token_parallel / emu_vit_forward_tp): this rank computes token rows
+    // [tp_r0, tp_r1) of every block; the K rows and V^T key columns of the others arrive through the exchange regions (p2p.hip)
+    int tp_rank = 0, tp_world = 0;                   // tp_world 0: not set
+    bool tp_emulate = false;                         // timing tools: the exchanges are skipped (only this rank's rows are right)
+    EmuVitX* xchg = nullptr;
+    int tp_r0 = 0, tp_r1 = 0;                        // rows computed by the last emu_vit_forward_tp
+    ~emu_vit() { emu_vitx_destroy(xchg); }
 };
 
 namespace {
@@ -1354,14 +1361,27 @@ int emu_vit_use_fp8(emu_vit* m, int enable) {
 }
 size_t emu_vit_workspace_bytes(const emu_vit* m, int Bn) { return m ? vit_ws(m, Bn, nullptr).total : 0; }
 
-// blocks [l0, l1) in place on tokens x [B * N, C]
-static int vit_blocks(emu_vit* m, bf16_t* x, int Bn, int l0, int l1, const VitWs& w, hipStream_t s) {
+// token rows [rows[r], rows[r + 1]) of rank r (emu_amd/tp.py::token_rows): ceil(N / 8) groups of 8 rows, rank r starting at group
+// ceil(r * groups / world) -- contiguous, balanced to one group, row 0 (CLS) on rank 0, a trailing rank may own none
+static void vit_token_rows(int N, int world, int* rows) {
+    const long U = (N + 7) / 8;
+    for (int r = 0; r <= world; ++r) rows[r] = std::min<long>(8 * ((r * U + world - 1) / world), N);
+}
+
+// one image's rows [r0, r1) of the token-parallel chain; rows: the partition of every rank, xchg: the exchange (null: skipped)
+struct VitTp { int r0, r1; const int* rows; EmuVitX* xchg; };
+
+// blocks [l0, l1) in place on tokens x [B * N, C]; tp: only rows [tp->r0, tp->r1) of one image (x and the qkv / V^T buffers stay
+// full size, own rows at their global offsets), every block's K rows and V^T keys exchanged between the qkv projection and attention
+static int vit_blocks(emu_vit* m, bf16_t* x, int Bn, int l0, int l1, const VitWs& w, hipStream_t s, const VitTp* tp = nullptr) {
     emu_ctx* cx = m->ctx;
     const emu_vit_cfg& c = m->cfg;
-    const int g = c.image_size / c.patch_size, T = g * g, N = T + 1, M = Bn * N, C = c.width, Hh = c.heads;
+    const int g = c.image_size / c.patch_size, T = g * g, N = T + 1, C = c.width, Hh = c.heads;
     const int QK = Hh * VIT_DP, F = c.mlp_hidden;
     const int npad = (N + 63) / 64 * 64;
     const float scale = 1.0f / sqrtf((float)c.head_width);
+    const int r0 = tp ? tp->r0 : 0, M = tp ? tp->r1 - tp->r0 : Bn * N;   // rows this call computes
+    x += (size_t)r0 * C;
     // one GEMM of a block: bf16, or (emu_vit_use_fp8) the activation rows quantised per row + the fp8 x fp8 GEMM
     // (quantised = true: the LayerNorm in front of this GEMM has left the rows in w.x8 / w.xs already: launch_layernorm_q8)
     auto lin = [&](const bf16_t* A, const bf16_t* W, const uint8_t* W8, const float* ws8, const bf16_t* bias, const bf16_t* res,
@@ -1381,7 +1401,7 @@ static int vit_blocks(emu_vit* m, bf16_t* x, int Bn, int l0, int l1, const VitWs
     // V^T out of the qkv epilogue (one image, bf16) writes keys [0, N) and the few pad keys of the last 8-key group; the rest of the
     // pad columns [N, npad) of the V^T buffer is nobody's: zeroed once per call (the attention kernel multiplies them by masked
     // probabilities, and a stale NaN pattern times zero is NaN)
-    if (m->fuse_vt && Bn == 1 && !m->fp8 && npad != N && l1 > l0 &&
+    if ((m->fuse_vt || tp) && Bn == 1 && !m->fp8 && npad != N && l1 > l0 &&
         hipMemsetAsync(w.vt, 0, (size_t)Hh * VIT_DP * npad * 2, s) != hipSuccess)
         return fail(cx, -5, "emu_vit_forward: hipMemsetAsync");
     const bool q8 = m->fp8 && C <= 2048;                 // LayerNorm rows leave as fp8 operands (launch_layernorm_q8)
@@ -1391,6 +1411,10 @@ static int vit_blocks(emu_vit* m, bf16_t* x, int Bn, int l0, int l1, const VitWs
         if (!Bk.wqkv) return fail(cx, -22, "emu_vit_forward: block weights not set");
         const emu_vit::Block8 B8 = m->fp8 ? m->blocks8[l] : emu_vit::Block8{};
         const bf16_t* ain = x;                           // attention input
+        if (M == 0) {                                    // a rank without rows still takes part in every exchange
+            if (tp->xchg) TRY(cx, emu_vitx_exchange(tp->xchg, tp->rows, w.qkv + QK, 3 * QK, QK, w.vt, npad, s));
+            continue;
+        }
         if (c.prenorm) {
             if (q8) TRY(cx, launch_layernorm_q8(x, Bk.ln1w, Bk.ln1b, nullptr, nullptr, w.x8, w.xs, M, C, c.ln_eps, s));
             else TRY(cx, launch_layernorm(x, Bk.ln1w, Bk.ln1b, nullptr, w.tmp, M, C, c.ln_eps, s));
@@ -1398,21 +1422,23 @@ static int vit_blocks(emu_vit* m, bf16_t* x, int Bn, int l0, int l1, const VitWs
         }
         // one image, bf16: the V heads leave the qkv projection key-contiguous (GemmArgs::vt_*, round 3's UNet epilogue; the
         // transposed staging takes a single batch element's ragged last tile since round 4) -- no transpose launch
-        const bool fvt = m->fuse_vt && Bn == 1 && !B8.wqkv;
+        const bool fvt = (m->fuse_vt || tp) && Bn == 1 && !B8.wqkv;
         if (fvt) {
-            GemmArgs gq{ain, Bk.wqkv, Bk.bqkv, nullptr, w.qkv, M, 3 * QK, C, C, C, 0, 3 * QK, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
+            // token-parallel: own rows land at row r0 of the qkv buffer and at key r0 of V^T (r0 is a multiple of 8: 16-byte aligned)
+            GemmArgs gq{ain, Bk.wqkv, Bk.bqkv, nullptr, w.qkv + (size_t)r0 * 3 * QK, M, 3 * QK, C, C, C, 0, 3 * QK, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
             gq.partial = w.splitk; gq.partial_floats = w.splitk_floats;
-            gq.vt_out = w.vt; gq.vt_col0 = 2 * QK; gq.vt_s = N; gq.vt_spad = npad;
+            gq.vt_out = w.vt + r0; gq.vt_col0 = 2 * QK; gq.vt_s = M; gq.vt_spad = npad;
             TRY(cx, launch_gemm(gq, s));
         } else {
             TRY(cx, lin(ain, Bk.wqkv, B8.wqkv, B8.sqkv, Bk.bqkv, nullptr, w.qkv, 3 * QK, C, 0, EPI_NONE, q8 && (c.prenorm || x8_valid)));
             TransposeVArgs tv{w.qkv + 2 * QK, (long)N * 3 * QK, (long)VIT_DP, (long)3 * QK, w.vt, Bn, Hh, N, VIT_DP, npad};
             TRY(cx, launch_transpose_v(tv, s));
         }
-        FlashArgs f{w.qkv, (long)N * 3 * QK, (long)VIT_DP, (long)3 * QK,
+        if (tp && tp->xchg) TRY(cx, emu_vitx_exchange(tp->xchg, tp->rows, w.qkv + QK, 3 * QK, QK, w.vt, npad, s));
+        FlashArgs f{w.qkv + (size_t)r0 * 3 * QK, (long)N * 3 * QK, (long)VIT_DP, (long)3 * QK,
                     w.qkv + QK, (long)N * 3 * QK, (long)VIT_DP, (long)3 * QK,
                     w.vt, w.attn, (long)N * QK, (long)VIT_DP, (long)QK, nullptr,
-                    Bn, Hh, N, N, npad, VIT_DP, 0, scale};
+                    Bn, Hh, tp ? M : N, N, npad, VIT_DP, 0, scale};
         TRY(cx, launch_flash_attn(f, s));
         if (c.prenorm) {
             // x = x + proj(attn);  x = x + fc2(gelu(fc1(LN2(x))))
@@ -1461,6 +1487,69 @@ int emu_vit_forward(emu_vit* m, const void* image, int image_is_f32, int Bn, voi
     TRY(cx, linear(w.patches, m->wpatch, m->bpatch, nullptr, nullptr, w.pemb, Bn * T, C, c.kpad, c.kpad, c.kpad, 0, C, 0.f, EPI_NONE, s));
     TRY(cx, launch_vit_assemble(w.pemb, m->cls, m->pos, x, Bn, T, C, s));
     return vit_blocks(m, x, Bn, 0, c.layers, w, s);
+}
+
+int emu_vit_set_token_parallel(emu_vit* m, int rank, int world, int emulate) {
+    if (!m || world < 1 || world > EMU_P2P_MAX_RANKS || rank < 0 || rank >= world) return -22;
+    if (m->xchg && (world != m->tp_world || rank != m->tp_rank)) { emu_vitx_destroy(m->xchg); m->xchg = nullptr; }
+    m->tp_rank = rank; m->tp_world = world; m->tp_emulate = emulate != 0;
+    return 0;
+}
+int emu_vit_tp_create(emu_vit* m, void* handle64_out) {
+    if (!m || !handle64_out || m->tp_world < 2) return -22;
+    if (m->xchg) return fail(m->ctx, -17, "emu_vit_tp_create: already created");
+    hipError_t e = hipSetDevice(m->ctx->device);
+    if (e != hipSuccess) return fail(m->ctx, (int)e, "hipSetDevice");
+    const emu_vit_cfg& c = m->cfg;
+    const int g = c.image_size / c.patch_size, N = g * g + 1, QK = c.heads * VIT_DP;
+    m->xchg = emu_vitx_create(m->tp_rank, m->tp_world, (size_t)N * std::max(QK, c.width), QK, (N + 63) / 64 * 64, handle64_out);
+    return m->xchg ? 0 : fail(m->ctx, -12, "emu_vit_tp_create: exchange region allocation / IPC export failed");
+}
+int emu_vit_tp_open(emu_vit* m, const void* handles, int timeout_ms, int fenced) {
+    if (!m || !m->xchg) return -22;
+    hipError_t e = hipSetDevice(m->ctx->device);
+    if (e != hipSuccess) return fail(m->ctx, (int)e, "hipSetDevice");
+    const int st = emu_vitx_open(m->xchg, handles, timeout_ms, fenced);
+    return st == 0 ? 0 : fail(m->ctx, st, "emu_vit_tp_open: hipIpcOpenMemHandle");
+}
+int emu_vit_tp_rows(const emu_vit* m, int* r0, int* r1) {
+    if (!m || !r0 || !r1) return -22;
+    *r0 = m->tp_r0; *r1 = m->tp_r1;
+    return 0;
+}
+
+int emu_vit_forward_tp(emu_vit* m, const void* image, int image_is_f32, void* out_tokens, void* workspace, size_t ws_bytes,
+                       emu_stream_t s_) {
+    if (!m || !image || !out_tokens || !m->wpatch) return -22;
+    emu_ctx* cx = m->ctx;
+    if (m->tp_world < 1) return fail(cx, -22, "emu_vit_forward_tp: emu_vit_set_token_parallel first");
+    if (m->fp8) return fail(cx, -22, "emu_vit_forward_tp: the fp8 blocks have no token-parallel form");
+    if (m->tp_world > 1 && !m->tp_emulate && !m->xchg) return fail(cx, -107, "emu_vit_forward_tp: exchange region not opened");
+    const emu_vit_cfg& c = m->cfg;
+    const VitWs w = vit_ws(m, 1, workspace);
+    if (w.total > ws_bytes) return fail(cx, -12, "emu_vit_forward_tp: workspace too small");
+    hipStream_t s = S(s_);
+    const int g = c.image_size / c.patch_size, T = g * g, N = T + 1, C = c.width;
+    int rows[EMU_P2P_MAX_RANKS + 1];
+    vit_token_rows(N, m->tp_world, rows);
+    const int r0 = rows[m->tp_rank], r1 = rows[m->tp_rank + 1];
+    EmuVitX* xg = m->tp_world > 1 && !m->tp_emulate ? m->xchg : nullptr;
+    bf16_t* x = B(out_tokens);
+    // stem: own patches only (token t > 0 is patch t - 1; the CLS row belongs to rank 0)
+    if (r1 > r0) {
+        TRY(cx, launch_patchify(image, image_is_f32, w.patches, 1, 3, c.image_size, c.patch_size, c.kpad, s));
+        const int p0 = std::max(r0, 1) - 1, p1 = r1 - 1;
+        if (p1 > p0)
+            TRY(cx, linear(w.patches + (size_t)p0 * c.kpad, m->wpatch, m->bpatch, nullptr, nullptr, w.pemb + (size_t)p0 * C, p1 - p0, C, c.kpad,
+                           c.kpad, c.kpad, 0, C, 0.f, EPI_NONE, s));
+        TRY(cx, launch_vit_assemble_rows(w.pemb, m->cls, m->pos, x, r0, r1, C, s));
+    }
+    const VitTp tp{r0, r1, rows, xg};
+    m->tp_r0 = r0; m->tp_r1 = r1;
+    TRY(cx, vit_blocks(m, x, 1, 0, c.layers, w, s, &tp));
+    // every rank ends with the same bytes: the final token rows are gathered once
+    if (xg) TRY(cx, emu_vitx_exchange(xg, rows, x, C, C, nullptr, 0, s));
+    return 0;
 }
 
 int emu_vit_blocks(emu_vit* m, void* tokens, int Bn, int l0, int l1, void* workspace, size_t ws_bytes, emu_stream_t s_) {

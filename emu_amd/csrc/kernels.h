@@ -206,6 +206,7 @@ int launch_patchify(const void* image, int image_is_f32, bf16_t* out, int B, int
 int launch_avgpool_tokens(const bf16_t* x, bf16_t* out, int B, int g, int C, int s, hipStream_t s_);
 // x[b, 0, :] = cls + pos[0]; x[b, 1+t, :] = patches[b, t, :] + pos[1+t]   (eva_vit.py:406-409)
 int launch_vit_assemble(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int B, int T, int C, hipStream_t s);
+int launch_vit_assemble_rows(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int t0, int t1, int C, hipStream_t s);  // one image, rows [t0, t1)
 
 // ---- attention (attention.hip)
 struct RopeKvArgs {
@@ -461,3 +462,12 @@ void emu_p2p_set_fenced(EmuP2p* p, int fenced);                        // 1 (def
 int emu_p2p_fenced(const EmuP2p* p);
 int emu_p2p_allreduce(EmuP2p* p, bf16_t* x, size_t n, hipStream_t s);  // in place; > one slot goes through in chunks
 unsigned int emu_p2p_giveups_read();
+// ViT token-row exchange (p2p.hip, emu_vit_forward_tp): every rank's exchange region holds two sets [A: a_elems | B: wb x ldb] bf16
+// + flags; one launch publishes my rows [rows[rank], rows[rank + 1]) of the token-major A and my 8-key groups of the token-minor B
+// (null: none) and pulls every peer's rows into my local A / B.  Same protocol, give-up counter and forms as the all-reduce.
+constexpr int VITX_PIECES = 64;
+struct EmuVitX;
+EmuVitX* emu_vitx_create(int rank, int n, size_t a_elems, int wb, int ldb, void* handle64_out);   // n >= 2; nullptr on failure
+int emu_vitx_open(EmuVitX* p, const void* handles, int timeout_ms, int fenced);
+void emu_vitx_destroy(EmuVitX* p);
+int emu_vitx_exchange(EmuVitX* p, const int* rows, bf16_t* a, int lda, int wa, bf16_t* b, int ldb, hipStream_t s);

@@ -69,7 +69,10 @@ class _Decoder:
 class EmuModel:
     def __init__(self, vision_cfg: CLIPVisionCfg = CLIPVisionCfg(), text_decoder_cfg: TextDecoderCfg = TextDecoderCfg(),
                  *, llama_cfg: Optional[LlamaCfg] = None, device="cuda", tp_rank: int = 0, tp_size: int = 1,
-                 ctx: Optional[EmuHipContext] = None):
+                 ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None):
+        """``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
+        parallelism a prompt with ONE image splits its ViT encode across the ranks by token rows (``encode_image``) instead of every
+        rank encoding the whole image.  Opt-in until a multi-GPU node has measured it."""
         from .vit import VitEngine
         self.vision_cfg, self.text_decoder_cfg = vision_cfg, text_decoder_cfg
         if llama_cfg is None:
@@ -89,6 +92,10 @@ class EmuModel:
         self.image_placeholder = DEFAULT_IMG_TOKEN + DEFAULT_IMAGE_TOKEN * self.n_query + DEFAULT_IMG_END_TOKEN
         self.video_placeholder = DEFAULT_IMG_TOKEN + DEFAULT_gIMG_TOKEN * self.v_query + DEFAULT_IMG_END_TOKEN
         self.use_graph = False
+        if vit_token_parallel is None:
+            vit_token_parallel = os.environ.get("EMU_VIT_TOKEN_PARALLEL", "0") == "1"
+        self.vit_token_parallel = bool(vit_token_parallel)
+        self._vit_tp_ready = False
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -146,11 +153,31 @@ class EmuModel:
 
         def enc(img):
             return ops.avgpool_tokens(self.visual(img), g, stride)    # [k, 1+g*g, C] -> [k, n_query, C]
+        # opt-in: ONE image is split across the tensor-parallel ranks by token rows (every rank returns the same tokens)
+        if self.ctx.tp_size > 1 and image.shape[0] == 1 and self.vit_token_parallel and self._image_parallel_ok():
+            self._init_vit_token_parallel()
+            tokens = self.visual.forward_token_parallel(image)
+            self.visual.check_exchange()
+            return ops.avgpool_tokens(tokens, g, stride)
         # tensor-parallel ranks split the IMAGES of a prompt between them (the ViT is replicated) and all-gather the pooled tokens
         if self.ctx.tp_size > 1 and image.shape[0] >= 2 and self._image_parallel_ok():
             from .tp import image_parallel_encode
             return image_parallel_encode(image, enc, self.ctx.tp_rank, self.ctx.tp_size, self._all_gather)
         return enc(image)
+
+    def _init_vit_token_parallel(self) -> None:
+        """First token-parallel encode (collective, like the encode itself): the exchange regions' IPC handles go round through
+        torch.distributed; the exchange takes the form the decoder's P2P all-reduce cleared (fence-free only after its soak)."""
+        if self._vit_tp_ready:
+            return
+        import torch.distributed as dist
+
+        def allgather(b):
+            box = [None] * dist.get_world_size()
+            dist.all_gather_object(box, b)
+            return box
+        self.visual.init_token_parallel(self.ctx.tp_rank, self.ctx.tp_size, allgather, fenced=not self.ctx.p2p_fence_free)
+        self._vit_tp_ready = True
 
     def _image_parallel_ok(self) -> bool:
         import torch.distributed as dist

@@ -86,6 +86,18 @@ class ShardPlan:
         return {"wqkv": wqkv, "wo": wo.contiguous(), "wgu": wgu, "wdown": wdown}
 
 
+def token_rows(N: int, rank: int, world: int):
+    """Token rows [r0, r1) rank ``rank`` of ``world`` computes in the token-parallel encode of one image (csrc/engine.hip:
+    vit_token_rows, emu_vit_forward_tp): the N rows are cut into ceil(N / 8) groups of 8 (the V^T epilogue stores 8-key groups),
+    rank r starting at group ceil(r * groups / world).  Contiguous, disjoint, covering, balanced to one group, row 0 (CLS) on
+    rank 0; a trailing rank may own no row (N = 17 at world 4: 8, 8, 1, 0), and still takes part in every exchange."""
+    if not (0 <= rank < world) or N < 1:
+        raise ValueError("token_rows: need 0 <= rank < world and N >= 1")
+    groups = (N + 7) // 8
+    at = lambda r: min(8 * ((r * groups + world - 1) // world), N)
+    return at(rank), at(rank + 1)
+
+
 def image_parallel_encode(images: torch.Tensor, encode, rank: int, world: int, all_gather):
     """Data-parallel ViT over the images of a prompt (BASELINE configs[2]: 4 images): instead of every
     tensor-parallel rank encoding all n images (the ViT is replicated: 8.7 GB), rank r encodes images r, r + world, ... and the

@@ -135,6 +135,66 @@ class VitEngine:
 
     __call__ = forward
 
+    # ------------------------------------------------------------------ token-parallel encode of one image (emu_vit_forward_tp)
+    def init_token_parallel(self, rank: int, world: int, allgather_bytes=None, timeout_ms: int = 0, fenced: bool = True,
+                            emulate: bool = False) -> None:
+        """Split one image's encode across ``world`` tensor-parallel ranks by token rows (emu_amd/tp.py::token_rows).  Every rank
+        calls it (``allgather_bytes(b: bytes) -> list[bytes]``, every rank's bytes in rank order, exchanges the IPC handles of the
+        exchange regions for world >= 2, as ``EmuHipContext._init_p2p`` does); ``fenced``: the exchange's form (False = the
+        fence-free form, only where the decoder's P2P soak passed).  ``emulate``: no exchange at all (tools/vit_sp_emulate.py:
+        one process times rank ``rank``'s shard; its output is right on this rank's rows only)."""
+        L = lib()
+        check(L.emu_vit_set_token_parallel(self.handle, int(rank), int(world), int(bool(emulate))), "emu_vit_set_token_parallel",
+              self.ctx.handle)
+        self.tp_rank, self.tp_world = int(rank), int(world)
+        if world < 2 or emulate:
+            return
+        if allgather_bytes is None:
+            raise ValueError("init_token_parallel: world >= 2 needs allgather_bytes to exchange the IPC handles")
+        h = (C.c_char * 64)()
+        ok = L.emu_vit_tp_create(self.handle, h) == 0
+        handles = allgather_bytes(bytes(h) if ok else b"")
+        if not all(len(x) == 64 for x in handles):
+            raise RuntimeError("token-parallel ViT: some rank could not export its exchange region")
+        buf = (C.c_char * (64 * world)).from_buffer_copy(b"".join(handles))
+        ok = L.emu_vit_tp_open(self.handle, buf, int(timeout_ms), int(bool(fenced))) == 0
+        if not all(x == b"1" for x in allgather_bytes(b"1" if ok else b"0")):   # also the barrier: every region is mapped
+            raise RuntimeError("token-parallel ViT: mapping the peers' exchange regions failed")
+
+    @torch.no_grad()
+    def forward_token_parallel(self, image: torch.Tensor) -> torch.Tensor:
+        """One image [1,3,H,W] -> tokens [1, 1+g*g, C] bf16, identical bytes on every rank; collective over the ranks of
+        ``init_token_parallel``.  This rank computes only its own rows (``rows_computed``)."""
+        c = self.cfg
+        if image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3 or image.shape[2] != c.image_size or image.shape[3] != c.image_size:
+            raise AssertionError(f"token-parallel encode takes one image of {c.image_size}*{c.image_size}, got {tuple(image.shape)}")
+        if not self.ready:
+            raise RuntimeError("ViT weights not fully loaded")
+        img = image.to(self.device)
+        if img.dtype not in (torch.float32, BF16):
+            img = img.float()
+        img = img.contiguous()
+        need = lib().emu_vit_workspace_bytes(self.handle, 1)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        out = torch.empty(1, c.tokens, c.width, device=self.device, dtype=BF16)
+        check(lib().emu_vit_forward_tp(self.handle, img.data_ptr(), int(img.dtype == torch.float32), out.data_ptr(),
+                                       self._ws.data_ptr(), self._ws.numel(), ops.stream(self.device)), "emu_vit_forward_tp",
+              self.ctx.handle)
+        return out
+
+    def check_exchange(self) -> None:
+        """Raise if a device-side wait of an exchange (or of the decoder's P2P all-reduce: the give-up counter is shared) ever timed
+        out: the tokens since then are invalid.  Synchronises with the device, so it runs outside any captured graph."""
+        if lib().emu_tp_p2p_giveups() != 0:
+            raise RuntimeError("token-parallel ViT: an exchange timed out waiting for a peer rank; the encoded tokens are invalid")
+
+    def rows_computed(self) -> Tuple[int, int]:
+        """Token rows [r0, r1) this rank computed in its last ``forward_token_parallel``."""
+        r0, r1 = C.c_int(), C.c_int()
+        check(lib().emu_vit_tp_rows(self.handle, C.byref(r0), C.byref(r1)), "emu_vit_tp_rows", self.ctx.handle)
+        return r0.value, r1.value
+
     # ------------------------------------------------------------------ optional W8A8 mode (BASELINE configs[4]: fp8 MFMA)
     def quantize_fp8(self) -> None:
         """Per-row-scaled e4m3fn copies of the four packed matrices of every block (the bf16 set stays resident: +4.3 GB for

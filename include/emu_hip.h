@@ -493,6 +493,23 @@ int emu_vit_forward(emu_vit* m, const void* image, int image_is_f32, int B, void
  * for l0 = 0, l1 = layers); the full-size tests compare every block on a common input.  Same workspace as emu_vit_forward. */
 int emu_vit_blocks(emu_vit* m, void* tokens, int B, int l0, int l1, void* workspace, size_t ws_bytes, emu_stream_t s);
 
+/* Token-parallel encode of ONE image across tensor-parallel ranks (emu_amd/vit.py: VitEngine.init_token_parallel): rank r computes
+ * token rows [r0, r1) of the stem and of every block (emu_amd/tp.py::token_rows: 8-row groups, CLS on rank 0, balanced; a trailing
+ * rank may own none).  Every rank holds the whole encoder; after each block's qkv projection the ranks exchange their K rows and
+ * V^T key columns over IPC-mapped exchange regions (csrc/p2p.hip, the one-shot all-reduce's protocol and give-up counter,
+ * emu_tp_p2p_giveups), attention runs over all N keys, and the final tokens are gathered once: every rank returns the same bytes.
+ * emu_vit_set_token_parallel: this rank and the world size (1 <= world <= 8); emulate != 0 skips every exchange (timing tools:
+ * only this rank's rows are right).  world >= 2: emu_vit_tp_create exports this rank's region (64-byte IPC handle), then
+ * emu_vit_tp_open maps every rank's (world x 64 bytes in rank order; timeout_ms bounds every wait, 0 = 10 s; fenced as
+ * emu_tp_p2p_set_fenced).  emu_vit_forward_tp is collective over the ranks and takes emu_vit_forward's workspace for B = 1;
+ * out_tokens [1+g*g, C].  The fp8 blocks have no token-parallel form: -22.  emu_vit_tp_rows: the rows the last call computed. */
+int emu_vit_set_token_parallel(emu_vit* m, int rank, int world, int emulate);
+int emu_vit_tp_create(emu_vit* m, void* handle64_out);
+int emu_vit_tp_open(emu_vit* m, const void* handles, int timeout_ms, int fenced);
+int emu_vit_forward_tp(emu_vit* m, const void* image, int image_is_f32, void* out_tokens, void* workspace, size_t ws_bytes,
+                       emu_stream_t s);
+int emu_vit_tp_rows(const emu_vit* m, int* r0, int* r1);
+
 /* ---- SDXL-style UNet denoise engine ---------------------------------------------------------------------
  * One call = one iteration of EmuVisualGeneration's denoising loop (Emu2/emu/diffusion.py:130-149):
  * cat([latents]*2) -> scheduler.scale_model_input -> UNet2DConditionModel (conf/diffusion_config/unet/config.json)
