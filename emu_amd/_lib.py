@@ -106,6 +106,9 @@ _PROTOS = {
     "emu_scatter_rows_bf16": (i32, [vp, vp, vp, i32, i32, vp]),
     "emu_argmax_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "emu_patchify": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "emu_image_resample_ws_bytes": (sz, [i32, i32, i32]),
+    "emu_image_resample_norm": (i32, [vp, lng, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp]),
+    "emu_image_to_u8_nhwc": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "emu_vit_assemble_bf16": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "emu_avgpool_tokens_bf16": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "emu_rope_kv_append_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -7,6 +7,7 @@ device list onto tensor parallelism instead of layer placement (one process per 
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Union
 
 import numpy as np
@@ -32,6 +33,17 @@ def image_transform(img, size: int = EVA_IMAGE_SIZE, mean=OPENAI_DATASET_MEAN, s
     m = torch.tensor(mean, dtype=torch.float32)[:, None, None]
     s = torch.tensor(std, dtype=torch.float32)[:, None, None]
     return (t - m) / s
+
+
+def gpu_preprocess_default(gpu_preprocess: Optional[bool]) -> bool:
+    """The ``gpu_preprocess`` option of the two pipelines: None reads ``EMU_GPU_PREPROCESS`` (off unless "1")."""
+    if gpu_preprocess is None:
+        gpu_preprocess = os.environ.get("EMU_GPU_PREPROCESS", "0") == "1"
+    return bool(gpu_preprocess)
+
+
+def _is_image(x) -> bool:
+    return hasattr(x, "resize") or isinstance(x, (np.ndarray, torch.Tensor))
 
 
 def prepare_inputs(inputs, transform=image_transform, image_placeholder: str = DEFAULT_IMG_PLACEHOLDER,
@@ -88,9 +100,18 @@ def prepare_chat_inputs(inputs, is_grounding: bool = False, transform=image_tran
 
 
 class EmuChatGeneration:
-    def __init__(self, emu_model, eva_size=EVA_IMAGE_SIZE, eva_mean=OPENAI_DATASET_MEAN, eva_std=OPENAI_DATASET_STD, **kwargs):
+    def __init__(self, emu_model, eva_size=EVA_IMAGE_SIZE, eva_mean=OPENAI_DATASET_MEAN, eva_std=OPENAI_DATASET_STD,
+                 gpu_preprocess: Optional[bool] = None, **kwargs):
+        """``gpu_preprocess`` (default: the ``EMU_GPU_PREPROCESS`` environment variable, off unless "1"): resize + normalise on the
+        device (emu_amd/preprocess.py; bit-identical to ``image_transform``, and the ViT stem reads the bf16 result as it reads the
+        rounded fp32 one).  Images may then also be uint8 [H, W, 3] numpy arrays or torch tensors (video decoders deliver those)."""
         self.emu_model = emu_model
-        self.transform = lambda img: image_transform(img, eva_size, eva_mean, eva_std)
+        self.gpu_preprocess = gpu_preprocess_default(gpu_preprocess)
+        if self.gpu_preprocess:
+            from .preprocess import GpuImageTransform
+            self.transform = GpuImageTransform(eva_size, eva_mean, eva_std, device=emu_model.device())
+        else:
+            self.transform = lambda img: image_transform(img, eva_size, eva_mean, eva_std)
 
     @torch.no_grad()
     def forward(self, inputs, is_grounding: bool = False, num_beams: int = 5, max_new_tokens: int = 10, min_len: int = 1,
@@ -104,7 +125,7 @@ class EmuChatGeneration:
             assert len(inputs) % 2 == 1, "last message must be user input"
             text, image, video = prepare_chat_inputs(inputs, is_grounding, self.transform)
         else:
-            assert all(isinstance(i, str) or hasattr(i, "resize") for i in inputs), \
+            assert all(isinstance(i, str) or hasattr(i, "resize") or (self.gpu_preprocess and _is_image(i)) for i in inputs), \
                 "input can't be list of list for normal generation"
             text, image, video = prepare_inputs(inputs, self.transform)
         dev = self.emu_model.device()

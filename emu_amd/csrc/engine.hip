@@ -402,6 +402,16 @@ int emu_argmax_bf16(const void* logits, int ld, int rows, int vocab, int suppres
 int emu_patchify(const void* image, int image_is_f32, void* out, int Bn, int C, int HW, int patch, int Kpad, emu_stream_t s) {
     return launch_patchify(image, image_is_f32, B(out), Bn, C, HW, patch, Kpad, S(s));
 }
+size_t emu_image_resample_ws_bytes(int H, int W, int Sz) { return image_resample_ws_bytes(H, W, Sz); }
+int emu_image_resample_norm(const uint8_t* src, long pitch, int H, int W, const int32_t* hcoef, const int32_t* hbounds, int hk,
+                            const int32_t* vcoef, const int32_t* vbounds, int vk, int row0, int nrows, const float* lut, void* out,
+                            int out_is_f32, int Sz, void* ws, size_t ws_bytes, emu_stream_t s) {
+    ImageResampleArgs a{src, pitch, H, W, hcoef, hbounds, hk, vcoef, vbounds, vk, row0, nrows, lut, out, out_is_f32, Sz, ws, ws_bytes};
+    return launch_image_resample_norm(a, S(s));
+}
+int emu_image_to_u8_nhwc(const void* x, uint8_t* out, int N, int C, int H, int W, emu_stream_t s) {
+    return launch_image_to_u8(B(x), out, N, C, H, W, S(s));
+}
 int emu_vit_assemble_bf16(const void* patches, const void* cls, const void* pos, void* x, int Bn, int T, int C, emu_stream_t s) {
     return launch_vit_assemble(B(patches), B(cls), B(pos), B(x), Bn, T, C, S(s));
 }

@@ -208,6 +208,30 @@ int launch_avgpool_tokens(const bf16_t* x, bf16_t* out, int B, int g, int C, int
 int launch_vit_assemble(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int B, int T, int C, hipStream_t s);
 int launch_vit_assemble_rows(const bf16_t* patches, const bf16_t* cls, const bf16_t* pos, bf16_t* x, int t0, int t1, int C, hipStream_t s);  // one image, rows [t0, t1)
 
+// ---- image front / back end (image.hip)
+struct ImageResampleArgs {
+    const uint8_t* src;     // [H, W, 3] interleaved, rows `pitch` bytes apart
+    long pitch;
+    int H, W;
+    const int32_t* hcoef;   // [S, hk] horizontal coefficients (22 fractional bits); unused when W == S
+    const int32_t* hbounds; // [S, 2]  first tap, tap count
+    int hk;
+    const int32_t* vcoef;   // [S, vk], [S, 2]; unused when H == S
+    const int32_t* vbounds;
+    int vk;
+    int row0, nrows;        // source rows the vertical pass reads: [row0, row0 + nrows)
+    const float* lut;       // [3, 256] ToTensor + Normalize
+    void* out;              // [3, S, S] bf16 or fp32
+    int out_is_f32;
+    int S;
+    void* ws;               // image_resample_ws_bytes(H, W, S)
+    size_t ws_bytes;
+};
+size_t image_resample_ws_bytes(int H, int W, int S);
+int launch_image_resample_norm(const ImageResampleArgs& a, hipStream_t s);
+// bf16 [N, C, H, W] in [0, 1] -> uint8 [N, H, W, C] = rint(x * 255) (C <= 4)
+int launch_image_to_u8(const bf16_t* x, uint8_t* out, int N, int C, int H, int W, hipStream_t s);
+
 // ---- attention (attention.hip)
 struct RopeKvArgs {
     bf16_t* qkv;            // [B*T, 3*Hl*D] rows; q at col 0, k at Hl*D, v at 2*Hl*D  (q, k rotated in place)

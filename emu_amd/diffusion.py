@@ -15,7 +15,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .chat import image_transform
+from .chat import gpu_preprocess_default, image_transform
 from .conf.emu_conf import CLIPVisionCfg, TextDecoderCfg
 from .constants import DEFAULT_IMG_PLACEHOLDER, EVA_IMAGE_SIZE, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
 from .unet import UNetCfg, UNetEngine
@@ -32,17 +32,26 @@ class EmuVisualGenerationPipelineOutput:
 
 class EmuVisualGeneration:
     def __init__(self, multimodal_encoder, unet: UNetEngine, vae: VaeDecoder, eva_size=EVA_IMAGE_SIZE,
-                 eva_mean=OPENAI_DATASET_MEAN, eva_std=OPENAI_DATASET_STD, safety_checker=None, **kwargs):
+                 eva_mean=OPENAI_DATASET_MEAN, eva_std=OPENAI_DATASET_STD, safety_checker=None,
+                 gpu_preprocess: Optional[bool] = None, **kwargs):
         """``safety_checker``: optional callable ``(images float32 [N, H, W, 3] in [0, 1]) -> (images, [bool] * N)`` run on
         the decoded images, the hook for the reference's StableDiffusionSafetyChecker stage (diffusion.py:154-166,236-249;
         a CLIP classifier outside the hot path, not rebuilt here).  None = no filter: ``nsfw_content_detected`` is None and
-        nothing is blacked out -- a checkpoint that carries ``safety_checker.*`` weights triggers a warning at load."""
+        nothing is blacked out -- a checkpoint that carries ``safety_checker.*`` weights triggers a warning at load.
+        ``gpu_preprocess`` (default: the ``EMU_GPU_PREPROCESS`` environment variable, off unless "1"): the input images are resized
+        and normalised on the device, and without a ``safety_checker`` the decoded image leaves the device as uint8 NHWC bytes
+        (emu_amd/preprocess.py); both are bit-identical to the host path."""
         self.multimodal_encoder = multimodal_encoder
         self.unet = unet
         self.vae = vae
         self.safety_checker = safety_checker
         self.vae_scale_factor = 2 ** (len(vae.cfg.block_out_channels) - 1)
-        self.transform = lambda img: image_transform(img, eva_size, eva_mean, eva_std)
+        self.gpu_preprocess = gpu_preprocess_default(gpu_preprocess)
+        if self.gpu_preprocess:
+            from .preprocess import GpuImageTransform
+            self.transform = GpuImageTransform(eva_size, eva_mean, eva_std, device=multimodal_encoder.ctx.device)
+        else:
+            self.transform = lambda img: image_transform(img, eva_size, eva_mean, eva_std)
         self.negative_prompt = {}                   # "" / "[NULL_IMAGE]" -> embeds, computed once (diffusion.py:197-210)
         self.use_graph = True
         # classifier-free guidance split over ranks 0 and 1 (``enable_cfg_split``; SURVEY 8e): a single image's denoise loop then
@@ -137,6 +146,12 @@ class EmuVisualGeneration:
         prompt_embeds = self._prepare_and_encode_inputs(inputs, do_cfg).to(self.device(), BF16)
         latents = self.generate_latents(prompt_embeds, height, width, num_inference_steps, guidance_scale, crop_info,
                                         original_size)
+        if self.gpu_preprocess and self.safety_checker is None:      # bytes in their final layout leave the device
+            from PIL import Image
+            from .preprocess import to_uint8_hwc
+            u8 = to_uint8_hwc(self.vae.decode_latents(latents).contiguous()).cpu().numpy()
+            return EmuVisualGenerationPipelineOutput(image=Image.fromarray(u8[0].squeeze(-1) if u8.shape[-1] == 1 else u8[0]),
+                                                     nsfw_content_detected=None)
         images = self.decode_latents(latents)
         nsfw = None
         if self.safety_checker is not None:                          # diffusion.py:154-166 (run_safety_checker)

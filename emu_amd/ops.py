@@ -351,3 +351,35 @@ def gemv_chain(ctx_handle, specs, err: Optional[torch.Tensor] = None):
         err = torch.zeros(1, device=dev, dtype=torch.int32)
     check(lib().emu_gemv_chain_bf16(ctx_handle, arr, n, gran.data_ptr(), gran.numel(), err.data_ptr(), stream(dev)), "emu_gemv_chain_bf16")
     return outs, err, (gran, keep)
+
+
+def image_resample_norm(src, plan, lut, out, ws=None):
+    """emu_image_resample_norm: src uint8 [H, W, 3] (unit pixel / channel strides, any row pitch) -> out [3, S, S] bf16 or fp32 =
+    Normalize(ToTensor(PIL bicubic resize)), bit-exact.  ``plan``: the device tables (emu_amd.preprocess.ResamplePlan); launch only."""
+    _req(src, "src", torch.uint8)
+    if src.dim() != 3 or src.shape[2] != 3 or src.stride(1) != 3 or tuple(src.shape[:2]) != (plan.h, plan.w):
+        raise ValueError(f"src must be uint8 [{plan.h}, {plan.w}, 3] with interleaved pixels, got {tuple(src.shape)} strides {src.stride()}")
+    if out.dtype not in (BF16, torch.float32) or not out.is_cuda or not out.is_contiguous() or out.dim() != 3 \
+            or out.shape[0] != 3 or out.shape[1] != out.shape[2]:
+        raise ValueError("out must be a contiguous GPU [3, S, S] tensor, bf16 or fp32")
+    _req(lut, "lut", torch.float32)
+    if ws is not None:
+        _req(ws, "ws", torch.uint8)
+    check(lib().emu_image_resample_norm(_p(src), src.stride(0), plan.h, plan.w, _p(plan.hcoef), _p(plan.hbounds), plan.hk,
+                                        _p(plan.vcoef), _p(plan.vbounds), plan.vk, plan.row0, plan.nrows, _p(lut), _p(out),
+                                        int(out.dtype == torch.float32), out.shape[1], _p(ws), ws.numel() if ws is not None else 0,
+                                        stream(src)), "emu_image_resample_norm")
+    return out
+
+
+def image_to_u8_nhwc(x, out=None):
+    """emu_image_to_u8_nhwc: bf16 [N, C, H, W] in [0, 1] -> uint8 [N, H, W, C] = rint(x * 255)."""
+    _req(x, "x")
+    if x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [N, C, H, W] tensor")
+    N, Cc, H, W = x.shape
+    if out is None:
+        out = torch.empty(N, H, W, Cc, device=x.device, dtype=torch.uint8)
+    _req(out, "out", torch.uint8)
+    check(lib().emu_image_to_u8_nhwc(_p(x), _p(out), N, Cc, H, W, stream(x)), "emu_image_to_u8_nhwc")
+    return out

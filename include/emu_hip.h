@@ -251,6 +251,26 @@ int emu_argmax_bf16(const void* logits, int ld, int rows, int vocab, int suppres
 /* PatchEmbed conv as im2col (eva_vit.py:327-335): image NCHW (fp32 or bf16) -> [B*g*g, Kpad] bf16 */
 int emu_patchify(const void* image, int image_is_f32, void* out, int B, int C, int HW, int patch, int Kpad,
                  emu_stream_t s);
+/* Image front end: torchvision Resize((S, S), BICUBIC) -> ToTensor -> Normalize of one uint8 RGB image (Emu2/emu/chat.py:35-39,
+ * Emu2/emu/diffusion.py:58-63), bit-exact with Pillow's 8-bit resample.  src [H, W, 3] interleaved on the device, rows `pitch` bytes
+ * apart.  hcoef / vcoef int32 [S, hk] / [S, vk] (22 fractional bits) and hbounds / vbounds int32 [S, 2] (first tap, tap count) are
+ * Pillow's precompute_coeffs + normalize_coeffs_8bpc tables (emu_amd/preprocess.py::resample_coeffs); the vertical pass reads source
+ * rows [row0, row0 + nrows) = [vbounds[0][0], vbounds[S-1][0] + vbounds[S-1][1]) and the horizontal pass is made over those rows only.
+ * A pass whose input size equals S is skipped and its tables may be NULL.  lut fp32 [3, 256] = (v / 255 - mean[c]) / std[c];
+ * out = image [3, S, S] of an [N, 3, S, S] batch, bf16 (round to nearest even of the table value) or fp32.  ws: at least
+ * emu_image_resample_ws_bytes.  No allocation, no synchronisation: capturable.  -22: H or W above EMU_IMAGE_MAX_SIDE, S above
+ * EMU_IMAGE_MAX_OUT, more than EMU_IMAGE_MAX_TAPS taps, pitch < 3 * W, rows outside the image, a workspace too small. */
+#define EMU_IMAGE_MAX_SIDE 16384
+#define EMU_IMAGE_MAX_OUT 4096
+#define EMU_IMAGE_MAX_TAPS 1024
+size_t emu_image_resample_ws_bytes(int H, int W, int S);
+int emu_image_resample_norm(const uint8_t* src, long pitch, int H, int W, const int32_t* hcoef, const int32_t* hbounds, int hk,
+                            const int32_t* vcoef, const int32_t* vbounds, int vk, int row0, int nrows, const float* lut, void* out,
+                            int out_is_f32, int S, void* ws, size_t ws_bytes, emu_stream_t s);
+/* Image back end: numpy_to_pil's (images * 255).round().astype("uint8") (Emu2/emu/diffusion.py:214-234) on the decoded image while
+ * it is still on the device: x bf16 [N, C, H, W] with values in [0, 1] -> out uint8 [N, H, W, C] = rint(float(x) * 255.0f), round
+ * half to even (values outside [0, 1] saturate).  C <= 4.  -22: sizes out of range. */
+int emu_image_to_u8_nhwc(const void* x, uint8_t* out, int N, int C, int H, int W, emu_stream_t s);
 /* cat(cls, patches) + pos_embed (eva_vit.py:406-409) */
 int emu_vit_assemble_bf16(const void* patches, const void* cls, const void* pos, void* x, int B, int T, int C,
                           emu_stream_t s);
