@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -16,6 +17,7 @@
 
 struct emu_ctx {
     int device = 0, tp_rank = 0, tp_size = 1;
+    int ncu = 0;                                    // compute units of the device (0: the query failed; the persistent engine stays off)
     ncclComm_t comm = nullptr;
     EmuP2p* p2p = nullptr;                          // one-shot all-reduce blocks (p2p.hip); used only once enabled
     bool p2p_on = false;
@@ -56,6 +58,23 @@ struct LaunchProfiler {
     hipEvent_t cur_a = nullptr, cur_b = nullptr;
 } g_lprof;
 
+// a weight-streaming launch between a HIP-event pair of the GEMV profiler when that is on
+template <class Launch>
+int gemv_profiled(double weight_bytes, hipStream_t s, Launch launch) {
+    if (!g_prof.on) return launch();
+    if (g_prof.used == g_prof.ev.size()) {
+        hipEvent_t a, b;
+        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -12;
+        g_prof.ev.emplace_back(a, b);
+    }
+    auto& e = g_prof.ev[g_prof.used++];
+    g_prof.bytes += weight_bytes;
+    (void)hipEventRecord(e.first, s);
+    const int st = launch();
+    (void)hipEventRecord(e.second, s);
+    return st;
+}
+
 int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* res, const bf16_t* norm_w,
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
            const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0) {
@@ -67,18 +86,7 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     // A/B aid (emu_gemm_tune bit 2): 2..32 rows without a fused norm go through the thin MFMA tile instead
     if (M <= 8 || skinny) {
         GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, wscale};
-        if (!g_prof.on) return launch_gemv(g, s);
-        if (g_prof.used == g_prof.ev.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -12;
-            g_prof.ev.emplace_back(a, b);
-        }
-        auto& e = g_prof.ev[g_prof.used++];
-        g_prof.bytes += (wscale ? 1.0 : 2.0) * (double)N * (double)K;
-        (void)hipEventRecord(e.first, s);
-        const int st = launch_gemv(g, s);
-        (void)hipEventRecord(e.second, s);
-        return st;
+        return gemv_profiled((wscale ? 1.0 : 2.0) * (double)N * (double)K, s, [&] { return launch_gemv(g, s); });
     }
     if (norm_w) return -22;
     GemmArgs g{A, W, bias, res, C, M, N, K, lda, ldw, ldres, ldc, epi, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
@@ -87,18 +95,14 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
-    if (!g_prof.on) return launch_gemv_merge(g, s);
-    if (g_prof.used == g_prof.ev.size()) {
-        hipEvent_t a, b;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -12;
-        g_prof.ev.emplace_back(a, b);
-    }
-    auto& e = g_prof.ev[g_prof.used++];
-    g_prof.bytes += 2.0 * (double)g.N * (double)g.K;
-    (void)hipEventRecord(e.first, s);
-    const int st = launch_gemv_merge(g, s);
-    (void)hipEventRecord(e.second, s);
-    return st;
+    return gemv_profiled(2.0 * (double)g.N * (double)g.K, s, [&] { return launch_gemv_merge(g, s); });
+}
+// the wait bound and loader waves of a persistent-engine launch (decode_engine.hip): 2 s and the kernel's default, unless the tool
+// switches EMU_ENGINE_TIMEOUT_MS / EMU_ENGINE_LOADERS (tools/README.md) say otherwise
+void engine_tool_switches(EngArgs& a) {
+    a.limit_ticks = 200000000LL;
+    if (const char* e = getenv("EMU_ENGINE_TIMEOUT_MS")) { const long ms = atol(e); if (ms > 0) a.limit_ticks = ms * 100000LL; }
+    if (const char* e = getenv("EMU_ENGINE_LOADERS")) a.nload = atoi(e);
 }
 }  // namespace
 
@@ -204,6 +208,7 @@ int emu_ctx_create(int device, int tp_rank, int tp_size, emu_ctx** out) {
     if (e != hipSuccess || device < 0 || device >= n) return e != hipSuccess ? (int)e : -19;
     emu_ctx* c = new emu_ctx();
     c->device = device; c->tp_rank = tp_rank; c->tp_size = tp_size;
+    if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); c->ncu = 0; }
     *out = c;
     return 0;
 }
@@ -357,13 +362,11 @@ int emu_gemv_chain_bf16(emu_ctx* ctx, const emu_chain_op* ops, int nops, void* g
     if (need > granule_bytes || (need && !granules)) return fail(ctx, -12, "emu_gemv_chain_bf16: granule buffer too small");
     hipStream_t s = S(s_);
     EngArgs a{};
-    a.nops = nops; a.err = err; a.limit_ticks = 200000000LL;           // 2 s
-    if (const char* e = getenv("EMU_ENGINE_TIMEOUT_MS")) { const long ms = atol(e); if (ms > 0) a.limit_ticks = ms * 100000LL; }   // tools
-    if (const char* e = getenv("EMU_ENGINE_LOADERS")) a.nload = atoi(e);
+    a.nops = nops; a.err = err;
+    engine_tool_switches(a);
     if (const char* e = getenv("EMU_ENGINE_DBG")) a.dbg = atoi(e);
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -5;
-    a.ncu = ncu;
+    if (ctx->ncu < 1) return -5;
+    a.ncu = ctx->ncu;
     char* gp = reinterpret_cast<char*>(granules);
     size_t off = 0;
     for (int i = 0; i < nops; ++i) {
@@ -562,139 +565,447 @@ int linear_then_rmsnorm(const LlamaWs& w, const bf16_t* A, const bf16_t* W, cons
     return launch_rmsnorm(C, gain, xn, M, N, N, N, eps, s);
 }
 
-// ---- Tensor-parallel prefill of a long prompt as TWO CONCURRENT LANES (SURVEY 8e / north_star: "all-reduce overlapped with the
-// next GEMM"; replaces the serial schedule of the loop in emu_llama_forward).  The prompt's rows are cut once, at a multiple of 256
-// (whole 256-row GEMM tiles and whole 64-key attention tiles below the cut), into A = [0, Ma) and B = [Ma, M).  Causal attention
-// makes A independent of B, and B needs nothing of A but its keys / values of the SAME layer, so each half walks all layers as its
-// own chain
-//     [RMSNorm, qkv (+ RoPE / KV append / V^T), attention, o_proj] -> all-reduce -> [RMSNorm, gate/up + SwiGLU, down] -> all-reduce
-// on its own stream: A on the caller's, B on cx->lane_stream, one event per layer (A's K / V rows are in the cache) the only edge
-// between them.  While one lane's partial sums are on the wire the other lane's GEMMs have the CUs, and where both lanes compute,
-// their launches (a TP = 8 shard's GEMM over 772 rows is 30-odd tiles on 256 CUs) share the chip instead of queueing behind each
-// other.  A first version kept ONE compute stream and interleaved the halves stage by stage with every all-reduce on a side
-// stream: +43 % per rank on one GPU (profiles/r05_tp_prefill_two_half_v1_single_compute_stream.log) -- half-size launches back to
-// back leave most of the chip idle, and every all-reduce cost two cross-stream edges.  All-reduces run in their lane's stream
-// where RCCL takes them (one communicator, calls in one host order on every rank); on a context without a communicator (rank
-// processes sharing a device: validation) every peer-to-peer all-reduce additionally waits for the one issued before it in
-// either lane, because the comm blocks serve one all-reduce at a time.  Lane B keeps its own V^T buffer (A's keys transposed from the cache + its own columns
-// from the epilogue) and K-slice scratch, so no buffer is written by one lane while the other reads it.  Same kernels and
-// rounding points as the serial schedule; a half may take another GEMM tile configuration than the whole prompt (K-slice sums in
-// another order), so the schedules agree to bf16 rounding, not bit for bit.  Capturable: lane_stream forks from and joins the
-// caller's stream through events.
-int llama_prefill_lanes(emu_llama* m, const LlamaWs& w, bf16_t* hA, int M, const int32_t* pos, const int32_t* slot,
-                        const int32_t* kstart, bool fuse_rope, hipStream_t s) {
-    emu_ctx* cx = m->ctx;
-    const emu_llama_cfg& c = m->cfg;
-    const int H = c.hidden, Hl = c.heads_local, D = c.head_dim, HD = Hl * D, Fl = c.ffn_local;
-    const int epi_res = cx->tp_rank == 0 ? EPI_RESID : EPI_NONE;        // the residual enters the all-reduce once
-    const float scale = 1.0f / sqrtf((float)D);
-    const size_t kv_layer = (size_t)Hl * m->s_max * D;                  // one batch element
-    const int spad = (M + 63) / 64 * 64;
-    const int l_end = m->l1 < 0 ? c.layers : m->l1;
-    if (l_end <= m->l0) return 0;
-    int Ma = (M / 2 + 128) / 256 * 256;
-    if (Ma < 256) Ma = 256;
-    if (Ma > M - 256) Ma = (M - 256) / 256 * 256;
-    const int r0[2] = {0, Ma}, rows[2] = {Ma, M - Ma};
-    hipStream_t lane[2] = {s, cx->lane_stream};
-    bf16_t* vt[2] = {w.vt, w.vt2};
-    float* sk[2] = {w.splitk, w.splitk2};
-    hipEvent_t eStart = cx->ar_ev[0], eKV = cx->ar_ev[1];              // (ar_ev[2]: the join in llama_prefill_overlapped)
-    hipEvent_t* ePrev = cx->ar_ev + 3;   // [lane]  the lane's latest peer-to-peer all-reduce is through (an event is only ever recorded on
-    int prev_lane = -1;                  //         ONE stream: one event recorded on both streams of a capture crashed hipGraphInstantiate)
-#define HIPTRY(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(cx, -5, #expr); } } while (0)
-    auto lane_allreduce = [&](int h, bf16_t* buf, size_t n) -> int {
-        const bool by_rccl = cx->comm && !(cx->p2p_on && n * sizeof(bf16_t) <= EMU_P2P_SLOT_BYTES);   // emu_allreduce_bf16's own choice
-        if (by_rccl) return emu_allreduce_bf16(cx, buf, n, reinterpret_cast<emu_stream_t>(lane[h]));
-        // the comm blocks serve ONE all-reduce at a time: every peer-to-peer all-reduce waits for the one issued before it (host order,
-        // the same on every rank), whichever lane that was in
-        if (prev_lane >= 0 && prev_lane != h) HIPTRY(hipStreamWaitEvent(lane[h], ePrev[prev_lane], 0));
-        TRY(cx, emu_allreduce_bf16(cx, buf, n, reinterpret_cast<emu_stream_t>(lane[h])));
-        HIPTRY(hipEventRecord(ePrev[h], lane[h]));
-        prev_lane = h;
-        return 0;
-    };
-    HIPTRY(hipEventRecord(eStart, s));                                   // inputs (and whatever the caller queued before) are ready
-    HIPTRY(hipStreamWaitEvent(lane[1], eStart, 0));
-    for (int l = m->l0; l < l_end; ++l) {
+// ---- one emu_llama_forward call.  LlamaPlan: which schedule runs it and what that schedule fuses -- pick_path decides; the one
+// later change is layer_kv's demotion of fuse_rope when the GEMM refuses the epilogue (-95).  LlamaCall: the arguments and derived sizes every routine of the call shares, and one routine per schedule.
+enum class LlamaPath { Launches, Engine, FusedLayers, FusedCutAtAllReduce, FusedTailAllReduce, TwoLane };
+struct LlamaPlan {
+    LlamaPath path;
+    // fuse_rope      the qkv GEMM's epilogue rotates q / k, appends k / v and writes V^T (demoted for the rest of the call on -95)
+    // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
+    // fp8_rows       1..2 rows stream the fp8 weight set (decode)
+    // fp8_gemm       prefill rows run W8A8 GEMMs in the layers that have fp8 weights
+    // norm_in_gemv   one row, or two with fp8 weights: the weight stream applies the RMSNorm in front of it itself
+    // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
+    // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
+    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, norm_in_gemv, decode_tail, merge_o;
+    // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
+    // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
+    DecodeLayersArgs dl; EngArgs eng;
+};
+// a window of the call's rows that one stream walks through a layer: every row on the caller's stream (run_launches), or one
+// lane's half of a long prompt (llama_prefill_lanes)
+struct RowWindow {
+    int r0, T, kend;                             // first row; rows per batch element; the window's last row sees keys [0, kend)
+    hipStream_t s;
+    LlamaWs w;                                   // the call's buffers at row r0; V^T and the K-slice scratch are the window's own
+    bf16_t* x; const int32_t *pos, *slot;        // the residual stream and the rows' positions / cache slots, at row r0
+    std::function<int(bf16_t*, size_t)> allreduce;   // sums partial rows over the ranks, in the window's stream
+};
+using LaneHook = std::function<int()>;           // what a schedule issues between two launches of the layer body (events of the two lanes)
+struct ProjWeights { const bf16_t* W; const uint8_t* W8; const float* s8; };   // bf16 weight; fp8 weight + per-row scale, or nulls
+struct LlamaCall {
+    emu_llama* m; emu_ctx* cx; LlamaWs ws; hipStream_t s;
+    bf16_t* hA;                                  // the residual stream, [M, H]
+    const int32_t *pos, *slot, *kstart;
+    int Bn, T, M, ctx, H, Hl, D, HD, Fl, spad, l_end;
+    bool tp;                                     // a 1-rank communicator / comm block still runs the all-reduces (tests, tools/tp_emulate.py)
+    int epi_res;                                 // the residual enters the all-reduce once: rank 0 adds it
+    float scale, eps; size_t kv_layer;
+    LlamaPlan plan;
+    bool xn_ready;                               // the down projection of the layer before left this layer's normalised rows in w.xn
+
+    // Decides the call's schedule and fusions; launches, zeroes and uploads nothing.  Precedence: the engine, whole layers per launch,
+    // the two-lane prefill, the per-layer launches -- a schedule whose guard fails falls through to the next.
+    void pick_path(bool promise) {
+        LlamaPlan& p = plan = LlamaPlan{};
+        p.path = LlamaPath::Launches;                  // unless a schedule below takes the call
+        const bool own_kv = m->kv_share_nb <= 1, some_layers = l_end > m->l0;
+        // the caller promised (emu_llama_set_prefill_fusion) that the rows of the one batch element are the whole context in slot
+        // order, slot[i] = i.  The promise is per call: emu_llama_forward consumed it, so a later forward with rows in another slot
+        // order (any caller that did not renew it) runs the unfused sequence, which honours slot[] everywhere.
+        const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv;
+        // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
+        // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
+        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255);
+        // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
+        // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
+        // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
+        // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
+        // with B * beams > 16) keep the fused path they had before the promise became one-shot.
+        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill;
+        p.fp8_rows = m->fp8_decode && M <= 2;
+        // prefill with the fp8 weight set: activations are quantised per row ahead of every GEMM, the block-scaled MFMA
+        // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
+        p.fp8_gemm = m->fp8_prefill && M > 16 && !(H & 127) && !(HD & 127) && !(Fl & 127);
+        p.norm_in_gemv = p.fp8_rows || M == 1;
+        p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
+        // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
+        // itself, no combine launch (gemv_merge.hip).  Bit-identical and measured LEVEL with the two launches (3.15 vs 3.15-3.18 ms
+        // per token of a TP = 8 shard, profiles/r05_tp_emulate_merged_o_proj.log): the merge is a dependent L2 trip inside the
+        // projection, which is what the combine launch cost -- one launch less buys nothing here, like the in-kernel split merge
+        // and the tail all-reduce before it
+        p.merge_o = T == 1 && M == 1 && !p.fp8_rows && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
+                    (emu_gemm_tune_get() & (1 << 19)) != 0;
+
+        const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && own_kv && some_layers;
+        // the fence-free peer-to-peer all-reduce is on (which implies tensor parallelism and an opened cx->p2p): what the all-reduces
+        // inside a launch build on
+        const bool p2p_fence_free = cx->p2p_on && emu_p2p_fenced(cx->p2p) == 0;
+        // ---- the persistent weight-streaming engine (mode 4; run_engine).  Tensor-parallel shards with rows of at most 13 KiB (TP >= 4)
+        // whose ranks have the device to themselves; anything else takes the launches.
+        if (m->decode_fused == 4 && one_row_bf16 && m->eng_gran && m->dl_err && p2p_fence_free && H <= 6656 && HD <= 6656 && Fl <= 6656 &&
+            !(H & 7) && !(Fl & 7) && emu_p2p_engine_view(cx->p2p, p.eng.comm, &p.eng.seq, &p.eng.tp_n, &p.eng.tp_rank) && cx->ncu > 0 &&
+            3 * HD >= 2 * cx->ncu && H >= 2 * cx->ncu && Fl >= cx->ncu && cx->ncu <= 1024) { p.path = LlamaPath::Engine; return; }
+        // ---- whole layers per launch (modes 1 to 3; run_fused_layers)
+        if (m->decode_fused && m->decode_fused != 4 && one_row_bf16 && m->dl_cnt) {
+            DecodeLayersArgs& d = p.dl;
+            d.H = H; d.Hl = Hl; d.Fl = Fl;
+            bool ok = decode_layers_ok(d);
+            // wait bound: 2 s of wall clock (100 MHz ticks), or the peer-to-peer time-out where that is longer -- rank processes that SHARE
+            // a GPU (validation runs) are time-sliced against each other, and a wave that is switched out keeps its start time: the 0.2 s
+            // of the first version ran out under eight ranks on one device (garbage from step 4 on, give-ups counted)
+            d.limit_ticks = 200000000LL;
+            // tensor parallelism: mode 2 runs the all-reduces inside the launch over the P2P comm blocks (every rank on its own GPU); mode 1
+            // cuts every layer at its two all-reduces -- [q, attention, o_proj] | all-reduce | [gate/up, down] | all-reduce -- which also
+            // serves RCCL and ranks that share a GPU (a launch that waits for a peer must not hold the CUs the peer needs); mode 3 leaves
+            // each all-reduce to the last workgroup of the projection's launch, and falls back to the cut where that is not available
+            bool in_kernel_ar = false, tail_ar = false;
+            if (ok && tp && cx->p2p) {
+                long long lim = 0; int n = 0;
+                const bool view = emu_p2p_view(cx->p2p, d.tp_block, &d.tp_seq, &n, &d.tp_rank, &lim);
+                in_kernel_ar = view && p2p_fence_free && m->decode_fused == 2;       // the in-launch all-reduce is the fence-free form only
+                tail_ar = view && p2p_fence_free && m->decode_fused == 3;
+                if (view && lim > d.limit_ticks) d.limit_ticks = lim;  // a lagging peer holds every downstream wait: the peer bound applies
+                d.tp_n = in_kernel_ar ? n : 0;
+                ok = decode_layers_ok(d);
+                if (tail_ar) d.tp_n = n;                               // (launch_decode_layers checks the shape for the launches that all-reduce)
+            }
+            if (ok) p.path = tail_ar ? LlamaPath::FusedTailAllReduce : tp && !in_kernel_ar ? LlamaPath::FusedCutAtAllReduce : LlamaPath::FusedLayers;
+            if (ok) return;
+        }
+        // ---- long prompt under tensor parallelism: two row halves, every all-reduce behind the other half's GEMMs (needs the slot-order
+        // promise: the rows of the one batch element are the whole context in order, so the first half never reads the second's keys)
+        if (tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
+            p.path = LlamaPath::TwoLane;
+    }
+
+    // One projection of a layer, C = epi(A W^T [+ res]): qkv, o_proj, gate/up and down all come through here.  pw holds the fp8 weight
+    // only where the plan's fp8 form applies to the layer.  gain_in: the RMSNorm in front, fused into a one-row weight stream;
+    // gain_out: w.xn = RMSNorm(C) * gain_out behind the K-slice sums.
+    int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
+                const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
+        const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
+        if (pw.W8 && plan.fp8_rows) return linear(A, B(pw.W8), nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, gain_in ? eps : 0.f, epi, s, pw.s8);
+        if (pw.W8) return linear_q8(w, A, K, pw.W8, pw.s8, res, C, rows, N, K, ldres, ldc, epi, s);
+        if (gain_in) return linear(A, pw.W, nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, eps, epi, s);
+        if (gain_out) return linear_then_rmsnorm(w, A, pw.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
+        return linear(A, pw.W, nullptr, res, nullptr, C, rows, N, K, K, K, ldres, ldc, 0.f, epi, s, nullptr, w.splitk, w.splitk_floats);
+    }
+
+    RowWindow window(int r0, int T, int kend, hipStream_t s, bf16_t* vt, float* splitk) {
+        LlamaWs w = ws;
+        w.hB += (size_t)r0 * H; w.xn += (size_t)r0 * H; w.qkv += (size_t)r0 * 3 * HD; w.attn += (size_t)r0 * HD; w.act += (size_t)r0 * Fl;
+        w.vt = vt; w.splitk = splitk;
+        return RowWindow{r0, T, kend, s, w, hA + (size_t)r0 * H, pos + r0, slot + r0, nullptr};
+    }
+    // the fp8 weights of layer l where the plan's fp8 form applies to it (emu_llama_set_layer_fp8 sets all of a layer's or none), else nulls
+    emu_llama::Layer8 layer_fp8(int l) {
+        return plan.fp8_rows || (plan.fp8_gemm && m->layers8[l].wqkv) ? m->layers8[l] : emu_llama::Layer8{};
+    }
+
+    // ---- The decoder layer, written once, in three steps that are cut where the schedules hook in:
+    //     layer_kv      RMSNorm, [after_norm], qkv projection (+ RoPE / KV append / V^T in its epilogue, else the rope_kv launch): the
+    //                   window's K / V are cached
+    //     layer_attend  [V^T], [after_vt], attention, o_proj, all-reduce
+    //     layer_mlp     RMSNorm, gate/up + SwiGLU, down, all-reduce
+    int layer_kv(const RowWindow& win, int l, const LaneHook& after_norm = nullptr) {
+        const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
         if (!L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
-        bf16_t* kc = m->kcache + l * kv_layer;
-        bf16_t* vc = m->vcache + l * kv_layer;
-        // Host order per layer: A.attention, B.attention, A.mlp, B.mlp -- so B's wait for eKV sees A's record of this layer, and the
-        // all-reduces are issued in the order o_A, o_B, down_A, down_B.  The order matters beyond bookkeeping: all-reduces of one
-        // communicator run in issue order (RCCL makes a call on another stream wait for the stream of the call before it; the
-        // peer-to-peer chain below does the same), so an all-reduce can only wait for work issued ahead of it.  Issued lane by lane
-        // (A's whole layer, then B's), B's first all-reduce would wait for A's second and the lanes would take turns instead of overlapping.
-        for (int stage = 0; stage < 2; ++stage)
-        for (int h = 0; h < 2; ++h) {
-            hipStream_t ls = lane[h];
-            const int Mh = rows[h], kend = r0[h] + Mh;
-            bf16_t* x = hA + (size_t)r0[h] * H;
-            bf16_t* xn = w.xn + (size_t)r0[h] * H;
-            bf16_t* qkv = w.qkv + (size_t)r0[h] * 3 * HD;
-            bf16_t* att = w.attn + (size_t)r0[h] * HD;
-            bf16_t* act = w.act + (size_t)r0[h] * Fl;
-            bf16_t* hB = w.hB + (size_t)r0[h] * H;
-            if (stage == 1) {                                            // ---- SwiGLU MLP
-                TRY(cx, launch_rmsnorm(hB, L.ln2, xn, Mh, H, H, H, c.rms_eps, ls));
-                TRY(cx, linear(xn, L.wgu, nullptr, nullptr, nullptr, act, Mh, 2 * Fl, H, H, H, 0, Fl, 0.f, EPI_SWIGLU, ls, nullptr, sk[h], w.splitk_floats));
-                TRY(cx, linear(act, L.wdown, nullptr, hB, nullptr, x, Mh, H, Fl, Fl, Fl, H, H, 0.f, epi_res, ls, nullptr, sk[h], w.splitk_floats));
-                TRY(cx, lane_allreduce(h, x, (size_t)Mh * H));
-                continue;
-            }
-            // ---- attention
-            TRY(cx, launch_rmsnorm(x, L.ln1, xn, Mh, H, H, H, c.rms_eps, ls));
-            int st = -95;
-            if (fuse_rope) {
-                if (h == 1) {
-                    // lane B's V^T: A's keys of this layer out of the cache (zero behind them), its own columns from the epilogue below
-                    HIPTRY(hipStreamWaitEvent(ls, eKV, 0));
-                    TransposeVArgs tv{vc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, vt[1], 1, Hl, Ma, D, spad};
-                    TRY(cx, launch_transpose_v(tv, ls));
-                }
-                GemmArgs g{xn, L.wqkv, nullptr, nullptr, qkv, Mh, 3 * HD, H, H, H, 0, 3 * HD, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
-                g.partial = sk[h]; g.partial_floats = w.splitk_floats;
-                g.rope_cos = m->cos; g.rope_sin = m->sin; g.rope_pos = pos + r0[h]; g.rope_slot = slot + r0[h]; g.rope_kc = kc; g.rope_vc = vc;
-                g.rope_hl = Hl; g.rope_smax = m->s_max;
-                g.vt_out = vt[h] + r0[h]; g.vt_col0 = 2 * HD; g.vt_s = Mh; g.vt_spad = spad;   // key index = row index: column r0 + m
-                st = launch_gemm(g, ls);
-                if (st != 0 && st != -95) return fail(cx, st, "emu_llama_forward: qkv projection with the RoPE epilogue");
-                if (st == -95) fuse_rope = false;                        // (before anything of this call was launched fused: lane A, first layer)
-            }
-            if (st == -95) {
-                TRY(cx, linear(xn, L.wqkv, nullptr, nullptr, nullptr, qkv, Mh, 3 * HD, H, H, H, 0, 3 * HD, 0.f, EPI_NONE, ls, nullptr, sk[h], w.splitk_floats));
-                RopeKvArgs r{qkv, m->cos, m->sin, pos + r0[h], slot + r0[h], kc, vc, 1, Mh, Hl, D, m->s_max};
-                TRY(cx, launch_rope_kv(r, ls));
-                if (h == 1) HIPTRY(hipStreamWaitEvent(ls, eKV, 0));
-                TransposeVArgs tv{vc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, vt[h], 1, Hl, kend, D, spad};
-                TRY(cx, launch_transpose_v(tv, ls));                     // keys [0, kend) key-contiguous, zero up to spad
-            }
-            if (h == 0) HIPTRY(hipEventRecord(eKV, ls));                 // K / V rows [0, Ma) of layer l are in the cache
-            FlashArgs f{qkv, (long)Mh * 3 * HD, (long)D, (long)3 * HD,
-                        kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D,
-                        vt[h], att, (long)Mh * HD, (long)D, (long)HD, kstart,
-                        1, Hl, Mh, kend, spad, D, 1, scale};                 // query i of the half sees keys <= r0 + i
-            TRY(cx, launch_flash_attn(f, ls));
-            TRY(cx, linear(att, L.wo, nullptr, x, nullptr, hB, Mh, H, HD, HD, HD, H, H, 0.f, epi_res, ls, nullptr, sk[h], w.splitk_floats));
-            TRY(cx, lane_allreduce(h, hB, (size_t)Mh * H));
+        const emu_llama::Layer8 L8 = layer_fp8(l);
+        if (plan.fp8_rows && !L8.wqkv) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
+        const int rows = Bn * win.T;
+        bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
+        if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
+            if (!xn_ready) TRY(cx, launch_rmsnorm(win.x, L.ln1, w.xn, rows, H, H, H, eps, win.s));
+            xn_ready = false;
         }
+        if (after_norm) TRY(cx, after_norm());
+        int st = -95;
+        if (plan.fuse_rope) {
+            GemmArgs g{w.xn, L.wqkv, nullptr, nullptr, w.qkv, rows, 3 * HD, H, H, H, 0, 3 * HD, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
+            g.partial = w.splitk; g.partial_floats = w.splitk_floats;
+            g.rope_cos = m->cos; g.rope_sin = m->sin; g.rope_pos = win.pos; g.rope_slot = win.slot; g.rope_kc = kc; g.rope_vc = vc;
+            g.rope_hl = Hl; g.rope_smax = m->s_max;
+            g.vt_out = w.vt + win.r0; g.vt_col0 = 2 * HD; g.vt_s = rows; g.vt_spad = spad;   // key index = row index: column r0 + m
+            st = launch_gemm(g, win.s);
+            if (st != 0 && st != -95) return fail(cx, st, "emu_llama_forward: qkv projection with the RoPE epilogue");
+            if (st == -95) plan.fuse_rope = false;       // the 256x256 tile does not take this shape unsliced: unfused sequence from here on
+        }
+        if (st == -95)
+            TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, {L.wqkv, L8.wqkv, L8.sqkv}, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
+                            nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE));
+        if (T == 1) return 0;                            // single-token step: the attention launch rotates and appends
+        if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
+        if (plan.fuse_rope) return 0;
+        RopeKvArgs r{w.qkv, m->cos, m->sin, win.pos, win.slot, kc, vc, Bn, win.T, Hl, D, m->s_max};
+        TRY(cx, launch_rope_kv(r, win.s));
+        return 0;
     }
+
+    int layer_attend(const RowWindow& win, int l, const LaneHook& after_vt = nullptr) {
+        const LlamaWs& w = win.w;
+        const emu_llama::Layer& L = m->layers[l];
+        const emu_llama::Layer8 L8 = layer_fp8(l);
+        const int rows = Bn * win.T;
+        bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
+        if (T == 1) {
+            // RoPE + KV append + attention in one launch; context = slot + 1 is read on the device (graph replay)
+            DecodeFusedArgs a{w.qkv, m->cos, m->sin, win.pos, win.slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec,
+                              Bn, Hl, D, m->s_max, ctx, scale, m->kv_share_nb, m->kv_share_len};
+            if (plan.decode_tail) a.arrive = m->arrive;
+            a.skip_combine = plan.merge_o;
+            TRY(cx, launch_decode_fused(a, win.s));
+        } else {
+            if (!plan.fuse_rope) {
+                TransposeVArgs tv{vc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, w.vt, Bn, Hl, win.kend, D, spad};
+                TRY(cx, launch_transpose_v(tv, win.s));      // keys [0, kend) key-contiguous, zero up to spad
+            }
+            if (after_vt) TRY(cx, after_vt());
+            FlashArgs fa{w.qkv, (long)win.T * 3 * HD, (long)D, (long)3 * HD,
+                         kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D,
+                         w.vt, w.attn, (long)win.T * HD, (long)D, (long)HD, kstart,
+                         Bn, Hl, win.T, win.kend, spad, D, 1, scale};              // query i of the window sees keys <= r0 + i
+            TRY(cx, launch_flash_attn(fa, win.s));
+        }
+        if (plan.merge_o) {
+            GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.wo, win.x, w.hB, H, HD, HD, epi_res, nullptr};
+            TRY(cx, gemv_merge_profiled(g, win.s));
+        } else
+            TRY(cx, project(w, win.s, w.attn, {L.wo, L8.wo, L8.so}, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
+        return win.allreduce(w.hB, (size_t)rows * H);
+    }
+
+    int layer_mlp(const RowWindow& win, int l) {
+        const LlamaWs& w = win.w;
+        const emu_llama::Layer& L = m->layers[l];
+        const emu_llama::Layer8 L8 = layer_fp8(l);
+        const int rows = Bn * win.T;
+        if (!plan.norm_in_gemv && !plan.fuse_norm) TRY(cx, launch_rmsnorm(w.hB, L.ln2, w.xn, rows, H, H, H, eps, win.s));
+        TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, {L.wgu, L8.wgu, L8.sgu}, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
+                        w.act, rows, 2 * Fl, H, EPI_SWIGLU));
+        // (fuse_norm: the RMSNorm behind down_proj is the NEXT layer's input norm, which then finds its rows in w.xn)
+        const bf16_t* next_ln1 = plan.fuse_norm && l + 1 < l_end ? m->layers[l + 1].ln1 : nullptr;
+        TRY(cx, project(w, win.s, w.act, {L.wdown, L8.wdown, L8.sdown}, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
+        if (next_ln1) xn_ready = true;
+        return win.allreduce(win.x, (size_t)rows * H);
+    }
+
+    // ---- the per-layer launches: every row of the call on the caller's stream
+    int run_launches() {
+        RowWindow win = window(0, T, ctx, s, ws.vt, ws.splitk);
+        win.allreduce = [this](bf16_t* buf, size_t n) { return tp ? emu_allreduce_bf16(cx, buf, n, reinterpret_cast<emu_stream_t>(s)) : 0; };
+        for (int l = m->l0; l < l_end; ++l) {
+            TRY(cx, layer_kv(win, l));
+            TRY(cx, layer_attend(win, l));
+            TRY(cx, layer_mlp(win, l));
+        }
+        return 0;
+    }
+
+    // ---- Tensor-parallel prefill of a long prompt as TWO CONCURRENT LANES (SURVEY 8e / north_star: "all-reduce overlapped with the
+    // next GEMM"; replaces the serial schedule of run_launches).  The prompt's rows are cut once, at a multiple of 256
+    // (whole 256-row GEMM tiles and whole 64-key attention tiles below the cut), into A = [0, Ma) and B = [Ma, M).  Causal attention
+    // makes A independent of B, and B needs nothing of A but its keys / values of the SAME layer, so each half walks all layers as its
+    // own chain
+    //     [RMSNorm, qkv (+ RoPE / KV append / V^T), attention, o_proj] -> all-reduce -> [RMSNorm, gate/up + SwiGLU, down] -> all-reduce
+    // on its own stream: A on the caller's, B on cx->lane_stream, one event per layer (A's K / V rows are in the cache) the only edge
+    // between them.  While one lane's partial sums are on the wire the other lane's GEMMs have the CUs, and where both lanes compute,
+    // their launches (a TP = 8 shard's GEMM over 772 rows is 30-odd tiles on 256 CUs) share the chip instead of queueing behind each
+    // other.  A first version kept ONE compute stream and interleaved the halves stage by stage with every all-reduce on a side
+    // stream: +43 % per rank on one GPU (profiles/r05_tp_prefill_two_half_v1_single_compute_stream.log) -- half-size launches back to
+    // back leave most of the chip idle, and every all-reduce cost two cross-stream edges.  All-reduces run in their lane's stream
+    // where RCCL takes them (one communicator, calls in one host order on every rank); on a context without a communicator (rank
+    // processes sharing a device: validation) every peer-to-peer all-reduce additionally waits for the one issued before it in
+    // either lane, because the comm blocks serve one all-reduce at a time.  Lane B keeps its own V^T buffer (A's keys transposed from the cache + its own columns
+    // from the epilogue) and K-slice scratch, so no buffer is written by one lane while the other reads it.  Same kernels and
+    // rounding points as the serial schedule; a half may take another GEMM tile configuration than the whole prompt (K-slice sums in
+    // another order), so the schedules agree to bf16 rounding, not bit for bit.  Capturable: lane_stream forks from and joins the
+    // caller's stream through events.
+    int llama_prefill_lanes() {
+        const int Ma = (M / 2 + 128) / 256 * 256;        // M >= 512 (emu_llama_set_tp_overlap, pick_path): 256 <= Ma <= M - 256
+        hipStream_t lane[2] = {s, cx->lane_stream};
+        RowWindow win[2] = {window(0, Ma, Ma, lane[0], ws.vt, ws.splitk), window(Ma, M - Ma, M, lane[1], ws.vt2, ws.splitk2)};
+        hipEvent_t eStart = cx->ar_ev[0], eKV = cx->ar_ev[1];              // (ar_ev[2]: the join in llama_prefill_overlapped)
+        hipEvent_t* ePrev = cx->ar_ev + 3;   // [lane]  the lane's latest peer-to-peer all-reduce is through (an event is only ever recorded on
+        int prev_lane = -1;                  //         ONE stream: one event recorded on both streams of a capture crashed hipGraphInstantiate)
+#define HIPTRY(expr) do { if ((expr) != hipSuccess) { (void)hipGetLastError(); return fail(cx, -5, #expr); } } while (0)
+        auto lane_allreduce = [&](int h, bf16_t* buf, size_t n) -> int {
+            const bool by_rccl = cx->comm && !(cx->p2p_on && n * sizeof(bf16_t) <= EMU_P2P_SLOT_BYTES);   // emu_allreduce_bf16's own choice
+            if (by_rccl) return emu_allreduce_bf16(cx, buf, n, reinterpret_cast<emu_stream_t>(lane[h]));
+            // the comm blocks serve ONE all-reduce at a time: every peer-to-peer all-reduce waits for the one issued before it (host order,
+            // the same on every rank), whichever lane that was in
+            if (prev_lane >= 0 && prev_lane != h) HIPTRY(hipStreamWaitEvent(lane[h], ePrev[prev_lane], 0));
+            TRY(cx, emu_allreduce_bf16(cx, buf, n, reinterpret_cast<emu_stream_t>(lane[h])));
+            HIPTRY(hipEventRecord(ePrev[h], lane[h]));
+            prev_lane = h;
+            return 0;
+        };
+        for (int h = 0; h < 2; ++h) win[h].allreduce = [&lane_allreduce, h](bf16_t* buf, size_t n) { return lane_allreduce(h, buf, n); };
+        HIPTRY(hipEventRecord(eStart, lane[0]));                             // inputs (and whatever the caller queued before) are ready
+        HIPTRY(hipStreamWaitEvent(lane[1], eStart, 0));
+        for (int l = m->l0; l < l_end; ++l) {
+            // Host order per layer: A.attention, B.attention, A.mlp, B.mlp -- so B's wait for eKV sees A's record of this layer, and the
+            // all-reduces are issued in the order o_A, o_B, down_A, down_B.  The order matters beyond bookkeeping: all-reduces of one
+            // communicator run in issue order (RCCL makes a call on another stream wait for the stream of the call before it; the
+            // peer-to-peer chain above does the same), so an all-reduce can only wait for work issued ahead of it.  Issued lane by lane
+            // (A's whole layer, then B's), B's first all-reduce would wait for A's second and the lanes would take turns instead of overlapping.
+            // lane B's V^T with the RoPE epilogue: A's keys of this layer out of the cache (zero behind them), between B's RMSNorm and
+            // its qkv GEMM, whose epilogue adds B's own columns
+            const LaneHook keys_of_A = [&]() -> int {
+                HIPTRY(hipStreamWaitEvent(lane[1], eKV, 0));
+                TransposeVArgs tv{m->vcache + l * kv_layer, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, ws.vt2, 1, Hl, Ma, D, spad};
+                return launch_transpose_v(tv, lane[1]);
+            };
+            // K / V rows [0, Ma) of layer l are in the cache: recorded behind A's qkv GEMM, or behind A's transpose_v in the unfused sequence
+            const LaneHook kv_of_A_cached = [&]() -> int { HIPTRY(hipEventRecord(eKV, lane[0])); return 0; };
+            for (int h = 0; h < 2; ++h) {
+                // (-95 from the fused qkv GEMM: the unfused sequence from there on, in both lanes)
+                TRY(cx, layer_kv(win[h], l, h == 1 && plan.fuse_rope ? keys_of_A : LaneHook()));
+                if (h == 1 && !plan.fuse_rope) HIPTRY(hipStreamWaitEvent(lane[1], eKV, 0));   // layer_attend transposes keys [0, M) out of the cache
+                TRY(cx, layer_attend(win[h], l, h == 0 ? kv_of_A_cached : LaneHook()));
+            }
+            for (int h = 0; h < 2; ++h) TRY(cx, layer_mlp(win[h], l));
+        }
 #undef HIPTRY
-    return 0;
-}
-int llama_prefill_overlapped(emu_llama* m, const LlamaWs& w, bf16_t* hA, int M, const int32_t* pos, const int32_t* slot,
-                             const int32_t* kstart, bool fuse_rope, hipStream_t s) {
-    emu_ctx* cx = m->ctx;
-    const int st = llama_prefill_lanes(m, w, hA, M, pos, slot, kstart, fuse_rope, s);
-    // join, on the error path as well: whatever reached the second lane is ordered ahead of the caller's next launch (and a stream
-    // capture in progress ends with the lane joined); the caller's stream owns the residual stream again
-    const bool joined = hipEventRecord(cx->ar_ev[2], cx->lane_stream) == hipSuccess && hipStreamWaitEvent(s, cx->ar_ev[2], 0) == hipSuccess;
-    if (st != 0) return st;
-    if (!joined) { (void)hipGetLastError(); return fail(cx, -5, "emu_llama_forward: joining the second lane"); }
-    ++m->ov_forwards;
-    return 0;
-}
+        return 0;
+    }
+    int llama_prefill_overlapped() {
+        const int st = llama_prefill_lanes();
+        // join, on the error path as well: whatever reached the second lane is ordered ahead of the caller's next launch (and a stream
+        // capture in progress ends with the lane joined); the caller's stream owns the residual stream again
+        const bool joined = hipEventRecord(cx->ar_ev[2], cx->lane_stream) == hipSuccess && hipStreamWaitEvent(s, cx->ar_ev[2], 0) == hipSuccess;
+        if (st != 0) return st;
+        if (!joined) { (void)hipGetLastError(); return fail(cx, -5, "emu_llama_forward: joining the second lane"); }
+        ++m->ov_forwards;
+        return 0;
+    }
+
+    // ---- one-row step with bf16 weights on the persistent weight-streaming engine (decode_engine.hip; mode 4): per layer the attention
+    // launches, then ONE launch for  o_proj -> all-reduce -> RMSNorm + gate/up (SwiGLU) -> down -> all-reduce -> RMSNorm + the NEXT
+    // layer's qkv projection, the weight stream running ahead of the four hand-offs; same bits as the launches of run_launches.
+    int run_engine() {
+        const LlamaWs& w = ws;
+        EngArgs e = plan.eng;
+        e.err = m->dl_err; e.ncu = cx->ncu;
+        engine_tool_switches(e);
+        for (int l = m->l0; l < l_end; ++l)
+            if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+        if (hipMemsetAsync(m->eng_gran, 0, m->eng_gran_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
+        const size_t gH = align_up((size_t)H * 4), gF = align_up((size_t)Fl * 4);
+        const bool res_here = epi_res == EPI_RESID;           // rank 0 adds the residuals (they enter the all-reduce once)
+        // the first layer's qkv projection is a launch of its own
+        TRY(cx, project(w, s, hA, {m->layers[m->l0].wqkv, nullptr, nullptr}, nullptr, m->layers[m->l0].ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
+        for (int l = m->l0; l < l_end; ++l) {
+            const emu_llama::Layer& L = m->layers[l];
+            bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
+            DecodeFusedArgs da{w.qkv, m->cos, m->sin, pos, slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec, Bn, Hl, D, m->s_max, ctx, scale, 0, 0};
+            TRY(cx, launch_decode_fused(da, s));
+            const bool last = l + 1 == l_end;
+            char* gl = reinterpret_cast<char*>(m->eng_gran) + (size_t)l * (2 * gH + gF);
+            uint32_t* g_hb = reinterpret_cast<uint32_t*>(gl);
+            uint32_t* g_act = reinterpret_cast<uint32_t*>(gl + gH);
+            uint32_t* g_ha = reinterpret_cast<uint32_t*>(gl + gH + gF);
+            int k = 0;
+            EngOp& o0 = e.op[k++] = EngOp{};                          // o_proj: partial sums of the post-attention stream
+            o0.W = L.wo; o0.N = H; o0.K = HD; o0.epi = res_here ? EPI_RESID : EPI_NONE; o0.res = hA; o0.res_src = 0;
+            o0.vw = emu_gemv_partition(H, HD, false, epi_res); o0.x_src = 0; o0.xg = w.attn; o0.out_dst = 2; o0.ar_k = 0;
+            EngOp& o1 = e.op[k++] = EngOp{};                          // all-reduce -> RMSNorm -> gate / up -> SwiGLU
+            o1.W = L.wgu; o1.N = 2 * Fl; o1.K = H; o1.gain = L.ln2; o1.eps = eps; o1.epi = EPI_SWIGLU;
+            o1.vw = emu_gemv_partition(2 * Fl, H, true, EPI_SWIGLU); o1.x_src = 2; o1.xgran = g_hb; o1.ar_k = 0; o1.keep_raw = 1;
+            o1.out_dst = 1; o1.ogran = g_act;
+            EngOp& o2 = e.op[k++] = EngOp{};                          // down: partial sums of the layer output (+ the summed stream on rank 0)
+            o2.W = L.wdown; o2.N = H; o2.K = Fl; o2.epi = res_here ? EPI_RESID : EPI_NONE; o2.res_src = 1;
+            o2.vw = emu_gemv_partition(H, Fl, false, epi_res); o2.x_src = 1; o2.xgran = g_act;
+            if (!last) {
+                o2.out_dst = 2; o2.ar_k = 1;
+                EngOp& o3 = e.op[k++] = EngOp{};                      // all-reduce -> RMSNorm -> the NEXT layer's qkv projection
+                const emu_llama::Layer& Ln = m->layers[l + 1];
+                o3.W = Ln.wqkv; o3.N = 3 * HD; o3.K = H; o3.gain = Ln.ln1; o3.eps = eps; o3.epi = EPI_NONE;
+                o3.vw = emu_gemv_partition(3 * HD, H, true, EPI_NONE); o3.x_src = 2; o3.xgran = g_ha; o3.ar_k = 1; o3.sum_out = hA;
+                o3.out_dst = 0; o3.out = w.qkv;
+                e.n_ar = 2;
+            } else {
+                o2.out_dst = 0; o2.out = hA;                // the last layer's output leaves as this rank's partial sums
+                e.n_ar = 1;
+            }
+            e.nops = k;
+            const int st = launch_decode_engine(e, s);
+            if (st) return fail(cx, st, "emu_llama_forward: decode engine launch");
+            if (last) TRY(cx, emu_allreduce_bf16(cx, hA, (size_t)H, reinterpret_cast<emu_stream_t>(s)));
+        }
+        ++m->eng_forwards;
+        ++m->dl_forwards;
+        return 0;
+    }
+
+    // ---- one-row step with bf16 weights: whole layers per launch (decode_layer.hip), same bits as the launches of run_launches.  Three
+    // schedules (pick_path): layers_per_launch layers in a launch with the all-reduces, if any, inside it; every layer cut at its two
+    // all-reduces; or each all-reduce in the tail of the row-sharded projection's launch.
+    int run_fused_layers() {
+        const LlamaWs& w = ws;
+        const emu_stream_t s_ = reinterpret_cast<emu_stream_t>(s);
+        DecodeLayersArgs d = plan.dl;
+        d.table = m->dl_table; d.hA = hA; d.hB = w.hB; d.qkv = w.qkv; d.attn = w.attn; d.act = w.act; d.ws = w.dec;
+        d.cos = m->cos; d.sin = m->sin; d.pos = pos; d.slot = slot; d.kstart = kstart;
+        d.kcache = m->kcache; d.vcache = m->vcache; d.kv_layer = kv_layer;
+        d.S_max = m->s_max; d.ctx_max = ctx;
+        d.eps = eps; d.scale = scale; d.epi_res = epi_res == EPI_RESID ? 1 : 0;
+        d.cnt = m->dl_cnt; d.err = m->dl_err;
+        d.trace = m->dl_trace;
+        if (m->dl_dirty) {
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            (void)hipStreamIsCapturing(s, &cs);
+            if (cs != hipStreamCaptureStatusNone)
+                return fail(cx, -16, "emu_llama_forward: the fused decode path needs one eager step before a capture (weight table upload)");
+            std::vector<DecodeLayerPtrs> t(m->layers.size());
+            for (size_t l = 0; l < t.size(); ++l) { const emu_llama::Layer& L = m->layers[l]; t[l] = {L.wqkv, L.wo, L.wgu, L.wdown, L.ln1, L.ln2}; }
+            if (hipStreamSynchronize(s) != hipSuccess ||        // fused launches still in flight on s read the table
+                hipMemcpy(m->dl_table, t.data(), sizeof(DecodeLayerPtrs) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
+                return fail(cx, -5, "emu_llama_forward: weight table upload");
+            m->dl_dirty = false;
+        }
+        for (int l = m->l0; l < l_end; ++l)
+            if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+        if (hipMemsetAsync(m->dl_cnt, 0, m->dl_cnt_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
+        if (plan.path == LlamaPath::FusedTailAllReduce) {
+            // mode 3: the weight streams with an RMSNorm in front stay stand-alone launches; the attention (split merge by the
+            // head's last split) and the two row-sharded projections run as single-role launches whose LAST workgroup to arrive
+            // runs the all-reduce -- nobody waits inside a launch except that one workgroup for its peers, so rank processes that
+            // share a device cannot starve each other: 5 launches per layer instead of 8
+            for (int l = m->l0; l < l_end; ++l) {
+                const emu_llama::Layer& L = m->layers[l];
+                d.layer0 = l; d.nlayers = 1;
+                TRY(cx, project(w, s, hA, {L.wqkv, nullptr, nullptr}, nullptr, L.ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
+                DecodeLayersArgs a1 = d; a1.tp_n = 0; a1.role0 = 1; a1.role1 = 2;
+                TRY(cx, launch_decode_layers(a1, s));
+                d.role0 = 2; d.role1 = 3;
+                TRY(cx, launch_decode_layers(d, s));
+                TRY(cx, project(w, s, w.hB, {L.wgu, nullptr, nullptr}, nullptr, L.ln2, nullptr, w.act, 1, 2 * Fl, H, EPI_SWIGLU));
+                d.role0 = 4; d.role1 = 5;
+                TRY(cx, launch_decode_layers(d, s));
+            }
+        } else if (plan.path == LlamaPath::FusedCutAtAllReduce) {
+            for (int l = m->l0; l < l_end; ++l) {
+                d.layer0 = l; d.nlayers = 1;
+                d.role0 = 0; d.role1 = 3;
+                TRY(cx, launch_decode_layers(d, s));
+                TRY(cx, emu_allreduce_bf16(cx, w.hB, (size_t)H, s_));
+                d.role0 = 3; d.role1 = 5;
+                TRY(cx, launch_decode_layers(d, s));
+                TRY(cx, emu_allreduce_bf16(cx, hA, (size_t)H, s_));
+            }
+        } else {
+            const int per = m->dl_per_launch > 0 ? m->dl_per_launch : l_end - m->l0;
+            for (int l = m->l0; l < l_end; l += per) {
+                d.layer0 = l; d.nlayers = std::min(per, l_end - l);
+                TRY(cx, launch_decode_layers(d, s));
+            }
+        }
+        ++m->dl_forwards;
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -882,289 +1193,26 @@ int emu_llama_forward(emu_llama* m, void* hidden, int Bn, int T, const int32_t* 
     if (!m->kcache || Bn != m->kv_batch) return fail(cx, -22, "emu_llama_forward: KV cache not set for this batch size");
     if (ctx < 1 || ctx > m->s_max) return fail(cx, -22, "emu_llama_forward: ctx out of range");
     if (!m->cos) return fail(cx, -22, "emu_llama_forward: rope tables not set");
-    const LlamaWs w = llama_ws(m, Bn, T, workspace);
-    if (w.total > ws_bytes) return fail(cx, -12, "emu_llama_forward: workspace too small");
-    hipStream_t s = S(s_);
-    const int M = Bn * T, H = c.hidden, Hl = c.heads_local, D = c.head_dim, HD = Hl * D, Fl = c.ffn_local;
-    const bool tp = cx->tp_size > 1 || cx->comm != nullptr || cx->p2p_on;   // a 1-rank communicator / comm block still runs the all-reduces (tests, tools/tp_emulate.py)
-    const int epi_res = (!tp || cx->tp_rank == 0) ? EPI_RESID : EPI_NONE;   // residual enters the all-reduce once
-    const float scale = 1.0f / sqrtf((float)D);
-    const size_t kv_layer = (size_t)Bn * Hl * m->s_max * D;
-    const int spad = (ctx + 63) / 64 * 64;
-    bf16_t* hA = B(hidden);
-    const int l_end = m->l1 < 0 ? c.layers : m->l1;
-    // Prefill of ONE batch element whose rows are the whole context in slot order (emu_llama_set_prefill_fusion: the caller
-    // promises slot[i] = i): the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
-    // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.  The V^T buffer's pad columns [ctx, spad) are
-    // never written on that path: zeroed once per call (the attention kernel multiplies them by masked probabilities).
-    // The promise is per call: it is consumed here, so a later emu_llama_forward with rows in another slot order (any caller that did
-    // not renew it) runs the unfused sequence, which honours slot[] everywhere.
-    bool fuse_rope = promise && Bn == 1 && T > 16 && T == ctx && D == 128 && !(HD & 255) && !m->fp8_prefill && m->kv_share_nb <= 1;
-    if (fuse_rope && hipMemsetAsync(w.vt, 0, (size_t)HD * spad * 2, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
-    // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
-    // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
-    // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
-    // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
-    // with B * beams > 16) keep the fused path they had before the promise became one-shot.
-    const bool fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill;
-    bool xn_ready = false;
-    // ---- one-row step with bf16 weights on the persistent weight-streaming engine (decode_engine.hip; mode 4): per layer the attention
-    // launches, then ONE launch for  o_proj -> all-reduce -> RMSNorm + gate/up (SwiGLU) -> down -> all-reduce -> RMSNorm + the NEXT
-    // layer's qkv projection, the weight stream running ahead of the four hand-offs; same bits as the launches below.  Tensor-parallel
-    // shards with rows of at most 13 KiB (TP >= 4) whose ranks have the device to themselves; anything else takes the launches.
-    if (m->decode_fused == 4 && T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && m->kv_share_nb <= 1 && l_end > m->l0 && m->eng_gran && m->dl_err &&
-        tp && cx->p2p && cx->p2p_on && emu_p2p_fenced(cx->p2p) == 0 && H <= 6656 && HD <= 6656 && Fl <= 6656 && !(H & 7) && !(Fl & 7)) {
-        EngArgs e{};
-        unsigned int* eseq = nullptr;
-        int en = 0, er = 0;
-        int ncu = 0;
-        if (emu_p2p_engine_view(cx->p2p, e.comm, &eseq, &en, &er) && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, cx->device) == hipSuccess &&
-            3 * HD >= 2 * ncu && H >= 2 * ncu && Fl >= ncu && ncu <= 1024) {
-            e.tp_n = en; e.tp_rank = er; e.seq = eseq; e.err = m->dl_err; e.limit_ticks = 200000000LL; e.ncu = ncu;
-            if (const char* ev = getenv("EMU_ENGINE_TIMEOUT_MS")) { const long ms = atol(ev); if (ms > 0) e.limit_ticks = ms * 100000LL; }
-            if (const char* ev = getenv("EMU_ENGINE_LOADERS")) e.nload = atoi(ev);
-            for (int l = m->l0; l < l_end; ++l)
-                if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
-            if (hipMemsetAsync(m->eng_gran, 0, m->eng_gran_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
-            const size_t gH = align_up((size_t)H * 4), gF = align_up((size_t)Fl * 4);
-            const bool res_here = epi_res == EPI_RESID;           // rank 0 adds the residuals (they enter the all-reduce once)
-            // the first layer's qkv projection is a launch of its own
-            TRY(cx, linear(hA, m->layers[m->l0].wqkv, nullptr, nullptr, m->layers[m->l0].ln1, w.qkv, 1, 3 * HD, H, H, H, 0, 3 * HD, c.rms_eps, EPI_NONE, s));
-            for (int l = m->l0; l < l_end; ++l) {
-                const emu_llama::Layer& L = m->layers[l];
-                bf16_t* kc = m->kcache + l * kv_layer;
-                bf16_t* vc = m->vcache + l * kv_layer;
-                DecodeFusedArgs da{w.qkv, m->cos, m->sin, pos, slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec, Bn, Hl, D, m->s_max, ctx, scale, 0, 0};
-                TRY(cx, launch_decode_fused(da, s));
-                const bool last = l + 1 == l_end;
-                char* gl = reinterpret_cast<char*>(m->eng_gran) + (size_t)(l - 0) * (2 * gH + gF);
-                uint32_t* g_hb = reinterpret_cast<uint32_t*>(gl);
-                uint32_t* g_act = reinterpret_cast<uint32_t*>(gl + gH);
-                uint32_t* g_ha = reinterpret_cast<uint32_t*>(gl + gH + gF);
-                int k = 0;
-                EngOp& o0 = e.op[k++];                          // o_proj: partial sums of the post-attention stream
-                o0 = EngOp{};
-                o0.W = L.wo; o0.N = H; o0.K = HD; o0.epi = res_here ? EPI_RESID : EPI_NONE; o0.res = hA; o0.res_src = 0;
-                o0.vw = emu_gemv_partition(H, HD, false, epi_res); o0.x_src = 0; o0.xg = w.attn; o0.out_dst = 2; o0.ar_k = 0;
-                EngOp& o1 = e.op[k++];                          // all-reduce -> RMSNorm -> gate / up -> SwiGLU
-                o1 = EngOp{};
-                o1.W = L.wgu; o1.N = 2 * Fl; o1.K = H; o1.gain = L.ln2; o1.eps = c.rms_eps; o1.epi = EPI_SWIGLU;
-                o1.vw = emu_gemv_partition(2 * Fl, H, true, EPI_SWIGLU); o1.x_src = 2; o1.xgran = g_hb; o1.ar_k = 0; o1.keep_raw = 1;
-                o1.out_dst = 1; o1.ogran = g_act;
-                EngOp& o2 = e.op[k++];                          // down: partial sums of the layer output (+ the summed stream on rank 0)
-                o2 = EngOp{};
-                o2.W = L.wdown; o2.N = H; o2.K = Fl; o2.epi = res_here ? EPI_RESID : EPI_NONE; o2.res_src = 1;
-                o2.vw = emu_gemv_partition(H, Fl, false, epi_res); o2.x_src = 1; o2.xgran = g_act;
-                if (!last) {
-                    o2.out_dst = 2; o2.ar_k = 1;
-                    EngOp& o3 = e.op[k++];                      // all-reduce -> RMSNorm -> the NEXT layer's qkv projection
-                    o3 = EngOp{};
-                    const emu_llama::Layer& Ln = m->layers[l + 1];
-                    o3.W = Ln.wqkv; o3.N = 3 * HD; o3.K = H; o3.gain = Ln.ln1; o3.eps = c.rms_eps; o3.epi = EPI_NONE;
-                    o3.vw = emu_gemv_partition(3 * HD, H, true, EPI_NONE); o3.x_src = 2; o3.xgran = g_ha; o3.ar_k = 1; o3.sum_out = hA;
-                    o3.out_dst = 0; o3.out = w.qkv;
-                    e.n_ar = 2;
-                } else {
-                    o2.out_dst = 0; o2.out = hA;                // the last layer's output leaves as this rank's partial sums
-                    e.n_ar = 1;
-                }
-                e.nops = k;
-                const int st = launch_decode_engine(e, s);
-                if (st) return fail(cx, st, "emu_llama_forward: decode engine launch");
-                if (last) TRY(cx, emu_allreduce_bf16(cx, hA, (size_t)H, s_));
-            }
-            ++m->eng_forwards;
-            ++m->dl_forwards;
-            return 0;
-        }
+    LlamaCall f{};
+    f.m = m; f.cx = cx; f.ws = llama_ws(m, Bn, T, workspace);
+    if (f.ws.total > ws_bytes) return fail(cx, -12, "emu_llama_forward: workspace too small");
+    f.hA = B(hidden); f.pos = pos; f.slot = slot; f.kstart = kstart; f.s = S(s_);
+    f.Bn = Bn; f.T = T; f.M = Bn * T; f.ctx = ctx; f.spad = (ctx + 63) / 64 * 64; f.l_end = m->l1 < 0 ? c.layers : m->l1;
+    f.H = c.hidden; f.Hl = c.heads_local; f.D = c.head_dim; f.HD = f.Hl * f.D; f.Fl = c.ffn_local;
+    f.tp = cx->tp_size > 1 || cx->comm != nullptr || cx->p2p_on;
+    f.epi_res = (!f.tp || cx->tp_rank == 0) ? EPI_RESID : EPI_NONE;
+    f.scale = 1.0f / sqrtf((float)f.D); f.eps = c.rms_eps; f.kv_layer = (size_t)Bn * f.Hl * m->s_max * f.D;
+    f.pick_path(promise);
+    // The V^T buffer's pad columns [ctx, spad) are never written by the qkv epilogue: zeroed once per call (the attention kernel
+    // multiplies them by masked probabilities).
+    if (f.plan.fuse_rope && hipMemsetAsync(f.ws.vt, 0, (size_t)f.HD * f.spad * 2, f.s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
+    switch (f.plan.path) {
+    case LlamaPath::Engine: return f.run_engine();
+    case LlamaPath::TwoLane: return f.llama_prefill_overlapped();
+    case LlamaPath::Launches: return f.run_launches();
+    case LlamaPath::FusedLayers: case LlamaPath::FusedCutAtAllReduce: case LlamaPath::FusedTailAllReduce: return f.run_fused_layers();
     }
-    // ---- one-row step with bf16 weights: whole layers per launch (decode_layer.hip), same bits as the launches below
-    if (m->decode_fused && m->decode_fused != 4 && T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && m->kv_share_nb <= 1 && l_end > m->l0 && m->dl_cnt) {
-        DecodeLayersArgs d{};
-        d.table = m->dl_table; d.hA = hA; d.hB = w.hB; d.qkv = w.qkv; d.attn = w.attn; d.act = w.act; d.ws = w.dec;
-        d.cos = m->cos; d.sin = m->sin; d.pos = pos; d.slot = slot; d.kstart = kstart;
-        d.kcache = m->kcache; d.vcache = m->vcache; d.kv_layer = kv_layer;
-        d.H = H; d.Hl = Hl; d.Fl = Fl; d.S_max = m->s_max; d.ctx_max = ctx;
-        d.eps = c.rms_eps; d.scale = scale; d.epi_res = (!tp || cx->tp_rank == 0) ? 1 : 0;
-        // wait bound: 2 s of wall clock (100 MHz ticks), or the peer-to-peer time-out where that is longer -- rank processes that SHARE
-        // a GPU (validation runs) are time-sliced against each other, and a wave that is switched out keeps its start time: the 0.2 s
-        // of the first version ran out under eight ranks on one device (garbage from step 4 on, give-ups counted)
-        d.cnt = m->dl_cnt; d.err = m->dl_err; d.limit_ticks = 200000000LL;
-        d.trace = m->dl_trace;
-        bool ok = decode_layers_ok(d);
-        // tensor parallelism: mode 2 runs the all-reduces inside the launch over the P2P comm blocks (every rank on its own GPU); mode 1
-        // cuts every layer at its two all-reduces -- [q, attention, o_proj] | all-reduce | [gate/up, down] | all-reduce -- which also
-        // serves RCCL and ranks that share a GPU (a launch that waits for a peer must not hold the CUs the peer needs)
-        bool in_kernel_ar = false;
-        if (ok && tp && cx->p2p) {
-            long long lim = 0;
-            const bool view = emu_p2p_view(cx->p2p, d.tp_block, &d.tp_seq, &d.tp_n, &d.tp_rank, &lim);
-            in_kernel_ar = view && cx->p2p_on && m->decode_fused == 2 && emu_p2p_fenced(cx->p2p) == 0;   // the in-launch all-reduce is the fence-free form only
-            if (!in_kernel_ar) d.tp_n = 0;
-            if (view && lim > d.limit_ticks) d.limit_ticks = lim;  // a lagging peer holds every downstream wait: the peer bound applies
-            ok = decode_layers_ok(d);
-        }
-        if (ok) {
-            if (m->dl_dirty) {
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                (void)hipStreamIsCapturing(s, &cs);
-                if (cs != hipStreamCaptureStatusNone)
-                    return fail(cx, -16, "emu_llama_forward: the fused decode path needs one eager step before a capture (weight table upload)");
-                std::vector<DecodeLayerPtrs> t(c.layers);
-                for (int l = 0; l < c.layers; ++l) {
-                    const emu_llama::Layer& L = m->layers[l];
-                    t[l] = {L.wqkv, L.wo, L.wgu, L.wdown, L.ln1, L.ln2};
-                }
-                if (hipStreamSynchronize(s) != hipSuccess ||        // fused launches still in flight on s read the table
-                    hipMemcpy(m->dl_table, t.data(), sizeof(DecodeLayerPtrs) * c.layers, hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(cx, -5, "emu_llama_forward: weight table upload");
-                m->dl_dirty = false;
-            }
-            for (int l = m->l0; l < l_end; ++l)
-                if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
-            if (hipMemsetAsync(m->dl_cnt, 0, m->dl_cnt_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
-            if (tp && m->decode_fused == 3 && cx->p2p_on && emu_p2p_fenced(cx->p2p) == 0 && emu_p2p_view(cx->p2p, d.tp_block, &d.tp_seq, &d.tp_n, &d.tp_rank, &d.limit_ticks)) {
-                // mode 3: the weight streams with an RMSNorm in front stay stand-alone launches; the attention (split merge by the
-                // head's last split) and the two row-sharded projections run as single-role launches whose LAST workgroup to arrive
-                // runs the all-reduce -- nobody waits inside a launch except that one workgroup for its peers, so rank processes that
-                // share a device cannot starve each other: 5 launches per layer instead of 8
-                if (d.limit_ticks < 200000000LL) d.limit_ticks = 200000000LL;
-                for (int l = m->l0; l < l_end; ++l) {
-                    const emu_llama::Layer& L = m->layers[l];
-                    d.layer0 = l; d.nlayers = 1;
-                    TRY(cx, linear(hA, L.wqkv, nullptr, nullptr, L.ln1, w.qkv, 1, 3 * HD, H, H, H, 0, 3 * HD, c.rms_eps, EPI_NONE, s));
-                    DecodeLayersArgs a1 = d; a1.tp_n = 0; a1.role0 = 1; a1.role1 = 2;
-                    TRY(cx, launch_decode_layers(a1, s));
-                    d.role0 = 2; d.role1 = 3;
-                    TRY(cx, launch_decode_layers(d, s));
-                    TRY(cx, linear(w.hB, L.wgu, nullptr, nullptr, L.ln2, w.act, 1, 2 * Fl, H, H, H, 0, Fl, c.rms_eps, EPI_SWIGLU, s));
-                    d.role0 = 4; d.role1 = 5;
-                    TRY(cx, launch_decode_layers(d, s));
-                }
-                ++m->dl_forwards;
-                return 0;
-            }
-            if (tp && !in_kernel_ar) {
-                d.tp_n = 0;
-                for (int l = m->l0; l < l_end; ++l) {
-                    d.layer0 = l; d.nlayers = 1;
-                    d.role0 = 0; d.role1 = 3;
-                    TRY(cx, launch_decode_layers(d, s));
-                    TRY(cx, emu_allreduce_bf16(cx, w.hB, (size_t)H, s_));
-                    d.role0 = 3; d.role1 = 5;
-                    TRY(cx, launch_decode_layers(d, s));
-                    TRY(cx, emu_allreduce_bf16(cx, hA, (size_t)H, s_));
-                }
-            } else {
-                const int per = m->dl_per_launch > 0 ? m->dl_per_launch : l_end - m->l0;
-                for (int l = m->l0; l < l_end; l += per) {
-                    d.layer0 = l; d.nlayers = std::min(per, l_end - l);
-                    TRY(cx, launch_decode_layers(d, s));
-                }
-            }
-            ++m->dl_forwards;
-            return 0;
-        }
-    }
-    // ---- long prompt under tensor parallelism: two row halves, every all-reduce behind the other half's GEMMs (needs the slot-order
-    // promise: the rows of the one batch element are the whole context in order, so the first half never reads the second's keys)
-    if (tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && w.vt2 && promise && Bn == 1 && T == ctx && M >= m->tp_overlap_rows && l_end > m->l0 &&
-        !m->fp8_prefill && m->kv_share_nb <= 1)
-        return llama_prefill_overlapped(m, w, hA, M, pos, slot, kstart, fuse_rope, s);
-    for (int l = m->l0; l < l_end; ++l) {
-        const emu_llama::Layer& L = m->layers[l];
-        if (!L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
-        bf16_t* kc = m->kcache + l * kv_layer;
-        bf16_t* vc = m->vcache + l * kv_layer;
-        // ---- attention
-        bool merge_o = false;
-        const bool f8 = m->fp8_decode && M <= 2;
-        // prefill with the fp8 weight set: activations are quantised per row ahead of every GEMM, the block-scaled MFMA
-        // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
-        const bool f8p = m->fp8_prefill && M > 16 && !(H & 127) && !(HD & 127) && !(Fl & 127) && m->layers8[l].wqkv;
-        const emu_llama::Layer8 L8 = f8 ? m->layers8[l] : emu_llama::Layer8{};
-        if (f8 && !L8.wqkv) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
-        if (f8) {
-            TRY(cx, linear(hA, B(L8.wqkv), nullptr, nullptr, L.ln1, w.qkv, M, 3 * HD, H, H, H, 0, 3 * HD, c.rms_eps, EPI_NONE, s, L8.sqkv));
-        } else if (M == 1) {
-            TRY(cx, linear(hA, L.wqkv, nullptr, nullptr, L.ln1, w.qkv, M, 3 * HD, H, H, H, 0, 3 * HD, c.rms_eps, EPI_NONE, s));
-        } else {                                     // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
-            if (!xn_ready) TRY(cx, launch_rmsnorm(hA, L.ln1, w.xn, M, H, H, H, c.rms_eps, s));
-            xn_ready = false;
-            if (f8p) TRY(cx, linear_q8(w, w.xn, H, m->layers8[l].wqkv, m->layers8[l].sqkv, nullptr, w.qkv, M, 3 * HD, H, 0, 3 * HD, EPI_NONE, s));
-            else {
-                int st = -95;
-                if (fuse_rope) {
-                    GemmArgs g{w.xn, L.wqkv, nullptr, nullptr, w.qkv, M, 3 * HD, H, H, H, 0, 3 * HD, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
-                    g.partial = w.splitk; g.partial_floats = w.splitk_floats;
-                    g.rope_cos = m->cos; g.rope_sin = m->sin; g.rope_pos = pos; g.rope_slot = slot; g.rope_kc = kc; g.rope_vc = vc;
-                    g.rope_hl = Hl; g.rope_smax = m->s_max;
-                    g.vt_out = w.vt; g.vt_col0 = 2 * HD; g.vt_s = M; g.vt_spad = spad;
-                    st = launch_gemm(g, s);
-                    if (st != 0 && st != -95) return fail(cx, st, "emu_llama_forward: qkv projection with the RoPE epilogue");
-                    if (st == -95) fuse_rope = false;  // the 256x256 tile does not take this shape unsliced: unfused sequence
-                }
-                if (st == -95)
-                    TRY(cx, linear(w.xn, L.wqkv, nullptr, nullptr, nullptr, w.qkv, M, 3 * HD, H, H, H, 0, 3 * HD, 0.f, EPI_NONE, s, nullptr, w.splitk, w.splitk_floats));
-            }
-        }
-        if (T == 1) {
-            // RoPE + KV append + attention in one launch; context = slot + 1 is read on the device (graph replay)
-            DecodeFusedArgs a{w.qkv, m->cos, m->sin, pos, slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec,
-                              Bn, Hl, D, m->s_max, ctx, scale, m->kv_share_nb, m->kv_share_len};
-            if (m->decode_tail && m->arrive && m->kv_share_nb <= 1 && (long)Bn * Hl <= EMU_ARRIVE_INTS) a.arrive = m->arrive;
-            // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
-            // itself, no combine launch (gemv_merge.hip).  Bit-identical and measured LEVEL with the two launches (3.15 vs 3.15-3.18 ms
-            // per token of a TP = 8 shard, profiles/r05_tp_emulate_merged_o_proj.log): the merge is a dependent L2 trip inside the
-            // projection, which is what the combine launch cost -- one launch less buys nothing here, like the in-kernel split merge
-            // and the tail all-reduce before it
-            merge_o = M == 1 && !f8 && !a.arrive && m->kv_share_nb <= 1 && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
-                      (emu_gemm_tune_get() & (1 << 19)) != 0;
-            a.skip_combine = merge_o;
-            TRY(cx, launch_decode_fused(a, s));
-        } else {
-            if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
-            if (!fuse_rope) {
-                { RopeKvArgs r{w.qkv, m->cos, m->sin, pos, slot, kc, vc, Bn, T, Hl, D, m->s_max};
-                  TRY(cx, launch_rope_kv(r, s)); }
-                TransposeVArgs tv{vc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, w.vt, Bn, Hl, ctx, D, spad};
-                TRY(cx, launch_transpose_v(tv, s));
-            }
-            FlashArgs f{w.qkv, (long)T * 3 * HD, (long)D, (long)3 * HD,
-                        kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D,
-                        w.vt, w.attn, (long)T * HD, (long)D, (long)HD, kstart,
-                        Bn, Hl, T, ctx, spad, D, 1, scale};
-            TRY(cx, launch_flash_attn(f, s));
-        }
-        if (merge_o) {
-            GemvMergeArgs g{w.dec, slot, (ctx + 127) / 128, Hl, L.wo, hA, w.hB, H, HD, HD, epi_res, nullptr};
-            TRY(cx, gemv_merge_profiled(g, s));
-        } else
-        if (f8) TRY(cx, linear(w.attn, B(L8.wo), nullptr, hA, nullptr, w.hB, M, H, HD, HD, HD, H, H, 0.f, epi_res, s, L8.so));
-        else if (f8p) TRY(cx, linear_q8(w, w.attn, HD, m->layers8[l].wo, m->layers8[l].so, hA, w.hB, M, H, HD, H, H, epi_res, s));
-        else if (fuse_norm) TRY(cx, linear_then_rmsnorm(w, w.attn, L.wo, hA, w.hB, M, H, HD, epi_res, L.ln2, w.xn, c.rms_eps, true, s));
-        else TRY(cx, linear(w.attn, L.wo, nullptr, hA, nullptr, w.hB, M, H, HD, HD, HD, H, H, 0.f, epi_res, s, nullptr, w.splitk, w.splitk_floats));
-        if (tp) TRY(cx, emu_allreduce_bf16(cx, w.hB, (size_t)M * H, s_));
-        // ---- SwiGLU MLP
-        if (f8) {
-            TRY(cx, linear(w.hB, B(L8.wgu), nullptr, nullptr, L.ln2, w.act, M, 2 * Fl, H, H, H, 0, Fl, c.rms_eps, EPI_SWIGLU, s, L8.sgu));
-        } else if (M == 1) {
-            TRY(cx, linear(w.hB, L.wgu, nullptr, nullptr, L.ln2, w.act, M, 2 * Fl, H, H, H, 0, Fl, c.rms_eps, EPI_SWIGLU, s));
-        } else {
-            if (!fuse_norm) TRY(cx, launch_rmsnorm(w.hB, L.ln2, w.xn, M, H, H, H, c.rms_eps, s));
-            if (f8p) TRY(cx, linear_q8(w, w.xn, H, m->layers8[l].wgu, m->layers8[l].sgu, nullptr, w.act, M, 2 * Fl, H, 0, Fl, EPI_SWIGLU, s));
-            else TRY(cx, linear(w.xn, L.wgu, nullptr, nullptr, nullptr, w.act, M, 2 * Fl, H, H, H, 0, Fl, 0.f, EPI_SWIGLU, s, nullptr, w.splitk, w.splitk_floats));
-        }
-        if (f8) TRY(cx, linear(w.act, B(L8.wdown), nullptr, w.hB, nullptr, hA, M, H, Fl, Fl, Fl, H, H, 0.f, epi_res, s, L8.sdown));
-        else if (f8p) TRY(cx, linear_q8(w, w.act, Fl, m->layers8[l].wdown, m->layers8[l].sdown, w.hB, hA, M, H, Fl, H, H, epi_res, s));
-        else if (fuse_norm && l + 1 < l_end && m->layers[l + 1].ln1) {
-            TRY(cx, linear_then_rmsnorm(w, w.act, L.wdown, w.hB, hA, M, H, Fl, epi_res, m->layers[l + 1].ln1, w.xn, c.rms_eps, true, s));
-            xn_ready = true;
-        }
-        else TRY(cx, linear(w.act, L.wdown, nullptr, w.hB, nullptr, hA, M, H, Fl, Fl, Fl, H, H, 0.f, epi_res, s, nullptr, w.splitk, w.splitk_floats));
-        if (tp) TRY(cx, emu_allreduce_bf16(cx, hA, (size_t)M * H, s_));
-    }
-    return 0;
+    return -22;                                  // (not reached: every path returns above)
 }
 
 size_t emu_beam_step_workspace_bytes(int Bn, int nb, int V) { return beam_step_ws_floats(Bn, nb, V) * sizeof(float); }

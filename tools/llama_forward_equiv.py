@@ -1,0 +1,217 @@
+"""Bit-for-bit check of emu_llama_forward between two builds of libemu_hip.so: seeded cases over every schedule of the forward
+(per-layer launches for decode / prefill / left-padded batch / beam-shaped steps / fp8, decode tail and merged o_proj, the fused
+decode modes 1-4 on the shard-emulation engines, the two-lane tensor-parallel prefill over p2p and 1-rank RCCL).  Per case it
+writes the sha256 of the residual stream forward returned and of the K and V cache it wrote, plus the path counters, as JSON:
+
+    python tools/llama_forward_equiv.py new.json [main|merge|fused|lanes ...]
+    EMU_HIP_TOOLS=1 EMU_HIP_LIB=/path/to/other/libemu_hip.so python tools/llama_forward_equiv.py other.json
+
+Equal files = equal bits in every case (profiles/llama_forward_refactor_equivalence.md)."""
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+BF16 = torch.bfloat16
+out_path = sys.argv[1] if len(sys.argv) > 1 else "llama_forward_equiv.json"
+only = set(sys.argv[2:])
+res = {}
+WAVE = dict(hidden_size=1024, intermediate_size=2048, num_attention_heads=8, num_hidden_layers=3)   # o_proj / down_proj in the wave forms
+
+
+class ShardView:                      # rank 0's 1/tp shard of the model; the comm block sees the 1-rank context
+    def __init__(self, ctx, size):
+        self.__dict__.update(ctx=ctx, tp_rank=0, tp_size=size)
+
+    def __getattr__(self, k):
+        return getattr(self.ctx, k)
+
+
+def make_engine(cfg, vocab, tp=1, comm=None):
+    """comm: None, "p2p" (one-rank peer-to-peer comm block) or "rccl" (one-rank communicator)."""
+    from emu_amd import synth
+    from emu_amd.llama import EmuHipContext, LlamaEngine
+    dev = torch.device("cuda", 0)
+    real = EmuHipContext(dev, 0, 1)
+    if comm == "p2p":
+        real.init_tp(lambda b: b, force=True, allgather_bytes=lambda b: [b], rccl=False)
+    elif comm == "rccl":
+        real.init_tp(lambda b: b, force=True)
+    eng = LlamaEngine(cfg, vocab, ShardView(real, tp) if tp > 1 else real)
+    eng.load_weights(synth.iter_synth(synth.llama_param_shapes(cfg, vocab), seed=3, device=dev, dtype=BF16))
+    return eng, real
+
+
+def decode_run(eng, mode, S, steps):
+    """prefill S random rows, then `steps` greedy steps under set_decode_fused(mode): (ids, hidden after every step)."""
+    from emu_amd import ops
+    from emu_amd.llama import GreedyState
+    eng.set_decode_fused(mode, 0)
+    x = rand(1, S, eng.cfg.hidden_size, seed=0)
+    hidden, kstart, next_pos = eng.prefill(x, torch.ones(1, S, dtype=torch.long), eng.kv_capacity(S + steps + 8))
+    cur = ops.argmax(eng.logits(hidden[:, -1, :].contiguous()), suppress_id=2)
+    out = torch.zeros(steps + 2, 1, device=eng.device, dtype=torch.int32)
+    st = GreedyState(eng, 1, cur, next_pos, S, kstart, out)
+    hs = []
+    for _ in range(steps):
+        st.step()
+        hs.append(st.hidden.clone())
+    torch.cuda.synchronize()
+    return out.clone(), torch.stack(hs)
+
+
+def h(t):
+    torch.cuda.synchronize()
+    return hashlib.sha256(t.detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:24]
+
+
+def rec(name, hidden, eng, extra=None, kv=None):
+    k, v = kv if kv else (eng.kcache, eng.vcache)
+    res[name] = {"hidden": h(hidden), "k": h(k), "v": h(v)}
+    if extra:
+        res[name].update(extra)
+    print(name, res[name], flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
+def want(n):
+    return not only or n in only
+
+
+def rand(*shape, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * 0.1).to(BF16).cuda()
+
+
+def main():
+    from emu_amd._lib import lib
+    from emu_amd.conf.emu_conf import LlamaCfg
+    dev = torch.device("cuda", 0)
+    with torch.no_grad():
+        if want("main"):
+            cfg = LlamaCfg(num_hidden_layers=3)                    # the true LLaMA-33B width
+            eng, _ = make_engine(cfg, 2048)
+            H = cfg.hidden_size
+            # (a) one-row decode steps
+            ids, hs = decode_run(eng, 0, 380, 4)
+            rec("a_decode_1row", hs, eng, {"ids": h(ids)})
+            # (b) B = 1 prefill, S = 770, with the promise; (c) without
+            x = rand(1, 770, H, seed=11)
+            m1 = torch.ones(1, 770, dtype=torch.long)
+            cap = eng.kv_capacity(800)
+            eng.kcache.zero_(); eng.vcache.zero_()
+            hid, _, _ = eng.prefill(x, m1, cap)
+            rec("b_prefill_770_promise", hid, eng)
+            eng.set_prefill_fusion(False)
+            eng.kcache.zero_(); eng.vcache.zero_()
+            hid, _, _ = eng.prefill(x, m1, cap)
+            rec("c_prefill_770_unfused", hid, eng)
+            eng.set_prefill_fusion(True)
+            # (d) B = 2 left padded
+            x2 = rand(2, 300, H, seed=12)
+            m2 = torch.ones(2, 300, dtype=torch.long); m2[1, :37] = 0
+            hid, kstart, next_pos = eng.prefill(x2, m2, eng.kv_capacity(320))
+            rec("d_prefill_B2_leftpad", hid, eng)
+            # (e) single-token steps with 5 and with 20 rows (kv_share on, sticky fused norm)
+            for B, n in ((1, 5), (4, 5)):
+                S = 200
+                xb = rand(B, S, H, seed=13 + B)
+                hid, kstart, next_pos = eng.prefill(xb, torch.ones(B, S, dtype=torch.long), eng.kv_capacity(S + 16))
+                s_max = eng.s_max
+                eng.fan_out_kv(B, n, S, s_max)
+                rows = B * n
+                outs = []
+                for step in range(3):
+                    hx = rand(rows, H, seed=20 + step)
+                    pos = torch.full((rows,), S + step, device=dev, dtype=torch.int32)
+                    slot = torch.full((rows,), S + step, device=dev, dtype=torch.int32)
+                    ks = torch.zeros(rows, device=dev, dtype=torch.int32)
+                    outs.append(eng.forward(hx, rows, 1, pos, slot, ks, ctx=S + step + 1).clone())
+                # (the beam cache is allocated without a zero fill: compare the slots the steps wrote)
+                rec(f"e_beam_rows_{rows}", torch.stack(outs), eng, kv=(eng.kcache[:, :, :, S:S + 3], eng.vcache[:, :, :, S:S + 3]))
+                eng.set_kv_share(0, 0)
+                eng.release_kv()
+            # (i) decode tail, merged o_proj bit (the 33B width is outside gemv_merge_ok: the bit must change nothing here; the
+            # wave engine below takes the merge)
+            eng.set_decode_tail(True)
+            ids, hs = decode_run(eng, 0, 380, 4)
+            rec("i_decode_tail", hs, eng, {"ids": h(ids)})
+            eng.set_decode_tail(False)
+            # (f) fp8 decode with 1 and 2 rows, fp8 prefill
+            eng.quantize_fp8()
+            eng.use_fp8(True)
+            ids, hs = decode_run(eng, 0, 380, 4)
+            rec("f_fp8_decode_1row", hs, eng, {"ids": h(ids)})
+            xb = rand(2, 100, H, seed=31)
+            hid, kstart, next_pos = eng.prefill(xb, torch.ones(2, 100, dtype=torch.long), eng.kv_capacity(116))
+            outs = []
+            for step in range(3):
+                hx = rand(2, H, seed=40 + step)
+                pos = torch.full((2,), 100 + step, device=dev, dtype=torch.int32)
+                outs.append(eng.forward(hx, 2, 1, pos, pos.clone(), torch.zeros(2, device=dev, dtype=torch.int32), ctx=100 + step + 1).clone())
+            rec("f_fp8_decode_2rows", torch.stack(outs), eng)
+            eng.use_fp8(True, prefill=True)
+            eng.release_kv()
+            hid, _, _ = eng.prefill(x, m1, cap)
+            rec("f_fp8_prefill_770", hid, eng)
+            eng.use_fp8(False)
+            del eng
+            torch.cuda.empty_cache()
+        if want("merge"):
+            eng, _ = make_engine(LlamaCfg(**WAVE), 2048)
+            lib().emu_gemm_tune(1 << 19)
+            ids, hs = decode_run(eng, 0, 250, 12)
+            lib().emu_gemm_tune(0)
+            rec("i_merged_o_proj", hs, eng, {"ids": h(ids)})
+            del eng
+        if want("fused"):
+            # (g) modes 1, 2, 3 on the TP = 8 shard emulation, mode 4 on the TP = 4 one
+            eng, _ = make_engine(LlamaCfg(num_hidden_layers=2), 2048, tp=8, comm="p2p")
+            for mode in (0, 1, 2, 3):
+                f0 = eng.decode_fused_stats()[1]
+                ids, hs = decode_run(eng, mode, 200, 5)
+                g, f1 = eng.decode_fused_stats()
+                rec(f"g_tp8_mode{mode}", hs, eng, {"ids": h(ids), "fused_forwards": f1 - f0, "giveups": g})
+            eng.set_decode_fused(0)
+            eng.ctx.check_p2p()
+            del eng
+            cfg = LlamaCfg(hidden_size=4096, intermediate_size=4 * 2048, num_attention_heads=4 * 8, num_hidden_layers=3)
+            eng, _ = make_engine(cfg, 1024, tp=4, comm="p2p")
+            for mode in (0, 4):
+                f0 = eng.decode_fused_stats()[1]
+                ids, hs = decode_run(eng, mode, 250, 10)
+                g, f1 = eng.decode_fused_stats()
+                rec(f"g_tp4_mode{mode}", hs, eng, {"ids": h(ids), "fused_forwards": f1 - f0, "giveups": g})
+            eng.set_decode_fused(0)
+            del eng
+            torch.cuda.empty_cache()
+        for comm, tp, S in (("p2p", 8, 1544), ("rccl", 8, 1544), ("p2p", 4, 1544), ("p2p", 2, 1100)):
+            if not want("lanes"):
+                break
+            # (h) the two-lane schedule as tests/test_gpu_tp_overlap.py drives it (TP = 2: 26 heads, the RoPE epilogue in both lanes;
+            # TP = 4 / 8 shards: 13 / 7 heads, the rope_kv + transpose_v sequence)
+            cfg = LlamaCfg(num_hidden_layers=2)
+            eng, real = make_engine(cfg, 2048, tp=tp, comm=comm)
+            x = rand(1, S, cfg.hidden_size, seed=7)
+            mask = torch.ones(1, S, dtype=torch.long, device=dev)
+            cap = eng.kv_capacity(S + 8)
+            eng.set_tp_overlap(1024)
+            n0 = eng.tp_overlap_count()
+            hid, _, _ = eng.prefill(x, mask, cap)
+            rec(f"h_two_lane_tp{tp}_{comm}", hid, eng, {"overlap_forwards": eng.tp_overlap_count() - n0})
+            eng.set_tp_overlap(0)
+            hid, _, _ = eng.prefill(x, mask, cap)
+            rec(f"h_serial_tp{tp}_{comm}", hid, eng, {"overlap_forwards": eng.tp_overlap_count() - n0 - 1})
+            if comm == "p2p":
+                real.check_p2p()
+            del eng, real
+            torch.cuda.empty_cache()
+    print("EQUIV DONE", flush=True)
+
+
+if __name__ == "__main__":
+    main()
