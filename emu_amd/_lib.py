@@ -94,6 +94,8 @@ _PROTOS = {
     "emu_gemm_plan": (i32, [vp, i32, i32, vp, C.POINTER(i32)]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "emu_quantize_mxfp4_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
+    "emu_linear_fp4w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_rmsnorm_bf16": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "emu_layernorm_bf16": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, vp]),
@@ -123,6 +125,9 @@ _PROTOS = {
     "emu_llama_set_layer_fp8": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_fp8": (i32, [vp, vp, vp]),
     "emu_llama_use_fp8": (i32, [vp, i32]),
+    "emu_llama_set_layer_fp4": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "emu_llama_set_head_fp4": (i32, [vp, vp, vp]),
+    "emu_llama_use_fp4": (i32, [vp, i32]),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),

@@ -77,8 +77,14 @@ int gemv_profiled(double weight_bytes, hipStream_t s, Launch launch) {
 
 int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* res, const bf16_t* norm_w,
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
-           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0) {
+           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0, const uint8_t* w4scale = nullptr,
+           int lds = 0) {
     if (wscale && M > 2) return -22;                 // fp8 weights are a decode-only stream
+    if (w4scale) {                                   // so are MXFP4 weights (gemv_fp4.hip): W = element bytes, ldw in bytes
+        if (M > 2 || (K & 31) || wscale) return -22;
+        GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, nullptr, w4scale, lds};
+        return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemv(g, s); });
+    }
     // rows <= 8 stream the weights through the GEMV family (M >= 2 without a fused norm: skinny MFMA kernel); 9..16
     // rows too when the MFMA kernel covers the shape -- a 128-row GEMM tile would be > 87 % padding there
     const bool skinny = M > 8 && M <= 16 && !norm_w && (K & 31) == 0 && (ldw & 7) == 0 && (lda & 7) == 0 &&
@@ -310,6 +316,17 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
     if (!wscale) return -22;
     return linear(B(A), B(W8), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), wscale);
 }
+int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
+                         const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc, float eps,
+                         int epi, emu_stream_t s) {
+    if (!A || !W4 || !scales || !C || M < 1 || M > 2 || K < 32 || (K & 31)) return -22;
+    return linear(B(A), B(W4), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), nullptr, nullptr, 0,
+                  reinterpret_cast<const uint8_t*>(scales), lds);
+}
+int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
+    if (!w || !q || !scales) return -22;
+    return launch_quant_mxfp4_rows(B(w), ldw, reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(scales), lds, N, K, S(s));
+}
 int emu_linear_fp8_bf16(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const void* bias,
                         const void* res, void* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi,
                         emu_stream_t s) {
@@ -465,6 +482,14 @@ struct emu_llama {
     const float* lm_scale8 = nullptr;
     bool fp8_decode = false;
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2): W8A8 GEMMs for prefill rows as well
+    // optional MXFP4 copies for the decode stream (emu_llama_use_fp4; exclusive with the fp8 stream): element bytes [N, K/2] + E8M0
+    // block scales [N, K/32] of the packed matrices.  Prefill and steps of more than two rows keep the bf16 weights.
+    struct Layer4 { const uint8_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
+                    const uint8_t *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sdown = nullptr; };
+    std::vector<Layer4> layers4;
+    const uint8_t* lm_head4 = nullptr;
+    const uint8_t* lm_scale4 = nullptr;
+    bool fp4_decode = false;
     const bf16_t *final_norm = nullptr, *lm_head = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
     // tensor parallelism: lm_head holds rows [head_row0, head_row0 + head_rows) of the vocabulary only (emu_llama_set_head_shard);
     // head_rows < 0: the whole matrix
@@ -574,10 +599,11 @@ struct LlamaPlan {
     // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
     // fp8_rows       1..2 rows stream the fp8 weight set (decode)
     // fp8_gemm       prefill rows run W8A8 GEMMs in the layers that have fp8 weights
-    // norm_in_gemv   one row, or two with fp8 weights: the weight stream applies the RMSNorm in front of it itself
+    // fp4_rows       1..2 rows stream the MXFP4 weight set (decode; emu_llama_use_fp4, never together with fp8_rows)
+    // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
-    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, norm_in_gemv, decode_tail, merge_o;
+    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, norm_in_gemv, decode_tail, merge_o;
     // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
     // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
     DecodeLayersArgs dl; EngArgs eng;
@@ -592,7 +618,8 @@ struct RowWindow {
     std::function<int(bf16_t*, size_t)> allreduce;   // sums partial rows over the ranks, in the window's stream
 };
 using LaneHook = std::function<int()>;           // what a schedule issues between two launches of the layer body (events of the two lanes)
-struct ProjWeights { const bf16_t* W; const uint8_t* W8; const float* s8; };   // bf16 weight; fp8 weight + per-row scale, or nulls
+struct ProjWeights { const bf16_t* W; const uint8_t* W8; const float* s8;      // bf16 weight; fp8 weight + per-row scale, or nulls;
+                     const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr; };   // MXFP4 elements + block scales, or nulls
 struct LlamaCall {
     emu_llama* m; emu_ctx* cx; LlamaWs ws; hipStream_t s;
     bf16_t* hA;                                  // the residual stream, [M, H]
@@ -627,17 +654,18 @@ struct LlamaCall {
         // prefill with the fp8 weight set: activations are quantised per row ahead of every GEMM, the block-scaled MFMA
         // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
         p.fp8_gemm = m->fp8_prefill && M > 16 && !(H & 127) && !(HD & 127) && !(Fl & 127);
-        p.norm_in_gemv = p.fp8_rows || M == 1;
+        p.fp4_rows = m->fp4_decode && M <= 2;
+        p.norm_in_gemv = p.fp8_rows || p.fp4_rows || M == 1;
         p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
         // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
         // itself, no combine launch (gemv_merge.hip).  Bit-identical and measured LEVEL with the two launches (3.15 vs 3.15-3.18 ms
         // per token of a TP = 8 shard, profiles/r05_tp_emulate_merged_o_proj.log): the merge is a dependent L2 trip inside the
         // projection, which is what the combine launch cost -- one launch less buys nothing here, like the in-kernel split merge
         // and the tail all-reduce before it
-        p.merge_o = T == 1 && M == 1 && !p.fp8_rows && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
+        p.merge_o = T == 1 && M == 1 && !p.fp8_rows && !p.fp4_rows && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
                     (emu_gemm_tune_get() & (1 << 19)) != 0;
 
-        const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && own_kv && some_layers;
+        const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && !m->fp4_decode && own_kv && some_layers;
         // the fence-free peer-to-peer all-reduce is on (which implies tensor parallelism and an opened cx->p2p): what the all-reduces
         // inside a launch build on
         const bool p2p_fence_free = cx->p2p_on && emu_p2p_fenced(cx->p2p) == 0;
@@ -685,6 +713,9 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
+        if (pw.W4 && plan.fp4_rows)
+            return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
+                          pw.s4, K / 32);
         if (pw.W8 && plan.fp8_rows) return linear(A, B(pw.W8), nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, gain_in ? eps : 0.f, epi, s, pw.s8);
         if (pw.W8) return linear_q8(w, A, K, pw.W8, pw.s8, res, C, rows, N, K, ldres, ldc, epi, s);
         if (gain_in) return linear(A, pw.W, nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, eps, epi, s);
@@ -703,6 +734,9 @@ struct LlamaCall {
         return plan.fp8_rows || (plan.fp8_gemm && m->layers8[l].wqkv) ? m->layers8[l] : emu_llama::Layer8{};
     }
 
+    // the MXFP4 weights of layer l where the plan streams them (emu_llama_use_fp4 checked that every layer has them), else nulls
+    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows ? m->layers4[l] : emu_llama::Layer4{}; }
+
     // ---- The decoder layer, written once, in three steps that are cut where the schedules hook in:
     //     layer_kv      RMSNorm, [after_norm], qkv projection (+ RoPE / KV append / V^T in its epilogue, else the rope_kv launch): the
     //                   window's K / V are cached
@@ -714,6 +748,7 @@ struct LlamaCall {
         if (!L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const emu_llama::Layer8 L8 = layer_fp8(l);
         if (plan.fp8_rows && !L8.wqkv) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
+        const emu_llama::Layer4 L4 = layer_fp4(l);
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
@@ -733,7 +768,7 @@ struct LlamaCall {
             if (st == -95) plan.fuse_rope = false;       // the 256x256 tile does not take this shape unsliced: unfused sequence from here on
         }
         if (st == -95)
-            TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, {L.wqkv, L8.wqkv, L8.sqkv}, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
+            TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, {L.wqkv, L8.wqkv, L8.sqkv, L4.wqkv, L4.sqkv}, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
                             nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE));
         if (T == 1) return 0;                            // single-token step: the attention launch rotates and appends
         if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
@@ -747,6 +782,7 @@ struct LlamaCall {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
         const emu_llama::Layer8 L8 = layer_fp8(l);
+        const emu_llama::Layer4 L4 = layer_fp4(l);
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (T == 1) {
@@ -772,7 +808,7 @@ struct LlamaCall {
             GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.wo, win.x, w.hB, H, HD, HD, epi_res, nullptr};
             TRY(cx, gemv_merge_profiled(g, win.s));
         } else
-            TRY(cx, project(w, win.s, w.attn, {L.wo, L8.wo, L8.so}, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
+            TRY(cx, project(w, win.s, w.attn, {L.wo, L8.wo, L8.so, L4.wo, L4.so}, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
         return win.allreduce(w.hB, (size_t)rows * H);
     }
 
@@ -780,13 +816,14 @@ struct LlamaCall {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
         const emu_llama::Layer8 L8 = layer_fp8(l);
+        const emu_llama::Layer4 L4 = layer_fp4(l);
         const int rows = Bn * win.T;
         if (!plan.norm_in_gemv && !plan.fuse_norm) TRY(cx, launch_rmsnorm(w.hB, L.ln2, w.xn, rows, H, H, H, eps, win.s));
-        TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, {L.wgu, L8.wgu, L8.sgu}, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
+        TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, {L.wgu, L8.wgu, L8.sgu, L4.wgu, L4.sgu}, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
                         w.act, rows, 2 * Fl, H, EPI_SWIGLU));
         // (fuse_norm: the RMSNorm behind down_proj is the NEXT layer's input norm, which then finds its rows in w.xn)
         const bf16_t* next_ln1 = plan.fuse_norm && l + 1 < l_end ? m->layers[l + 1].ln1 : nullptr;
-        TRY(cx, project(w, win.s, w.act, {L.wdown, L8.wdown, L8.sdown}, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
+        TRY(cx, project(w, win.s, w.act, {L.wdown, L8.wdown, L8.sdown, L4.wdown, L4.sdown}, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
         if (next_ln1) xn_ready = true;
         return win.allreduce(win.x, (size_t)rows * H);
     }
@@ -1098,6 +1135,36 @@ int emu_llama_set_head_fp8(emu_llama* m, const void* lm_head8, const float* lm_s
     m->lm_head8 = reinterpret_cast<const uint8_t*>(lm_head8); m->lm_scale8 = lm_scale;
     return 0;
 }
+int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const void* sqkv, const void* wo4, const void* so,
+                            const void* wgu4, const void* sgu, const void* wdown4, const void* sdown) {
+    if (!m || layer < 0 || layer >= m->cfg.layers) return -22;
+    if (!wqkv4 || !sqkv || !wo4 || !so || !wgu4 || !sgu || !wdown4 || !sdown) return -22;
+    if (m->layers4.size() != (size_t)m->cfg.layers) m->layers4.assign(m->cfg.layers, emu_llama::Layer4{});
+    auto U = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
+    m->layers4[layer] = {U(wqkv4), U(wo4), U(wgu4), U(wdown4), U(sqkv), U(so), U(sgu), U(sdown)};
+    return 0;
+}
+int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales) {
+    if (!m || !lm_head4 || !lm_scales) return -22;
+    m->lm_head4 = reinterpret_cast<const uint8_t*>(lm_head4); m->lm_scale4 = reinterpret_cast<const uint8_t*>(lm_scales);
+    return 0;
+}
+int emu_llama_use_fp4(emu_llama* m, int enable) {
+    if (!m) return -22;
+    if (enable) {
+        const emu_llama_cfg& c = m->cfg;
+        if (m->fp8_decode)
+            return fail(m->ctx, -22, "emu_llama_use_fp4: the fp8 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp8(m, 0) first)");
+        if ((c.hidden & 31) || ((c.heads_local * c.head_dim) & 31) || (c.ffn_local & 31))
+            return fail(m->ctx, -22, "emu_llama_use_fp4: reduction widths (hidden, heads_local * head_dim, ffn_local) must be multiples of 32");
+        if (m->layers4.size() != (size_t)c.layers || !m->lm_head4)
+            return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
+        for (const auto& l : m->layers4)
+            if (!l.wqkv) return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
+    }
+    m->fp4_decode = enable != 0;
+    return 0;
+}
 int emu_llama_set_decode_tail(emu_llama* m, int enable) {
     if (!m) return -22;
     m->decode_tail = enable != 0;
@@ -1130,6 +1197,8 @@ int emu_llama_set_tp_overlap(emu_llama* m, int min_rows) {
 long emu_llama_tp_overlap_count(const emu_llama* m) { return m ? m->ov_forwards : -1; }
 int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (!m) return -22;
+    if (enable && m->fp4_decode)
+        return fail(m->ctx, -22, "emu_llama_use_fp8: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp4(m, 0) first)");
     if (enable && m->layers8.size() != (size_t)m->cfg.layers)
         return fail(m->ctx, -22, "emu_llama_use_fp8: fp8 layer weights not set");
     m->fp8_decode = enable != 0;
@@ -1264,7 +1333,10 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
         const int N = m->head_rows, n0 = m->head_row0;
         if (hipMemsetAsync(lg, 0, ((size_t)(M - 1) * ld + c.vocab) * sizeof(bf16_t), S(s)) != hipSuccess)
             return fail(cx, -5, "emu_llama_logits: hipMemsetAsync");
-        if (m->fp8_decode && M <= 2 && m->lm_head8) {             // the e4m3 copy covers the same rows (quantised from the shard)
+        if (m->fp4_decode && M <= 2) {                            // the MXFP4 copy covers the same rows (quantised from the shard)
+            TRY(cx, linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden / 2, 0, ld,
+                           c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32));
+        } else if (m->fp8_decode && M <= 2 && m->lm_head8) {      // the e4m3 copy covers the same rows (quantised from the shard)
             TRY(cx, linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden, 0, ld,
                            c.rms_eps, EPI_NONE, S(s), m->lm_scale8));
         } else if (M == 1 || (M <= 8 && ws_bytes < (size_t)M * c.hidden * 2)) {
@@ -1280,6 +1352,9 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
         for (int r = 0; r < M; ++r) TRY(cx, emu_allreduce_bf16(cx, lg + (size_t)r * ld, (size_t)c.vocab, s));
         return 0;
     }
+    if (m->fp4_decode && M <= 2)
+        return linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh, c.hidden / 2, 0, ld,
+                      c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32);
     if (m->fp8_decode && M <= 2 && m->lm_head8)
         return linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh,
                       c.hidden, 0, ld, c.rms_eps, EPI_NONE, S(s), m->lm_scale8);

@@ -11,6 +11,7 @@
 //   gemv_wave_kernel M = 1, K <= 2560: one wave per 4 whole rows, no LDS / barrier (TP-shard o_proj / down_proj).
 //   gemv_mfma_kernel 9..16 rows on v_mfma_f32_16x16x32_bf16.
 //   gemv_fp8_*       optional e4m3 weight stream (per-row scale).
+//   (gemv_fp4.hip)   optional MXFP4 weight stream (4-bit elements, one E8M0 scale per 32), M <= 2.
 //
 // Replaces (reference call sites): LlamaDecoderLayer linears + RMSNorm reached from Emu2/emu/emu.py:133-138
 // and :213-229 at S=1 (greedy: 1 row; beam search: num_beams rows), project_up/project_down emu.py:131,147.
@@ -1004,6 +1005,7 @@ int emu_gemv_partition(int N, int K, bool norm, int epi) {
 }
 
 int launch_gemv(const GemvArgs& a, hipStream_t s) {
+    if (a.w4scale) return a.wscale ? -22 : launch_gemv_fp4(a, s);     // MXFP4 weight stream (gemv_fp4.hip)
     if (a.M < 1 || a.M > 16 || (a.K & 7) || a.N < 1) return -22;
     if (a.epi == EPI_SWIGLU && (a.N & 1)) return -22;
     // 9..16 rows: the 16x16x32 MFMA stream.  Up to 8 rows the v_dot2c block kernel is faster (M = 2: 6.4 vs 4.1 TB/s,

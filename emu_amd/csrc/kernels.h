@@ -22,8 +22,18 @@ struct GemvArgs {
     int epi;
     int rows_per_block;     // 0 = heuristic
     const float* wscale;    // non-null: W holds OCP fp8 e4m3 bytes [N, ldw] with one fp32 scale per row (K % 16 == 0)
+    // non-null: W holds MXFP4 element bytes [N, ldw] (two E2M1 codes per byte, ldw in bytes) and w4scale the E8M0 block scales
+    // [N, lds], one per 32 elements (K % 32 == 0, M <= 2): gemv_fp4.hip
+    const uint8_t* w4scale = nullptr;
+    int lds = 0;
 };
 int launch_gemv(const GemvArgs& a, hipStream_t s);
+// the MXFP4 weight stream (gemv_fp4.hip; launch_gemv forwards to it when a.w4scale is set) and its quantiser: bf16 [N, ldw] ->
+// element bytes [N, ldq] + E8M0 scales [N, lds], bit-exact with emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the
+// call waits for its own result)
+int launch_gemv_fp4(const GemvArgs& a, hipStream_t s);
+int launch_quant_mxfp4_rows(const bf16_t* w, int ldw, uint8_t* q, int ldq, uint8_t* scales, int lds, int N, int K, hipStream_t s);
+void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
 // o_proj of a tensor-parallel shard's one-row step with the decode attention's split merge in its prologue (gemv_merge.hip):
 // x = merge of the live splits in decode_fused_kernel's workspace (batch row 0), out = epi(x W^T [+ res]); bit-identical to
 // decode_fused_combine_kernel followed by the wave-form GEMV.  K = H * 128 <= 1024, nsplit <= 8, N >= 1024 (gemv_merge_ok).

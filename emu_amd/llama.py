@@ -13,7 +13,7 @@ from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import mxfp4, ops
 from ._lib import EmuHipError, LlamaCfgC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .tp import ShardPlan
@@ -339,9 +339,13 @@ class LlamaEngine:
 
     def weight_bytes_per_token(self) -> int:
         """Algorithmic bytes one decode step of THIS shard must stream (all packed matrices once + lm_head)."""
-        b = 1 if getattr(self, "fp8_decode", False) else 2
-        per = sum(v.numel() * b for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
-        return per + (self.lm_head.numel() * b if self.lm_head is not None else 0)
+        if getattr(self, "fp4_decode", False):             # MXFP4: K/2 element bytes + K/32 scale bytes per row
+            size = lambda v: v.shape[0] * mxfp4.bytes_per_row(v.shape[1])
+        else:
+            b = 1 if getattr(self, "fp8_decode", False) else 2
+            size = lambda v: v.numel() * b
+        per = sum(size(v) for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
+        return per + (size(self.lm_head) if self.lm_head is not None else 0)
 
     # ------------------------------------------------------------------ optional fp8 decode stream
     def quantize_fp8(self) -> None:
@@ -377,6 +381,78 @@ class LlamaEngine:
         """fp32 value of a registered fp8 tensor (tests: feed the oracle the exact weights the stream uses)."""
         q, sc = self._fp8[key]
         return q.view(torch.float8_e4m3fn).to(torch.float32) * sc[:, None]
+
+    # ------------------------------------------------------------------ optional MXFP4 decode stream
+    _FP4_KINDS = ("wqkv", "wo", "wgu", "wdown")
+
+    def _fp4_source(self, key: str) -> torch.Tensor:
+        """The packed (and sharded) bf16 matrix an fp4 key stands for: "<layer>.wqkv|wo|wgu|wdown" or "lm_head"."""
+        if key == "lm_head":
+            return self.lm_head
+        layer, _, kind = key.partition(".")
+        if kind not in self._FP4_KINDS or not layer.isdigit() or int(layer) >= self.cfg.num_hidden_layers:
+            raise KeyError(f"fp4 key {key!r}: expected '<layer>.wqkv|wo|wgu|wdown' or 'lm_head'")
+        return self._keep[key]
+
+    def _fp4_keys(self):
+        return [f"{i}.{k}" for i in range(self.cfg.num_hidden_layers) for k in self._FP4_KINDS] + ["lm_head"]
+
+    def _fp4_register(self, key: str) -> None:
+        """Hand the library the pointers of a layer once its four matrices are here (or of the head)."""
+        if key == "lm_head":
+            q, sc = self._fp4[key]
+            check(lib().emu_llama_set_head_fp4(self.handle, q.data_ptr(), sc.data_ptr()), "emu_llama_set_head_fp4", self.ctx.handle)
+            return
+        i = key.split(".")[0]
+        if all(f"{i}.{k}" in self._fp4 for k in self._FP4_KINDS):
+            a = [t.data_ptr() for k in self._FP4_KINDS for t in self._fp4[f"{i}.{k}"]]
+            check(lib().emu_llama_set_layer_fp4(self.handle, int(i), *a), "emu_llama_set_layer_fp4", self.ctx.handle)
+
+    def quantize_fp4(self) -> None:
+        """Build MXFP4 copies (4-bit elements, one power-of-two scale per 32: ``emu_amd.mxfp4``) of every packed matrix and of
+        lm_head with the device quantiser and register them for the decode stream (B*T <= 2 rows).  Keys already provided through
+        ``load_fp4`` are kept.  Prefill and steps of more rows keep the bf16 weights, so both sets stay resident (33B: bf16 66 GB +
+        fp4 17 GB).  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
+        if not self.ready:
+            raise RuntimeError("quantize_fp4: load all weights first")
+        self.__dict__.setdefault("_fp4", {})
+        for key in self._fp4_keys():
+            if key not in self._fp4:
+                self._fp4[key] = ops.quantize_mxfp4_rows(self._fp4_source(key))
+                self._fp4_register(key)
+
+    def load_fp4(self, key: str, packed: torch.Tensor, scales: torch.Tensor) -> None:
+        """Register externally prepared MXFP4 tensors (``mxfp4.quantize_rows`` or any quantiser that writes the format) for
+        ``"<layer>.wqkv|wo|wgu|wdown"`` or ``"lm_head"``: ``packed`` uint8 [N, K/2], ``scales`` uint8 [N, K/32] for the [N, K] packed
+        bf16 matrix of this rank (the tensor-parallel shard; lm_head: the rows this rank holds)."""
+        src = self._fp4_source(key)
+        if src is None:
+            raise RuntimeError(f"load_fp4({key!r}): load the bf16 weights first (their packed shapes define the fp4 shapes)")
+        N, K = src.shape
+        if K % 32:
+            raise ValueError(f"load_fp4({key!r}): K = {K} is not a multiple of 32")
+        for name, t, shape in (("packed", packed, (N, K // 2)), ("scales", scales, (N, K // 32))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != shape:
+                raise ValueError(f"load_fp4({key!r}): {name} must be uint8 {shape}, got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if getattr(self, "fp4_decode", False):
+            raise RuntimeError("load_fp4: switch the fp4 stream off first (use_fp4(False)); captured graphs hold the old pointers")
+        self.__dict__.setdefault("_fp4", {})
+        self._fp4[key] = (packed.to(self.device).contiguous(), scales.to(self.device).contiguous())
+        self._fp4_register(key)
+
+    def use_fp4(self, enable: bool = True) -> None:
+        """Switch the decode stream between the bf16 and the MXFP4 weights (invalidates captured decode graphs).  Whatever was not
+        provided through ``load_fp4`` is quantised on the device first.  Exclusive with ``use_fp8``."""
+        if enable and not getattr(self, "fp8_decode", False):      # (with fp8 on, the library refuses and says why)
+            self.quantize_fp4()
+        check(lib().emu_llama_use_fp4(self.handle, 1 if enable else 0), "emu_llama_use_fp4", self.ctx.handle)
+        self.fp4_decode = bool(enable)
+        self._mode_changed()
+
+    def fp4_dequantized(self, key: str) -> torch.Tensor:
+        """fp32 value of a registered MXFP4 tensor (exact in bf16; tests feed the oracle the weights the stream uses)."""
+        return mxfp4.dequantize(*self._fp4[key])
 
     # ------------------------------------------------------------------ KV cache / workspace
     KV_BUCKETS = (256, 512, 1024)

@@ -113,6 +113,40 @@ def quantize_fp8_rows(w):
     return q, sc
 
 
+def quantize_mxfp4_rows(w):
+    """Round-to-nearest MXFP4 quantisation of a packed bf16 weight [N, K] (K % 32 == 0) on the device: returns (element bytes
+    uint8 [N, K/2], E8M0 scales uint8 [N, K/32]), bit-exact with ``emu_amd.mxfp4.quantize_rows``; see emu_quantize_mxfp4_rows."""
+    _req(w, "w")
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    sc = torch.empty(N, K // 32, device=w.device, dtype=torch.uint8)
+    check(lib().emu_quantize_mxfp4_rows(_p(w), w.stride(0), _p(q), q.stride(0), _p(sc), sc.stride(0), N, K, stream(w)),
+          "emu_quantize_mxfp4_rows")
+    return q, sc
+
+
+def linear_fp4w(x, w4, scales, bias=None, res=None, norm_w=None, eps: float = 0.0, epi: int = EPI_NONE, out=None):
+    """``linear`` over an MXFP4 weight stream (decode rows only, M <= 2; K % 32 == 0); see emu_linear_fp4w_bf16."""
+    _req(x, "x"); _req(w4, "w4", torch.uint8); _req(scales, "scales", torch.uint8)
+    assert x.dim() == 2 and w4.dim() == 2 and scales.dim() == 2 and w4.shape[0] == scales.shape[0], (x.shape, w4.shape, scales.shape)
+    assert w4.stride(1) == 1 and scales.stride(1) == 1
+    M, K = x.shape
+    N = w4.shape[0]
+    if K % 32 == 0:                                # (any other K is the library's to refuse)
+        assert w4.shape[1] == K // 2 and scales.shape[1] == K // 32, (x.shape, w4.shape, scales.shape)
+    cols = N // 2 if epi == EPI_SWIGLU else N
+    if out is None:
+        out = torch.empty(M, cols, device=x.device, dtype=BF16)
+    _req(out, "out")
+    if res is not None:
+        _req(res, "res")
+    check(lib().emu_linear_fp4w_bf16(_p(x), _p(w4), _p(scales), _p(bias), _p(res), _p(norm_w), _p(out), M, N, K,
+                                     x.stride(0), w4.stride(0), scales.stride(0), res.stride(0) if res is not None else 0,
+                                     out.stride(0), float(eps), int(epi), stream(x)), "emu_linear_fp4w_bf16")
+    return out
+
+
 def linear_fp8(x8, xscale, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):
     """fp8 x fp8 GEMM (both operands from ``quantize_fp8_rows``) -> bf16; see emu_linear_fp8_bf16."""
     _req(x8, "x8", torch.uint8); _req(w8, "w8", torch.uint8)

@@ -110,7 +110,8 @@ int emu_gemm_plan(const emu_gemm_shape* shape, int force_cfg, int tune, emu_gemm
  * bits 21-23 (round 6, the four-wave 256x256 tile of gemm_w4.hip): 21 = never take it (the eight-wave ping-pong
  * tile everywhere: the same-run A/B twin), 22 = take it wherever it is instantiated (tests: bf16 plain GEMMs and convs of the
  * 256x256 configuration, whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of
- * through LDS. */
+ * through LDS; bits 24-25 (the MXFP4 weight stream, gemv_fp4.hip; tools/fp4_time.py --ab): 1 / 2 / 3 = 1 / 2 / 4 row sets per
+ * workgroup instead of the planned number, bits 26-27: 1 / 2 = 4 / 8 weight rows per lane. */
 void emu_gemm_tune(int mask);
 
 /* Tools hook (tools/gemm_trace.py): per-workgroup timelines of the following GEMM launches -- 8 x uint64 per workgroup at
@@ -162,6 +163,22 @@ int emu_linear_fp8_bf16(const void* A8, const float* a_scale, const void* W8, co
                         emu_stream_t s);
 int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc,
+                         float eps, int epi, emu_stream_t s);
+/* MXFP4 (OCP microscaling) weights, the 4-bit weight-only stream; emu_amd/mxfp4.py is the definition of the format.
+ *   elements  uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j+1 in the high nibble; a code is a sign bit (8) and an
+ *             E2M1 magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}
+ *   scales    uint8 [N, K/32], E8M0: one per 32 consecutive elements of a row, 2^(byte - 127)
+ * emu_quantize_mxfp4_rows: round-to-nearest of a bf16 matrix [N, ldw], K % 32 == 0, ldq % 16 == 0.  Per block, amax > 0:
+ * e = floor(log2(amax)) - 2 clamped to [-126, 125], magnitudes rounded to the nearest grid point of w / 2^e (ties to the even code,
+ * above 6 saturates), sign kept; an all-zero block gets byte 127; byte 255 is never produced.  Non-finite weights: -22 (the call
+ * waits for its own result, so it must not be issued into a stream capture).
+ * emu_linear_fp4w_bf16: emu_linear_bf16 over such a weight, M <= 2 and K % 32 == 0 (else -22), ldw in bytes (% 16 == 0), epi in
+ * {NONE, RESID, SWIGLU}, optional bias and fused RMSNorm (norm_w, eps) as emu_linear_fp8w_bf16:
+ *   out = epi(bf16(sum_k fp4(W4[n,k]) * 2^(scales[n,k/32] - 127) * x[k] + bias[n]))   (fp32 accumulation, scale applied per block)
+ * Not a reference feature; what round-to-nearest MXFP4 does to a trained checkpoint is NOT measured by this project. */
+int emu_quantize_mxfp4_rows(const void* w_bf16, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s);
+int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
+                         const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc,
                          float eps, int epi, emu_stream_t s);
 /* emu_linear_bf16 (M > 8, epi in {NONE, RESID, GEGLU}) with the fused epilogues of the UNet transformer blocks -- what
  * diffusers' BasicTransformerBlock computes as LayerNorm -> Linear (norm1/2/3 ahead of attn1.to_q/k/v, attn2.to_q,
@@ -324,6 +341,18 @@ int emu_llama_set_layer_fp8(emu_llama* m, int layer, const void* wqkv8, const fl
                             const float* sdown);
 int emu_llama_set_head_fp8(emu_llama* m, const void* lm_head8, const float* lm_scale);
 int emu_llama_use_fp8(emu_llama* m, int enable);
+/* Optional MXFP4 decode stream (not in the reference; 0.53125 byte per weight, 0.53 of the fp8 stream's bytes).  W4 / scales: the
+ * two tensors of emu_quantize_mxfp4_rows over the SAME packed (and, under tensor parallelism, sharded) bf16 matrix -- or prepared
+ * offline by any quantiser that writes the format (emu_amd/mxfp4.py).  emu_llama_set_head_fp4 covers the rows the bf16 lm_head
+ * pointer holds (emu_llama_set_head_shard is honoured).  emu_llama_use_fp4(m, 1): steps of B*T <= 2 rows stream the 4-bit set
+ * through the per-layer launches; prefill and steps of more rows keep the bf16 weights, so both sets stay resident.  It fails
+ * (-22) unless every layer and the head are registered, if hidden, heads_local*head_dim or ffn_local is not a multiple of 32, and
+ * while the fp8 stream is on; emu_llama_use_fp8 fails while the fp4 stream is on (the two streams are exclusive).  The fused-layer
+ * modes, the persistent engine and the merged o_proj do not run in this mode.  Accuracy on a trained checkpoint is unmeasured. */
+int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const void* sqkv, const void* wo4, const void* so,
+                            const void* wgu4, const void* sgu, const void* wdown4, const void* sdown);
+int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales);
+int emu_llama_use_fp4(emu_llama* m, int enable);
 /* Vocabulary-sharded lm_head under tensor parallelism (the reference's lm_head is lm.lm_head of LlamaForCausalLM reached
  * from Emu2/emu/emu.py:213-229): the lm_head pointer of emu_llama_set_head holds rows [row0, row0 + rows) of the vocabulary only;
  * emu_llama_logits fills this rank's columns of the caller's [M, vocab] rows, zeroes the others and all-reduces the rows, so every
