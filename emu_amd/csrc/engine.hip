@@ -99,6 +99,13 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     g.partial = splitk; g.partial_floats = splitk_floats;
     return launch_gemm(g, s);
 }
+// 1..16 rows over MXFP4 weights on the matrix cores (gemv_fp4_thin.hip): no fused norm, ldw = K / 2 bytes and lds = K / 32 unless given
+int linear_fp4_thin(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
+                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s) {
+    GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
+    if (!gemv_fp4_thin_ok(g)) return -22;
+    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemv_fp4_thin(g, s); });
+}
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
     return gemv_profiled(2.0 * (double)g.N * (double)g.K, s, [&] { return launch_gemv_merge(g, s); });
@@ -142,7 +149,7 @@ void emu_prof_end(hipStream_t s, const char* klass, int M, int N, int K, int tag
 
 extern "C" {
 
-int emu_version(void) { return 3; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
+int emu_version(void) { return 4; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
 void emu_gemm_force_config(int cfg) { emu_gemm_force_config_set(cfg); }
@@ -323,6 +330,12 @@ int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, cons
     return linear(B(A), B(W4), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), nullptr, nullptr, 0,
                   reinterpret_cast<const uint8_t*>(scales), lds);
 }
+int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
+    if (!A || !W4 || !scales || !C) return -22;
+    return linear_fp4_thin(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
+                           lda, ldw, lds, ldres, ldc, epi, S(s));
+}
 int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
     if (!w || !q || !scales) return -22;
     return launch_quant_mxfp4_rows(B(w), ldw, reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(scales), lds, N, K, S(s));
@@ -483,13 +496,15 @@ struct emu_llama {
     bool fp8_decode = false;
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2): W8A8 GEMMs for prefill rows as well
     // optional MXFP4 copies for the decode stream (emu_llama_use_fp4; exclusive with the fp8 stream): element bytes [N, K/2] + E8M0
-    // block scales [N, K/32] of the packed matrices.  Prefill and steps of more than two rows keep the bf16 weights.
+    // block scales [N, K/32] of the packed matrices.  Prefill and steps of more than two rows keep the bf16 weights, unless fp4_wide
+    // (emu_llama_use_fp4(m, 2)) sends steps of 3..16 rows through the matrix-core stream (gemv_fp4_thin.hip).
     struct Layer4 { const uint8_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
                     const uint8_t *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sdown = nullptr; };
     std::vector<Layer4> layers4;
     const uint8_t* lm_head4 = nullptr;
     const uint8_t* lm_scale4 = nullptr;
     bool fp4_decode = false;
+    bool fp4_wide = false;
     const bf16_t *final_norm = nullptr, *lm_head = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
     // tensor parallelism: lm_head holds rows [head_row0, head_row0 + head_rows) of the vocabulary only (emu_llama_set_head_shard);
     // head_rows < 0: the whole matrix
@@ -600,10 +615,11 @@ struct LlamaPlan {
     // fp8_rows       1..2 rows stream the fp8 weight set (decode)
     // fp8_gemm       prefill rows run W8A8 GEMMs in the layers that have fp8 weights
     // fp4_rows       1..2 rows stream the MXFP4 weight set (decode; emu_llama_use_fp4, never together with fp8_rows)
+    // fp4_thin       3..16 rows stream the MXFP4 weight set through the matrix cores (emu_llama_use_fp4(m, 2)); norms stay launches
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
-    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, norm_in_gemv, decode_tail, merge_o;
+    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, fp4_thin, norm_in_gemv, decode_tail, merge_o;
     // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
     // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
     DecodeLayersArgs dl; EngArgs eng;
@@ -655,6 +671,7 @@ struct LlamaCall {
         // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
         p.fp8_gemm = m->fp8_prefill && M > 16 && !(H & 127) && !(HD & 127) && !(Fl & 127);
         p.fp4_rows = m->fp4_decode && M <= 2;
+        p.fp4_thin = m->fp4_wide && M >= 3 && M <= 16;
         p.norm_in_gemv = p.fp8_rows || p.fp4_rows || M == 1;
         p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
         // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
@@ -713,6 +730,7 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
+        if (pw.W4 && plan.fp4_thin) return linear_fp4_thin(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s);
         if (pw.W4 && plan.fp4_rows)
             return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
                           pw.s4, K / 32);
@@ -735,7 +753,7 @@ struct LlamaCall {
     }
 
     // the MXFP4 weights of layer l where the plan streams them (emu_llama_use_fp4 checked that every layer has them), else nulls
-    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows ? m->layers4[l] : emu_llama::Layer4{}; }
+    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows || plan.fp4_thin ? m->layers4[l] : emu_llama::Layer4{}; }
 
     // ---- The decoder layer, written once, in three steps that are cut where the schedules hook in:
     //     layer_kv      RMSNorm, [after_norm], qkv projection (+ RoPE / KV append / V^T in its epilogue, else the rope_kv launch): the
@@ -1161,8 +1179,11 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
             return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
         for (const auto& l : m->layers4)
             if (!l.wqkv) return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
+        if (enable == 2 && ((c.hidden & 255) || ((c.heads_local * c.head_dim) & 255) || (c.ffn_local & 255)))
+            return fail(m->ctx, -22, "emu_llama_use_fp4: mode 2 (3..16-row steps) needs reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
     }
     m->fp4_decode = enable != 0;
+    m->fp4_wide = enable == 2;
     return 0;
 }
 int emu_llama_set_decode_tail(emu_llama* m, int enable) {
@@ -1336,6 +1357,10 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
         if (m->fp4_decode && M <= 2) {                            // the MXFP4 copy covers the same rows (quantised from the shard)
             TRY(cx, linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden / 2, 0, ld,
                            c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32));
+        } else if (m->fp4_wide && M >= 3 && M <= 16 && ws_bytes >= (size_t)M * c.hidden * 2) {    // 3..16 rows: norm launch, then the matrix-core stream
+            TRY(cx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
+            TRY(cx, linear_fp4_thin(B(workspace), m->lm_head4, m->lm_scale4, nullptr, nullptr, lg + n0, M, N, c.hidden, c.hidden, c.hidden / 2,
+                                    c.hidden / 32, 0, ld, EPI_NONE, S(s)));
         } else if (m->fp8_decode && M <= 2 && m->lm_head8) {      // the e4m3 copy covers the same rows (quantised from the shard)
             TRY(cx, linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden, 0, ld,
                            c.rms_eps, EPI_NONE, S(s), m->lm_scale8));
@@ -1355,6 +1380,11 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
     if (m->fp4_decode && M <= 2)
         return linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh, c.hidden / 2, 0, ld,
                       c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32);
+    if (m->fp4_wide && M >= 3 && M <= 16 && ws_bytes >= (size_t)M * c.hidden * 2) {
+        TRY(m->ctx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
+        return linear_fp4_thin(B(workspace), m->lm_head4, m->lm_scale4, nullptr, nullptr, B(logits), M, c.vocab, c.hidden, c.hidden, c.hidden / 2,
+                               c.hidden / 32, 0, ld, EPI_NONE, S(s));
+    }
     if (m->fp8_decode && M <= 2 && m->lm_head8)
         return linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh,
                       c.hidden, 0, ld, c.rms_eps, EPI_NONE, S(s), m->lm_scale8);

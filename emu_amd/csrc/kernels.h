@@ -52,6 +52,10 @@ int launch_gemv_merge(const GemvMergeArgs& a, hipStream_t s);
 // 2..16 rows through LDS-DMA stages and v_mfma_f32_16x16x32_bf16 (gemv_thin.hip); needs K % 256 == 0, no fused norm, bf16 weights
 bool gemv_thin_ok(const GemvArgs& a);
 int launch_gemv_thin(const GemvArgs& a, hipStream_t s);
+// 1..16 rows over MXFP4 weights (a.w4scale set; W = element bytes, ldw in bytes) through LDS-DMA stages, v_cvt_scalef32_pk_bf16_fp4 and
+// v_mfma_f32_16x16x32_bf16 (gemv_fp4_thin.hip); needs K % 256 == 0, lds % 4 == 0, no fused norm; epi NONE / RESID / SWIGLU
+bool gemv_fp4_thin_ok(const GemvArgs& a);
+int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

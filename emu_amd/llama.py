@@ -410,9 +410,9 @@ class LlamaEngine:
 
     def quantize_fp4(self) -> None:
         """Build MXFP4 copies (4-bit elements, one power-of-two scale per 32: ``emu_amd.mxfp4``) of every packed matrix and of
-        lm_head with the device quantiser and register them for the decode stream (B*T <= 2 rows).  Keys already provided through
-        ``load_fp4`` are kept.  Prefill and steps of more rows keep the bf16 weights, so both sets stay resident (33B: bf16 66 GB +
-        fp4 17 GB).  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
+        lm_head with the device quantiser and register them for the decode stream (B*T <= 2 rows; with ``use_fp4(wide=True)`` also
+        steps of 3..16 rows).  Keys already provided through ``load_fp4`` are kept.  Prefill and steps of more rows keep the bf16
+        weights, so both sets stay resident (33B: bf16 66 GB + fp4 17 GB).  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
         if not self.ready:
             raise RuntimeError("quantize_fp4: load all weights first")
         self.__dict__.setdefault("_fp4", {})
@@ -441,13 +441,20 @@ class LlamaEngine:
         self._fp4[key] = (packed.to(self.device).contiguous(), scales.to(self.device).contiguous())
         self._fp4_register(key)
 
-    def use_fp4(self, enable: bool = True) -> None:
+    def use_fp4(self, enable: bool = True, wide: bool = False) -> None:
         """Switch the decode stream between the bf16 and the MXFP4 weights (invalidates captured decode graphs).  Whatever was not
-        provided through ``load_fp4`` is quantised on the device first.  Exclusive with ``use_fp8``."""
+        provided through ``load_fp4`` is quantised on the device first.  Exclusive with ``use_fp8``.
+
+        ``use_fp4(True)``: steps of B*T <= 2 rows (greedy / sampled decode) stream the 4-bit set; everything else streams bf16.
+        ``use_fp4(True, wide=True)``: steps of 3..16 rows (the default 5-beam search, a batch of prompts, contrastive search) stream
+        the 4-bit set as well, through the matrix-core kernel (csrc/gemv_fp4_thin.hip); needs hidden, heads_local * head_dim and
+        ffn_local to be multiples of 256 (the library refuses otherwise and says why).  Prefill and steps of more than 16 rows
+        stream bf16 in every mode."""
         if enable and not getattr(self, "fp8_decode", False):      # (with fp8 on, the library refuses and says why)
             self.quantize_fp4()
-        check(lib().emu_llama_use_fp4(self.handle, 1 if enable else 0), "emu_llama_use_fp4", self.ctx.handle)
+        check(lib().emu_llama_use_fp4(self.handle, (2 if wide else 1) if enable else 0), "emu_llama_use_fp4", self.ctx.handle)
         self.fp4_decode = bool(enable)
+        self.fp4_wide = bool(enable and wide)
         self._mode_changed()
 
     def fp4_dequantized(self, key: str) -> torch.Tensor:

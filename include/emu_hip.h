@@ -111,7 +111,8 @@ int emu_gemm_plan(const emu_gemm_shape* shape, int force_cfg, int tune, emu_gemm
  * tile everywhere: the same-run A/B twin), 22 = take it wherever it is instantiated (tests: bf16 plain GEMMs and convs of the
  * 256x256 configuration, whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of
  * through LDS; bits 24-25 (the MXFP4 weight stream, gemv_fp4.hip; tools/fp4_time.py --ab): 1 / 2 / 3 = 1 / 2 / 4 row sets per
- * workgroup instead of the planned number, bits 26-27: 1 / 2 = 4 / 8 weight rows per lane. */
+ * workgroup instead of the planned number, bits 26-27: 1 / 2 = 4 / 8 weight rows per lane; bits 28-29 (the few-row MXFP4 stream,
+ * gemv_fp4_thin.hip; tools/fp4_wide_time.py --ab): 1 / 2 = 16 / 32 weight rows per workgroup instead of the heuristic. */
 void emu_gemm_tune(int mask);
 
 /* Tools hook (tools/gemm_trace.py): per-workgroup timelines of the following GEMM launches -- 8 x uint64 per workgroup at
@@ -175,11 +176,17 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
  * emu_linear_fp4w_bf16: emu_linear_bf16 over such a weight, M <= 2 and K % 32 == 0 (else -22), ldw in bytes (% 16 == 0), epi in
  * {NONE, RESID, SWIGLU}, optional bias and fused RMSNorm (norm_w, eps) as emu_linear_fp8w_bf16:
  *   out = epi(bf16(sum_k fp4(W4[n,k]) * 2^(scales[n,k/32] - 127) * x[k] + bias[n]))   (fp32 accumulation, scale applied per block)
+ * emu_linear_fp4w_thin_bf16: the same product for 1 <= M <= 16 rows on the matrix cores (gemv_fp4_thin.hip: LDS-DMA stages, the block
+ * scale applied by v_cvt_scalef32_pk_bf16_fp4, v_mfma_f32_16x16x32_bf16, fp32 accumulation), same epilogues and rounding points, no
+ * fused RMSNorm (normalise first).  N >= 1, K >= 256 and K % 256 == 0, ldw % 16 == 0 (bytes), lda % 8 == 0, lds % 4 == 0, A / W4
+ * 16-byte aligned, N even under SWIGLU; anything else -22.  emu_linear_fp4w_bf16 keeps answering -22 for M > 2.
  * Not a reference feature; what round-to-nearest MXFP4 does to a trained checkpoint is NOT measured by this project. */
 int emu_quantize_mxfp4_rows(const void* w_bf16, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s);
 int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc,
                          float eps, int epi, emu_stream_t s);
+int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
 /* emu_linear_bf16 (M > 8, epi in {NONE, RESID, GEGLU}) with the fused epilogues of the UNet transformer blocks -- what
  * diffusers' BasicTransformerBlock computes as LayerNorm -> Linear (norm1/2/3 ahead of attn1.to_q/k/v, attn2.to_q,
  * ff.net.0.proj; Emu2/emu/diffusion.py:136-141), without a LayerNorm launch in between:
@@ -348,7 +355,12 @@ int emu_llama_use_fp8(emu_llama* m, int enable);
  * through the per-layer launches; prefill and steps of more rows keep the bf16 weights, so both sets stay resident.  It fails
  * (-22) unless every layer and the head are registered, if hidden, heads_local*head_dim or ffn_local is not a multiple of 32, and
  * while the fp8 stream is on; emu_llama_use_fp8 fails while the fp4 stream is on (the two streams are exclusive).  The fused-layer
- * modes, the persistent engine and the merged o_proj do not run in this mode.  Accuracy on a trained checkpoint is unmeasured. */
+ * modes, the persistent engine and the merged o_proj do not run in this mode.  Accuracy on a trained checkpoint is unmeasured.
+ * emu_llama_use_fp4(m, 2) is mode 1 plus: every forward / logits call of 3 <= B*T <= 16 rows (a 5-beam step, a batch of prompts,
+ * contrastive search) streams the 4-bit set through emu_linear_fp4w_thin_bf16's kernel -- qkv, o_proj, gate/up, down and the head
+ * (whole or emu_llama_set_head_shard rows); the RMSNorm launches of the bf16 few-row path stay, attention is untouched.  It also
+ * fails (-22) if hidden, heads_local*head_dim or ffn_local is not a multiple of 256 (TP = 4 / 8 shards of the 33B shapes: keep mode 1).
+ * Steps of 17 rows and more, and prefill, keep the bf16 weights in every mode. */
 int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const void* sqkv, const void* wo4, const void* so,
                             const void* wgu4, const void* sgu, const void* wdown4, const void* sdown);
 int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales);
