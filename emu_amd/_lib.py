@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # announced on stderr, and the loaded library must report this binding's ABI version either way.
 _OVERRIDE = os.environ.get("EMU_HIP_LIB") if os.environ.get("EMU_HIP_TOOLS") == "1" else None
 LIB_PATH = _OVERRIDE or os.path.join(HERE, "csrc", "libemu_hip.so")
-ABI_VERSION = 4            # emu_version() of the library these prototypes and struct layouts belong to
+ABI_VERSION = 5            # emu_version() of the library these prototypes and struct layouts belong to
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "emu_hip.h")
 
 
@@ -126,9 +126,11 @@ _PROTOS = {
     "emu_llama_set_head_fp8": (i32, [vp, vp, vp]),
     "emu_llama_use_fp8": (i32, [vp, i32]),
     "emu_linear_fp4w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_linear_fp4w_gemm_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_llama_set_layer_fp4": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_fp4": (i32, [vp, vp, vp]),
     "emu_llama_use_fp4": (i32, [vp, i32]),
+    "emu_llama_release_bf16": (i32, [vp]),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),

@@ -106,6 +106,13 @@ int linear_fp4_thin(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, c
     if (!gemv_fp4_thin_ok(g)) return -22;
     return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemv_fp4_thin(g, s); });
 }
+// 17 rows and more over MXFP4 weights (gemm_fp4.hip), under the same profiler accounting: the 4-bit bytes of the matrix, once
+int linear_fp4_gemm(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
+                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s) {
+    GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
+    if (!gemm_fp4_ok(g)) return -22;
+    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemm_fp4(g, s); });
+}
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
     return gemv_profiled(2.0 * (double)g.N * (double)g.K, s, [&] { return launch_gemv_merge(g, s); });
@@ -149,7 +156,7 @@ void emu_prof_end(hipStream_t s, const char* klass, int M, int N, int K, int tag
 
 extern "C" {
 
-int emu_version(void) { return 4; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
+int emu_version(void) { return 5; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
 void emu_gemm_force_config(int cfg) { emu_gemm_force_config_set(cfg); }
@@ -336,6 +343,12 @@ int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales,
     return linear_fp4_thin(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
                            lda, ldw, lds, ldres, ldc, epi, S(s));
 }
+int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
+    if (!A || !W4 || !scales || !C) return -22;
+    return linear_fp4_gemm(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
+                           lda, ldw, lds, ldres, ldc, epi, S(s));
+}
 int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
     if (!w || !q || !scales) return -22;
     return launch_quant_mxfp4_rows(B(w), ldw, reinterpret_cast<uint8_t*>(q), ldq, reinterpret_cast<uint8_t*>(scales), lds, N, K, S(s));
@@ -497,7 +510,9 @@ struct emu_llama {
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2): W8A8 GEMMs for prefill rows as well
     // optional MXFP4 copies for the decode stream (emu_llama_use_fp4; exclusive with the fp8 stream): element bytes [N, K/2] + E8M0
     // block scales [N, K/32] of the packed matrices.  Prefill and steps of more than two rows keep the bf16 weights, unless fp4_wide
-    // (emu_llama_use_fp4(m, 2)) sends steps of 3..16 rows through the matrix-core stream (gemv_fp4_thin.hip).
+    // (emu_llama_use_fp4(m, 2)) sends steps of 3..16 rows through the matrix-core stream (gemv_fp4_thin.hip) and fp4_all
+    // (emu_llama_use_fp4(m, 3)) the calls of 17 rows and more through the 4-bit GEMM (gemm_fp4.hip).  bf16_released
+    // (emu_llama_release_bf16; mode 3 only, which it pins): the layers' bf16 matrix pointers and lm_head are null.
     struct Layer4 { const uint8_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
                     const uint8_t *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sdown = nullptr; };
     std::vector<Layer4> layers4;
@@ -505,6 +520,8 @@ struct emu_llama {
     const uint8_t* lm_scale4 = nullptr;
     bool fp4_decode = false;
     bool fp4_wide = false;
+    bool fp4_all = false;
+    bool bf16_released = false;
     const bf16_t *final_norm = nullptr, *lm_head = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
     // tensor parallelism: lm_head holds rows [head_row0, head_row0 + head_rows) of the vocabulary only (emu_llama_set_head_shard);
     // head_rows < 0: the whole matrix
@@ -616,10 +633,12 @@ struct LlamaPlan {
     // fp8_gemm       prefill rows run W8A8 GEMMs in the layers that have fp8 weights
     // fp4_rows       1..2 rows stream the MXFP4 weight set (decode; emu_llama_use_fp4, never together with fp8_rows)
     // fp4_thin       3..16 rows stream the MXFP4 weight set through the matrix cores (emu_llama_use_fp4(m, 2)); norms stay launches
+    // fp4_gemm       17 rows and more run the MXFP4 weight set through the 4-bit GEMM (emu_llama_use_fp4(m, 3)); norms, RoPE / KV
+    //                append and V^T stay launches: fuse_rope and fuse_norm are off and the call never takes TwoLane
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
-    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, fp4_thin, norm_in_gemv, decode_tail, merge_o;
+    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, fp4_thin, fp4_gemm, norm_in_gemv, decode_tail, merge_o;
     // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
     // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
     DecodeLayersArgs dl; EngArgs eng;
@@ -659,13 +678,14 @@ struct LlamaCall {
         const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv;
         // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
         // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
-        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255);
+        p.fp4_gemm = m->fp4_all && M >= 17;
+        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && !p.fp4_gemm;
         // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
         // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
         // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
         // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
         // with B * beams > 16) keep the fused path they had before the promise became one-shot.
-        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill;
+        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && !p.fp4_gemm;
         p.fp8_rows = m->fp8_decode && M <= 2;
         // prefill with the fp8 weight set: activations are quantised per row ahead of every GEMM, the block-scaled MFMA
         // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
@@ -720,7 +740,7 @@ struct LlamaCall {
         }
         // ---- long prompt under tensor parallelism: two row halves, every all-reduce behind the other half's GEMMs (needs the slot-order
         // promise: the rows of the one batch element are the whole context in order, so the first half never reads the second's keys)
-        if (tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
+        if (!p.fp4_gemm && tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
             p.path = LlamaPath::TwoLane;
     }
 
@@ -730,11 +750,13 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
+        if (pw.W4 && plan.fp4_gemm) return linear_fp4_gemm(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s);
         if (pw.W4 && plan.fp4_thin) return linear_fp4_thin(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s);
         if (pw.W4 && plan.fp4_rows)
             return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
                           pw.s4, K / 32);
         if (pw.W8 && plan.fp8_rows) return linear(A, B(pw.W8), nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, gain_in ? eps : 0.f, epi, s, pw.s8);
+        if (!pw.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
         if (pw.W8) return linear_q8(w, A, K, pw.W8, pw.s8, res, C, rows, N, K, ldres, ldc, epi, s);
         if (gain_in) return linear(A, pw.W, nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, eps, epi, s);
         if (gain_out) return linear_then_rmsnorm(w, A, pw.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
@@ -753,7 +775,7 @@ struct LlamaCall {
     }
 
     // the MXFP4 weights of layer l where the plan streams them (emu_llama_use_fp4 checked that every layer has them), else nulls
-    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows || plan.fp4_thin ? m->layers4[l] : emu_llama::Layer4{}; }
+    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows || plan.fp4_thin || plan.fp4_gemm ? m->layers4[l] : emu_llama::Layer4{}; }
 
     // ---- The decoder layer, written once, in three steps that are cut where the schedules hook in:
     //     layer_kv      RMSNorm, [after_norm], qkv projection (+ RoPE / KV append / V^T in its epilogue, else the rope_kv launch): the
@@ -763,10 +785,11 @@ struct LlamaCall {
     int layer_kv(const RowWindow& win, int l, const LaneHook& after_norm = nullptr) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        if (!L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const emu_llama::Layer8 L8 = layer_fp8(l);
         if (plan.fp8_rows && !L8.wqkv) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
         const emu_llama::Layer4 L4 = layer_fp4(l);
+        // after emu_llama_release_bf16 the 4-bit set is the layer's weights (mode 3 is pinned: every row count has a 4-bit path)
+        if (m->bf16_released ? !L4.wqkv || !L.ln1 : !L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
@@ -1093,6 +1116,8 @@ void emu_llama_destroy(emu_llama* m) {
 
 int emu_llama_set_decode_fused(emu_llama* m, int enable, int layers_per_launch) {
     if (!m || layers_per_launch < 0) return -22;
+    if (enable > 0 && m->bf16_released)
+        return fail(m->ctx, -22, "emu_llama_set_decode_fused: the bf16 weights were released (emu_llama_release_bf16); the fused decode modes read them");
     if (enable && !m->dl_cnt) {
         const emu_llama_cfg& c = m->cfg;
         m->dl_cnt_bytes = decode_layers_cnt_ints(c.layers, c.heads_local) * sizeof(int);
@@ -1169,6 +1194,9 @@ int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_sc
 }
 int emu_llama_use_fp4(emu_llama* m, int enable) {
     if (!m) return -22;
+    if (enable < 0 || enable > 3) return fail(m->ctx, -22, "emu_llama_use_fp4: modes 0 to 3");
+    if (m->bf16_released && enable != 3)
+        return fail(m->ctx, -22, "emu_llama_use_fp4: the bf16 weights were released (emu_llama_release_bf16); only mode 3 runs without them");
     if (enable) {
         const emu_llama_cfg& c = m->cfg;
         if (m->fp8_decode)
@@ -1179,11 +1207,22 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
             return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
         for (const auto& l : m->layers4)
             if (!l.wqkv) return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
-        if (enable == 2 && ((c.hidden & 255) || ((c.heads_local * c.head_dim) & 255) || (c.ffn_local & 255)))
-            return fail(m->ctx, -22, "emu_llama_use_fp4: mode 2 (3..16-row steps) needs reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
+        if (enable >= 2 && ((c.hidden & 255) || ((c.heads_local * c.head_dim) & 255) || (c.ffn_local & 255)))
+            return fail(m->ctx, -22, "emu_llama_use_fp4: modes 2 and 3 (steps of 3 rows and more) need reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
     }
     m->fp4_decode = enable != 0;
-    m->fp4_wide = enable == 2;
+    m->fp4_wide = enable >= 2;
+    m->fp4_all = enable == 3;
+    return 0;
+}
+int emu_llama_release_bf16(emu_llama* m) {
+    if (!m) return -22;
+    if (!m->fp4_all) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
+    if (m->decode_fused) return fail(m->ctx, -22, "emu_llama_release_bf16: the fused decode modes read the bf16 weights (emu_llama_set_decode_fused(m, 0, 0) first)");
+    for (auto& l : m->layers) l.wqkv = l.wo = l.wgu = l.wdown = nullptr;
+    m->lm_head = nullptr;
+    m->dl_dirty = true;
+    m->bf16_released = true;
     return 0;
 }
 int emu_llama_set_decode_tail(emu_llama* m, int enable) {
@@ -1218,6 +1257,8 @@ int emu_llama_set_tp_overlap(emu_llama* m, int min_rows) {
 long emu_llama_tp_overlap_count(const emu_llama* m) { return m ? m->ov_forwards : -1; }
 int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (!m) return -22;
+    if (enable && m->bf16_released)
+        return fail(m->ctx, -22, "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
     if (enable && m->fp4_decode)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp4(m, 0) first)");
     if (enable && m->layers8.size() != (size_t)m->cfg.layers)
@@ -1340,61 +1381,50 @@ int emu_llama_final_norm(emu_llama* m, const void* hidden, void* out, int rows, 
                           m->cfg.rms_eps, S(s));
 }
 
+// final RMSNorm + rows of the head (N of them, from the engine's head pointers) on M hidden rows -> out: the one place that picks the
+// head's kernel.  The few-row streams fuse the norm; every other path runs the norm launch into the workspace first.
+static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t* out, int N, int ld, bf16_t* ws, size_t ws_bytes,
+                      hipStream_t s) {
+    const emu_llama_cfg& c = m->cfg;
+    const int H = c.hidden;
+    const bool ws_fits = ws_bytes >= (size_t)M * H * 2;
+    const bool thin = m->fp4_wide && M >= 3 && M <= 16 && (ws_fits || m->bf16_released), gemm = m->fp4_all && M >= 17;
+    if (m->fp4_decode && M <= 2)                                  // the MXFP4 copy covers the same rows (quantised from the shard)
+        return linear(hidden, B(m->lm_head4), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H / 2, 0, ld, c.rms_eps, EPI_NONE, s,
+                      nullptr, nullptr, 0, m->lm_scale4, H / 32);
+    if (!thin && !gemm) {
+        if (m->fp8_decode && M <= 2 && m->lm_head8)               // the e4m3 copy covers the same rows (quantised from the shard)
+            return linear(hidden, B(m->lm_head8), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H, 0, ld, c.rms_eps, EPI_NONE, s,
+                          m->lm_scale8);
+        if (M == 1 || (M <= 8 && !ws_fits))
+            return linear(hidden, m->lm_head, nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H, 0, ld, c.rms_eps, EPI_NONE, s);
+    }
+    if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
+    TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
+    if (thin) return linear_fp4_thin(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s);
+    if (gemm) return linear_fp4_gemm(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s);
+    return linear(ws, m->lm_head, nullptr, nullptr, nullptr, out, M, N, H, H, H, 0, ld, 0.f, EPI_NONE, s);
+}
+
 int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* logits, int ld, void* workspace,
                      size_t ws_bytes, emu_stream_t s) {
-    if (!m || !m->lm_head || !m->final_norm) return -22;
+    if (!m || !m->final_norm) return -22;
+    // after emu_llama_release_bf16 the 4-bit head is the head (mode 3 is pinned: every row count has a 4-bit path in llama_head)
+    if (m->bf16_released ? !m->fp4_all || !m->lm_head4 : !m->lm_head) return -22;
     const emu_llama_cfg& c = m->cfg;
-    if (m->head_rows >= 0) {
-        // vocabulary-sharded head (tensor parallelism): this rank streams its rows of lm_head only (4035 of 32 274 at TP = 8:
-        // 54 MB instead of 430 MB per token) into its own columns of the caller's [M, vocab] rows, every other column zero, and one
-        // all-reduce makes the rows whole on every rank -- each logit is computed by exactly one rank and summed with zeros, so the
-        // result is bit-identical to the replicated head and every consumer (arg-max, beam scorer, samplers) stays as it is.
-        emu_ctx* cx = m->ctx;
-        bf16_t* lg = B(logits);
-        const int N = m->head_rows, n0 = m->head_row0;
-        if (hipMemsetAsync(lg, 0, ((size_t)(M - 1) * ld + c.vocab) * sizeof(bf16_t), S(s)) != hipSuccess)
-            return fail(cx, -5, "emu_llama_logits: hipMemsetAsync");
-        if (m->fp4_decode && M <= 2) {                            // the MXFP4 copy covers the same rows (quantised from the shard)
-            TRY(cx, linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden / 2, 0, ld,
-                           c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32));
-        } else if (m->fp4_wide && M >= 3 && M <= 16 && ws_bytes >= (size_t)M * c.hidden * 2) {    // 3..16 rows: norm launch, then the matrix-core stream
-            TRY(cx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
-            TRY(cx, linear_fp4_thin(B(workspace), m->lm_head4, m->lm_scale4, nullptr, nullptr, lg + n0, M, N, c.hidden, c.hidden, c.hidden / 2,
-                                    c.hidden / 32, 0, ld, EPI_NONE, S(s)));
-        } else if (m->fp8_decode && M <= 2 && m->lm_head8) {      // the e4m3 copy covers the same rows (quantised from the shard)
-            TRY(cx, linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden, 0, ld,
-                           c.rms_eps, EPI_NONE, S(s), m->lm_scale8));
-        } else if (M == 1 || (M <= 8 && ws_bytes < (size_t)M * c.hidden * 2)) {
-            TRY(cx, linear(B(hidden), m->lm_head, nullptr, nullptr, m->final_norm, lg + n0, M, N, c.hidden, ldh, c.hidden, 0, ld,
-                           c.rms_eps, EPI_NONE, S(s)));
-        } else {
-            if (ws_bytes < (size_t)M * c.hidden * 2) return fail(cx, -12, "emu_llama_logits: workspace too small");
-            TRY(cx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
-            TRY(cx, linear(B(workspace), m->lm_head, nullptr, nullptr, nullptr, lg + n0, M, N, c.hidden, c.hidden, c.hidden, 0, ld, 0.f,
-                           EPI_NONE, S(s)));
-        }
-        if (ld == c.vocab) return emu_allreduce_bf16(cx, lg, (size_t)M * c.vocab, s);
-        for (int r = 0; r < M; ++r) TRY(cx, emu_allreduce_bf16(cx, lg + (size_t)r * ld, (size_t)c.vocab, s));
-        return 0;
-    }
-    if (m->fp4_decode && M <= 2)
-        return linear(B(hidden), B(m->lm_head4), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh, c.hidden / 2, 0, ld,
-                      c.rms_eps, EPI_NONE, S(s), nullptr, nullptr, 0, m->lm_scale4, c.hidden / 32);
-    if (m->fp4_wide && M >= 3 && M <= 16 && ws_bytes >= (size_t)M * c.hidden * 2) {
-        TRY(m->ctx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
-        return linear_fp4_thin(B(workspace), m->lm_head4, m->lm_scale4, nullptr, nullptr, B(logits), M, c.vocab, c.hidden, c.hidden, c.hidden / 2,
-                               c.hidden / 32, 0, ld, EPI_NONE, S(s));
-    }
-    if (m->fp8_decode && M <= 2 && m->lm_head8)
-        return linear(B(hidden), B(m->lm_head8), nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh,
-                      c.hidden, 0, ld, c.rms_eps, EPI_NONE, S(s), m->lm_scale8);
-    if (M == 1 || (M <= 8 && ws_bytes < (size_t)M * c.hidden * 2))
-        return linear(B(hidden), m->lm_head, nullptr, nullptr, m->final_norm, B(logits), M, c.vocab, c.hidden, ldh,
-                      c.hidden, 0, ld, c.rms_eps, EPI_NONE, S(s));
-    if (ws_bytes < (size_t)M * c.hidden * 2) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
-    TRY(m->ctx, launch_rmsnorm(B(hidden), m->final_norm, B(workspace), M, c.hidden, ldh, c.hidden, c.rms_eps, S(s)));
-    return linear(B(workspace), m->lm_head, nullptr, nullptr, nullptr, B(logits), M, c.vocab, c.hidden, c.hidden, c.hidden,
-                  0, ld, 0.f, EPI_NONE, S(s));
+    if (m->head_rows < 0) return llama_head(m, B(hidden), ldh, M, B(logits), c.vocab, ld, B(workspace), ws_bytes, S(s));
+    // vocabulary-sharded head (tensor parallelism): this rank streams its rows of lm_head only (4035 of 32 274 at TP = 8:
+    // 54 MB instead of 430 MB per token) into its own columns of the caller's [M, vocab] rows, every other column zero, and one
+    // all-reduce makes the rows whole on every rank -- each logit is computed by exactly one rank and summed with zeros, so the
+    // result is bit-identical to the replicated head and every consumer (arg-max, beam scorer, samplers) stays as it is.
+    emu_ctx* cx = m->ctx;
+    bf16_t* lg = B(logits);
+    if (hipMemsetAsync(lg, 0, ((size_t)(M - 1) * ld + c.vocab) * sizeof(bf16_t), S(s)) != hipSuccess)
+        return fail(cx, -5, "emu_llama_logits: hipMemsetAsync");
+    TRY(cx, llama_head(m, B(hidden), ldh, M, lg + m->head_row0, m->head_rows, ld, B(workspace), ws_bytes, S(s)));
+    if (ld == c.vocab) return emu_allreduce_bf16(cx, lg, (size_t)M * c.vocab, s);
+    for (int r = 0; r < M; ++r) TRY(cx, emu_allreduce_bf16(cx, lg + (size_t)r * ld, (size_t)c.vocab, s));
+    return 0;
 }
 
 int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,

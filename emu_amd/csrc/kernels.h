@@ -56,6 +56,10 @@ int launch_gemv_thin(const GemvArgs& a, hipStream_t s);
 // v_mfma_f32_16x16x32_bf16 (gemv_fp4_thin.hip); needs K % 256 == 0, lds % 4 == 0, no fused norm; epi NONE / RESID / SWIGLU
 bool gemv_fp4_thin_ok(const GemvArgs& a);
 int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s);
+// 17 rows and more over MXFP4 weights: the thin kernel's arithmetic and epilogues on a two-dimensional tile, each converted weight
+// fragment feeding several MFMAs (gemm_fp4.hip); same requirements; ragged M and N
+bool gemm_fp4_ok(const GemvArgs& a);
+int launch_gemm_fp4(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

@@ -174,6 +174,9 @@ class EmuHipContext:
 
 
 class LlamaEngine:
+    fp4_all = False            # use_fp4(True, wide=True, all_rows=True) is on: every row count runs the 4-bit set
+    bf16_released = False      # release_bf16() was called: the bf16 matrices and lm_head are gone, fp4_all is pinned
+
     def __init__(self, cfg: LlamaCfg, vocab: int, ctx: EmuHipContext):
         self.cfg, self.vocab, self.ctx = cfg, vocab, ctx
         self.device = ctx.device
@@ -335,10 +338,12 @@ class LlamaEngine:
     @property
     def ready(self) -> bool:
         return (len(self.layers_loaded) == self.cfg.num_hidden_layers and self.embed is not None
-                and self.final_norm is not None and self.lm_head is not None)
+                and self.final_norm is not None and (self.lm_head is not None or self.bf16_released))
 
     def weight_bytes_per_token(self) -> int:
         """Algorithmic bytes one decode step of THIS shard must stream (all packed matrices once + lm_head)."""
+        if self.bf16_released:          # only the 4-bit tensors are left: their shapes
+            return sum(self._fp4_shape(k)[0] * mxfp4.bytes_per_row(self._fp4_shape(k)[1]) for k in self._fp4_keys())
         if getattr(self, "fp4_decode", False):             # MXFP4: K/2 element bytes + K/32 scale bytes per row
             size = lambda v: v.shape[0] * mxfp4.bytes_per_row(v.shape[1])
         else:
@@ -354,6 +359,8 @@ class LlamaEngine:
         33B bf16 + fp8 = 98 GB).  Not a reference feature (the reference is bf16 end to end); off unless enabled."""
         if not self.ready:
             raise RuntimeError("quantize_fp8: load all weights first")
+        if self.bf16_released:
+            raise RuntimeError("quantize_fp8: the bf16 weights were released (release_bf16); there is nothing left to quantise")
         if getattr(self, "_fp8", None):
             return
         self._fp8 = {}
@@ -371,7 +378,7 @@ class LlamaEngine:
     def use_fp8(self, enable: bool = True, prefill: bool = False) -> None:
         """Switch the decode stream between the bf16 and the fp8 weights (invalidates captured decode graphs).
         ``prefill=True`` also runs the prefill GEMMs W8A8 on the block-scaled fp8 MFMA (activations quantised per row)."""
-        if enable:
+        if enable and not self.bf16_released:   # (after release_bf16 the library refuses and says why)
             self.quantize_fp8()
         check(lib().emu_llama_use_fp8(self.handle, (2 if prefill else 1) if enable else 0), "emu_llama_use_fp8", self.ctx.handle)
         self.fp8_decode = bool(enable)
@@ -385,14 +392,20 @@ class LlamaEngine:
     # ------------------------------------------------------------------ optional MXFP4 decode stream
     _FP4_KINDS = ("wqkv", "wo", "wgu", "wdown")
 
+    def _fp4_shape(self, key: str) -> Tuple[int, int]:
+        """[N, K] of the matrix a registered fp4 key stands for, from its element bytes [N, K/2]."""
+        q = self._fp4[key][0]
+        return int(q.shape[0]), int(q.shape[1]) * 2
+
     def _fp4_source(self, key: str) -> torch.Tensor:
-        """The packed (and sharded) bf16 matrix an fp4 key stands for: "<layer>.wqkv|wo|wgu|wdown" or "lm_head"."""
-        if key == "lm_head":
-            return self.lm_head
+        """The packed (and sharded) bf16 matrix an fp4 key stands for: "<layer>.wqkv|wo|wgu|wdown" or "lm_head".  After
+        ``release_bf16`` the matrix is gone: a storage-less (meta) bf16 tensor of its shape, taken from the 4-bit tensors."""
         layer, _, kind = key.partition(".")
-        if kind not in self._FP4_KINDS or not layer.isdigit() or int(layer) >= self.cfg.num_hidden_layers:
+        if key != "lm_head" and (kind not in self._FP4_KINDS or not layer.isdigit() or int(layer) >= self.cfg.num_hidden_layers):
             raise KeyError(f"fp4 key {key!r}: expected '<layer>.wqkv|wo|wgu|wdown' or 'lm_head'")
-        return self._keep[key]
+        if self.bf16_released:
+            return torch.empty(self._fp4_shape(key), dtype=BF16, device="meta")
+        return self.lm_head if key == "lm_head" else self._keep[key]
 
     def _fp4_keys(self):
         return [f"{i}.{k}" for i in range(self.cfg.num_hidden_layers) for k in self._FP4_KINDS] + ["lm_head"]
@@ -411,13 +424,16 @@ class LlamaEngine:
     def quantize_fp4(self) -> None:
         """Build MXFP4 copies (4-bit elements, one power-of-two scale per 32: ``emu_amd.mxfp4``) of every packed matrix and of
         lm_head with the device quantiser and register them for the decode stream (B*T <= 2 rows; with ``use_fp4(wide=True)`` also
-        steps of 3..16 rows).  Keys already provided through ``load_fp4`` are kept.  Prefill and steps of more rows keep the bf16
-        weights, so both sets stay resident (33B: bf16 66 GB + fp4 17 GB).  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
+        steps of 3..16 rows, with ``all_rows=True`` every row count).  Keys already provided through ``load_fp4`` are kept.  Prefill and
+        steps of more than 16 rows keep the bf16 weights unless ``all_rows``, so both sets stay resident (33B: bf16 66 GB + fp4
+        17 GB) until ``release_bf16``.  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
         if not self.ready:
             raise RuntimeError("quantize_fp4: load all weights first")
         self.__dict__.setdefault("_fp4", {})
         for key in self._fp4_keys():
             if key not in self._fp4:
+                if self.bf16_released:
+                    raise RuntimeError(f"quantize_fp4: the bf16 weights were released (release_bf16); {key!r} cannot be quantised anew")
                 self._fp4[key] = ops.quantize_mxfp4_rows(self._fp4_source(key))
                 self._fp4_register(key)
 
@@ -441,7 +457,7 @@ class LlamaEngine:
         self._fp4[key] = (packed.to(self.device).contiguous(), scales.to(self.device).contiguous())
         self._fp4_register(key)
 
-    def use_fp4(self, enable: bool = True, wide: bool = False) -> None:
+    def use_fp4(self, enable: bool = True, wide: bool = False, all_rows: bool = False) -> None:
         """Switch the decode stream between the bf16 and the MXFP4 weights (invalidates captured decode graphs).  Whatever was not
         provided through ``load_fp4`` is quantised on the device first.  Exclusive with ``use_fp8``.
 
@@ -449,12 +465,34 @@ class LlamaEngine:
         ``use_fp4(True, wide=True)``: steps of 3..16 rows (the default 5-beam search, a batch of prompts, contrastive search) stream
         the 4-bit set as well, through the matrix-core kernel (csrc/gemv_fp4_thin.hip); needs hidden, heads_local * head_dim and
         ffn_local to be multiples of 256 (the library refuses otherwise and says why).  Prefill and steps of more than 16 rows
-        stream bf16 in every mode."""
-        if enable and not getattr(self, "fp8_decode", False):      # (with fp8 on, the library refuses and says why)
-            self.quantize_fp4()
-        check(lib().emu_llama_use_fp4(self.handle, (2 if wide else 1) if enable else 0), "emu_llama_use_fp4", self.ctx.handle)
+        stream bf16 unless ``all_rows``.
+        ``use_fp4(True, wide=True, all_rows=True)``: prefill and steps of 17 rows and more (beams x batch) run the 4-bit set too,
+        through the 4-bit GEMM (csrc/gemm_fp4.hip; the RoPE and RMSNorm epilogue fusions of the bf16 prefill and the two-lane
+        prefill are off), so one generation sees one weight set and ``release_bf16`` may free the bf16 matrices.  Same width
+        requirement as ``wide``; ``all_rows`` without ``wide`` is a ``ValueError``."""
+        if all_rows and not wide:
+            raise ValueError("use_fp4: all_rows=True needs wide=True (mode 3 is mode 2 plus the calls of 17 rows and more)")
+        if enable and not getattr(self, "fp8_decode", False) and not self.bf16_released:
+            self.quantize_fp4()                                    # (with fp8 on, the library refuses and says why)
+        mode = (3 if all_rows else 2 if wide else 1) if enable else 0
+        check(lib().emu_llama_use_fp4(self.handle, mode), "emu_llama_use_fp4", self.ctx.handle)
         self.fp4_decode = bool(enable)
         self.fp4_wide = bool(enable and wide)
+        self.fp4_all = bool(enable and all_rows)
+        self._mode_changed()
+
+    def release_bf16(self) -> None:
+        """Free the bf16 packed matrices and the bf16 lm_head; needs ``use_fp4(True, wide=True, all_rows=True)``, which it pins (33B:
+        65 GB leave, the 17 GB of 4-bit tensors stay; the norm gains, the embedding and the RoPE tables stay).  Afterwards
+        ``use_fp4(False)``, ``use_fp4(True)`` without ``all_rows``, ``use_fp8`` and ``set_decode_fused(!= 0)`` raise with the
+        library's message; there is no way back short of a new engine.  Invalidates captured decode graphs."""
+        if not self.fp4_all:
+            raise RuntimeError("release_bf16: switch every row count to the 4-bit set first (use_fp4(True, wide=True, all_rows=True))")
+        check(lib().emu_llama_release_bf16(self.handle), "emu_llama_release_bf16", self.ctx.handle)
+        self.bf16_released = True
+        for key in [k for k in self._keep if k.split(".")[1] in self._FP4_KINDS]:
+            del self._keep[key]
+        self.lm_head = None
         self._mode_changed()
 
     def fp4_dequantized(self, key: str) -> torch.Tensor:

@@ -180,12 +180,18 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
  * scale applied by v_cvt_scalef32_pk_bf16_fp4, v_mfma_f32_16x16x32_bf16, fp32 accumulation), same epilogues and rounding points, no
  * fused RMSNorm (normalise first).  N >= 1, K >= 256 and K % 256 == 0, ldw % 16 == 0 (bytes), lda % 8 == 0, lds % 4 == 0, A / W4
  * 16-byte aligned, N even under SWIGLU; anything else -22.  emu_linear_fp4w_bf16 keeps answering -22 for M > 2.
+ * emu_linear_fp4w_gemm_bf16: the same product, arguments, epilogues, rounding points and requirements for M >= 17 rows
+ * (gemm_fp4.hip: a workgroup owns 64 weight rows x 32 / 64 / 128 activation rows, every converted weight fragment feeds 2 or 4
+ * MFMAs; ragged M and N); M < 17 and every violated requirement: -22.  It computes what emu_linear_bf16 computes on the
+ * dequantised weights, up to fp32 summation order.
  * Not a reference feature; what round-to-nearest MXFP4 does to a trained checkpoint is NOT measured by this project. */
 int emu_quantize_mxfp4_rows(const void* w_bf16, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s);
 int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc,
                          float eps, int epi, emu_stream_t s);
 int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
+int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
 /* emu_linear_bf16 (M > 8, epi in {NONE, RESID, GEGLU}) with the fused epilogues of the UNet transformer blocks -- what
  * diffusers' BasicTransformerBlock computes as LayerNorm -> Linear (norm1/2/3 ahead of attn1.to_q/k/v, attn2.to_q,
@@ -360,11 +366,20 @@ int emu_llama_use_fp8(emu_llama* m, int enable);
  * contrastive search) streams the 4-bit set through emu_linear_fp4w_thin_bf16's kernel -- qkv, o_proj, gate/up, down and the head
  * (whole or emu_llama_set_head_shard rows); the RMSNorm launches of the bf16 few-row path stay, attention is untouched.  It also
  * fails (-22) if hidden, heads_local*head_dim or ffn_local is not a multiple of 256 (TP = 4 / 8 shards of the 33B shapes: keep mode 1).
- * Steps of 17 rows and more, and prefill, keep the bf16 weights in every mode. */
+ * Steps of 17 rows and more, and prefill, keep the bf16 weights in modes 1 and 2.
+ * emu_llama_use_fp4(m, 3) is mode 2 plus: every forward / logits call of B*T >= 17 rows (prefill, beams x batch) runs qkv, o_proj,
+ * gate/up, down and the head (whole or sharded) through emu_linear_fp4w_gemm_bf16's kernel, so no row count reads a bf16 matrix.
+ * The RMSNorm launches stay in front of the projections; RoPE / KV append, V^T and flash attention are the unfused launches (no
+ * RoPE epilogue, no K-slice sum + RMSNorm fusion, no two-lane prefill while the mode is on).  Same width requirement as mode 2.
+ * emu_llama_release_bf16(m): valid only in mode 3 (else -22).  Forgets every layer's four bf16 matrix pointers and the bf16 lm_head
+ * pointer, so the caller may free them (33B: 65 GB leave, 17 GB of 4-bit tensors stay); the norm gains, the embedding and the RoPE
+ * tables stay.  From then on emu_llama_use_fp4(m, 0 | 1 | 2), emu_llama_use_fp8(m, != 0) and emu_llama_set_decode_fused(m, != 0, ..)
+ * answer -22 with a message that names the release; there is no way back. */
 int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const void* sqkv, const void* wo4, const void* so,
                             const void* wgu4, const void* sgu, const void* wdown4, const void* sdown);
 int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales);
 int emu_llama_use_fp4(emu_llama* m, int enable);
+int emu_llama_release_bf16(emu_llama* m);
 /* Vocabulary-sharded lm_head under tensor parallelism (the reference's lm_head is lm.lm_head of LlamaForCausalLM reached
  * from Emu2/emu/emu.py:213-229): the lm_head pointer of emu_llama_set_head holds rows [row0, row0 + rows) of the vocabulary only;
  * emu_llama_logits fills this rank's columns of the caller's [M, vocab] rows, zeroes the others and all-reduces the rows, so every
