@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # announced on stderr, and the loaded library must report this binding's ABI version either way.
 _OVERRIDE = os.environ.get("EMU_HIP_LIB") if os.environ.get("EMU_HIP_TOOLS") == "1" else None
 LIB_PATH = _OVERRIDE or os.path.join(HERE, "csrc", "libemu_hip.so")
-ABI_VERSION = 5            # emu_version() of the library these prototypes and struct layouts belong to
+ABI_VERSION = 6            # emu_version() of the library these prototypes and struct layouts belong to
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "emu_hip.h")
 
 
@@ -119,6 +119,8 @@ _PROTOS = {
                                   i32, i32, i32, i32, i32, i32, i32, f32, vp]),
     "emu_decode_attn_ws_bytes": (sz, [i32, i32, i32, i32]),
     "emu_decode_attn_bf16": (i32, [vp, lng, lng, vp, vp, vp, lng, lng, vp, vp, i32, i32, vp, i32, i32, i32, i32, f32, vp]),
+    "emu_decode_fused_ws_bytes": (sz, [i32, i32, i32, i32]),
+    "emu_decode_fused_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, lng, lng, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]),
     "emu_llama_create": (i32, [vp, C.POINTER(LlamaCfgC), C.POINTER(vp)]),
     "emu_llama_destroy": (None, [vp]),
     "emu_llama_set_layer": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),

@@ -367,8 +367,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const DecodeAttnArgs a
         float f[8];
         unpack8(ld16(vc + (size_t)(k0 + j) * D + dv * 8), f);
         const float pj = sp[j];
+        // a masked key's V row is selected away, not multiplied by its zero weight: the slot may hold anything (0 * NaN = NaN)
+        const bool dead = k0 + j < kstart;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, f[e], acc[e]);
+        for (int e = 0; e < 8; ++e) acc[e] = fmaf(pj, dead ? 0.f : f[e], acc[e]);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) red[kg][dv * 8 + e] = acc[e];

@@ -156,7 +156,7 @@ void emu_prof_end(hipStream_t s, const char* klass, int M, int N, int K, int tag
 
 extern "C" {
 
-int emu_version(void) { return 5; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
+int emu_version(void) { return 6; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
 void emu_gemm_force_config(int cfg) { emu_gemm_force_config_set(cfg); }
@@ -490,6 +490,15 @@ int emu_decode_attn_bf16(const void* q, long q_sb, long q_sh, const void* kcache
     DecodeAttnArgs a{B(q), q_sb, q_sh, B(kcache), B(vcache), B(o), o_sb, o_sh, kstart, ctx_dev,
                      reinterpret_cast<float*>(ws), Bn, H, D, S_max, ctx, ctx_max, scale};
     return launch_decode_attn(a, S(s));
+}
+size_t emu_decode_fused_ws_bytes(int Bn, int H, int D, int ctx_max) { return decode_fused_ws_floats(Bn, H, D, ctx_max) * sizeof(float); }
+int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, const int32_t* pos, const int32_t* slot,
+                          void* kcache, void* vcache, void* o, long o_sb, long o_sh, const int32_t* kstart, void* ws, int Bn,
+                          int H, int D, int S_max, int ctx_max, float scale, int share_nb, int share_len, int32_t* arrive,
+                          emu_stream_t s) {
+    DecodeFusedArgs a{B(qkv), B(cos), B(sin), pos, slot, B(kcache), B(vcache), B(o), o_sb, o_sh, kstart,
+                      reinterpret_cast<float*>(ws), Bn, H, D, S_max, ctx_max, scale, share_nb, share_len, arrive};
+    return launch_decode_fused(a, S(s));
 }
 
 }  // extern "C"

@@ -353,6 +353,33 @@ def decode_attn(q, kcache, vcache, ctx: int, scale: float, kstart=None, ctx_dev=
     return o
 
 
+def decode_fused(qkv, cos, sin, pos, slot, kcache, vcache, H: int, ctx_max: int, scale: float, kstart=None, ws=None,
+                 share_nb: int = 0, share_len: int = 0, arrive=None):
+    """The decode step's attention launch (emu_decode_fused_bf16): qkv [B, 3*H*D] (q | k | v, not rotated); caches
+    [B,H,S_max,D], the new token's rotated key and its value are appended at slot[b] -> o [B,H,D].  ``ws``: the fp32 split-state
+    workspace (emu_decode_fused_ws_bytes), allocated here unless the caller brings one; ``arrive``: B*H zeroed int32 counters."""
+    _req(qkv, "qkv"); _req(cos, "cos"); _req(sin, "sin"); _req(kcache, "kcache"); _req(vcache, "vcache")
+    _req(pos, "pos", torch.int32); _req(slot, "slot", torch.int32)
+    assert qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous() and kcache.shape == vcache.shape
+    B, _, S_max, D = kcache.shape
+    assert qkv.shape == (B, 3 * H * D) and kcache.shape[1] == H, (qkv.shape, kcache.shape)
+    need = lib().emu_decode_fused_ws_bytes(B, H, D, ctx_max) // 4
+    if ws is None:
+        ws = torch.empty(need, device=qkv.device, dtype=torch.float32)
+    _req(ws, "ws", torch.float32)
+    assert ws.is_contiguous() and ws.numel() >= need, (ws.numel(), need)
+    if kstart is not None:
+        _req(kstart, "kstart", torch.int32)
+    if arrive is not None:
+        _req(arrive, "arrive", torch.int32)
+        assert arrive.is_contiguous() and arrive.numel() >= B * H
+    o = torch.empty(B, H, D, device=qkv.device, dtype=BF16)
+    check(lib().emu_decode_fused_bf16(_p(qkv), _p(cos), _p(sin), _p(pos), _p(slot), _p(kcache), _p(vcache), _p(o), o.stride(0),
+                                      o.stride(1), _p(kstart), _p(ws), B, H, D, S_max, ctx_max, float(scale), share_nb,
+                                      share_len, _p(arrive), stream(qkv)), "emu_decode_fused_bf16")
+    return o
+
+
 CONV_3X3, CONV_3X3_S2, CONV_3X3_UP2 = 1, 2, 3
 
 

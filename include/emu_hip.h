@@ -326,6 +326,19 @@ size_t emu_decode_attn_ws_bytes(int B, int H, int D, int ctx_max);
 int emu_decode_attn_bf16(const void* q, long q_sb, long q_sh, const void* kcache, const void* vcache, void* o,
                          long o_sb, long o_sh, const int32_t* kstart, const int32_t* ctx_dev, int ctx,
                          int ctx_max, void* ws, int B, int H, int D, int S_max, float scale, emu_stream_t s);
+/* The decode step's attention launch (transformers LlamaAttention with a KV cache, one new token per row; emu.py:213-229): RoPE of
+ * q and of the new key at pos[b], append of the new key / value at cache slot[b], attention of the rotated q over the keys
+ * kstart[b] <= key <= slot[b] in splits of 128 keys, and the merge of the splits.  qkv [B, 3*H*D] (q | k | v, not rotated, left as
+ * it is); caches [B, H, S_max, D]; o[b*o_sb + h*o_sh + d]; kstart may be NULL; ws: emu_decode_fused_ws_bytes; ctx_max sizes the
+ * launch (max slot + 1 <= ctx_max <= S_max).  share_nb in 2..8: the rows are groups of share_nb beams whose first share_len
+ * slots are stored in the group's first row only (B % share_nb == 0, 0 <= share_len < ctx_max, share_len <= every slot).
+ * arrive (share_nb <= 1 only; may be NULL): B*H zeroed int32 counters -- the last split of a head to arrive merges the head, the
+ * counters are zero again afterwards.  D in {64, 128}.  -22: refused, nothing was launched. */
+size_t emu_decode_fused_ws_bytes(int B, int H, int D, int ctx_max);
+int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, const int32_t* pos, const int32_t* slot,
+                          void* kcache, void* vcache, void* o, long o_sb, long o_sh, const int32_t* kstart, void* ws, int B,
+                          int H, int D, int S_max, int ctx_max, float scale, int share_nb, int share_len, int32_t* arrive,
+                          emu_stream_t s);
 
 /* ---- LLaMA decoder engine ------------------------------------------------------------------------------
  * transformers LlamaModel / LlamaForCausalLM as used by EmuModel.generate / generate_image

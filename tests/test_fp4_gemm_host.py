@@ -9,11 +9,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["emu_linear_fp4w_gemm_bf16", "emu_llama_release_bf16"]
 
 
-def test_abi_version_is_5():
+def test_abi_version_is_6():
     from emu_amd import _lib
-    assert _lib.ABI_VERSION == 5
+    assert _lib.ABI_VERSION == 6
     src = open(os.path.join(ROOT, "emu_amd", "csrc", "engine.hip")).read()
-    assert re.search(r"int emu_version\(void\) \{ return 5; \}", src)
+    assert re.search(r"int emu_version\(void\) \{ return 6; \}", src)
 
 
 @pytest.mark.parametrize("name", NEW)

@@ -1,6 +1,7 @@
 """GPU parity tests of the primitive C-ABI operators (through emu_amd.ops -> libemu_hip.so) against CPU fp32
 references that keep the reference's bf16 rounding points.  Run on an MI355X with `-m gpu`."""
 import math
+import os
 
 import pytest
 import torch
@@ -411,3 +412,63 @@ def test_decode_attn(D, ctx):
     got2 = ops.decode_attn(q.cuda(), kc.cuda(), vc.cuda(), S_max, D ** -0.5, kstart=kstart.cuda(), ctx_dev=ctx_dev,
                            ctx_max=S_max)
     assert torch.equal(got.cpu(), got2.cpu())
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("ks", [128, 256, 300])
+@pytest.mark.parametrize("poison", [False, True])
+def test_decode_attn_left_padding_of_whole_chunks(D, ks, poison):
+    """Left padding that masks half a 256-key chunk, a whole one, and a whole one and a part: the dead chunk's state is
+    (m = -inf, l = 0) and the merge drops it.  Poisoned: the padded slots hold NaN in K and in V -- a masked key is selected
+    away, never multiplied by its zero weight -- and the result is the one with finite padding, bit for bit."""
+    ops = _ops()
+    B, H, S_max, ctx = 2, 3, 768, 700
+    q = rnd(B, H, D, seed=74)
+    kc, vc = rnd(B, H, S_max, D, seed=75), rnd(B, H, S_max, D, seed=76)
+    kstart = torch.tensor([0, ks], dtype=torch.int32)
+    want = ref_attention(q[:, None], kc[:, :, :ctx].transpose(1, 2), vc[:, :, :ctx].transpose(1, 2), False, D ** -0.5,
+                         kstart.long())[:, 0]
+    clean = ops.decode_attn(q.cuda(), kc.cuda(), vc.cuda(), ctx, D ** -0.5, kstart=kstart.cuda()).cpu()
+    got = clean
+    if poison:
+        kp, vp = kc.clone(), vc.clone()
+        kp[1, :, :ks] = float("nan"); vp[1, :, :ks] = float("nan")
+        got = ops.decode_attn(q.cuda(), kp.cuda(), vp.cuda(), ctx, D ** -0.5, kstart=kstart.cuda()).cpu()
+        assert bool(torch.isfinite(got.float()).all())
+        assert torch.equal(got, clean)
+    close(got, want, atol=2e-2, what=f"decode attn kstart{ks} poison{poison}")
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_decode_attn_finite_results_kept_their_bits(D, golden_dir):
+    """Selecting masked V rows away instead of multiplying them by their zero weight changes no bit for finite inputs
+    (0 * v = 0 either way): the output of the kernel as it was before the select, recorded once (tests/golden/decode_attn_bits.npz,
+    int16 views of the bf16 output), for left padding inside a chunk and of a whole chunk and more."""
+    import numpy as np
+    ops = _ops()
+    B, H, S_max, ctx = 2, 3, 768, 700
+    q = rnd(B, H, D, seed=74)
+    kc, vc = rnd(B, H, S_max, D, seed=75), rnd(B, H, S_max, D, seed=76)
+    kstart = torch.tensor([5, 300], dtype=torch.int32)
+    got = ops.decode_attn(q.cuda(), kc.cuda(), vc.cuda(), ctx, D ** -0.5, kstart=kstart.cuda()).cpu()
+    want = torch.from_numpy(np.load(os.path.join(golden_dir, "decode_attn_bits.npz"))[f"D{D}"])
+    assert torch.equal(got.view(torch.int16), want)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("Sq,Sk", [(260, 260), (70, 200)])
+@pytest.mark.parametrize("ks", [64, 65, 130, 200])
+def test_flash_attn_left_padding_of_whole_key_tiles(D, Sq, Sk, ks):
+    """Left padding of one whole 64-key tile, a tile and a key, two tiles and a part, three and a part -- dead then alive rows
+    inside one query block -- for the causal prefill and for the chunked-prefill window (the last Sq queries of Sk keys).  Finite
+    data: a masked key reaches the P.V MFMA as 0 * v, by design.  Padded query rows are don't-care but finite."""
+    ops = _ops()
+    B, H = 2, 2
+    q, k, v = rnd(B, Sq, H, D, seed=164), rnd(B, Sk, H, D, seed=165), rnd(B, Sk, H, D, seed=166)
+    kstart = torch.tensor([0, ks], dtype=torch.int32)
+    got = ops.flash_attn(q.cuda(), k.cuda(), v.cuda(), True, D ** -0.5, kstart=kstart.cuda()).cpu()
+    want = ref_attention(q, k, v, True, D ** -0.5, kstart.long())
+    ok_rows = torch.ones(B, Sq, dtype=torch.bool)
+    ok_rows[1, :max(0, ks - (Sk - Sq))] = False           # query i is key i + (Sk - Sq): padded where that key is (200 of 200 keys: all)
+    close(got[ok_rows], want[ok_rows], atol=2e-2, what=f"flash left pad D{D} {Sq}x{Sk} kstart{ks}")
+    assert bool(torch.isfinite(got.float()).all())

@@ -735,3 +735,26 @@ def test_round6_bench_line_has_no_stale_traffic_and_every_leg_its_objects():
         assert L["roofline"]["bound"] == bound and 0 < L["roofline"]["frac"] < 1, leg
         assert L["cpu_baseline"]["value"] > 0 and L["cpu_baseline"]["sample"], leg
     assert abs(d["legs"]["vae_decode"]["roofline"]["flops"] - 10.47e12) < 0.01e12
+
+
+@pytest.mark.parametrize("what,kw", [
+    ("ctx_max < 1", dict(ctx_max=0)),
+    ("ctx_max > S_max", dict(ctx_max=513)),
+    ("more beams per group than the shared form takes", dict(B=18, share_nb=9, share_len=100)),
+    ("rows not a multiple of the group", dict(B=7, share_nb=3, share_len=100)),
+    ("shared slots reach the new token's", dict(share_nb=2, share_len=256)),
+    ("shared slots past the launch", dict(share_nb=2, share_len=300)),
+    ("negative shared length", dict(share_nb=2, share_len=-1)),
+    ("head dim 96, beam groups", dict(D=96, share_nb=2, share_len=100)),
+    ("head dim 96, one row", dict(D=96)),
+])
+def test_decode_fused_refuses_before_any_launch(what, kw):
+    """emu_decode_fused_bf16 returns -22 from the host-side argument check, ahead of any launch: no GPU, and every pointer null."""
+    from emu_amd._lib import lib
+    a = dict(B=8, H=2, D=128, S_max=512, ctx_max=256, share_nb=0, share_len=0)
+    a.update(kw)
+    st = lib().emu_decode_fused_bf16(None, None, None, None, None, None, None, None, a["H"] * a["D"], a["D"], None, None,
+                                     a["B"], a["H"], a["D"], a["S_max"], a["ctx_max"], a["D"] ** -0.5, a["share_nb"],
+                                     a["share_len"], None, None)
+    assert st == -22, (what, st)
+    assert lib().emu_decode_fused_ws_bytes(3, 2, 64, 129) == 3 * 2 * 2 * 66 * 4
