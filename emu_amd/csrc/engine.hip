@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -99,19 +100,14 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     g.partial = splitk; g.partial_floats = splitk_floats;
     return launch_gemm(g, s);
 }
-// 1..16 rows over MXFP4 weights on the matrix cores (gemv_fp4_thin.hip): no fused norm, ldw = K / 2 bytes and lds = K / 32 unless given
-int linear_fp4_thin(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
-                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s) {
+// MXFP4 weights on the matrix cores: up to 16 rows stream them (gemv_fp4_thin.hip), 17 and more run the 4-bit GEMM (gemm_fp4.hip),
+// both under the GEMV profiler's accounting (the 4-bit bytes of the matrix, once).  No fused norm; a row count outside
+// [min_rows, max_rows] is refused, never forwarded to the other kernel
+int linear_fp4_mfma(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
+                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s, int min_rows, int max_rows) {
     GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
-    if (!gemv_fp4_thin_ok(g)) return -22;
-    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemv_fp4_thin(g, s); });
-}
-// 17 rows and more over MXFP4 weights (gemm_fp4.hip), under the same profiler accounting: the 4-bit bytes of the matrix, once
-int linear_fp4_gemm(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
-                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s) {
-    GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
-    if (!gemm_fp4_ok(g)) return -22;
-    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemm_fp4(g, s); });
+    if (!fp4_mfma_ok(g, min_rows, max_rows)) return -22;
+    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return M <= 16 ? launch_gemv_fp4_thin(g, s) : launch_gemm_fp4(g, s); });
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
@@ -340,14 +336,14 @@ int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, cons
 int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     if (!A || !W4 || !scales || !C) return -22;
-    return linear_fp4_thin(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s));
+    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
+                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, 16);
 }
 int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     if (!A || !W4 || !scales || !C) return -22;
-    return linear_fp4_gemm(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s));
+    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
+                           lda, ldw, lds, ldres, ldc, epi, S(s), 17, INT_MAX);
 }
 int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
     if (!w || !q || !scales) return -22;
@@ -759,8 +755,9 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
-        if (pw.W4 && plan.fp4_gemm) return linear_fp4_gemm(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s);
-        if (pw.W4 && plan.fp4_thin) return linear_fp4_thin(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s);
+        if (pw.W4 && (plan.fp4_gemm || plan.fp4_thin))             // (the plan's row range: 17 and more, or up to 16)
+            return linear_fp4_mfma(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s, plan.fp4_gemm ? 17 : 1,
+                                   plan.fp4_gemm ? INT_MAX : 16);
         if (pw.W4 && plan.fp4_rows)
             return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
                           pw.s4, K / 32);
@@ -1410,8 +1407,9 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
     }
     if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
     TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
-    if (thin) return linear_fp4_thin(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s);
-    if (gemm) return linear_fp4_gemm(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s);
+    if (thin || gemm)
+        return linear_fp4_mfma(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s, gemm ? 17 : 1,
+                               gemm ? INT_MAX : 16);
     return linear(ws, m->lm_head, nullptr, nullptr, nullptr, out, M, N, H, H, H, 0, ld, 0.f, EPI_NONE, s);
 }
 

@@ -3,16 +3,17 @@
 //
 // gemv_fp4_thin.hip streams the 4-bit set for up to 16 rows: one 16-row activation tile, every converted weight fragment used by ONE
 // MFMA.  This is the same arithmetic with a two-dimensional tile (format: emu_amd/mxfp4.py -- elements [N, K/2], element 2j in the
-// low nibble; E8M0 scales [N, K/32]); what it keeps of the thin kernel:
+// low nibble; E8M0 scales [N, K/32]); what the two kernels share is defined once, in fp4_tile.h:
 //   * K is walked in stages of 256 (128 element bytes + 8 scale bytes per weight row, 512 bytes per activation row), NSTG stages
 //     deep, counted vmcnt + one raw s_barrier per stage; element bytes, scale bytes and activation rows arrive by LDS-DMA, the DMA
-//     source address carries the swizzle and the LDS image is lane-linear;
-//   * slot b of weight row r sits at b ^ ((r >> 1) & 7), chunk c of activation row r at c ^ xswz(r & 15): every ds_read_b128 of 16
-//     rows x one block is conflict-free in every lane group;
+//     source address carries the swizzle and the LDS image is lane-linear (fp4_tile.h: stage constants, w_src / x_src on the
+//     source side, w_off / x_off on the read side): every ds_read_b128 of 16 rows x one block is conflict-free in every lane group;
 //   * lane (i, g) of a wave owns ONE whole MX block per round -- row i, block 4 * ku + g of the stage, one 16-byte LDS read, one
 //     scale byte -- and its four dwords become four A fragments through 4 x v_cvt_scalef32_pk_bf16_fp4 each (block scale applied
-//     in the conversion; every dequantised value is exact in bf16).
-// What changes is the tile: a workgroup (4 waves, WN x WM) owns BN = 16 * A_ * WN weight rows x BM = 16 * B_ * WM activation rows;
+//     in the conversion; every dequantised value is exact in bf16: cvt8);
+//   * the epilogue and its rounding points: store_c4 (bias, round to bf16, then residual or SiLU(gate) * up on
+//     interleaved rows).
+// What differs is the tile: a workgroup (4 waves, WN x WM) owns BN = 16 * A_ * WN weight rows x BM = 16 * B_ * WM activation rows;
 // a wave owns A_ x 16 weight rows x B_ x 16 activation rows and walks the whole stage itself (no k split, no reduction through
 // LDS).  A converted fragment feeds B_ MFMAs, so the 16 conversions of a block sit behind 4 * B_ matrix instructions.
 //   form        A_ B_ WN WM   BN x BM    stage             ring   LDS        rows
@@ -22,43 +23,21 @@
 //                                                                             workgroups in flight share weight rows in L2)
 // The first two are bound by the weight stream (use-once bytes: nt loads); the third re-reads the 4-bit bytes once per row tile
 // from L2 / the Infinity Cache.  Ragged M and N: rows and columns are clamped on load and masked on store.
-// Epilogues and rounding points are the thin kernel's (bias, round to bf16, then residual or SiLU(gate) * up on interleaved rows).
 // No fused RMSNorm, no RoPE epilogue, no K-slicing.  The result is what the bf16 GEMM computes on the dequantised weights, up to
 // fp32 summation order.
+#include <climits>
+
 #include "common.h"
 #include "kernels.h"
-#include "gemm_tile.h"
+#include "fp4_tile.h"
 
 using namespace emu_gemm;
 
 namespace {
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void glds16_nt(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2);
-}
-__device__ __forceinline__ void glds4(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
-}
-// activation-row swizzle: the two 2-bit halves of the row index (within its 16-row tile) swapped
-__device__ __forceinline__ int xswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
-// one dword of element bytes (8 codes) -> the 8 bf16 of an MFMA fragment, scaled by 2^(exponent field of sc - 127)
-__device__ __forceinline__ bf16x8_t cvt8(uint32_t d, float sc) {
-    const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0);
-    const bf16x2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1);
-    const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2);
-    const bf16x2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3);
-    return bf16x8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
-
 template <int EPI, int A_, int B_, int WN, int WM, int NSTG, bool STREAM>
 __global__ __launch_bounds__(256) void fp4_gemm_kernel(const GemvArgs a) {
     static_assert(WN * WM == 4, "four waves");
-    constexpr int KC = 256, WROW = KC / 2, XROW = KC * 2, SROW = KC / 32;  // k per stage; bytes per staged weight / activation / scale row
     constexpr int BN = 16 * A_ * WN, BM = 16 * B_ * WM;
     static_assert(BN == 64, "two 32-row scale instructions per stage");
     constexpr int WI = BN / 8, XI = BM / 2, TOT = WI + XI;                 // 1 KiB DMA instructions per stage: weights, activations
@@ -72,22 +51,13 @@ __global__ __launch_bounds__(256) void fp4_gemm_kernel(const GemvArgs a) {
     const int i = lane & 15, g = lane >> 4;
     const int wn = wave % WN, wm = wave / WN;
     const int m0 = (STREAM ? 0 : blockIdx.x) * BM, n0 = (STREAM ? blockIdx.x : blockIdx.y) * BN;
-    const char* W4 = reinterpret_cast<const char*>(a.W);
 
-    // DMA sources.  Instruction q < WI fills weight rows 8q .. 8q + 7 (lane / 8 selects, slot p = lane % 8 receives block
-    // p ^ ((row >> 1) & 7), rows clamped at N - 1); q >= WI fills activation rows 2(q - WI), + 1 of the tile (slot p = lane % 32
-    // receives chunk p ^ xswz(row), rows clamped at M - 1).
+    // DMA sources (fp4_tile.h): instruction q < WI fills weight rows 8q .. 8q + 7 of the tile, q >= WI activation rows 2(q - WI), + 1
     const char* src[JN];
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
         const int q = j * 4 + wave;
-        if (j < WI / 4) {
-            const int r = 8 * q + (lane >> 3), c = (lane & 7) ^ ((r >> 1) & 7), n = n0 + r;
-            src[j] = W4 + (size_t)(n < a.N ? n : a.N - 1) * a.ldw + c * 16;
-        } else {
-            const int r = 2 * (q - WI) + (lane >> 5), c = (lane & 31) ^ xswz(r), m = m0 + r;
-            src[j] = reinterpret_cast<const char*>(a.x + (size_t)(m < a.M ? m : a.M - 1) * a.ldx) + c * 16;
-        }
+        src[j] = j < WI / 4 ? w_src(a, n0, q, lane) : x_src(a, m0, x_dma_row(q - WI, lane), lane);
     }
     // scale rows: one 4-byte instruction = 32 rows x 8 bytes; waves w and w + 2 fill the same half with the same bytes
     const char* ssrc;
@@ -108,15 +78,13 @@ __global__ __launch_bounds__(256) void fp4_gemm_kernel(const GemvArgs a) {
             } else
                 glds16(src[j] + kt * XROW, base + q * 1024);
         }
-        glds4(ssrc + kt * SROW, base + WB + XB + (wave & 1) * 256);
+        glds4<false>(ssrc + kt * SROW, base + WB + XB + (wave & 1) * 256);
     };
     f32x4_t acc[A_][B_];
 #pragma unroll
     for (int ai = 0; ai < A_; ++ai)
 #pragma unroll
         for (int bi = 0; bi < B_; ++bi) acc[ai][bi] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int xsw = xswz(i);
-    const int wsw = (i >> 1) & 7;                      // (weight rows of a wave start at multiples of 16)
 #pragma unroll
     for (int t = 0; t < NSTG - 1; ++t) issue(t, t);
     for (int kt = 0; kt < nk; ++kt) {
@@ -132,15 +100,15 @@ __global__ __launch_bounds__(256) void fp4_gemm_kernel(const GemvArgs a) {
 #pragma unroll
             for (int ai = 0; ai < A_; ++ai) {
                 const int wr = (wn * A_ + ai) * 16 + i;
-                wv[ai] = *reinterpret_cast<const u32x4*>(sb + wr * WROW + ((blk ^ wsw) << 4));
-                sc[ai] = __uint_as_float((uint32_t) * reinterpret_cast<const uint8_t*>(sb + WB + XB + wr * SROW + blk) << 23);
+                wv[ai] = *reinterpret_cast<const u32x4*>(sb + w_off(wr, blk));
+                sc[ai] = scale_operand(*reinterpret_cast<const uint8_t*>(sb + WB + XB + wr * SROW + blk));
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 bf16x8_t bf[B_];
 #pragma unroll
                 for (int bi = 0; bi < B_; ++bi)
-                    bf[bi] = *reinterpret_cast<const bf16x8_t*>(sb + WB + ((wm * B_ + bi) * 16 + i) * XROW + (((4 * blk + q) ^ xsw) << 4));
+                    bf[bi] = *reinterpret_cast<const bf16x8_t*>(sb + WB + x_off((wm * B_ + bi) * 16 + i, 4 * blk + q));
 #pragma unroll
                 for (int ai = 0; ai < A_; ++ai) {
                     const bf16x8_t af = cvt8(wv[ai][q], sc[ai]);
@@ -157,46 +125,8 @@ __global__ __launch_bounds__(256) void fp4_gemm_kernel(const GemvArgs a) {
         const int m = m0 + (wm * B_ + bi) * 16 + i;
         if (m >= a.M) continue;
 #pragma unroll
-        for (int ai = 0; ai < A_; ++ai) {
-            const f32x4_t v = acc[ai][bi];
-            const int nb = n0 + (wn * A_ + ai) * 16 + 4 * g;   // first of this lane's 4 output columns
-            if constexpr (EPI == EPI_SWIGLU) {
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    const int n = nb + r;
-                    if (n + 1 < a.N) {
-                        float gt = v[r], up = v[r + 1];
-                        if (a.bias) { gt += bf2f(a.bias[n]); up += bf2f(a.bias[n + 1]); }
-                        gt = bfround(gt); up = bfround(up);
-                        a.out[(size_t)m * a.ldo + (n >> 1)] = f2bf(bfround(silu(gt)) * up);
-                    }
-                }
-            } else {
-                float o[4];
-                const bool full = nb + 3 < a.N;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = nb + r;
-                    float t = v[r];
-                    if (n < a.N) {
-                        if (a.bias) t += bf2f(a.bias[n]);
-                        t = bfround(t);
-                        if constexpr (EPI == EPI_RESID) t = t + bf2f(a.res[(size_t)m * a.ldres + n]);
-                    }
-                    o[r] = t;
-                }
-                bf16_t* dst = a.out + (size_t)m * a.ldo + nb;
-                if (full && ((reinterpret_cast<size_t>(dst) & 7) == 0)) {
-                    uint2 pk;
-                    pk.x = packbf(o[0], o[1]); pk.y = packbf(o[2], o[3]);
-                    *reinterpret_cast<uint2*>(dst) = pk;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (nb + r < a.N) dst[r] = f2bf(o[r]);
-                }
-            }
-        }
+        for (int ai = 0; ai < A_; ++ai)
+            store_c4<EPI>(a, m, n0 + (wn * A_ + ai) * 16 + 4 * g, acc[ai][bi]);   // nb = first of this lane's 4 output columns
     }
 }
 
@@ -220,13 +150,7 @@ int launch_fp4_gemm(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool gemm_fp4_ok(const GemvArgs& a) {
-    return a.w4scale && a.x && a.W && a.out && !a.norm_w && !a.wscale && a.M >= 17 && a.N >= 1 && a.K >= 256 && (a.K % 256) == 0 &&
-           (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K && a.lds >= a.K / 32 &&
-           (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
-           (reinterpret_cast<size_t>(a.w4scale) & 3) == 0 &&
-           (a.epi == EPI_NONE || (a.epi == EPI_RESID && a.res) || (a.epi == EPI_SWIGLU && !(a.N & 1)));
-}
+bool gemm_fp4_ok(const GemvArgs& a) { return fp4_mfma_ok(a, 17, INT_MAX); }
 
 int launch_gemm_fp4(const GemvArgs& a, hipStream_t s) {
     if (!gemm_fp4_ok(a)) return -22;

@@ -20,6 +20,11 @@ __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
+// the same from a use-once stream (nt: do not keep the weight bytes in L2 / the Infinity Cache)
+__device__ __forceinline__ void glds16_nt(const void* src, char* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2);
+}
 
 // Per-workgroup timeline of a GEMM kernel (only in a library built with -DEMU_TRACE: `python -m emu_amd.build --trace`,
 // tools/gemm_trace.py).  Record = 8 x u64 at trace[blockIdx.x * 8]: [0] entry, [1] first k tile landed (after the first

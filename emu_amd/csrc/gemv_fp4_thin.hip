@@ -7,18 +7,17 @@
 //   * a workgroup (4 waves) owns RN = 16 / 32 weight rows and walks K in stages of 256 (128 element bytes + 8 scale bytes per
 //     weight row, 512 bytes per activation row), NSTG stages deep, counted vmcnt + one raw s_barrier per stage;
 //   * element bytes and activations arrive by 16-byte LDS-DMA (one instruction = 8 weight rows or 2 activation rows); the DMA source
-//     address carries the swizzle, the LDS image is lane-linear.  Weight rows are 128 bytes, so rows r and r + 2 share banks: slot
-//     b of row r sits at b ^ ((r >> 1) & 7), which makes the ds_read_b128 of 16 rows x one block conflict-free in every lane group;
+//     address carries the swizzle, the LDS image is lane-linear.  The stage geometry, both swizzles (source side and read side)
+//     and the conversion are fp4_tile.h's, shared with gemm_fp4.hip;
 //   * the k order inside an MFMA is free as long as A and B agree: lane (i, g) of a wave takes ONE whole MX block -- row i, block
 //     4 * ku + g of the stage, one 16-byte LDS read, one scale byte -- and spends its four dwords on four MFMAs; dword q becomes the
 //     A fragment through 4 x v_cvt_scalef32_pk_bf16_fp4 (one byte -> two bf16, the block scale applied in the conversion; every
-//     dequantised value is exact in bf16), and the B lane reads the matching 8 k of activation row i: 16-byte chunk 4 * block + q.
-//     Chunk c of activation row r sits at c ^ s(r), s = the two 2-bit halves of r swapped: lanes g and g + 1 of one lane group read
-//     chunks 4 apart, which the plain c ^ r of gemv_thin.hip would fold onto the same banks;
+//     dequantised value is exact in bf16), and the B lane reads the matching 8 k of activation row i: 16-byte chunk 4 * block + q;
 //   * a unit of work is (16-row group, k half of the stage): RN / 8 units on 4 waves.  Wave u streams the scale bytes of ITS unit
 //     itself: 16 rows x 4 contiguous bytes by one 4-byte DMA into a region of its own (lanes 16..63 repeat lanes 0..15);
-//   * the two k-half partials of a row group meet in LDS at the end; epilogues and rounding points are thin_stream_kernel's
-//     (bias, round to bf16, then residual or SiLU(gate) * up).  No fused RMSNorm: callers normalise first.
+//   * the two k-half partials of a row group meet in LDS at the end; the epilogue is store_c4 (fp4_tile.h: bias, round to bf16,
+//     then residual or SiLU(gate) * up -- thin_stream_kernel's rounding points), the one the 4-bit GEMM uses.  No fused RMSNorm:
+//     callers normalise first.
 // Algorithmic bytes per call = N * (K/2 + K/32).  Activations add MR * 512 / (RN * 136) of that as L2 -> LDS traffic.
 //
 // Conversion semantics on the device (pinned by tests/test_gpu_fp4_wide.py::test_decode_exhaustive_mfma): low nibble -> element 0;
@@ -26,38 +25,14 @@
 // denormals): neither the conversion nor the MFMA flushes them on MI355X (test_decode_denormal_products: all exact).
 #include "common.h"
 #include "kernels.h"
-#include "gemm_tile.h"
+#include "fp4_tile.h"
 
 using namespace emu_gemm;
 
 namespace {
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-// LDS-DMA of a use-once stream (nt: do not keep the bytes in L2 / the Infinity Cache): 16 and 4 bytes per lane
-__device__ __forceinline__ void glds16_nt(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2);
-}
-__device__ __forceinline__ void glds4_nt(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 2);
-}
-// activation-row swizzle: the two 2-bit halves of the row index swapped
-__device__ __forceinline__ int xswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
-// one dword of element bytes (8 codes) -> the 8 bf16 of an MFMA fragment, scaled by 2^(exponent field of sc - 127)
-__device__ __forceinline__ bf16x8_t cvt8(uint32_t d, float sc) {
-    const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0);
-    const bf16x2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1);
-    const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2);
-    const bf16x2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3);
-    return bf16x8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
-
 template <int EPI, int RN, int MR, int NSTG>
 __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
-    constexpr int KC = 256, WROW = KC / 2, XROW = KC * 2;                 // k per stage; bytes per staged weight / activation row
     constexpr int WI = RN / 8, XI = MR / 2, TOT = WI + XI, JMAX = (TOT + 3) / 4;   // 1 KiB DMA instructions per stage: weights, activations
     constexpr int WB = RN * WROW, XB = MR * XROW, ST = WB + XB + 4 * 256;  // stage = weight rows | activation rows | 4 scale regions
     constexpr int RG = RN / 16, UNITS = 2 * RG;
@@ -72,23 +47,17 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     const int i = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * RN;
     const int unit = wave % UNITS, rg = unit >> 1, ku = unit & 1;         // waves >= UNITS stage only (their unit is a repeat)
-    const char* W4 = reinterpret_cast<const char*>(a.W);
 
-    // DMA sources.  Instruction q < WI fills weight rows 8q .. 8q + 7 (lane / 8 selects, slot p = lane % 8 receives block
-    // p ^ ((row >> 1) & 7), rows clamped at N - 1); q >= WI fills activation rows 2(q - WI), + 1 (slot p = lane % 32 receives chunk
-    // p ^ xswz(row), rows clamped at M - 1).
+    // DMA sources (fp4_tile.h): instruction q < WI fills weight rows 8q .. 8q + 7, q >= WI activation rows 2(q - WI), + 1
     const char* src[JMAX];
 #pragma unroll
     for (int j = 0; j < JMAX; ++j) {
         const int q = j * 4 + wave;
         if (q < WI) {
-            const int r = 8 * q + (lane >> 3), c = (lane & 7) ^ ((r >> 1) & 7), n = n0 + r;
-            src[j] = W4 + (size_t)(n < a.N ? n : a.N - 1) * a.ldw + c * 16;
+            src[j] = w_src(a, n0, q, lane);
         } else {
-            int r = 2 * (q - WI) + (lane >> 5);
-            r = r < MR ? r : MR - 1;                                      // (q >= TOT: never issued)
-            const int c = (lane & 31) ^ xswz(r);
-            src[j] = reinterpret_cast<const char*>(a.x + (size_t)(r < a.M ? r : a.M - 1) * a.ldx) + c * 16;
+            const int r = x_dma_row(q - WI, lane);
+            src[j] = x_src(a, 0, r < MR ? r : MR - 1, lane);              // (q >= TOT: never issued)
         }
     }
     const char* ssrc;
@@ -108,15 +77,14 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
                 else glds16(src[j] + kt * XROW, base + q * 1024);
             }
         }
-        glds4_nt(ssrc + kt * (KC / 32), base + WB + XB + wave * 256);
+        glds4<true>(ssrc + kt * SROW, base + WB + XB + wave * 256);
     };
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     const int rb = i < a.M ? i : a.M - 1;              // this lane's activation row (B operand column i)
     const int blk = ku * 4 + g;                        // this lane's MX block of the stage
     const int wr = rg * 16 + i;                        // this lane's weight row (A operand row i)
-    const int woff = wr * WROW + ((blk ^ ((wr >> 1) & 7)) << 4);
+    const int woff = w_off(wr, blk);
     const int soff = WB + XB + wave * 256 + i * 4;
-    const int xsw = xswz(rb);
 #pragma unroll
     for (int t = 0; t < NSTG - 1; ++t) issue(t, t);
     for (int kt = 0; kt < nk; ++kt) {
@@ -129,11 +97,11 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
             const char* sb = smem + (kt % NSTG) * ST;
             const u32x4 wv = *reinterpret_cast<const u32x4*>(sb + woff);
             const uint32_t sd = *reinterpret_cast<const uint32_t*>(sb + soff);
-            const float sc = __uint_as_float(((sd >> (8 * g)) & 0xffu) << 23);
+            const float sc = scale_operand((sd >> (8 * g)) & 0xffu);
             bf16x8_t bf[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                bf[q] = *reinterpret_cast<const bf16x8_t*>(sb + WB + rb * XROW + (((4 * blk + q) ^ xsw) << 4));
+                bf[q] = *reinterpret_cast<const bf16x8_t*>(sb + WB + x_off(rb, 4 * blk + q));
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(wv[q], sc), bf[q], acc, 0, 0, 0);
         }
@@ -153,42 +121,7 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     }
     if (m >= a.M) return;
     const int nb = n0 + 16 * wave + 4 * g;             // first of this lane's 4 output columns
-    if constexpr (EPI == EPI_SWIGLU) {
-#pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-            const int n = nb + r;
-            if (n + 1 < a.N) {
-                float gt = v[r], up = v[r + 1];
-                if (a.bias) { gt += bf2f(a.bias[n]); up += bf2f(a.bias[n + 1]); }
-                gt = bfround(gt); up = bfround(up);
-                a.out[(size_t)m * a.ldo + (n >> 1)] = f2bf(bfround(silu(gt)) * up);
-            }
-        }
-    } else {
-        float o[4];
-        const bool full = nb + 3 < a.N;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = nb + r;
-            float t = v[r];
-            if (n < a.N) {
-                if (a.bias) t += bf2f(a.bias[n]);
-                t = bfround(t);
-                if constexpr (EPI == EPI_RESID) t = t + bf2f(a.res[(size_t)m * a.ldres + n]);
-            }
-            o[r] = t;
-        }
-        bf16_t* dst = a.out + (size_t)m * a.ldo + nb;
-        if (full && ((reinterpret_cast<size_t>(dst) & 7) == 0)) {
-            uint2 pk;
-            pk.x = packbf(o[0], o[1]); pk.y = packbf(o[2], o[3]);
-            *reinterpret_cast<uint2*>(dst) = pk;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (nb + r < a.N) dst[r] = f2bf(o[r]);
-        }
-    }
+    store_c4<EPI>(a, m, nb, v);
 }
 
 template <int RN, int MR, int NSTG>
@@ -208,13 +141,14 @@ int launch_fp4_thin(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool gemv_fp4_thin_ok(const GemvArgs& a) {
-    return a.w4scale && a.x && a.W && a.out && !a.norm_w && !a.wscale && a.M >= 1 && a.M <= 16 && a.N >= 1 && a.K >= 256 && (a.K % 256) == 0 &&
-           (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K && a.lds >= a.K / 32 &&
-           (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
+bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows) {
+    return a.w4scale && a.x && a.W && a.out && !a.norm_w && !a.wscale && a.M >= min_rows && a.M <= max_rows && a.N >= 1 && a.K >= 256 &&
+           (a.K % 256) == 0 && (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K &&
+           a.lds >= a.K / 32 && (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
            (reinterpret_cast<size_t>(a.w4scale) & 3) == 0 &&
            (a.epi == EPI_NONE || (a.epi == EPI_RESID && a.res) || (a.epi == EPI_SWIGLU && !(a.N & 1)));
 }
+bool gemv_fp4_thin_ok(const GemvArgs& a) { return fp4_mfma_ok(a, 1, 16); }
 
 // 32 weight rows per workgroup: measured against 16 at the five LLaMA-33B shapes (tools/fp4_wide_time.py --ab, emu_gemm_tune bits
 // 28-29: 1 / 2 = 16 / 32), 32 rows win everywhere, also where they leave CUs without a workgroup -- qkv 28.1 vs 42.0 us, o_proj 13.1

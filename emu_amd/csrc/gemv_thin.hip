@@ -21,12 +21,6 @@ using namespace emu_gemm;
 
 namespace {
 
-// one LDS-DMA instruction whose source is a use-once stream (nt: do not keep the weight bytes in L2 / the Infinity Cache)
-__device__ __forceinline__ void glds16_nt(const void* src, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 2);
-}
-
 // KCH = 16-byte slots per row and stage: 32 (256 k, one DMA instruction = two rows) or 64 (512 k, one instruction = one row)
 template <int EPI, int RN, int MR, int NSTG, int KCH>
 __global__ __launch_bounds__(256) void thin_stream_kernel(const GemvArgs a) {

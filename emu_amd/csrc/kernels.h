@@ -52,12 +52,16 @@ int launch_gemv_merge(const GemvMergeArgs& a, hipStream_t s);
 // 2..16 rows through LDS-DMA stages and v_mfma_f32_16x16x32_bf16 (gemv_thin.hip); needs K % 256 == 0, no fused norm, bf16 weights
 bool gemv_thin_ok(const GemvArgs& a);
 int launch_gemv_thin(const GemvArgs& a, hipStream_t s);
-// 1..16 rows over MXFP4 weights (a.w4scale set; W = element bytes, ldw in bytes) through LDS-DMA stages, v_cvt_scalef32_pk_bf16_fp4 and
-// v_mfma_f32_16x16x32_bf16 (gemv_fp4_thin.hip); needs K % 256 == 0, lds % 4 == 0, no fused norm; epi NONE / RESID / SWIGLU
+// MXFP4 weights (a.w4scale set; W = element bytes, ldw in bytes) on the matrix cores: LDS-DMA stages, v_cvt_scalef32_pk_bf16_fp4 and
+// v_mfma_f32_16x16x32_bf16, the stage layout and the epilogue shared (fp4_tile.h).  fp4_mfma_ok is the one argument
+// check of both kernels: min_rows <= M <= max_rows, K % 256 == 0, lds % 4 == 0, 16-byte aligned W and x, no fused norm; epi NONE /
+// RESID / SWIGLU
+bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows);
+// 1..16 rows: a weight stream, every converted fragment used by one MFMA (gemv_fp4_thin.hip); fp4_mfma_ok(a, 1, 16)
 bool gemv_fp4_thin_ok(const GemvArgs& a);
 int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s);
-// 17 rows and more over MXFP4 weights: the thin kernel's arithmetic and epilogues on a two-dimensional tile, each converted weight
-// fragment feeding several MFMAs (gemm_fp4.hip); same requirements; ragged M and N
+// 17 rows and more: a two-dimensional tile, each converted weight fragment feeding several MFMAs (gemm_fp4.hip); ragged M and N;
+// fp4_mfma_ok(a, 17, INT_MAX)
 bool gemm_fp4_ok(const GemvArgs& a);
 int launch_gemm_fp4(const GemvArgs& a, hipStream_t s);
 

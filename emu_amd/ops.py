@@ -147,9 +147,8 @@ def linear_fp4w(x, w4, scales, bias=None, res=None, norm_w=None, eps: float = 0.
     return out
 
 
-def linear_fp4w_thin(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
-    """``linear`` over an MXFP4 weight stream for 1..16 rows on the matrix cores (K % 256 == 0, no fused norm; epi NONE / RESID /
-    SWIGLU); see emu_linear_fp4w_thin_bf16."""
+def _linear_fp4w_mfma(symbol, x, w4, scales, bias, res, epi, out):
+    """The shared body of ``linear_fp4w_thin`` and ``linear_fp4w_gemm``: one argument list, ``symbol`` names the C entry point."""
     _req(x, "x"); _req(w4, "w4", torch.uint8); _req(scales, "scales", torch.uint8)
     assert x.dim() == 2 and w4.dim() == 2 and scales.dim() == 2 and w4.shape[0] == scales.shape[0], (x.shape, w4.shape, scales.shape)
     assert x.stride(1) == 1 and w4.stride(1) == 1 and scales.stride(1) == 1
@@ -165,34 +164,21 @@ def linear_fp4w_thin(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, ou
         _req(bias, "bias")
     if res is not None:
         _req(res, "res")
-    check(lib().emu_linear_fp4w_thin_bf16(_p(x), _p(w4), _p(scales), _p(bias), _p(res), _p(out), M, N, K, x.stride(0), w4.stride(0),
-                                          scales.stride(0), res.stride(0) if res is not None else 0, out.stride(0), int(epi),
-                                          stream(x)), "emu_linear_fp4w_thin_bf16")
+    check(getattr(lib(), symbol)(_p(x), _p(w4), _p(scales), _p(bias), _p(res), _p(out), M, N, K, x.stride(0), w4.stride(0),
+                                 scales.stride(0), res.stride(0) if res is not None else 0, out.stride(0), int(epi), stream(x)), symbol)
     return out
+
+
+def linear_fp4w_thin(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
+    """``linear`` over an MXFP4 weight stream for 1..16 rows on the matrix cores (K % 256 == 0, no fused norm; epi NONE / RESID /
+    SWIGLU); see emu_linear_fp4w_thin_bf16."""
+    return _linear_fp4w_mfma("emu_linear_fp4w_thin_bf16", x, w4, scales, bias, res, epi, out)
 
 
 def linear_fp4w_gemm(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
     """``linear`` over MXFP4 weights for 17 rows and more (K % 256 == 0, no fused norm; epi NONE / RESID / SWIGLU): the 4-bit GEMM,
     same arithmetic and rounding points as ``linear_fp4w_thin``; see emu_linear_fp4w_gemm_bf16."""
-    _req(x, "x"); _req(w4, "w4", torch.uint8); _req(scales, "scales", torch.uint8)
-    assert x.dim() == 2 and w4.dim() == 2 and scales.dim() == 2 and w4.shape[0] == scales.shape[0], (x.shape, w4.shape, scales.shape)
-    assert x.stride(1) == 1 and w4.stride(1) == 1 and scales.stride(1) == 1
-    M, K = x.shape
-    N = w4.shape[0]
-    if K % 32 == 0:                                # (any other K is the library's to refuse)
-        assert w4.shape[1] == K // 2 and scales.shape[1] == K // 32, (x.shape, w4.shape, scales.shape)
-    cols = N // 2 if epi == EPI_SWIGLU else N
-    if out is None:
-        out = torch.empty(M, cols, device=x.device, dtype=BF16)
-    _req(out, "out")
-    if bias is not None:
-        _req(bias, "bias")
-    if res is not None:
-        _req(res, "res")
-    check(lib().emu_linear_fp4w_gemm_bf16(_p(x), _p(w4), _p(scales), _p(bias), _p(res), _p(out), M, N, K, x.stride(0), w4.stride(0),
-                                          scales.stride(0), res.stride(0) if res is not None else 0, out.stride(0), int(epi),
-                                          stream(x)), "emu_linear_fp4w_gemm_bf16")
-    return out
+    return _linear_fp4w_mfma("emu_linear_fp4w_gemm_bf16", x, w4, scales, bias, res, epi, out)
 
 
 def linear_fp8(x8, xscale, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):

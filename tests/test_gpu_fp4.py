@@ -11,18 +11,9 @@ import pytest
 import torch
 
 from tests import tiny
+from tests.fp4_common import BF16, _f32, _tiny_model, bfr, rel_err, tiny_fp4  # noqa: F401 (tiny_fp4: the fixture, used by name)
 
 pytestmark = pytest.mark.gpu
-BF16 = torch.bfloat16
-
-
-def rel_err(got, want):
-    got, want = got.float().cpu(), want.float().cpu()
-    return float((got - want).norm() / want.norm().clamp_min(1e-12))
-
-
-def bfr(x):
-    return x.to(BF16).float()
 
 
 # ------------------------------------------------------------------------------------------------ (a) quantiser
@@ -163,15 +154,6 @@ def test_fp4_rejects_prefill_rows_and_bad_k():
         ops.linear_fp4w(torch.zeros(1, 48, dtype=BF16, device="cuda"), q48, sc48)         # K % 32 != 0
 
 
-def _tiny_model(golden_dir):
-    from emu_amd import EmuModel, TextDecoderCfg
-    z = tiny.load(golden_dir, "generate_tiny.npz")
-    v, l, vocab, W = tiny.weights_from(z)
-    m = EmuModel(v, TextDecoderCfg(instruct=True), llama_cfg=l, device="cuda")
-    m.load_state_dict(W, strict=True)
-    return m, v, l, vocab, W
-
-
 def test_use_fp4_needs_registration_and_excludes_fp8(golden_dir):
     from emu_amd import mxfp4
     from emu_amd._lib import EmuHipError, check, lib
@@ -203,25 +185,6 @@ def test_use_fp4_needs_registration_and_excludes_fp8(golden_dir):
 
 
 # ------------------------------------------------------------------------------------------------ engine
-@pytest.fixture(scope="module")
-def tiny_fp4(golden_dir):
-    from emu_amd import mxfp4
-    from oracle import emu2_ref as R
-    m, v, l, vocab, W = _tiny_model(golden_dir)
-    W = R.bf16_round(W)
-    W4 = dict(W)
-    for k, t in W.items():                       # blocks run along K inside a row: they commute with the row packing
-        if k.startswith("decoder.lm.") and t.dim() == 2 and "embed_tokens" not in k:
-            W4[k] = mxfp4.dequantize(*mxfp4.quantize_rows(t))
-    return m, W, W4, tiny.oracle_cfg(v, l, vocab)
-
-
-def _f32(cache):
-    cache.k = [None if t is None else t.float() for t in cache.k]
-    cache.v = [None if t is None else t.float() for t in cache.v]
-    return cache
-
-
 def test_engine_dequantised_weights_match_host_definition(tiny_fp4):                     # (f)
     m, W, W4, cfg = tiny_fp4
     lm = m.decoder.lm

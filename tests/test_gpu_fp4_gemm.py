@@ -9,24 +9,13 @@ and with the residual, on both sides of every row-tile boundary of the three ins
 4-bit bytes streamed; (f) mode 2 leaves such a prefill bit-identical to bf16; (g) greedy and 5-beam ids against a twin engine that
 holds the dequantised weights as bf16; (h) ``release_bf16``: memory falls, every output is bit-identical, the other modes refuse.
 """
-import ctypes as C
-
 import pytest
 import torch
 
 from tests import tiny
+from tests.fp4_common import BF16, _case, _gemv_profile, _tiny_model, bfr, rel_err, tiny_fp4  # noqa: F401 (tiny_fp4: the fixture)
 
 pytestmark = pytest.mark.gpu
-BF16 = torch.bfloat16
-
-
-def rel_err(got, want):
-    got, want = got.float().cpu(), want.float().cpu()
-    return float((got - want).norm() / want.norm().clamp_min(1e-12))
-
-
-def bfr(x):
-    return x.to(BF16).float()
 
 
 # ------------------------------------------------------------------------------------------------ (a) decode, exhaustive
@@ -84,21 +73,6 @@ def test_decode_denormal_products_gemm():
 
 
 # ------------------------------------------------------------------------------------------------ (b) linear parity
-_CASE = {}
-
-
-def _case(N, K, seed_extra=0):
-    """Weights, their 4-bit tensors on the device and the exact dequantisation, once per shape."""
-    from emu_amd import mxfp4, ops
-    key = (N, K, seed_extra)
-    if key not in _CASE:
-        g = torch.Generator().manual_seed(N * 3 + K + seed_extra)
-        w = (torch.randn(N, K, generator=g) * 0.03).to(BF16)
-        q, sc = ops.quantize_mxfp4_rows(w.cuda())
-        _CASE[key] = (q, sc, mxfp4.dequantize(q.cpu(), sc.cpu()))
-    return _CASE[key]
-
-
 def _differs_from_bf16_gemm(x, wd, got, **kw):
     """Share of elements that differ from ``ops.linear`` on the dequantised weights; printed only.  nan where the bf16 GEMM does not
     take the shape (its SwiGLU epilogue refuses narrow N)."""
@@ -195,42 +169,6 @@ def test_fp4_gemm_rejections():
 
 
 # ------------------------------------------------------------------------------------------------ engine
-def _tiny_model(golden_dir, weights=None):
-    from emu_amd import EmuModel, TextDecoderCfg
-    z = tiny.load(golden_dir, "generate_tiny.npz")
-    v, l, vocab, W = tiny.weights_from(z)
-    m = EmuModel(v, TextDecoderCfg(instruct=True), llama_cfg=l, device="cuda")
-    m.load_state_dict(W if weights is None else weights, strict=True)
-    return m, v, l, vocab, W
-
-
-@pytest.fixture(scope="module")
-def tiny_fp4(golden_dir):
-    from emu_amd import mxfp4
-    from oracle import emu2_ref as R
-    m, v, l, vocab, W = _tiny_model(golden_dir)
-    W = R.bf16_round(W)
-    W4 = dict(W)
-    for k, t in W.items():                       # blocks run along K inside a row: they commute with the row packing
-        if k.startswith("decoder.lm.") and t.dim() == 2 and "embed_tokens" not in k:
-            W4[k] = mxfp4.dequantize(*mxfp4.quantize_rows(t))
-    return m, W, W4, tiny.oracle_cfg(v, l, vocab)
-
-
-def _gemv_profile(fn):
-    """weight_bytes and launches the weight-stream profiler saw while fn ran."""
-    from emu_amd._lib import check, lib
-    check(lib().emu_profile_gemv(1), "emu_profile_gemv")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, wb, nl = C.c_double(), C.c_double(), C.c_long()
-        check(lib().emu_profile_gemv_read(C.byref(ms), C.byref(wb), C.byref(nl)), "emu_profile_gemv_read")
-    finally:
-        check(lib().emu_profile_gemv(0), "emu_profile_gemv")
-    return wb.value, nl.value
-
-
 def _prefill_inputs(B, S, hidden, pad, seed):
     g = torch.Generator().manual_seed(seed)
     x = (torch.randn(B, S, hidden, generator=g) * 0.5).to(BF16)

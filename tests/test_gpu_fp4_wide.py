@@ -10,24 +10,13 @@ holding the dequantised weights as bf16; (f) the vocabulary-sharded head.
 Observed on MI355X for bf16-denormal products (scale bytes 1 and 2 in (a), test_decode_denormal_products): all 2048 of them come
 out exact -- neither v_cvt_scalef32_pk_bf16_fp4 nor the bf16 MFMA flushes them, as mxfp4.dequantize does not.
 """
-import ctypes as C
-
 import pytest
 import torch
 
 from tests import tiny
+from tests.fp4_common import BF16, _case, _f32, _gemv_profile, _tiny_model, bfr, rel_err, tiny_fp4  # noqa: F401 (tiny_fp4: the fixture)
 
 pytestmark = pytest.mark.gpu
-BF16 = torch.bfloat16
-
-
-def rel_err(got, want):
-    got, want = got.float().cpu(), want.float().cpu()
-    return float((got - want).norm() / want.norm().clamp_min(1e-12))
-
-
-def bfr(x):
-    return x.to(BF16).float()
 
 
 # ------------------------------------------------------------------------------------------------ (a) decode, exhaustive
@@ -87,21 +76,6 @@ def test_decode_denormal_products():
 
 
 # ------------------------------------------------------------------------------------------------ (b) linear parity
-_CASE = {}
-
-
-def _case(N, K, seed_extra=0):
-    """Weights, their 4-bit tensors on the device and the exact dequantisation, once per shape."""
-    from emu_amd import mxfp4, ops
-    key = (N, K, seed_extra)
-    if key not in _CASE:
-        g = torch.Generator().manual_seed(N * 3 + K + seed_extra)
-        w = (torch.randn(N, K, generator=g) * 0.03).to(BF16)
-        q, sc = ops.quantize_mxfp4_rows(w.cuda())
-        _CASE[key] = (q, sc, mxfp4.dequantize(q.cpu(), sc.cpu()))
-    return _CASE[key]
-
-
 def _differs_from_bf16_stream(x, wd, got, **kw):
     from emu_amd import ops
     ref = ops.linear(x.cuda(), wd.to(BF16).cuda(), **kw)
@@ -194,48 +168,6 @@ def test_use_fp4_wide_rejects_widths_not_multiple_of_256():
 
 
 # ------------------------------------------------------------------------------------------------ engine
-def _tiny_model(golden_dir, weights=None):
-    from emu_amd import EmuModel, TextDecoderCfg
-    z = tiny.load(golden_dir, "generate_tiny.npz")
-    v, l, vocab, W = tiny.weights_from(z)
-    m = EmuModel(v, TextDecoderCfg(instruct=True), llama_cfg=l, device="cuda")
-    m.load_state_dict(W if weights is None else weights, strict=True)
-    return m, v, l, vocab, W
-
-
-@pytest.fixture(scope="module")
-def tiny_fp4(golden_dir):
-    from emu_amd import mxfp4
-    from oracle import emu2_ref as R
-    m, v, l, vocab, W = _tiny_model(golden_dir)
-    W = R.bf16_round(W)
-    W4 = dict(W)
-    for k, t in W.items():                       # blocks run along K inside a row: they commute with the row packing
-        if k.startswith("decoder.lm.") and t.dim() == 2 and "embed_tokens" not in k:
-            W4[k] = mxfp4.dequantize(*mxfp4.quantize_rows(t))
-    return m, W, W4, tiny.oracle_cfg(v, l, vocab)
-
-
-def _f32(cache):
-    cache.k = [None if t is None else t.float() for t in cache.k]
-    cache.v = [None if t is None else t.float() for t in cache.v]
-    return cache
-
-
-def _gemv_profile(fn):
-    """weight_bytes and launches the GEMV profiler saw while fn ran."""
-    from emu_amd._lib import check, lib
-    check(lib().emu_profile_gemv(1), "emu_profile_gemv")
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms, wb, nl = C.c_double(), C.c_double(), C.c_long()
-        check(lib().emu_profile_gemv_read(C.byref(ms), C.byref(wb), C.byref(nl)), "emu_profile_gemv_read")
-    finally:
-        check(lib().emu_profile_gemv(0), "emu_profile_gemv")
-    return wb.value, nl.value
-
-
 @pytest.mark.parametrize("B", [5, 16])
 def test_fp4_wide_step_matches_oracle_and_streams_the_4bit_set(tiny_fp4, B):                 # (d)
     """bf16 prefill of B rows, then ONE cached single-token step of B rows through the wide fp4 stream == the oracle's step on the
