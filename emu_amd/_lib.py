@@ -129,6 +129,7 @@ _PROTOS = {
     "emu_llama_use_fp8": (i32, [vp, i32]),
     "emu_linear_fp4w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_linear_fp4w_gemm_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_linear_fp4w_mfma_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_llama_set_layer_fp4": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_fp4": (i32, [vp, vp, vp]),
     "emu_llama_use_fp4": (i32, [vp, i32]),
@@ -219,6 +220,8 @@ def lib() -> C.CDLL:
             l.emu_gemm_tune.restype, l.emu_gemm_tune.argtypes = None, [i32]
             l.emu_gemm_tune(int(os.environ["EMU_GEMM_TUNE"]))
         for name, (res, args) in _PROTOS.items():
+            if _OVERRIDE and not hasattr(l, name):       # tools A/B against an older build of the same ABI version: a symbol added
+                continue                                 # since is absent there, and calling it raises AttributeError
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
         _lib = l

@@ -102,12 +102,15 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 }
 // MXFP4 weights on the matrix cores: up to 16 rows stream them (gemv_fp4_thin.hip), 17 and more run the 4-bit GEMM (gemm_fp4.hip),
 // both under the GEMV profiler's accounting (the 4-bit bytes of the matrix, once).  No fused norm; a row count outside
-// [min_rows, max_rows] is refused, never forwarded to the other kernel
+// [min_rows, max_rows] is refused, never forwarded to the other kernel.  tail_ok: K may end in a partial stage (K % 32 == 0; scale
+// rows at fp4_scale_stride(K)) -- the engine and emu_linear_fp4w_mfma_bf16; the two older entry points keep K % 256 == 0
 int linear_fp4_mfma(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
-                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s, int min_rows, int max_rows) {
+                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s, int min_rows, int max_rows,
+                    bool tail_ok) {
     GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
-    if (!fp4_mfma_ok(g, min_rows, max_rows)) return -22;
-    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return M <= 16 ? launch_gemv_fp4_thin(g, s) : launch_gemm_fp4(g, s); });
+    if (!fp4_mfma_ok(g, min_rows, max_rows, tail_ok)) return -22;
+    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s,
+                         [&] { return M <= 16 ? launch_gemv_fp4_thin(g, s, tail_ok) : launch_gemm_fp4(g, s, tail_ok); });
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
@@ -337,13 +340,19 @@ int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     if (!A || !W4 || !scales || !C) return -22;
     return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, 16);
+                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, 16, false);
 }
 int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     if (!A || !W4 || !scales || !C) return -22;
     return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s), 17, INT_MAX);
+                           lda, ldw, lds, ldres, ldc, epi, S(s), 17, INT_MAX, false);
+}
+int emu_linear_fp4w_mfma_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
+    if (!A || !W4 || !scales || !C) return -22;
+    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
+                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, INT_MAX, true);
 }
 int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
     if (!w || !q || !scales) return -22;
@@ -514,7 +523,7 @@ struct emu_llama {
     bool fp8_decode = false;
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2): W8A8 GEMMs for prefill rows as well
     // optional MXFP4 copies for the decode stream (emu_llama_use_fp4; exclusive with the fp8 stream): element bytes [N, K/2] + E8M0
-    // block scales [N, K/32] of the packed matrices.  Prefill and steps of more than two rows keep the bf16 weights, unless fp4_wide
+    // block scales [N, K/32] of the packed matrices, scale rows at a stride of fp4_scale_stride(K).  Prefill and steps of more than two rows keep the bf16 weights, unless fp4_wide
     // (emu_llama_use_fp4(m, 2)) sends steps of 3..16 rows through the matrix-core stream (gemv_fp4_thin.hip) and fp4_all
     // (emu_llama_use_fp4(m, 3)) the calls of 17 rows and more through the 4-bit GEMM (gemm_fp4.hip).  bf16_released
     // (emu_llama_release_bf16; mode 3 only, which it pins): the layers' bf16 matrix pointers and lm_head are null.
@@ -756,11 +765,11 @@ struct LlamaCall {
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
         if (pw.W4 && (plan.fp4_gemm || plan.fp4_thin))             // (the plan's row range: 17 and more, or up to 16)
-            return linear_fp4_mfma(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, K / 32, ldres, ldc, epi, s, plan.fp4_gemm ? 17 : 1,
-                                   plan.fp4_gemm ? INT_MAX : 16);
+            return linear_fp4_mfma(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, fp4_scale_stride(K), ldres, ldc, epi, s,
+                                   plan.fp4_gemm ? 17 : 1, plan.fp4_gemm ? INT_MAX : 16, true);
         if (pw.W4 && plan.fp4_rows)
             return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
-                          pw.s4, K / 32);
+                          pw.s4, fp4_scale_stride(K));
         if (pw.W8 && plan.fp8_rows) return linear(A, B(pw.W8), nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, gain_in ? eps : 0.f, epi, s, pw.s8);
         if (!pw.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
         if (pw.W8) return linear_q8(w, A, K, pw.W8, pw.s8, res, C, rows, N, K, ldres, ldc, epi, s);
@@ -1213,8 +1222,8 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
             return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
         for (const auto& l : m->layers4)
             if (!l.wqkv) return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
-        if (enable >= 2 && ((c.hidden & 255) || ((c.heads_local * c.head_dim) & 255) || (c.ffn_local & 255)))
-            return fail(m->ctx, -22, "emu_llama_use_fp4: modes 2 and 3 (steps of 3 rows and more) need reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
+        if (enable >= 2 && (c.hidden < 256 || c.heads_local * c.head_dim < 256 || c.ffn_local < 256))
+            return fail(m->ctx, -22, "emu_llama_use_fp4: modes 2 and 3 (steps of 3 rows and more) need reduction widths (hidden, heads_local * head_dim, ffn_local) of at least 256 that are multiples of 32 (they need not be multiples of 256: the last K stage may be partial)");
     }
     m->fp4_decode = enable != 0;
     m->fp4_wide = enable >= 2;
@@ -1397,7 +1406,7 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
     const bool thin = m->fp4_wide && M >= 3 && M <= 16 && (ws_fits || m->bf16_released), gemm = m->fp4_all && M >= 17;
     if (m->fp4_decode && M <= 2)                                  // the MXFP4 copy covers the same rows (quantised from the shard)
         return linear(hidden, B(m->lm_head4), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H / 2, 0, ld, c.rms_eps, EPI_NONE, s,
-                      nullptr, nullptr, 0, m->lm_scale4, H / 32);
+                      nullptr, nullptr, 0, m->lm_scale4, fp4_scale_stride(H));
     if (!thin && !gemm) {
         if (m->fp8_decode && M <= 2 && m->lm_head8)               // the e4m3 copy covers the same rows (quantised from the shard)
             return linear(hidden, B(m->lm_head8), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H, 0, ld, c.rms_eps, EPI_NONE, s,
@@ -1408,8 +1417,8 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
     if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
     TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
     if (thin || gemm)
-        return linear_fp4_mfma(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, H / 32, 0, ld, EPI_NONE, s, gemm ? 17 : 1,
-                               gemm ? INT_MAX : 16);
+        return linear_fp4_mfma(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, fp4_scale_stride(H), 0, ld, EPI_NONE, s,
+                               gemm ? 17 : 1, gemm ? INT_MAX : 16, true);
     return linear(ws, m->lm_head, nullptr, nullptr, nullptr, out, M, N, H, H, H, 0, ld, 0.f, EPI_NONE, s);
 }
 

@@ -1,7 +1,8 @@
 // Device code shared by the two MXFP4 matrix-core kernels (gemv_fp4_thin.hip: 1..16 rows, k-split units; gemm_fp4.hip: 17 rows
 // and more, a two-dimensional tile): the geometry of one K stage in LDS, its two swizzles -- each defined ONCE and called by the
 // DMA-source side (w_src / x_src) and by the LDS-read side (w_off / x_off), which must agree or the MFMA multiplies the wrong k --,
-// the 4-bit -> bf16 fragment conversion and the lane epilogue (store_c4).  glds16_nt lives in gemm_tile.h next to glds16: the bf16
+// the partial last stage of a K that is no multiple of 256 (source clamp and read mask), the 4-bit -> bf16 fragment conversion and
+// the lane epilogue (store_c4).  glds16_nt lives in gemm_tile.h next to glds16: the bf16
 // few-row stream (gemv_thin.hip) uses it too.
 //
 // A stage is KC = 256 k: per weight row 128 element bytes (8 MX blocks of 16 bytes) + 8 scale bytes, per activation row 512 bytes
@@ -33,23 +34,41 @@ __device__ __forceinline__ int wswz(int r) { return (r >> 1) & 7; }
 __device__ __forceinline__ int xswz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
 // DMA sources of a lane.  Weight instruction q of a tile at weight row n0 fills tile rows 8q .. 8q + 7 (lane / 8 selects; slot
-// lane % 8 receives block slot ^ wswz(row); rows clamped at N - 1).  An activation instruction fills two tile rows (x_dma_row:
-// instruction qa, lane / 32 selects; slot lane % 32 receives chunk slot ^ xswz(row); rows clamped at M - 1).
+// lane % 8 receives block w_src_blk = slot ^ wswz(row); rows clamped at N - 1).  An activation instruction fills two tile rows
+// (x_dma_row: instruction qa, lane / 32 selects; slot lane % 32 receives chunk x_src_chunk = slot ^ xswz(row); rows clamped at M - 1).
+__device__ __forceinline__ int w_src_blk(int q, int lane) { return (lane & 7) ^ wswz(8 * q + (lane >> 3)); }
 __device__ __forceinline__ const char* w_src(const GemvArgs& a, int n0, int q, int lane) {
-    const int r = 8 * q + (lane >> 3), c = (lane & 7) ^ wswz(r), n = n0 + r;
+    const int r = 8 * q + (lane >> 3), c = w_src_blk(q, lane), n = n0 + r;
     return reinterpret_cast<const char*>(a.W) + (size_t)(n < a.N ? n : a.N - 1) * a.ldw + c * 16;
 }
 __device__ __forceinline__ int x_dma_row(int qa, int lane) { return 2 * qa + (lane >> 5); }
+__device__ __forceinline__ int x_src_chunk(int r, int lane) { return (lane & 31) ^ xswz(r); }
 __device__ __forceinline__ const char* x_src(const GemvArgs& a, int m0, int r, int lane) {
-    const int c = (lane & 31) ^ xswz(r), m = m0 + r;
+    const int c = x_src_chunk(r, lane), m = m0 + r;
     return reinterpret_cast<const char*>(a.x + (size_t)(m < a.M ? m : a.M - 1) * a.ldx) + c * 16;
 }
+// A partial last stage (K % 256 != 0) holds kb = (K % 256) / 32 valid MX blocks, kb = 1..7: a lane whose block (weights) or 16-byte
+// chunk (activations: four per block) lies at or past K fetches the same block / chunk of the stage before -- the same row, in
+// range because K >= 256, the same slot -- so nothing is read past a row's K, and what lands in those slots is dead: the read side
+// (tail_mask_w / tail_mask_x) keeps it out of the MFMA.  *_src_past: this lane's source of instruction q / activation row r is such a one.
+__device__ __forceinline__ bool w_src_past(int q, int lane, int kb) { return w_src_blk(q, lane) >= kb; }
+__device__ __forceinline__ bool x_src_past(int r, int lane, int kb) { return x_src_chunk(r, lane) >= 4 * kb; }
 // LDS-read side: byte offset of MX block blk in staged weight row r, and of chunk c in staged activation row r
 __device__ __forceinline__ int w_off(int r, int blk) { return r * WROW + ((blk ^ wswz(r)) << 4); }
 __device__ __forceinline__ int x_off(int r, int c) { return r * XROW + ((c ^ xswz(r)) << 4); }
 
 // E8M0 scale byte -> the scale operand of the conversion: a float whose exponent field is the byte (2^(byte - 127))
 __device__ __forceinline__ float scale_operand(uint32_t byte) { return __uint_as_float(byte << 23); }
+// The read side of a partial last stage: block blk >= kb is dead.  Whatever its LDS slots hold (the stage before; scale padding,
+// which may be 0xFF = NaN), the lane multiplies nothing: code 0 under scale 2^0 times activation 0 -- exactly the products of a
+// matrix extended to the next multiple of 256 with code 0, scale byte 127 and zero activations.
+__device__ __forceinline__ void tail_mask_w(bool live, u32x4& wv, float& sc) {
+    if (!live) { wv = u32x4{0u, 0u, 0u, 0u}; sc = 1.f; }
+}
+__device__ __forceinline__ bf16x8_t tail_mask_x(bool live, bf16x8_t bf) {
+    const u32x4 z = live ? __builtin_bit_cast(u32x4, bf) : u32x4{0u, 0u, 0u, 0u};
+    return __builtin_bit_cast(bf16x8_t, z);
+}
 // one dword of element bytes (8 codes) -> the 8 bf16 of an MFMA fragment, scaled by 2^(exponent field of sc - 127)
 __device__ __forceinline__ bf16x8_t cvt8(uint32_t d, float sc) {
     const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0);

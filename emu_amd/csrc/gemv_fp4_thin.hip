@@ -4,7 +4,8 @@
 // gemv_fp4.hip decodes and multiplies on the VALU and cannot hold more than two rows of accumulators; gemv_thin.hip already streams
 // bf16 weights for these row counts through LDS-DMA stages into v_mfma_f32_16x16x32_bf16 with no VALU in the loop.  This is that
 // structure fed from 4-bit bytes (format: emu_amd/mxfp4.py -- elements [N, K/2], element 2j in the low nibble; E8M0 scales [N, K/32]):
-//   * a workgroup (4 waves) owns RN = 16 / 32 weight rows and walks K in stages of 256 (128 element bytes + 8 scale bytes per
+//   * a workgroup (4 waves) owns RN = 16 / 32 weight rows and walks K in stages of 256, the last one partial when K % 256 != 0
+//     (K % 32 == 0: the TAIL instantiations) (128 element bytes + 8 scale bytes per
 //     weight row, 512 bytes per activation row), NSTG stages deep, counted vmcnt + one raw s_barrier per stage;
 //   * element bytes and activations arrive by 16-byte LDS-DMA (one instruction = 8 weight rows or 2 activation rows); the DMA source
 //     address carries the swizzle, the LDS image is lane-linear.  The stage geometry, both swizzles (source side and read side)
@@ -23,6 +24,8 @@
 // Conversion semantics on the device (pinned by tests/test_gpu_fp4_wide.py::test_decode_exhaustive_mfma): low nibble -> element 0;
 // the scale operand contributes 2^(its exponent field - 127).  With scale bytes 1 and 2 some products lie below 2^-126 (bf16
 // denormals): neither the conversion nor the MFMA flushes them on MI355X (test_decode_denormal_products: all exact).
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 #include "fp4_tile.h"
@@ -31,7 +34,12 @@ using namespace emu_gemm;
 
 namespace {
 
-template <int EPI, int RN, int MR, int NSTG>
+// TAIL: K % 256 != 0 (K % 32 == 0, K >= 256): one more stage with kb = (K % 256) / 32 valid MX blocks, peeled off the k loop, so
+// the instantiations for whole stages keep theirs.  fp4_tile.h has the two halves of it: lanes whose block / chunk lies at or past
+// K fetch the stage before (w_src_past / x_src_past; scale rows are padded to whole stages, fp4_scale_stride), and the read side
+// multiplies nothing for a dead block (tail_mask_w / tail_mask_x).  A unit whose k half is dead altogether (ku = 1, kb <= 4) sits
+// the stage out; it still issues and waits like everyone.
+template <int EPI, int RN, int MR, int NSTG, bool TAIL>
 __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     constexpr int WI = RN / 8, XI = MR / 2, TOT = WI + XI, JMAX = (TOT + 3) / 4;   // 1 KiB DMA instructions per stage: weights, activations
     constexpr int WB = RN * WROW, XB = MR * XROW, ST = WB + XB + 4 * 256;  // stage = weight rows | activation rows | 4 scale regions
@@ -49,15 +57,20 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     const int unit = wave % UNITS, rg = unit >> 1, ku = unit & 1;         // waves >= UNITS stage only (their unit is a repeat)
 
     // DMA sources (fp4_tile.h): instruction q < WI fills weight rows 8q .. 8q + 7, q >= WI activation rows 2(q - WI), + 1
+    const int nk = TAIL ? a.K / KC + 1 : a.K / KC;
+    const int kb = TAIL ? (a.K % KC) / 32 : SROW;      // valid MX blocks of the last stage
     const char* src[JMAX];
+    uint32_t past = 0;                                 // TAIL: bit j = in the last stage, the source of instruction j lies at or past K
 #pragma unroll
     for (int j = 0; j < JMAX; ++j) {
         const int q = j * 4 + wave;
         if (q < WI) {
             src[j] = w_src(a, n0, q, lane);
+            if constexpr (TAIL) past |= (w_src_past(q, lane, kb) ? 1u : 0u) << j;
         } else {
-            const int r = x_dma_row(q - WI, lane);
-            src[j] = x_src(a, 0, r < MR ? r : MR - 1, lane);              // (q >= TOT: never issued)
+            const int r = x_dma_row(q - WI, lane), rr = r < MR ? r : MR - 1;   // (q >= TOT: never issued)
+            src[j] = x_src(a, 0, rr, lane);
+            if constexpr (TAIL) past |= (x_src_past(rr, lane, kb) ? 1u : 0u) << j;
         }
     }
     const char* ssrc;
@@ -65,16 +78,18 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
         const int n = n0 + rg * 16 + i;
         ssrc = reinterpret_cast<const char*>(a.w4scale) + (size_t)(n < a.N ? n : a.N - 1) * a.lds + ku * 4;
     }
-    const int nk = a.K / KC;
     auto issue = [&](int kt, int stage) {
         kt = kt < nk ? kt : nk - 1;                    // past-the-end stages re-load the last one (uniform vmcnt counts)
+        const bool last = TAIL && kt == nk - 1;        // (nk >= 2 then: the stage before exists)
         char* base = smem + stage * ST;
 #pragma unroll
         for (int j = 0; j < JMAX; ++j) {
             const int q = j * 4 + wave;
             if (j * 4 + 3 < TOT || q < TOT) {
-                if (q < WI) glds16_nt(src[j] + kt * WROW, base + q * 1024);            // weight rows: stream
-                else glds16(src[j] + kt * XROW, base + q * 1024);
+                int kj = kt;
+                if constexpr (TAIL) kj -= last && ((past >> j) & 1u) ? 1 : 0;
+                if (q < WI) glds16_nt(src[j] + kj * WROW, base + q * 1024);            // weight rows: stream
+                else glds16(src[j] + kj * XROW, base + q * 1024);
             }
         }
         glds4<true>(ssrc + kt * SROW, base + WB + XB + wave * 256);
@@ -87,25 +102,33 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     const int soff = WB + XB + wave * 256 + i * 4;
 #pragma unroll
     for (int t = 0; t < NSTG - 1; ++t) issue(t, t);
-    for (int kt = 0; kt < nk; ++kt) {
+    // one stage of the k loop; LAST: the partial stage of a TAIL kernel
+    auto round = [&](int kt, auto last_stage) {
+        constexpr bool LAST = decltype(last_stage)::value;
         // this wave's share of stage kt has landed
         if (TOT % 4 == 0 || wave < TOT % 4) wait_vmcnt<(NSTG - 2) * L_HI>();
         else wait_vmcnt<(NSTG - 2) * L_LO>();
         __builtin_amdgcn_s_barrier();                  // ... and everyone's; everyone is done reading stage kt - 1
         issue(kt + NSTG - 1, (kt + NSTG - 1) % NSTG);
-        if (wave < UNITS) {
+        if (wave < UNITS && (!LAST || 4 * ku < kb)) {
             const char* sb = smem + (kt % NSTG) * ST;
-            const u32x4 wv = *reinterpret_cast<const u32x4*>(sb + woff);
+            u32x4 wv = *reinterpret_cast<const u32x4*>(sb + woff);
             const uint32_t sd = *reinterpret_cast<const uint32_t*>(sb + soff);
-            const float sc = scale_operand((sd >> (8 * g)) & 0xffu);
+            float sc = scale_operand((sd >> (8 * g)) & 0xffu);
+            if constexpr (LAST) tail_mask_w(blk < kb, wv, sc);
             bf16x8_t bf[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
+            for (int q = 0; q < 4; ++q) {
                 bf[q] = *reinterpret_cast<const bf16x8_t*>(sb + WB + x_off(rb, 4 * blk + q));
+                if constexpr (LAST) bf[q] = tail_mask_x(blk < kb, bf[q]);
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8(wv[q], sc), bf[q], acc, 0, 0, 0);
         }
-    }
+    };
+    const int nfull = TAIL ? nk - 1 : nk;
+    for (int kt = 0; kt < nfull; ++kt) round(kt, std::false_type{});
+    if constexpr (TAIL) round(nfull, std::true_type{});
     wait_vmcnt<0>();                                   // drain the tail DMA before the ring is reused
     __syncthreads();
     f32x4_t (*part)[64] = reinterpret_cast<f32x4_t (*)[64]>(smem);
@@ -124,10 +147,10 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
     store_c4<EPI>(a, m, nb, v);
 }
 
-template <int RN, int MR, int NSTG>
+template <int RN, int MR, int NSTG, bool TAIL>
 int launch_fp4_thin(const GemvArgs& a, hipStream_t s) {
     const dim3 grid((a.N + RN - 1) / RN), block(256);
-#define EMU_F4T_CASE(E) case E: hipLaunchKernelGGL((fp4_thin_kernel<E, RN, MR, NSTG>), grid, block, 0, s, a); break;
+#define EMU_F4T_CASE(E) case E: hipLaunchKernelGGL((fp4_thin_kernel<E, RN, MR, NSTG, TAIL>), grid, block, 0, s, a); break;
     switch (a.epi) {
         EMU_F4T_CASE(EPI_NONE)
         EMU_F4T_CASE(EPI_RESID)
@@ -141,10 +164,10 @@ int launch_fp4_thin(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows) {
+bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows, bool tail_ok) {
     return a.w4scale && a.x && a.W && a.out && !a.norm_w && !a.wscale && a.M >= min_rows && a.M <= max_rows && a.N >= 1 && a.K >= 256 &&
-           (a.K % 256) == 0 && (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K &&
-           a.lds >= a.K / 32 && (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
+           (a.K % (tail_ok ? 32 : 256)) == 0 && (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K &&
+           a.lds >= fp4_scale_stride(a.K) && (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
            (reinterpret_cast<size_t>(a.w4scale) & 3) == 0 &&
            (a.epi == EPI_NONE || (a.epi == EPI_RESID && a.res) || (a.epi == EPI_SWIGLU && !(a.N & 1)));
 }
@@ -154,10 +177,15 @@ bool gemv_fp4_thin_ok(const GemvArgs& a) { return fp4_mfma_ok(a, 1, 16); }
 // 28-29: 1 / 2 = 16 / 32), 32 rows win everywhere, also where they leave CUs without a workgroup -- qkv 28.1 vs 42.0 us, o_proj 13.1
 // vs 17.6, down 25.5 vs 38.6 at 5 rows: the activation rows a workgroup re-stages from L2 weigh twice the 4-bit bytes of 16 weight
 // rows.  The ring is as deep as lets three workgroups share a CU's LDS.
-int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s) {
-    if (!gemv_fp4_thin_ok(a)) return -22;
+// The same tiles whether or not K ends in a partial stage (tail_ok admits one; a K of whole stages runs the kernels without it).
+template <bool TAIL>
+static int dispatch_fp4_thin(const GemvArgs& a, hipStream_t s) {
     const int pin = (emu_gemm_tune_get() >> 28) & 3;
     const bool rn32 = pin != 1;
-    if (a.M <= 8) return rn32 ? launch_fp4_thin<32, 8, 5>(a, s) : launch_fp4_thin<16, 8, 6>(a, s);
-    return rn32 ? launch_fp4_thin<32, 16, 4>(a, s) : launch_fp4_thin<16, 16, 4>(a, s);
+    if (a.M <= 8) return rn32 ? launch_fp4_thin<32, 8, 5, TAIL>(a, s) : launch_fp4_thin<16, 8, 6, TAIL>(a, s);
+    return rn32 ? launch_fp4_thin<32, 16, 4, TAIL>(a, s) : launch_fp4_thin<16, 16, 4, TAIL>(a, s);
+}
+int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s, bool tail_ok) {
+    if (!fp4_mfma_ok(a, 1, 16, tail_ok)) return -22;
+    return a.K % KC ? dispatch_fp4_thin<true>(a, s) : dispatch_fp4_thin<false>(a, s);
 }

@@ -53,17 +53,21 @@ int launch_gemv_merge(const GemvMergeArgs& a, hipStream_t s);
 bool gemv_thin_ok(const GemvArgs& a);
 int launch_gemv_thin(const GemvArgs& a, hipStream_t s);
 // MXFP4 weights (a.w4scale set; W = element bytes, ldw in bytes) on the matrix cores: LDS-DMA stages, v_cvt_scalef32_pk_bf16_fp4 and
-// v_mfma_f32_16x16x32_bf16, the stage layout and the epilogue shared (fp4_tile.h).  fp4_mfma_ok is the one argument
-// check of both kernels: min_rows <= M <= max_rows, K % 256 == 0, lds % 4 == 0, 16-byte aligned W and x, no fused norm; epi NONE /
-// RESID / SWIGLU
-bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows);
-// 1..16 rows: a weight stream, every converted fragment used by one MFMA (gemv_fp4_thin.hip); fp4_mfma_ok(a, 1, 16)
+// v_mfma_f32_16x16x32_bf16, the stage layout and the epilogue shared (fp4_tile.h).  Both kernels fetch a stage's 8 scale bytes per
+// row by 4-byte LDS-DMA, so a scale row spans whole stages: fp4_scale_stride(K) bytes at least -- K / 32 where K % 256 == 0, else
+// 8 per started stage (K = 896: 32, K = 2240: 72); the padding bytes are read and never used (emu_amd/mxfp4.py::scale_stride).
+inline int fp4_scale_stride(int K) { return K % 256 == 0 ? K / 32 : 8 * ((K + 255) / 256); }
+// fp4_mfma_ok is the one argument check of both kernels: min_rows <= M <= max_rows, K >= 256 and K % 256 == 0 (tail_ok: K % 32 == 0,
+// the last stage partial), lds % 4 == 0 and lds >= fp4_scale_stride(K), 16-byte aligned W and x, no fused norm; epi NONE / RESID /
+// SWIGLU
+bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows, bool tail_ok = false);
+// 1..16 rows: a weight stream, every converted fragment used by one MFMA (gemv_fp4_thin.hip); fp4_mfma_ok(a, 1, 16, tail_ok)
 bool gemv_fp4_thin_ok(const GemvArgs& a);
-int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s);
+int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s, bool tail_ok = false);
 // 17 rows and more: a two-dimensional tile, each converted weight fragment feeding several MFMAs (gemm_fp4.hip); ragged M and N;
-// fp4_mfma_ok(a, 17, INT_MAX)
+// fp4_mfma_ok(a, 17, INT_MAX, tail_ok)
 bool gemm_fp4_ok(const GemvArgs& a);
-int launch_gemm_fp4(const GemvArgs& a, hipStream_t s);
+int launch_gemm_fp4(const GemvArgs& a, hipStream_t s, bool tail_ok = false);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

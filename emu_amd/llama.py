@@ -426,7 +426,8 @@ class LlamaEngine:
         lm_head with the device quantiser and register them for the decode stream (B*T <= 2 rows; with ``use_fp4(wide=True)`` also
         steps of 3..16 rows, with ``all_rows=True`` every row count).  Keys already provided through ``load_fp4`` are kept.  Prefill and
         steps of more than 16 rows keep the bf16 weights unless ``all_rows``, so both sets stay resident (33B: bf16 66 GB + fp4
-        17 GB) until ``release_bf16``.  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
+        17 GB) until ``release_bf16``.  The scale tensors are kept with their rows padded to ``mxfp4.scale_stride(K)`` bytes (byte 127;
+        only where K is no multiple of 256), which is how the matrix-core kernels read them.  Round-to-nearest, not calibrated; not a reference feature; quality on a trained checkpoint is unmeasured."""
         if not self.ready:
             raise RuntimeError("quantize_fp4: load all weights first")
         self.__dict__.setdefault("_fp4", {})
@@ -434,13 +435,15 @@ class LlamaEngine:
             if key not in self._fp4:
                 if self.bf16_released:
                     raise RuntimeError(f"quantize_fp4: the bf16 weights were released (release_bf16); {key!r} cannot be quantised anew")
-                self._fp4[key] = ops.quantize_mxfp4_rows(self._fp4_source(key))
+                q, sc = ops.quantize_mxfp4_rows(self._fp4_source(key))
+                self._fp4[key] = (q, mxfp4.pad_scales(sc, q.shape[1] * 2))
                 self._fp4_register(key)
 
     def load_fp4(self, key: str, packed: torch.Tensor, scales: torch.Tensor) -> None:
         """Register externally prepared MXFP4 tensors (``mxfp4.quantize_rows`` or any quantiser that writes the format) for
         ``"<layer>.wqkv|wo|wgu|wdown"`` or ``"lm_head"``: ``packed`` uint8 [N, K/2], ``scales`` uint8 [N, K/32] for the [N, K] packed
-        bf16 matrix of this rank (the tensor-parallel shard; lm_head: the rows this rank holds)."""
+        bf16 matrix of this rank (the tensor-parallel shard; lm_head: the rows this rank holds).  The scale rows are padded to
+        ``mxfp4.scale_stride(K)`` on registration (a copy of the scales only, never of the element bytes)."""
         src = self._fp4_source(key)
         if src is None:
             raise RuntimeError(f"load_fp4({key!r}): load the bf16 weights first (their packed shapes define the fp4 shapes)")
@@ -454,7 +457,7 @@ class LlamaEngine:
         if getattr(self, "fp4_decode", False):
             raise RuntimeError("load_fp4: switch the fp4 stream off first (use_fp4(False)); captured graphs hold the old pointers")
         self.__dict__.setdefault("_fp4", {})
-        self._fp4[key] = (packed.to(self.device).contiguous(), scales.to(self.device).contiguous())
+        self._fp4[key] = (packed.to(self.device).contiguous(), mxfp4.pad_scales(scales.to(self.device).contiguous(), K))
         self._fp4_register(key)
 
     def use_fp4(self, enable: bool = True, wide: bool = False, all_rows: bool = False) -> None:
@@ -464,8 +467,9 @@ class LlamaEngine:
         ``use_fp4(True)``: steps of B*T <= 2 rows (greedy / sampled decode) stream the 4-bit set; everything else streams bf16.
         ``use_fp4(True, wide=True)``: steps of 3..16 rows (the default 5-beam search, a batch of prompts, contrastive search) stream
         the 4-bit set as well, through the matrix-core kernel (csrc/gemv_fp4_thin.hip); needs hidden, heads_local * head_dim and
-        ffn_local to be multiples of 256 (the library refuses otherwise and says why).  Prefill and steps of more than 16 rows
-        stream bf16 unless ``all_rows``.
+        ffn_local to be at least 256 (the library refuses otherwise and says why; any multiple of 32 from there on will do, so the
+        TP = 4 / 8 shards of the 33B shapes run: a width that is no multiple of 256 ends in a partial K stage).  Prefill and steps
+        of more than 16 rows stream bf16 unless ``all_rows``.
         ``use_fp4(True, wide=True, all_rows=True)``: prefill and steps of 17 rows and more (beams x batch) run the 4-bit set too,
         through the 4-bit GEMM (csrc/gemm_fp4.hip; the RoPE and RMSNorm epilogue fusions of the bf16 prefill and the two-lane
         prefill are off), so one generation sees one weight set and ``release_bf16`` may free the bf16 matrices.  Same width
@@ -497,7 +501,8 @@ class LlamaEngine:
 
     def fp4_dequantized(self, key: str) -> torch.Tensor:
         """fp32 value of a registered MXFP4 tensor (exact in bf16; tests feed the oracle the weights the stream uses)."""
-        return mxfp4.dequantize(*self._fp4[key])
+        q, sc = self._fp4[key]
+        return mxfp4.dequantize(q, sc[:, :q.shape[1] // 16])        # (the scale rows are kept padded: mxfp4.scale_stride)
 
     # ------------------------------------------------------------------ KV cache / workspace
     KV_BUCKETS = (256, 512, 1024)

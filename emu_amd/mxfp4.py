@@ -4,7 +4,9 @@ A packed weight matrix ``[N, K]`` (``K % 32 == 0``) is stored as
 
 * elements ``uint8 [N, K/2]``: element ``2j`` in the low nibble of byte ``j``, element ``2j+1`` in the high nibble.  A code is a
   sign bit (8) and an E2M1 magnitude index: 0, 0.5, 1, 1.5, 2, 3, 4, 6;
-* scales ``uint8 [N, K/32]``, E8M0: one per block of 32 consecutive elements of a row, ``scale = 2 ** (byte - 127)``.
+* scales ``uint8 [N, K/32]``, E8M0: one per block of 32 consecutive elements of a row, ``scale = 2 ** (byte - 127)``.  The
+  matrix-core kernels want the scale rows at a stride of ``scale_stride(K)`` bytes, which is more than ``K/32`` where K is no
+  multiple of 256: ``pad_scales``.
 
 ``quantize_rows`` is round-to-nearest with the OCP MX scale rule: for a block with ``amax > 0`` the exponent is
 ``e = floor(log2(amax)) - 2`` clamped to [-126, 125] (so ``amax / 2**e`` lies in [4, 8) and magnitudes above 6 saturate), an
@@ -82,6 +84,28 @@ def dequantize(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
     N = packed.shape[0]
     v = decode_codes(unpack_codes(packed)).reshape(N, -1, BLOCK)
     return (v * scale_values(scales)[..., None]).reshape(N, -1)
+
+
+def scale_stride(K: int) -> int:
+    """Bytes between the scale rows of a [N, K] matrix as the matrix-core kernels want them (``fp4_scale_stride`` in
+    csrc/kernels.h): they fetch the 8 scale bytes of a 256-wide K stage by 4-byte DMA, so a row spans whole stages.  ``K / 32``
+    where ``K % 256 == 0`` (nothing to pad), else ``8 * ceil(K / 256)``: 32 for K = 896, 72 for K = 2240."""
+    if K < BLOCK or K % BLOCK:
+        raise ValueError(f"scale_stride: K = {K} is not a positive multiple of {BLOCK}")
+    return K // BLOCK if K % 256 == 0 else 8 * ((K + 255) // 256)
+
+
+def pad_scales(scales: torch.Tensor, K: int) -> torch.Tensor:
+    """scales uint8 [N, K/32] -> uint8 [N, scale_stride(K)], the new columns filled with byte 127 (2 ** 0; the kernels read them
+    and never use them).  ``padded[:, :K // 32]`` is the input again; where ``K % 256 == 0`` the input itself is returned."""
+    if scales.dtype != torch.uint8 or scales.dim() != 2 or scales.shape[1] != K // BLOCK:
+        raise ValueError(f"pad_scales: expected uint8 [N, {K // BLOCK}] for K = {K}, got {scales.dtype} {tuple(scales.shape)}")
+    stride = scale_stride(K)
+    if stride == scales.shape[1]:
+        return scales
+    out = torch.full((scales.shape[0], stride), 127, dtype=torch.uint8, device=scales.device)
+    out[:, :scales.shape[1]] = scales
+    return out
 
 
 def bytes_per_row(K: int) -> int:

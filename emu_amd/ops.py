@@ -9,6 +9,7 @@ from typing import Optional
 
 import torch
 
+from . import mxfp4
 from ._lib import check, lib
 
 EPI_NONE, EPI_RESID, EPI_SWIGLU, EPI_SILU, EPI_GELU, EPI_GEGLU = range(6)
@@ -171,14 +172,31 @@ def _linear_fp4w_mfma(symbol, x, w4, scales, bias, res, epi, out):
 
 def linear_fp4w_thin(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
     """``linear`` over an MXFP4 weight stream for 1..16 rows on the matrix cores (K % 256 == 0, no fused norm; epi NONE / RESID /
-    SWIGLU); see emu_linear_fp4w_thin_bf16."""
+    SWIGLU); see emu_linear_fp4w_thin_bf16.  Any other K % 32 == 0 from 256 up: ``linear_fp4w_mfma``."""
     return _linear_fp4w_mfma("emu_linear_fp4w_thin_bf16", x, w4, scales, bias, res, epi, out)
 
 
 def linear_fp4w_gemm(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
     """``linear`` over MXFP4 weights for 17 rows and more (K % 256 == 0, no fused norm; epi NONE / RESID / SWIGLU): the 4-bit GEMM,
-    same arithmetic and rounding points as ``linear_fp4w_thin``; see emu_linear_fp4w_gemm_bf16."""
+    same arithmetic and rounding points as ``linear_fp4w_thin``; see emu_linear_fp4w_gemm_bf16.  Any other K % 32 == 0 from 256 up:
+    ``linear_fp4w_mfma``."""
     return _linear_fp4w_mfma("emu_linear_fp4w_gemm_bf16", x, w4, scales, bias, res, epi, out)
+
+
+def linear_fp4w_mfma(x, w4, scales, bias=None, res=None, epi: int = EPI_NONE, out=None):
+    """``linear`` over MXFP4 weights on the matrix cores for any row count and any K >= 256 with K % 32 == 0 (no fused norm; epi NONE
+    / RESID / SWIGLU): ``linear_fp4w_thin``'s kernel up to 16 rows, ``linear_fp4w_gemm``'s above, the same tiles, a K that is no
+    multiple of 256 ending in a partial stage.  ``scales`` is [N, K/32] (padded here: ``mxfp4.pad_scales``) or already a view
+    [N, K/32] / [N, mxfp4.scale_stride(K)] whose row stride is a multiple of 4 and at least ``mxfp4.scale_stride(K)``; see
+    emu_linear_fp4w_mfma_bf16."""
+    K = x.shape[1]
+    if K >= 32 and K % 32 == 0 and scales.dim() == 2:      # (any other K is the library's to refuse)
+        stride = mxfp4.scale_stride(K)
+        if scales.shape[1] == K // 32 and scales.stride(0) < stride:
+            scales = mxfp4.pad_scales(scales.contiguous(), K)
+        if scales.shape[1] == stride:
+            scales = scales[:, :K // 32]
+    return _linear_fp4w_mfma("emu_linear_fp4w_mfma_bf16", x, w4, scales, bias, res, epi, out)
 
 
 def linear_fp8(x8, xscale, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):

@@ -184,6 +184,13 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
  * (gemm_fp4.hip: a workgroup owns 64 weight rows x 32 / 64 / 128 activation rows, every converted weight fragment feeds 2 or 4
  * MFMAs; ragged M and N); M < 17 and every violated requirement: -22.  It computes what emu_linear_bf16 computes on the
  * dequantised weights, up to fp32 summation order.
+ * emu_linear_fp4w_mfma_bf16: the same product, arguments, epilogues and rounding points for every M >= 1 (the kernel of
+ * emu_linear_fp4w_thin_bf16 up to 16 rows, that of emu_linear_fp4w_gemm_bf16 above, the same tiles) and every K >= 256 with
+ * K % 32 == 0: a K that is no multiple of 256 ends in a partial stage of (K % 256) / 32 blocks; nothing is read past a row's K
+ * elements and nothing past K contributes.  Both kernels fetch a K stage's 8 scale bytes per row by 4-byte DMA, so a scale row must
+ * span whole stages: lds % 4 == 0 and lds >= K / 32 where K % 256 == 0, else lds >= 8 * ceil(K / 256) (K = 896: 32, K = 2240: 72;
+ * emu_amd/mxfp4.py::scale_stride / pad_scales).  The bytes past K / 32 are read and never used, whatever they are.  With
+ * K % 256 == 0 it runs the two entry points above, bit for bit; they keep refusing any other K.
  * Not a reference feature; what round-to-nearest MXFP4 does to a trained checkpoint is NOT measured by this project. */
 int emu_quantize_mxfp4_rows(const void* w_bf16, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s);
 int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
@@ -192,6 +199,8 @@ int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, cons
 int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
 int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
+int emu_linear_fp4w_mfma_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s);
 /* emu_linear_bf16 (M > 8, epi in {NONE, RESID, GEGLU}) with the fused epilogues of the UNet transformer blocks -- what
  * diffusers' BasicTransformerBlock computes as LayerNorm -> Linear (norm1/2/3 ahead of attn1.to_q/k/v, attn2.to_q,
@@ -369,7 +378,8 @@ int emu_llama_set_head_fp8(emu_llama* m, const void* lm_head8, const float* lm_s
 int emu_llama_use_fp8(emu_llama* m, int enable);
 /* Optional MXFP4 decode stream (not in the reference; 0.53125 byte per weight, 0.53 of the fp8 stream's bytes).  W4 / scales: the
  * two tensors of emu_quantize_mxfp4_rows over the SAME packed (and, under tensor parallelism, sharded) bf16 matrix -- or prepared
- * offline by any quantiser that writes the format (emu_amd/mxfp4.py).  emu_llama_set_head_fp4 covers the rows the bf16 lm_head
+ * offline by any quantiser that writes the format (emu_amd/mxfp4.py), the scale rows of every matrix at the stride that
+ * emu_linear_fp4w_mfma_bf16 asks of its K (K / 32 where K % 256 == 0, else 8 * ceil(K / 256)).  emu_llama_set_head_fp4 covers the rows the bf16 lm_head
  * pointer holds (emu_llama_set_head_shard is honoured).  emu_llama_use_fp4(m, 1): steps of B*T <= 2 rows stream the 4-bit set
  * through the per-layer launches; prefill and steps of more rows keep the bf16 weights, so both sets stay resident.  It fails
  * (-22) unless every layer and the head are registered, if hidden, heads_local*head_dim or ffn_local is not a multiple of 32, and
@@ -378,7 +388,8 @@ int emu_llama_use_fp8(emu_llama* m, int enable);
  * emu_llama_use_fp4(m, 2) is mode 1 plus: every forward / logits call of 3 <= B*T <= 16 rows (a 5-beam step, a batch of prompts,
  * contrastive search) streams the 4-bit set through emu_linear_fp4w_thin_bf16's kernel -- qkv, o_proj, gate/up, down and the head
  * (whole or emu_llama_set_head_shard rows); the RMSNorm launches of the bf16 few-row path stay, attention is untouched.  It also
- * fails (-22) if hidden, heads_local*head_dim or ffn_local is not a multiple of 256 (TP = 4 / 8 shards of the 33B shapes: keep mode 1).
+ * fails (-22) if hidden, heads_local*head_dim or ffn_local is below 256 (a multiple of 32 at least 256 will do: the TP = 4 / 8
+ * shards of the 33B shapes, K = 896 / 2240 / 4480, run with a partial last K stage).
  * Steps of 17 rows and more, and prefill, keep the bf16 weights in modes 1 and 2.
  * emu_llama_use_fp4(m, 3) is mode 2 plus: every forward / logits call of B*T >= 17 rows (prefill, beams x batch) runs qkv, o_proj,
  * gate/up, down and the head (whole or sharded) through emu_linear_fp4w_gemm_bf16's kernel, so no row count reads a bf16 matrix.

@@ -3,6 +3,8 @@
 replaces, one process (needs a GPU):
 
     python tools/fp4_gemm_time.py [--layers 60] [--iters 20] [--rounds 2] [--skip shape,engine] [--out profiles/fp4_prefill.md]
+    python tools/fp4_gemm_time.py --shards --out FILE.md   # leg 1 at 20 / 64 rows on the TP = 4 / 8 per-rank shapes, through
+                                                           # ops.linear_fp4w_mfma (K = 896 / 2240 / 4480: a partial last K stage)
 
 1. Every projection on its own at the LLaMA-33B widths, M = 20 / 64 / 770 / 1544 rows: ``ops.linear`` on bf16 weights against
    ``ops.linear_fp4w_gemm`` (HIP events, the weights rotating through more than 600 MB of copies, the contenders alternating).
@@ -21,7 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from emu_amd import ops, synth  # noqa: E402
+from emu_amd import mxfp4, ops, synth  # noqa: E402
 from emu_amd.conf.emu_conf import LlamaCfg  # noqa: E402
 from emu_amd.constants import VOCAB_EMU2_CHAT  # noqa: E402
 from emu_amd.llama import EmuHipContext, LlamaEngine  # noqa: E402
@@ -29,6 +31,9 @@ from emu_amd.llama import EmuHipContext, LlamaEngine  # noqa: E402
 BF16 = torch.bfloat16
 SHAPES = [("qkv", 19968, 6656, 0), ("o+res", 6656, 6656, 1), ("gateup+swiglu", 35840, 6656, 2), ("down+res", 6656, 17920, 1),
           ("lm_head", 32274, 6656, 0)]
+# per-rank shapes of the 33B model at TP = 4 / 8 (emu_amd/tp.py): the row-parallel matrices' K is no multiple of 256 there
+SHARD_SHAPES = [("o+res tp8", 6656, 896, 1), ("down+res tp8", 6656, 2240, 1), ("down+res tp4", 6656, 4480, 1), ("qkv tp8", 2688, 6656, 0),
+                ("gateup+swiglu tp8", 4480, 6656, 2)]
 ROWS = (20, 64, 770, 1544)
 
 
@@ -48,25 +53,27 @@ def timeit(fn, iters):
 def shape_leg(a, dev):
     """rows: [name, N, K, M, bf16 us, fp4 us]"""
     out = []
-    for name, N, K, epi in SHAPES:
+    fp4_mfma = ops.linear_fp4w_mfma if a.shards else ops.linear_fp4w_gemm
+    for name, N, K, epi in (SHARD_SHAPES if a.shards else SHAPES):
         n4 = max(1, int(600e6 // (N * K * 17 / 32)) + 1)
         nb = max(1, int(600e6 // (N * K * 2)) + 1)
         w4, wb = [], []
         for c in range(max(n4, nb)):
             w = (torch.randn(N, K, device=dev) * 0.02).to(BF16)
             if c < n4:
-                w4.append(ops.quantize_mxfp4_rows(w))
+                q, sc = ops.quantize_mxfp4_rows(w)
+                w4.append((q, mxfp4.pad_scales(sc, K) if a.shards else sc))   # scale rows at the kernels' stride once, not per launch
             if c < nb:
                 wb.append(w)
             del w
-        for M in ROWS:
+        for M in (ROWS[:2] if a.shards else ROWS):
             xv = torch.randn(M, K, device=dev).to(BF16)
             res = torch.randn(M, N, device=dev).to(BF16) if epi == 1 else None
             i = [0]
 
             def new():
                 i[0] += 1
-                ops.linear_fp4w_gemm(xv, *w4[i[0] % len(w4)], res=res, epi=epi)
+                fp4_mfma(xv, *w4[i[0] % len(w4)], res=res, epi=epi)
 
             def other():
                 i[0] += 1
@@ -159,6 +166,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp4_prefill.md"))
     ap.add_argument("--skip", default="", help="comma list of legs to leave out: shape, engine")
+    ap.add_argument("--shards", action="store_true", help="only leg 1 at 20 / 64 rows, on the TP = 4 / 8 per-rank shapes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("fp4_gemm_time.py measures on a GPU; none found")
@@ -183,7 +191,7 @@ def main():
             out += ["", "At 20 and 64 rows (bound by the weight stream; after `release_bf16()` there is no bf16 to fall back to) the 4-bit GEMM is "
                     + ("not slower than bf16 on any of the five shapes." if not slow else
                        "**slower than bf16** at: " + ", ".join(f"{r[0]} M={r[3]} (x{r[5] / r[4]:.2f})" for r in slow) + "."), ""]
-        if "engine" not in skip:
+        if "engine" not in skip and not a.shards:
             res = engine_leg(a, dev)
             out += [f"## Whole prefill, {a.layers} layers at the LLaMA-33B shape, TP = 1", "",
                     "bf16 = the default path (RoPE / KV append / V^T in the qkv epilogue, K-slice sums with the RMSNorm); mode 3 = 4-bit GEMMs, unfused",

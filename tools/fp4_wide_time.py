@@ -3,6 +3,8 @@
 
     python tools/fp4_wide_time.py [--layers 60] [--iters 30] [--rounds 2] [--out profiles/fp4_wide.md]
     python tools/fp4_wide_time.py --ab          # 16 / 32 weight rows per workgroup (emu_gemm_tune bits 28-29); prints only
+    python tools/fp4_wide_time.py --shards --out FILE.md   # leg 1 at 5 / 8 / 16 rows on the TP = 4 / 8 per-rank shapes, through
+                                                           # ops.linear_fp4w_mfma (K = 896 / 2240 / 4480: a partial last K stage)
 
 1. Every weight stream on its own at the LLaMA-33B shapes (HIP events, the weights rotating through more copies than the infinity
    cache holds, the contenders alternating in windows of one run): at 5 / 8 / 16 rows the bf16 few-row stream (gemv_thin.hip)
@@ -21,7 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from emu_amd import ops, synth  # noqa: E402
+from emu_amd import mxfp4, ops, synth  # noqa: E402
 from emu_amd._lib import lib  # noqa: E402
 from emu_amd.conf.emu_conf import LlamaCfg  # noqa: E402
 from emu_amd.constants import VOCAB_EMU2_CHAT  # noqa: E402
@@ -31,6 +33,9 @@ BF16 = torch.bfloat16
 HBM = 8.0e12
 SHAPES = [("qkv", 19968, 6656, 0), ("o+res", 6656, 6656, 1), ("gateup+swiglu", 35840, 6656, 2), ("down+res", 6656, 17920, 1),
           ("lm_head", 32274, 6656, 0)]
+# per-rank shapes of the 33B model at TP = 4 / 8 (emu_amd/tp.py): the row-parallel matrices' K is no multiple of 256 there
+SHARD_SHAPES = [("o+res tp8", 6656, 896, 1), ("down+res tp8", 6656, 2240, 1), ("down+res tp4", 6656, 4480, 1), ("qkv tp8", 2688, 6656, 0),
+                ("gateup+swiglu tp8", 4480, 6656, 2)]
 
 
 def timeit(fn, iters):
@@ -64,8 +69,11 @@ def weight_sets(N, K, dev, want_bf16):
 def stream_leg(a, dev, rows_list, against):
     """rows: [name, N, K, M, other us, other frac, new us, new frac]; against = 'bf16' (thin bf16 stream) or 'valu' (gemv_fp4)."""
     out = []
-    for name, N, K, epi in SHAPES:
+    fp4_mfma = ops.linear_fp4w_mfma if a.shards else ops.linear_fp4w_thin
+    for name, N, K, epi in (SHARD_SHAPES if a.shards else SHAPES):
         w4, wb = weight_sets(N, K, dev, against == "bf16")
+        if a.shards:                                     # scale rows at the kernels' stride once, not per launch
+            w4 = [(q, mxfp4.pad_scales(sc, K)) for q, sc in w4]
         for M in rows_list:
             xv = torch.randn(M, K, device=dev).to(BF16)
             res = torch.randn(M, N, device=dev).to(BF16) if epi == 1 else None
@@ -73,7 +81,7 @@ def stream_leg(a, dev, rows_list, against):
 
             def new():
                 i[0] += 1
-                ops.linear_fp4w_thin(xv, *w4[i[0] % len(w4)], res=res, epi=epi)
+                fp4_mfma(xv, *w4[i[0] % len(w4)], res=res, epi=epi)
 
             def other():
                 i[0] += 1
@@ -165,6 +173,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp4_wide.md"))
     ap.add_argument("--ab", action="store_true", help="only the rows-per-workgroup A/B (prints, writes nothing)")
     ap.add_argument("--skip", default="", help="comma list of legs to leave out: stream, beam")
+    ap.add_argument("--shards", action="store_true", help="only leg 1 at 5 / 8 / 16 rows, on the TP = 4 / 8 per-rank shapes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("fp4_wide_time.py measures on a GPU; none found")
@@ -187,6 +196,7 @@ def main():
                     "| stream | N | K | rows | bf16 us | frac | fp4 us | frac | fp4 / bf16 time |", "|---|---|---|---|---|---|---|---|---|"]
             for r in wide:
                 out.append(f"| {r[0]} | {r[1]} | {r[2]} | {r[3]} | {r[4]:.1f} | {r[5]:.3f} | {r[6]:.1f} | {r[7]:.3f} | {r[6] / r[4]:.3f} |")
+        if "stream" not in skip and not a.shards:
             narrow = stream_leg(a, dev, (1, 2), "valu")
             out += ["", "## 1 / 2 rows: the VALU 4-bit stream (`gemv_fp4_kernel`, no fused norm) against the matrix-core stream", "",
                     "Same method.  This table says whether one-row fp4 decode should move onto the matrix cores.", "",
@@ -195,7 +205,7 @@ def main():
                 out.append(f"| {r[0]} | {r[1]} | {r[2]} | {r[3]} | {r[4]:.1f} | {r[5]:.3f} | {r[6]:.1f} | {r[7]:.3f} | {r[6] / r[4]:.3f} |")
             wins = sum(1 for r in narrow if r[6] < r[4])
             out += ["", f"The matrix-core stream is faster than the VALU stream in {wins} of {len(narrow)} of these cases.", ""]
-        if "beam" not in skip:
+        if "beam" not in skip and not a.shards:
             times, S = beam_leg(a, dev)
             b, f = min(times["bf16"]), min(times["fp4 wide"])
             out += [f"## A 5-beam step, {a.layers} layers at the LLaMA-33B shape, TP = 1", "",

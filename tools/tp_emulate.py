@@ -3,7 +3,9 @@
 loop (the all-reduce launches are real, their cross-GPU latency is not).  With a third argument "p2p" the all-reduces are the
 one-shot peer-to-peer kernel (csrc/p2p.hip) with one rank instead.  Usage: python tools/tp_emulate.py [tp] [steps] [p2p|rccl] [modes, e.g. 0,1,2]
 (modes: emu_llama_set_decode_fused -- 0 launches, 1 fused layers cut at the all-reduces, 2 all-reduce inside the launch, 3 the all-reduce in the
-tail of the o_proj / down_proj launches, 4 the persistent weight-streaming engine (csrc/decode_engine.hip); tp = 1: 0,1)"""
+tail of the o_proj / down_proj launches, 4 the persistent weight-streaming engine (csrc/decode_engine.hip); tp = 1: 0,1)
+A fifth argument "beam5" adds the weight modes: ms per 5-beam step of this rank with bf16 weights against ``use_fp4(True, wide=True)``
+(the few-row MXFP4 stream; at tp = 4 / 8 o_proj and down end in a partial K stage), from two beam searches of different lengths."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -67,3 +69,27 @@ with torch.no_grad():
             print(f"tp={tp} shard on one GPU, {'p2p' if p2p else 'rccl'} all-reduce, {names[mode]}, {'hipGraph' if graph else 'eager'}: "
                   f"{ms:.3f} ms/token ({eng.weight_bytes_per_token() / 1e9:.2f} GB of weights per token per rank; ids "
                   f"{'match' if ids == first else 'DIFFER'}; give-ups {eng.decode_fused_stats()[0]}{'; decode tail merge' if tail else ''})", flush=True)
+
+if len(sys.argv) > 5 and sys.argv[5] == "beam5":
+    eng.set_decode_fused(0, 0)
+    eng.quantize_fp4()
+
+    def search(n):
+        eng.beam_search_generate(x, mask, 5, n, min_len=n)
+        torch.cuda.synchronize()
+
+    def per_step(n0=8, n1=40):
+        ts = {}
+        for n in (n0, n1):
+            search(n)                                # warm-up: graph capture of this length
+            t = time.perf_counter()
+            search(n)
+            ts[n] = time.perf_counter() - t
+        return (ts[n1] - ts[n0]) / (n1 - n0) * 1e3
+    with torch.no_grad():
+        for rnd in range(2):
+            for wide in (False, True):
+                eng.use_fp4(wide, wide=wide)
+                print(f"tp={tp} shard on one GPU, 5-beam step behind a {S}-row prompt, {'fp4 wide (mode 2)' if wide else 'bf16'}, window {rnd}: "
+                      f"{per_step():.3f} ms per step", flush=True)
+        eng.use_fp4(False)
