@@ -134,6 +134,7 @@ _PROTOS = {
     "emu_llama_set_head_fp4": (i32, [vp, vp, vp]),
     "emu_llama_use_fp4": (i32, [vp, i32]),
     "emu_llama_release_bf16": (i32, [vp]),
+    "emu_llama_weight_kernel": (i32, [i32, i32, i32, i32, i32, i32]),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),

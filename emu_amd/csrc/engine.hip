@@ -33,6 +33,7 @@ namespace {
 inline hipStream_t S(emu_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline const bf16_t* B(const void* p) { return reinterpret_cast<const bf16_t*>(p); }
 inline bf16_t* B(void* p) { return reinterpret_cast<bf16_t*>(p); }
+inline const uint8_t* U8(const void* p) { return reinterpret_cast<const uint8_t*>(p); }
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 int fail(emu_ctx* c, int code, const char* what) {
@@ -78,14 +79,8 @@ int gemv_profiled(double weight_bytes, hipStream_t s, Launch launch) {
 
 int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* res, const bf16_t* norm_w,
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
-           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0, const uint8_t* w4scale = nullptr,
-           int lds = 0) {
+           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0) {
     if (wscale && M > 2) return -22;                 // fp8 weights are a decode-only stream
-    if (w4scale) {                                   // so are MXFP4 weights (gemv_fp4.hip): W = element bytes, ldw in bytes
-        if (M > 2 || (K & 31) || wscale) return -22;
-        GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, nullptr, w4scale, lds};
-        return gemv_profiled((double)N * (double)(K / 2 + K / 32), s, [&] { return launch_gemv(g, s); });
-    }
     // rows <= 8 stream the weights through the GEMV family (M >= 2 without a fused norm: skinny MFMA kernel); 9..16
     // rows too when the MFMA kernel covers the shape -- a 128-row GEMM tile would be > 87 % padding there
     const bool skinny = M > 8 && M <= 16 && !norm_w && (K & 31) == 0 && (ldw & 7) == 0 && (lda & 7) == 0 &&
@@ -100,17 +95,46 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     g.partial = splitk; g.partial_floats = splitk_floats;
     return launch_gemm(g, s);
 }
-// MXFP4 weights on the matrix cores: up to 16 rows stream them (gemv_fp4_thin.hip), 17 and more run the 4-bit GEMM (gemm_fp4.hip),
-// both under the GEMV profiler's accounting (the 4-bit bytes of the matrix, once).  No fused norm; a row count outside
-// [min_rows, max_rows] is refused, never forwarded to the other kernel.  tail_ok: K may end in a partial stage (K % 32 == 0; scale
-// rows at fp4_scale_stride(K)) -- the engine and emu_linear_fp4w_mfma_bf16; the two older entry points keep K % 256 == 0
-int linear_fp4_mfma(const bf16_t* A, const uint8_t* W4, const uint8_t* scales, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M,
-                    int N, int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, hipStream_t s, int min_rows, int max_rows,
-                    bool tail_ok) {
-    GemvArgs g{A, B(W4), nullptr, bias, res, C, M, N, K, lda, ldw, ldres, ldc, 0.f, epi, 0, nullptr, scales, lds};
-    if (!fp4_mfma_ok(g, min_rows, max_rows, tail_ok)) return -22;
-    return gemv_profiled((double)N * (double)(K / 2 + K / 32), s,
-                         [&] { return M <= 16 ? launch_gemv_fp4_thin(g, s, tail_ok) : launch_gemm_fp4(g, s, tail_ok); });
+// ---- The weight sets of one matrix, any of them null: bf16; fp8 (e4m3) bytes + one fp32 scale per output row; MXFP4 element bytes
+// [N, K/2] + E8M0 block scales [N, K/32] at a row stride of fp4_scale_stride(K) -- and the kernel that reads them
+struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
+                 const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr; };
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5 };   // (ABI: emu_llama_weight_kernel)
+// The one rule that picks a LLaMA projection's kernel, layers and head alike, from integers only: the modes as emu_llama_use_fp8 /
+// emu_llama_use_fp4 set them (never both), the call's rows, the shard's reduction widths.  1..2 rows: the weight streams with the
+// RMSNorm in front (gemv_fp4.hip, gemv.hip); 3..16: the MXFP4 matrix-core stream (gemv_fp4_thin.hip); 17 and more: the 4-bit GEMM
+// (gemm_fp4.hip), or W8A8 GEMMs on the block-scaled MFMA (twice the bf16 rate, BASELINE configs[4]; whole 128-element k tiles)
+WeightKernel weight_kernel(int fp8_mode, int fp4_mode, int rows, int H, int HD, int Fl) {
+    if (rows <= 2) return fp4_mode >= 1 ? WeightKernel::Fp4Rows : fp8_mode >= 1 ? WeightKernel::Fp8Rows : WeightKernel::Bf16;
+    if (rows <= 16) return fp4_mode >= 2 ? WeightKernel::Fp4Thin : WeightKernel::Bf16;
+    if (fp4_mode == 3) return WeightKernel::Fp4Gemm;
+    return fp8_mode == 2 && !(H & 127) && !(HD & 127) && !(Fl & 127) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
+}
+// out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
+// pointers, which come from w (ldw in elements of the set k reads).  The MXFP4 kernels run under the GEMV profiler, the 4-bit bytes of
+// the matrix once.  The row range follows from k, a row count outside it is refused: Fp4Rows 1..2 (fused norm allowed), Fp4Thin 1..16,
+// Fp4Gemm 17 and more (no fused norm; K >= 256, K % 32 == 0).  Fp8Gemm needs the caller's quantised rows (linear_q8): not served here.
+int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
+    if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows) {
+        const bool f8 = k == WeightKernel::Fp8Rows;
+        if (f8 ? !w.W8 || !w.s8 : !w.W) return -22;
+        return linear(g.x, f8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps, g.epi, s,
+                      f8 ? w.s8 : nullptr, splitk, splitk_floats);
+    }
+    if (k == WeightKernel::Fp8Gemm || !w.W4 || !w.s4) return -22;
+    g.W = B(w.W4); g.w4scale = w.s4;
+    const double bytes = (double)g.N * (double)(g.K / 2 + g.K / 32);
+    if (k == WeightKernel::Fp4Rows)
+        return g.M > 2 || (g.K & 31) ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv(g, s); });
+    const bool thin = k == WeightKernel::Fp4Thin;
+    if (!fp4_mfma_ok(g, thin ? 1 : 17, thin ? 16 : INT_MAX, true)) return -22;
+    return gemv_profiled(bytes, s, [&] { return thin ? launch_gemv_fp4_thin(g, s, true) : launch_gemm_fp4(g, s, true); });
+}
+// linear_w's launch block for a packed [N, K] matrix of the engines (rows of K elements: K bf16 / fp8 bytes, K / 2 MXFP4 bytes, scale
+// rows at fp4_scale_stride(K)), no bias; norm_w: the RMSNorm fused in front (eps), or null
+GemvArgs packed(WeightKernel k, const bf16_t* x, int ldx, const bf16_t* norm_w, float eps, const bf16_t* res, int ldres, bf16_t* out, int ldo, int M, int N, int K, int epi) {
+    const bool fp4 = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp4Thin || k == WeightKernel::Fp4Gemm;
+    return {x, nullptr, norm_w, nullptr, res, out, M, N, K, ldx, fp4 ? K / 2 : K, ldres, ldo, norm_w ? eps : 0.f, epi, 0, nullptr, nullptr, fp4_scale_stride(K)};
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
@@ -156,6 +180,9 @@ void emu_prof_end(hipStream_t s, const char* klass, int M, int N, int K, int tag
 extern "C" {
 
 int emu_version(void) { return 6; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
+int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local) {
+    return (int)weight_kernel(fp8_mode, fp4_mode, rows, hidden, heads_dim_local, ffn_local);
+}
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
 void emu_gemm_force_config(int cfg) { emu_gemm_force_config_set(cfg); }
@@ -329,30 +356,34 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
     if (!wscale) return -22;
     return linear(B(A), B(W8), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), wscale);
 }
+// the four MXFP4 entry points name their kernel (the caller's matrix as a weight record, its arguments as the launch block);
+// linear_w refuses a row count outside the kernel's range
+static int linear_fp4w(WeightKernel k, const void* A, const void* W4, const void* scales, const void* bias, const void* res, const void* norm_w,
+                       void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc, float eps, int epi, emu_stream_t s) {
+    if (!A || !W4 || !scales || !C) return -22;
+    return linear_w(k, {nullptr, nullptr, nullptr, U8(W4), U8(scales)},
+                    {B(A), nullptr, B(norm_w), B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, nullptr, nullptr, lds}, S(s));
+}
 int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc, float eps,
                          int epi, emu_stream_t s) {
-    if (!A || !W4 || !scales || !C || M < 1 || M > 2 || K < 32 || (K & 31)) return -22;
-    return linear(B(A), B(W4), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), nullptr, nullptr, 0,
-                  reinterpret_cast<const uint8_t*>(scales), lds);
-}
-int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
-                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
-    if (!A || !W4 || !scales || !C) return -22;
-    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, 16, false);
-}
-int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
-                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
-    if (!A || !W4 || !scales || !C) return -22;
-    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s), 17, INT_MAX, false);
+    if (M < 1 || K < 32) return -22;
+    return linear_fp4w(WeightKernel::Fp4Rows, A, W4, scales, bias, res, norm_w, C, M, N, K, lda, ldw, lds, ldres, ldc, eps, epi, s);
 }
 int emu_linear_fp4w_mfma_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
-    if (!A || !W4 || !scales || !C) return -22;
-    return linear_fp4_mfma(B(A), reinterpret_cast<const uint8_t*>(W4), reinterpret_cast<const uint8_t*>(scales), B(bias), B(res), B(C), M, N, K,
-                           lda, ldw, lds, ldres, ldc, epi, S(s), 1, INT_MAX, true);
+    return linear_fp4w(M <= 16 ? WeightKernel::Fp4Thin : WeightKernel::Fp4Gemm, A, W4, scales, bias, res, nullptr, C, M, N, K, lda, ldw, lds, ldres, ldc, 0.f, epi, s);
+}
+// the two older entry points keep K in whole stages (K % 256 == 0), refused here: the launchers pick the partial-stage (TAIL)
+// instantiation from K % 256 itself, never from tail_ok, which only widens the argument check -- so a K of whole stages launches
+// exactly what tail_ok = false launched
+int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
+    return K & 255 ? -22 : linear_fp4w(WeightKernel::Fp4Thin, A, W4, scales, bias, res, nullptr, C, M, N, K, lda, ldw, lds, ldres, ldc, 0.f, epi, s);
+}
+int emu_linear_fp4w_gemm_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
+    return K & 255 ? -22 : linear_fp4w(WeightKernel::Fp4Gemm, A, W4, scales, bias, res, nullptr, C, M, N, K, lda, ldw, lds, ldres, ldc, 0.f, epi, s);
 }
 int emu_quantize_mxfp4_rows(const void* w, int ldw, void* q, int ldq, void* scales, int lds, int N, int K, emu_stream_t s) {
     if (!w || !q || !scales) return -22;
@@ -512,31 +543,26 @@ int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, con
 struct emu_llama {
     emu_ctx* ctx;
     emu_llama_cfg cfg;
-    struct Layer { const bf16_t *wqkv, *wo, *wgu, *wdown, *ln1, *ln2; };
+    // one weight record per matrix (emu_llama_set_layer / _fp8 / _fp4 fill its three sets).  A layer without fp8 weights runs bf16
+    // under the fp8 prefill; emu_llama_use_fp4 checks that every layer and the head have the MXFP4 set.
+    struct Layer { Weights qkv, o, gu, down; const bf16_t *ln1 = nullptr, *ln2 = nullptr; };
     std::vector<Layer> layers;
-    // optional fp8 (e4m3) copies of the packed weights for the decode stream: bytes + one fp32 scale per output row
-    struct Layer8 { const uint8_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
-                    const float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sdown = nullptr; };
-    std::vector<Layer8> layers8;
-    const uint8_t* lm_head8 = nullptr;
-    const float* lm_scale8 = nullptr;
-    bool fp8_decode = false;
+    Weights head;                  // lm_head: the fp8 / MXFP4 copies cover the same rows (quantised from the shard)
+    bool fp8_decode = false;       // emu_llama_use_fp8(m, 1 | 2): 1..2 rows stream the fp8 set
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2): W8A8 GEMMs for prefill rows as well
-    // optional MXFP4 copies for the decode stream (emu_llama_use_fp4; exclusive with the fp8 stream): element bytes [N, K/2] + E8M0
-    // block scales [N, K/32] of the packed matrices, scale rows at a stride of fp4_scale_stride(K).  Prefill and steps of more than two rows keep the bf16 weights, unless fp4_wide
-    // (emu_llama_use_fp4(m, 2)) sends steps of 3..16 rows through the matrix-core stream (gemv_fp4_thin.hip) and fp4_all
-    // (emu_llama_use_fp4(m, 3)) the calls of 17 rows and more through the 4-bit GEMM (gemm_fp4.hip).  bf16_released
-    // (emu_llama_release_bf16; mode 3 only, which it pins): the layers' bf16 matrix pointers and lm_head are null.
-    struct Layer4 { const uint8_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr;
-                    const uint8_t *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sdown = nullptr; };
-    std::vector<Layer4> layers4;
-    const uint8_t* lm_head4 = nullptr;
-    const uint8_t* lm_scale4 = nullptr;
+    // emu_llama_use_fp4 (exclusive with the fp8 stream): 1..2 rows stream the MXFP4 set; fp4_wide (mode 2) steps of 3..16 rows too, on
+    // the matrix cores; fp4_all (mode 3) the calls of 17 rows and more run the 4-bit GEMM.  Every other row count keeps the bf16 weights.
+    // bf16_released (emu_llama_release_bf16; mode 3 only, which it pins): the records' bf16 pointers are null.
     bool fp4_decode = false;
     bool fp4_wide = false;
     bool fp4_all = false;
     bool bf16_released = false;
-    const bf16_t *final_norm = nullptr, *lm_head = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
+    // the kernel of a projection of `rows` rows, layers and head alike: the modes above through weight_kernel
+    WeightKernel kernel_for(int rows) const {
+        return weight_kernel(fp8_prefill ? 2 : fp8_decode, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
+                             cfg.heads_local * cfg.head_dim, cfg.ffn_local);
+    }
+    const bf16_t *final_norm = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
     // tensor parallelism: lm_head holds rows [head_row0, head_row0 + head_rows) of the vocabulary only (emu_llama_set_head_shard);
     // head_rows < 0: the whole matrix
     int head_row0 = 0, head_rows = -1;
@@ -643,16 +669,14 @@ struct LlamaPlan {
     LlamaPath path;
     // fuse_rope      the qkv GEMM's epilogue rotates q / k, appends k / v and writes V^T (demoted for the rest of the call on -95)
     // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
-    // fp8_rows       1..2 rows stream the fp8 weight set (decode)
-    // fp8_gemm       prefill rows run W8A8 GEMMs in the layers that have fp8 weights
-    // fp4_rows       1..2 rows stream the MXFP4 weight set (decode; emu_llama_use_fp4, never together with fp8_rows)
-    // fp4_thin       3..16 rows stream the MXFP4 weight set through the matrix cores (emu_llama_use_fp4(m, 2)); norms stay launches
-    // fp4_gemm       17 rows and more run the MXFP4 weight set through the 4-bit GEMM (emu_llama_use_fp4(m, 3)); norms, RoPE / KV
-    //                append and V^T stay launches: fuse_rope and fuse_norm are off and the call never takes TwoLane
+    // kernel         the weight set and kernel of the call's projections (weight_kernel).  Fp8Gemm: in the layers that have fp8
+    //                weights.  Fp4Thin: norms stay launches.  Fp4Gemm: norms, RoPE / KV append and V^T stay launches -- fuse_rope and
+    //                fuse_norm are off and the call never takes TwoLane
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
-    bool fuse_rope, fuse_norm, fp8_rows, fp8_gemm, fp4_rows, fp4_thin, fp4_gemm, norm_in_gemv, decode_tail, merge_o;
+    WeightKernel kernel;
+    bool fuse_rope, fuse_norm, norm_in_gemv, decode_tail, merge_o;
     // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
     // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
     DecodeLayersArgs dl; EngArgs eng;
@@ -667,8 +691,6 @@ struct RowWindow {
     std::function<int(bf16_t*, size_t)> allreduce;   // sums partial rows over the ranks, in the window's stream
 };
 using LaneHook = std::function<int()>;           // what a schedule issues between two launches of the layer body (events of the two lanes)
-struct ProjWeights { const bf16_t* W; const uint8_t* W8; const float* s8;      // bf16 weight; fp8 weight + per-row scale, or nulls;
-                     const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr; };   // MXFP4 elements + block scales, or nulls
 struct LlamaCall {
     emu_llama* m; emu_ctx* cx; LlamaWs ws; hipStream_t s;
     bf16_t* hA;                                  // the residual stream, [M, H]
@@ -692,28 +714,22 @@ struct LlamaCall {
         const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv;
         // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
         // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
-        p.fp4_gemm = m->fp4_all && M >= 17;
-        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && !p.fp4_gemm;
+        p.kernel = m->kernel_for(M);
+        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && p.kernel != WeightKernel::Fp4Gemm;
         // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
         // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
         // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
         // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
         // with B * beams > 16) keep the fused path they had before the promise became one-shot.
-        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && !p.fp4_gemm;
-        p.fp8_rows = m->fp8_decode && M <= 2;
-        // prefill with the fp8 weight set: activations are quantised per row ahead of every GEMM, the block-scaled MFMA
-        // runs at twice the bf16 rate (BASELINE configs[4]); needs whole 128-element k tiles
-        p.fp8_gemm = m->fp8_prefill && M > 16 && !(H & 127) && !(HD & 127) && !(Fl & 127);
-        p.fp4_rows = m->fp4_decode && M <= 2;
-        p.fp4_thin = m->fp4_wide && M >= 3 && M <= 16;
-        p.norm_in_gemv = p.fp8_rows || p.fp4_rows || M == 1;
+        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && p.kernel != WeightKernel::Fp4Gemm;
+        p.norm_in_gemv = p.kernel == WeightKernel::Fp8Rows || p.kernel == WeightKernel::Fp4Rows || M == 1;
         p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
         // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
         // itself, no combine launch (gemv_merge.hip).  Bit-identical and measured LEVEL with the two launches (3.15 vs 3.15-3.18 ms
         // per token of a TP = 8 shard, profiles/r05_tp_emulate_merged_o_proj.log): the merge is a dependent L2 trip inside the
         // projection, which is what the combine launch cost -- one launch less buys nothing here, like the in-kernel split merge
         // and the tail all-reduce before it
-        p.merge_o = T == 1 && M == 1 && !p.fp8_rows && !p.fp4_rows && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
+        p.merge_o = T == 1 && M == 1 && p.kernel == WeightKernel::Bf16 && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
                     (emu_gemm_tune_get() & (1 << 19)) != 0;
 
         const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && !m->fp4_decode && own_kv && some_layers;
@@ -754,28 +770,24 @@ struct LlamaCall {
         }
         // ---- long prompt under tensor parallelism: two row halves, every all-reduce behind the other half's GEMMs (needs the slot-order
         // promise: the rows of the one batch element are the whole context in order, so the first half never reads the second's keys)
-        if (!p.fp4_gemm && tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
+        if (p.kernel != WeightKernel::Fp4Gemm && tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
             p.path = LlamaPath::TwoLane;
     }
 
-    // One projection of a layer, C = epi(A W^T [+ res]): qkv, o_proj, gate/up and down all come through here.  pw holds the fp8 weight
-    // only where the plan's fp8 form applies to the layer.  gain_in: the RMSNorm in front, fused into a one-row weight stream;
-    // gain_out: w.xn = RMSNorm(C) * gain_out behind the K-slice sums.
-    int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const ProjWeights& pw, const bf16_t* res, const bf16_t* gain_in,
+    // One projection of a layer, C = epi(A W^T [+ res]): qkv, o_proj, gate/up and down all come through here, from the matrix's record
+    // by the plan's kernel (every window of a call has the row range the plan chose it for: pick_path).  gain_in: the RMSNorm in front,
+    // fused into a one-row weight stream; gain_out: w.xn = RMSNorm(C) * gain_out behind the K-slice sums.
+    int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const Weights& W, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
-        if (pw.W4 && (plan.fp4_gemm || plan.fp4_thin))             // (the plan's row range: 17 and more, or up to 16)
-            return linear_fp4_mfma(A, pw.W4, pw.s4, nullptr, res, C, rows, N, K, K, K / 2, fp4_scale_stride(K), ldres, ldc, epi, s,
-                                   plan.fp4_gemm ? 17 : 1, plan.fp4_gemm ? INT_MAX : 16, true);
-        if (pw.W4 && plan.fp4_rows)
-            return linear(A, B(pw.W4), nullptr, res, gain_in, C, rows, N, K, K, K / 2, ldres, ldc, gain_in ? eps : 0.f, epi, s, nullptr, nullptr, 0,
-                          pw.s4, fp4_scale_stride(K));
-        if (pw.W8 && plan.fp8_rows) return linear(A, B(pw.W8), nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, gain_in ? eps : 0.f, epi, s, pw.s8);
-        if (!pw.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
-        if (pw.W8) return linear_q8(w, A, K, pw.W8, pw.s8, res, C, rows, N, K, ldres, ldc, epi, s);
-        if (gain_in) return linear(A, pw.W, nullptr, res, gain_in, C, rows, N, K, K, K, ldres, ldc, eps, epi, s);
-        if (gain_out) return linear_then_rmsnorm(w, A, pw.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
-        return linear(A, pw.W, nullptr, res, nullptr, C, rows, N, K, K, K, ldres, ldc, 0.f, epi, s, nullptr, w.splitk, w.splitk_floats);
+        WeightKernel k = plan.kernel;
+        if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Gemm) {
+            if (!W.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
+            if (k == WeightKernel::Fp8Gemm && W.W8) return linear_q8(w, A, K, W.W8, W.s8, res, C, rows, N, K, ldres, ldc, epi, s);
+            if (gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
+            k = WeightKernel::Bf16;                      // (Fp8Gemm: a layer without fp8 weights runs bf16)
+        }
+        return linear_w(k, W, packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi), s, w.splitk, w.splitk_floats);
     }
 
     RowWindow window(int r0, int T, int kend, hipStream_t s, bf16_t* vt, float* splitk) {
@@ -784,14 +796,6 @@ struct LlamaCall {
         w.vt = vt; w.splitk = splitk;
         return RowWindow{r0, T, kend, s, w, hA + (size_t)r0 * H, pos + r0, slot + r0, nullptr};
     }
-    // the fp8 weights of layer l where the plan's fp8 form applies to it (emu_llama_set_layer_fp8 sets all of a layer's or none), else nulls
-    emu_llama::Layer8 layer_fp8(int l) {
-        return plan.fp8_rows || (plan.fp8_gemm && m->layers8[l].wqkv) ? m->layers8[l] : emu_llama::Layer8{};
-    }
-
-    // the MXFP4 weights of layer l where the plan streams them (emu_llama_use_fp4 checked that every layer has them), else nulls
-    emu_llama::Layer4 layer_fp4(int l) { return plan.fp4_rows || plan.fp4_thin || plan.fp4_gemm ? m->layers4[l] : emu_llama::Layer4{}; }
-
     // ---- The decoder layer, written once, in three steps that are cut where the schedules hook in:
     //     layer_kv      RMSNorm, [after_norm], qkv projection (+ RoPE / KV append / V^T in its epilogue, else the rope_kv launch): the
     //                   window's K / V are cached
@@ -800,11 +804,9 @@ struct LlamaCall {
     int layer_kv(const RowWindow& win, int l, const LaneHook& after_norm = nullptr) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        const emu_llama::Layer8 L8 = layer_fp8(l);
-        if (plan.fp8_rows && !L8.wqkv) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
-        const emu_llama::Layer4 L4 = layer_fp4(l);
+        if (plan.kernel == WeightKernel::Fp8Rows && !L.qkv.W8) return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
         // after emu_llama_release_bf16 the 4-bit set is the layer's weights (mode 3 is pinned: every row count has a 4-bit path)
-        if (m->bf16_released ? !L4.wqkv || !L.ln1 : !L.wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+        if (m->bf16_released ? !L.qkv.W4 || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
@@ -814,7 +816,7 @@ struct LlamaCall {
         if (after_norm) TRY(cx, after_norm());
         int st = -95;
         if (plan.fuse_rope) {
-            GemmArgs g{w.xn, L.wqkv, nullptr, nullptr, w.qkv, rows, 3 * HD, H, H, H, 0, 3 * HD, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
+            GemmArgs g{w.xn, L.qkv.W, nullptr, nullptr, w.qkv, rows, 3 * HD, H, H, H, 0, 3 * HD, EPI_NONE, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
             g.partial = w.splitk; g.partial_floats = w.splitk_floats;
             g.rope_cos = m->cos; g.rope_sin = m->sin; g.rope_pos = win.pos; g.rope_slot = win.slot; g.rope_kc = kc; g.rope_vc = vc;
             g.rope_hl = Hl; g.rope_smax = m->s_max;
@@ -824,7 +826,7 @@ struct LlamaCall {
             if (st == -95) plan.fuse_rope = false;       // the 256x256 tile does not take this shape unsliced: unfused sequence from here on
         }
         if (st == -95)
-            TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, {L.wqkv, L8.wqkv, L8.sqkv, L4.wqkv, L4.sqkv}, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
+            TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, L.qkv, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
                             nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE));
         if (T == 1) return 0;                            // single-token step: the attention launch rotates and appends
         if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
@@ -837,8 +839,6 @@ struct LlamaCall {
     int layer_attend(const RowWindow& win, int l, const LaneHook& after_vt = nullptr) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        const emu_llama::Layer8 L8 = layer_fp8(l);
-        const emu_llama::Layer4 L4 = layer_fp4(l);
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (T == 1) {
@@ -861,25 +861,23 @@ struct LlamaCall {
             TRY(cx, launch_flash_attn(fa, win.s));
         }
         if (plan.merge_o) {
-            GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.wo, win.x, w.hB, H, HD, HD, epi_res, nullptr};
+            GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.o.W, win.x, w.hB, H, HD, HD, epi_res, nullptr};
             TRY(cx, gemv_merge_profiled(g, win.s));
         } else
-            TRY(cx, project(w, win.s, w.attn, {L.wo, L8.wo, L8.so, L4.wo, L4.so}, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
+            TRY(cx, project(w, win.s, w.attn, L.o, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
         return win.allreduce(w.hB, (size_t)rows * H);
     }
 
     int layer_mlp(const RowWindow& win, int l) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        const emu_llama::Layer8 L8 = layer_fp8(l);
-        const emu_llama::Layer4 L4 = layer_fp4(l);
         const int rows = Bn * win.T;
         if (!plan.norm_in_gemv && !plan.fuse_norm) TRY(cx, launch_rmsnorm(w.hB, L.ln2, w.xn, rows, H, H, H, eps, win.s));
-        TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, {L.wgu, L8.wgu, L8.sgu, L4.wgu, L4.sgu}, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
+        TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, L.gu, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
                         w.act, rows, 2 * Fl, H, EPI_SWIGLU));
         // (fuse_norm: the RMSNorm behind down_proj is the NEXT layer's input norm, which then finds its rows in w.xn)
         const bf16_t* next_ln1 = plan.fuse_norm && l + 1 < l_end ? m->layers[l + 1].ln1 : nullptr;
-        TRY(cx, project(w, win.s, w.act, {L.wdown, L8.wdown, L8.sdown, L4.wdown, L4.sdown}, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
+        TRY(cx, project(w, win.s, w.act, L.down, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
         if (next_ln1) xn_ready = true;
         return win.allreduce(win.x, (size_t)rows * H);
     }
@@ -983,12 +981,12 @@ struct LlamaCall {
         e.err = m->dl_err; e.ncu = cx->ncu;
         engine_tool_switches(e);
         for (int l = m->l0; l < l_end; ++l)
-            if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+            if (!m->layers[l].qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         if (hipMemsetAsync(m->eng_gran, 0, m->eng_gran_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
         const size_t gH = align_up((size_t)H * 4), gF = align_up((size_t)Fl * 4);
         const bool res_here = epi_res == EPI_RESID;           // rank 0 adds the residuals (they enter the all-reduce once)
         // the first layer's qkv projection is a launch of its own
-        TRY(cx, project(w, s, hA, {m->layers[m->l0].wqkv, nullptr, nullptr}, nullptr, m->layers[m->l0].ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
+        TRY(cx, project(w, s, hA, m->layers[m->l0].qkv, nullptr, m->layers[m->l0].ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
         for (int l = m->l0; l < l_end; ++l) {
             const emu_llama::Layer& L = m->layers[l];
             bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
@@ -1001,20 +999,20 @@ struct LlamaCall {
             uint32_t* g_ha = reinterpret_cast<uint32_t*>(gl + gH + gF);
             int k = 0;
             EngOp& o0 = e.op[k++] = EngOp{};                          // o_proj: partial sums of the post-attention stream
-            o0.W = L.wo; o0.N = H; o0.K = HD; o0.epi = res_here ? EPI_RESID : EPI_NONE; o0.res = hA; o0.res_src = 0;
+            o0.W = L.o.W; o0.N = H; o0.K = HD; o0.epi = res_here ? EPI_RESID : EPI_NONE; o0.res = hA; o0.res_src = 0;
             o0.vw = emu_gemv_partition(H, HD, false, epi_res); o0.x_src = 0; o0.xg = w.attn; o0.out_dst = 2; o0.ar_k = 0;
             EngOp& o1 = e.op[k++] = EngOp{};                          // all-reduce -> RMSNorm -> gate / up -> SwiGLU
-            o1.W = L.wgu; o1.N = 2 * Fl; o1.K = H; o1.gain = L.ln2; o1.eps = eps; o1.epi = EPI_SWIGLU;
+            o1.W = L.gu.W; o1.N = 2 * Fl; o1.K = H; o1.gain = L.ln2; o1.eps = eps; o1.epi = EPI_SWIGLU;
             o1.vw = emu_gemv_partition(2 * Fl, H, true, EPI_SWIGLU); o1.x_src = 2; o1.xgran = g_hb; o1.ar_k = 0; o1.keep_raw = 1;
             o1.out_dst = 1; o1.ogran = g_act;
             EngOp& o2 = e.op[k++] = EngOp{};                          // down: partial sums of the layer output (+ the summed stream on rank 0)
-            o2.W = L.wdown; o2.N = H; o2.K = Fl; o2.epi = res_here ? EPI_RESID : EPI_NONE; o2.res_src = 1;
+            o2.W = L.down.W; o2.N = H; o2.K = Fl; o2.epi = res_here ? EPI_RESID : EPI_NONE; o2.res_src = 1;
             o2.vw = emu_gemv_partition(H, Fl, false, epi_res); o2.x_src = 1; o2.xgran = g_act;
             if (!last) {
                 o2.out_dst = 2; o2.ar_k = 1;
                 EngOp& o3 = e.op[k++] = EngOp{};                      // all-reduce -> RMSNorm -> the NEXT layer's qkv projection
                 const emu_llama::Layer& Ln = m->layers[l + 1];
-                o3.W = Ln.wqkv; o3.N = 3 * HD; o3.K = H; o3.gain = Ln.ln1; o3.eps = eps; o3.epi = EPI_NONE;
+                o3.W = Ln.qkv.W; o3.N = 3 * HD; o3.K = H; o3.gain = Ln.ln1; o3.eps = eps; o3.epi = EPI_NONE;
                 o3.vw = emu_gemv_partition(3 * HD, H, true, EPI_NONE); o3.x_src = 2; o3.xgran = g_ha; o3.ar_k = 1; o3.sum_out = hA;
                 o3.out_dst = 0; o3.out = w.qkv;
                 e.n_ar = 2;
@@ -1052,14 +1050,14 @@ struct LlamaCall {
             if (cs != hipStreamCaptureStatusNone)
                 return fail(cx, -16, "emu_llama_forward: the fused decode path needs one eager step before a capture (weight table upload)");
             std::vector<DecodeLayerPtrs> t(m->layers.size());
-            for (size_t l = 0; l < t.size(); ++l) { const emu_llama::Layer& L = m->layers[l]; t[l] = {L.wqkv, L.wo, L.wgu, L.wdown, L.ln1, L.ln2}; }
+            for (size_t l = 0; l < t.size(); ++l) { const emu_llama::Layer& L = m->layers[l]; t[l] = {L.qkv.W, L.o.W, L.gu.W, L.down.W, L.ln1, L.ln2}; }
             if (hipStreamSynchronize(s) != hipSuccess ||        // fused launches still in flight on s read the table
                 hipMemcpy(m->dl_table, t.data(), sizeof(DecodeLayerPtrs) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
                 return fail(cx, -5, "emu_llama_forward: weight table upload");
             m->dl_dirty = false;
         }
         for (int l = m->l0; l < l_end; ++l)
-            if (!m->layers[l].wqkv) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+            if (!m->layers[l].qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         if (hipMemsetAsync(m->dl_cnt, 0, m->dl_cnt_bytes, s) != hipSuccess) return fail(cx, -5, "emu_llama_forward: hipMemsetAsync");
         if (plan.path == LlamaPath::FusedTailAllReduce) {
             // mode 3: the weight streams with an RMSNorm in front stay stand-alone launches; the attention (split merge by the
@@ -1069,12 +1067,12 @@ struct LlamaCall {
             for (int l = m->l0; l < l_end; ++l) {
                 const emu_llama::Layer& L = m->layers[l];
                 d.layer0 = l; d.nlayers = 1;
-                TRY(cx, project(w, s, hA, {L.wqkv, nullptr, nullptr}, nullptr, L.ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
+                TRY(cx, project(w, s, hA, L.qkv, nullptr, L.ln1, nullptr, w.qkv, 1, 3 * HD, H, EPI_NONE));
                 DecodeLayersArgs a1 = d; a1.tp_n = 0; a1.role0 = 1; a1.role1 = 2;
                 TRY(cx, launch_decode_layers(a1, s));
                 d.role0 = 2; d.role1 = 3;
                 TRY(cx, launch_decode_layers(d, s));
-                TRY(cx, project(w, s, w.hB, {L.wgu, nullptr, nullptr}, nullptr, L.ln2, nullptr, w.act, 1, 2 * Fl, H, EPI_SWIGLU));
+                TRY(cx, project(w, s, w.hB, L.gu, nullptr, L.ln2, nullptr, w.act, 1, 2 * Fl, H, EPI_SWIGLU));
                 d.role0 = 4; d.role1 = 5;
                 TRY(cx, launch_decode_layers(d, s));
             }
@@ -1116,7 +1114,6 @@ int emu_llama_create(emu_ctx* ctx, const emu_llama_cfg* cfg, emu_llama** out) {
         m->arrive = nullptr;                           // the two-launch form needs none
     }
     m->layers.resize(cfg->layers);
-    memset(m->layers.data(), 0, sizeof(emu_llama::Layer) * cfg->layers);
     *out = m;
     return 0;
 }
@@ -1172,7 +1169,8 @@ int emu_llama_decode_fused_stats(emu_llama* m, unsigned int* giveups, long* forw
 int emu_llama_set_layer(emu_llama* m, int layer, const void* wqkv, const void* wo, const void* wgu, const void* wdown,
                         const void* ln1, const void* ln2) {
     if (!m || layer < 0 || layer >= m->cfg.layers) return -22;
-    m->layers[layer] = {B(wqkv), B(wo), B(wgu), B(wdown), B(ln1), B(ln2)};
+    emu_llama::Layer& L = m->layers[layer];
+    L.qkv.W = B(wqkv); L.o.W = B(wo); L.gu.W = B(wgu); L.down.W = B(wdown); L.ln1 = B(ln1); L.ln2 = B(ln2);
     m->dl_dirty = true;
     return 0;
 }
@@ -1183,28 +1181,28 @@ int emu_llama_set_layer_fp8(emu_llama* m, int layer, const void* wqkv8, const fl
     const emu_llama_cfg& c = m->cfg;
     if ((c.hidden & 15) || ((c.heads_local * c.head_dim) & 15) || (c.ffn_local & 15))
         return fail(m->ctx, -22, "emu_llama_set_layer_fp8: reduction widths must be multiples of 16");
-    if (m->layers8.size() != (size_t)c.layers) m->layers8.assign(c.layers, emu_llama::Layer8{});
-    auto U = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
-    m->layers8[layer] = {U(wqkv8), U(wo8), U(wgu8), U(wdown8), sqkv, so, sgu, sdown};
+    emu_llama::Layer& L = m->layers[layer];
+    L.qkv.W8 = U8(wqkv8); L.o.W8 = U8(wo8); L.gu.W8 = U8(wgu8); L.down.W8 = U8(wdown8);
+    L.qkv.s8 = sqkv; L.o.s8 = so; L.gu.s8 = sgu; L.down.s8 = sdown;
     return 0;
 }
 int emu_llama_set_head_fp8(emu_llama* m, const void* lm_head8, const float* lm_scale) {
     if (!m || !lm_head8 || !lm_scale) return -22;
-    m->lm_head8 = reinterpret_cast<const uint8_t*>(lm_head8); m->lm_scale8 = lm_scale;
+    m->head.W8 = U8(lm_head8); m->head.s8 = lm_scale;
     return 0;
 }
 int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const void* sqkv, const void* wo4, const void* so,
                             const void* wgu4, const void* sgu, const void* wdown4, const void* sdown) {
     if (!m || layer < 0 || layer >= m->cfg.layers) return -22;
     if (!wqkv4 || !sqkv || !wo4 || !so || !wgu4 || !sgu || !wdown4 || !sdown) return -22;
-    if (m->layers4.size() != (size_t)m->cfg.layers) m->layers4.assign(m->cfg.layers, emu_llama::Layer4{});
-    auto U = [](const void* p) { return reinterpret_cast<const uint8_t*>(p); };
-    m->layers4[layer] = {U(wqkv4), U(wo4), U(wgu4), U(wdown4), U(sqkv), U(so), U(sgu), U(sdown)};
+    emu_llama::Layer& L = m->layers[layer];
+    L.qkv.W4 = U8(wqkv4); L.o.W4 = U8(wo4); L.gu.W4 = U8(wgu4); L.down.W4 = U8(wdown4);
+    L.qkv.s4 = U8(sqkv); L.o.s4 = U8(so); L.gu.s4 = U8(sgu); L.down.s4 = U8(sdown);
     return 0;
 }
 int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales) {
     if (!m || !lm_head4 || !lm_scales) return -22;
-    m->lm_head4 = reinterpret_cast<const uint8_t*>(lm_head4); m->lm_scale4 = reinterpret_cast<const uint8_t*>(lm_scales);
+    m->head.W4 = U8(lm_head4); m->head.s4 = U8(lm_scales);
     return 0;
 }
 int emu_llama_use_fp4(emu_llama* m, int enable) {
@@ -1218,10 +1216,8 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
             return fail(m->ctx, -22, "emu_llama_use_fp4: the fp8 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp8(m, 0) first)");
         if ((c.hidden & 31) || ((c.heads_local * c.head_dim) & 31) || (c.ffn_local & 31))
             return fail(m->ctx, -22, "emu_llama_use_fp4: reduction widths (hidden, heads_local * head_dim, ffn_local) must be multiples of 32");
-        if (m->layers4.size() != (size_t)c.layers || !m->lm_head4)
+        if (!m->head.W4 || std::any_of(m->layers.begin(), m->layers.end(), [](const emu_llama::Layer& l) { return !l.qkv.W4; }))
             return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
-        for (const auto& l : m->layers4)
-            if (!l.wqkv) return fail(m->ctx, -22, "emu_llama_use_fp4: fp4 weights not set (every layer and the head)");
         if (enable >= 2 && (c.hidden < 256 || c.heads_local * c.head_dim < 256 || c.ffn_local < 256))
             return fail(m->ctx, -22, "emu_llama_use_fp4: modes 2 and 3 (steps of 3 rows and more) need reduction widths (hidden, heads_local * head_dim, ffn_local) of at least 256 that are multiples of 32 (they need not be multiples of 256: the last K stage may be partial)");
     }
@@ -1234,8 +1230,8 @@ int emu_llama_release_bf16(emu_llama* m) {
     if (!m) return -22;
     if (!m->fp4_all) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
     if (m->decode_fused) return fail(m->ctx, -22, "emu_llama_release_bf16: the fused decode modes read the bf16 weights (emu_llama_set_decode_fused(m, 0, 0) first)");
-    for (auto& l : m->layers) l.wqkv = l.wo = l.wgu = l.wdown = nullptr;
-    m->lm_head = nullptr;
+    for (auto& l : m->layers) l.qkv.W = l.o.W = l.gu.W = l.down.W = nullptr;
+    m->head.W = nullptr;
     m->dl_dirty = true;
     m->bf16_released = true;
     return 0;
@@ -1276,7 +1272,8 @@ int emu_llama_use_fp8(emu_llama* m, int enable) {
         return fail(m->ctx, -22, "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
     if (enable && m->fp4_decode)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp4(m, 0) first)");
-    if (enable && m->layers8.size() != (size_t)m->cfg.layers)
+    // (emu_llama_set_layer_fp8 was never called: it sets all of a layer's or refuses, and a model has at least one layer)
+    if (enable && std::none_of(m->layers.begin(), m->layers.end(), [](const emu_llama::Layer& l) { return l.qkv.W8; }))
         return fail(m->ctx, -22, "emu_llama_use_fp8: fp8 layer weights not set");
     m->fp8_decode = enable != 0;
     m->fp8_prefill = enable == 2;
@@ -1285,7 +1282,7 @@ int emu_llama_use_fp8(emu_llama* m, int enable) {
 int emu_llama_set_head(emu_llama* m, const void* final_norm, const void* lm_head, const void* embed, const void* rope_cos,
                        const void* rope_sin) {
     if (!m) return -22;
-    m->final_norm = B(final_norm); m->lm_head = B(lm_head); m->embed = B(embed); m->cos = B(rope_cos); m->sin = B(rope_sin);
+    m->final_norm = B(final_norm); m->head.W = B(lm_head); m->embed = B(embed); m->cos = B(rope_cos); m->sin = B(rope_sin);
     return 0;
 }
 int emu_llama_set_head_shard(emu_llama* m, int row0, int rows) {
@@ -1396,37 +1393,32 @@ int emu_llama_final_norm(emu_llama* m, const void* hidden, void* out, int rows, 
                           m->cfg.rms_eps, S(s));
 }
 
-// final RMSNorm + rows of the head (N of them, from the engine's head pointers) on M hidden rows -> out: the one place that picks the
-// head's kernel.  The few-row streams fuse the norm; every other path runs the norm launch into the workspace first.
+// final RMSNorm + rows of the head (N of them, from the engine's head record) on M hidden rows -> out.  The kernel is the layers'
+// (emu_llama::kernel_for) but for the head's own facts: it has no W8A8 GEMM and its fp8 copy is optional (both: bf16), and the 3..16-row
+// MXFP4 stream needs the workspace for the normalised rows (too small: bf16, while there are bf16 weights).  The few-row streams fuse
+// the norm -- bf16 also up to 8 rows when the workspace is too small; every other path runs the norm launch into the workspace first.
 static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t* out, int N, int ld, bf16_t* ws, size_t ws_bytes,
                       hipStream_t s) {
     const emu_llama_cfg& c = m->cfg;
     const int H = c.hidden;
     const bool ws_fits = ws_bytes >= (size_t)M * H * 2;
-    const bool thin = m->fp4_wide && M >= 3 && M <= 16 && (ws_fits || m->bf16_released), gemm = m->fp4_all && M >= 17;
-    if (m->fp4_decode && M <= 2)                                  // the MXFP4 copy covers the same rows (quantised from the shard)
-        return linear(hidden, B(m->lm_head4), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H / 2, 0, ld, c.rms_eps, EPI_NONE, s,
-                      nullptr, nullptr, 0, m->lm_scale4, fp4_scale_stride(H));
-    if (!thin && !gemm) {
-        if (m->fp8_decode && M <= 2 && m->lm_head8)               // the e4m3 copy covers the same rows (quantised from the shard)
-            return linear(hidden, B(m->lm_head8), nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H, 0, ld, c.rms_eps, EPI_NONE, s,
-                          m->lm_scale8);
-        if (M == 1 || (M <= 8 && !ws_fits))
-            return linear(hidden, m->lm_head, nullptr, nullptr, m->final_norm, out, M, N, H, ldh, H, 0, ld, c.rms_eps, EPI_NONE, s);
+    WeightKernel k = m->kernel_for(M);
+    if (k == WeightKernel::Fp8Gemm || (k == WeightKernel::Fp8Rows && !m->head.W8) ||
+        (k == WeightKernel::Fp4Thin && !ws_fits && !m->bf16_released)) k = WeightKernel::Bf16;
+    const bool fused = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp8Rows || (k == WeightKernel::Bf16 && (M == 1 || (M <= 8 && !ws_fits)));
+    if (!fused) {
+        if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
+        TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
     }
-    if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
-    TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
-    if (thin || gemm)
-        return linear_fp4_mfma(ws, m->lm_head4, m->lm_scale4, nullptr, nullptr, out, M, N, H, H, H / 2, fp4_scale_stride(H), 0, ld, EPI_NONE, s,
-                               gemm ? 17 : 1, gemm ? INT_MAX : 16, true);
-    return linear(ws, m->lm_head, nullptr, nullptr, nullptr, out, M, N, H, H, H, 0, ld, 0.f, EPI_NONE, s);
+    return linear_w(k, m->head, packed(k, fused ? hidden : ws, fused ? ldh : H, fused ? m->final_norm : nullptr, c.rms_eps, nullptr, 0, out, ld,
+                                       M, N, H, EPI_NONE), s);
 }
 
 int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* logits, int ld, void* workspace,
                      size_t ws_bytes, emu_stream_t s) {
     if (!m || !m->final_norm) return -22;
     // after emu_llama_release_bf16 the 4-bit head is the head (mode 3 is pinned: every row count has a 4-bit path in llama_head)
-    if (m->bf16_released ? !m->fp4_all || !m->lm_head4 : !m->lm_head) return -22;
+    if (m->bf16_released ? !m->fp4_all || !m->head.W4 : !m->head.W) return -22;
     const emu_llama_cfg& c = m->cfg;
     if (m->head_rows < 0) return llama_head(m, B(hidden), ldh, M, B(logits), c.vocab, ld, B(workspace), ws_bytes, S(s));
     // vocabulary-sharded head (tensor parallelism): this rank streams its rows of lm_head only (4035 of 32 274 at TP = 8:

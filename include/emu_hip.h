@@ -404,6 +404,12 @@ int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const vo
 int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales);
 int emu_llama_use_fp4(emu_llama* m, int enable);
 int emu_llama_release_bf16(emu_llama* m);
+/* CPU test hook (tests/test_llama_weight_kernel.py): the one rule by which emu_llama_forward and emu_llama_logits pick a projection's
+ * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..2 / fp4_mode 0..3 as emu_llama_use_fp8 /
+ * emu_llama_use_fp4 take them (never both non-zero), rows = B*T of the call, the shard's hidden, heads_local*head_dim and ffn_local.
+ * Returns 0 bf16, 1 the fp8 stream (1..2 rows), 2 W8A8 GEMMs (17 rows and more; in the layers that have fp8 weights), 3 the MXFP4
+ * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more).  The head runs 2 as bf16. */
+int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local);
 /* Vocabulary-sharded lm_head under tensor parallelism (the reference's lm_head is lm.lm_head of LlamaForCausalLM reached
  * from Emu2/emu/emu.py:213-229): the lm_head pointer of emu_llama_set_head holds rows [row0, row0 + rows) of the vocabulary only;
  * emu_llama_logits fills this rank's columns of the caller's [M, vocab] rows, zeroes the others and all-reduces the rows, so every

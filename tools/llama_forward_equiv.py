@@ -1,12 +1,16 @@
-"""Bit-for-bit check of emu_llama_forward between two builds of libemu_hip.so: seeded cases over every schedule of the forward
-(per-layer launches for decode / prefill / left-padded batch / beam-shaped steps / fp8, decode tail and merged o_proj, the fused
-decode modes 1-4 on the shard-emulation engines, the two-lane tensor-parallel prefill over p2p and 1-rank RCCL).  Per case it
-writes the sha256 of the residual stream forward returned and of the K and V cache it wrote, plus the path counters, as JSON:
+"""Bit-for-bit check of emu_llama_forward and emu_llama_logits between two builds of libemu_hip.so: seeded cases over every
+schedule of the forward (per-layer launches for decode / prefill / left-padded batch / beam-shaped steps / fp8, decode tail and
+merged o_proj, the MXFP4 modes 1-3 at every row range and after release_bf16, the fused decode modes 1-4 on the shard-emulation
+engines, the two-lane tensor-parallel prefill over p2p and 1-rank RCCL) and every kernel of the head (whole, with the workspace too
+small, vocabulary-sharded).  Per case it writes the sha256 of the residual stream forward returned and of the K and V cache it wrote,
+of the logits where the case takes them, plus the path counters (the weight-stream profiler's bytes and launches in the fp4 group),
+as JSON:
 
-    python tools/llama_forward_equiv.py new.json [main|merge|fused|lanes ...]
+    python tools/llama_forward_equiv.py new.json [main|merge|fp4|fused|lanes ...]
     EMU_HIP_TOOLS=1 EMU_HIP_LIB=/path/to/other/libemu_hip.so python tools/llama_forward_equiv.py other.json
 
-Equal files = equal bits in every case (profiles/llama_forward_refactor_equivalence.md)."""
+Equal files = equal bits in every case (profiles/llama_forward_refactor_equivalence.md, profiles/weight_path_refactor_equivalence.md)."""
+import ctypes as C
 import hashlib
 import json
 import os
@@ -78,6 +82,54 @@ def rec(name, hidden, eng, extra=None, kv=None):
     json.dump(res, open(out_path, "w"), indent=1)
 
 
+def logits_small_ws(eng, rows):
+    """emu_llama_logits with no workspace at all: up to 8 rows the head falls back to the bf16 stream with the norm fused."""
+    from emu_amd import ops
+    from emu_amd._lib import check, lib
+    out = torch.empty(rows.shape[0], eng.vocab, device=eng.device, dtype=BF16)
+    check(lib().emu_llama_logits(eng.handle, rows.data_ptr(), rows.stride(0), rows.shape[0], out.data_ptr(), out.stride(0), None, 0,
+                                 ops.stream(eng.device)), "emu_llama_logits", eng.ctx.handle)
+    return out
+
+
+def profiled(fn):
+    """fn() under the weight-stream profiler: (fn's result, {"stream_bytes", "stream_launches"})."""
+    from emu_amd._lib import check, lib
+    check(lib().emu_profile_gemv(1), "emu_profile_gemv")
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        ms, wb, nl = C.c_double(), C.c_double(), C.c_long()
+        check(lib().emu_profile_gemv_read(C.byref(ms), C.byref(wb), C.byref(nl)), "emu_profile_gemv_read")
+    finally:
+        check(lib().emu_profile_gemv(0), "emu_profile_gemv")
+    return out, {"stream_bytes": wb.value, "stream_launches": nl.value}
+
+
+def step_rows(eng, rows, S, seed, steps=2):
+    """a prefill of `rows` prompts of S rows, then `steps` single-token steps of `rows` rows: (every step's residual stream, the
+    logits of the last step's rows, the profiler's counters over the steps and the logits call)."""
+    dev, H = eng.device, eng.cfg.hidden_size
+    eng.release_kv()
+    eng.prefill(rand(rows, S, H, seed=seed), torch.ones(rows, S, dtype=torch.long), eng.kv_capacity(S + 8))
+
+    def run():
+        outs = []
+        for step in range(steps):
+            pos = torch.full((rows,), S + step, device=dev, dtype=torch.int32)
+            hx = rand(rows, H, seed=seed + 1 + step)
+            outs.append(eng.forward(hx, rows, 1, pos, pos.clone(), torch.zeros(rows, device=dev, dtype=torch.int32), ctx=S + step + 1).clone())
+        return torch.stack(outs), eng.logits(outs[-1])
+    (hs, lg), counters = profiled(run)
+    return hs, lg, counters
+
+
+def rec_logits(name, logits):
+    res[name] = {"logits": h(logits)}
+    print(name, res[name], flush=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+
+
 def want(n):
     return not only or n in only
 
@@ -88,7 +140,7 @@ def rand(*shape, seed):
 
 
 def main():
-    from emu_amd._lib import lib
+    from emu_amd._lib import check, lib
     from emu_amd.conf.emu_conf import LlamaCfg
     dev = torch.device("cuda", 0)
     with torch.no_grad():
@@ -98,7 +150,7 @@ def main():
             H = cfg.hidden_size
             # (a) one-row decode steps
             ids, hs = decode_run(eng, 0, 380, 4)
-            rec("a_decode_1row", hs, eng, {"ids": h(ids)})
+            rec("a_decode_1row", hs, eng, {"ids": h(ids), "logits": h(eng.logits(hs[-1]))})
             # (b) B = 1 prefill, S = 770, with the promise; (c) without
             x = rand(1, 770, H, seed=11)
             m1 = torch.ones(1, 770, dtype=torch.long)
@@ -132,7 +184,10 @@ def main():
                     ks = torch.zeros(rows, device=dev, dtype=torch.int32)
                     outs.append(eng.forward(hx, rows, 1, pos, slot, ks, ctx=S + step + 1).clone())
                 # (the beam cache is allocated without a zero fill: compare the slots the steps wrote)
-                rec(f"e_beam_rows_{rows}", torch.stack(outs), eng, kv=(eng.kcache[:, :, :, S:S + 3], eng.vcache[:, :, :, S:S + 3]))
+                extra = {"logits": h(eng.logits(outs[-1]))}
+                if rows == 5:
+                    extra["logits_small_ws"] = h(logits_small_ws(eng, outs[-1]))
+                rec(f"e_beam_rows_{rows}", torch.stack(outs), eng, extra, kv=(eng.kcache[:, :, :, S:S + 3], eng.vcache[:, :, :, S:S + 3]))
                 eng.set_kv_share(0, 0)
                 eng.release_kv()
             # (i) decode tail, merged o_proj bit (the 33B width is outside gemv_merge_ok: the bit must change nothing here; the
@@ -153,7 +208,7 @@ def main():
                 hx = rand(2, H, seed=40 + step)
                 pos = torch.full((2,), 100 + step, device=dev, dtype=torch.int32)
                 outs.append(eng.forward(hx, 2, 1, pos, pos.clone(), torch.zeros(2, device=dev, dtype=torch.int32), ctx=100 + step + 1).clone())
-            rec("f_fp8_decode_2rows", torch.stack(outs), eng)
+            rec("f_fp8_decode_2rows", torch.stack(outs), eng, {"logits": h(eng.logits(outs[-1]))})
             eng.use_fp8(True, prefill=True)
             eng.release_kv()
             hid, _, _ = eng.prefill(x, m1, cap)
@@ -168,6 +223,46 @@ def main():
             lib().emu_gemm_tune(0)
             rec("i_merged_o_proj", hs, eng, {"ids": h(ids)})
             del eng
+        if want("fp4"):
+            # (j) the MXFP4 modes on the small shape of tests/test_gpu_fp4*.py (hidden 256, 2 heads, ffn 512, 2 layers; a vocabulary
+            # that is no multiple of 64): every row range of every mode, the head with it
+            cfg = LlamaCfg(hidden_size=256, intermediate_size=512, num_attention_heads=2, num_hidden_layers=2)
+            eng, _ = make_engine(cfg, 2050)
+            for tag, mode, row_counts in (("mode1", {}, (1, 2, 5, 16)), ("mode2", {"wide": True}, (1, 2, 5, 16)),
+                                          ("mode3", {"wide": True, "all_rows": True}, (17, 20))):
+                eng.use_fp4(True, **mode)
+                for rows in row_counts:
+                    hs, lg, counters = step_rows(eng, rows, 40, seed=50 + rows)
+                    if rows == 20:                              # mode 3, 5 rows, no workspace: bf16 while there are bf16 weights
+                        counters["logits_5rows_small_ws"] = h(logits_small_ws(eng, hs[-1, :5].contiguous()))
+                    rec(f"j_fp4_{tag}_{rows}rows", hs, eng, {"logits": h(lg), **counters},
+                        kv=(eng.kcache[:, :, :, 40:42], eng.vcache[:, :, :, 40:42]))
+            # a prefill in mode 3 and the same step again after release_bf16
+            x = rand(1, 70, cfg.hidden_size, seed=61)
+
+            def prefill_70():
+                hid = eng.prefill(x, torch.ones(1, 70, dtype=torch.long), eng.kv_capacity(80))[0]
+                return hid, eng.logits(hid.reshape(70, -1).contiguous())
+            for tag in ("mode3", "released"):
+                eng.release_kv()
+                (hid, lg), counters = profiled(prefill_70)
+                rec(f"j_fp4_{tag}_prefill_70", hid, eng, {"logits": h(lg), **counters})
+                hs, lg, counters = step_rows(eng, 5, 40, seed=70)
+                rec(f"j_fp4_{tag}_5rows", hs, eng, {"logits": h(lg), **counters}, kv=(eng.kcache[:, :, :, 40:42], eng.vcache[:, :, :, 40:42]))
+                if tag == "mode3":
+                    eng.release_bf16()
+            del eng
+            # (k) the vocabulary-sharded head (emu_llama_set_head_shard) on a 1-rank communicator: rows [64, 1065) of the head, bf16
+            # and every MXFP4 head kernel
+            eng, real = make_engine(cfg, 2050, comm="rccl")
+            check(lib().emu_llama_set_head_shard(eng.handle, 64, 1001), "emu_llama_set_head_shard", eng.ctx.handle)
+            for tag, mode in (("bf16", None), ("fp4_mode3", {"wide": True, "all_rows": True})):
+                if mode:
+                    eng.use_fp4(True, **mode)
+                for rows in (1, 5, 20):
+                    rec_logits(f"k_head_shard_{tag}_{rows}rows", eng.logits(rand(rows, cfg.hidden_size, seed=80 + rows)))
+            del eng, real
+            torch.cuda.empty_cache()
         if want("fused"):
             # (g) modes 1, 2, 3 on the TP = 8 shard emulation, mode 4 on the TP = 4 one
             eng, _ = make_engine(LlamaCfg(num_hidden_layers=2), 2048, tp=8, comm="p2p")
