@@ -58,6 +58,11 @@ class ProfRowC(C.Structure):
                 ("ms", C.c_double), ("flops", C.c_double)]
 
 
+class WarmPlanC(C.Structure):
+    _fields_ = [("base", vp), ("twin", C.c_longlong), ("limit", C.c_ulonglong), ("group_bytes", C.c_ulonglong)] + \
+               [(n, C.c_uint) for n in ("block_bytes", "row_bytes", "head_bytes", "nsucc", "gx", "first", "ntouch", "lanes", "xcds")]
+
+
 class UNetCfgC(C.Structure):
     _fields_ = [("in_ch", i32), ("out_ch", i32), ("ch", i32 * 3), ("layers_per_block", i32), ("depth", i32 * 3),
                 ("heads", i32 * 3), ("attn", i32 * 3), ("cross_dim", i32), ("groups", i32), ("gn_eps", f32),
@@ -101,6 +106,13 @@ _PROTOS = {
     "emu_layernorm_bf16": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "emu_layernorm_q8_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
     "emu_prefetch": (i32, [vp, sz, i32, vp]),
+    "emu_l2_warm_plan_make": (i32, [vp, lng, C.c_uint, C.c_uint, C.c_uint, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, i32, C.c_uint,
+                                    C.c_ulonglong, i32, C.POINTER(WarmPlanC)]),
+    "emu_l2_warm_enumerate": (lng, [C.POINTER(WarmPlanC), C.c_uint, C.POINTER(C.c_longlong), lng]),
+    "emu_gemv_geometry_query": (i32, [i32, i32, i32, i32, C.POINTER(i32)]),
+    "emu_l2_warm_test_plan": (None, [C.POINTER(WarmPlanC)]),
+    "emu_llama_set_l2_warm": (i32, [vp, i32]),
+    "emu_llama_l2_warm_count": (lng, [vp]),
     "emu_gemv_chain_granule_bytes": (sz, [C.POINTER(ChainOpC), i32]),
     "emu_gemv_chain_bf16": (i32, [vp, C.POINTER(ChainOpC), i32, vp, sz, vp, vp]),
     "emu_softmax_rows_bf16": (i32, [vp, vp, i32, i32, i32, i32, f32, vp]),

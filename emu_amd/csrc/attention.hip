@@ -811,7 +811,14 @@ __global__ __launch_bounds__(256) void decode_fused_kernel(const DecodeFusedArgs
 // same order as the loop form (NS = 0: more splits than the unrolled forms hold), bit-identical.
 template <int D, int NS>
 __global__ void decode_fused_combine_kernel(const float* ws, const int32_t* slot, bf16_t* o, long o_sb, long o_sh, int H,
-                                            int nsplit) {
+                                            int nsplit, const WarmPlan warm) {
+    // workgroups behind the H merging ones (one-row launches with a plan only): they request the head of the next launch's weights
+    // while this launch waits on its own dependent trips (l2_warm.h) and do nothing else
+    if (blockIdx.x >= (unsigned)H) {
+        const uint32_t wd = warm_touch(warm, blockIdx.x, threadIdx.x);
+        asm volatile("" :: "v"(wd));
+        return;
+    }
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
     const float* w = ws + ((size_t)b * H + h) * nsplit * (D + 2);
     if constexpr (NS > 0) {
@@ -855,13 +862,16 @@ __global__ void decode_fused_combine_kernel(const float* ws, const int32_t* slot
 }
 template <int D>
 void launch_combine(const DecodeFusedArgs& a, int ns, hipStream_t s) {
-    const dim3 grid(a.H, a.B), block(D);
+    // a plan (DecodeFusedArgs::warm, one-row launches: its touchers are the linear ids [H, H + ntouch)) enlarges the grid
+    const bool warms = a.warm.ntouch != 0 && a.B == 1 && a.warm.first == (uint32_t)a.H && a.warm.lanes == (uint32_t)D;
+    const WarmPlan wp = warms ? a.warm : WarmPlan{};
+    const dim3 grid(a.H + wp.ntouch, a.B), block(D);
     if (ns <= 8 && !(emu_gemm_tune_get() & (1 << 20)))
-        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 8>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns);
+        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 8>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns, wp);
     else if (ns <= 16 && !(emu_gemm_tune_get() & (1 << 20)))
-        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 16>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns);
+        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 16>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns, wp);
     else
-        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 0>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns);
+        hipLaunchKernelGGL((decode_fused_combine_kernel<D, 0>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns, wp);
 }
 }  // namespace
 

@@ -378,14 +378,27 @@ __global__ __launch_bounds__(256) void layernorm_q8_kernel(const bf16_t* __restr
         *reinterpret_cast<uint2*>(q + roff + vi * 8) = make_uint2((unsigned)lo, (unsigned)hi);
     }
 }
-// touch [ptr, ptr + bytes) into the infinity cache ahead of the launch that streams it (stand-alone form of common.h::pf_touch)
-__global__ __launch_bounds__(256) void prefetch_kernel(PfSpan sp) { pf_touch(sp, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256); }
+// touch [ptr, ptr + bytes) ahead of the launch that streams it: the stand-alone form of l2_warm.h::warm_touch, every workgroup a toucher
+__global__ __launch_bounds__(256) void prefetch_kernel(const WarmPlan p) {
+    const uint32_t d = warm_touch(p, blockIdx.x, threadIdx.x);
+    asm volatile("" :: "v"(d));
+}
 }  // namespace
 int launch_prefetch(const void* ptr, size_t bytes, int workgroups, hipStream_t s) {
-    if (!ptr || workgroups < 1 || (bytes >> 7) > 0xffffffffull) return -22;
-    PfSpan sp;
-    sp.p0 = reinterpret_cast<const char*>(ptr); sp.n0 = (uint32_t)(bytes >> 7);
-    hipLaunchKernelGGL(prefetch_kernel, dim3(workgroups), dim3(256), 0, s, sp);
+    if (!ptr || workgroups < 1 || (bytes >> 7) > 0x3fffffffull) return -22;
+    // the span as "rows" of 32 KiB (one per successor block, the tail row shorter: limit), whole lines only; chunk j is requested by
+    // the workgroups of j's XCD class, so fewer than 8 workgroups cover only their own classes' chunks
+    constexpr uint32_t CHUNK = 32768;
+    const uintptr_t lo = (reinterpret_cast<uintptr_t>(ptr) + 127) & ~(uintptr_t)127, hi = reinterpret_cast<uintptr_t>(ptr) + bytes;
+    if (hi < lo + 128) return 0;
+    WarmPlan p;
+    p.base = reinterpret_cast<const char*>(lo);
+    p.limit = (hi - lo) & ~(size_t)127;
+    p.block_bytes = p.row_bytes = p.head_bytes = CHUNK;
+    p.nsucc = (uint32_t)((p.limit + CHUNK - 1) / CHUNK);
+    p.first = 0; p.ntouch = (uint32_t)workgroups; p.lanes = 256;
+    if (workgroups < (int)p.xcds) p.xcds = 1;            // too few workgroups for every class: one class, every chunk
+    hipLaunchKernelGGL(prefetch_kernel, dim3(workgroups), dim3(256), 0, s, p);
     EMU_CHECK_LAUNCH();
     return 0;
 }

@@ -79,7 +79,7 @@ int gemv_profiled(double weight_bytes, hipStream_t s, Launch launch) {
 
 int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* res, const bf16_t* norm_w,
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
-           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0) {
+           const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0, const WarmPlan* warm = nullptr) {
     if (wscale && M > 2) return -22;                 // fp8 weights are a decode-only stream
     // rows <= 8 stream the weights through the GEMV family (M >= 2 without a fused norm: skinny MFMA kernel); 9..16
     // rows too when the MFMA kernel covers the shape -- a 128-row GEMM tile would be > 87 % padding there
@@ -88,6 +88,7 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     // A/B aid (emu_gemm_tune bit 2): 2..32 rows without a fused norm go through the thin MFMA tile instead
     if (M <= 8 || skinny) {
         GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, wscale};
+        if (warm && M == 1 && !wscale) g.warm = *warm;
         return gemv_profiled((wscale ? 1.0 : 2.0) * (double)N * (double)K, s, [&] { return launch_gemv(g, s); });
     }
     if (norm_w) return -22;
@@ -119,7 +120,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
         const bool f8 = k == WeightKernel::Fp8Rows;
         if (f8 ? !w.W8 || !w.s8 : !w.W) return -22;
         return linear(g.x, f8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps, g.epi, s,
-                      f8 ? w.s8 : nullptr, splitk, splitk_floats);
+                      f8 ? w.s8 : nullptr, splitk, splitk_floats, &g.warm);
     }
     if (k == WeightKernel::Fp8Gemm || !w.W4 || !w.s4) return -22;
     g.W = B(w.W4); g.w4scale = w.s4;
@@ -147,6 +148,10 @@ void engine_tool_switches(EngArgs& a) {
     if (const char* e = getenv("EMU_ENGINE_TIMEOUT_MS")) { const long ms = atol(e); if (ms > 0) a.limit_ticks = ms * 100000LL; }
     if (const char* e = getenv("EMU_ENGINE_LOADERS")) a.nload = atoi(e);
 }
+// tests: the plan the C-ABI primitives emu_linear_bf16 / emu_decode_fused_bf16 attach to their launch (emu_l2_warm_test_plan)
+WarmPlan g_test_warm;
+static_assert(sizeof(emu_warm_plan) == sizeof(WarmPlan) && offsetof(emu_warm_plan, xcds) == offsetof(WarmPlan, xcds) &&
+              offsetof(emu_warm_plan, block_bytes) == offsetof(WarmPlan, block_bytes), "emu_warm_plan mirrors WarmPlan");
 }  // namespace
 
 int emu_ctx_fail(emu_ctx* c, int code, const char* what) { return fail(c, code, what); }
@@ -348,7 +353,45 @@ int emu_allreduce_bf16(emu_ctx* ctx, void* buf, size_t n, emu_stream_t s) {
 // ---------------------------------------------------------------------------------------------- primitives
 int emu_linear_bf16(const void* A, const void* W, const void* bias, const void* res, const void* norm_w, void* C,
                     int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, emu_stream_t s) {
-    return linear(B(A), B(W), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s));
+    return linear(B(A), B(W), B(bias), B(res), B(norm_w), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, S(s), nullptr, nullptr, 0,
+                  g_test_warm.ntouch ? &g_test_warm : nullptr);
+}
+// ---- L2 warming (l2_warm.h): the plan arithmetic for the CPU test, and a test hook that attaches a plan to the primitives
+int emu_l2_warm_plan_make(const void* base, long twin, unsigned rows, unsigned row_bytes, unsigned used_bytes, unsigned long long nrows,
+                          unsigned gx, unsigned groups, unsigned pred_wgs, int extra, unsigned lanes, unsigned long long budget_bytes,
+                          int shape, emu_warm_plan* out) {
+    if (!out) return -22;
+    WarmSucc su;
+    su.base = base; su.twin = twin; su.rows = rows; su.row_bytes = row_bytes; su.used_bytes = used_bytes; su.nrows = nrows;
+    su.gx = gx; su.groups = groups ? groups : 1;
+    const WarmPlan p = make_warm_plan(su, pred_wgs, extra != 0, lanes, budget_bytes, shape);
+    memcpy(out, &p, sizeof p);
+    return 0;
+}
+long emu_l2_warm_enumerate(const emu_warm_plan* plan, unsigned wg, long long* offsets, long cap) {
+    if (!plan) return -22;
+    WarmPlan p;
+    memcpy(&p, plan, sizeof p);
+    long n = 0;
+    const uint32_t trips = warm_trips(p, wg);
+    for (uint32_t i = 0; i < trips; ++i)
+        for (uint32_t t = 0; t < p.lanes; ++t) {
+            const int64_t off = warm_line(p, wg, t, i);
+            if (off < 0) continue;
+            if (offsets && n < cap) offsets[n] = off;
+            ++n;
+        }
+    return n;
+}
+int emu_gemv_geometry_query(int N, int K, int norm, int epi, int out[4]) {
+    if (!out || N < 1 || K < 8) return -22;
+    const GemvGeom g = emu_gemv_geometry(N, K, norm != 0, epi);
+    out[0] = g.form; out[1] = g.rows; out[2] = emu_gemv_rows_per_block(N, K, norm != 0); out[3] = emu_gemv_partition(N, K, norm != 0, epi);
+    return 0;
+}
+void emu_l2_warm_test_plan(const emu_warm_plan* plan) {
+    g_test_warm = WarmPlan{};
+    if (plan) memcpy(&g_test_warm, plan, sizeof g_test_warm);
 }
 int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps,
@@ -534,6 +577,7 @@ int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, con
                           emu_stream_t s) {
     DecodeFusedArgs a{B(qkv), B(cos), B(sin), pos, slot, B(kcache), B(vcache), B(o), o_sb, o_sh, kstart,
                       reinterpret_cast<float*>(ws), Bn, H, D, S_max, ctx_max, scale, share_nb, share_len, arrive};
+    a.warm = g_test_warm;                            // (emu_l2_warm_test_plan; the launch ignores a plan that does not fit it)
     return launch_decode_fused(a, S(s));
 }
 
@@ -575,6 +619,9 @@ struct emu_llama {
     // decode attention without the combine launch (emu_llama_set_decode_tail, off by default): per (row, head) arrival counters of
     // the split workgroups (zero between launches; owned here: EMU_ARRIVE_INTS ints of device memory)
     int* arrive = nullptr;
+    // L2 warming across the launch boundaries of the default one-row bf16 step (emu_llama_set_l2_warm; l2_warm.h)
+    int l2_warm = EMU_L2_WARM_DEFAULT;
+    long warm_launches = 0;                      // launches that carried a non-empty plan (tests)
     bool decode_tail = false;                    // measured 0.4 % SLOWER than the combine launch (profiles/r04_decode_tail_merge_ab.log): opt-in
     // whole decoder layers of a one-row step in one launch (decode_layer.hip; emu_llama_set_decode_fused)
     int decode_fused = 0;                        // 0: the launches above; 1: fused where the shape / mode allows; 2: + in-kernel all-reduce
@@ -677,6 +724,9 @@ struct LlamaPlan {
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
     WeightKernel kernel;
     bool fuse_rope, fuse_norm, norm_in_gemv, decode_tail, merge_o;
+    // warm           boundaries of the layer whose predecessor warms the XCDs' L2s with the head of its successor (emu_llama_set_l2_warm's
+    //                bits 0-4); only the default one-row step has any: bf16 weights, no tensor parallelism, own KV rows, the combine launch
+    int warm = 0;
     // the launch arguments as far as they are decided here -- Fused*: H, Hl, Fl, the wait bound and the peers' comm blocks (tp_n == 0:
     // no all-reduce inside a launch); Engine: the engine areas of the comm blocks (comm, seq, tp_n, tp_rank)
     DecodeLayersArgs dl; EngArgs eng;
@@ -731,6 +781,9 @@ struct LlamaCall {
         // and the tail all-reduce before it
         p.merge_o = T == 1 && M == 1 && p.kernel == WeightKernel::Bf16 && !p.decode_tail && own_kv && gemv_merge_ok(Hl, D, H, (ctx + 127) / 128) &&
                     (emu_gemm_tune_get() & (1 << 19)) != 0;
+        if (T == 1 && M == 1 && p.kernel == WeightKernel::Bf16 && !tp && own_kv && !p.decode_tail && !p.merge_o && !m->decode_fused &&
+            !(emu_gemm_tune_get() & (1 << 30)))
+            p.warm = m->l2_warm;
 
         const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && !m->fp4_decode && own_kv && some_layers;
         // the fence-free peer-to-peer all-reduce is on (which implies tensor parallelism and an opened cx->p2p): what the all-reduces
@@ -778,7 +831,7 @@ struct LlamaCall {
     // by the plan's kernel (every window of a call has the row range the plan chose it for: pick_path).  gain_in: the RMSNorm in front,
     // fused into a one-row weight stream; gain_out: w.xn = RMSNorm(C) * gain_out behind the K-slice sums.
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const Weights& W, const bf16_t* res, const bf16_t* gain_in,
-                const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi) {
+                const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi, const WarmPlan& warm = WarmPlan{}) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
         WeightKernel k = plan.kernel;
         if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Gemm) {
@@ -787,7 +840,27 @@ struct LlamaCall {
             if (gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
             k = WeightKernel::Bf16;                      // (Fp8Gemm: a layer without fp8 weights runs bf16)
         }
-        return linear_w(k, W, packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi), s, w.splitk, w.splitk_floats);
+        GemvArgs g = packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi);
+        if (warm.ntouch && k == WeightKernel::Bf16) { g.warm = warm; ++m->warm_launches; }
+        return linear_w(k, W, g, s, w.splitk, w.splitk_floats);
+    }
+
+    // ---- L2 warming (l2_warm.h).  The budget and the head's shape ride in the mask (include/emu_hip.h: emu_llama_set_l2_warm).
+    uint64_t warm_budget() const { const int mib = (plan.warm >> 8) & 0xff; return (uint64_t)(mib ? mib : EMU_L2_WARM_DEFAULT_MIB) << 20; }
+    int warm_shape() const { return plan.warm & 32 ? WARM_FIRST_TRIP : WARM_WHOLE_BLOCKS; }
+    // the packed [N, K] matrix Wn as the one-row stream that follows reads it (emu_gemv_geometry: the rule launch_gemv applies)
+    static WarmSucc warm_succ(const bf16_t* Wn, int N, int K, bool norm, int epi) {
+        WarmSucc su;
+        su.base = Wn; su.rows = (uint32_t)emu_gemv_geometry(N, K, norm, epi).rows; su.row_bytes = su.used_bytes = (uint32_t)K * 2;
+        su.nrows = (uint64_t)N;
+        return su;
+    }
+    // boundary `bit`: the one-row stream over [N, K] (a form that carries the loop, else no plan) warms su from its last workgroups
+    WarmPlan warm_from_gemv(int bit, int N, int K, bool norm, int epi, const WarmSucc& su) const {
+        if (!(plan.warm & (1 << bit)) || !su.base) return WarmPlan{};
+        const GemvGeom g = emu_gemv_geometry(N, K, norm, epi);
+        if (!gemv_form_warms(g.form)) return WarmPlan{};
+        return make_warm_plan(su, (uint32_t)((N + g.rows - 1) / g.rows), false, 256, warm_budget(), warm_shape());
     }
 
     RowWindow window(int r0, int T, int kend, hipStream_t s, bf16_t* vt, float* splitk) {
@@ -825,9 +898,17 @@ struct LlamaCall {
             if (st != 0 && st != -95) return fail(cx, st, "emu_llama_forward: qkv projection with the RoPE epilogue");
             if (st == -95) plan.fuse_rope = false;       // the 256x256 tile does not take this shape unsliced: unfused sequence from here on
         }
-        if (st == -95)
+        if (st == -95) {
+            WarmPlan wp;
+            if (plan.warm & 16) {                        // this layer's cache rows as the attention grid (split, head) reads them
+                WarmSucc su;
+                su.base = kc; su.twin = (int64_t)(vc - kc) * 2; su.rows = 128; su.row_bytes = su.used_bytes = (uint32_t)D * 2;
+                su.nrows = (uint64_t)m->s_max; su.gx = (uint32_t)((ctx + 127) / 128); su.groups = (uint32_t)Hl;
+                if (D == 128) wp = warm_from_gemv(4, 3 * HD, H, true, EPI_NONE, su);
+            }
             TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, L.qkv, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
-                            nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE));
+                            nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE, wp));
+        }
         if (T == 1) return 0;                            // single-token step: the attention launch rotates and appends
         if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
         if (plan.fuse_rope) return 0;
@@ -847,6 +928,10 @@ struct LlamaCall {
                               Bn, Hl, D, m->s_max, ctx, scale, m->kv_share_nb, m->kv_share_len};
             if (plan.decode_tail) a.arrive = m->arrive;
             a.skip_combine = plan.merge_o;
+            if ((plan.warm & 1) && Bn == 1 && L.o.W) {   // extra workgroups of the combine launch warm o_proj
+                a.warm = make_warm_plan(warm_succ(L.o.W, H, HD, false, epi_res), (uint32_t)Hl, true, (uint32_t)D, warm_budget(), warm_shape());
+                if (a.warm.ntouch) ++m->warm_launches;
+            }
             TRY(cx, launch_decode_fused(a, win.s));
         } else {
             if (!plan.fuse_rope) {
@@ -864,7 +949,8 @@ struct LlamaCall {
             GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.o.W, win.x, w.hB, H, HD, HD, epi_res, nullptr};
             TRY(cx, gemv_merge_profiled(g, win.s));
         } else
-            TRY(cx, project(w, win.s, w.attn, L.o, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res));
+            TRY(cx, project(w, win.s, w.attn, L.o, win.x, nullptr, plan.fuse_norm ? L.ln2 : nullptr, w.hB, rows, H, HD, epi_res,
+                            warm_from_gemv(1, H, HD, false, epi_res, warm_succ(L.gu.W, 2 * Fl, H, true, EPI_SWIGLU))));
         return win.allreduce(w.hB, (size_t)rows * H);
     }
 
@@ -874,10 +960,16 @@ struct LlamaCall {
         const int rows = Bn * win.T;
         if (!plan.norm_in_gemv && !plan.fuse_norm) TRY(cx, launch_rmsnorm(w.hB, L.ln2, w.xn, rows, H, H, H, eps, win.s));
         TRY(cx, project(w, win.s, plan.norm_in_gemv ? w.hB : w.xn, L.gu, nullptr, plan.norm_in_gemv ? L.ln2 : nullptr, nullptr,
-                        w.act, rows, 2 * Fl, H, EPI_SWIGLU));
+                        w.act, rows, 2 * Fl, H, EPI_SWIGLU,
+                        warm_from_gemv(2, 2 * Fl, H, true, EPI_SWIGLU, warm_succ(L.down.W, H, Fl, false, epi_res))));
         // (fuse_norm: the RMSNorm behind down_proj is the NEXT layer's input norm, which then finds its rows in w.xn)
         const bf16_t* next_ln1 = plan.fuse_norm && l + 1 < l_end ? m->layers[l + 1].ln1 : nullptr;
-        TRY(cx, project(w, win.s, w.act, L.down, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res));
+        // (behind the model's last layer the whole head follows: emu_llama_logits' one-row stream with the final norm in front)
+        WarmSucc after;
+        if (l + 1 < l_end) after = warm_succ(m->layers[l + 1].qkv.W, 3 * HD, H, true, EPI_NONE);
+        else if (l + 1 == m->cfg.layers && m->head_rows < 0 && m->final_norm) after = warm_succ(m->head.W, m->cfg.vocab, H, true, EPI_NONE);
+        TRY(cx, project(w, win.s, w.act, L.down, w.hB, nullptr, next_ln1, win.x, rows, H, Fl, epi_res,
+                        warm_from_gemv(3, H, Fl, false, epi_res, after)));
         if (next_ln1) xn_ready = true;
         return win.allreduce(win.x, (size_t)rows * H);
     }
@@ -1241,6 +1333,12 @@ int emu_llama_set_decode_tail(emu_llama* m, int enable) {
     m->decode_tail = enable != 0;
     return 0;
 }
+int emu_llama_set_l2_warm(emu_llama* m, int mask) {
+    if (!m || mask < 0 || (mask >> 16)) return -22;
+    m->l2_warm = mask;
+    return 0;
+}
+long emu_llama_l2_warm_count(const emu_llama* m) { return m ? m->warm_launches : -1; }
 int emu_llama_set_prefill_fusion(emu_llama* m, int enable) {
     if (!m) return -22;
     m->prefill_fusion = enable != 0;

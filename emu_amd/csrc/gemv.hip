@@ -182,6 +182,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
         }
     };
 
+    uint32_t warm = 0;                                                 // destination of the successor touches (l2_warm.h): live to the end
     if constexpr (PRE < 0) {
         auto dots = [&](const u32x4 (&wv)[R], const u32x4& xp) {
 #pragma unroll
@@ -210,9 +211,11 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
         if (tid + 256 < KV) dots(w1, hx[1]);
         __builtin_amdgcn_sched_barrier(0);
         fetch(w1, 3);
+        warm = warm_touch(a.warm, blockIdx.x, tid);                    // behind this workgroup's last weight load
         if (tid + 512 < KV) dots(hw, hx[2]);
         if (tid + 768 < KV) dots(w1, hx[3]);
     } else if constexpr (PRE > 0) {
+        warm = warm_touch(a.warm, blockIdx.x, tid);                    // every weight load was issued in the prologue
 #pragma unroll
         for (int c = 0; c < PRE; ++c) {
             const int vi = tid + 256 * c;
@@ -266,6 +269,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
             }
         }
     }
+    if constexpr (PRE != 0) asm volatile("" :: "v"(warm));
 }
 
 // Single-round-trip GEMV (decode, M = 1): every load of the block -- x, gain, and the block's WHOLE weight slice
@@ -310,6 +314,9 @@ __global__ __launch_bounds__(256) void gemv_rt_kernel(const GemvArgs a) {
                     reinterpret_cast<const WT*>(W8 + ((size_t)n * a.ldw + (size_t)vi * 8) * WB));
         }
     }
+
+    uint32_t warm = 0;                                               // successor touches (l2_warm.h), behind the last weight load
+    if constexpr (!FP8) warm = warm_touch(a.warm, blockIdx.x, tid);
 
     float rinv = 1.f;
     if constexpr (NORM) {
@@ -403,6 +410,7 @@ __global__ __launch_bounds__(256) void gemv_rt_kernel(const GemvArgs a) {
             }
         }
     }
+    if constexpr (!FP8) asm volatile("" :: "v"(warm));
 }
 
 template <int R, int KIT, bool FP8>
@@ -480,6 +488,29 @@ __global__ __launch_bounds__(256) void gemv_wave_kernel(const GemvArgs a) {
     }
 }
 
+// ---- which one-row (M = 1) shapes the wave form and the single-round-trip form take: pure integer rules, shared by the launchers
+// below and by emu_gemv_geometry (the successor's geometry for l2_warm.h comes from the same place as the launch).
+// wave form: 64-lane trips per row (1..5), or 0 when the shape is not covered (bf16 only)
+int gemv_wave_trips(int N, int K, bool norm, int epi) {
+    if (norm || (epi != EPI_NONE && epi != EPI_RESID)) return 0;
+    const int kitw = ((K >> 3) + 63) / 64;
+    return kitw > 5 || N < 1024 ? 0 : kitw;                          // K <= 2560; tiny N stays on the block kernels
+}
+// single-round-trip form: the built trip count (4 or 9) that holds the row, or 0 when the shape is not covered
+int gemv_rt_trips(int N, int K, bool norm, int epi, bool f8) {
+    if (epi == EPI_SWIGLU && (N & 1)) return 0;
+    const int kit = ((K >> 3) + 255) / 256;
+    if (f8 && (epi == EPI_SILU || epi == EPI_GELU)) return 0;
+    // measured (tools/kbench.py, profiles/r01_gemv_variants.log): one round trip wins for matrices small enough
+    // that latency, not bandwidth, sets the time (TP shards, tiny models) and for long rows without the RMSNorm
+    // prologue (down_proj: 6.3 vs 5.85 TB/s); big fused-norm matrices amortise the prologue better over 8 rows
+    const size_t bytes = (size_t)N * K * (f8 ? 1 : 2);
+    const bool small = bytes < ((size_t)(f8 ? 32 : 64) << 20);
+    const bool long_rows = !f8 && kit >= 5 && !norm;
+    if (!small && !long_rows) return 0;
+    return kit <= 4 ? 4 : kit <= 9 ? 9 : 0;
+}
+
 template <int RW, int KITW>
 int launch_wave(const GemvArgs& a, hipStream_t s) {
     const dim3 grid((a.N + 4 * RW - 1) / (4 * RW)), block(256);
@@ -491,9 +522,9 @@ int launch_wave(const GemvArgs& a, hipStream_t s) {
 
 // returns 1 when the shape is not covered
 int try_launch_wave(const GemvArgs& a, hipStream_t s) {
-    if (a.M != 1 || a.norm_w || a.wscale || (a.epi != EPI_NONE && a.epi != EPI_RESID)) return 1;
-    const int kitw = ((a.K >> 3) + 63) / 64;
-    if (kitw > 5 || a.N < 1024) return 1;                            // K <= 2560; tiny N stays on the block kernels
+    if (a.M != 1 || a.wscale) return 1;
+    const int kitw = gemv_wave_trips(a.N, a.K, a.norm_w != nullptr, a.epi);
+    if (!kitw) return 1;
     switch (kitw) {
         case 1: return launch_wave<4, 1>(a, s);
         case 2: return launch_wave<4, 2>(a, s);
@@ -506,19 +537,10 @@ int try_launch_wave(const GemvArgs& a, hipStream_t s) {
 // M = 1 dispatch onto the single-round-trip kernel; returns 1 when the shape is not covered.
 int try_launch_rt(const GemvArgs& a, hipStream_t s) {
     if (a.M != 1) return 1;
-    if (a.epi == EPI_SWIGLU && (a.N & 1)) return 1;
-    const int kit = ((a.K >> 3) + 255) / 256;
     const bool f8 = a.wscale != nullptr;
-    if (f8 && (a.epi == EPI_SILU || a.epi == EPI_GELU)) return 1;
-    // measured (tools/kbench.py, profiles/r01_gemv_variants.log): one round trip wins for matrices small enough
-    // that latency, not bandwidth, sets the time (TP shards, tiny models) and for long rows without the RMSNorm
-    // prologue (down_proj: 6.3 vs 5.85 TB/s); big fused-norm matrices amortise the prologue better over 8 rows
-    const size_t bytes = (size_t)a.N * a.K * (f8 ? 1 : 2);
-    const bool small = bytes < ((size_t)(f8 ? 32 : 64) << 20);
-    const bool long_rows = !f8 && kit >= 5 && a.norm_w == nullptr;
-    if (!small && !long_rows) return 1;
-    if (kit <= 4) return f8 ? launch_rt<8, 4, true>(a, s) : launch_rt<4, 4, false>(a, s);
-    if (kit <= 9) return f8 ? launch_rt<4, 9, true>(a, s) : launch_rt<2, 9, false>(a, s);
+    const int kit = gemv_rt_trips(a.N, a.K, a.norm_w != nullptr, a.epi, f8);
+    if (kit == 4) return f8 ? launch_rt<8, 4, true>(a, s) : launch_rt<4, 4, false>(a, s);
+    if (kit == 9) return f8 ? launch_rt<4, 9, true>(a, s) : launch_rt<2, 9, false>(a, s);
     return 1;
 }
 
@@ -954,16 +976,23 @@ int launch_epi(const GemvArgs& a, hipStream_t s) {
     return 0;
 }
 
+// the form of the one-row block kernel for R rows per workgroup (launch_norm below)
+int gemv_block_form(int R, int K, bool norm) {
+    if (!norm && R <= 4 && (K >> 3) <= 1024) return GEMV_FORM_PRELOAD;
+    if (norm && (K >> 3) <= 1024) return GEMV_FORM_HEAD;
+    return GEMV_FORM_ROLLING;
+}
+
 template <int R, int MB>
 int launch_norm(const GemvArgs& a, hipStream_t s) {
     // the preload-everything form only for the single-row decode case (register budget: PRE*R*4 VGPRs)
     // measured: the preload form wins only for plain streams (o_proj); with the RMSNorm prologue it loses 20 %
     // (clamped tail chunks + lower occupancy), so those keep the rolling loop.
     if constexpr (MB == 1 && R <= 4) {
-        if (!a.norm_w && (a.K >> 3) <= 1024) return launch_epi<R, MB, false, 4>(a, s);
+        if (gemv_block_form(R, a.K, a.norm_w != nullptr) == GEMV_FORM_PRELOAD) return launch_epi<R, MB, false, 4>(a, s);
     }
     if constexpr (MB == 1) {
-        if (a.norm_w && (a.K >> 3) <= 1024) return launch_epi<R, MB, true, -1>(a, s);
+        if (gemv_block_form(R, a.K, a.norm_w != nullptr) == GEMV_FORM_HEAD) return launch_epi<R, MB, true, -1>(a, s);
     }
     return a.norm_w ? launch_epi<R, MB, true, 0>(a, s) : launch_epi<R, MB, false, 0>(a, s);
 }
@@ -997,6 +1026,15 @@ int emu_gemv_rows_per_block_multi(int N) {
     return R;
 }
 
+GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi) {
+    // (emu_gemm_tune bit 17, tests: no wave / single-round-trip form, so small matrices reach the block kernels' head and preload forms)
+    const bool block_only = (emu_gemm_tune_get() & (1 << 17)) != 0;
+    if (!block_only && gemv_wave_trips(N, K, norm, epi)) return {GEMV_FORM_WAVE, 16};
+    if (const int kit = block_only ? 0 : gemv_rt_trips(N, K, norm, epi, false)) return {GEMV_FORM_RT, kit == 4 ? 4 : 2};
+    const int R = emu_gemv_rows_per_block(N, K, norm);
+    return {gemv_block_form(R, K, norm), R};
+}
+
 int emu_gemv_partition(int N, int K, bool norm, int epi) {
     // try_launch_wave's conditions (M = 1, bf16): no fused norm, EPI_NONE / EPI_RESID, K <= 2560, N >= 1024
     const int kitw = ((K >> 3) + 63) / 64;
@@ -1021,8 +1059,14 @@ int launch_gemv(const GemvArgs& a, hipStream_t s) {
         return launch_gemv_mfma(a, s);
     if (a.M > 8) return -22;
     if (a.wscale && ((a.K & 15) || a.M > 2)) return -22;
-    { const int st = try_launch_wave(a, s); if (st != 1) return st; }
-    { const int st = try_launch_rt(a, s); if (st != 1) return st; }
+    if (a.M == 1 && !a.wscale) {                     // one bf16 row: the form and the rows per workgroup from emu_gemv_geometry
+        const GemvGeom g = emu_gemv_geometry(a.N, a.K, a.norm_w != nullptr, a.epi);
+        if (g.form == GEMV_FORM_WAVE) return try_launch_wave(a, s);
+        if (g.form == GEMV_FORM_RT) return try_launch_rt(a, s);
+    } else {
+        const int st = try_launch_rt(a, s);          // (fp8 rows; the launcher refuses M > 1)
+        if (st != 1) return st;
+    }
     if (a.wscale) {                                  // fp8 weight stream (decode, batch <= 2 built)
         // 16 weights per 16-byte load: K = 6656 is only 416 groups, so short rows run 2-wave blocks (3.25 trips per
         // lane, like the bf16 kernel) and long rows (down_proj, K = 17920) 4-wave blocks

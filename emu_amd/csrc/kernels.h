@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/emu_hip.h"
+#include "l2_warm.h"
 
 typedef uint16_t bf16_t;
 
@@ -26,7 +27,17 @@ struct GemvArgs {
     // [N, lds], one per 32 elements (K % 32 == 0, M <= 2): gemv_fp4.hip
     const uint8_t* w4scale = nullptr;
     int lds = 0;
+    // L2 warming of the launch that follows (l2_warm.h): the last workgroups of the one-row bf16 stream forms (head, preload,
+    // single round trip) request the head of the successor's weights.  ntouch == 0: none; every other kernel ignores it.
+    WarmPlan warm;
 };
+// The rule launch_gemv applies to a one-row bf16 stream, as a pure host function: which kernel form runs the shape and how many
+// weight rows a workgroup owns -- workgroup j reads rows [j * rows, j * rows + rows).  (GEMV_FORM_WAVE: 4 waves x 4 whole rows.)
+enum GemvForm { GEMV_FORM_ROLLING = 0, GEMV_FORM_HEAD = 1, GEMV_FORM_PRELOAD = 2, GEMV_FORM_RT = 3, GEMV_FORM_WAVE = 4 };
+struct GemvGeom { int form, rows; };
+GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi);
+int emu_gemv_rows_per_block(int N, int K, bool norm);      // the block kernels' heuristic (gemv.hip)
+inline bool gemv_form_warms(int form) { return form == GEMV_FORM_HEAD || form == GEMV_FORM_PRELOAD || form == GEMV_FORM_RT; }
 int launch_gemv(const GemvArgs& a, hipStream_t s);
 // the MXFP4 weight stream (gemv_fp4.hip; launch_gemv forwards to it when a.w4scale is set) and its quantiser: bf16 [N, ldw] ->
 // element bytes [N, ldq] + E8M0 scales [N, lds], bit-exact with emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the
@@ -338,6 +349,9 @@ struct DecodeFusedArgs {
     int* arrive = nullptr;
     // one-row path: leave the split states in ws and launch no combine -- the consumer merges them itself (launch_gemv_merge)
     bool skip_combine = false;
+    // one-row launches (B == 1) with the combine launch: extra workgroups behind its H merging ones request the head of the launch
+    // that follows (l2_warm.h; make_warm_plan with extra = true, pred_wgs = H, lanes = D).  ntouch == 0: none.
+    WarmPlan warm;
 };
 constexpr int DECODE_SHARE_MAX = 8;            // beams per group the shared-prefix path takes
 size_t decode_fused_ws_floats(int B, int H, int D, int ctx_max);
@@ -488,7 +502,7 @@ int launch_add_silu(const bf16_t* a, const bf16_t* b, bf16_t* sum_out, bf16_t* s
 // out[r, :] = table[step[0], :] for r < rows
 int launch_gather_step_row(const bf16_t* table, const int32_t* step, bf16_t* out, int rows, int cols, hipStream_t s);
 
-// stand-alone successor prefetch (common.h::pf_touch): [ptr, ptr + bytes) -> infinity cache, workgroups x 256 threads
+// stand-alone touch (l2_warm.h::warm_touch): [ptr, ptr + bytes) -> infinity cache and the XCDs' L2s, workgroups x 256 threads
 int launch_prefetch(const void* ptr, size_t bytes, int workgroups, hipStream_t s);
 // in-place row softmax of x [rows, ld] over the first `cols` columns: x = bf16(softmax(float(x) * scale))
 // (materialised-score attention for head dims the flash kernel does not cover: the VAE mid block, D = 512)

@@ -207,6 +207,8 @@ class LlamaEngine:
         # MI355X (12.45 vs 10.57 ms per token at TP = 1, 3.95 vs 3.57 for a TP = 8 shard: profiles/r05_decode_fused_*.log), so it
         # is an option (EMU_DECODE_FUSED=1|2 or set_decode_fused), off by default
         self.decode_fused = 0
+        if os.environ.get("EMU_L2_WARM") and hasattr(lib(), "emu_llama_set_l2_warm"):      # A/B aid: the warm mask of this engine
+            self.set_l2_warm(int(os.environ["EMU_L2_WARM"], 0))
         mode = int(os.environ.get("EMU_DECODE_FUSED", "0"))
         if mode:
             self.set_decode_fused(mode)
@@ -222,6 +224,17 @@ class LlamaEngine:
     def _mode_changed(self) -> None:
         self.mode_epoch += 1
         self.__dict__.pop("_beam_graphs", None)
+
+    def set_l2_warm(self, mask: int) -> None:
+        """L2 warming across the launch boundaries of the default one-row decode step (include/emu_hip.h: emu_llama_set_l2_warm):
+        bits 0-4 = combine -> o_proj, o_proj -> gate/up, gate/up -> down, down -> next qkv / lm_head, qkv -> K/V rows; bit 5 = first
+        trips instead of whole blocks; bits 8-15 = budget in MiB.  Same bits whatever the mask.  Invalidates captured decode graphs."""
+        check(lib().emu_llama_set_l2_warm(self.handle, int(mask)), "emu_llama_set_l2_warm", self.ctx.handle)
+        self._mode_changed()
+
+    def l2_warm_count(self) -> int:
+        """Launches that carried a non-empty warm plan since the engine was created (tests)."""
+        return int(lib().emu_llama_l2_warm_count(self.handle))
 
     def set_decode_tail(self, enable: bool) -> None:
         """Decode attention in one launch (the last split workgroup of a head merges the splits) or, the default, with the separate

@@ -112,7 +112,9 @@ int emu_gemm_plan(const emu_gemm_shape* shape, int force_cfg, int tune, emu_gemm
  * 256x256 configuration, whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of
  * through LDS; bits 24-25 (the MXFP4 weight stream, gemv_fp4.hip; tools/fp4_time.py --ab): 1 / 2 / 3 = 1 / 2 / 4 row sets per
  * workgroup instead of the planned number, bits 26-27: 1 / 2 = 4 / 8 weight rows per lane; bits 28-29 (the few-row MXFP4 stream,
- * gemv_fp4_thin.hip; tools/fp4_wide_time.py --ab): 1 / 2 = 16 / 32 weight rows per workgroup instead of the heuristic. */
+ * gemv_fp4_thin.hip; tools/fp4_wide_time.py --ab): 1 / 2 = 16 / 32 weight rows per workgroup instead of the heuristic;
+ * bit 17 (tests): one-row bf16 streams skip the wave and single-round-trip forms, so a small matrix reaches the block kernel's head /
+ * preload form; bit 30: no L2 warming anywhere (emu_llama_set_l2_warm's plans are all empty: the same-build twin of a warmed run). */
 void emu_gemm_tune(int mask);
 
 /* Tools hook (tools/gemm_trace.py): per-workgroup timelines of the following GEMM launches -- 8 x uint64 per workgroup at
@@ -274,10 +276,34 @@ int emu_gemv_chain_bf16(emu_ctx* ctx, const emu_chain_op* ops, int nops, void* g
                         emu_stream_t s);
 /* Touch [ptr, ptr + bytes) -- the weight matrix of a launch that FOLLOWS on the stream -- into the 256 MB infinity cache with
  * `workgroups` x 256 threads, one dword per 128-byte line, nothing waited for.  The stand-alone form of the successor prefetch the
- * one-row decode step carries inside its own launches (emu_llama_set_decode_prefetch): the reference's nn.Linear weights
+ * one-row decode step can carry inside its own launches (emu_llama_set_l2_warm): the reference's nn.Linear weights
  * (transformers LlamaDecoderLayer reached from Emu2/emu/emu.py:213-229) are read once per token, and every kernel of a layer that
  * leaves HBM idle (attention, split merge, all-reduce) pulls the next projection's rows on-die meanwhile.  tools / tests. */
 int emu_prefetch(const void* ptr, size_t bytes, int workgroups, emu_stream_t s);
+
+/* ---- L2 warming across a kernel boundary (csrc/l2_warm.h has the story).  emu_warm_plan is the plan as it travels in the
+ * kernel-argument segment: toucher workgroups [first, first + ntouch) of the predecessor request 128-byte lines of the successor,
+ * each from a workgroup of the reader's linear id % xcds.  emu_l2_warm_plan_make: the host planner (successor: `rows` rows of
+ * row_bytes stride per workgroup, used_bytes read per row, nrows rows -- per group when gx > 0: gx blocks per group, `groups` groups;
+ * twin: byte distance to a second array of the same geometry or 0; predecessor: pred_wgs working workgroups whose last ones touch, or
+ * with extra != 0 ntouch workgroups behind them; shape 0 = whole blocks, 1 = the first 4 KiB of every row).  An empty plan has
+ * ntouch == 0.  emu_l2_warm_enumerate: byte offsets (from base) of the lines workgroup wg requests, through the function the kernels
+ * run; returns their number (offsets may be NULL, at most cap are written).  emu_gemv_geometry_query: out = {form, rows per workgroup,
+ * the block kernels' rows-per-workgroup heuristic, the column partition} of a one-row bf16 stream, the rule the launch applies
+ * (form 0 rolling, 1 head, 2 preload, 3 single round trip, 4 wave).  emu_l2_warm_test_plan (tests): the plan emu_linear_bf16 (one row)
+ * and emu_decode_fused_bf16 (one row, combine launch) attach to their launches until it is cleared with NULL. */
+typedef struct {
+    const char* base;
+    long long twin;
+    unsigned long long limit, group_bytes;
+    unsigned int block_bytes, row_bytes, head_bytes, nsucc, gx, first, ntouch, lanes, xcds;
+} emu_warm_plan;
+int emu_l2_warm_plan_make(const void* base, long twin, unsigned rows, unsigned row_bytes, unsigned used_bytes, unsigned long long nrows,
+                          unsigned gx, unsigned groups, unsigned pred_wgs, int extra, unsigned lanes, unsigned long long budget_bytes,
+                          int shape, emu_warm_plan* out);
+long emu_l2_warm_enumerate(const emu_warm_plan* plan, unsigned wg, long long* offsets, long cap);
+int emu_gemv_geometry_query(int N, int K, int norm, int epi, int out[4]);
+void emu_l2_warm_test_plan(const emu_warm_plan* plan);
 /* embed_tokens (emu.py:119,193) and the masked row overwrite text_embeds[ids == IMAGE] = ... (emu.py:202-203) */
 int emu_embed_gather_bf16(const int32_t* ids, const void* table, void* out, int n_tok, int hidden, int vocab,
                           emu_stream_t s);
@@ -466,6 +492,19 @@ long emu_llama_tp_overlap_count(const emu_llama* m);
  * combine launch; same arithmetic, bit-identical outputs.  Measured 0.4 % slower than the two launches on MI355X (three
  * dependent fabric round trips in the tail cost what the launch does), so it stays an option for A/B timing. */
 int emu_llama_set_decode_tail(emu_llama* m, int enable);
+
+/* L2 warming in the default one-row decode step (per-layer launches, bf16 weights, no tensor parallelism, own KV rows): the last
+ * workgroups of a launch -- extra workgroups in the combine launch -- request the head of what the NEXT launch reads, each line from
+ * a workgroup of the reader's XCD class, never waited for; results are bit-identical whatever the mask.  Bits 0-4, one boundary each:
+ * 0 combine -> o_proj, 1 o_proj -> gate/up, 2 gate/up -> down, 3 down -> the next layer's qkv (lm_head behind the last layer),
+ * 4 qkv -> this layer's K / V cache rows.  Bit 5: the first 4 KiB of every row of more workgroups instead of whole blocks of the
+ * first ones; bits 8-15: the budget per boundary in MiB (0 = EMU_L2_WARM_DEFAULT_MIB).  Every other mode of the engine (beams, fp8,
+ * fp4, tensor parallelism, fused layers, the persistent engine) runs without.  The default is what measured faster
+ * (profiles/l2_warm.md); emu_gemm_tune bit 30 switches all of it off.  emu_llama_l2_warm_count: launches that carried a plan (tests). */
+#define EMU_L2_WARM_DEFAULT 0
+#define EMU_L2_WARM_DEFAULT_MIB 16
+int emu_llama_set_l2_warm(emu_llama* m, int mask);
+long emu_llama_l2_warm_count(const emu_llama* m);
 
 /* Whole decoder layers of a one-row decode step in ONE launch (csrc/decode_layer.hip): with enable != 0, emu_llama_forward calls
  * with B == 1, T == 1, bf16 weights, head_dim 128 and no shared-prefix KV rows run layers_per_launch layers (0 = all layers of the
