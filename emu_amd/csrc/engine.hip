@@ -81,13 +81,10 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
            const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0, const WarmPlan* warm = nullptr) {
     if (wscale && M > 2) return -22;                 // fp8 weights are a decode-only stream
-    // rows <= 8 stream the weights through the GEMV family (M >= 2 without a fused norm: skinny MFMA kernel); 9..16
-    // rows too when the MFMA kernel covers the shape -- a 128-row GEMM tile would be > 87 % padding there
-    const bool skinny = M > 8 && M <= 16 && !norm_w && (K & 31) == 0 && (ldw & 7) == 0 && (lda & 7) == 0 &&
-                        (epi == EPI_NONE || epi == EPI_RESID || epi == EPI_SWIGLU || epi == EPI_SILU || epi == EPI_GELU);
-    // A/B aid (emu_gemm_tune bit 2): 2..32 rows without a fused norm go through the thin MFMA tile instead
-    if (M <= 8 || skinny) {
-        GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, wscale};
+    // rows <= 8 stream the weights through the GEMV family, which plans its own kernel (gemv.hip::gemv_plan); 9..16 rows too where
+    // that family takes them (gemv_rows_9_16_ok) -- a 128-row GEMM tile would be > 87 % padding there
+    if (M <= 8 || gemv_rows_9_16_ok(M, K, lda, ldw, norm_w != nullptr, wscale != nullptr, epi)) {
+        GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, wscale};
         if (warm && M == 1 && !wscale) g.warm = *warm;
         return gemv_profiled((wscale ? 1.0 : 2.0) * (double)N * (double)K, s, [&] { return launch_gemv(g, s); });
     }
@@ -135,7 +132,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
 // rows at fp4_scale_stride(K)), no bias; norm_w: the RMSNorm fused in front (eps), or null
 GemvArgs packed(WeightKernel k, const bf16_t* x, int ldx, const bf16_t* norm_w, float eps, const bf16_t* res, int ldres, bf16_t* out, int ldo, int M, int N, int K, int epi) {
     const bool fp4 = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp4Thin || k == WeightKernel::Fp4Gemm;
-    return {x, nullptr, norm_w, nullptr, res, out, M, N, K, ldx, fp4 ? K / 2 : K, ldres, ldo, norm_w ? eps : 0.f, epi, 0, nullptr, nullptr, fp4_scale_stride(K)};
+    return {x, nullptr, norm_w, nullptr, res, out, M, N, K, ldx, fp4 ? K / 2 : K, ldres, ldo, norm_w ? eps : 0.f, epi, nullptr, nullptr, fp4_scale_stride(K)};
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
@@ -405,7 +402,7 @@ static int linear_fp4w(WeightKernel k, const void* A, const void* W4, const void
                        void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc, float eps, int epi, emu_stream_t s) {
     if (!A || !W4 || !scales || !C) return -22;
     return linear_w(k, {nullptr, nullptr, nullptr, U8(W4), U8(scales)},
-                    {B(A), nullptr, B(norm_w), B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, 0, nullptr, nullptr, lds}, S(s));
+                    {B(A), nullptr, B(norm_w), B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, eps, epi, nullptr, nullptr, lds}, S(s));
 }
 int emu_linear_fp4w_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int lds, int ldres, int ldc, float eps,

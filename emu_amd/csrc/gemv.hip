@@ -1,17 +1,23 @@
 // Decode-shape (M <= 16 rows) weight streams:  out[m, n] = epilogue( sum_k xeff[m, k] * W[n, k] )
 //
 // HBM-bound: every weight byte is read exactly once per call (PMC: traffic / algorithmic = 1.0013) with non-temporal
-// loads; the activations (a few KB) come from L1/L2.  The family, dispatched by launch_gemv():
-//   gemv_kernel      1..8 rows.  One 256-thread workgroup owns R (16/8/4/2) consecutive weight rows and splits K across its
+// loads; the activations (a few KB) come from L1/L2.  launch_gemv() is three steps: the shape of the argument block (GemvShape:
+// integers and flags), gemv_plan() -- the one place that decides the kernel family, its form, rows per workgroup, waves, trips, grid
+// -- and launch_planned(), which maps the plan's values to template arguments.  The planner is pure host arithmetic (no HIP call,
+// no global; the emu_gemm_tune mask is an argument), exported as emu_gemv_plan and held against recorded launches by
+// tests/test_gemv_plan.py; emu_gemv_geometry / emu_gemv_partition are views of the same plan.  The families:
+//   block (gemv_kernel)      1..8 rows.  One 256-thread workgroup owns R (16/8/4/2) consecutive weight rows and splits K across its
 //                    4 waves (thread t owns 16-byte vectors t, t+256, ...), N/R workgroups >> 256 CUs.  Inner product on
 //                    v_dot2c_f32_bf16 (weights consumed unpacked), wave reductions on DPP.  Optional fused prologue: LLaMA
 //                    RMSNorm of x (fp32 variance, the reference's bf16 rounding points: xeff = bf16(g * bf16(x * rinv))).
 //                    Fused epilogues: bias, residual add, SwiGLU over interleaved (gate, up) row pairs, SiLU, GELU.
-//   gemv_rt_kernel   M = 1, single HBM round trip per workgroup (all loads issued up front): down_proj, small shards.
-//   gemv_wave_kernel M = 1, K <= 2560: one wave per 4 whole rows, no LDS / barrier (TP-shard o_proj / down_proj).
-//   gemv_mfma_kernel 9..16 rows on v_mfma_f32_16x16x32_bf16.
-//   gemv_fp8_*       optional e4m3 weight stream (per-row scale).
-//   (gemv_fp4.hip)   optional MXFP4 weight stream (4-bit elements, one E8M0 scale per 32), M <= 2.
+//                    One row runs in one of three forms (GemvForm): head, preload, rolling loop.
+//   single round trip (gemv_rt_kernel)   M = 1, all loads of a workgroup issued up front: down_proj, small shards; bf16 or fp8.
+//   wave (gemv_wave_kernel)  M = 1, K <= 2560: one wave per 4 whole rows, no LDS / barrier (TP-shard o_proj / down_proj).
+//   register-fed MFMA (gemv_mfma_kernel)   9..16 rows on v_mfma_f32_16x16x32_bf16 where the thin stream does not apply.
+//   thin stream (gemv_thin.hip)            4..16 rows, K in whole 256-wide stages: LDS-DMA stages + MFMA.
+//   fp8 block (gemv_fp8_kernel)            optional e4m3 weight stream (per-row scale), 1..2 rows, 8- or 16-byte weight loads.
+//   MXFP4 rows (gemv_fp4.hip)              optional MXFP4 weight stream (4-bit elements, one E8M0 scale per 32), M <= 2.
 //
 // Replaces (reference call sites): LlamaDecoderLayer linears + RMSNorm reached from Emu2/emu/emu.py:133-138
 // and :213-229 at S=1 (greedy: 1 row; beam search: num_beams rows), project_up/project_down emu.py:131,147.
@@ -413,28 +419,6 @@ __global__ __launch_bounds__(256) void gemv_rt_kernel(const GemvArgs a) {
     if constexpr (!FP8) asm volatile("" :: "v"(warm));
 }
 
-template <int R, int KIT, bool FP8>
-int launch_rt(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + R - 1) / R), block(256);
-    const bool norm = a.norm_w != nullptr;
-#define EMU_RT_CASE(E)                                                                                               \
-    case E:                                                                                                          \
-        if (norm) hipLaunchKernelGGL((gemv_rt_kernel<R, KIT, true, E, FP8>), grid, block, 0, s, a);                  \
-        else hipLaunchKernelGGL((gemv_rt_kernel<R, KIT, false, E, FP8>), grid, block, 0, s, a);                      \
-        break;
-    switch (a.epi) {
-        EMU_RT_CASE(EPI_NONE)
-        EMU_RT_CASE(EPI_RESID)
-        EMU_RT_CASE(EPI_SWIGLU)
-        EMU_RT_CASE(EPI_SILU)
-        EMU_RT_CASE(EPI_GELU)
-        default: return -22;
-    }
-#undef EMU_RT_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
-
 // Short rows (K <= 2560: the o_proj / down_proj of a tensor-parallel shard, K = 896 / 2240 at TP = 8): splitting such
 // a row over 256 threads leaves most lanes idle and pays two barriers for a cross-wave sum.  Here every wave owns RW whole
 // rows -- all loads up front, v_dot2c, one DPP wave reduction, lane 0 stores -- no LDS, no barrier: the launch is pure
@@ -486,62 +470,6 @@ __global__ __launch_bounds__(256) void gemv_wave_kernel(const GemvArgs a) {
             }
         }
     }
-}
-
-// ---- which one-row (M = 1) shapes the wave form and the single-round-trip form take: pure integer rules, shared by the launchers
-// below and by emu_gemv_geometry (the successor's geometry for l2_warm.h comes from the same place as the launch).
-// wave form: 64-lane trips per row (1..5), or 0 when the shape is not covered (bf16 only)
-int gemv_wave_trips(int N, int K, bool norm, int epi) {
-    if (norm || (epi != EPI_NONE && epi != EPI_RESID)) return 0;
-    const int kitw = ((K >> 3) + 63) / 64;
-    return kitw > 5 || N < 1024 ? 0 : kitw;                          // K <= 2560; tiny N stays on the block kernels
-}
-// single-round-trip form: the built trip count (4 or 9) that holds the row, or 0 when the shape is not covered
-int gemv_rt_trips(int N, int K, bool norm, int epi, bool f8) {
-    if (epi == EPI_SWIGLU && (N & 1)) return 0;
-    const int kit = ((K >> 3) + 255) / 256;
-    if (f8 && (epi == EPI_SILU || epi == EPI_GELU)) return 0;
-    // measured (tools/kbench.py, profiles/r01_gemv_variants.log): one round trip wins for matrices small enough
-    // that latency, not bandwidth, sets the time (TP shards, tiny models) and for long rows without the RMSNorm
-    // prologue (down_proj: 6.3 vs 5.85 TB/s); big fused-norm matrices amortise the prologue better over 8 rows
-    const size_t bytes = (size_t)N * K * (f8 ? 1 : 2);
-    const bool small = bytes < ((size_t)(f8 ? 32 : 64) << 20);
-    const bool long_rows = !f8 && kit >= 5 && !norm;
-    if (!small && !long_rows) return 0;
-    return kit <= 4 ? 4 : kit <= 9 ? 9 : 0;
-}
-
-template <int RW, int KITW>
-int launch_wave(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + 4 * RW - 1) / (4 * RW)), block(256);
-    if (a.epi == EPI_RESID) hipLaunchKernelGGL((gemv_wave_kernel<RW, KITW, EPI_RESID>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((gemv_wave_kernel<RW, KITW, EPI_NONE>), grid, block, 0, s, a);
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
-
-// returns 1 when the shape is not covered
-int try_launch_wave(const GemvArgs& a, hipStream_t s) {
-    if (a.M != 1 || a.wscale) return 1;
-    const int kitw = gemv_wave_trips(a.N, a.K, a.norm_w != nullptr, a.epi);
-    if (!kitw) return 1;
-    switch (kitw) {
-        case 1: return launch_wave<4, 1>(a, s);
-        case 2: return launch_wave<4, 2>(a, s);
-        case 3: return launch_wave<4, 3>(a, s);
-        case 4: return launch_wave<4, 4>(a, s);
-        default: return launch_wave<4, 5>(a, s);
-    }
-}
-
-// M = 1 dispatch onto the single-round-trip kernel; returns 1 when the shape is not covered.
-int try_launch_rt(const GemvArgs& a, hipStream_t s) {
-    if (a.M != 1) return 1;
-    const bool f8 = a.wscale != nullptr;
-    const int kit = gemv_rt_trips(a.N, a.K, a.norm_w != nullptr, a.epi, f8);
-    if (kit == 4) return f8 ? launch_rt<8, 4, true>(a, s) : launch_rt<4, 4, false>(a, s);
-    if (kit == 9) return f8 ? launch_rt<4, 9, true>(a, s) : launch_rt<2, 9, false>(a, s);
-    return 1;
 }
 
 // Skinny-M weight stream on the matrix cores (2 <= M <= 16 rows: beam search, CFG pairs).  The FMA kernel above costs
@@ -650,40 +578,20 @@ __global__ __launch_bounds__(256) void gemv_mfma_kernel(const GemvArgs a) {
     }
 }
 
-template <int RG>
-int launch_gemv_mfma_rg(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + 16 * RG - 1) / (16 * RG)), block(256);
-#define EMU_MF_CASE(E) case E: hipLaunchKernelGGL((gemv_mfma_kernel<E, RG>), grid, block, 0, s, a); break;
-    switch (a.epi) {
-        EMU_MF_CASE(EPI_NONE)
-        EMU_MF_CASE(EPI_RESID)
-        EMU_MF_CASE(EPI_SWIGLU)
-        EMU_MF_CASE(EPI_SILU)
-        EMU_MF_CASE(EPI_GELU)
-        default: return -22;
-    }
-#undef EMU_MF_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
 
-int launch_gemv_mfma(const GemvArgs& a, hipStream_t s) {
-    // Row groups per workgroup (each activation fragment, re-read from L2, then serves RG weight fragments): measured
-    // flat at M = 5 (RG 1 / 2 / 4: 69.5 / 71.7 / 82.9 us on qkv), so the activation re-read is not what holds the kernel
-    // at 3.8 TB/s -- the 64-byte-per-row fragment loads are; RG = 1 keeps the most workgroups in flight.
-    return launch_gemv_mfma_rg<1>(a, s);
-}
-
-// fp8 (OCP e4m3fn) weight stream: half the HBM bytes per token.  One 16-byte load = 16 weights of one row; the per-row
-// fp32 scale is applied once to the fp32 dot product.  Same fused RMSNorm prologue / epilogues as the bf16 kernel.
-template <int R, int MB, bool NORM, int EPI, int NW>
+// fp8 (OCP e4m3fn) weight stream: half the HBM bytes per token.  One VB-byte load = VB weights of one row (16: long rows; 8: rows of
+// K <= 8192, where 16-byte groups would leave 3.25 trips per lane at K = 6656 to half the lanes); the per-row fp32 scale is applied
+// once to the fp32 dot product.  Same fused RMSNorm / epilogues as the bf16 kernel.
+template <int R, int MB, bool NORM, int EPI, int NW, int VB>
 __global__ __launch_bounds__(NW * 64) void gemv_fp8_kernel(const GemvArgs a) {
+    static_assert(VB == 8 || VB == 16, "one weight load is 8 or 16 bytes");
+    using WT = typename std::conditional<VB == 16, u32x4, u32x2>::type;
     __shared__ float red[NW][R * MB];
     __shared__ float red_ss[NW][MB];
     __shared__ float fin[R * MB];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
-    const int KV = a.K >> 4;                       // 16-element groups per row
+    const int KV = a.K >> (VB == 16 ? 4 : 3);      // VB-element groups per row
     const int n0 = blockIdx.x * R;
     const uint8_t* W8 = reinterpret_cast<const uint8_t*>(a.W);
     const uint8_t* wrow[R];
@@ -708,31 +616,34 @@ __global__ __launch_bounds__(NW * 64) void gemv_fp8_kernel(const GemvArgs a) {
 
 #pragma unroll 2
     for (int vi = tid; vi < KV; vi += NW * 64) {
-        u32x4 wv[R];
+        WT wv[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) wv[r] = ld_stream(reinterpret_cast<const u32x4*>(wrow[r] + vi * 16));
-        float xf[MB][16];
-        float g[16];
-        if constexpr (NORM) { unpack8(ld16(a.norm_w + vi * 16), g); unpack8(ld16(a.norm_w + vi * 16 + 8), g + 8); }
+        for (int r = 0; r < R; ++r) wv[r] = __builtin_nontemporal_load(reinterpret_cast<const WT*>(wrow[r] + vi * VB));
+        float xf[MB][VB];
+        float g[VB];
+        if constexpr (NORM) {
+            unpack8(ld16(a.norm_w + vi * VB), g);
+            if constexpr (VB == 16) unpack8(ld16(a.norm_w + vi * VB + 8), g + 8);
+        }
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
             if (m < a.M) {
-                unpack8(ld16(a.x + (size_t)m * a.ldx + vi * 16), xf[m]);
-                unpack8(ld16(a.x + (size_t)m * a.ldx + vi * 16 + 8), xf[m] + 8);
+                unpack8(ld16(a.x + (size_t)m * a.ldx + vi * VB), xf[m]);
+                if constexpr (VB == 16) unpack8(ld16(a.x + (size_t)m * a.ldx + vi * VB + 8), xf[m] + 8);
                 if constexpr (NORM) {
 #pragma unroll
-                    for (int j = 0; j < 16; ++j) { ss[m] = fmaf(xf[m][j], xf[m][j], ss[m]); xf[m][j] *= g[j]; }
+                    for (int j = 0; j < VB; ++j) { ss[m] = fmaf(xf[m][j], xf[m][j], ss[m]); xf[m][j] *= g[j]; }
                 }
             } else {
 #pragma unroll
-                for (int j = 0; j < 16; ++j) xf[m][j] = 0.f;
+                for (int j = 0; j < VB; ++j) xf[m][j] = 0.f;
             }
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            f32x2_t wf[8];                                            // v_cvt_pk_f32_fp8 pairs feed v_pk_fma_f32
+            f32x2_t wf[VB / 2];                                       // v_cvt_pk_f32_fp8 pairs feed v_pk_fma_f32
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = 0; q < VB / 4; ++q) {
                 wf[2 * q] = __builtin_amdgcn_cvt_pk_f32_fp8(wv[r][q], false);
                 wf[2 * q + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(wv[r][q], true);
             }
@@ -740,7 +651,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_fp8_kernel(const GemvArgs a) {
             for (int m = 0; m < MB; ++m) {
                 f32x2_t a2 = {0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < 8; ++j)
+                for (int j = 0; j < VB / 2; ++j)
                     a2 = __builtin_elementwise_fma(wf[j], f32x2_t{xf[m][2 * j], xf[m][2 * j + 1]}, a2);
                 acc[r][m] += a2[0] + a2[1];
             }
@@ -800,211 +711,223 @@ __global__ __launch_bounds__(NW * 64) void gemv_fp8_kernel(const GemvArgs a) {
     }
 }
 
-template <int R, int MB, bool NORM, int EPI, int NW>
-__global__ __launch_bounds__(NW * 64) void gemv_fp8v8_kernel(const GemvArgs a) {
-    __shared__ float red[NW][R * MB];
-    __shared__ float red_ss[NW][MB];
-    __shared__ float fin[R * MB];
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
-    const int KV = a.K >> 3;                       // 8-element groups per row (8-byte weight loads)
-    const int n0 = blockIdx.x * R;
-    const uint8_t* W8 = reinterpret_cast<const uint8_t*>(a.W);
-    const uint8_t* wrow[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        int n = n0 + r;
-        n = n < a.N ? n : a.N - 1;
-        wrow[r] = W8 + (size_t)n * a.ldw;
-    }
-    float ss[MB];                                  // sum of squares rides along the pass over x (see gemv_fp8_kernel)
-#pragma unroll
-    for (int m = 0; m < MB; ++m) ss[m] = 0.f;
-    float acc[R][MB];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int m = 0; m < MB; ++m) acc[r][m] = 0.f;
-
-#pragma unroll 2
-    for (int vi = tid; vi < KV; vi += NW * 64) {
-        u32x2 wv[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) wv[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wrow[r] + vi * 8));
-        float xf[MB][8];
-        float g[8];
-        if constexpr (NORM) unpack8(ld16(a.norm_w + vi * 8), g);
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            if (m < a.M) {
-                unpack8(ld16(a.x + (size_t)m * a.ldx + vi * 8), xf[m]);
-                if constexpr (NORM) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { ss[m] = fmaf(xf[m][j], xf[m][j], ss[m]); xf[m][j] *= g[j]; }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xf[m][j] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            f32x2_t wf[4];                                            // v_cvt_pk_f32_fp8 pairs feed v_pk_fma_f32
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                wf[2 * q] = __builtin_amdgcn_cvt_pk_f32_fp8(wv[r][q], false);
-                wf[2 * q + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(wv[r][q], true);
-            }
-#pragma unroll
-            for (int m = 0; m < MB; ++m) {
-                f32x2_t a2 = {0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    a2 = __builtin_elementwise_fma(wf[j], f32x2_t{xf[m][2 * j], xf[m][2 * j + 1]}, a2);
-                acc[r][m] += a2[0] + a2[1];
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            const float v = wave_sum(acc[r][m]);
-            if (lane == 0) red[wave][r * MB + m] = v;
-        }
-    if constexpr (NORM) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            const float v = wave_sum(ss[m]);
-            if (lane == 0) red_ss[wave][m] = v;
-        }
-    }
-    __syncthreads();
-    if (tid < R * MB) {
-        const int n = n0 + tid / MB;
-        float t = 0.f, rinv = 1.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) t += red[w][tid];
-        if constexpr (NORM) {
-            float q = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) q += red_ss[w][tid % MB];
-            rinv = rsqrtf(q / (float)a.K + a.eps);
-        }
-        fin[tid] = t * rinv * a.wscale[n < a.N ? n : a.N - 1];
-    }
-    __syncthreads();
-    if constexpr (EPI == EPI_SWIGLU) {
-        if (tid < (R / 2) * MB) {
-            const int j = tid / MB, m = tid % MB;
-            const int n = n0 + 2 * j;
-            if (m < a.M && n + 1 < a.N) {
-                const float gt = bfround(fin[(2 * j) * MB + m] + (a.bias ? bf2f(a.bias[n]) : 0.f));
-                const float up = bfround(fin[(2 * j + 1) * MB + m] + (a.bias ? bf2f(a.bias[n + 1]) : 0.f));
-                a.out[(size_t)m * a.ldo + (n >> 1)] = f2bf(bfround(silu(gt)) * up);
-            }
-        }
-    } else {
-        if (tid < R * MB) {
-            const int r = tid / MB, m = tid % MB;
-            const int n = n0 + r;
-            if (m < a.M && n < a.N) {
-                float v = fin[tid];
-                if (a.bias) v += bf2f(a.bias[n]);
-                v = bfround(v);
-                if constexpr (EPI == EPI_RESID) v = v + bf2f(a.res[(size_t)m * a.ldres + n]);
-                a.out[(size_t)m * a.ldo + n] = f2bf(v);
-            }
-        }
-    }
-}
-
-template <int R, int MB, int NW>
-int launch_fp8v8(const GemvArgs& a, hipStream_t s) {
-    static_assert(R * MB <= NW * 64, "epilogue needs one thread per (row, m)");
-    const dim3 grid((a.N + R - 1) / R), block(NW * 64);
-    const bool norm = a.norm_w != nullptr;
-#define EMU_FP8_CASE(E)                                                                                              \
-    case E:                                                                                                          \
-        if (norm) hipLaunchKernelGGL((gemv_fp8v8_kernel<R, MB, true, E, NW>), grid, block, 0, s, a);                 \
-        else hipLaunchKernelGGL((gemv_fp8v8_kernel<R, MB, false, E, NW>), grid, block, 0, s, a);                     \
-        break;
-    switch (a.epi) {
-        EMU_FP8_CASE(EPI_NONE)
-        EMU_FP8_CASE(EPI_RESID)
-        EMU_FP8_CASE(EPI_SWIGLU)
-        default: return -22;
-    }
-#undef EMU_FP8_CASE
-    EMU_CHECK_LAUNCH();
+// ---- the launchers: plan values -> template arguments.  Grid and workgroup size come from the plan; nothing below tests a shape.
+#define EMU_EPI_LAUNCH(...)                                                                                          \
+    switch (a.epi) {                                                                                                 \
+        __VA_ARGS__                                                                                                  \
+        default: return -22;                                                                                         \
+    }                                                                                                                \
+    EMU_CHECK_LAUNCH();                                                                                              \
     return 0;
-}
-
-template <int R, int MB, int NW>
-int launch_fp8(const GemvArgs& a, hipStream_t s) {
-    static_assert(R * MB <= NW * 64, "epilogue needs one thread per (row, m)");
-    const dim3 grid((a.N + R - 1) / R), block(NW * 64);
-    const bool norm = a.norm_w != nullptr;
-#define EMU_FP8_CASE(E)                                                                                              \
-    case E:                                                                                                          \
-        if (norm) hipLaunchKernelGGL((gemv_fp8_kernel<R, MB, true, E, NW>), grid, block, 0, s, a);                       \
-        else hipLaunchKernelGGL((gemv_fp8_kernel<R, MB, false, E, NW>), grid, block, 0, s, a);                           \
-        break;
-    switch (a.epi) {
-        EMU_FP8_CASE(EPI_NONE)
-        EMU_FP8_CASE(EPI_RESID)
-        EMU_FP8_CASE(EPI_SWIGLU)
-        default: return -22;
-    }
-#undef EMU_FP8_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
+#define EMU_EPI3(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU))
+#define EMU_EPI5(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU) CASE(EPI_SILU) CASE(EPI_GELU))
 
 template <int R, int MB, bool NORM, int PRE>
-int launch_epi(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + R - 1) / R), block(256);
-    switch (a.epi) {
-        case EPI_NONE:   hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, EPI_NONE, PRE>), grid, block, 0, s, a); break;
-        case EPI_RESID:  hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, EPI_RESID, PRE>), grid, block, 0, s, a); break;
-        case EPI_SWIGLU: hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, EPI_SWIGLU, PRE>), grid, block, 0, s, a); break;
-        case EPI_SILU:   hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, EPI_SILU, PRE>), grid, block, 0, s, a); break;
-        case EPI_GELU:   hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, EPI_GELU, PRE>), grid, block, 0, s, a); break;
+int launch_block_epi(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+#define EMU_CASE(E) case E: hipLaunchKernelGGL((gemv_kernel<R, MB, NORM, E, PRE>), dim3(p.grid), dim3(p.block), 0, s, a); break;
+    EMU_EPI5(EMU_CASE)
+#undef EMU_CASE
+}
+
+// the block kernel's form as the template pair (NORM, PRE): preload = (false, 4), head = (true, -1), rolling = (norm, 0)
+template <int R, int MB>
+int launch_block(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+    if (p.form == GEMV_FORM_PRELOAD) {
+        if constexpr (MB == 1 && R <= 4) return launch_block_epi<R, MB, false, 4>(p, a, s);       // register budget: PRE * R * 4 VGPRs
+    } else if (p.form == GEMV_FORM_HEAD) {
+        if constexpr (MB == 1) return launch_block_epi<R, MB, true, -1>(p, a, s);
+    } else if (p.form == GEMV_FORM_ROLLING) {
+        return a.norm_w ? launch_block_epi<R, MB, true, 0>(p, a, s) : launch_block_epi<R, MB, false, 0>(p, a, s);
+    }
+    return -22;
+}
+
+template <int R>
+int launch_block_rows(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+    switch (p.mb) {
+        case 1: return launch_block<R, 1>(p, a, s);
+        case 2: return launch_block<R, 2>(p, a, s);
+        case 3: return launch_block<R, 3>(p, a, s);
+        case 4: return launch_block<R, 4>(p, a, s);
+        case 5: return launch_block<R, 5>(p, a, s);           // 5 beams: the reference's default decoding mode
+        case 8: return launch_block<R, 8>(p, a, s);
         default: return -22;
     }
+}
+
+template <int R, int KIT, bool FP8>
+int launch_rt(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+#define EMU_CASE(E)                                                                                                              \
+    case E:                                                                                                                      \
+        if (a.norm_w) hipLaunchKernelGGL((gemv_rt_kernel<R, KIT, true, E, FP8>), dim3(p.grid), dim3(p.block), 0, s, a);          \
+        else hipLaunchKernelGGL((gemv_rt_kernel<R, KIT, false, E, FP8>), dim3(p.grid), dim3(p.block), 0, s, a);                  \
+        break;
+    EMU_EPI5(EMU_CASE)
+#undef EMU_CASE
+}
+
+template <int KITW>
+int launch_wave(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+    if (a.epi == EPI_RESID) hipLaunchKernelGGL((gemv_wave_kernel<4, KITW, EPI_RESID>), dim3(p.grid), dim3(p.block), 0, s, a);
+    else hipLaunchKernelGGL((gemv_wave_kernel<4, KITW, EPI_NONE>), dim3(p.grid), dim3(p.block), 0, s, a);
     EMU_CHECK_LAUNCH();
     return 0;
 }
 
-// the form of the one-row block kernel for R rows per workgroup (launch_norm below)
+// Row groups per workgroup (each activation fragment, re-read from L2, then serves RG weight fragments): measured flat at M = 5
+// (RG 1 / 2 / 4: 69.5 / 71.7 / 82.9 us on qkv), so the activation re-read is not what holds the kernel at 3.8 TB/s -- the
+// 64-byte-per-row fragment loads are; RG = 1 keeps the most workgroups in flight.
+int launch_mfma(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+#define EMU_CASE(E) case E: hipLaunchKernelGGL((gemv_mfma_kernel<E, 1>), dim3(p.grid), dim3(p.block), 0, s, a); break;
+    EMU_EPI5(EMU_CASE)
+#undef EMU_CASE
+}
+
+template <int R, int MB, int NW, int VB>
+int launch_fp8(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+    static_assert(R * MB <= NW * 64, "epilogue needs one thread per (row, m)");
+#define EMU_CASE(E)                                                                                                              \
+    case E:                                                                                                                      \
+        if (a.norm_w) hipLaunchKernelGGL((gemv_fp8_kernel<R, MB, true, E, NW, VB>), dim3(p.grid), dim3(p.block), 0, s, a);       \
+        else hipLaunchKernelGGL((gemv_fp8_kernel<R, MB, false, E, NW, VB>), dim3(p.grid), dim3(p.block), 0, s, a);               \
+        break;
+    EMU_EPI3(EMU_CASE)
+#undef EMU_CASE
+}
+
+int launch_planned(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
+    if (p.status) return p.status;
+    switch (p.family) {
+        case GEMV_FAM_BLOCK:
+            switch (p.rows) {
+                case 2: return launch_block_rows<2>(p, a, s);
+                case 4: return launch_block_rows<4>(p, a, s);
+                case 8: return launch_block_rows<8>(p, a, s);
+                case 16: return p.mb == 1 ? launch_block<16, 1>(p, a, s) : -22;    // 16 rows only pay at one row (accumulator registers)
+                default: return -22;
+            }
+        case GEMV_FAM_RT: return p.trips == 4 ? launch_rt<4, 4, false>(p, a, s) : launch_rt<2, 9, false>(p, a, s);
+        case GEMV_FAM_FP8_RT: return p.trips == 4 ? launch_rt<8, 4, true>(p, a, s) : launch_rt<4, 9, true>(p, a, s);
+        case GEMV_FAM_WAVE:
+            switch (p.trips) {
+                case 1: return launch_wave<1>(p, a, s);
+                case 2: return launch_wave<2>(p, a, s);
+                case 3: return launch_wave<3>(p, a, s);
+                case 4: return launch_wave<4>(p, a, s);
+                case 5: return launch_wave<5>(p, a, s);
+                default: return -22;
+            }
+        case GEMV_FAM_MFMA: return launch_mfma(p, a, s);
+        case GEMV_FAM_THIN: return launch_gemv_thin(a, p, s);
+        case GEMV_FAM_FP8_BLOCK:
+            if (p.vb == 8) return p.mb == 1 ? launch_fp8<8, 1, 4, 8>(p, a, s) : launch_fp8<8, 2, 4, 8>(p, a, s);
+            if (p.mb == 1) return p.waves == 2 ? launch_fp8<4, 1, 2, 16>(p, a, s) : launch_fp8<4, 1, 4, 16>(p, a, s);
+            return p.rows == 4 ? launch_fp8<4, 2, 2, 16>(p, a, s) : launch_fp8<8, 2, 2, 16>(p, a, s);
+        case GEMV_FAM_FP4_ROWS: return launch_gemv_fp4(a, p, s);
+        default: return -22;
+    }
+}
+
+// ---- the planner: every decision between a shape and a launch, in integers.  No HIP call, no global; the tune mask (emu_gemm_tune)
+// is an argument.  tests/test_gemv_plan.py holds its answers against the launches recorded before it existed.
+
+// the one-row wave form's 64-lane trips per row (1..5), or 0 when the shape is not covered
+int gemv_wave_trips(int N, int K, bool norm, int epi) {
+    if (norm || (epi != EPI_NONE && epi != EPI_RESID)) return 0;
+    const int kitw = ((K >> 3) + 63) / 64;
+    return kitw > 5 || N < 1024 ? 0 : kitw;                          // K <= 2560; tiny N stays on the block kernels
+}
+// the single-round-trip form's built trip count (4 or 9) that holds the row, or 0 when the shape is not covered
+int gemv_rt_trips(int N, int K, bool norm, int epi, bool f8) {
+    if (epi == EPI_SWIGLU && (N & 1)) return 0;
+    const int kit = ((K >> 3) + 255) / 256;
+    if (f8 && (epi == EPI_SILU || epi == EPI_GELU)) return 0;
+    // measured (tools/kbench.py, profiles/r01_gemv_variants.log): one round trip wins for matrices small enough
+    // that latency, not bandwidth, sets the time (TP shards, tiny models) and for long rows without the RMSNorm
+    // prologue (down_proj: 6.3 vs 5.85 TB/s); big fused-norm matrices amortise the prologue better over 8 rows
+    const size_t bytes = (size_t)N * K * (f8 ? 1 : 2);
+    const bool small = bytes < ((size_t)(f8 ? 32 : 64) << 20);
+    const bool long_rows = !f8 && kit >= 5 && !norm;
+    if (!small && !long_rows) return 0;
+    return kit <= 4 ? 4 : kit <= 9 ? 9 : 0;
+}
+// the form of the one-row block kernel for R rows per workgroup.  The preload form wins only for plain streams (o_proj); with the
+// RMSNorm prologue it loses 20 % (clamped tail chunks + lower occupancy), so those take the head form or the rolling loop.
 int gemv_block_form(int R, int K, bool norm) {
     if (!norm && R <= 4 && (K >> 3) <= 1024) return GEMV_FORM_PRELOAD;
     if (norm && (K >> 3) <= 1024) return GEMV_FORM_HEAD;
     return GEMV_FORM_ROLLING;
 }
-
-template <int R, int MB>
-int launch_norm(const GemvArgs& a, hipStream_t s) {
-    // the preload-everything form only for the single-row decode case (register budget: PRE*R*4 VGPRs)
-    // measured: the preload form wins only for plain streams (o_proj); with the RMSNorm prologue it loses 20 %
-    // (clamped tail chunks + lower occupancy), so those keep the rolling loop.
-    if constexpr (MB == 1 && R <= 4) {
-        if (gemv_block_form(R, a.K, a.norm_w != nullptr) == GEMV_FORM_PRELOAD) return launch_epi<R, MB, false, 4>(a, s);
-    }
-    if constexpr (MB == 1) {
-        if (gemv_block_form(R, a.K, a.norm_w != nullptr) == GEMV_FORM_HEAD) return launch_epi<R, MB, true, -1>(a, s);
-    }
-    return a.norm_w ? launch_epi<R, MB, true, 0>(a, s) : launch_epi<R, MB, false, 0>(a, s);
+// rows per workgroup for 2..8 activation rows (beam search, CFG pairs): 8 amortises the activation unpack best
+int gemv_rows_per_block_multi(int N) {
+    int R = 8;
+    while (R > 2 && (N + R - 1) / R < 512) R >>= 1;
+    return R;
 }
 
-template <int R>
-int launch_mb(const GemvArgs& a, hipStream_t s) {
-    if (a.M <= 1) return launch_norm<R, 1>(a, s);
-    if (a.M <= 2) return launch_norm<R, 2>(a, s);
-    if (a.M <= 3) return launch_norm<R, 3>(a, s);
-    if (a.M <= 4) return launch_norm<R, 4>(a, s);
-    if (a.M <= 5) return launch_norm<R, 5>(a, s);             // 5 beams: the reference's default decoding mode
-    return launch_norm<R, 8>(a, s);
+GemvPlan planned(const GemvShape& sh, int family, int form, int rows, int mb, int waves, int trips) {
+    GemvPlan p{};
+    p.family = family; p.form = form; p.rows = rows; p.mb = mb; p.waves = waves; p.trips = trips;
+    p.grid = (sh.N + rows - 1) / rows; p.block = 64 * waves;
+    p.partition = family == GEMV_FAM_WAVE ? 1 : family == GEMV_FAM_BLOCK || family == GEMV_FAM_RT || family == GEMV_FAM_FP8_RT ? 4 : 0;
+    return p;
+}
+
+// one bf16 row, the arguments checked by the caller: wave form, single round trip, or the block kernel in one of its three forms
+// (emu_gemm_tune bit 17, tests: no wave / single-round-trip form, so small matrices reach the block kernel's head and preload forms)
+GemvPlan plan_one_row(const GemvShape& sh, int tune) {
+    const bool norm = sh.norm != 0, block_only = (tune & (1 << 17)) != 0;
+    if (const int kitw = block_only ? 0 : gemv_wave_trips(sh.N, sh.K, norm, sh.epi))
+        return planned(sh, GEMV_FAM_WAVE, GEMV_FORM_WAVE, 16, 1, 4, kitw);         // 4 waves x 4 whole rows
+    if (const int kit = block_only ? 0 : gemv_rt_trips(sh.N, sh.K, norm, sh.epi, false))
+        return planned(sh, GEMV_FAM_RT, GEMV_FORM_RT, kit == 4 ? 4 : 2, 1, 4, kit);
+    const int R = emu_gemv_rows_per_block(sh.N, sh.K, norm);
+    const int form = gemv_block_form(R, sh.K, norm);
+    return planned(sh, GEMV_FAM_BLOCK, form, R, 1, 4, form == GEMV_FORM_PRELOAD ? 4 : form == GEMV_FORM_HEAD ? -1 : 0);
+}
+
+// 2..16 rows through LDS-DMA stages (gemv_thin.hip): whole 256-wide k stages, no fused norm, bf16 weights, 16-byte aligned operands
+bool gemv_thin_ok(const GemvShape& sh) {
+    return sh.M >= 2 && sh.M <= 16 && !sh.norm && !sh.fp8 && sh.K >= 256 && (sh.K % 256) == 0 && (sh.ldw & 7) == 0 && (sh.ldx & 7) == 0 &&
+           sh.w_aligned && sh.x_aligned;
+}
+// 16 weight rows per workgroup (three co-resident workgroups per CU at <= 8 rows): measured at 5 rows against 32-row
+// workgroups and 512-k stages (tools/thin_ab.py, profiles/r03_thin_stream_ab.log): qkv 42.1 vs 45.5 / 47.1 us.
+// emu_gemm_tune bits 8-11 pick the other variants (A/B aid).
+GemvPlan plan_thin(const GemvShape& sh, int tune) {
+    const int variant = (tune >> 8) & 15;
+    const bool rows8 = sh.M <= 8;
+    int rn = 16, nstg = 4, kch = 32;
+    if (variant == 1 && (sh.N + 31) / 32 >= 512) { rn = 32; nstg = 3; }
+    else if (variant == 2) nstg = rows8 ? 6 : 3;
+    else if (variant == 3 && rows8 && sh.K % 512 == 0) { nstg = 3; kch = 64; }
+    GemvPlan p = planned(sh, GEMV_FAM_THIN, 0, rn, rows8 ? 8 : 16, 4, 0);
+    p.stages = nstg; p.kch = kch;
+    return p;
+}
+
+// the MXFP4 weight stream (gemv_fp4.hip): 16-byte loads of whole blocks, 32-bit row offsets; emu_gemm_tune bits 24-25 set the row
+// sets per workgroup, bits 26-27 the weight rows per lane
+GemvPlan plan_fp4_rows(const GemvShape& sh, int tune) {
+    GemvPlan refused{};
+    refused.status = -22;
+    if (sh.M < 1 || sh.M > 2 || sh.N < 1 || sh.K < 32 || (sh.K & 31)) return refused;
+    if ((sh.ldw & 15) || (sh.ldx & 7) || sh.ldw < sh.K / 2 || sh.lds < sh.K / 32) return refused;
+    if (sh.epi != EPI_NONE && sh.epi != EPI_RESID && sh.epi != EPI_SWIGLU) return refused;
+    if (sh.epi == EPI_SWIGLU && (sh.N & 1)) return refused;
+    int tpr, rs;
+    plan_fp4(sh.K >> 5, &tpr, &rs);
+    if ((tune >> 24) & 3) rs = 1 << (((tune >> 24) & 3) - 1);
+    if (rs > GEMV_FP4_MAX_SETS || rs * tpr > 1024) return refused;
+    if ((size_t)sh.N * sh.ldw > 0xffffffffull || (size_t)sh.N * sh.lds > 0xffffffffull) return refused;
+    // one row: 8 weight rows per lane share one unpack of the activations, where the grid still covers the device with them; two
+    // rows keep 4 (the accumulators and activations of 8 x 2 do not fit the 128 registers of a 13-wave workgroup)
+    const bool wide = (sh.N + rs * 8 - 1) / (rs * 8) >= 128;
+    const int asked = 4 * ((tune >> 26) & 3);
+    const int rpl = sh.M > 1 || asked == 4 || (!wide && asked != 8) ? 4 : 8;
+    GemvPlan p = planned(sh, GEMV_FAM_FP4_ROWS, 0, rs * rpl, sh.M, (tpr * rs + 63) / 64, 0);   // lanes beyond the last row set idle
+    p.tpr = tpr; p.row_sets = rs; p.rpl = rpl;
+    return p;
 }
 
 }  // namespace
@@ -1019,71 +942,71 @@ int emu_gemv_rows_per_block(int N, int K, bool norm) {
     return R;
 }
 
-// rows per workgroup for 2..8 activation rows (beam search, CFG pairs): 8 amortises the activation unpack best
-int emu_gemv_rows_per_block_multi(int N) {
-    int R = 8;
-    while (R > 2 && (N + R - 1) / R < 512) R >>= 1;
-    return R;
+bool gemv_rows_9_16_ok(int M, int K, int ldx, int ldw, bool norm, bool fp8, int epi) {
+    return M > 8 && M <= 16 && !norm && !fp8 && (K & 31) == 0 && (ldw & 7) == 0 && (ldx & 7) == 0 && epi >= EPI_NONE && epi <= EPI_GELU;
 }
 
-GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi) {
-    // (emu_gemm_tune bit 17, tests: no wave / single-round-trip form, so small matrices reach the block kernels' head and preload forms)
-    const bool block_only = (emu_gemm_tune_get() & (1 << 17)) != 0;
-    if (!block_only && gemv_wave_trips(N, K, norm, epi)) return {GEMV_FORM_WAVE, 16};
-    if (const int kit = block_only ? 0 : gemv_rt_trips(N, K, norm, epi, false)) return {GEMV_FORM_RT, kit == 4 ? 4 : 2};
-    const int R = emu_gemv_rows_per_block(N, K, norm);
-    return {gemv_block_form(R, K, norm), R};
-}
-
-int emu_gemv_partition(int N, int K, bool norm, int epi) {
-    // try_launch_wave's conditions (M = 1, bf16): no fused norm, EPI_NONE / EPI_RESID, K <= 2560, N >= 1024
-    const int kitw = ((K >> 3) + 63) / 64;
-    if (!norm && (epi == EPI_NONE || epi == EPI_RESID) && kitw <= 5 && N >= 1024) return 1;
-    return 4;                                  // gemv_rt_kernel and gemv_kernel alike: thread t owns 16-byte columns t, t + 256, ...
-}
-
-int launch_gemv(const GemvArgs& a, hipStream_t s) {
-    if (a.w4scale) return a.wscale ? -22 : launch_gemv_fp4(a, s);     // MXFP4 weight stream (gemv_fp4.hip)
-    if (a.M < 1 || a.M > 16 || (a.K & 7) || a.N < 1) return -22;
-    if (a.epi == EPI_SWIGLU && (a.N & 1)) return -22;
-    // 9..16 rows: the 16x16x32 MFMA stream.  Up to 8 rows the v_dot2c block kernel is faster (M = 2: 6.4 vs 4.1 TB/s,
-    // M = 5: 4.5 vs 3.9, M = 8: 3.7 vs 3.5; tools/kbench.py --filter rows): its row-contiguous 1 KiB loads use HBM better
-    // than the MFMA fragment's 64 bytes per row.
+GemvPlan gemv_plan(const GemvShape& sh, int tune) {
+    GemvPlan refused{};
+    refused.status = -22;
+    const bool norm = sh.norm != 0, f8 = sh.fp8 != 0;
+    if (sh.fp4) return f8 ? refused : plan_fp4_rows(sh, tune);
+    if (sh.M < 1 || sh.M > 16 || (sh.K & 7) || sh.N < 1) return refused;
+    if (sh.epi < EPI_NONE || sh.epi > (f8 ? EPI_SWIGLU : EPI_GELU)) return refused;
+    if (sh.epi == EPI_SWIGLU && (sh.N & 1)) return refused;
     // 4..16 rows with whole 256-wide k stages: LDS-DMA stages + MFMA (gemv_thin.hip).  Measured on the LLaMA-33B shapes
     // (tools/thin_ab.py, profiles/r03_thin_stream_ab.log): 5 rows 42.7 / 17.9 / 74.6 / 42.6 us (qkv / o / gate-up / down) against
-    // 46.4 / 21.7 / 77.4 / 47.6 on the v_dot2c kernel below, 8 rows 43.7 vs 60.7, 16 rows 49.2 vs 92.0 (register-fed MFMA); at 2-3
+    // 46.4 / 21.7 / 77.4 / 47.6 on the v_dot2c kernel, 8 rows 43.7 vs 60.7, 16 rows 49.2 vs 92.0 (register-fed MFMA); at 2-3
     // rows the v_dot2c kernel is level or ahead (qkv 40.6 vs 41.0).  emu_gemm_tune bit 2 switches it off (A/B).
-    if (a.M >= 4 && !(emu_gemm_tune_get() & 4) && gemv_thin_ok(a)) return launch_gemv_thin(a, s);
-    if (a.M > 8 && !a.wscale && !a.norm_w && (a.K & 31) == 0 && (a.ldw & 7) == 0 &&
-        (a.ldx & 7) == 0)
-        return launch_gemv_mfma(a, s);
-    if (a.M > 8) return -22;
-    if (a.wscale && ((a.K & 15) || a.M > 2)) return -22;
-    if (a.M == 1 && !a.wscale) {                     // one bf16 row: the form and the rows per workgroup from emu_gemv_geometry
-        const GemvGeom g = emu_gemv_geometry(a.N, a.K, a.norm_w != nullptr, a.epi);
-        if (g.form == GEMV_FORM_WAVE) return try_launch_wave(a, s);
-        if (g.form == GEMV_FORM_RT) return try_launch_rt(a, s);
-    } else {
-        const int st = try_launch_rt(a, s);          // (fp8 rows; the launcher refuses M > 1)
-        if (st != 1) return st;
+    if (sh.M >= 4 && !(tune & 4) && gemv_thin_ok(sh)) return plan_thin(sh, tune);
+    // 9..16 rows: the register-fed 16x16x32 MFMA stream.  Up to 8 rows the v_dot2c block kernel is faster (M = 2: 6.4 vs 4.1 TB/s,
+    // M = 5: 4.5 vs 3.9, M = 8: 3.7 vs 3.5; tools/kbench.py --filter rows): its row-contiguous 1 KiB loads use HBM better
+    // than the MFMA fragment's 64 bytes per row.
+    if (sh.M > 8)
+        return gemv_rows_9_16_ok(sh.M, sh.K, sh.ldx, sh.ldw, norm, f8, sh.epi) ? planned(sh, GEMV_FAM_MFMA, 0, 16, 16, 4, 0) : refused;
+    if (f8) {                                        // fp8 weight stream (decode, batch <= 2 built)
+        if ((sh.K & 15) || sh.M > 2) return refused;
+        if (const int kit = sh.M == 1 ? gemv_rt_trips(sh.N, sh.K, norm, sh.epi, true) : 0)
+            return planned(sh, GEMV_FAM_FP8_RT, GEMV_FORM_RT, kit == 4 ? 8 : 4, 1, 4, kit);
+        // K = 6656 is only 416 16-byte groups, so rows of K <= 8192 take 8-byte loads on 4-wave blocks (3.25 trips per lane, like
+        // the bf16 kernel); longer rows 16-byte loads: one row 4 rows x 4 waves (down_proj: 21.8 vs 23.1 us), few workgroups 2 waves
+        GemvPlan p;
+        if (sh.K <= 8192) p = planned(sh, GEMV_FAM_FP8_BLOCK, 0, 8, sh.M, 4, 0);
+        else {
+            const bool small = (sh.N + 7) / 8 < 512;
+            p = planned(sh, GEMV_FAM_FP8_BLOCK, 0, small || sh.M == 1 ? 4 : 8, sh.M, sh.M == 1 && !small ? 4 : 2, 0);
+        }
+        p.vb = sh.K <= 8192 ? 8 : 16;
+        return p;
     }
-    if (a.wscale) {                                  // fp8 weight stream (decode, batch <= 2 built)
-        // 16 weights per 16-byte load: K = 6656 is only 416 groups, so short rows run 2-wave blocks (3.25 trips per
-        // lane, like the bf16 kernel) and long rows (down_proj, K = 17920) 4-wave blocks
-        if (a.K <= 8192) return a.M <= 1 ? launch_fp8v8<8, 1, 4>(a, s) : launch_fp8v8<8, 2, 4>(a, s);   // 8-byte loads: 3.25 trips per lane at K = 6656
-        const bool small = (a.N + 7) / 8 < 512;
-        if (a.M <= 1) return small ? launch_fp8<4, 1, 2>(a, s) : launch_fp8<4, 1, 4>(a, s);   // down_proj: 4 rows x 4 waves (21.8 vs 23.1 us)
-        return small ? launch_fp8<4, 2, 2>(a, s) : launch_fp8<8, 2, 2>(a, s);
-    }
-    int R = a.rows_per_block > 0 ? a.rows_per_block
-                                 : (a.M > 1 ? emu_gemv_rows_per_block_multi(a.N)
-                                            : emu_gemv_rows_per_block(a.N, a.K, a.norm_w != nullptr));
-    if (a.M > 1 && R > 8) R = 8;                   // 16 rows per workgroup only pays at M = 1 (accumulator registers)
-    switch (R) {
-        case 2: return launch_mb<2>(a, s);
-        case 4: return launch_mb<4>(a, s);
-        case 8: return launch_mb<8>(a, s);
-        case 16: return a.M <= 1 ? launch_norm<16, 1>(a, s) : launch_mb<8>(a, s);
-        default: return -22;
-    }
+    if (sh.M == 1) return plan_one_row(sh, tune);
+    return planned(sh, GEMV_FAM_BLOCK, GEMV_FORM_ROLLING, gemv_rows_per_block_multi(sh.N), sh.M <= 5 ? sh.M : 8, 4, 0);
+}
+
+// the one-row views of the plan (the successor's geometry for l2_warm.h and the persistent engine's column partition come from the
+// same place as the launch)
+static GemvPlan one_row_view(int N, int K, bool norm, int epi) {
+    GemvShape sh{};
+    sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm; sh.w_aligned = sh.x_aligned = 1;
+    return plan_one_row(sh, emu_gemm_tune_get());
+}
+GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi) {
+    const GemvPlan p = one_row_view(N, K, norm, epi);
+    return {p.form, p.rows};
+}
+int emu_gemv_partition(int N, int K, bool norm, int epi) { return one_row_view(N, K, norm, epi).partition; }
+
+int launch_gemv(const GemvArgs& a, hipStream_t s) {
+    GemvShape sh{};
+    sh.M = a.M; sh.N = a.N; sh.K = a.K; sh.ldx = a.ldx; sh.ldw = a.ldw; sh.lds = a.lds; sh.epi = a.epi;
+    sh.norm = a.norm_w != nullptr; sh.fp8 = a.wscale != nullptr; sh.fp4 = a.w4scale != nullptr;
+    sh.w_aligned = (reinterpret_cast<size_t>(a.W) & 15) == 0; sh.x_aligned = (reinterpret_cast<size_t>(a.x) & 15) == 0;
+    return launch_planned(gemv_plan(sh, emu_gemm_tune_get()), a, s);
+}
+
+// C-ABI test hook (include/emu_hip.h)
+int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
+    if (!shape || !out) return -22;
+    *out = gemv_plan(*shape, tune);
+    return out->status;
 }

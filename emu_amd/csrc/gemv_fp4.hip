@@ -24,13 +24,11 @@
 
 namespace {
 
-constexpr int FP4_MAX_SETS = 16;
-
 template <int R, int MB, bool NORM, int EPI>
 __global__ __launch_bounds__(1024) void gemv_fp4_kernel(const GemvArgs a, const int tpr, const int rs) {
     __shared__ float red[64][R * MB];              // one slot per 16-lane row of the workgroup (<= 1024 / 16)
     __shared__ float red_ss[64][MB];
-    __shared__ float fin[FP4_MAX_SETS * R * MB];
+    __shared__ float fin[GEMV_FP4_MAX_SETS * R * MB];
     const int tid = threadIdx.x;
     const int grp = tid >> 4, gpt = tpr >> 4;      // 16-lane row of this thread; 16-lane rows per row set
     const int set = grp / gpt;
@@ -157,9 +155,10 @@ __global__ __launch_bounds__(1024) void gemv_fp4_kernel(const GemvArgs a, const 
 }
 
 template <int R, int MB>
-int launch_fp4(const GemvArgs& a, int tpr, int rs, hipStream_t s) {
-    const dim3 grid((a.N + rs * R - 1) / (rs * R)), block((tpr * rs + 63) / 64 * 64);     // lanes beyond the last row set idle
+int launch_fp4(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    const dim3 grid(p.grid), block(p.block);
     const bool norm = a.norm_w != nullptr;
+    const int tpr = p.tpr, rs = p.row_sets;
 #define EMU_FP4_CASE(E)                                                                                              \
     case E:                                                                                                          \
         if (norm) hipLaunchKernelGGL((gemv_fp4_kernel<R, MB, true, E>), grid, block, 0, s, a, tpr, rs);              \
@@ -245,23 +244,10 @@ void plan_fp4(int KB, int* tpr_out, int* rs_out) {
     *tpr_out = tpr; *rs_out = rs;
 }
 
-int launch_gemv_fp4(const GemvArgs& a, hipStream_t s) {
-    if (!a.w4scale || a.M < 1 || a.M > 2 || a.N < 1 || a.K < 32 || (a.K & 31)) return -22;
-    if ((a.ldw & 15) || (a.ldx & 7) || a.ldw < a.K / 2 || a.lds < a.K / 32) return -22;   // 16-byte loads of whole blocks
-    if (a.epi == EPI_SWIGLU && (a.N & 1)) return -22;
-    int tpr, rs;
-    plan_fp4(a.K >> 5, &tpr, &rs);
-    const int tune = emu_gemm_tune_get();          // A/B switches (include/emu_hip.h: emu_gemm_tune bits 24-27)
-    if ((tune >> 24) & 3) rs = 1 << (((tune >> 24) & 3) - 1);
-    if (rs > FP4_MAX_SETS || rs * tpr > 1024) return -22;
-    if ((size_t)a.N * a.ldw > 0xffffffffull || (size_t)a.N * a.lds > 0xffffffffull) return -22;    // 32-bit row offsets
-    // one row: 8 weight rows per lane share one unpack of the activations, where the grid still covers the device with them; two
-    // rows keep 4 (the accumulators and activations of 8 x 2 do not fit the 128 registers of a 13-wave workgroup)
-    if (a.M > 1) return launch_fp4<4, 2>(a, tpr, rs, s);
-    const bool wide = (a.N + rs * 8 - 1) / (rs * 8) >= 128;
-    const int rows = (tune >> 26) & 3 ? 4 * ((tune >> 26) & 3) : a.rows_per_block;
-    if (rows == 4 || (!wide && rows != 8)) return launch_fp4<4, 1>(a, tpr, rs, s);
-    return launch_fp4<8, 1>(a, tpr, rs, s);
+// (weight rows per lane, built activation rows) of a plan of this family (gemv.hip::plan_fp4_rows)
+int launch_gemv_fp4(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    if (p.mb == 2) return p.rpl == 4 ? launch_fp4<4, 2>(a, p, s) : -22;
+    return p.rpl == 4 ? launch_fp4<4, 1>(a, p, s) : p.rpl == 8 ? launch_fp4<8, 1>(a, p, s) : -22;
 }
 
 int launch_quant_mxfp4_rows(const bf16_t* w, int ldw, uint8_t* q, int ldq, uint8_t* scales, int lds, int N, int K, hipStream_t s) {

@@ -142,9 +142,8 @@ __global__ __launch_bounds__(256) void thin_stream_kernel(const GemvArgs a) {
 }
 
 template <int RN, int MR, int NSTG, int KCH>
-int launch_thin(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + RN - 1) / RN), block(256);
-#define EMU_TH_CASE(E) case E: hipLaunchKernelGGL((thin_stream_kernel<E, RN, MR, NSTG, KCH>), grid, block, 0, s, a); break;
+int launch_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+#define EMU_TH_CASE(E) case E: hipLaunchKernelGGL((thin_stream_kernel<E, RN, MR, NSTG, KCH>), dim3(p.grid), dim3(p.block), 0, s, a); break;
     switch (a.epi) {
         EMU_TH_CASE(EPI_NONE)
         EMU_TH_CASE(EPI_RESID)
@@ -160,28 +159,16 @@ int launch_thin(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool gemv_thin_ok(const GemvArgs& a) {
-    return a.M >= 2 && a.M <= 16 && !a.norm_w && !a.wscale && a.K >= 256 && (a.K % 256) == 0 && (a.ldw & 7) == 0 && (a.ldx & 7) == 0 &&
-           (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
-           !(a.epi == EPI_SWIGLU && (a.N & 1));
-}
-
-// 16 weight rows per workgroup (three co-resident workgroups per CU at <= 8 rows): measured at 5 rows against 32-row
-// workgroups and 512-k stages (tools/thin_ab.py, profiles/r03_thin_stream_ab.log): qkv 42.1 vs 45.5 / 47.1 us.
-int launch_gemv_thin(const GemvArgs& a, hipStream_t s) {
-    if (!gemv_thin_ok(a)) return -22;
-    const int variant = (emu_gemm_tune_get() >> 8) & 15;          // A/B aid
-    if (a.M <= 8) {
-        switch (variant) {
-            case 1: return (a.N + 31) / 32 >= 512 ? launch_thin<32, 8, 3, 32>(a, s) : launch_thin<16, 8, 4, 32>(a, s);
-            case 2: return launch_thin<16, 8, 6, 32>(a, s);
-            case 3: if (a.K % 512 == 0) return launch_thin<16, 8, 3, 64>(a, s); return launch_thin<16, 8, 4, 32>(a, s);
-            default: return launch_thin<16, 8, 4, 32>(a, s);
-        }
-    }
-    switch (variant) {
-        case 1: return (a.N + 31) / 32 >= 512 ? launch_thin<32, 16, 3, 32>(a, s) : launch_thin<16, 16, 4, 32>(a, s);
-        case 2: return launch_thin<16, 16, 3, 32>(a, s);
-        default: return launch_thin<16, 16, 4, 32>(a, s);
+// the built (weight rows, activation rows, ring depth, slots per row and stage) combinations; gemv.hip::plan_thin picks among them
+int launch_gemv_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+    switch (((p.rows * 100 + p.mb) * 10 + p.stages) * 100 + p.kch) {       // digits: rows, mb (two), stages ' kch
+        case 16084'32: return launch_thin<16, 8, 4, 32>(a, p, s);
+        case 32083'32: return launch_thin<32, 8, 3, 32>(a, p, s);
+        case 16086'32: return launch_thin<16, 8, 6, 32>(a, p, s);
+        case 16083'64: return launch_thin<16, 8, 3, 64>(a, p, s);
+        case 16164'32: return launch_thin<16, 16, 4, 32>(a, p, s);
+        case 32163'32: return launch_thin<32, 16, 3, 32>(a, p, s);
+        case 16163'32: return launch_thin<16, 16, 3, 32>(a, p, s);
+        default: return -22;
     }
 }

@@ -21,7 +21,6 @@ struct GemvArgs {
     int ldx, ldw, ldres, ldo;
     float eps;
     int epi;
-    int rows_per_block;     // 0 = heuristic
     const float* wscale;    // non-null: W holds OCP fp8 e4m3 bytes [N, ldw] with one fp32 scale per row (K % 16 == 0)
     // non-null: W holds MXFP4 element bytes [N, ldw] (two E2M1 codes per byte, ldw in bytes) and w4scale the E8M0 block scales
     // [N, lds], one per 32 elements (K % 32 == 0, M <= 2): gemv_fp4.hip
@@ -31,18 +30,34 @@ struct GemvArgs {
     // single round trip) request the head of the successor's weights.  ntouch == 0: none; every other kernel ignores it.
     WarmPlan warm;
 };
-// The rule launch_gemv applies to a one-row bf16 stream, as a pure host function: which kernel form runs the shape and how many
-// weight rows a workgroup owns -- workgroup j reads rows [j * rows, j * rows + rows).  (GEMV_FORM_WAVE: 4 waves x 4 whole rows.)
+// The stream plan (gemv.hip): gemv_plan is everything launch_gemv decides between a shape and a launch -- pure host arithmetic, no
+// HIP call, no global read (tune: the emu_gemm_tune mask) -- and launch_gemv is shape -> gemv_plan -> one launch of the plan.  The
+// C-ABI test hook emu_gemv_plan returns the same (include/emu_hip.h describes the fields).
+using GemvShape = emu_gemv_shape;
+using GemvPlan = emu_gemv_plan_t;
+enum GemvFamily { GEMV_FAM_BLOCK = 0, GEMV_FAM_RT = 1, GEMV_FAM_WAVE = 2, GEMV_FAM_MFMA = 3, GEMV_FAM_THIN = 4, GEMV_FAM_FP8_BLOCK = 5,
+                  GEMV_FAM_FP8_RT = 6, GEMV_FAM_FP4_ROWS = 7 };
+// the form of a one-row bf16 stream; workgroup j reads weight rows [j * rows, j * rows + rows)  (GEMV_FORM_WAVE: 4 waves x 4 whole rows)
 enum GemvForm { GEMV_FORM_ROLLING = 0, GEMV_FORM_HEAD = 1, GEMV_FORM_PRELOAD = 2, GEMV_FORM_RT = 3, GEMV_FORM_WAVE = 4 };
+GemvPlan gemv_plan(const GemvShape& shape, int tune);
+int launch_gemv(const GemvArgs& a, hipStream_t s);
+// the plan of a one-row bf16 stream on aligned, row-contiguous operands under the current emu_gemm_tune mask, projected to
+// {form, rows} (the successor geometry of l2_warm.h)
 struct GemvGeom { int form, rows; };
 GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi);
-int emu_gemv_rows_per_block(int N, int K, bool norm);      // the block kernels' heuristic (gemv.hip)
+int emu_gemv_rows_per_block(int N, int K, bool norm);      // the one-row block kernel's heuristic (gemv.hip)
 inline bool gemv_form_warms(int form) { return form == GEMV_FORM_HEAD || form == GEMV_FORM_PRELOAD || form == GEMV_FORM_RT; }
-int launch_gemv(const GemvArgs& a, hipStream_t s);
-// the MXFP4 weight stream (gemv_fp4.hip; launch_gemv forwards to it when a.w4scale is set) and its quantiser: bf16 [N, ldw] ->
-// element bytes [N, ldq] + E8M0 scales [N, lds], bit-exact with emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the
-// call waits for its own result)
-int launch_gemv_fp4(const GemvArgs& a, hipStream_t s);
+// 9..16 rows reach the stream family (the register-fed MFMA kernel, or the thin stream ahead of it) exactly when this holds; the
+// callers that choose between launch_gemv and a GEMM ask here
+bool gemv_rows_9_16_ok(int M, int K, int ldx, int ldw, bool norm, bool fp8, int epi);
+// the family launchers of the other files, called by launch_gemv with a plan of their family: the MXFP4 weight stream (gemv_fp4.hip;
+// plan_fp4: threads per row set and row sets per workgroup for rows of KB blocks) and the thin LDS-DMA stream (gemv_thin.hip)
+constexpr int GEMV_FP4_MAX_SETS = 16;
+int launch_gemv_fp4(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
+void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
+int launch_gemv_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
+// the MXFP4 quantiser: bf16 [N, ldw] -> element bytes [N, ldq] + E8M0 scales [N, lds], bit-exact with
+// emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the call waits for its own result)
 int launch_quant_mxfp4_rows(const bf16_t* w, int ldw, uint8_t* q, int ldq, uint8_t* scales, int lds, int N, int K, hipStream_t s);
 void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
 // o_proj of a tensor-parallel shard's one-row step with the decode attention's split merge in its prologue (gemv_merge.hip):
@@ -60,9 +75,6 @@ struct GemvMergeArgs {
 };
 bool gemv_merge_ok(int heads, int D, int N, int nsplit);
 int launch_gemv_merge(const GemvMergeArgs& a, hipStream_t s);
-// 2..16 rows through LDS-DMA stages and v_mfma_f32_16x16x32_bf16 (gemv_thin.hip); needs K % 256 == 0, no fused norm, bf16 weights
-bool gemv_thin_ok(const GemvArgs& a);
-int launch_gemv_thin(const GemvArgs& a, hipStream_t s);
 // MXFP4 weights (a.w4scale set; W = element bytes, ldw in bytes) on the matrix cores: LDS-DMA stages, v_cvt_scalef32_pk_bf16_fp4 and
 // v_mfma_f32_16x16x32_bf16, the stage layout and the epilogue shared (fp4_tile.h).  Both kernels fetch a stage's 8 scale bytes per
 // row by 4-byte LDS-DMA, so a scale row spans whole stages: fp4_scale_stride(K) bytes at least -- K / 32 where K % 256 == 0, else
@@ -454,8 +466,8 @@ struct EngArgs {
     int nslot, xbytes;                         // set by launch_decode_engine
 };
 int launch_decode_engine(EngArgs a, hipStream_t s);
-// which column partition launch_gemv's kernel uses for a one-row bf16 GEMV of this shape (the engine mirrors it bit for bit):
-// 1 = gemv_wave_kernel (one wave per row), 4 = the 256-thread block kernels
+// the same plan's column partition (the engine mirrors it bit for bit): 1 = gemv_wave_kernel (one wave per row), 4 = the 256-thread
+// block and single-round-trip kernels
 int emu_gemv_partition(int N, int K, bool norm, int epi);
 
 // One beam-search step on the device (beam.hip): see emu_beam_step_bf16 in include/emu_hip.h

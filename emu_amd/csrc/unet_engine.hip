@@ -229,7 +229,7 @@ int gemm(emu_unet* u, const bf16_t* A, const bf16_t* Wt, const bf16_t* bias, con
          int lda, int ldres, int ldc, int epi, hipStream_t s, const Fx* fx = nullptr) {
     if (M <= 8) {
         if (fx) return -22;
-        GemvArgs g{A, Wt, nullptr, bias, res, C, M, N, K, lda, K, ldres, ldc, 0.f, epi, 0, nullptr};
+        GemvArgs g{A, Wt, nullptr, bias, res, C, M, N, K, lda, K, ldres, ldc, 0.f, epi, nullptr};
         return launch_gemv(g, s);
     }
     GemmArgs g{A, Wt, bias, res, C, M, N, K, lda, K, ldres, ldc, epi, NOCONV, nullptr, 0, 0};

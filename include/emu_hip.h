@@ -96,6 +96,27 @@ typedef struct {
     int reduce;                 /* the launch after it: 0 none, 1 split-K reduce, 2 256x256 slice reduce, 3 rows + norm */
 } emu_gemm_plan_entry;
 int emu_gemm_plan(const emu_gemm_shape* shape, int force_cfg, int tune, emu_gemm_plan_entry plan[2], int* entries);
+/* CPU test hook (tests/test_gemv_plan.py): what launch_gemv (emu_linear_bf16 and its fp8 / MXFP4 twins at 1..16 rows) would launch
+ * for an argument block of this shape under tune (emu_gemm_tune) -- host arithmetic only, no HIP call, no global read.  norm: fused
+ * RMSNorm; fp8 / fp4: the weight kind (neither: bf16; ldw in elements of it, bytes for MXFP4; lds: the MXFP4 scale row stride);
+ * w_aligned / x_aligned: W / x on a 16-byte boundary.  The plan: family 0 block kernel, 1 single round trip, 2 wave, 3 register-fed
+ * MFMA, 4 thin LDS-DMA stream, 5 fp8 block kernel, 6 fp8 single round trip, 7 MXFP4 rows; form (one-row bf16 / fp8 round trip):
+ * 0 rolling loop, 1 head, 2 preload, 3 single round trip, 4 wave; rows: weight rows per workgroup (grid = ceil(N / rows)); mb: the
+ * built activation-row count; waves per workgroup (block = 64 * waves); trips: the block kernel's PRE, the round trip's KIT, the
+ * wave form's KITW; stages / kch: the thin stream's ring depth and 16-byte slots per row and stage; vb: bytes per fp8 weight load;
+ * tpr / row_sets / rpl: MXFP4 threads per row set, row sets per workgroup, weight rows per lane; partition: 1 one wave per row,
+ * 4 thread t owns 16-byte columns t, t + 256, ... (0: neither).  Returns the status launch_gemv would: 0 or -22 (then the other
+ * fields are 0). */
+typedef struct {
+    int M, N, K, ldx, ldw, lds, epi;
+    int norm, fp8, fp4, w_aligned, x_aligned;
+} emu_gemv_shape;
+typedef struct {
+    int status, family, form, rows, mb, waves, trips;
+    int stages, kch, vb, tpr, row_sets, rpl;
+    int grid, block, partition;
+} emu_gemv_plan_t;
+int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
 /* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bits 0, 4, 5, 14, 17 and 18: retired,
  * ignored.  Bit 1: the K-slice workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before
  * round 3) instead of the XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip)

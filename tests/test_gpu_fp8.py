@@ -92,6 +92,35 @@ def test_linear_fp8w_fused_norm_and_swiglu(M):
     assert rel_err(got, want) < 8e-3
 
 
+@pytest.mark.parametrize("M,N,K", [(2, 38, 8208), (2, 4100, 8208), (1, 4100, 8208), (1, 2048, 16400)])
+def test_linear_fp8w_long_rows_16_byte_loads(M, N, K):
+    """K > 8192 takes the block kernel with 16-byte weight loads, the smallest shapes that reach each of its instantiations
+    (tests/test_gemv_plan.py holds the plans): 4 rows x 2 waves at two activation rows with a ragged last workgroup; 8 rows x 2
+    waves; 4 rows x 4 waves (one row, the matrix just past the 32 MiB bound of the round-trip form); 4 rows x 2 waves at one row.
+    K is no multiple of the workgroup's stride.  Plain, with the residual, and with the fused norm + SwiGLU."""
+    from emu_amd import ops
+    eps = 1e-5
+    g = torch.Generator().manual_seed(M + N + K)
+    w = (torch.randn(N, K, generator=g) * 0.02).to(BF16)
+    x = (torch.randn(M, K, generator=g)).to(BF16)
+    res = (torch.randn(M, N, generator=g)).to(BF16)
+    nw = (1 + 0.1 * torch.randn(K, generator=g)).to(BF16)
+    q, sc = ops.quantize_fp8_rows(w.cuda())
+    wd = q.cpu().view(torch.float8_e4m3fn).float() * sc.cpu()[:, None]
+    want = bfr(x.float() @ wd.T)
+    got = ops.linear_fp8w(x.cuda(), q, sc)
+    assert rel_err(got, want) < 4e-3
+    got = ops.linear_fp8w(x.cuda(), q, sc, res=res.cuda(), epi=ops.EPI_RESID)
+    assert rel_err(got, bfr(want + res.float())) < 4e-3
+    xf = x.float()
+    xn = bfr(nw.float() * bfr(xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)))
+    y = bfr(xn @ wd.T)
+    want = bfr(bfr(torch.nn.functional.silu(y[:, 0::2])) * y[:, 1::2])
+    got = ops.linear_fp8w(x.cuda(), q, sc, norm_w=nw.cuda(), eps=eps, epi=ops.EPI_SWIGLU)
+    assert got.shape == (M, N // 2)
+    assert rel_err(got, want) < 8e-3
+
+
 def test_fp8_rejects_prefill_rows_and_bad_k():
     from emu_amd import ops
     from emu_amd._lib import EmuHipError

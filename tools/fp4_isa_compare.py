@@ -30,10 +30,10 @@ def demangle(names):
     return dict(zip(names, out))
 
 
-def kernels(tree, tmp):
-    """{demangled kernel name: (metadata dict, [opcode, ...])} of the two files of a tree."""
+def kernels(tree, tmp, files=FILES, prefixes=("fp4_thin_kernel", "fp4_gemm_kernel")):
+    """{demangled kernel name: (metadata dict, [opcode, ...])} of the kernels of a tree's files whose names start with one of prefixes."""
     res = {}
-    for f in FILES:
+    for f in files:
         asm = os.path.join(tmp, f + ".s")
         subprocess.run([_hipcc(), *FLAGS, "--cuda-device-only", "-S", os.path.join(tree, "emu_amd", "csrc", f), "-o", asm], check=True,
                        capture_output=True)
@@ -53,8 +53,8 @@ def kernels(tree, tmp):
             body[m.group(1)] = ops
         names = demangle(sorted(meta))
         for k in meta:
-            short = re.sub(r"^void \(anonymous namespace\)::|\(GemvArgs\)$", "", names[k])
-            if short.startswith(("fp4_thin_kernel", "fp4_gemm_kernel")):
+            short = re.sub(r"^void \(anonymous namespace\)::|\(GemvArgs(, int, int)?\)$", "", names[k])
+            if short.startswith(prefixes):
                 res[short] = (meta[k], body[k])
     return res
 
