@@ -177,6 +177,7 @@ _PROTOS = {
     "emu_unet_finalize": (i32, [vp]),
     "emu_unet_set_fusion": (i32, [vp, i32]),
     "emu_unet_use_fp8": (i32, [vp, i32]),
+    "emu_unet_block_plan": (i32, [i32, i32, i32, i32, i32, i32, i32]),
     "emu_unet_temb_total": (i32, [vp]),
     "emu_llama_set_layer_range": (i32, [vp, i32, i32]),
     "emu_llama_set_prefill_fusion": (i32, [vp, i32]),

@@ -34,20 +34,21 @@ struct Resnet {
     int cin, cout, temb_off;
     const bf16_t *n1g, *n1b, *c1w, *c1b, *n2g, *n2b, *c2w, *c2b, *scw, *scb;
 };
-struct LnW {                        // a LayerNorm folded into its consumer GEMM: W * gamma, fp32 row sums, W @ beta + bias
-    const bf16_t* w = nullptr;
+struct Proj {                       // one matrix of a transformer block and everything registered for it (resolve_proj)
+    const bf16_t *w = nullptr, *b = nullptr;        // "<base>.w" [N, K], "<base>.b" (null: the projection has no bias)
+    // optional: the LayerNorm in front folded in -- "<base>.wln" = W * gamma, ".c" = its fp32 row sums, ".d" = W @ beta + bias
+    const bf16_t* wln = nullptr;
     const float *c = nullptr, *d = nullptr;
-    bool ok() const { return w && c && d; }
-};
-struct W8 {                         // optional e4m3 copy of a packed matrix: bytes [N, K] + one fp32 scale per output row
+    // optional (emu_unet_use_fp8): "<base>.w.fp8" = e4m3 bytes [N, K], ".w.fp8s" = one fp32 scale per output row
     const uint8_t* q = nullptr;
     const float* s = nullptr;
-    bool ok() const { return q && s; }
+    bool folded() const { return wln && c && d; }
 };
+struct LnGB { const bf16_t *g, *b; };
 struct TBlock {
-    const bf16_t *ln1g, *ln1b, *qkv, *o1w, *o1b, *ln2g, *ln2b, *q2, *kv2, *o2w, *o2b, *ln3g, *ln3b, *ggw, *ggb, *ffw, *ffb;
-    LnW qkv_ln, q2_ln, gg_ln;       // optional packed tensors of the fused-LayerNorm path
-    W8 qkv8, o1_8, q2_8, o2_8, gg8, ff8;   // emu_unet_use_fp8: the six matrices of the block as fp8 operands
+    Proj qkv, o1, q2, o2, gg, ff;
+    LnGB ln1, ln2, ln3;
+    const bf16_t* kv2;
     size_t ctx_off;                 // element offset of this block's {K|V rows, Vt} in the context cache
 };
 struct Transformer {
@@ -56,7 +57,23 @@ struct Transformer {
     const bf16_t *gng, *gnb, *piw, *pib, *pow_, *pob;
     std::vector<TBlock> blocks;
 };
-struct Level { int c, hw_shift; };
+
+// What a transformer's blocks fuse and in which format their six GEMMs run: the one rule, on integers only (no HIP call, no
+// global, no engine; exported as emu_unet_block_plan, tests/test_unet_block_plan.py).  fp8 = emu_unet_use_fp8, fusion =
+// emu_unet_set_fusion's mask, M = rows (batch elements x HW).  M <= 8 (toy latents) is the GEMV path, which fuses nothing.
+struct BlockPlan {
+    bool fp8;               // W8A8 GEMMs: whole 128-column k tiles, rows no wider than launch_layernorm_q8 holds
+    bool ln_fold;           // bit 0: the LayerNorms live in their consumer GEMMs (statistics slots are 128 columns wide; no fp8 form)
+    bool vt_epilogue;       // bit 1: the qkv projection stores V^T itself (whole 64-key groups)
+    bool cross_epilogue;    // bit 2: cross-attention inside the to_q epilogue (rows of one tile within one batch element, <= 64 keys)
+    bool prefetch;          // every GEMM of the chain names its successor's weights (Fx::pf; the fp8 GEMM has no such argument)
+};
+BlockPlan unet_block_plan(bool fp8, int fusion, int M, int C, int HW, int n_ctx, int depth) {
+    const bool gemm = M > 8, keys64 = HW % 64 == 0;
+    const bool f8 = fp8 && gemm && C % 128 == 0 && C <= 2048;
+    return {f8, !f8 && (fusion & 1) && gemm && C % 128 == 0, (fusion & 2) && gemm && keys64,
+            (fusion & 4) && gemm && keys64 && n_ctx <= 64, !f8 && gemm && depth > 0};
+}
 }  // namespace
 
 struct emu_unet {
@@ -94,6 +111,7 @@ int ufail(emu_unet* u, int code, const std::string& what) {
     return emu_ctx_fail(u->ctx, code, u->err.c_str());
 }
 #define UTRY(expr) do { int st__ = (expr); if (st__ != 0) return ufail(u, st__, #expr); } while (0)
+#define UPASS(expr) do { int st__ = (expr); if (st__ != 0) return st__; } while (0)     // the callee has recorded the failure
 
 const bf16_t* find(emu_unet* u, const std::string& k, bool required, bool* ok) {
     auto it = u->w.find(k);
@@ -114,6 +132,27 @@ void resolve_resnet(emu_unet* u, Resnet& r, bool* ok) {
     r.scw = find(u, p + "shortcut.w", sc, ok); r.scb = find(u, p + "shortcut.b", sc, ok);
 }
 
+// One block matrix from its registered names: "<base>.w" and, with `bias`, "<base>.b" are required; the LayerNorm fold
+// "<base>.wln" / ".c" / ".d" is optional (fusion_avail bit 0); the e4m3 copy "<base>.w.fp8" / ".w.fp8s" is required with `fp8`.
+Proj resolve_proj(emu_unet* u, const std::string& base, bool bias, bool fp8, bool* ok) {
+    Proj p;
+    p.w = find(u, base + ".w", true, ok);
+    if (bias) p.b = find(u, base + ".b", true, ok);
+    p.wln = find(u, base + ".wln", false, ok);
+    p.c = reinterpret_cast<const float*>(find(u, base + ".c", false, ok));
+    p.d = reinterpret_cast<const float*>(find(u, base + ".d", false, ok));
+    p.q = reinterpret_cast<const uint8_t*>(find(u, base + ".w.fp8", fp8, ok));
+    p.s = reinterpret_cast<const float*>(find(u, base + ".w.fp8s", fp8, ok));
+    return p;
+}
+
+// the six matrices of block `b` ("<transformer>transformer_blocks.<k>."): emu_unet_finalize (fp8 = false) and emu_unet_use_fp8
+void resolve_block(emu_unet* u, TBlock& tb, const std::string& b, bool fp8, bool* ok) {
+    tb.qkv = resolve_proj(u, b + "attn1.qkv", false, fp8, ok); tb.o1 = resolve_proj(u, b + "attn1.out", true, fp8, ok);
+    tb.q2 = resolve_proj(u, b + "attn2.q", false, fp8, ok); tb.o2 = resolve_proj(u, b + "attn2.out", true, fp8, ok);
+    tb.gg = resolve_proj(u, b + "ff.geglu", true, fp8, ok); tb.ff = resolve_proj(u, b + "ff.out", true, fp8, ok);
+}
+
 void resolve_transformer(emu_unet* u, Transformer& t, bool* ok) {
     const std::string& p = t.name;
     t.gng = find(u, p + "norm.g", true, ok); t.gnb = find(u, p + "norm.b", true, ok);
@@ -123,25 +162,21 @@ void resolve_transformer(emu_unet* u, Transformer& t, bool* ok) {
     for (int k = 0; k < t.depth; ++k) {
         const std::string b = p + "transformer_blocks." + std::to_string(k) + ".";
         TBlock& tb = t.blocks[k];
-        tb.ln1g = find(u, b + "norm1.g", true, ok); tb.ln1b = find(u, b + "norm1.b", true, ok);
-        tb.ln2g = find(u, b + "norm2.g", true, ok); tb.ln2b = find(u, b + "norm2.b", true, ok);
-        tb.ln3g = find(u, b + "norm3.g", true, ok); tb.ln3b = find(u, b + "norm3.b", true, ok);
-        tb.qkv = find(u, b + "attn1.qkv.w", true, ok);
-        tb.o1w = find(u, b + "attn1.out.w", true, ok); tb.o1b = find(u, b + "attn1.out.b", true, ok);
-        tb.q2 = find(u, b + "attn2.q.w", true, ok); tb.kv2 = find(u, b + "attn2.kv.w", true, ok);
-        tb.o2w = find(u, b + "attn2.out.w", true, ok); tb.o2b = find(u, b + "attn2.out.b", true, ok);
-        tb.ggw = find(u, b + "ff.geglu.w", true, ok); tb.ggb = find(u, b + "ff.geglu.b", true, ok);
-        tb.ffw = find(u, b + "ff.out.w", true, ok); tb.ffb = find(u, b + "ff.out.b", true, ok);
-        auto lnw = [&](const std::string& base) {
-            LnW l;
-            l.w = find(u, base + ".wln", false, ok);
-            l.c = reinterpret_cast<const float*>(find(u, base + ".c", false, ok));
-            l.d = reinterpret_cast<const float*>(find(u, base + ".d", false, ok));
-            return l;
-        };
-        tb.qkv_ln = lnw(b + "attn1.qkv"); tb.q2_ln = lnw(b + "attn2.q"); tb.gg_ln = lnw(b + "ff.geglu");
-        if (!(tb.qkv_ln.ok() && tb.q2_ln.ok() && tb.gg_ln.ok())) u->fusion_avail &= ~1;
+        tb.ln1 = {find(u, b + "norm1.g", true, ok), find(u, b + "norm1.b", true, ok)};
+        tb.ln2 = {find(u, b + "norm2.g", true, ok), find(u, b + "norm2.b", true, ok)};
+        tb.ln3 = {find(u, b + "norm3.g", true, ok), find(u, b + "norm3.b", true, ok)};
+        tb.kv2 = find(u, b + "attn2.kv.w", true, ok);
+        resolve_block(u, tb, b, false, ok);
+        if (!(tb.qkv.folded() && tb.q2.folded() && tb.gg.folded())) u->fusion_avail &= ~1;
     }
+}
+
+// f(transformer) -> status over every transformer in traversal order (down, mid, up: the order of the context cache); stops at a failure
+template <class U, class F> int each_transformer(U* u, F&& f) {
+    for (int i = 0; i < 3; ++i) for (auto& t : u->down_tr[i]) UPASS(f(t));
+    UPASS(f(u->mid_tr));
+    for (int i = 0; i < 3; ++i) for (auto& t : u->up_tr[i]) UPASS(f(t));
+    return 0;
 }
 
 // ---------------------------------------------------------------- workspace plan
@@ -213,7 +248,7 @@ Ws plan_ws(const emu_unet* u, int H, int W, void* base) {
 // optional fused epilogues of one GEMM of a transformer block (GemmArgs: row_stats_out / ln_* / vt_*)
 struct Fx {
     float* stats_out = nullptr;         // producer: per-row partial sums of the output for the next LayerNorm
-    const LnW* ln = nullptr;            // consumer: LayerNorm of A folded in (W = ln->w), statistics from `stats_in`
+    const Proj* ln = nullptr;           // consumer: LayerNorm of A folded in (W = ln->wln), statistics from `stats_in`
     const float* stats_in = nullptr;
     bf16_t* vt = nullptr;               // qkv projection: V heads (columns >= vt_col0) stored key-contiguous
     int vt_col0 = 0, vt_s = 0, vt_spad = 0;
@@ -223,7 +258,21 @@ struct Fx {
     float cross_scale = 0.f;
     const void* pf = nullptr;           // GemmArgs::pf_*: the weight matrix of the GEMM that follows this one on the stream
     size_t pf_bytes = 0;
+    bool any() const { return stats_out || ln || vt || cross_k || pf; }
 };
+
+// (an all-default Fx leaves the argument block as it was)
+void apply_fx(GemmArgs& g, const Fx& fx) {
+    g.row_stats_out = fx.stats_out;
+    if (fx.ln) {
+        g.W = fx.ln->wln; g.bias = nullptr;
+        g.ln_c = fx.ln->c; g.ln_d = fx.ln->d; g.ln_stats = fx.stats_in; g.ln_slots = g.K / 128; g.ln_eps = 1e-5f;
+    }
+    g.vt_out = fx.vt; g.vt_col0 = fx.vt_col0; g.vt_s = fx.vt_s; g.vt_spad = fx.vt_spad;
+    g.cross_k = fx.cross_k; g.cross_vt = fx.cross_vt; g.cross_ldk = fx.cross_ldk; g.cross_n = fx.cross_n;
+    g.cross_npad = fx.cross_npad; g.cross_rows = fx.cross_rows; g.cross_scale = fx.cross_scale;
+    g.pf_ptr = fx.pf; g.pf_bytes = fx.pf_bytes;
+}
 
 int gemm(emu_unet* u, const bf16_t* A, const bf16_t* Wt, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M, int N, int K,
          int lda, int ldres, int ldc, int epi, hipStream_t s, const Fx* fx = nullptr) {
@@ -234,34 +283,8 @@ int gemm(emu_unet* u, const bf16_t* A, const bf16_t* Wt, const bf16_t* bias, con
     }
     GemmArgs g{A, Wt, bias, res, C, M, N, K, lda, K, ldres, ldc, epi, NOCONV, nullptr, 0, 0};
     if (u) { g.partial = u->splitk; g.partial_floats = u->splitk_floats; }    // primitives (u == null): process scratch
-    if (fx) {
-        g.row_stats_out = fx->stats_out;
-        if (fx->ln) {
-            g.W = fx->ln->w; g.bias = nullptr;
-            g.ln_c = fx->ln->c; g.ln_d = fx->ln->d; g.ln_stats = fx->stats_in; g.ln_slots = K / 128; g.ln_eps = 1e-5f;
-        }
-        g.vt_out = fx->vt; g.vt_col0 = fx->vt_col0; g.vt_s = fx->vt_s; g.vt_spad = fx->vt_spad;
-        g.cross_k = fx->cross_k; g.cross_vt = fx->cross_vt; g.cross_ldk = fx->cross_ldk; g.cross_n = fx->cross_n;
-        g.cross_npad = fx->cross_npad; g.cross_rows = fx->cross_rows; g.cross_scale = fx->cross_scale;
-        g.pf_ptr = fx->pf; g.pf_bytes = fx->pf_bytes;
-    }
+    if (fx) apply_fx(g, *fx);
     return launch_gemm(g, s);
-}
-
-// epi(fp8 rows in w.x8 / w.xs  x  fp8 weights): launch_gemm_fp8 (emu_linear_fp8_bf16's kernels)
-// (of the fused epilogues the V^T stores and the cross-attention are available with fp8 operands: Fx::vt / Fx::cross_*)
-int gemm8(emu_unet* u, const Ws& w, const W8& W, const bf16_t* bias, const bf16_t* res, bf16_t* C, int M, int N, int K, int ldres,
-          int ldc, int epi, hipStream_t s, const Fx* fx = nullptr) {
-    GemmArgs g{reinterpret_cast<const bf16_t*>(w.x8), reinterpret_cast<const bf16_t*>(W.q), bias, res, C, M, N, K, K, K, ldres, ldc, epi,
-               NOCONV, nullptr, 0, 0};
-    g.a_scale = w.xs; g.w_scale = W.s;
-    g.partial = u->splitk; g.partial_floats = u->splitk_floats;
-    if (fx) {
-        g.vt_out = fx->vt; g.vt_col0 = fx->vt_col0; g.vt_s = fx->vt_s; g.vt_spad = fx->vt_spad;
-        g.cross_k = fx->cross_k; g.cross_vt = fx->cross_vt; g.cross_ldk = fx->cross_ldk; g.cross_n = fx->cross_n;
-        g.cross_npad = fx->cross_npad; g.cross_rows = fx->cross_rows; g.cross_scale = fx->cross_scale;
-    }
-    return launch_gemm_fp8(g, s);
 }
 
 int conv3(emu_unet* u, const bf16_t* x, const bf16_t* Wt, const bf16_t* bias, const bf16_t* bias2, int ldb2, const bf16_t* res,
@@ -290,130 +313,118 @@ int run_resnet(emu_unet* u, const Resnet& r, const bf16_t* x, bf16_t* out, const
     return 0;
 }
 
+// Transformer2D: GroupNorm -> proj_in -> blocks of {self-attention, cross-attention on the cached prompt K / V^T, GEGLU
+// feed-forward}, each behind its LayerNorm and added to the stream -> proj_out + input.  unet_block_plan says once what the blocks
+// fuse; nothing else decides a path.
+// Fused path (emu_unet_set_fusion): the three LayerNorms of a block live inside their consumer GEMMs -- the producer of the
+// stream (proj_in, attn1 / attn2 out-projection, ff-out) emits per-row partial sums from its epilogue, the consumer (qkv,
+// attn2 q, GEGLU) multiplies the un-normalised rows by W * gamma and corrects with mean / rstd in its epilogue -- and the qkv
+// projection writes V^T itself.  M <= 8 (toy latents) stays on the unfused GEMV path.
+// W8A8 mode (emu_unet_use_fp8; not a reference feature): the six GEMMs of a block take fp8 operands.  The three LayerNorms
+// run as launches again -- they hold whole rows, so their output leaves as the consumer's fp8 operand with its per-row scale
+// for free (launch_layernorm_q8) -- the attention outputs and the GEGLU product are quantised by a launch of their own
+// (their rows are spread over the workgroups of the producing kernel); the V^T stores of the qkv projection and the
+// cross-attention inside the to_q epilogue (fusion bits 1, 2) work on finished sums and stay available.  proj_in / proj_out,
+// the convs and everything outside the transformer blocks stay bf16.
+// Successor prefetch (Fx::pf, GemmArgs::pf_*): every GEMM of the chain names the weight matrix of the GEMM behind it (the
+// LayerNorm-folded copy where that is the operand); the attention launches in between only widen the lead.  Same-run A/B on the
+// true config: 25.07 -> 24.19 ms per denoise step (profiles/r05_prefetch_ab_unet_linear_transformer_chain.log); naming the
+// resnets' conv weights as well added nothing (..._plus_conv_modules.log) and is not done
 int run_transformer(emu_unet* u, const Transformer& t, const bf16_t* x, bf16_t* out, const Ws& w, int Bn, int H, int W, hipStream_t s) {
     const int HW = H * W, M = Bn * HW, C = t.c, D = 64;
     const int hwpad = (HW + 63) / 64 * 64, npad = (u->n_ctx + 63) / 64 * 64, n = u->n_ctx;
     const float scale = 0.125f;
     const int hb = u->cfg_half < 0 ? 0 : u->cfg_half;     // first row of the CFG pair this call computes
-    // Fused path (emu_unet_set_fusion): the three LayerNorms of a block live inside their consumer GEMMs -- the producer of the
-    // stream (proj_in, attn1 / attn2 out-projection, ff-out) emits per-row partial sums from its epilogue, the consumer (qkv,
-    // attn2 q, GEGLU) multiplies the un-normalised rows by W * gamma and corrects with mean / rstd in its epilogue -- and the qkv
-    // projection writes V^T itself.  M <= 8 (toy latents) stays on the unfused GEMV path.
-    // W8A8 mode (emu_unet_use_fp8; not a reference feature): the six GEMMs of a block take fp8 operands.  The three LayerNorms
-    // run as launches again -- they hold whole rows, so their output leaves as the consumer's fp8 operand with its per-row scale
-    // for free (launch_layernorm_q8) -- the attention outputs and the GEGLU product are quantised by a launch of their own
-    // (their rows are spread over the workgroups of the producing kernel); the V^T stores of the qkv projection and the
-    // cross-attention inside the to_q epilogue (fusion bits 1, 2) work on finished sums and stay available.  proj_in / proj_out,
-    // the convs and everything outside the transformer blocks stay bf16.
-    const bool f8 = u->fp8 && M > 8 && (C & 127) == 0 && C <= 2048;
-    const bool fvt8 = f8 && (u->fusion & 2) && HW == hwpad;
-    const bool fca8 = f8 && (u->fusion & 4) && HW == hwpad && n <= 64;
-    const bool fln = !f8 && (u->fusion & 1) && M > 8 && (C & 127) == 0;     // statistics slots are 128 columns wide
-    const bool fvt = !f8 && (u->fusion & 2) && M > 8 && HW == hwpad;
-    const bool fca = !f8 && (u->fusion & 4) && M > 8 && HW == hwpad && n <= 64;     // rows of one tile within one batch element
-    float* st = w.lnstats;
-    UTRY(launch_groupnorm(x, t.gng, t.gnb, w.gn, w.gnws, Bn, HW, C, u->cfg.groups, 1e-6f, 0, s));
-    // successor prefetch (Fx::pf, GemmArgs::pf_*): every GEMM of the chain names the weight matrix of the GEMM behind it (the
-    // LayerNorm-folded copy where that is the operand); the attention launches in between only widen the lead.  Same-run A/B on the
-    // true config: 25.07 -> 24.19 ms per denoise step (profiles/r05_prefetch_ab_unet_linear_transformer_chain.log); naming the
-    // resnets' conv weights as well added nothing (..._plus_conv_modules.log) and is not done
     const size_t CC = (size_t)C * C * 2;
-    const bool pfon = !f8 && M > 8 && !t.blocks.empty();
-    auto qkv_w = [&](const TBlock& b_) { return fln ? (const void*)b_.qkv_ln.w : (const void*)b_.qkv; };
-    { Fx fx; fx.stats_out = fln ? st : nullptr;
-      if (pfon) { fx.pf = qkv_w(t.blocks[0]); fx.pf_bytes = 3 * CC; }
-      UTRY(gemm(u, w.gn, t.piw, t.pib, nullptr, w.tokA, M, C, C, C, 0, C, EPI_NONE, s, (fln || pfon) ? &fx : nullptr)); }
-    bf16_t *a = w.tokA, *b = w.tokB;
-    for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
-        const TBlock& tb = t.blocks[bi];
-        if (f8) {
-            UTRY(launch_layernorm_q8(a, tb.ln1g, tb.ln1b, nullptr, nullptr, w.x8, w.xs, M, C, 1e-5f, s));
-            { Fx fx;
-              if (fvt8) { fx.vt = w.vt; fx.vt_col0 = 2 * C; fx.vt_s = HW; fx.vt_spad = hwpad; }
-              UTRY(gemm8(u, w, tb.qkv8, nullptr, nullptr, w.qkv, M, 3 * C, C, 0, 3 * C, EPI_NONE, s, fvt8 ? &fx : nullptr)); }
-            if (!fvt8) {
-                TransposeVArgs tv{w.qkv + 2 * C, (long)HW * 3 * C, (long)D, (long)3 * C, w.vt, Bn, t.heads, HW, D, hwpad};
-                UTRY(launch_transpose_v(tv, s));
-            }
-            { FlashArgs f{w.qkv, (long)HW * 3 * C, (long)D, (long)3 * C, w.qkv + C, (long)HW * 3 * C, (long)D, (long)3 * C, w.vt,
-                          w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, HW, hwpad, D, 0, scale};
-              UTRY(launch_flash_attn(f, s)); }
-            UTRY(launch_quant_fp8_rows(w.att, C, w.x8, C, w.xs, M, C, s));
-            UTRY(gemm8(u, w, tb.o1_8, tb.o1b, a, b, M, C, C, C, C, EPI_RESID, s));
-            UTRY(launch_layernorm_q8(b, tb.ln2g, tb.ln2b, nullptr, nullptr, w.x8, w.xs, M, C, 1e-5f, s));
-            { const bf16_t* kv = u->ctx_cache + tb.ctx_off + (size_t)hb * n * 2 * C;     // the cache holds both rows of the CFG pair
-              const bf16_t* vt = u->ctx_cache + tb.ctx_off + (size_t)2 * n * 2 * C + (size_t)hb * C * npad;
-              if (fca8) {                                // to_q + the 64-key attention in one launch: writes w.att directly
-                  Fx fx;
-                  fx.cross_k = kv; fx.cross_vt = vt; fx.cross_ldk = 2 * C; fx.cross_n = n; fx.cross_npad = npad; fx.cross_rows = HW;
-                  fx.cross_scale = scale;
-                  UTRY(gemm8(u, w, tb.q2_8, nullptr, nullptr, w.att, M, C, C, 0, C, EPI_NONE, s, &fx));
-              } else {
-                  UTRY(gemm8(u, w, tb.q2_8, nullptr, nullptr, w.q2, M, C, C, 0, C, EPI_NONE, s));
-                  FlashArgs f{w.q2, (long)HW * C, (long)D, (long)C, kv, (long)n * 2 * C, (long)D, (long)2 * C, vt,
-                              w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, n, npad, D, 0, scale};
-                  UTRY(launch_flash_attn(f, s));
-              } }
-            UTRY(launch_quant_fp8_rows(w.att, C, w.x8, C, w.xs, M, C, s));
-            UTRY(gemm8(u, w, tb.o2_8, tb.o2b, b, a, M, C, C, C, C, EPI_RESID, s));
-            UTRY(launch_layernorm_q8(a, tb.ln3g, tb.ln3b, nullptr, nullptr, w.x8, w.xs, M, C, 1e-5f, s));
-            UTRY(gemm8(u, w, tb.gg8, tb.ggb, nullptr, w.ff, M, 8 * C, C, 0, 4 * C, EPI_GEGLU, s));
-            UTRY(launch_quant_fp8_rows(w.ff, 4 * C, w.x8, 4 * C, w.xs, M, 4 * C, s));
-            UTRY(gemm8(u, w, tb.ff8, tb.ffb, a, b, M, C, 4 * C, C, C, EPI_RESID, s));
-            std::swap(a, b);
-            continue;
+    const BlockPlan plan = unet_block_plan(u->fp8, u->fusion, M, C, HW, n, (int)t.blocks.size());
+    // the epilogue block of a GEMM that writes the stream (`stats`: a folded LayerNorm reads its rows next) and names its successor
+    auto chain = [&](bool stats, const void* next, size_t next_bytes) {
+        Fx fx;
+        if (stats && plan.ln_fold) fx.stats_out = w.lnstats;
+        if (plan.prefetch) { fx.pf = next; fx.pf_bytes = next_bytes; }
+        return fx;
+    };
+    auto operand = [&](const Proj& P) { return plan.ln_fold ? (const void*)P.wln : (const void*)P.w; };   // of a GEMM behind a LayerNorm
+    // the LayerNorm in front of a projection, three ways: folded into the projection (nothing launched: project(.., normed) hands
+    // it the stream's statistics), a launch into w.ln, or (fp8) a launch that leaves the projection's e4m3 operand in w.x8 / w.xs
+    auto norm_into = [&](const bf16_t* xin, const LnGB& ln, const bf16_t** A) -> int {
+        *A = plan.ln_fold ? xin : w.ln;
+        if (plan.fp8) UTRY(launch_layernorm_q8(xin, ln.g, ln.b, nullptr, nullptr, w.x8, w.xs, M, C, 1e-5f, s));
+        else if (!plan.ln_fold) UTRY(launch_layernorm(xin, ln.g, ln.b, nullptr, w.ln, M, C, 1e-5f, s));
+        return 0;
+    };
+    // one projection of a block, A [M, K] packed: bf16, or (plan.fp8) the rows quantised per row unless norm_into just did + the
+    // fp8 x fp8 GEMM (emu_linear_fp8_bf16's kernels).  normed: A comes from norm_into.  gemm() refuses an Fx at M <= 8, and the
+    // plan sets no field there: it is passed only when it says something.  (The fp8 GEMM takes the V^T and cross-attention fields;
+    // the plan leaves the LayerNorm fold, the row statistics and the prefetch unset in fp8 mode.)
+    auto project = [&](const bf16_t* A, const Proj& P, const bf16_t* res, bf16_t* Cc, int N, int K, int ldres, int ldc, int epi, Fx fx,
+                       bool normed = false) -> int {
+        if (normed && plan.ln_fold) { fx.ln = &P; fx.stats_in = w.lnstats; }
+        if (!plan.fp8) {
+            UTRY(gemm(u, A, P.w, P.b, res, Cc, M, N, K, K, ldres, ldc, epi, s, fx.any() ? &fx : nullptr));
+            return 0;
         }
-        // self attention
-        const bf16_t* lnx = a;
-        if (!fln) { UTRY(launch_layernorm(a, tb.ln1g, tb.ln1b, nullptr, w.ln, M, C, 1e-5f, s)); lnx = w.ln; }
-        { Fx fx;
-          if (fln) { fx.ln = &tb.qkv_ln; fx.stats_in = st; }
-          if (fvt) { fx.vt = w.vt; fx.vt_col0 = 2 * C; fx.vt_s = HW; fx.vt_spad = hwpad; }
-          if (pfon) { fx.pf = tb.o1w; fx.pf_bytes = CC; }
-          UTRY(gemm(u, lnx, tb.qkv, nullptr, nullptr, w.qkv, M, 3 * C, C, C, 0, 3 * C, EPI_NONE, s, (fln || fvt || pfon) ? &fx : nullptr)); }
-        if (!fvt) {
+        if (!normed) UTRY(launch_quant_fp8_rows(A, K, w.x8, K, w.xs, M, K, s));
+        GemmArgs g{reinterpret_cast<const bf16_t*>(w.x8), reinterpret_cast<const bf16_t*>(P.q), P.b, res, Cc, M, N, K, K, K, ldres, ldc,
+                   epi, NOCONV, nullptr, 0, 0};
+        g.a_scale = w.xs; g.w_scale = P.s;
+        g.partial = u->splitk; g.partial_floats = u->splitk_floats;
+        apply_fx(g, fx);
+        UTRY(launch_gemm_fp8(g, s));
+        return 0;
+    };
+    // a -> b = a + out(attention(qkv(LayerNorm(a))))
+    auto self_attention = [&](const TBlock& tb, const bf16_t* a, bf16_t* b) -> int {
+        const bf16_t* A;
+        UPASS(norm_into(a, tb.ln1, &A));
+        Fx fx = chain(false, tb.o1.w, CC);
+        if (plan.vt_epilogue) { fx.vt = w.vt; fx.vt_col0 = 2 * C; fx.vt_s = HW; fx.vt_spad = hwpad; }
+        UPASS(project(A, tb.qkv, nullptr, w.qkv, 3 * C, C, 0, 3 * C, EPI_NONE, fx, true));
+        if (!plan.vt_epilogue) {
             TransposeVArgs tv{w.qkv + 2 * C, (long)HW * 3 * C, (long)D, (long)3 * C, w.vt, Bn, t.heads, HW, D, hwpad};
             UTRY(launch_transpose_v(tv, s));
         }
-        { FlashArgs f{w.qkv, (long)HW * 3 * C, (long)D, (long)3 * C, w.qkv + C, (long)HW * 3 * C, (long)D, (long)3 * C, w.vt,
-                      w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, HW, hwpad, D, 0, scale};
-          UTRY(launch_flash_attn(f, s)); }
-        { Fx fx; fx.stats_out = fln ? st : nullptr;
-          if (pfon) { fx.pf = fln ? (const void*)tb.q2_ln.w : (const void*)tb.q2; fx.pf_bytes = CC; }
-          UTRY(gemm(u, w.att, tb.o1w, tb.o1b, a, b, M, C, C, C, C, C, EPI_RESID, s, (fln || pfon) ? &fx : nullptr)); }
-        // cross attention on the cached context K / Vt
-        lnx = b;
-        if (!fln) { UTRY(launch_layernorm(b, tb.ln2g, tb.ln2b, nullptr, w.ln, M, C, 1e-5f, s)); lnx = w.ln; }
-        { const bf16_t* kv = u->ctx_cache + tb.ctx_off + (size_t)hb * n * 2 * C;
-          const bf16_t* vt = u->ctx_cache + tb.ctx_off + (size_t)2 * n * 2 * C + (size_t)hb * C * npad;
-          Fx fx;
-          if (fln) { fx.ln = &tb.q2_ln; fx.stats_in = st; }
-          if (pfon) { fx.pf = tb.o2w; fx.pf_bytes = CC; }
-          if (fca) {                                     // to_q + the whole 64-key attention in one launch: writes w.att directly
-              fx.cross_k = kv; fx.cross_vt = vt; fx.cross_ldk = 2 * C; fx.cross_n = n; fx.cross_npad = npad; fx.cross_rows = HW;
-              fx.cross_scale = scale;
-              UTRY(gemm(u, lnx, tb.q2, nullptr, nullptr, w.att, M, C, C, C, 0, C, EPI_NONE, s, &fx));
-          } else {
-              UTRY(gemm(u, lnx, tb.q2, nullptr, nullptr, w.q2, M, C, C, C, 0, C, EPI_NONE, s, (fln || pfon) ? &fx : nullptr));
-              FlashArgs f{w.q2, (long)HW * C, (long)D, (long)C, kv, (long)n * 2 * C, (long)D, (long)2 * C, vt,
-                          w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, n, npad, D, 0, scale};
-              UTRY(launch_flash_attn(f, s));
-          } }
-        { Fx fx; fx.stats_out = fln ? st : nullptr;
-          if (pfon) { fx.pf = fln ? (const void*)tb.gg_ln.w : (const void*)tb.ggw; fx.pf_bytes = 8 * CC; }
-          UTRY(gemm(u, w.att, tb.o2w, tb.o2b, b, a, M, C, C, C, C, C, EPI_RESID, s, (fln || pfon) ? &fx : nullptr)); }
-        // GEGLU feed-forward
-        lnx = a;
-        if (!fln) { UTRY(launch_layernorm(a, tb.ln3g, tb.ln3b, nullptr, w.ln, M, C, 1e-5f, s)); lnx = w.ln; }
-        { Fx fx;
-          if (fln) { fx.ln = &tb.gg_ln; fx.stats_in = st; }
-          if (pfon) { fx.pf = tb.ffw; fx.pf_bytes = 4 * CC; }
-          UTRY(gemm(u, lnx, tb.ggw, tb.ggb, nullptr, w.ff, M, 8 * C, C, C, 0, 4 * C, EPI_GEGLU, s, (fln || pfon) ? &fx : nullptr)); }
-        { Fx fx; fx.stats_out = st;                          // feeds the next block's first LayerNorm (none after the last)
-          const bool last = bi + 1 == t.blocks.size();
-          if (!(fln && !last)) fx.stats_out = nullptr;
-          if (pfon) { fx.pf = last ? (const void*)t.pow_ : qkv_w(t.blocks[bi + 1]); fx.pf_bytes = last ? CC : 3 * CC; }
-          UTRY(gemm(u, w.ff, tb.ffw, tb.ffb, a, b, M, C, 4 * C, 4 * C, C, C, EPI_RESID, s, ((fln && !last) || pfon) ? &fx : nullptr)); }
+        FlashArgs f{w.qkv, (long)HW * 3 * C, (long)D, (long)3 * C, w.qkv + C, (long)HW * 3 * C, (long)D, (long)3 * C, w.vt,
+                    w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, HW, hwpad, D, 0, scale};
+        UTRY(launch_flash_attn(f, s));
+        return project(w.att, tb.o1, a, b, C, C, C, C, EPI_RESID, chain(true, operand(tb.q2), CC));
+    };
+    // b -> a = b + out(attention of to_q(LayerNorm(b)) over the cached context K / Vt)
+    auto cross_attention = [&](const TBlock& tb, const bf16_t* b, bf16_t* a) -> int {
+        const bf16_t* A;
+        UPASS(norm_into(b, tb.ln2, &A));
+        const bf16_t* kv = u->ctx_cache + tb.ctx_off + (size_t)hb * n * 2 * C;      // the cache holds both rows of the CFG pair
+        const bf16_t* vt = u->ctx_cache + tb.ctx_off + (size_t)2 * n * 2 * C + (size_t)hb * C * npad;
+        Fx fx = chain(false, tb.o2.w, CC);
+        if (plan.cross_epilogue) {                       // to_q + the whole 64-key attention in one launch: writes w.att directly
+            fx.cross_k = kv; fx.cross_vt = vt; fx.cross_ldk = 2 * C; fx.cross_n = n; fx.cross_npad = npad; fx.cross_rows = HW;
+            fx.cross_scale = scale;
+        }
+        UPASS(project(A, tb.q2, nullptr, plan.cross_epilogue ? w.att : w.q2, C, C, 0, C, EPI_NONE, fx, true));
+        if (!plan.cross_epilogue) {
+            FlashArgs f{w.q2, (long)HW * C, (long)D, (long)C, kv, (long)n * 2 * C, (long)D, (long)2 * C, vt,
+                        w.att, (long)HW * C, (long)D, (long)C, nullptr, Bn, t.heads, HW, n, npad, D, 0, scale};
+            UTRY(launch_flash_attn(f, s));
+        }
+        return project(w.att, tb.o2, b, a, C, C, C, C, EPI_RESID, chain(true, operand(tb.gg), 8 * CC));
+    };
+    // a -> b = a + ff_out(GEGLU(LayerNorm(a))); its statistics feed the next block's first LayerNorm (none after the last block)
+    auto feed_forward = [&](const TBlock& tb, const bf16_t* a, bf16_t* b, const TBlock* next) -> int {
+        const bf16_t* A;
+        UPASS(norm_into(a, tb.ln3, &A));
+        UPASS(project(A, tb.gg, nullptr, w.ff, 8 * C, C, 0, 4 * C, EPI_GEGLU, chain(false, tb.ff.w, 4 * CC), true));
+        return project(w.ff, tb.ff, a, b, C, 4 * C, C, C, EPI_RESID,
+                       chain(next != nullptr, next ? operand(next->qkv) : (const void*)t.pow_, next ? 3 * CC : CC));
+    };
+    UTRY(launch_groupnorm(x, t.gng, t.gnb, w.gn, w.gnws, Bn, HW, C, u->cfg.groups, 1e-6f, 0, s));
+    { const Fx fx = chain(true, plan.prefetch ? operand(t.blocks[0].qkv) : nullptr, 3 * CC);
+      UTRY(gemm(u, w.gn, t.piw, t.pib, nullptr, w.tokA, M, C, C, C, 0, C, EPI_NONE, s, fx.any() ? &fx : nullptr)); }
+    bf16_t *a = w.tokA, *b = w.tokB;
+    for (size_t bi = 0; bi < t.blocks.size(); ++bi) {
+        const TBlock& tb = t.blocks[bi];
+        UPASS(self_attention(tb, a, b));
+        UPASS(cross_attention(tb, b, a));
+        UPASS(feed_forward(tb, a, b, bi + 1 < t.blocks.size() ? &t.blocks[bi + 1] : nullptr));
         std::swap(a, b);
     }
     UTRY(gemm(u, a, t.pow_, t.pob, x, out, M, C, C, C, C, C, EPI_RESID, s));
@@ -466,25 +477,10 @@ int emu_unet_use_fp8(emu_unet* u, int enable) {
     if (!u || !u->finalized) return -22;
     if (!enable) { u->fp8 = false; return 0; }
     bool ok = true;
-    auto w8 = [&](const std::string& base) {
-        W8 r;
-        r.q = reinterpret_cast<const uint8_t*>(find(u, base + ".fp8", true, &ok));
-        r.s = reinterpret_cast<const float*>(find(u, base + ".fp8s", true, &ok));
-        return r;
-    };
-    auto resolve = [&](Transformer& t) {
-        for (int k = 0; k < t.depth; ++k) {
-            const std::string b = t.name + "transformer_blocks." + std::to_string(k) + ".";
-            TBlock& tb = t.blocks[k];
-            tb.qkv8 = w8(b + "attn1.qkv.w"); tb.o1_8 = w8(b + "attn1.out.w"); tb.q2_8 = w8(b + "attn2.q.w");
-            tb.o2_8 = w8(b + "attn2.out.w"); tb.gg8 = w8(b + "ff.geglu.w"); tb.ff8 = w8(b + "ff.out.w");
-        }
-    };
-    for (int i = 0; i < 3; ++i) {
-        for (auto& t : u->down_tr[i]) resolve(t);
-        for (auto& t : u->up_tr[i]) resolve(t);
-    }
-    resolve(u->mid_tr);
+    each_transformer(u, [&](Transformer& t) {
+        for (int k = 0; k < t.depth; ++k) resolve_block(u, t.blocks[k], t.name + "transformer_blocks." + std::to_string(k) + ".", true, &ok);
+        return 0;
+    });
     if (!ok) return emu_ctx_fail(u->ctx, -2, u->err.c_str());
     u->fp8 = true;
     return 0;
@@ -502,7 +498,6 @@ int emu_unet_finalize(emu_unet* u) {
         resolve_resnet(u, r, &ok);
         return r;
     };
-    size_t coff = 0;
     auto mk_tr = [&](const std::string& name, int ch, int depth, int heads) {
         Transformer t{}; t.name = name; t.c = ch; t.depth = depth; t.heads = heads;
         resolve_transformer(u, t, &ok);
@@ -551,7 +546,6 @@ int emu_unet_finalize(emu_unet* u) {
             u->up_us_w[i] = find(u, p + "w", true, &ok); u->up_us_b[i] = find(u, p + "b", true, &ok);
         }
     }
-    (void)coff;
     u->temb_total = toff;
     if (!ok) return emu_ctx_fail(u->ctx, -2, u->err.c_str());
     u->fusion = u->fusion_avail;
@@ -566,6 +560,12 @@ int emu_unet_set_fusion(emu_unet* u, int mask) {
     return u->fusion;
 }
 
+int emu_unet_block_plan(int fp8, int fusion, int M, int C, int HW, int n_ctx, int depth) {
+    if ((fp8 | 1) != 1 || (fusion | 7) != 7 || HW < 1 || M < HW || M % HW || C < 1 || n_ctx < 1 || depth < 0) return -22;
+    const BlockPlan p = unet_block_plan(fp8 != 0, fusion, M, C, HW, n_ctx, depth);
+    return p.fp8 | p.ln_fold << 1 | p.vt_epilogue << 2 | p.cross_epilogue << 3 | p.prefetch << 4;
+}
+
 int emu_unet_temb_total(const emu_unet* u) { return u ? u->temb_total : 0; }
 
 size_t emu_unet_workspace_bytes(const emu_unet* u, int H, int W) {
@@ -578,9 +578,7 @@ size_t emu_unet_context_bytes(const emu_unet* u, int n_ctx) {
     if (!u || !u->finalized) return 0;
     const size_t npad = (size_t)(n_ctx + 63) / 64 * 64;
     size_t el = 0;
-    auto add = [&](const Transformer& t) { el += t.blocks.size() * ((size_t)2 * n_ctx * 2 * t.c + (size_t)2 * t.c * npad); };
-    for (int i = 0; i < 3; ++i) { for (auto& t : u->down_tr[i]) add(t); for (auto& t : u->up_tr[i]) add(t); }
-    add(u->mid_tr);
+    each_transformer(u, [&](const Transformer& t) { el += t.blocks.size() * ((size_t)2 * n_ctx * 2 * t.c + (size_t)2 * t.c * npad); return 0; });
     return el * 2 + (size_t)2 * u->cfg.temb_dim * 2 + 256;
 }
 
@@ -598,7 +596,7 @@ int emu_unet_set_context(emu_unet* u, const void* ctx_tokens, int n_ctx, const v
     bf16_t* base = reinterpret_cast<bf16_t*>(cache);
     size_t off = 0;
     u->n_ctx = n_ctx;
-    auto run = [&](Transformer& t) -> int {
+    UPASS(each_transformer(u, [&](Transformer& t) -> int {
         for (TBlock& tb : t.blocks) {
             tb.ctx_off = off;
             bf16_t* kv = base + off;
@@ -609,10 +607,7 @@ int emu_unet_set_context(emu_unet* u, const void* ctx_tokens, int n_ctx, const v
             off += (size_t)Bn * n_ctx * 2 * t.c + (size_t)Bn * t.c * npad;
         }
         return 0;
-    };
-    for (int i = 0; i < 3; ++i) for (auto& t : u->down_tr[i]) { int st = run(t); if (st) return st; }
-    { int st = run(u->mid_tr); if (st) return st; }
-    for (int i = 0; i < 3; ++i) for (auto& t : u->up_tr[i]) { int st = run(t); if (st) return st; }
+    }));
     bf16_t* aug = base + off;
     bf16_t* tmp = reinterpret_cast<bf16_t*>(workspace);
     UTRY(gemm(u, B16(add_in), u->ae1w, u->ae1b, nullptr, tmp, Bn, u->cfg.temb_dim, add_dim, add_dim, 0, u->cfg.temb_dim, EPI_SILU, s));
@@ -642,8 +637,8 @@ static int unet_body(emu_unet* u, const Ws& w, int H, int W, const bf16_t* temb_
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < c.layers_per_block; ++j) {
             bf16_t* dst = c.attn[i] ? w.hA : w.skip[k];
-            { int st = run_resnet(u, u->down_res[i][j], h, dst, w, Bn, hs[i], wsz[i], s); if (st) return st; }
-            if (c.attn[i]) { int st = run_transformer(u, u->down_tr[i][j], dst, w.skip[k], w, Bn, hs[i], wsz[i], s); if (st) return st; }
+            UPASS(run_resnet(u, u->down_res[i][j], h, dst, w, Bn, hs[i], wsz[i], s));
+            if (c.attn[i]) UPASS(run_transformer(u, u->down_tr[i][j], dst, w.skip[k], w, Bn, hs[i], wsz[i], s));
             h = w.skip[k++];
         }
         if (i < 2) {
@@ -652,9 +647,9 @@ static int unet_body(emu_unet* u, const Ws& w, int H, int W, const bf16_t* temb_
         }
     }
     // ---- mid
-    { int st = run_resnet(u, u->mid_res[0], h, w.hA, w, Bn, hs[2], wsz[2], s); if (st) return st; }
-    { int st = run_transformer(u, u->mid_tr, w.hA, w.hB, w, Bn, hs[2], wsz[2], s); if (st) return st; }
-    { int st = run_resnet(u, u->mid_res[1], w.hB, w.hA, w, Bn, hs[2], wsz[2], s); if (st) return st; }
+    UPASS(run_resnet(u, u->mid_res[0], h, w.hA, w, Bn, hs[2], wsz[2], s));
+    UPASS(run_transformer(u, u->mid_tr, w.hA, w.hB, w, Bn, hs[2], wsz[2], s));
+    UPASS(run_resnet(u, u->mid_res[1], w.hB, w.hA, w, Bn, hs[2], wsz[2], s));
     bf16_t* cur = w.hA;
     bf16_t* oth = w.hB;
     int cur_c = c.ch[2];
@@ -666,13 +661,9 @@ static int unet_body(emu_unet* u, const Ws& w, int H, int W, const bf16_t* temb_
             const bf16_t* skip = w.skip[--k];
             const int skip_c = r.cin - cur_c;
             UTRY(launch_concat_channels(cur, skip, w.cat, Bn * hs[lvl] * wsz[lvl], cur_c, skip_c, s));
-            if (c.attn[lvl]) {
-                { int st = run_resnet(u, r, w.cat, oth, w, Bn, hs[lvl], wsz[lvl], s); if (st) return st; }
-                { int st = run_transformer(u, u->up_tr[i][j], oth, cur, w, Bn, hs[lvl], wsz[lvl], s); if (st) return st; }
-            } else {
-                { int st = run_resnet(u, r, w.cat, oth, w, Bn, hs[lvl], wsz[lvl], s); if (st) return st; }
-                std::swap(cur, oth);
-            }
+            UPASS(run_resnet(u, r, w.cat, oth, w, Bn, hs[lvl], wsz[lvl], s));
+            if (c.attn[lvl]) UPASS(run_transformer(u, u->up_tr[i][j], oth, cur, w, Bn, hs[lvl], wsz[lvl], s));
+            else std::swap(cur, oth);
             cur_c = r.cout;
         }
         if (i < 2) {
@@ -699,7 +690,7 @@ int emu_unet_step(emu_unet* u, void* latents, int H, int W, const void* temb_tab
     UTRY(launch_unet_prep_input(reinterpret_cast<bf16_t*>(latents), reinterpret_cast<const float*>(sigmas), step_dev, w.colin,
                                 u->cfg.in_ch, H, W, u->cfg.kpad_in, s));
     bf16_t* eps = w.t1;                                  // [2*H*W, 4], t1 is free once the last resnet is done
-    { int st = unet_body(u, w, H, W, B16(temb_table), step_dev, eps, s); if (st) return st; }
+    UPASS(unet_body(u, w, H, W, B16(temb_table), step_dev, eps, s));
     UTRY(launch_cfg_euler_step(eps, reinterpret_cast<bf16_t*>(latents), reinterpret_cast<const float*>(sigmas), step_dev, guidance,
                                u->cfg.in_ch, H * W, s));
     return 0;

@@ -722,6 +722,17 @@ int emu_unet_set_fusion(emu_unet* u, int mask);
  * V^T stores (1) and the cross-attention epilogue (2) stay in effect -- they work on finished sums -- the LayerNorm fold (0) has
  * no fp8 form.  Changes emu_unet_workspace_bytes; returns -2 when a copy is missing. */
 int emu_unet_use_fp8(emu_unet* u, int enable);
+/* CPU test hook (tests/test_unet_block_plan.py): the one rule by which a transformer's blocks pick their GEMM format and their
+ * fusions -- host arithmetic on integers, no HIP call, no engine.  fp8 0 / 1 as emu_unet_use_fp8 takes it, fusion 0..7 the mask in
+ * effect (emu_unet_set_fusion), M = rows of the token stream (batch elements x HW: 2 x HW for the CFG pair, HW for one row of it),
+ * C = the transformer's channels, HW = tokens per batch element, n_ctx = prompt tokens, depth = its blocks.  Returns a bit set:
+ *   1  fp8: the six GEMMs of a block run W8A8 (fp8 on, M > 8, C a multiple of 128 and <= 2048)
+ *   2  ln_fold: the LayerNorms are folded into their consumer GEMMs (not fp8, fusion bit 0, M > 8, C a multiple of 128)
+ *   4  vt_epilogue: the qkv projection stores V^T (fusion bit 1, M > 8, HW a multiple of 64)
+ *   8  cross_epilogue: cross-attention inside the to_q projection (fusion bit 2, M > 8, HW a multiple of 64, n_ctx <= 64)
+ *  16  prefetch: every GEMM of the chain requests its successor's weights (not fp8, M > 8, depth > 0)
+ * M <= 8 is the few-row stream, which fuses nothing: 0.  -22: an argument outside its range, or M no multiple of HW. */
+int emu_unet_block_plan(int fp8, int fusion, int M, int C, int HW, int n_ctx, int depth);
 int emu_unet_temb_total(const emu_unet* u);               /* rows of temb_proj_all (sum of resnet out channels) */
 size_t emu_unet_workspace_bytes(const emu_unet* u, int H, int W);
 size_t emu_unet_context_bytes(const emu_unet* u, int n_ctx);

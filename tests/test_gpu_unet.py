@@ -384,3 +384,44 @@ def test_successor_prefetch_changes_no_bit(tiny_unet):
     for x, y in zip(outs[0], outs[1 << 16]):
         assert torch.equal(x, y)
     assert torch.equal(outs[0][1], outs[0][2])
+
+
+def test_fp8_blocks_exact_identities(tiny_unet):
+    """emu_unet_use_fp8 on the tiny UNet, exact identities only (no tolerance): the V^T epilogue changes no arithmetic in fp8 mode
+    either (mask 2 = mask 0, mask 6 = mask 4); the LayerNorm fold has no fp8 form and both attention levels of this engine (128 and
+    256 channels) take fp8, so mask 1 = mask 0; a forward repeats itself; the result is finite and is not the bf16 one;
+    use_fp8(False) brings the bf16 forward back bit for bit; a 2-step loop replayed from the captured graph equals the eager one.
+    16 x 16 latents: both levels above 8 rows, level 1 on whole 64-key groups.  (8 x 8 latents leave level 2 with 8 rows, and the
+    few-row stream has no GEGLU epilogue: emu_unet_forward answers -22 there in either mode.)"""
+    eng, W, ocfg = tiny_unet
+    side = 16
+    prompt = rnd(2, 8, 128, seed=91)
+    sch = eng.set_timesteps(4)
+    eng.set_context(prompt.cuda(), 8 * side, 8 * side)
+    lat = (rnd(1, 4, side, side, seed=92).float() * sch.init_noise_sigma).to(BF16).cuda().contiguous()
+    outs = {}
+    try:
+        assert eng.set_fusion(0) == 0
+        bf16 = eng.forward(lat, 0).clone()
+        eng.use_fp8(True)
+        for mask in (0, 1, 2, 4, 6):
+            assert eng.set_fusion(mask) == mask
+            outs[mask] = eng.forward(lat, 0).clone()
+        assert torch.equal(outs[2], outs[0]) and torch.equal(outs[6], outs[4])
+        assert torch.equal(outs[1], outs[0])
+        assert torch.equal(eng.forward(lat, 0), outs[6])
+        assert all(bool(torch.isfinite(o.float()).all()) for o in outs.values())
+        assert not torch.equal(outs[0], bf16)
+        eng.set_fusion(7)
+        eng.set_timesteps(4)
+        a = eng.denoise(lat.clone(), 3.0, use_graph=False, steps=2).clone()
+        eng.set_timesteps(4)
+        eng._graph = None
+        b = eng.denoise(lat.clone(), 3.0, use_graph=True, steps=2).clone()
+        assert torch.equal(a, b) and bool(torch.isfinite(a.float()).all())
+        eng.use_fp8(False)
+        assert eng.set_fusion(0) == 0
+        assert torch.equal(eng.forward(lat, 0), bf16)
+    finally:
+        eng.use_fp8(False)
+        eng.set_fusion(7)
