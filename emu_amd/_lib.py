@@ -63,6 +63,15 @@ class WarmPlanC(C.Structure):
                [(n, C.c_uint) for n in ("block_bytes", "row_bytes", "head_bytes", "nsucc", "gx", "first", "ntouch", "lanes", "xcds")]
 
 
+class SampleParamsC(C.Structure):
+    """emu_sample_params (include/emu_hip.h)."""
+    _fields_ = [("repetition_penalty", f32), ("suppress_id", i32), ("min_len", i32), ("do_sample", i32), ("temperature", f32),
+                ("top_k", i32), ("top_p", f32), ("min_keep", i32), ("eos_id", i32), ("pad_id", i32)]
+
+
+SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
+
+
 class UNetCfgC(C.Structure):
     _fields_ = [("in_ch", i32), ("out_ch", i32), ("ch", i32 * 3), ("layers_per_block", i32), ("depth", i32 * 3),
                 ("heads", i32 * 3), ("attn", i32 * 3), ("cross_dim", i32), ("groups", i32), ("gn_eps", f32),
@@ -120,6 +129,7 @@ _PROTOS = {
     "emu_embed_gather_bf16": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "emu_scatter_rows_bf16": (i32, [vp, vp, vp, i32, i32, vp]),
     "emu_argmax_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "emu_sample_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32, vp]),
     "emu_patchify": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "emu_image_resample_ws_bytes": (sz, [i32, i32, i32]),
     "emu_image_resample_norm": (i32, [vp, lng, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp]),
@@ -159,6 +169,8 @@ _PROTOS = {
     "emu_llama_final_norm": (i32, [vp, vp, vp, i32, vp]),
     "emu_llama_logits": (i32, [vp, vp, i32, i32, vp, i32, vp, sz, vp]),
     "emu_llama_greedy_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, sz, vp]),
+    "emu_llama_sample_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
+                                    C.POINTER(SampleParamsC), vp]),
     "emu_vit_create": (i32, [vp, C.POINTER(VitCfgC), C.POINTER(vp)]),
     "emu_vit_destroy": (None, [vp]),
     "emu_vit_set_stem": (i32, [vp, vp, vp, vp, vp]),

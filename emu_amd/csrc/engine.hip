@@ -521,6 +521,12 @@ int emu_scatter_rows_bf16(const void* src, const int32_t* dst_rows, void* out, i
 int emu_argmax_bf16(const void* logits, int ld, int rows, int vocab, int suppress_id, int32_t* out, emu_stream_t s) {
     return launch_argmax(B(logits), ld, rows, vocab, suppress_id, out, S(s));
 }
+int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                    const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
+                    int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, emu_stream_t s) {
+    return launch_sample(B(logits), ld, rows, vocab, hist, hist_ld, hist_rows, step_dev, uniforms, uni_ld, uni_rows, params, unfinished,
+                         out, probs_out, ld_probs, S(s));
+}
 int emu_patchify(const void* image, int image_is_f32, void* out, int Bn, int C, int HW, int patch, int Kpad, emu_stream_t s) {
     return launch_patchify(image, image_is_f32, B(out), Bn, C, HW, patch, Kpad, S(s));
 }
@@ -1539,6 +1545,23 @@ int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
     TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
     TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
+    TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, S(s)));
+    return 0;
+}
+
+int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                          int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
+                          int32_t* unfinished, const emu_sample_params* params, emu_stream_t s) {
+    if (!m || !m->embed || !params || !unfinished || max_new < 1) return -22;
+    const emu_llama_cfg& c = m->cfg;
+    if (c.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;                // refused before anything is launched
+    TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
+    TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
+    TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
+    // the ids of steps 0 .. step - 1 in out_ids are the history; the selection goes to cur_ids and the advance files it at `step`
+    TRY(m->ctx, launch_sample(B(logits), ld_logits, Bn, c.vocab, out_ids, Bn, max_new, step_dev, uniforms, Bn, max_new, params,
+                              unfinished, cur_ids, nullptr, 0, S(s)));
     TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, S(s)));
     return 0;
 }

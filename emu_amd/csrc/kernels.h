@@ -249,6 +249,10 @@ int launch_embed_gather(const int32_t* ids, const bf16_t* table, bf16_t* out, in
 // out[dst_rows[i], :] = src[i, :]
 int launch_scatter_rows(const bf16_t* src, const int32_t* dst_rows, bf16_t* out, int n_rows, int hidden, hipStream_t s);
 int launch_argmax(const bf16_t* logits, int ld, int rows, int vocab, int suppress_id, int32_t* out, hipStream_t s);
+// sample.hip: emu_sample_bf16 (include/emu_hip.h)
+int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                  const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* p,
+                  int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, hipStream_t s);
 // NCHW fp32/bf16 image -> [B*gh*gw, Kpad] bf16 patch matrix (k = c*p*p + i*p + j, zero padded to Kpad)
 int launch_patchify(const void* image, int image_is_f32, bf16_t* out, int B, int C, int HW, int p, int Kpad, hipStream_t s);
 // tokens [B, 1+g*g, C] (cls dropped) -> [B, (g/s)^2, C] average over s x s windows (emu.py:82-89)

@@ -69,8 +69,13 @@ class _Decoder:
 class EmuModel:
     def __init__(self, vision_cfg: CLIPVisionCfg = CLIPVisionCfg(), text_decoder_cfg: TextDecoderCfg = TextDecoderCfg(),
                  *, llama_cfg: Optional[LlamaCfg] = None, device="cuda", tp_rank: int = 0, tp_size: int = 1,
-                 ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None):
-        """``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
+                 ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None,
+                 device_sampler: Optional[bool] = None):
+        """``device_sampler`` (default: the ``EMU_DEVICE_SAMPLER`` environment variable, off unless "1"): sampling and penalised
+        greedy generation (one beam) keep their token loop on the device (``LlamaEngine.sample_generate(device_sampler=True)``:
+        uniforms drawn once up front, so a different random stream from the default's ``torch.multinomial``).
+
+        ``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
         parallelism a prompt with ONE image splits its ViT encode across the ranks by token rows (``encode_image``) instead of every
         rank encoding the whole image.  Opt-in until a multi-GPU node has measured it."""
         from .vit import VitEngine
@@ -96,6 +101,9 @@ class EmuModel:
             vit_token_parallel = os.environ.get("EMU_VIT_TOKEN_PARALLEL", "0") == "1"
         self.vit_token_parallel = bool(vit_token_parallel)
         self._vit_tp_ready = False
+        if device_sampler is None:
+            device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
+        self.device_sampler = bool(device_sampler)
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -276,7 +284,10 @@ class EmuModel:
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
             return self.decoder.lm.sample_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len, do_sample,
                                                    temperature, top_k, top_p, repetition_penalty, eos_id=eos,
-                                                   pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram, num_return_sequences=nret)
+                                                   pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram, num_return_sequences=nret,
+                                                   # the n-gram ban is not built on the device: it keeps the host loop
+                                                   device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram,
+                                                   use_graph=self.use_graph)
         return self.decoder.lm.greedy_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len,
                                                eos_id=eos, pad_id=PAD_TOKEN_ID, use_graph=self.use_graph,
                                                stop_on_eos=stop_on_eos)

@@ -12,6 +12,7 @@ instruct checkpoints must be merged beforehand.  PARITY UNPINNED (see oracle/emu
 from __future__ import annotations
 
 import math
+import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -209,7 +210,8 @@ class Emu:
 
     def __init__(self, vision_cfg: Optional[CLIPVisionCfg] = None, llama_cfg: Optional[LlamaCfg] = None,
                  t5_cfg: Optional[T5DecoderCfg] = None, vocab: int = 32006, device="cuda", instruct: bool = False,
-                 ctx: Optional[EmuHipContext] = None):
+                 ctx: Optional[EmuHipContext] = None, device_sampler: Optional[bool] = None):
+        """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1"): as ``EmuModel``'s option of that name."""
         self.vision_cfg = vision_cfg or emu1_vision_cfg()
         self.llama_cfg = llama_cfg or emu1_llama_cfg()
         self.t5_cfg = t5_cfg or T5DecoderCfg()
@@ -227,6 +229,9 @@ class Emu:
         self.n_causal = self.t5_cfg.n_causal
         self.image_placeholder = "[IMG]" + "<image>" * self.n_causal + "[/IMG]"
         self.tokenizer = None
+        if device_sampler is None:
+            device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
+        self.device_sampler = bool(device_sampler)
 
     def load_state_dict(self, sd, strict: bool = True, lora_r: int = 16, lora_alpha: float = 16.0):
         """Reference key names (Emu1/models/modeling_emu.py).  The instruct checkpoint is saved with peft LoRA adapters
@@ -297,7 +302,8 @@ class Emu:
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
             return self.lm.sample_generate(x, attention_mask, max_new_tokens, min_length, do_sample, temperature, top_k, top_p,
                                            repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID,
-                                           no_repeat_ngram_size=ngram, num_return_sequences=nret)
+                                           no_repeat_ngram_size=ngram, num_return_sequences=nret,
+                                           device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram)
         return self.lm.greedy_generate(x, attention_mask, max_new_tokens, min_length, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
 
     @torch.no_grad()

@@ -14,7 +14,7 @@ from typing import Dict, Iterable, Optional, Tuple
 import torch
 
 from . import mxfp4, ops
-from ._lib import EmuHipError, LlamaCfgC, check, lib
+from ._lib import SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .tp import ShardPlan
 
@@ -731,12 +731,39 @@ class LlamaEngine:
     def sample_generate(self, embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int, min_len: int = 1,
                         do_sample: bool = True, temperature: Optional[float] = None, top_k: Optional[int] = None,
                         top_p: Optional[float] = None, repetition_penalty: float = 1.0, eos_id: int = 2,
-                        pad_id: int = 32000, no_repeat_ngram_size: int = 0, num_return_sequences: int = 1) -> torch.Tensor:
+                        pad_id: int = 32000, no_repeat_ngram_size: int = 0, num_return_sequences: int = 1,
+                        device_sampler: bool = False, use_graph: bool = False,
+                        uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=1)`` with logits processing: repetition penalty, min_length, then
         (when sampling) temperature / top-k / top-p warpers and a multinomial draw from torch's global CUDA generator
         (transformers' processor order).  The decoder runs on the HIP engine; the tiny per-step logits post-processing is
         host-driven, so this path is not graph-replayed.  ``num_return_sequences`` = n samples every prompt n times (rows
-        prompt-major, as the library expands its inputs); without sampling the library refuses n > 1 and so does this."""
+        prompt-major, as the library expands its inputs); without sampling the library refuses n > 1 and so does this.
+
+        ``device_sampler=True`` (opt-in) keeps the token loop on the device instead: the first token comes from
+        ``emu_sample_bf16`` on the prefill logits, every further one from one ``emu_llama_sample_step`` call (embed -> layers ->
+        logits -> penalty / suppress / temperature / top-k / top-p / draw / EOS bookkeeping in one kernel -> state advance),
+        replayed from one hipGraph with ``use_graph``; the host only reads the rows' ``unfinished`` flags every ``EOS_POLL`` steps.
+        What is computed is specified in ``emu_amd/sampling.py``.  The draws use ``uniforms`` [max_new_tokens, rows] fp32 in [0, 1)
+        -- by default ONE ``torch.rand`` from the global generator up front: seed-stable, but a different random stream from the
+        host path's ``multinomial``, which is why this is an option.  Refused with a ValueError before any device work:
+        ``no_repeat_ngram_size > 0`` (the n-gram ban keeps the host path) and tensor parallelism (the ranks would need one shared
+        table of uniforms).  A vocabulary above the kernel's bound (``_lib.SAMPLE_MAX_VOCAB``, where ``emu_sample_bf16`` answers
+        -22) stays on the host path with one warning."""
+        if device_sampler:
+            if int(no_repeat_ngram_size or 0) > 0:
+                raise ValueError("device_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
+                                 "(device_sampler=False)")
+            if self.ctx.tp_size > 1:
+                raise ValueError("device_sampler: not built for tensor parallelism (the ranks would need one shared table of "
+                                 "uniforms); use device_sampler=False")
+            if self.vocab > SAMPLE_MAX_VOCAB:
+                if not LlamaEngine._warned_sampler_vocab:
+                    LlamaEngine._warned_sampler_vocab = True
+                    import warnings
+                    warnings.warn(f"emu_amd: device_sampler: vocabulary {self.vocab} is above the sample kernel's bound "
+                                  f"{SAMPLE_MAX_VOCAB} (emu_sample_bf16 answers -22); staying on the host path", stacklevel=2)
+                device_sampler = False
         if num_return_sequences > 1:
             if not do_sample:
                 raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1")
@@ -745,8 +772,13 @@ class LlamaEngine:
         B, S, H = embeds.shape
         dev = self.device
         s_max = self.kv_capacity(S + max_new_tokens)
+        if device_sampler and uniforms is not None and tuple(uniforms.shape) != (max_new_tokens, B):
+            raise ValueError(f"uniforms must be [max_new_tokens, rows] = [{max_new_tokens}, {B}], got {tuple(uniforms.shape)}")
         hidden, kstart, pos = self.prefill(embeds, attention_mask, s_max)
         row = hidden[:, -1, :]
+        if device_sampler:
+            return self._sample_device(row, B, S, kstart, pos, max_new_tokens, min_len, do_sample, temperature, top_k, top_p,
+                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms)
         out = torch.full((B, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
         unfinished = torch.ones(B, dtype=torch.int64, device=dev)
         hid = torch.empty(B, H, device=dev, dtype=BF16)
@@ -771,6 +803,38 @@ class LlamaEngine:
             row = hid
         self.ctx.check_p2p()
         return out[:, :n]
+
+    _warned_sampler_vocab = False          # one warning per process (sample_generate)
+
+    def _sample_device(self, row: torch.Tensor, B: int, S: int, kstart: torch.Tensor, next_pos: torch.Tensor, max_new: int,
+                       min_len: int, do_sample: bool, temperature, top_k, top_p, repetition_penalty: float, eos_id: int,
+                       pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor]) -> torch.Tensor:
+        """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill."""
+        dev = self.device
+        if do_sample:
+            uni = torch.rand(max_new, B, dtype=torch.float32, device=dev) if uniforms is None else \
+                uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            uni = None
+        out_ids = torch.full((max_new, B), pad_id, device=dev, dtype=torch.int32)
+        st = SampleState(self, B, next_pos, S, kstart, out_ids, uni,
+                         sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id))
+        self.logits(row, out=st.logits)
+        st.first()
+        steps = max_new - 1
+        for i in range(steps):
+            if use_graph:
+                st.step_graph()
+            else:
+                st.step()
+            # the only host read: the rows' flags, every EOS_POLL steps (the launches in between stay queued ahead)
+            if (i + 1) % EOS_POLL == 0 and i + 1 < steps and not bool(st.unfinished.any()):
+                break
+        ids = out_ids.t().to(torch.int64)
+        self.ctx.check_p2p()
+        # a finished row emitted PAD on the device; steps between the last row's EOS and the poll that saw it are cut off here:
+        # the width is one past the last step at which any row was still unfinished, the host path's rule
+        return apply_eos_padding(ids, eos_id, pad_id)
 
     # ------------------------------------------------------------------ contrastive search
     @torch.no_grad()
@@ -1201,6 +1265,65 @@ def apply_eos_padding(ids: torch.Tensor, eos_id: int, pad_id: int) -> torch.Tens
     ids[ar > first[:, None]] = pad_id
     keep = int(min(n, int(first.max().item()) + 1))
     return ids[:, :keep]
+
+
+def sample_params(do_sample: bool, temperature, top_k, top_p, repetition_penalty: float, suppress_id: Optional[int], min_len: int,
+                  eos_id: int, pad_id: int, min_keep: int = 1) -> SampleParamsC:
+    """The options of ``emu_sample_bf16`` / ``emu_llama_sample_step`` (include/emu_hip.h: emu_sample_params) from generate's."""
+    return SampleParamsC(float(repetition_penalty), -1 if suppress_id is None else int(suppress_id), int(min_len), int(bool(do_sample)),
+                         1.0 if temperature is None else float(temperature), 0 if top_k is None else int(top_k),
+                         1.0 if top_p is None else float(top_p), int(min_keep), int(eos_id), int(pad_id))
+
+
+class SampleState:
+    """Device-resident state of the sampling / penalised-greedy token loop (see emu_llama_sample_step): GreedyState's arrays, the
+    rows' ``unfinished`` flags, the table of uniforms and the options.  ``out_ids`` [max_new, B] is also the penalty's history."""
+
+    def __init__(self, eng: "LlamaEngine", B: int, next_pos: torch.Tensor, S: int, kstart: torch.Tensor, out_ids: torch.Tensor,
+                 uniforms: Optional[torch.Tensor], params: SampleParamsC):
+        self.eng, self.B = eng, B
+        dev = eng.device
+        self.cur = torch.zeros(B, device=dev, dtype=torch.int32)
+        self.pos = next_pos.to(torch.int32).clone()
+        self.slot = torch.full((B,), S, device=dev, dtype=torch.int32)
+        self.ctx = torch.tensor([S + 1], device=dev, dtype=torch.int32)
+        self.step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.unfinished = torch.ones(B, device=dev, dtype=torch.int32)
+        self.kstart, self.out_ids, self.uniforms, self.params = kstart, out_ids, uniforms, params
+        self.max_new = out_ids.shape[0]
+        self.hidden = torch.empty(B, eng.cfg.hidden_size, device=dev, dtype=BF16)
+        self.logits = torch.empty(B, eng.vocab, device=dev, dtype=BF16)
+        self.ws = eng._workspace(B, 1)
+        self.graph, self._epoch = None, -1
+
+    def first(self) -> None:
+        """The first token, from ``self.logits`` (the prefill's last rows): step 0 of the table."""
+        ops.sample(self.logits, self.step_idx, self.params, self.cur, hist=self.out_ids, uniforms=self.uniforms,
+                   unfinished=self.unfinished)
+        self.out_ids[0] = self.cur
+        self.step_idx.fill_(1)
+
+    def step(self) -> None:
+        e = self.eng
+        check(lib().emu_llama_sample_step(e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(),
+                                          self.kstart.data_ptr(), self.ctx.data_ptr(), self.step_idx.data_ptr(),
+                                          self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
+                                          self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(),
+                                          ops._p(self.uniforms), self.unfinished.data_ptr(), C.byref(self.params),
+                                          ops.stream(e.device)),
+              "emu_llama_sample_step", e.ctx.handle)
+
+    def step_graph(self) -> None:
+        """Replay the step from a hipGraph captured on first use; the kernel reads the step index from the device, so the one
+        captured step serves every token (the min-length suppress and the history length included)."""
+        if self.graph is None or self._epoch != self.eng.mode_epoch:
+            self.step()                                   # warm-up outside capture (it advances the state by one real step)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self.step()
+            self.graph, self._epoch = g, self.eng.mode_epoch
+            return
+        self.graph.replay()
 
 
 class GreedyState:

@@ -5,6 +5,7 @@ PyTorch is only the allocator/stream provider here: every function hands raw dev
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
@@ -297,6 +298,30 @@ def argmax(logits, vocab: Optional[int] = None, suppress_id: int = -1, out=None)
         out = torch.empty(rows, device=logits.device, dtype=torch.int32)
     check(lib().emu_argmax_bf16(_p(logits), logits.stride(0), rows, vocab, suppress_id, _p(out), stream(logits)),
           "emu_argmax_bf16")
+    return out
+
+
+def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist=None, uniforms=None, unfinished=None,
+           probs_out=None):
+    """``emu_sample_bf16`` (include/emu_hip.h; specified in emu_amd/sampling.py): one token per row of bf16 ``logits`` [rows, >= vocab]
+    under ``params`` (``_lib.SampleParamsC``).  ``step_dev`` int32 [1] on the device = the step index the kernel reads: the number of
+    history rows of ``hist`` int32 [steps, rows] in use, the row of ``uniforms`` fp32 [steps, rows], the min-length comparison.
+    ``unfinished`` int32 [rows] and ``probs_out`` fp32 [rows, >= vocab] are optional.  Returns ``out`` int32 [rows]."""
+    _req(logits, "logits")
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else vocab
+    if out is None:
+        out = torch.empty(rows, device=logits.device, dtype=torch.int32)
+    for name, t, dt in (("step_dev", step_dev, torch.int32), ("hist", hist, torch.int32), ("uniforms", uniforms, torch.float32),
+                        ("unfinished", unfinished, torch.int32), ("probs_out", probs_out, torch.float32), ("out", out, torch.int32)):
+        if t is not None:
+            _req(t, name, dt)
+    check(lib().emu_sample_bf16(_p(logits), logits.stride(0), rows, vocab, _p(hist), hist.stride(0) if hist is not None else 0,
+                                hist.shape[0] if hist is not None else 0, _p(step_dev), _p(uniforms),
+                                uniforms.stride(0) if uniforms is not None else 0, uniforms.shape[0] if uniforms is not None else 0,
+                                C.byref(params), _p(unfinished), _p(out), _p(probs_out),
+                                probs_out.stride(0) if probs_out is not None else 0, stream(logits)),
+          "emu_sample_bf16")
     return out
 
 

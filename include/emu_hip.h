@@ -334,6 +334,37 @@ int emu_scatter_rows_bf16(const void* src, const int32_t* dst_rows, void* out, i
  * EOS while fewer than min_length tokens exist, else -1.  First index wins ties. */
 int emu_argmax_bf16(const void* logits, int ld, int rows, int vocab, int suppress_id, int32_t* out,
                     emu_stream_t s);
+/* Next-token selection with the logits pipeline of lm.generate(num_beams=1, do_sample=..., temperature, top_k, top_p,
+ * repetition_penalty, min_length) (emu.py:213-229; the chat demo's chat.py:86-148 runs it with temperature 0.7, top_p 0.9) in ONE
+ * launch, one workgroup per row; the specification is emu_amd/sampling.py.  In transformers' order: s = float(logit); repetition
+ * penalty once per distinct id of the row's history (s < 0 ? s * pen : s / pen, ids outside [0, vocab) ignored); s[suppress_id] = -inf
+ * while step < min_len; then do_sample = 0: first index of the maximum; do_sample = 1: s / temperature, top-k with k' = min(max(top_k,
+ * min_keep), vocab) (ties with the k'-th value stay; top_k <= 0 = off), top-p (token i stays iff the softmax mass of {j: s_j <= s_i}
+ * exceeds 1 - top_p, or s_i >= the min_keep-th largest value; ties at the threshold stay as a group; top_p >= 1 = off), and the draw:
+ * the lowest id whose inclusive cumulative probability over the kept tokens in ascending id order exceeds u (rounding left u at or
+ * beyond the total: the highest kept id). */
+typedef struct emu_sample_params {
+    float repetition_penalty;      /* 1 = off */
+    int suppress_id, min_len;      /* suppress_id < 0 = off */
+    int do_sample;
+    float temperature;             /* > 0 */
+    int top_k;
+    float top_p;                   /* (0, 1]; >= 1 = off */
+    int min_keep;                  /* >= 1 */
+    int eos_id, pad_id;
+} emu_sample_params;
+#define EMU_SAMPLE_MAX_VOCAB 40000 /* the row is held as 4 bytes per token in the CU's 160 KiB of LDS */
+/* logits: bf16 rows `ld` elements apart, any 2-byte-aligned base.  step_dev: device int32[1], read by the kernel (never a host
+ * scalar, so one captured graph serves every step): the row's history is hist[t * hist_ld + row] for t < min(step, hist_rows) (hist
+ * may be NULL), its uniform is uniforms[min(step, uni_rows - 1) * uni_ld + row] (fp32 in [0, 1); needed when do_sample), and the
+ * min-length suppress applies while step < min_len.  unfinished (device int32 [rows], may be NULL): a row whose flag is 0 emits
+ * pad_id and nothing else of it is written; a row that selects eos_id clears its flag.  out: int32 [rows].  probs_out (may be NULL;
+ * do_sample only): fp32 rows ld_probs apart receive the probabilities the draw was made from, exactly 0 for removed tokens.
+ * No allocation, no synchronisation: capturable.  The same inputs give the same outputs bit for bit.
+ * -22: vocab > EMU_SAMPLE_MAX_VOCAB (nothing is launched or written), or an argument out of range. */
+int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                    const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
+                    int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, emu_stream_t s);
 /* PatchEmbed conv as im2col (eva_vit.py:327-335): image NCHW (fp32 or bf16) -> [B*g*g, Kpad] bf16 */
 int emu_patchify(const void* image, int image_is_f32, void* out, int B, int C, int HW, int patch, int Kpad,
                  emu_stream_t s);
@@ -580,6 +611,14 @@ int emu_llama_greedy_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, i
                           int ctx_upper, void* hidden, void* logits, int ld_logits, void* workspace,
                           size_t ws_bytes, emu_stream_t s);
 
+/* emu_llama_greedy_step with emu_sample_bf16 in the place of the arg-max (emu.py:213-229 with do_sample / repetition_penalty; the
+ * demo's chat.py:86-148): embed(cur_ids) -> layers -> logits -> select -> out_ids[step_dev[0], :] = cur_ids = next; pos / slot / ctx /
+ * step advance by one.  out_ids [max_new, B] is also the history the penalty reads; uniforms fp32 [max_new, B] (may be NULL without
+ * do_sample); unfinished int32 [B].  Graph-capturable: one captured step replays for every token. */
+int emu_llama_sample_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                          int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
+                          int32_t* unfinished, const emu_sample_params* params, emu_stream_t s);
 /* One step of transformers' beam search (lm.generate(num_beams=N), Emu2/emu/emu.py:163-172,213-229: the library's BeamSearchScorer
  * logic in its vectorised form), deterministic mode, in two launches: log-softmax of the N beams' logit rows of every prompt, the 2N
  * best continuations over beams x vocabulary of (log p + running score) with EOS masked while cur < min_len, then the bookkeeping --
