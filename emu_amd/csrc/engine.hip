@@ -1472,6 +1472,28 @@ int emu_beam_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, 
     return launch_beam_step(a, reinterpret_cast<float*>(workspace), ws_bytes / sizeof(float), S(s));
 }
 
+size_t emu_beam_sample_workspace_bytes(int Bn, int nb, int V) { return beam_sample_ws_floats(Bn, nb, V) * sizeof(float); }
+int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
+                              int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                              float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                              unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                              const emu_sample_params* params, int warp_accumulated, const float* uniforms, int uni_rows,
+                              int32_t* draws_out, float* acc_out, long ld_acc, emu_stream_t s) {
+    if (!logits || !running_seq || !sequences || !running_scores || !beam_scores || !finished || !seq_len || !heuristic_open ||
+        !next_tok || !beam_flat || !params)
+        return -22;
+    BeamSampleArgs a;
+    a.st = BeamStepArgs{B(logits), ld_prompt, ld_beam, V, Bn, nb, L, cur, cur_dev, min_len, eos_id, length_penalty, hf431, running_seq,
+                        sequences, running_scores, beam_scores, finished, seq_len, heuristic_open, next_tok, beam_flat};
+    a.penalty = params->repetition_penalty;
+    a.do_sample = params->do_sample; a.temperature = params->temperature; a.top_k = params->top_k; a.top_p = params->top_p;
+    a.min_keep = params->min_keep < 2 ? 2 : params->min_keep;      // the library's warpers under beam search: one EOS id + 1
+    a.warp_accumulated = warp_accumulated;
+    a.uniforms = uniforms; a.uni_rows = uni_rows;
+    a.draws_out = draws_out; a.acc_out = acc_out; a.ld_acc = ld_acc;
+    return launch_beam_sample_step(a, reinterpret_cast<float*>(workspace), ws_bytes / sizeof(float), S(s));
+}
+
 int emu_regress_advance_bf16(const void* src, void* out_all, void* prev, int32_t* pos, int32_t* slot, int32_t* step_dev, int Bn,
                              int cols, emu_stream_t s) {
     if (!src || !out_all || !prev || !pos || !slot || !step_dev) return -22;

@@ -496,6 +496,18 @@ int launch_beam_reorder(bf16_t* kc, bf16_t* vc, const long* beam_flat, const int
                         int D, int nb, int slot0, int L, hipStream_t s);
 size_t beam_step_ws_floats(int B, int nb, int V);     // scratch of the two-launch step (chunk partials)
 int launch_beam_step(const BeamStepArgs& a, float* ws, size_t ws_floats, hipStream_t s);
+// One step of beam-search sampling / penalised beam search (beam_sample.hip): see emu_beam_sample_step_bf16 in include/emu_hip.h
+struct BeamSampleArgs {
+    BeamStepArgs st;                           // the step's logits, limits and state, as for launch_beam_step
+    float penalty;                             // repetition penalty over running_seq[b, j, :cur]; 1 = off
+    int do_sample; float temperature; int top_k; float top_p; int min_keep;
+    int warp_accumulated;                      // 1: the warpers act on lp + running score and the draws are sorted ("4.31" order)
+    const float* uniforms; int uni_rows;       // [uni_rows, B, 2 * nb]; the step's row is min(cur, uni_rows - 1)
+    int32_t* draws_out;                        // optional [B, 2 * nb]: flat indices in draw order
+    float* acc_out; long ld_acc;               // optional [B * nb] rows of V accumulated scores, ld_acc apart
+};
+size_t beam_sample_ws_floats(int B, int nb, int V);   // per row: the scores, their masses, the row maximum
+int launch_beam_sample_step(const BeamSampleArgs& a, float* ws, size_t ws_floats, hipStream_t s);
 
 // ---- UNet denoise helpers (unet.hip); activations are NHWC: [B, H*W, C] bf16
 // GroupNorm(groups, eps) (+ optional SiLU) over x [B, HW, C]: three launches (partial sums, finalize to per-(b, c)

@@ -70,10 +70,15 @@ class EmuModel:
     def __init__(self, vision_cfg: CLIPVisionCfg = CLIPVisionCfg(), text_decoder_cfg: TextDecoderCfg = TextDecoderCfg(),
                  *, llama_cfg: Optional[LlamaCfg] = None, device="cuda", tp_rank: int = 0, tp_size: int = 1,
                  ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None,
-                 device_sampler: Optional[bool] = None):
+                 device_sampler: Optional[bool] = None, device_beam_sampler: Optional[bool] = None):
         """``device_sampler`` (default: the ``EMU_DEVICE_SAMPLER`` environment variable, off unless "1"): sampling and penalised
         greedy generation (one beam) keep their token loop on the device (``LlamaEngine.sample_generate(device_sampler=True)``:
         uniforms drawn once up front, so a different random stream from the default's ``torch.multinomial``).
+
+        ``device_beam_sampler`` (default: the ``EMU_DEVICE_BEAM_SAMPLER`` environment variable, off unless "1"; an option of its
+        own, ``device_sampler`` does not switch it on): beam search with ``do_sample`` or a repetition penalty keeps its token loop
+        on the device too (``LlamaEngine.beam_search_generate(device_beam_sampler=True)``: one table of uniforms up front, again
+        another random stream than ``torch.multinomial``).
 
         ``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
         parallelism a prompt with ONE image splits its ViT encode across the ranks by token rows (``encode_image``) instead of every
@@ -104,6 +109,9 @@ class EmuModel:
         if device_sampler is None:
             device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
         self.device_sampler = bool(device_sampler)
+        if device_beam_sampler is None:
+            device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
+        self.device_beam_sampler = bool(device_beam_sampler)
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -276,11 +284,13 @@ class EmuModel:
                               "tests/golden/ (the library is not installable offline).  hf_semantics='5.x' is the mode pinned to the "
                               "installed library's ids; the two differ only where a hypothesis ends on EOS (INTEGRATION.md).",
                               stacklevel=2)
+            # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
+            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
             return self.decoder.lm.beam_search_generate(x.view(B, S, -1), attention_mask, num_beams, max_new_tokens, min_len,
                                                         length_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID,
                                                         do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
-                                                        num_return_sequences=nret, hf_semantics=sem)
+                                                        num_return_sequences=nret, hf_semantics=sem, **on_device)
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
             return self.decoder.lm.sample_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len, do_sample,
                                                    temperature, top_k, top_p, repetition_penalty, eos_id=eos,

@@ -210,8 +210,10 @@ class Emu:
 
     def __init__(self, vision_cfg: Optional[CLIPVisionCfg] = None, llama_cfg: Optional[LlamaCfg] = None,
                  t5_cfg: Optional[T5DecoderCfg] = None, vocab: int = 32006, device="cuda", instruct: bool = False,
-                 ctx: Optional[EmuHipContext] = None, device_sampler: Optional[bool] = None):
-        """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1"): as ``EmuModel``'s option of that name."""
+                 ctx: Optional[EmuHipContext] = None, device_sampler: Optional[bool] = None,
+                 device_beam_sampler: Optional[bool] = None):
+        """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1") and ``device_beam_sampler`` (default:
+        ``EMU_DEVICE_BEAM_SAMPLER``, off unless "1"): as ``EmuModel``'s options of those names."""
         self.vision_cfg = vision_cfg or emu1_vision_cfg()
         self.llama_cfg = llama_cfg or emu1_llama_cfg()
         self.t5_cfg = t5_cfg or T5DecoderCfg()
@@ -232,6 +234,9 @@ class Emu:
         if device_sampler is None:
             device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
         self.device_sampler = bool(device_sampler)
+        if device_beam_sampler is None:
+            device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
+        self.device_beam_sampler = bool(device_beam_sampler)
 
     def load_state_dict(self, sd, strict: bool = True, lora_r: int = 16, lora_alpha: float = 16.0):
         """Reference key names (Emu1/models/modeling_emu.py).  The instruct checkpoint is saved with peft LoRA adapters
@@ -293,12 +298,14 @@ class Emu:
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,
                                                 repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
         if num_beams > 1:
+            # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
+            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
             return self.lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_length, length_penalty,
                                                 eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, do_sample=do_sample,
                                                 temperature=temperature, top_k=top_k, top_p=top_p,
                                                 repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
                                                 num_return_sequences=nret,
-                                                hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"))
+                                                hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"), **on_device)
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
             return self.lm.sample_generate(x, attention_mask, max_new_tokens, min_length, do_sample, temperature, top_k, top_p,
                                            repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID,

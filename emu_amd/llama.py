@@ -16,6 +16,7 @@ import torch
 from . import mxfp4, ops
 from ._lib import SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
+from .sampling import beam_draw_margin, beam_reference_select
 from .tp import ShardPlan
 
 BF16 = torch.bfloat16
@@ -922,7 +923,8 @@ class LlamaEngine:
                              top_k: Optional[int] = None, top_p: Optional[float] = None,
                              repetition_penalty: float = 1.0, hf_semantics: str = "4.31",
                              trace: Optional[dict] = None, no_repeat_ngram_size: int = 0,
-                             num_return_sequences: int = 1) -> torch.Tensor:
+                             num_return_sequences: int = 1, uniforms: Optional[torch.Tensor] = None,
+                             device_beam_sampler: bool = False) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=N, do_sample=False, early_stopping=False)`` -- the reference's
         DEFAULT decoding mode (num_beams=5, length_penalty=-1, Emu2/emu/emu.py:163-172,213-229).  Restates
         transformers' vectorised beam search: per step keep the 2N best continuations over beams x vocab, the N best
@@ -959,13 +961,54 @@ class LlamaEngine:
         returns the n best results of every prompt ([B * n, len], prompt-major: what Emu1's ``num_captions`` asks for,
         Emu1/models/modeling_emu.py:110,173).
 
+        ``uniforms`` [max_new_tokens, B, 2 * num_beams] fp32 in [0, 1) (sampling only): the 2N continuations of step ``cur`` are
+        drawn from row ``cur`` of this table by the rule of ``emu_amd/sampling.py::beam_reference_select`` (masses in fp64) instead of
+        ``torch.multinomial`` -- another random stream, and the reference of the device loop below.  None (the default): the
+        multinomial draw from torch's global generator, as ever.  With a table, ties between candidate scores go to the first in
+        candidate order (stable top-k, the device kernels' rule; ``torch.topk`` leaves them open), so that the table alone decides.
+
+        ``device_beam_sampler=True`` (opt-in) keeps the token loop of beam-search sampling and of penalised beam search
+        (``do_sample`` or ``repetition_penalty != 1``) on the device: ``_beam_search_device`` with ``emu_beam_sample_step_bf16``
+        (csrc/beam_sample.hip) in place of ``emu_beam_step_bf16``, captured and replayed in the same way.  Its draws come from
+        ``uniforms``, by default ONE ``torch.rand(max_new_tokens, B, 2 * num_beams)`` from the global generator up front: seed-stable,
+        but a different random stream from ``multinomial``, which is why this is an option.  Refused with a ValueError before any
+        device work: ``no_repeat_ngram_size > 0`` and tensor parallelism (the ranks would need one shared table).  The host pipeline
+        takes over, with one warning per process, for more than 8 beams, more than 256 new tokens, a vocabulary above
+        ``_lib.SAMPLE_MAX_VOCAB`` or below 2N, or when a ``trace`` is asked for.  The deterministic, unpenalised search goes to its
+        own kernel whatever this flag says.
+
         ``trace`` (a dict, diagnostics for the tests): receives ``margin`` = the smallest gap seen between the N-th and the
-        (N+1)-th running candidate at a pruning step and between the two best final results."""
+        (N+1)-th running candidate at a pruning step and between the two best final results, and, with a table of uniforms,
+        ``draw_margin`` = the smallest distance seen of a draw's ``u * R`` from a boundary between two entries
+        (``sampling.beam_draw_margin``)."""
         if hf_semantics not in ("4.31", "5.x"):
             raise ValueError("hf_semantics must be '4.31' or '5.x'")
         if not 1 <= num_return_sequences <= num_beams:
             raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`")       # the library's own check
         ngram = int(no_repeat_ngram_size or 0)
+        if uniforms is not None and tuple(uniforms.shape) != (max_new_tokens, embeds.shape[0], 2 * num_beams):
+            raise ValueError(f"uniforms must be [max_new_tokens, prompts, 2 * num_beams] = "
+                             f"[{max_new_tokens}, {embeds.shape[0]}, {2 * num_beams}], got {tuple(uniforms.shape)}")
+        device_beam_sampler = bool(device_beam_sampler) and (do_sample or repetition_penalty != 1.0)
+        if device_beam_sampler:
+            if ngram > 0:
+                raise ValueError("device_beam_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
+                                 "(device_beam_sampler=False)")
+            if self.ctx.tp_size > 1:
+                raise ValueError("device_beam_sampler: not built for tensor parallelism (the ranks would need one shared table of "
+                                 "uniforms); use device_beam_sampler=False")
+            why = (f"{num_beams} beams (the kernel takes 8)" if num_beams > 8 else
+                   f"{max_new_tokens} new tokens (the kernel takes 256)" if max_new_tokens > 256 else
+                   f"vocabulary {self.vocab} above the kernel's bound {SAMPLE_MAX_VOCAB}" if self.vocab > SAMPLE_MAX_VOCAB else
+                   f"vocabulary {self.vocab} below 2 * num_beams" if self.vocab < 2 * num_beams else
+                   "a trace is asked for" if trace is not None else None)
+            if why is not None:
+                if not LlamaEngine._warned_beam_sampler:
+                    LlamaEngine._warned_beam_sampler = True
+                    import warnings
+                    warnings.warn(f"emu_amd: device_beam_sampler: {why} (emu_beam_sample_step_bf16 answers -22 outside its range); "
+                                  "staying on the host path", stacklevel=2)
+                device_beam_sampler = False
         B, S, H = embeds.shape
         nb, V, dev = num_beams, self.vocab, self.device
         s_max = self.kv_capacity(S + max_new_tokens)
@@ -984,6 +1027,13 @@ class LlamaEngine:
                 and V >= 2 * nb and hasattr(self, "handle") and logits.dtype == BF16):
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
                                             int(num_return_sequences), hf_semantics == "4.31")
+        if device_beam_sampler:
+            if not hasattr(self, "handle") or logits.dtype != BF16:
+                raise RuntimeError("device_beam_sampler needs the HIP engine and its bf16 logits")
+            return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
+                                            int(num_return_sequences), hf_semantics == "4.31",
+                                            sampler=(sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id,
+                                                                   min_len, eos_id, pad_id, min_keep=2), uniforms))
         logits = logits.float()
         running_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=dev)
         sequences = running_seq.clone()
@@ -1000,9 +1050,16 @@ class LlamaEngine:
 
         cur = 0
         lp_rows = logits[:, None, :].expand(B, nb, V)                                   # step 0: every beam = the prompt
-        margin = float("inf")
+        margin = draw_margin = float("inf")
         v431 = hf_semantics == "4.31"
         old = do_sample and v431
+        table = uniforms is not None and do_sample
+        # with a table the result has to be a function of the table alone, so ties between candidates (the rule, not the exception:
+        # at step 0 every beam holds the same hypothesis) go to the first in candidate order, the device kernels' rule
+        topk = torch.topk if not table else \
+            (lambda t, k: tuple(r[:, :k] for r in torch.sort(t, dim=1, descending=True, stable=True)))
+        # (such exact ties are decided alike on both sides and do not count as a margin)
+        gap = (lambda d: float(d.min())) if not table else (lambda d: float(d.masked_fill(d == 0, float("inf")).min()))
         while True:
             log_probs = torch.log_softmax(lp_rows, dim=-1)
             if do_sample or repetition_penalty != 1.0 or ngram:
@@ -1017,10 +1074,16 @@ class LlamaEngine:
                 acc = warp_logits(acc.reshape(B * nb, V), temperature, top_k, top_p, min_keep=2).view(B, nb, V)
             acc = acc.reshape(B, nb * V)
             if do_sample:
-                top_idx = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=2 * nb)
+                if table:                              # the draws of step cur from row cur of the table (emu_amd/sampling.py)
+                    u = uniforms[cur].to(torch.float32)
+                    top_idx = beam_reference_select(acc.view(B, nb, V), nb, u, True, "5.x", torch.float64)[1]
+                    if trace is not None:
+                        draw_margin = min(draw_margin, float(beam_draw_margin(acc.view(B, nb, V), nb, u, top_idx).min()))
+                else:
+                    top_idx = torch.multinomial(torch.softmax(acc, dim=-1), num_samples=2 * nb)
                 top_lp = torch.gather(acc, 1, top_idx)
                 if old:                                # ... and its draws are ranked before the beam scorer sees them
-                    top_lp, order = torch.sort(top_lp, descending=True, dim=1)
+                    top_lp, order = torch.sort(top_lp, descending=True, dim=1, stable=table)
                     top_idx = torch.gather(top_idx, 1, order)
             else:
                 top_lp, top_idx = torch.topk(acc, k=2 * nb)
@@ -1033,10 +1096,10 @@ class LlamaEngine:
             hits = (tok == eos_id) if v431 else (tok == eos_id) | at_limit
             # running beams for the next step: best N non-finished candidates
             run_lp = top_lp + hits.float() * NEG
-            nxt = torch.topk(run_lp, k=nb)[1]
+            nxt = topk(run_lp, k=nb)[1]
             if trace is not None and cur + 1 < max_len:
                 srt = torch.sort(run_lp, dim=1, descending=True)[0]
-                margin = min(margin, float((srt[:, nb - 1] - srt[:, nb]).min()))
+                margin = min(margin, gap(srt[:, nb - 1] - srt[:, nb]))
             running_seq = gather(cand_seq, nxt)
             running_scores = torch.gather(run_lp, 1, nxt)
             beam_idx = torch.gather(src_beam, 1, nxt)                                   # which old beam each new beam extends
@@ -1050,7 +1113,7 @@ class LlamaEngine:
             m_sc = torch.cat((beam_scores, fin_lp), dim=1)
             m_fin = torch.cat((finished, just), dim=1)
             m_len = torch.cat((seq_len, torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1)
-            keep = torch.topk(m_sc, k=nb)[1]
+            keep = topk(m_sc, k=nb)[1]
             sequences = gather(m_seq, keep)
             beam_scores = torch.gather(m_sc, 1, keep)
             finished = torch.gather(m_fin, 1, keep)
@@ -1065,7 +1128,7 @@ class LlamaEngine:
                 # 4.31 finalize: the running beams (now L tokens) join the kept results at L ** length_penalty unless done
                 fin2 = running_scores / float(cur ** length_penalty) + (~heuristic_open).float() * NEG
                 m_sc = torch.cat((beam_scores, fin2), dim=1)
-                keep = torch.topk(m_sc, k=nb)[1]
+                keep = topk(m_sc, k=nb)[1]
                 sequences = gather(torch.cat((sequences, running_seq), dim=1), keep)
                 beam_scores = torch.gather(m_sc, 1, keep)
                 finished = torch.gather(torch.cat((finished, torch.ones_like(finished)), dim=1), 1, keep)
@@ -1092,17 +1155,20 @@ class LlamaEngine:
         nret = int(num_return_sequences)
         out_len = int(seq_len[:, :nret].max().item())
         if trace is not None:
-            trace["margin"] = min(margin, float((beam_scores[:, 0] - beam_scores[:, 1]).min()))
+            trace["margin"] = min(margin, gap(beam_scores[:, 0] - beam_scores[:, 1]))
+            if table:
+                trace["draw_margin"] = draw_margin
         self.ctx.check_p2p()
         if nret == 1:
             return sequences[:, 0, :out_len]
         return sequences[:, :nret, :out_len].reshape(B * nret, out_len)
 
     BEAM_POLL = 4          # graph-replayed beam steps between two looks at the done flags
+    _warned_beam_sampler = False           # one warning per process (beam_search_generate(device_beam_sampler=True))
 
     def _beam_search_device(self, logits0: torch.Tensor, B: int, S: int, nb: int, max_len: int, min_len: int,
                             length_penalty: float, eos_id: int, pad_id: int, kstart_b: torch.Tensor, pos: torch.Tensor,
-                            nret: int, v431: bool = True) -> torch.Tensor:
+                            nret: int, v431: bool = True, sampler: Optional[tuple] = None) -> torch.Tensor:
         """The loop of ``beam_search_generate`` for the deterministic mode, with nothing left on the host but the replay of a
         hipGraph: per step {``emu_beam_advance`` (slot / position of the token to feed from the device-side step counter) ->
         ``emu_llama_beam_reorder_kv`` (the generated KV slots follow the beam permutation) -> embedding gather -> the decoder
@@ -1112,11 +1178,19 @@ class LlamaEngine:
         captured once per (prompt length, batch, beams, limits) on the persistent beam cache and replayed ``BEAM_POLL`` steps at
         a time between two reads of the done flags -- steps replayed beyond the end of the search change nothing (kept results
         are frozen once a prompt is done, and the kernels do nothing from the length limit on).  ``self.beam_graph = False``
-        runs the same launches eagerly."""
+        runs the same launches eagerly.
+
+        ``sampler`` = (options, table of uniforms or None) (``beam_search_generate(device_beam_sampler=True)``): the same loop with
+        ``emu_beam_sample_step_bf16`` (csrc/beam_sample.hip: beam-search sampling, penalised beam search) as its step.  The table
+        is copied into a buffer the captured graph owns, so a call with another table replays the same graph; under the "4.31"
+        order with sampling all N running scores start at 0, as on the host."""
         dev, V, rows = self.device, self.vocab, B * nb
         L = lib()
+        params = sampler[0] if sampler is not None else None
+        sampling = params is not None and bool(params.do_sample)
+        opts = None if params is None else (sampling, params.repetition_penalty, params.temperature, params.top_k, params.top_p)
         key = (B, nb, S, self.s_max, max_len, int(min_len), float(length_penalty), int(eos_id), bool(v431), self.kcache.data_ptr(),
-               self.mode_epoch)
+               self.mode_epoch, opts)
         cache = self.__dict__.setdefault("_beam_graphs", {})
         st = cache.get(key)
         if st is None:
@@ -1130,25 +1204,37 @@ class LlamaEngine:
                       hid=torch.empty(rows, self.cfg.hidden_size, device=dev, dtype=BF16), slot=torch.empty(rows, **i32),
                       pos=torch.empty(rows, **i32), pos0=torch.empty(rows, **i32), kstart=torch.empty(rows, **i32),
                       cur=torch.empty(1, **i32), lg=torch.empty(rows, V, device=dev, dtype=BF16),
-                      ws=torch.empty(L.emu_beam_step_workspace_bytes(B, nb, V), dtype=torch.uint8, device=dev), graph=None)
+                      ws=torch.empty((L.emu_beam_step_workspace_bytes if params is None else L.emu_beam_sample_workspace_bytes)(B, nb, V),
+                                     dtype=torch.uint8, device=dev), graph=None)
+            if sampling:
+                st["uni"] = torch.empty(max_len, B, 2 * nb, dtype=torch.float32, device=dev)
             # the decoder step's workspace: owned here, because the pointers a captured graph holds must outlive any
             # re-allocation of the engine's shared workspace by a later, larger call
             need = max(int(L.emu_llama_workspace_bytes(self.handle, rows, 1)), rows * self.cfg.hidden_size * 2)
             st["fws"] = torch.empty(need, dtype=torch.uint8, device=dev)
             cache[key] = st
         st["running_seq"].fill_(pad_id); st["sequences"].fill_(pad_id)
-        st["running_scores"].zero_(); st["running_scores"][:, 1:] = -1.0e9
+        st["running_scores"].zero_()
+        if not (sampling and v431):
+            st["running_scores"][:, 1:] = -1.0e9           # 4.31's beam_sample starts EVERY beam at 0 (the draws tell them apart)
+        if sampling:
+            table = sampler[1]
+            st["uni"].copy_(torch.rand(max_len, B, 2 * nb, dtype=torch.float32, device=dev) if table is None else table)
         st["beam_scores"].fill_(-1.0e9); st["finished"].zero_(); st["seq_len"].zero_(); st["still_open"].fill_(1)
         st["pos0"].copy_(pos); st["kstart"].copy_(kstart_b)
         stream = lambda: ops.stream(self.device)           # (inside a capture the current stream is the capturing one)
 
         def beam_step(lg, ld_prompt, ld_beam, cur, cur_dev):
-            check(L.emu_beam_step_bf16(lg.data_ptr(), ld_prompt, ld_beam, V, B, nb, max_len, cur, cur_dev, int(min_len), eos_id,
-                                       float(length_penalty), int(v431), st["running_seq"].data_ptr(), st["sequences"].data_ptr(),
-                                       st["running_scores"].data_ptr(), st["beam_scores"].data_ptr(), st["finished"].data_ptr(),
-                                       st["seq_len"].data_ptr(), st["still_open"].data_ptr(), st["next_tok"].data_ptr(),
-                                       st["beam_flat"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel(), stream()),
-                  "emu_beam_step_bf16", self.ctx.handle)
+            state = (lg.data_ptr(), ld_prompt, ld_beam, V, B, nb, max_len, cur, cur_dev, int(min_len), eos_id,
+                     float(length_penalty), int(v431), st["running_seq"].data_ptr(), st["sequences"].data_ptr(),
+                     st["running_scores"].data_ptr(), st["beam_scores"].data_ptr(), st["finished"].data_ptr(),
+                     st["seq_len"].data_ptr(), st["still_open"].data_ptr(), st["next_tok"].data_ptr(),
+                     st["beam_flat"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel())
+            if params is None:
+                check(L.emu_beam_step_bf16(*state, stream()), "emu_beam_step_bf16", self.ctx.handle)
+            else:
+                check(L.emu_beam_sample_step_bf16(*state, params, int(sampling and v431), st["uni"].data_ptr() if sampling else None,
+                                                  max_len, None, None, 0, stream()), "emu_beam_sample_step_bf16", self.ctx.handle)
 
         def body():
             """One step, every index read on the device."""

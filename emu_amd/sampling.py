@@ -157,3 +157,162 @@ def top_p_threshold_group(logits: torch.Tensor, **opts) -> Tuple[torch.Tensor, t
     last[:, :-1] = srt[:, :-1] != srt[:, 1:]
     margin = margin.masked_fill(~last | torch.isinf(srt), float("inf")).min(dim=-1)[0]
     return group, margin
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Beam-search sampling and penalised beam search (emu_amd/csrc/beam_sample.hip, ``emu_beam_sample_step_bf16``): what the two kernels
+# compute for the nb beam rows of every prompt.  Tested against the host pipeline of ``LlamaEngine.beam_search_generate``
+# (``log_softmax`` -> ``process_logits(min_keep=2)`` / ``warp_logits`` in the order's sequence), which with a table of uniforms draws by
+# ``beam_reference_select``.
+#
+# Per beam row (b, j), from its bf16 logits, the ids the beam has generated, its running score rs_j and the options:
+#
+# 1. ``lp = x - (m + log sum exp(x - m))`` with ``x = float32(logit)`` and m the row maximum; the subtraction is fp32, the sum is taken
+#    in ``dtype``.
+# 2. The processors act on lp: the repetition penalty of step 2 above (``lp < 0`` multiplies, otherwise divides; once per distinct
+#    history id; ids outside the vocabulary are ignored), then ``lp[eos] = -inf`` while ``cur < min_len``.
+# 3. The warpers are steps 5-7 above with ``min_keep = 2``.  ``order="5.x"``: they act on lp, and ``acc = warped + rs_j``;
+#    ``order="4.31"``: they act on ``lp + rs_j`` and acc is that warped row; ``do_sample=False`` (penalised beam search): no warpers,
+#    ``acc = lp + rs_j``.  All these sums are fp32; removed entries are -inf.
+#
+# Per prompt, over the flattened [nb * V] scores (flat index = j * V + id):
+#
+# * ``do_sample=False``: the 2N best; ties go to the lower flat index (beam.hip's rule).
+# * ``do_sample=True``: 2N draws without replacement, one uniform u_k each.  ``p = softmax(acc)`` in ``dtype``.  Draw k takes the
+#   lowest flat index not yet drawn whose inclusive cumulative mass -- over the not-yet-drawn entries only, in ascending flat index --
+#   exceeds ``u_k * R_k``, R_k the mass that remains; if rounding leaves ``u_k * R_k`` at or beyond the total, the highest remaining
+#   entry of positive mass.  When no positive mass remains (the "5.x" start: beams 1..N-1 carry -1e9, and with top_k = 3 beam 0 alone
+#   cannot supply ten tokens) the draw takes the lowest not-yet-drawn flat index whose acc is finite; removed entries are never drawn
+#   (with ``min_keep = 2`` there are always at least 2N finite entries).  Under ``order="4.31"`` the 2N draws are then sorted by score,
+#   descending, stably: equal scores keep draw order.
+# * The results are ``top_idx`` and ``top_lp = acc[top_idx]``, which the scorer's bookkeeping consumes unchanged.
+
+BEAM_MIN_KEEP = 2          # the library's min_tokens_to_keep under beam search: one EOS id + 1
+
+
+def _check_order(order: str) -> bool:
+    if order not in ("4.31", "5.x"):
+        raise ValueError("order must be '4.31' or '5.x'")
+    return order == "4.31"
+
+
+def _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype):
+    """Steps 1-2: the penalised, EOS-suppressed log-probabilities [R, vocab] fp32."""
+    x = logits.float()
+    m = x.max(dim=-1, keepdim=True)[0]
+    lse = m + torch.log(torch.exp((x - m).to(dtype)).sum(dim=-1, keepdim=True)).float()
+    return reference_scores(x - lse, history, repetition_penalty, eos_id if suppress_eos else None)
+
+
+def beam_reference_warp_input(logits: torch.Tensor, running_scores: torch.Tensor, history: History = None,
+                              repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
+                              order: str = "5.x", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The fp32 rows [R, vocab] the warpers act on (ahead of the temperature): steps 1-2, under ``order="4.31"`` with the running
+    score added."""
+    lp = _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype)
+    return lp + running_scores.reshape(-1, 1).float().to(lp.device) if _check_order(order) else lp
+
+
+def beam_reference_rows(logits: torch.Tensor, running_scores: torch.Tensor, history: History = None,
+                        repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
+                        do_sample: bool = True, temperature: Optional[float] = None, top_k: Optional[int] = None,
+                        top_p: Optional[float] = None, order: str = "5.x", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Steps 1-3: acc [R, vocab] fp32 of R beam rows (bf16 or fp32-held bf16 logits [R, vocab], running scores [R] or [B, nb], one
+    history per row), -inf for removed entries."""
+    accumulated = _check_order(order)
+    rs = running_scores.reshape(-1, 1).float().to(logits.device)
+    if not do_sample:
+        return _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype) + rs
+    w = beam_reference_warp_input(logits, running_scores, history, repetition_penalty, eos_id, suppress_eos, order, dtype)
+    s, kept = reference_warped(w, None, 1.0, None, temperature, top_k, top_p, BEAM_MIN_KEEP, dtype)
+    return (s if accumulated else s + rs).masked_fill(~kept, -float("inf"))
+
+
+def beam_reference_probs(acc: torch.Tensor, nb: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[B, nb * vocab] probabilities the draws are made from (``dtype``): softmax over the flattened rows of every prompt, exactly
+    0 for removed entries.  ``acc`` [B * nb, vocab] or [B, nb, vocab]."""
+    flat = acc.reshape(-1, nb * acc.shape[-1])
+    p = torch.softmax(flat.to(dtype), dim=-1)
+    return p.masked_fill(torch.isinf(flat) & (flat < 0), 0.0)
+
+
+def _draw_state(p_row: torch.Tensor, drawn):
+    rem = p_row.clone()
+    if drawn:
+        rem[torch.tensor(list(drawn), dtype=torch.int64, device=p_row.device)] = 0
+    return rem
+
+
+def _draw_one(rem: torch.Tensor, finite: torch.Tensor, u) -> int:
+    """One draw from the remaining masses ``rem`` (drawn entries zeroed; ``finite`` marks the not-yet-drawn entries of finite acc)."""
+    R = rem.sum()
+    if not bool(R > 0):
+        return int(torch.nonzero(finite)[0])
+    target = torch.as_tensor(u, dtype=rem.dtype, device=rem.device) * R
+    over = (rem.cumsum(dim=0) > target) & (rem > 0)
+    hit = torch.nonzero(over)
+    if hit.numel():
+        return int(hit[0])
+    return int(torch.nonzero(rem > 0)[-1])
+
+
+def beam_reference_select(acc: torch.Tensor, nb: int, uniforms: Optional[torch.Tensor] = None, do_sample: bool = True,
+                          order: str = "5.x", dtype: torch.dtype = torch.float32, return_draws: bool = False):
+    """The selection per prompt: (top_lp [B, 2 nb] fp32, top_idx [B, 2 nb] int64) of ``acc`` [B * nb, vocab] or [B, nb, vocab];
+    ``uniforms`` [B, 2 nb] when sampling.  ``return_draws`` adds the flat indices in draw order (before the "4.31" sort)."""
+    accumulated = _check_order(order)
+    flat = acc.reshape(-1, nb * acc.shape[-1])
+    B, n2 = flat.shape[0], 2 * nb
+    if not do_sample:
+        # stable descending order: equal scores keep ascending flat index
+        idx = torch.sort(flat, dim=-1, descending=True, stable=True)[1][:, :n2]
+        return (torch.gather(flat, 1, idx), idx, idx) if return_draws else (torch.gather(flat, 1, idx), idx)
+    p = beam_reference_probs(acc, nb, dtype)
+    u = uniforms.to(torch.float32).cpu()
+    draws = torch.empty(B, n2, dtype=torch.int64)
+    for b in range(B):
+        rem = p[b].clone()
+        finite = ~(torch.isinf(flat[b]) & (flat[b] < 0))
+        for k in range(n2):
+            i = _draw_one(rem, finite, float(u[b, k]))
+            draws[b, k] = i
+            rem[i] = 0
+            finite[i] = False
+    draws = draws.to(flat.device)
+    top_idx = draws
+    top_lp = torch.gather(flat, 1, top_idx)
+    if accumulated:
+        top_lp, o = torch.sort(top_lp, descending=True, dim=1, stable=True)
+        top_idx = torch.gather(top_idx, 1, o)
+    return (top_lp, top_idx, draws) if return_draws else (top_lp, top_idx)
+
+
+def beam_draw_intervals(acc_flat: torch.Tensor, drawn) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """For one prompt's flattened acc [nb * vocab] with the flat indices ``drawn`` already taken: (lo, hi, R) in fp64 and in units of
+    the INITIAL total mass (softmax(acc) sums to 1): entry i is drawn for ``u * R`` in [lo_i, hi_i), R the mass that remains."""
+    p = beam_reference_probs(acc_flat[None], 1, torch.float64)[0]
+    rem = _draw_state(p, drawn)
+    hi = rem.cumsum(dim=0)
+    return hi - rem, hi, rem.sum()
+
+
+def beam_draw_margin(acc: torch.Tensor, nb: int, uniforms: torch.Tensor, draws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """For the tests' screening of their inputs, per prompt and draw [B, 2 nb] fp64: the distance of ``u_k * R_k`` from the nearest
+    boundary between two remaining entries of positive mass, in units of the initial total mass (the draws 0..k-1 removed: those
+    of ``draws``, default the fp64 spec's own).  The two ends of the remaining mass, 0 and R_k, are not decisions (below the first
+    entry's end or beyond the total the rule names one entry whatever the rounding), so a draw with a single entry of positive mass
+    left, and a draw by the zero-mass rule, report inf."""
+    flat = acc.reshape(-1, nb * acc.shape[-1])
+    B, n2 = uniforms.shape
+    if draws is None:
+        draws = beam_reference_select(acc, nb, uniforms, True, "5.x", torch.float64, return_draws=True)[2]
+    out = torch.full((B, n2), float("inf"), dtype=torch.float64)
+    for b in range(B):
+        for k in range(n2):
+            lo, hi, R = beam_draw_intervals(flat[b], [int(v) for v in draws[b, :k]])
+            pos = hi[(hi - lo) > 0]
+            if pos.numel() < 2:
+                continue
+            t = float(torch.tensor(float(uniforms[b, k]), dtype=torch.float64) * R)
+            out[b, k] = float((pos[:-1] - t).abs().min())
+    return out

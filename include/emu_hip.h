@@ -643,6 +643,31 @@ int emu_beam_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, 
                        unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
                        emu_stream_t s);
 
+/* One step of the library's beam-search multinomial sampling (lm.generate(num_beams=N, do_sample=True, temperature, top_k, top_p,
+ * repetition_penalty): the call of the demo backend, demo/backend/pytorch_model/backend.py:179-186) and of penalised beam search
+ * (do_sample = 0 with a repetition penalty), in two launches; the specification is emu_amd/sampling.py (beam_reference_*).  Per beam
+ * row: lp = x - logsumexp(x); repetition penalty once per distinct id of running_seq[b, j, :cur] (lp < 0 ? lp * pen : lp / pen);
+ * lp[eos_id] = -inf while cur < min_len; then do_sample = 0: acc = lp + running score; do_sample = 1: temperature, top-k, top-p
+ * (emu_sample_bf16's rules, min_keep forced to at least 2) on lp with the running score added afterwards (warp_accumulated = 0, the
+ * order of transformers 5.x) or on lp + running score (warp_accumulated = 1, beam_sample of transformers 4.31).  Per prompt, over the
+ * flattened [nb * V] scores: do_sample = 0: the 2N best, ties to the lower flat index; do_sample = 1: 2N draws without replacement
+ * from softmax(acc), draw k taking the lowest flat index not yet drawn whose inclusive cumulative mass over the not-yet-drawn
+ * entries exceeds u_k * (the mass that remains) (rounding left it at or beyond the total: the highest remaining entry of positive
+ * mass; no mass left: the lowest not-yet-drawn flat index of finite score), sorted by score (stable) when warp_accumulated.  Then
+ * emu_beam_step_bf16's bookkeeping, with its arguments and state (params->suppress_id, eos_id and pad_id are not read: eos_id and
+ * min_len are the step's own).  uniforms: fp32 [uni_rows, B, 2 * nb] in [0, 1), the step reads row min(cur, uni_rows - 1); needed
+ * when do_sample.  draws_out (may be NULL): int32 [B, 2 * nb] flat indices in draw order, before the sort; acc_out (may be NULL):
+ * fp32 [B * nb] rows ld_acc apart receive acc, -inf for removed ids.  workspace: emu_beam_sample_workspace_bytes(B, nb, V).
+ * No allocation, no synchronisation: capturable.  The same inputs give the same outputs bit for bit.
+ * -22, nothing launched or written: V > EMU_SAMPLE_MAX_VOCAB, V < 2 * nb, nb > 8, L > 256, a missing pointer, a workspace too small. */
+size_t emu_beam_sample_workspace_bytes(int B, int nb, int V);
+int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int B, int nb, int L, int cur, const int32_t* cur_dev,
+                              int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                              float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                              unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                              const emu_sample_params* params, int warp_accumulated, const float* uniforms, int uni_rows,
+                              int32_t* draws_out, float* acc_out, long ld_acc, emu_stream_t s);
+
 /* Loop state of EmuModel.generate_image (emu.py:92-153, KV-cached form: step j feeds project_up(project_down(h_{j-1}))) on the
  * device, so that {project_up, decoder step, final norm, project_down, this} is captured once and replayed n_query - 1 times:
  * out_all[step_dev[0]] = prev = src ([B, cols] bf16: the step's visual embedding), pos[b]++, slot[b]++, step_dev[0]++. */
