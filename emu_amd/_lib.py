@@ -70,6 +70,9 @@ class SampleParamsC(C.Structure):
 
 
 SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
+CONTRASTIVE_MAX_K = 8      # EMU_CONTRASTIVE_MAX_K: candidates per prompt of the contrastive-search kernels
+CONTRASTIVE_CHUNK_ROWS = 8   # EMU_CONTRASTIVE_CHUNK_ROWS: context rows per workgroup of emu_contrastive_score's first launch
+CONTRASTIVE_MAX_HIDDEN = 8192   # EMU_CONTRASTIVE_MAX_HIDDEN
 
 
 class UNetCfgC(C.Structure):
@@ -205,6 +208,11 @@ _PROTOS = {
     "emu_regress_advance_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "emu_beam_advance": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "emu_llama_beam_reorder_kv": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "emu_contrastive_pick_bf16": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, f32, i32, i32, vp, vp, vp]),
+    "emu_contrastive_workspace_bytes": (sz, [i32, i32, i32]),
+    "emu_contrastive_score": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "emu_llama_contrastive_keep_kv": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "emu_contrastive_advance": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "emu_vit_blocks": (i32, [vp, vp, i32, i32, i32, vp, sz, vp]),
     "emu_vit_set_token_parallel": (i32, [vp, i32, i32, i32]),
     "emu_vit_tp_create": (i32, [vp, vp]),

@@ -1510,6 +1510,31 @@ int emu_llama_beam_reorder_kv(emu_llama* m, const long* beam_flat, const int32_t
                                m->cfg.head_dim, beams, slot0, L, S(s));
 }
 
+int emu_llama_contrastive_keep_kv(emu_llama* m, const int32_t* sel, const int32_t* step_dev, int k, int slot0, int L, emu_stream_t s) {
+    if (!m || !m->kcache) return -22;
+    return launch_contrastive_keep(m->kcache, m->vcache, sel, step_dev, m->cfg.layers, m->kv_batch, m->cfg.heads_local, m->s_max,
+                                   m->cfg.head_dim, k, slot0, L, S(s));
+}
+int emu_contrastive_pick_bf16(const void* logits, int ld, int V, int Bn, int k, int L, const int32_t* sel, const int32_t* hist, int hist_ld,
+                              const int32_t* step_dev, float repetition_penalty, int eos_id, int min_len, int32_t* cand_ids,
+                              float* cand_p, emu_stream_t s) {
+    ContrastivePickArgs a{B(logits), ld, V, Bn, k, L, sel, hist, hist_ld, step_dev, repetition_penalty, eos_id, min_len, cand_ids, cand_p};
+    return launch_contrastive_pick(a, S(s));
+}
+size_t emu_contrastive_workspace_bytes(int Bn, int k, int Lc) { return contrastive_ws_floats(Bn, k, Lc) * sizeof(float); }
+int emu_contrastive_score(float* ctx_n, const void* cand, const int32_t* cand_ids, const float* cand_p, const int32_t* kstart,
+                          const int32_t* step_dev, int Bn, int k, int H, int S_, int L, int Lc, float alpha, float one_minus_alpha,
+                          int eos_id, int pad_id, int32_t* out_ids, int32_t* unfinished, int32_t* sel, float* pen_out, void* workspace,
+                          size_t ws_bytes, emu_stream_t s) {
+    ContrastiveScoreArgs a{ctx_n, B(cand), cand_ids, cand_p, kstart, step_dev, Bn, k, H, S_, L, Lc, alpha, one_minus_alpha, eos_id, pad_id,
+                           out_ids, unfinished, sel, pen_out, reinterpret_cast<float*>(workspace), 0};
+    return launch_contrastive_score(a, ws_bytes / sizeof(float), S(s));
+}
+int emu_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
+                            emu_stream_t s) {
+    return launch_contrastive_advance(step_dev, pos, slot, pos0, slot0, rows, L, phase, S(s));
+}
+
 int emu_llama_final_norm(emu_llama* m, const void* hidden, void* out, int rows, emu_stream_t s) {
     if (!m || !m->final_norm) return -22;
     return launch_rmsnorm(B(hidden), m->final_norm, B(out), rows, m->cfg.hidden, m->cfg.hidden, m->cfg.hidden,

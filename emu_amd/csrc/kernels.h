@@ -509,6 +509,36 @@ struct BeamSampleArgs {
 size_t beam_sample_ws_floats(int B, int nb, int V);   // per row: the scores, their masses, the row maximum
 int launch_beam_sample_step(const BeamSampleArgs& a, float* ws, size_t ws_floats, hipStream_t s);
 
+// Contrastive search on the device (contrastive.hip): see emu_contrastive_pick_bf16 / emu_contrastive_score in include/emu_hip.h
+struct ContrastivePickArgs {
+    const bf16_t* logits; int ld; int vocab;   // [B * k] rows ld apart; prompt b reads row b * k + sel[b]
+    int B, k, L;                               // prompts, candidates, max new tokens (steps >= L are no-ops)
+    const int32_t* sel;                        // [B] or null (= 0)
+    const int32_t* hist; int hist_ld;          // ids generated so far: hist[t * hist_ld + b], t < step; may be null
+    const int32_t* step;                       // device int32[1]
+    float penalty; int eos_id, min_len;        // EOS is masked while step < min_len
+    int32_t* cand_ids; float* cand_p;          // [B * k] out
+};
+int launch_contrastive_pick(const ContrastivePickArgs& a, hipStream_t s);
+struct ContrastiveScoreArgs {
+    float* ctx_n;                              // [B, Lc, H] fp32 normalised context rows; row S + step is appended
+    const bf16_t* cand;                        // [B * k, H] final-normed rows of the candidates
+    const int32_t* cand_ids; const float* cand_p;
+    const int32_t* kstart;                     // [B] first valid context row, or null (= 0)
+    const int32_t* step;
+    int B, k, H, S, L, Lc;
+    float alpha, one_minus_alpha;
+    int eos_id, pad_id;
+    int32_t* out_ids; int32_t* unfinished; int32_t* sel; float* pen_out;
+    float* ws; int nchunks;                    // per (prompt, chunk) partial maxima; nchunks is set by the launcher
+};
+size_t contrastive_ws_floats(int B, int k, int Lc);
+int launch_contrastive_score(ContrastiveScoreArgs a, size_t ws_floats, hipStream_t s);
+int launch_contrastive_keep(bf16_t* kc, bf16_t* vc, const int32_t* sel, const int32_t* step_dev, int layers, int rows, int Hl, int s_max,
+                            int D, int k, int slot0, int L, hipStream_t s);
+int launch_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
+                               hipStream_t s);
+
 // ---- UNet denoise helpers (unet.hip); activations are NHWC: [B, H*W, C] bf16
 // GroupNorm(groups, eps) (+ optional SiLU) over x [B, HW, C]: three launches (partial sums, finalize to per-(b, c)
 // scale/shift, apply).  ws must hold gn_ws_floats(B, C, HW) floats.

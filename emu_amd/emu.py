@@ -70,7 +70,8 @@ class EmuModel:
     def __init__(self, vision_cfg: CLIPVisionCfg = CLIPVisionCfg(), text_decoder_cfg: TextDecoderCfg = TextDecoderCfg(),
                  *, llama_cfg: Optional[LlamaCfg] = None, device="cuda", tp_rank: int = 0, tp_size: int = 1,
                  ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None,
-                 device_sampler: Optional[bool] = None, device_beam_sampler: Optional[bool] = None):
+                 device_sampler: Optional[bool] = None, device_beam_sampler: Optional[bool] = None,
+                 device_contrastive: Optional[bool] = None):
         """``device_sampler`` (default: the ``EMU_DEVICE_SAMPLER`` environment variable, off unless "1"): sampling and penalised
         greedy generation (one beam) keep their token loop on the device (``LlamaEngine.sample_generate(device_sampler=True)``:
         uniforms drawn once up front, so a different random stream from the default's ``torch.multinomial``).
@@ -79,6 +80,12 @@ class EmuModel:
         own, ``device_sampler`` does not switch it on): beam search with ``do_sample`` or a repetition penalty keeps its token loop
         on the device too (``LlamaEngine.beam_search_generate(device_beam_sampler=True)``: one table of uniforms up front, again
         another random stream than ``torch.multinomial``).
+
+        ``device_contrastive`` (default: the ``EMU_DEVICE_CONTRASTIVE`` environment variable, off unless "1"; an option of its own
+        beside the two above): contrastive search (``penalty_alpha``, ``top_k``) keeps its token loop on the device
+        (``LlamaEngine.contrastive_generate(device_contrastive=True)``: candidates, degeneration penalty, selection and the KV copy
+        in kernels of csrc/contrastive.hip, replayed from one hipGraph with ``use_graph``).  Its sums are fp32 in a fixed order, so
+        a choice the host loop decides by less than its own rounding may fall the other way.
 
         ``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
         parallelism a prompt with ONE image splits its ViT encode across the ranks by token rows (``encode_image``) instead of every
@@ -112,6 +119,9 @@ class EmuModel:
         if device_beam_sampler is None:
             device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
         self.device_beam_sampler = bool(device_beam_sampler)
+        if device_contrastive is None:
+            device_contrastive = os.environ.get("EMU_DEVICE_CONTRASTIVE", "0") == "1"
+        self.device_contrastive = bool(device_contrastive)
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -271,9 +281,12 @@ class EmuModel:
                 and not do_sample):
             if ngram or nret != 1:
                 raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
+            # with the option off the call is the old one
+            on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
+                if getattr(self, "device_contrastive", False) else {}
             return self.decoder.lm.contrastive_generate(x.view(B, S, -1), attention_mask, max_new_tokens, float(penalty_alpha),
                                                         int(top_k), min_len, repetition_penalty, eos_id=eos,
-                                                        pad_id=PAD_TOKEN_ID)
+                                                        pad_id=PAD_TOKEN_ID, **on_device)
         if num_beams > 1:
             if sem == "4.31" and not EmuModel._warned_431:
                 # honesty in code, not only in INTEGRATION.md: this is the DEFAULT mode (emu.py:163-172: 5 beams, length_penalty -1)

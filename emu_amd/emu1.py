@@ -211,9 +211,10 @@ class Emu:
     def __init__(self, vision_cfg: Optional[CLIPVisionCfg] = None, llama_cfg: Optional[LlamaCfg] = None,
                  t5_cfg: Optional[T5DecoderCfg] = None, vocab: int = 32006, device="cuda", instruct: bool = False,
                  ctx: Optional[EmuHipContext] = None, device_sampler: Optional[bool] = None,
-                 device_beam_sampler: Optional[bool] = None):
-        """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1") and ``device_beam_sampler`` (default:
-        ``EMU_DEVICE_BEAM_SAMPLER``, off unless "1"): as ``EmuModel``'s options of those names."""
+                 device_beam_sampler: Optional[bool] = None, device_contrastive: Optional[bool] = None):
+        """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1"), ``device_beam_sampler`` (default:
+        ``EMU_DEVICE_BEAM_SAMPLER``, off unless "1") and ``device_contrastive`` (default: ``EMU_DEVICE_CONTRASTIVE``, off unless
+        "1"): as ``EmuModel``'s options of those names."""
         self.vision_cfg = vision_cfg or emu1_vision_cfg()
         self.llama_cfg = llama_cfg or emu1_llama_cfg()
         self.t5_cfg = t5_cfg or T5DecoderCfg()
@@ -237,6 +238,9 @@ class Emu:
         if device_beam_sampler is None:
             device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
         self.device_beam_sampler = bool(device_beam_sampler)
+        if device_contrastive is None:
+            device_contrastive = os.environ.get("EMU_DEVICE_CONTRASTIVE", "0") == "1"
+        self.device_contrastive = bool(device_contrastive)
 
     def load_state_dict(self, sd, strict: bool = True, lora_r: int = 16, lora_alpha: float = 16.0):
         """Reference key names (Emu1/models/modeling_emu.py).  The instruct checkpoint is saved with peft LoRA adapters
@@ -295,8 +299,11 @@ class Emu:
         if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample:
             if ngram or nret != 1:
                 raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
+            # with the option off the call is the old one
+            on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
+                if getattr(self, "device_contrastive", False) else {}
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,
-                                                repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
+                                                repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, **on_device)
         if num_beams > 1:
             # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
             on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}

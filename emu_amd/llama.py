@@ -14,7 +14,7 @@ from typing import Dict, Iterable, Optional, Tuple
 import torch
 
 from . import mxfp4, ops
-from ._lib import SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
+from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .sampling import beam_draw_margin, beam_reference_select
 from .tp import ShardPlan
@@ -549,6 +549,7 @@ class LlamaEngine:
             slots[which] = cur
             self._ws = None
             self.__dict__.pop("_beam_graphs", None)        # graphs captured on the replaced cache are void
+            self.__dict__.pop("_contrastive_graphs", None)
         if self.kcache is cur[0]:
             self.set_kv_share(0, 0)
             return
@@ -842,7 +843,8 @@ class LlamaEngine:
     def contrastive_generate(self, embeds: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int,
                              penalty_alpha: float, top_k: int, min_len: int = 1, repetition_penalty: float = 1.0,
                              eos_id: int = 2, pad_id: int = 32000, trace: Optional[dict] = None,
-                             force_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+                             force_ids: Optional[torch.Tensor] = None, device_contrastive: bool = False,
+                             use_graph: bool = False) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., penalty_alpha=a, top_k=k)`` -- contrastive search as the reference's pinned
         transformers 4.31 runs it (Emu2/emu/emu.py:167,223 forwards both arguments): per step the k most probable tokens
         are each run one step further, and the one maximising (1 - a) * p(token) - a * max_j cos(h_token, h_j) over the
@@ -855,7 +857,32 @@ class LlamaEngine:
         Diagnostics for the tests: ``trace`` receives ``margin`` (smallest winner / runner-up score gap) and ``steps`` (per
         step the candidate ids, their probabilities, their degeneration penalties and the selection, on the host);
         ``force_ids`` [B, n] replays a given token path (each forced token must be one of the step's k candidates) so two
-        engines can be compared number by number along the same path."""
+        engines can be compared number by number along the same path.
+
+        ``device_contrastive=True`` (opt-in) keeps the token loop on the device: ``_contrastive_device`` (csrc/contrastive.hip,
+        specified in ``emu_amd/sampling.py``: ``contrastive_reference_*``), replayed from one hipGraph with ``use_graph``.  The loop
+        above stays the default and the fallback; the device's sums are fp32 in a fixed order, so a choice this loop decides by less
+        than the rounding of either may fall the other way.  Refused with a ValueError before any device work: tensor parallelism
+        (the ranks would have to agree on every selection).  The host loop takes over, with one warning per process, for
+        ``top_k > 8``, a vocabulary above ``_lib.SAMPLE_MAX_VOCAB`` or below ``top_k``, and when a ``trace`` or ``force_ids`` is
+        given."""
+        if device_contrastive:
+            if self.ctx.tp_size > 1:
+                raise ValueError("device_contrastive: not built for tensor parallelism (the ranks would have to agree on every "
+                                 "selection); use device_contrastive=False")
+            why = (f"top_k {int(top_k)} (the kernels take {CONTRASTIVE_MAX_K})" if int(top_k) > CONTRASTIVE_MAX_K else
+                   f"vocabulary {self.vocab} above the kernel's bound {SAMPLE_MAX_VOCAB}" if self.vocab > SAMPLE_MAX_VOCAB else
+                   f"vocabulary {self.vocab} below top_k" if self.vocab < int(top_k) else
+                   "a trace is asked for" if trace is not None else
+                   "a forced token path is given" if force_ids is not None else None)
+            if why is None:
+                return self._contrastive_device(embeds, attention_mask, int(max_new_tokens), float(penalty_alpha), int(top_k),
+                                                int(min_len), float(repetition_penalty), int(eos_id), int(pad_id), bool(use_graph))
+            if not LlamaEngine._warned_contrastive:
+                LlamaEngine._warned_contrastive = True
+                import warnings
+                warnings.warn(f"emu_amd: device_contrastive: {why} (the kernels answer -22 outside their range); staying on the "
+                              "host path", stacklevel=2)
         B, S, H = embeds.shape
         k, V, dev = int(top_k), self.vocab, self.device
         s_max = self.kv_capacity(S + max_new_tokens)
@@ -914,6 +941,104 @@ class LlamaEngine:
         self.set_kv_share(0, 0)
         self.ctx.check_p2p()
         return out[:, :n]
+
+    _warned_contrastive = False            # one warning per process (contrastive_generate(device_contrastive=True))
+
+    def _contrastive_device(self, embeds: torch.Tensor, attention_mask: torch.Tensor, L_new: int, alpha: float, k: int, min_len: int,
+                            repetition_penalty: float, eos_id: int, pad_id: int, use_graph: bool) -> torch.Tensor:
+        """The loop of ``contrastive_generate`` with nothing left on the host but the replay of a hipGraph.  After the prefill the
+        prompt's final-normed rows are divided by their norms ONCE into ``ctx_n`` [B, S + max_new_tokens, H] fp32 (every kept
+        token's row joins it normalised; nothing is re-normalised per step), the prefill's logits go to row b * k of the step's
+        [B * k, V] logits and ``sel`` starts at 0.  One step = {``emu_contrastive_advance`` phase 0 (slot / position from the device
+        step counter) -> ``emu_contrastive_pick_bf16`` (the k candidates of the row the previous step kept) -> embedding gather ->
+        the decoder step on B * k rows that share the prompt's KV rows -> final norm, logits -> ``emu_contrastive_score`` (penalty,
+        selection, token / EOS / PAD bookkeeping, the kept row appended) -> ``emu_llama_contrastive_keep_kv`` (the kept KV slot to
+        its siblings) -> counter + 1}: captured once per (B, k, S, cache, limits, options) with buffers the graph owns and replayed
+        ``BEAM_POLL`` steps at a time between two reads of the ``unfinished`` flags; ``use_graph=False`` runs the same launches
+        eagerly.  Steps replayed beyond the end change nothing (a finished prompt writes PAD; from the length limit on every kernel
+        returns at once)."""
+        if not hasattr(self, "handle"):
+            raise RuntimeError("device_contrastive needs the HIP engine")
+        B, S, H = embeds.shape
+        V, dev, rows = self.vocab, self.device, B * k
+        Lb = lib()
+        s_max = self.kv_capacity(S + L_new)
+        hidden, kstart, next_pos = self.prefill(embeds, attention_mask, s_max)
+        ctx0 = self.final_norm_rows(hidden.reshape(B * S, H).contiguous()).view(B, S, H).double()
+        logit0 = self.logits(hidden[:, -1, :])                                          # [B, V] bf16
+        self.fan_out_kv(B, k, S, s_max)
+        Lc = S + L_new
+        key = (B, k, S, self.s_max, L_new, min_len, alpha, repetition_penalty, eos_id, pad_id, self.kcache.data_ptr(), self.mode_epoch)
+        cache = self.__dict__.setdefault("_contrastive_graphs", {})
+        st = cache.get(key)
+        if st is None:
+            cache.clear()                                   # one signature at a time
+            i32 = dict(dtype=torch.int32, device=dev)
+            st = dict(ctx_n=torch.zeros(B, Lc, H, dtype=torch.float32, device=dev), lg=torch.zeros(rows, V, device=dev, dtype=BF16),
+                      hid=torch.empty(rows, H, device=dev, dtype=BF16), normed=torch.empty(rows, H, device=dev, dtype=BF16),
+                      cand_ids=torch.zeros(rows, **i32), cand_p=torch.zeros(rows, dtype=torch.float32, device=dev),
+                      sel=torch.zeros(B, **i32), unfinished=torch.ones(B, **i32), out_ids=torch.empty(L_new, B, **i32),
+                      step=torch.zeros(1, **i32), slot=torch.empty(rows, **i32), pos=torch.empty(rows, **i32),
+                      pos0=torch.empty(rows, **i32), kstart=torch.empty(B, **i32), kstart_k=torch.empty(rows, **i32),
+                      ws=torch.empty(int(Lb.emu_contrastive_workspace_bytes(B, k, Lc)), dtype=torch.uint8, device=dev), graph=None)
+            # the decoder step's workspace: owned here, because the pointers a captured graph holds must outlive any re-allocation
+            # of the engine's shared workspace by a later, larger call
+            need = max(int(Lb.emu_llama_workspace_bytes(self.handle, rows, 1)), rows * H * 2)
+            st["fws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+            cache[key] = st
+        st["ctx_n"][:, :S] = (ctx0 / ctx0.norm(dim=2, keepdim=True)).float()
+        st["lg"].view(B, k, V)[:, 0] = logit0
+        st["sel"].zero_(); st["step"].zero_(); st["unfinished"].fill_(1); st["out_ids"].fill_(pad_id)
+        st["kstart"].copy_(kstart); st["kstart_k"].copy_(kstart.repeat_interleave(k))
+        st["pos0"].copy_(next_pos.repeat_interleave(k))
+        stream = lambda: ops.stream(self.device)           # (inside a capture the current stream is the capturing one)
+        p = lambda name: st[name].data_ptr()
+
+        def body():
+            """One step, every index read on the device."""
+            sm = stream()
+            check(Lb.emu_contrastive_advance(p("step"), p("pos"), p("slot"), p("pos0"), S, rows, L_new, 0, sm), "emu_contrastive_advance")
+            check(Lb.emu_contrastive_pick_bf16(p("lg"), st["lg"].stride(0), V, B, k, L_new, p("sel"), p("out_ids"), B, p("step"),
+                                               repetition_penalty, eos_id, min_len, p("cand_ids"), p("cand_p"), sm),
+                  "emu_contrastive_pick_bf16")
+            ops.embed_gather(st["cand_ids"], self.embed, out=st["hid"])
+            check(Lb.emu_llama_forward(self.handle, p("hid"), rows, 1, p("pos"), p("slot"), p("kstart_k"), None,
+                                       min(S + L_new, self.s_max), p("fws"), st["fws"].numel(), sm), "emu_llama_forward", self.ctx.handle)
+            check(Lb.emu_llama_final_norm(self.handle, p("hid"), p("normed"), rows, sm), "emu_llama_final_norm")
+            check(Lb.emu_llama_logits(self.handle, p("hid"), st["hid"].stride(0), rows, p("lg"), st["lg"].stride(0), p("fws"),
+                                      st["fws"].numel(), sm), "emu_llama_logits", self.ctx.handle)
+            check(Lb.emu_contrastive_score(p("ctx_n"), p("normed"), p("cand_ids"), p("cand_p"), p("kstart"), p("step"), B, k, H, S, L_new,
+                                           Lc, alpha, 1.0 - alpha, eos_id, pad_id, p("out_ids"), p("unfinished"), p("sel"), None,
+                                           p("ws"), st["ws"].numel(), sm), "emu_contrastive_score")
+            check(Lb.emu_llama_contrastive_keep_kv(self.handle, p("sel"), p("step"), k, S, L_new, sm), "emu_llama_contrastive_keep_kv",
+                  self.ctx.handle)
+            check(Lb.emu_contrastive_advance(p("step"), None, None, None, S, rows, L_new, 1, sm), "emu_contrastive_advance")
+
+        done_steps = 0
+        while done_steps < L_new:
+            if done_steps and not bool(st["unfinished"].any()):
+                break
+            n = min(self.BEAM_POLL, L_new - done_steps)
+            if use_graph and st["graph"] is None:
+                body()                                      # warm-up outside capture: a real step
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body()
+                st["graph"] = g
+                done_steps += 1
+                continue
+            for _ in range(n):
+                if use_graph:
+                    st["graph"].replay()
+                else:
+                    body()
+            done_steps += n
+        ids = st["out_ids"].t().to(torch.int64)
+        self.set_kv_share(0, 0)
+        self.ctx.check_p2p()
+        # a finished prompt emitted PAD on the device; steps between the last prompt's EOS and the poll that saw it are cut off
+        # here: the width is one past the last step at which any prompt was still unfinished, the host loop's rule
+        return apply_eos_padding(ids, eos_id, pad_id)
 
     # ------------------------------------------------------------------ beam search
     @torch.no_grad()

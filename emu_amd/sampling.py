@@ -316,3 +316,40 @@ def beam_draw_margin(acc: torch.Tensor, nb: int, uniforms: torch.Tensor, draws: 
             t = float(torch.tensor(float(uniforms[b, k]), dtype=torch.float64) * R)
             out[b, k] = float((pos[:-1] - t).abs().min())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Contrastive search (emu_amd/csrc/contrastive.hip: ``emu_contrastive_pick_bf16`` and ``emu_contrastive_score``): what the kernels
+# compute per prompt and step.  It restates the arithmetic of the host loop ``LlamaEngine.contrastive_generate`` and is tested against it.
+#
+# Candidates, from the logit row the previous step kept: steps 1-3 above (repetition penalty once per distinct id of the prompt's
+# history, EOS at -inf while ``step < min_len``), ``p = softmax(s)`` in ``dtype``, and the k largest in descending order of s (p is
+# monotone in s), ties to the lower id.
+#
+# Selection: ``pen[b, j]`` = the largest cosine between candidate j's final-normed hidden row and the VALID context rows of prompt b
+# (the prompt from its first real token, then every kept token: left padding is left out); ``score = (1 - alpha) * p - alpha * pen``;
+# the first index of the maximum is kept.  Both depend on a candidate only through its row and its p, never through j: two identical
+# candidates tie and the lower index wins.
+
+def contrastive_reference_candidates(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
+                                     eos_id: Optional[int] = None, suppress_eos: bool = False, k: int = 1,
+                                     dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(ids [B, k] int64, p [B, k] ``dtype``) of bf16 (or fp32-held) logit rows [B, vocab]."""
+    s = reference_scores(logits, history, repetition_penalty, eos_id if suppress_eos else None)
+    p = torch.softmax(s.to(dtype), dim=-1)
+    ids = torch.sort(s, dim=-1, descending=True, stable=True)[1][:, :int(k)]         # stable: equal scores keep ascending id
+    return ids, torch.gather(p, 1, ids)
+
+
+def contrastive_reference_select(ctx: torch.Tensor, ctx_valid: torch.Tensor, cand_h: torch.Tensor, p: torch.Tensor, alpha: float,
+                                 dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(pen [B, k] ``dtype``, sel [B] int64): ``ctx`` [B, L, H] hidden rows (any scale: they are normalised here), ``ctx_valid``
+    [B, L] bool, ``cand_h`` [B, k, H], ``p`` [B, k]."""
+    c, n = ctx.to(dtype), cand_h.to(dtype)
+    cn = c / c.norm(dim=2, keepdim=True)
+    nn_ = n / n.norm(dim=2, keepdim=True)
+    cos = torch.einsum("bld,bkd->bkl", cn, nn_).masked_fill(~ctx_valid.to(torch.bool)[:, None, :], -float("inf"))
+    pen = cos.max(dim=-1)[0]
+    score = (1.0 - alpha) * p.to(dtype) - alpha * pen
+    first = (score == score.max(dim=-1, keepdim=True)[0]).float().argmax(dim=-1)    # argmax of a 0/1 row: the first 1
+    return pen, first

@@ -685,6 +685,48 @@ int emu_beam_advance(int32_t* cur_dev, int32_t* pos, int32_t* slot, const int32_
 int emu_llama_beam_reorder_kv(emu_llama* m, const long* beam_flat, const int32_t* cur_dev, int beams, int slot0, int L,
                               emu_stream_t s);
 
+/* Contrastive search (lm.generate(penalty_alpha = a, top_k = k), Emu2/emu/emu.py:167,223) with its token loop on the device; the
+ * specification is emu_amd/sampling.py (contrastive_reference_candidates / contrastive_reference_select).  One step is {advance phase
+ * 0, pick, embedding gather of cand_ids, emu_llama_forward on the B * k candidate rows, emu_llama_final_norm, emu_llama_logits, score,
+ * keep, advance phase 1}; every launch reads the step from step_dev (device int32[1]) and does nothing once step >= L, so one captured
+ * hipGraph replays for every token and replays beyond the end are harmless.  No allocation, no synchronisation: capturable.  The same
+ * inputs give the same outputs bit for bit (every sum has a fixed order, no floating-point atomics).
+ *
+ * emu_contrastive_pick_bf16: per prompt b, from the bf16 logit row b * k + sel[b] (rows ld elements apart; sel NULL = 0):
+ *   s = float32(logit); repetition penalty once per distinct id of hist[t * hist_ld + b], t < step (s < 0 ? s * pen : s / pen, ids
+ *   outside [0, V) ignored; hist may be NULL); s[eos_id] = -inf while step < min_len (eos_id < 0 = off); p = softmax(s) (blocked
+ *   fixed-order fp32 sums); cand_ids int32 [B * k] / cand_p fp32 [B * k] receive the k largest in descending order, ties to the
+ *   lower id.
+ * emu_contrastive_score (two launches): ctx_n fp32 [B, Lc, H] holds the context rows ALREADY divided by their norms; the valid rows
+ *   of prompt b are [kstart[b], S + step) (kstart NULL = 0; rows outside are never read).  cand: bf16 [B * k, H], the candidates'
+ *   final-normed hidden rows.  pen[b, j] = max over the valid rows of dot(ctx_n row, cand row) / |cand row| (the dot products in
+ *   fp32, the norm from an fp64 sum; identical candidates get identical penalties); score = (1 - alpha) * cand_p - alpha * pen; the
+ *   first maximum wins.  Then, for a prompt whose unfinished flag (int32 [B]) is set: out_ids[step * B + b] = the kept id, the flag
+ *   is cleared when that id is eos_id, sel[b] = the kept index, ctx_n[b, S + step] = the kept row / its norm, pen_out (fp32 [B * k],
+ *   may be NULL) = pen.  A finished prompt gets out_ids[step * B + b] = pad_id and nothing else of it is written.  Phase 1 gives
+ *   every EMU_CONTRASTIVE_CHUNK_ROWS context rows a workgroup (chunks beyond S + step exit at once) and leaves per-chunk maxima in
+ *   the workspace: emu_contrastive_workspace_bytes(B, k, Lc).
+ * emu_llama_contrastive_keep_kv: cache slot slot0 + step of row b * k + sel[b] goes to its k - 1 siblings, in every layer, K and V, of
+ *   the engine's current cache (rows in groups of k; nothing else moves).
+ * emu_contrastive_advance phase 0: slot[i] = slot0 + step, pos[i] = pos0[i] + step (rows = B * k); phase 1: step_dev += 1.
+ * -22, nothing launched or written: k < 1 or k > EMU_CONTRASTIVE_MAX_K, V > EMU_SAMPLE_MAX_VOCAB, V < k, H not a multiple of 4 or
+ * above EMU_CONTRASTIVE_MAX_HIDDEN, Lc < S + L, slot0 + L beyond the cache, rows not a multiple of k, a missing pointer (those not
+ * marked optional above), a workspace too small. */
+#define EMU_CONTRASTIVE_MAX_K 8
+#define EMU_CONTRASTIVE_CHUNK_ROWS 8
+#define EMU_CONTRASTIVE_MAX_HIDDEN 8192 /* k x H bf16 candidate rows in the CU's LDS */
+int emu_contrastive_pick_bf16(const void* logits, int ld, int V, int B, int k, int L, const int32_t* sel, const int32_t* hist, int hist_ld,
+                              const int32_t* step_dev, float repetition_penalty, int eos_id, int min_len, int32_t* cand_ids,
+                              float* cand_p, emu_stream_t s);
+size_t emu_contrastive_workspace_bytes(int B, int k, int Lc);
+int emu_contrastive_score(float* ctx_n, const void* cand, const int32_t* cand_ids, const float* cand_p, const int32_t* kstart,
+                          const int32_t* step_dev, int B, int k, int H, int S, int L, int Lc, float alpha, float one_minus_alpha,
+                          int eos_id, int pad_id, int32_t* out_ids, int32_t* unfinished, int32_t* sel, float* pen_out, void* workspace,
+                          size_t ws_bytes, emu_stream_t s);
+int emu_llama_contrastive_keep_kv(emu_llama* m, const int32_t* sel, const int32_t* step_dev, int k, int slot0, int L, emu_stream_t s);
+int emu_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
+                            emu_stream_t s);
+
 /* ---- EVA-CLIP ViT engine -------------------------------------------------------------------------------
  * EVAVisionTransformer.forward_features (eva_vit.py:402-431), post-norm blocks (:296-300), naive attention
  * (:182-252) with heads zero-padded from head_width to 128 at pack time (see emu_amd/vit.py):
