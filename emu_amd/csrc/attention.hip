@@ -477,7 +477,27 @@ __global__ void regress_advance_kernel(const bf16_t* src, bf16_t* out_all, bf16_
     if (threadIdx.x == 0) *step = st + 1;
 }
 
+// the beam and contrastive loops' bookkeeping (kernels.h: launch_step_advance)
+__global__ void step_advance_kernel(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int bias, int rows,
+                                    int L, int phase) {
+    const int c = *step_dev;
+    if (c >= L) return;
+    if (phase == 0) {
+        for (int i = threadIdx.x; i < rows; i += blockDim.x) { slot[i] = slot0 + c + bias; pos[i] = pos0[i] + c + bias; }
+    } else if (threadIdx.x == 0) {
+        *step_dev = c + 1;
+    }
+}
+
 }  // namespace
+
+int launch_step_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int bias, int rows, int L,
+                        int phase, hipStream_t s) {
+    if (!step_dev || rows < 1 || (phase == 0 && (!pos || !slot || !pos0))) return -22;
+    hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, s, step_dev, pos, slot, pos0, slot0, bias, rows, L, phase);
+    EMU_CHECK_LAUNCH();
+    return 0;
+}
 
 int launch_regress_advance(const bf16_t* src, bf16_t* out_all, bf16_t* prev, int32_t* pos, int32_t* slot, int32_t* step, int B,
                            int cols, hipStream_t s) {

@@ -147,21 +147,8 @@ __global__ __launch_bounds__(NT) void beam_step_kernel(const BeamStepArgs a, con
     beam_bookkeeping<NT>(a, b, cur, top_lp, top_idx);
 }
 
-// ---- the rest of a beam step that used to be host work: with these two the whole step {advance, re-order, embed, 60 layers,
-// logits, beam_step_kernel} reads its step index from a device counter and is replayed from one hipGraph.
-// Step bookkeeping.  phase 0 (ahead of the decoder step that feeds token cur - 1): slot = slot0 + cur - 1, pos = pos0 + cur - 1;
-// phase 1 (behind beam_step_kernel): cur += 1.  Steps at the length limit change nothing (replays beyond it are no-ops).
-__global__ void beam_advance_kernel(int32_t* cur_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L,
-                                    int phase) {
-    const int c = *cur_dev;
-    if (c >= L) return;
-    if (phase == 0) {
-        for (int i = threadIdx.x; i < rows; i += blockDim.x) { slot[i] = slot0 + c - 1; pos[i] = pos0[i] + c - 1; }
-    } else if (threadIdx.x == 0) {
-        *cur_dev = c + 1;
-    }
-}
-
+// ---- the rest of a beam step that used to be host work: with this and launch_step_advance (attention.hip) the whole step {advance,
+// re-order, embed, 60 layers, logits, beam_step_kernel} reads its step index from a device counter and is replayed from one hipGraph.
 // transformers' _reorder_cache for the GENERATED slots [slot0, slot0 + cur - 1) (the prompt's slots are shared by the beams of a
 // group and never move): cache row r takes the slots of row beam_flat[r].  In place: one workgroup owns a (layer, head, slot) of
 // all the rows of a group -- it loads the nb source vectors, then stores them (a barrier in between).  grid = (layers * heads,
@@ -192,14 +179,6 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(bf16_t* kc, bf16_t* v
 }
 
 }  // namespace
-
-int launch_beam_advance(int32_t* cur_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
-                        hipStream_t s) {
-    if (!cur_dev || rows < 1 || (phase == 0 && (!pos || !slot || !pos0))) return -22;
-    hipLaunchKernelGGL(beam_advance_kernel, dim3(1), dim3(64), 0, s, cur_dev, pos, slot, pos0, slot0, rows, L, phase);
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
 
 int launch_beam_reorder(bf16_t* kc, bf16_t* vc, const long* beam_flat, const int32_t* cur_dev, int layers, int rows, int Hl, int s_max,
                         int D, int nb, int slot0, int L, hipStream_t s) {

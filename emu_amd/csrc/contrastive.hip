@@ -11,7 +11,7 @@
 //   score 2  one workgroup per prompt: maxima over the chunks, the candidates' norms (fp64 sums), score = (1 - a) p - a pen, first
 //            maximum wins; token / EOS / PAD bookkeeping; the kept candidate's normalised row joins the context.
 //   keep     the kept candidate's KV slot goes to its k - 1 siblings (one slot per row and layer).
-//   advance  slot / position of the step's rows from the counter; counter + 1.
+//   advance  slot / position of the step's rows from the counter; counter + 1 (launch_step_advance, attention.hip).
 //
 // Every sum has a fixed order (no floating-point atomics): the same inputs give the same outputs bit for bit.  One dot product is, per
 // lane, 4 * ceil(H / 256) sequential fp32 multiply-adds (elements it * 256 + lane * 4 + 0..3 in ascending order) and then the
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(CS_THREADS) void contrastive_score2_kernel(Contrast
     for (int e = tid; e < H; e += CS_THREADS) dst[e] = __fmul_rn(bf2f(src[e]), inv);
 }
 
-// ------------------------------------------------------------------------------------------------------------------ keep, advance
+// ------------------------------------------------------------------------------------------------------------------ keep
 // cache [layers, rows, Hl, s_max, D]: slot slot0 + step of row g * k + sel[g] -> its k - 1 siblings.  grid (layers * Hl, groups).
 __global__ __launch_bounds__(128) void contrastive_keep_kernel(bf16_t* kc, bf16_t* vc, const int32_t* sel, const int32_t* step_dev,
                                                                int rows, int Hl, int s_max, int D, int k, int slot0, int L) {
@@ -292,18 +292,6 @@ __global__ __launch_bounds__(128) void contrastive_keep_kernel(bf16_t* kc, bf16_
         const size_t dofs = ((((size_t)layer * rows + g * k + j) * Hl + h) * s_max + slot) * D;
         st16(kc + dofs + piece * 8, ld16(kc + so + piece * 8));
         st16(vc + dofs + piece * 8, ld16(vc + so + piece * 8));
-    }
-}
-
-// phase 0 (ahead of the decoder step on the candidates of token `step`): slot = slot0 + step, pos = pos0 + step; phase 1: step += 1
-__global__ void contrastive_advance_kernel(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows,
-                                           int L, int phase) {
-    const int c = *step_dev;
-    if (c >= L) return;
-    if (phase == 0) {
-        for (int i = threadIdx.x; i < rows; i += blockDim.x) { slot[i] = slot0 + c; pos[i] = pos0[i] + c; }
-    } else if (threadIdx.x == 0) {
-        *step_dev = c + 1;
     }
 }
 
@@ -371,14 +359,6 @@ int launch_contrastive_keep(bf16_t* kc, bf16_t* vc, const int32_t* sel, const in
     if (k == 1) return 0;                              // no sibling
     hipLaunchKernelGGL(contrastive_keep_kernel, dim3(layers * Hl, rows / k), dim3(128), 0, s, kc, vc, sel, step_dev, rows, Hl, s_max, D,
                        k, slot0, L);
-    EMU_CHECK_LAUNCH();
-    return 0;
-}
-
-int launch_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
-                               hipStream_t s) {
-    if (!step_dev || rows < 1 || (phase == 0 && (!pos || !slot || !pos0))) return -22;
-    hipLaunchKernelGGL(contrastive_advance_kernel, dim3(1), dim3(64), 0, s, step_dev, pos, slot, pos0, slot0, rows, L, phase);
     EMU_CHECK_LAUNCH();
     return 0;
 }

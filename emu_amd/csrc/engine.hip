@@ -1501,7 +1501,7 @@ int emu_regress_advance_bf16(const void* src, void* out_all, void* prev, int32_t
 }
 int emu_beam_advance(int32_t* cur_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
                      emu_stream_t s) {
-    return launch_beam_advance(cur_dev, pos, slot, pos0, slot0, rows, L, phase, S(s));
+    return launch_step_advance(cur_dev, pos, slot, pos0, slot0, -1, rows, L, phase, S(s));
 }
 int emu_llama_beam_reorder_kv(emu_llama* m, const long* beam_flat, const int32_t* cur_dev, int beams, int slot0, int L,
                               emu_stream_t s) {
@@ -1532,7 +1532,7 @@ int emu_contrastive_score(float* ctx_n, const void* cand, const int32_t* cand_id
 }
 int emu_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
                             emu_stream_t s) {
-    return launch_contrastive_advance(step_dev, pos, slot, pos0, slot0, rows, L, phase, S(s));
+    return launch_step_advance(step_dev, pos, slot, pos0, slot0, 0, rows, L, phase, S(s));
 }
 
 int emu_llama_final_norm(emu_llama* m, const void* hidden, void* out, int rows, emu_stream_t s) {
@@ -1583,17 +1583,30 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
     return 0;
 }
 
-int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
-                          int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int ctx_upper, void* hidden,
-                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
-    if (!m || !m->embed) return -22;
+// One token of the greedy and the sampling loop: embed -> layers -> logits -> select -> state advance.  The selection is the only
+// difference: `params` null = arg-max; else emu_sample_bf16's kernel, for which the ids of steps 0 .. step - 1 in out_ids are the
+// history.  Either way the selection goes to cur_ids and the advance files it at `step`.
+static int llama_token_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart, int32_t* ctx_dev,
+                            int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden, void* logits, int ld_logits,
+                            void* workspace, size_t ws_bytes, const float* uniforms, int32_t* unfinished,
+                            const emu_sample_params* params, emu_stream_t s) {
     const emu_llama_cfg& c = m->cfg;
     TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
-    TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
+    if (!params) TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
+    else TRY(m->ctx, launch_sample(B(logits), ld_logits, Bn, c.vocab, out_ids, Bn, max_new, step_dev, uniforms, Bn, max_new, params,
+                                   unfinished, cur_ids, nullptr, 0, S(s)));
     TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, S(s)));
     return 0;
+}
+
+int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                          int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
+    if (!m || !m->embed) return -22;
+    return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, 0, ctx_upper, hidden, logits, ld_logits,
+                            workspace, ws_bytes, nullptr, nullptr, nullptr, s);
 }
 
 int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
@@ -1601,16 +1614,9 @@ int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
                           int32_t* unfinished, const emu_sample_params* params, emu_stream_t s) {
     if (!m || !m->embed || !params || !unfinished || max_new < 1) return -22;
-    const emu_llama_cfg& c = m->cfg;
-    if (c.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;                // refused before anything is launched
-    TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
-    TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
-    TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
-    // the ids of steps 0 .. step - 1 in out_ids are the history; the selection goes to cur_ids and the advance files it at `step`
-    TRY(m->ctx, launch_sample(B(logits), ld_logits, Bn, c.vocab, out_ids, Bn, max_new, step_dev, uniforms, Bn, max_new, params,
-                              unfinished, cur_ids, nullptr, 0, S(s)));
-    TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, S(s)));
-    return 0;
+    if (m->cfg.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;           // refused before anything is launched
+    return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, max_new, ctx_upper, hidden, logits, ld_logits,
+                            workspace, ws_bytes, uniforms, unfinished, params, s);
 }
 
 }  // extern "C"

@@ -341,6 +341,12 @@ int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
 // out_all[step[0]] = prev = src ([B, cols] bf16); pos[b]++, slot[b]++, step[0]++   (generate_image's loop state, on the device)
 int launch_regress_advance(const bf16_t* src, bf16_t* out_all, bf16_t* prev, int32_t* pos, int32_t* slot, int32_t* step, int B,
                            int cols, hipStream_t s);
+// Step bookkeeping of the hipGraph-replayed beam and contrastive loops, from the device counter c = step_dev[0].  phase 0 (ahead of
+// the decoder step): slot[i] = slot0 + c + bias, pos[i] = pos0[i] + c + bias for the `rows` rows; phase 1 (behind the step's last
+// kernel): c += 1.  bias = -1: the step feeds token c - 1 (beam search); 0: it runs the candidates of token c (contrastive
+// search).  From c >= L on nothing changes (replays beyond the length limit are no-ops).
+int launch_step_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int bias, int rows, int L,
+                        int phase, hipStream_t s);
 
 // Decode step, fused: RoPE of q and of the new k, KV-cache append of the new token, and single-query attention over
 // the cache, in one launch (+ the split combine).  Context length of row b = slot[b] + 1, read on the device.
@@ -489,9 +495,7 @@ struct BeamStepArgs {
     unsigned char* heuristic_open;             // [B]
     int32_t* next_tok; long* beam_flat;        // [B * nb] out: token to feed / cache row it continues
 };
-// device-side step bookkeeping and KV re-order of a hipGraph-replayed beam step (beam.hip)
-int launch_beam_advance(int32_t* cur_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
-                        hipStream_t s);
+// KV re-order of a hipGraph-replayed beam step (beam.hip)
 int launch_beam_reorder(bf16_t* kc, bf16_t* vc, const long* beam_flat, const int32_t* cur_dev, int layers, int rows, int Hl, int s_max,
                         int D, int nb, int slot0, int L, hipStream_t s);
 size_t beam_step_ws_floats(int B, int nb, int V);     // scratch of the two-launch step (chunk partials)
@@ -536,8 +540,6 @@ size_t contrastive_ws_floats(int B, int k, int Lc);
 int launch_contrastive_score(ContrastiveScoreArgs a, size_t ws_floats, hipStream_t s);
 int launch_contrastive_keep(bf16_t* kc, bf16_t* vc, const int32_t* sel, const int32_t* step_dev, int layers, int rows, int Hl, int s_max,
                             int D, int k, int slot0, int L, hipStream_t s);
-int launch_contrastive_advance(int32_t* step_dev, int32_t* pos, int32_t* slot, const int32_t* pos0, int slot0, int rows, int L, int phase,
-                               hipStream_t s);
 
 // ---- UNet denoise helpers (unet.hip); activations are NHWC: [B, H*W, C] bf16
 // GroupNorm(groups, eps) (+ optional SiLU) over x [B, HW, C]: three launches (partial sums, finalize to per-(b, c)

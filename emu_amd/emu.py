@@ -20,6 +20,7 @@ from .constants import *  # noqa: F401,F403  (re-exported like the reference mod
 from .constants import (DEFAULT_gIMG_TOKEN, DEFAULT_IMAGE_TOKEN, DEFAULT_IMG_END_TOKEN, DEFAULT_IMG_PLACEHOLDER,
                         DEFAULT_IMG_TOKEN, DEFAULT_VID_PLACEHOLDER, EOS_TOKEN_ID, IMAGE_TOKEN_ID, IMG_TOKEN_ID,
                         PAD_TOKEN_ID, VOCAB_EMU2, VOCAB_EMU2_CHAT, gIMG_TOKEN_ID, special_tokens_list)
+from .device_loop import CapturedStep, option_or_env
 from .llama import EmuHipContext, LlamaEngine
 
 BF16 = torch.bfloat16
@@ -109,19 +110,11 @@ class EmuModel:
         self.image_placeholder = DEFAULT_IMG_TOKEN + DEFAULT_IMAGE_TOKEN * self.n_query + DEFAULT_IMG_END_TOKEN
         self.video_placeholder = DEFAULT_IMG_TOKEN + DEFAULT_gIMG_TOKEN * self.v_query + DEFAULT_IMG_END_TOKEN
         self.use_graph = False
-        if vit_token_parallel is None:
-            vit_token_parallel = os.environ.get("EMU_VIT_TOKEN_PARALLEL", "0") == "1"
-        self.vit_token_parallel = bool(vit_token_parallel)
+        self.vit_token_parallel = option_or_env(vit_token_parallel, "EMU_VIT_TOKEN_PARALLEL")
         self._vit_tp_ready = False
-        if device_sampler is None:
-            device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
-        self.device_sampler = bool(device_sampler)
-        if device_beam_sampler is None:
-            device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
-        self.device_beam_sampler = bool(device_beam_sampler)
-        if device_contrastive is None:
-            device_contrastive = os.environ.get("EMU_DEVICE_CONTRASTIVE", "0") == "1"
-        self.device_contrastive = bool(device_contrastive)
+        self.device_sampler = option_or_env(device_sampler, "EMU_DEVICE_SAMPLER")
+        self.device_beam_sampler = option_or_env(device_beam_sampler, "EMU_DEVICE_BEAM_SAMPLER")
+        self.device_contrastive = option_or_env(device_contrastive, "EMU_DEVICE_CONTRASTIVE")
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -399,7 +392,8 @@ class EmuModel:
             st = dict(key=key, prev=torch.empty(B, width, device=dev, dtype=BF16), xin=torch.empty(B, hidden, device=dev, dtype=BF16),
                       normed=torch.empty(B, hidden, device=dev, dtype=BF16), cur=torch.empty(B, width, device=dev, dtype=BF16),
                       out_all=torch.empty(self.n_query, B, width, device=dev, dtype=BF16), pos=torch.empty(B, **i32),
-                      slot=torch.empty(B, **i32), step=torch.empty(1, **i32), kstart=torch.empty(B, **i32), graph=None,
+                      slot=torch.empty(B, **i32), step=torch.empty(1, **i32), kstart=torch.empty(B, **i32),
+                      captured=CapturedStep(),
                       ws=torch.empty(max(int(L.emu_llama_workspace_bytes(lm.handle, B, 1)), B * hidden * 2), dtype=torch.uint8, device=dev))
             self._regress_state = st
         st["prev"].copy_(first); st["out_all"][0].copy_(first)
@@ -416,16 +410,8 @@ class EmuModel:
             check(L.emu_regress_advance_bf16(st["cur"].data_ptr(), st["out_all"].data_ptr(), st["prev"].data_ptr(), st["pos"].data_ptr(),
                                              st["slot"].data_ptr(), st["step"].data_ptr(), B, width, sm), "emu_regress_advance_bf16")
 
-        n = self.n_query - 1
-        if st["graph"] is None:
-            body()                                              # warm-up outside capture: a real step
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                body()
-            st["graph"] = g
-            n -= 1
-        for _ in range(n):
-            st["graph"].replay()
+        for _ in range(self.n_query - 1):
+            st["captured"].step(body, True, key)
         lm.ctx.check_p2p()
         lm.check_decode_fused()
         return st["out_all"].permute(1, 0, 2).clone()                               # [B, n_query, width] (never a view of the state)

@@ -12,7 +12,6 @@ instruct checkpoints must be merged beforehand.  PARITY UNPINNED (see oracle/emu
 from __future__ import annotations
 
 import math
-import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -22,6 +21,7 @@ import torch
 from . import ops
 from .conf.emu_conf import CLIPVisionCfg, LlamaCfg
 from .constants import EOS_TOKEN_ID, IMAGE_TOKEN_ID, PAD_TOKEN_ID
+from .device_loop import option_or_env
 from .llama import EmuHipContext, LlamaEngine
 from .vit import VitEngine
 
@@ -232,15 +232,9 @@ class Emu:
         self.n_causal = self.t5_cfg.n_causal
         self.image_placeholder = "[IMG]" + "<image>" * self.n_causal + "[/IMG]"
         self.tokenizer = None
-        if device_sampler is None:
-            device_sampler = os.environ.get("EMU_DEVICE_SAMPLER", "0") == "1"
-        self.device_sampler = bool(device_sampler)
-        if device_beam_sampler is None:
-            device_beam_sampler = os.environ.get("EMU_DEVICE_BEAM_SAMPLER", "0") == "1"
-        self.device_beam_sampler = bool(device_beam_sampler)
-        if device_contrastive is None:
-            device_contrastive = os.environ.get("EMU_DEVICE_CONTRASTIVE", "0") == "1"
-        self.device_contrastive = bool(device_contrastive)
+        self.device_sampler = option_or_env(device_sampler, "EMU_DEVICE_SAMPLER")
+        self.device_beam_sampler = option_or_env(device_beam_sampler, "EMU_DEVICE_BEAM_SAMPLER")
+        self.device_contrastive = option_or_env(device_contrastive, "EMU_DEVICE_CONTRASTIVE")
 
     def load_state_dict(self, sd, strict: bool = True, lora_r: int = 16, lora_alpha: float = 16.0):
         """Reference key names (Emu1/models/modeling_emu.py).  The instruct checkpoint is saved with peft LoRA adapters

@@ -16,6 +16,7 @@ import torch
 from . import mxfp4, ops
 from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
+from .device_loop import CapturedStep, run_polled, warn_once
 from .sampling import beam_draw_margin, beam_reference_select
 from .tp import ShardPlan
 
@@ -224,7 +225,28 @@ class LlamaEngine:
 
     def _mode_changed(self) -> None:
         self.mode_epoch += 1
-        self.__dict__.pop("_beam_graphs", None)
+        self._drop_loop_states()
+
+    def _drop_loop_states(self) -> None:
+        """Forget every cached loop state (``_loop_state``): its buffers, and a graph that holds pointers into a cache or a mode
+        that is gone.  (The keys hold the epoch and the cache pointer, so a stale graph is never replayed; this frees it.)"""
+        self.__dict__.setdefault("_loop_states", {}).clear()          # loop name -> (key, state)
+
+    def _loop_state(self, name: str, key: tuple, rows: int, build) -> dict:
+        """The cached state of the device loop ``name`` ("beam", "contrastive") for ``key``, or a new one: ``build()``'s buffers, the
+        decoder step's workspace ``fws`` for ``rows`` rows and ``captured``, the ``CapturedStep`` of the loop's body.  ``key`` must
+        hold everything that body reads besides the state."""
+        states = self.__dict__.setdefault("_loop_states", {})
+        if name not in states or states[name][0] != key:
+            states.pop(name, None)                          # one signature at a time: its buffers are a few MB, its graph ~430 nodes
+            st = build()
+            # the decoder step's workspace: owned here, because the pointers a captured graph holds must outlive any re-allocation
+            # of the engine's shared workspace by a later, larger call
+            need = max(int(lib().emu_llama_workspace_bytes(self.handle, rows, 1)), rows * self.cfg.hidden_size * 2)
+            st["fws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            st["captured"] = CapturedStep()
+            states[name] = (key, st)
+        return states[name][1]
 
     def set_l2_warm(self, mask: int) -> None:
         """L2 warming across the launch boundaries of the default one-row decode step (include/emu_hip.h: emu_llama_set_l2_warm):
@@ -548,8 +570,7 @@ class LlamaEngine:
                    make(L, batch, Hl, s_max, D, device=self.device, dtype=BF16), batch, s_max)
             slots[which] = cur
             self._ws = None
-            self.__dict__.pop("_beam_graphs", None)        # graphs captured on the replaced cache are void
-            self.__dict__.pop("_contrastive_graphs", None)
+            self._drop_loop_states()                       # graphs captured on the replaced cache are void
         if self.kcache is cur[0]:
             self.set_kv_share(0, 0)
             return
@@ -706,20 +727,19 @@ class LlamaEngine:
         if max_new_tokens > 1:
             st = GreedyState(self, B, cur, next_pos, S, kstart, out_ids)
             n_eager = max(0, min_len - 1)
-            steps = max_new_tokens - 1
-            for i in range(steps):
-                suppress = eos_id if i < n_eager else -1
-                if suppress >= 0:
-                    st.step_eager_suppress(suppress)
-                elif use_graph:
-                    st.step_graph()
+            done = [1]                                          # rows of out_ids written so far
+
+            def one(i):
+                if i < n_eager and eos_id >= 0:
+                    st.step_eager_suppress(eos_id)
                 else:
-                    st.step()
-                # the reference's loop ends when every row has emitted EOS (transformers' stopping criteria): look at the
-                # device-side ids every EOS_POLL steps (one small host read; the launches in between stay queued ahead)
-                if stop_on_eos and (i + 1) % EOS_POLL == 0 and i + 1 < steps:
-                    if bool((out_ids[: i + 2] == eos_id).any(dim=0).all()):
-                        break
+                    (st.step_graph if use_graph else st.step)()
+                done[0] = i + 2
+
+            # the reference's loop ends when every row has emitted EOS (transformers' stopping criteria): look at the
+            # device-side ids every EOS_POLL steps (one small host read; the launches in between stay queued ahead)
+            run_polled(one, max_new_tokens - 1, EOS_POLL,
+                       lambda: stop_on_eos and bool((out_ids[: done[0]] == eos_id).any(dim=0).all()))
         ids = out_ids.t().to(torch.int64)                       # [B, max_new]
         self.ctx.check_p2p()
         self.check_decode_fused()
@@ -760,11 +780,9 @@ class LlamaEngine:
                 raise ValueError("device_sampler: not built for tensor parallelism (the ranks would need one shared table of "
                                  "uniforms); use device_sampler=False")
             if self.vocab > SAMPLE_MAX_VOCAB:
-                if not LlamaEngine._warned_sampler_vocab:
-                    LlamaEngine._warned_sampler_vocab = True
-                    import warnings
-                    warnings.warn(f"emu_amd: device_sampler: vocabulary {self.vocab} is above the sample kernel's bound "
-                                  f"{SAMPLE_MAX_VOCAB} (emu_sample_bf16 answers -22); staying on the host path", stacklevel=2)
+                warn_once(LlamaEngine, "_warned_sampler_vocab",
+                          f"emu_amd: device_sampler: vocabulary {self.vocab} is above the sample kernel's bound "
+                          f"{SAMPLE_MAX_VOCAB} (emu_sample_bf16 answers -22); staying on the host path")
                 device_sampler = False
         if num_return_sequences > 1:
             if not do_sample:
@@ -823,15 +841,8 @@ class LlamaEngine:
                          sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id))
         self.logits(row, out=st.logits)
         st.first()
-        steps = max_new - 1
-        for i in range(steps):
-            if use_graph:
-                st.step_graph()
-            else:
-                st.step()
-            # the only host read: the rows' flags, every EOS_POLL steps (the launches in between stay queued ahead)
-            if (i + 1) % EOS_POLL == 0 and i + 1 < steps and not bool(st.unfinished.any()):
-                break
+        # the only host read: the rows' flags, every EOS_POLL steps (the launches in between stay queued ahead)
+        run_polled(lambda i: (st.step_graph if use_graph else st.step)(), max_new - 1, EOS_POLL, lambda: not bool(st.unfinished.any()))
         ids = out_ids.t().to(torch.int64)
         self.ctx.check_p2p()
         # a finished row emitted PAD on the device; steps between the last row's EOS and the poll that saw it are cut off here:
@@ -878,11 +889,8 @@ class LlamaEngine:
             if why is None:
                 return self._contrastive_device(embeds, attention_mask, int(max_new_tokens), float(penalty_alpha), int(top_k),
                                                 int(min_len), float(repetition_penalty), int(eos_id), int(pad_id), bool(use_graph))
-            if not LlamaEngine._warned_contrastive:
-                LlamaEngine._warned_contrastive = True
-                import warnings
-                warnings.warn(f"emu_amd: device_contrastive: {why} (the kernels answer -22 outside their range); staying on the "
-                              "host path", stacklevel=2)
+            warn_once(LlamaEngine, "_warned_contrastive",
+                      f"emu_amd: device_contrastive: {why} (the kernels answer -22 outside their range); staying on the host path")
         B, S, H = embeds.shape
         k, V, dev = int(top_k), self.vocab, self.device
         s_max = self.kv_capacity(S + max_new_tokens)
@@ -969,23 +977,18 @@ class LlamaEngine:
         self.fan_out_kv(B, k, S, s_max)
         Lc = S + L_new
         key = (B, k, S, self.s_max, L_new, min_len, alpha, repetition_penalty, eos_id, pad_id, self.kcache.data_ptr(), self.mode_epoch)
-        cache = self.__dict__.setdefault("_contrastive_graphs", {})
-        st = cache.get(key)
-        if st is None:
-            cache.clear()                                   # one signature at a time
+
+        def build():
             i32 = dict(dtype=torch.int32, device=dev)
-            st = dict(ctx_n=torch.zeros(B, Lc, H, dtype=torch.float32, device=dev), lg=torch.zeros(rows, V, device=dev, dtype=BF16),
-                      hid=torch.empty(rows, H, device=dev, dtype=BF16), normed=torch.empty(rows, H, device=dev, dtype=BF16),
-                      cand_ids=torch.zeros(rows, **i32), cand_p=torch.zeros(rows, dtype=torch.float32, device=dev),
-                      sel=torch.zeros(B, **i32), unfinished=torch.ones(B, **i32), out_ids=torch.empty(L_new, B, **i32),
-                      step=torch.zeros(1, **i32), slot=torch.empty(rows, **i32), pos=torch.empty(rows, **i32),
-                      pos0=torch.empty(rows, **i32), kstart=torch.empty(B, **i32), kstart_k=torch.empty(rows, **i32),
-                      ws=torch.empty(int(Lb.emu_contrastive_workspace_bytes(B, k, Lc)), dtype=torch.uint8, device=dev), graph=None)
-            # the decoder step's workspace: owned here, because the pointers a captured graph holds must outlive any re-allocation
-            # of the engine's shared workspace by a later, larger call
-            need = max(int(Lb.emu_llama_workspace_bytes(self.handle, rows, 1)), rows * H * 2)
-            st["fws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-            cache[key] = st
+            return dict(ctx_n=torch.zeros(B, Lc, H, dtype=torch.float32, device=dev), lg=torch.zeros(rows, V, device=dev, dtype=BF16),
+                        hid=torch.empty(rows, H, device=dev, dtype=BF16), normed=torch.empty(rows, H, device=dev, dtype=BF16),
+                        cand_ids=torch.zeros(rows, **i32), cand_p=torch.zeros(rows, dtype=torch.float32, device=dev),
+                        sel=torch.zeros(B, **i32), unfinished=torch.ones(B, **i32), out_ids=torch.empty(L_new, B, **i32),
+                        step=torch.zeros(1, **i32), slot=torch.empty(rows, **i32), pos=torch.empty(rows, **i32),
+                        pos0=torch.empty(rows, **i32), kstart=torch.empty(B, **i32), kstart_k=torch.empty(rows, **i32),
+                        ws=torch.empty(int(Lb.emu_contrastive_workspace_bytes(B, k, Lc)), dtype=torch.uint8, device=dev))
+
+        st = self._loop_state("contrastive", key, rows, build)
         st["ctx_n"][:, :S] = (ctx0 / ctx0.norm(dim=2, keepdim=True)).float()
         st["lg"].view(B, k, V)[:, 0] = logit0
         st["sel"].zero_(); st["step"].zero_(); st["unfinished"].fill_(1); st["out_ids"].fill_(pad_id)
@@ -1014,25 +1017,7 @@ class LlamaEngine:
                   self.ctx.handle)
             check(Lb.emu_contrastive_advance(p("step"), None, None, None, S, rows, L_new, 1, sm), "emu_contrastive_advance")
 
-        done_steps = 0
-        while done_steps < L_new:
-            if done_steps and not bool(st["unfinished"].any()):
-                break
-            n = min(self.BEAM_POLL, L_new - done_steps)
-            if use_graph and st["graph"] is None:
-                body()                                      # warm-up outside capture: a real step
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    body()
-                st["graph"] = g
-                done_steps += 1
-                continue
-            for _ in range(n):
-                if use_graph:
-                    st["graph"].replay()
-                else:
-                    body()
-            done_steps += n
+        run_polled(lambda i: st["captured"].step(body, use_graph, key), L_new, self.BEAM_POLL, lambda: not bool(st["unfinished"].any()))
         ids = st["out_ids"].t().to(torch.int64)
         self.set_kv_share(0, 0)
         self.ctx.check_p2p()
@@ -1128,11 +1113,9 @@ class LlamaEngine:
                    f"vocabulary {self.vocab} below 2 * num_beams" if self.vocab < 2 * num_beams else
                    "a trace is asked for" if trace is not None else None)
             if why is not None:
-                if not LlamaEngine._warned_beam_sampler:
-                    LlamaEngine._warned_beam_sampler = True
-                    import warnings
-                    warnings.warn(f"emu_amd: device_beam_sampler: {why} (emu_beam_sample_step_bf16 answers -22 outside its range); "
-                                  "staying on the host path", stacklevel=2)
+                warn_once(LlamaEngine, "_warned_beam_sampler",
+                          f"emu_amd: device_beam_sampler: {why} (emu_beam_sample_step_bf16 answers -22 outside its range); "
+                          "staying on the host path")
                 device_beam_sampler = False
         B, S, H = embeds.shape
         nb, V, dev = num_beams, self.vocab, self.device
@@ -1316,10 +1299,8 @@ class LlamaEngine:
         opts = None if params is None else (sampling, params.repetition_penalty, params.temperature, params.top_k, params.top_p)
         key = (B, nb, S, self.s_max, max_len, int(min_len), float(length_penalty), int(eos_id), bool(v431), self.kcache.data_ptr(),
                self.mode_epoch, opts)
-        cache = self.__dict__.setdefault("_beam_graphs", {})
-        st = cache.get(key)
-        if st is None:
-            cache.clear()                                   # one signature at a time: its buffers are a few MB, its graph ~430 nodes
+
+        def build():
             i32 = dict(dtype=torch.int32, device=dev)
             st = dict(running_seq=torch.empty(B, nb, max_len, **i32), sequences=torch.empty(B, nb, max_len, **i32),
                       running_scores=torch.empty(B, nb, device=dev), beam_scores=torch.empty(B, nb, device=dev),
@@ -1330,14 +1311,12 @@ class LlamaEngine:
                       pos=torch.empty(rows, **i32), pos0=torch.empty(rows, **i32), kstart=torch.empty(rows, **i32),
                       cur=torch.empty(1, **i32), lg=torch.empty(rows, V, device=dev, dtype=BF16),
                       ws=torch.empty((L.emu_beam_step_workspace_bytes if params is None else L.emu_beam_sample_workspace_bytes)(B, nb, V),
-                                     dtype=torch.uint8, device=dev), graph=None)
+                                     dtype=torch.uint8, device=dev))
             if sampling:
                 st["uni"] = torch.empty(max_len, B, 2 * nb, dtype=torch.float32, device=dev)
-            # the decoder step's workspace: owned here, because the pointers a captured graph holds must outlive any
-            # re-allocation of the engine's shared workspace by a later, larger call
-            need = max(int(L.emu_llama_workspace_bytes(self.handle, rows, 1)), rows * self.cfg.hidden_size * 2)
-            st["fws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-            cache[key] = st
+            return st
+
+        st = self._loop_state("beam", key, rows, build)
         st["running_seq"].fill_(pad_id); st["sequences"].fill_(pad_id)
         st["running_scores"].zero_()
         if not (sampling and v431):
@@ -1380,26 +1359,9 @@ class LlamaEngine:
 
         beam_step(logits0, logits0.stride(0), 0, 0, None)     # step 0: every beam continues the prompt
         st["cur"].fill_(1)
-        done_steps = 1
         use_graph = getattr(self, "beam_graph", True)
-        while done_steps < max_len:
-            if not bool(st["still_open"].any()):
-                break
-            n = min(self.BEAM_POLL, max_len - done_steps)
-            if use_graph and st["graph"] is None:
-                body()                                      # warm-up outside capture: a real step
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    body()
-                st["graph"] = g
-                done_steps += 1
-                continue
-            for _ in range(n):
-                if use_graph:
-                    st["graph"].replay()
-                else:
-                    body()
-            done_steps += n
+        run_polled(lambda i: st["captured"].step(body, use_graph, key), max_len - 1, self.BEAM_POLL,
+                   lambda: not bool(st["still_open"].any()))
         self.set_kv_share(0, 0)
         out_len = int(st["seq_len"][:, :nret].max().item())
         self.ctx.check_p2p()
@@ -1486,57 +1448,6 @@ def sample_params(do_sample: bool, temperature, top_k, top_p, repetition_penalty
                          1.0 if top_p is None else float(top_p), int(min_keep), int(eos_id), int(pad_id))
 
 
-class SampleState:
-    """Device-resident state of the sampling / penalised-greedy token loop (see emu_llama_sample_step): GreedyState's arrays, the
-    rows' ``unfinished`` flags, the table of uniforms and the options.  ``out_ids`` [max_new, B] is also the penalty's history."""
-
-    def __init__(self, eng: "LlamaEngine", B: int, next_pos: torch.Tensor, S: int, kstart: torch.Tensor, out_ids: torch.Tensor,
-                 uniforms: Optional[torch.Tensor], params: SampleParamsC):
-        self.eng, self.B = eng, B
-        dev = eng.device
-        self.cur = torch.zeros(B, device=dev, dtype=torch.int32)
-        self.pos = next_pos.to(torch.int32).clone()
-        self.slot = torch.full((B,), S, device=dev, dtype=torch.int32)
-        self.ctx = torch.tensor([S + 1], device=dev, dtype=torch.int32)
-        self.step_idx = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.unfinished = torch.ones(B, device=dev, dtype=torch.int32)
-        self.kstart, self.out_ids, self.uniforms, self.params = kstart, out_ids, uniforms, params
-        self.max_new = out_ids.shape[0]
-        self.hidden = torch.empty(B, eng.cfg.hidden_size, device=dev, dtype=BF16)
-        self.logits = torch.empty(B, eng.vocab, device=dev, dtype=BF16)
-        self.ws = eng._workspace(B, 1)
-        self.graph, self._epoch = None, -1
-
-    def first(self) -> None:
-        """The first token, from ``self.logits`` (the prefill's last rows): step 0 of the table."""
-        ops.sample(self.logits, self.step_idx, self.params, self.cur, hist=self.out_ids, uniforms=self.uniforms,
-                   unfinished=self.unfinished)
-        self.out_ids[0] = self.cur
-        self.step_idx.fill_(1)
-
-    def step(self) -> None:
-        e = self.eng
-        check(lib().emu_llama_sample_step(e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(),
-                                          self.kstart.data_ptr(), self.ctx.data_ptr(), self.step_idx.data_ptr(),
-                                          self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
-                                          self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(),
-                                          ops._p(self.uniforms), self.unfinished.data_ptr(), C.byref(self.params),
-                                          ops.stream(e.device)),
-              "emu_llama_sample_step", e.ctx.handle)
-
-    def step_graph(self) -> None:
-        """Replay the step from a hipGraph captured on first use; the kernel reads the step index from the device, so the one
-        captured step serves every token (the min-length suppress and the history length included)."""
-        if self.graph is None or self._epoch != self.eng.mode_epoch:
-            self.step()                                   # warm-up outside capture (it advances the state by one real step)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-            self.graph, self._epoch = g, self.eng.mode_epoch
-            return
-        self.graph.replay()
-
-
 class GreedyState:
     """Device-resident state of the greedy token loop (see emu_llama_greedy_step)."""
 
@@ -1554,7 +1465,7 @@ class GreedyState:
         self.hidden = torch.empty(B, eng.cfg.hidden_size, device=dev, dtype=BF16)
         self.logits = torch.empty(B, eng.vocab, device=dev, dtype=BF16)
         self.ws = eng._workspace(B, 1)
-        self.graph, self._epoch = None, -1
+        self.captured = CapturedStep()
 
     def reset(self, first_ids: torch.Tensor, next_pos: torch.Tensor, S: int) -> None:
         """Rewind the device-side state to the end of the prompt, in place (a captured graph stays valid)."""
@@ -1574,15 +1485,9 @@ class GreedyState:
               "emu_llama_greedy_step", e.ctx.handle)
 
     def step_graph(self) -> None:
-        """Replay the step from a hipGraph captured on first use (launch-bound at TP>1: ~550 launches/token)."""
-        if self.graph is None or self._epoch != self.eng.mode_epoch:
-            self.step()                                   # warm-up outside capture (lazy module loads, weight table upload)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step()
-            self.graph, self._epoch = g, self.eng.mode_epoch
-            return                                        # capture does not execute: state advanced once by warm-up...
-        self.graph.replay()
+        """One step from a hipGraph captured on first use and anew after a mode switch (launch-bound at TP>1: ~550 launches/token).
+        The kernels read the step index from the device, so the one captured step serves every token."""
+        self.captured.step(self.step, True, self.eng.mode_epoch)
 
     def step_eager_suppress(self, suppress: int) -> None:
         """A step with a suppressed id (min_length > 1): same as step() but argmax masks ``suppress``."""
@@ -1597,3 +1502,34 @@ class GreedyState:
         self.slot += 1
         self.ctx += 1
         self.step_idx += 1
+
+
+class SampleState(GreedyState):
+    """Device-resident state of the sampling / penalised-greedy token loop (see emu_llama_sample_step): GreedyState's arrays, the
+    rows' ``unfinished`` flags, the table of uniforms and the options.  ``out_ids`` [max_new, B] is also the penalty's history.
+    ``step_graph`` is GreedyState's: the min-length suppress and the history length, too, come from the device-side step index."""
+
+    def __init__(self, eng: "LlamaEngine", B: int, next_pos: torch.Tensor, S: int, kstart: torch.Tensor, out_ids: torch.Tensor,
+                 uniforms: Optional[torch.Tensor], params: SampleParamsC):
+        super().__init__(eng, B, torch.zeros(B, device=eng.device, dtype=torch.int32), next_pos, S, kstart, out_ids)
+        self.step_idx.zero_()                              # no token yet: first() draws it
+        self.unfinished = torch.ones(B, device=eng.device, dtype=torch.int32)
+        self.uniforms, self.params = uniforms, params
+        self.max_new = out_ids.shape[0]
+
+    def first(self) -> None:
+        """The first token, from ``self.logits`` (the prefill's last rows): step 0 of the table."""
+        ops.sample(self.logits, self.step_idx, self.params, self.cur, hist=self.out_ids, uniforms=self.uniforms,
+                   unfinished=self.unfinished)
+        self.out_ids[0] = self.cur
+        self.step_idx.fill_(1)
+
+    def step(self) -> None:
+        e = self.eng
+        check(lib().emu_llama_sample_step(e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(),
+                                          self.kstart.data_ptr(), self.ctx.data_ptr(), self.step_idx.data_ptr(),
+                                          self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
+                                          self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(),
+                                          ops._p(self.uniforms), self.unfinished.data_ptr(), C.byref(self.params),
+                                          ops.stream(e.device)),
+              "emu_llama_sample_step", e.ctx.handle)

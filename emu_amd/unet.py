@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from ._lib import UNetCfgC, check, lib
+from .device_loop import CapturedStep
 
 BF16 = torch.bfloat16
 
@@ -445,18 +446,12 @@ class UNetEngine:
         assert latents.is_cuda and latents.dtype == BF16 and latents.is_contiguous() and latents.shape[0] == 1
         n = len(self.schedule.timesteps) if steps is None else steps
         self._workspace(latents.shape[2], latents.shape[3])
-        i = 0
         if use_graph and n > 1:
             key = (latents.data_ptr(), float(guidance), tuple(latents.shape))
-            if self._graph is None or self._graph[0] != key:
-                self.step(latents, guidance); i += 1                      # warm-up outside capture
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self.step(latents, guidance)
-                self._graph = (key, g)
-            g = self._graph[1]
-            for _ in range(i, n):
-                g.replay()
+            if self._graph is None:
+                self._graph = CapturedStep()
+            for _ in range(n):
+                self._graph.step(lambda: self.step(latents, guidance), True, key)
         else:
             for _ in range(n):
                 self.step(latents, guidance)

@@ -410,11 +410,11 @@ def test_device_loop_with_an_early_end_and_a_reused_graph(tiny_model, prompts, o
     captures = []
     real = torch.cuda.graph
     monkeypatch.setattr(torch.cuda, "graph", lambda g, *a, **k: (captures.append(g), real(g, *a, **k))[1])
-    lm.__dict__.pop("_beam_graphs", None)
+    lm._drop_loop_states()
     run = lambda s: lm.beam_search_generate(x, mask, NB, N_NEW, min_len=MIN_LEN, uniforms=table(s, 1), device_beam_sampler=True,
                                             **kw).cpu().tolist()
     assert run(seed) == want
-    st = next(iter(lm._beam_graphs.values()))
+    st = lm._loop_states["beam"][1]
     assert len(captures) == 1 and bool(st["finished"].any()) and len(want[0]) < N_NEW and want[0][-1] == eos
     assert len(run(seed + 1)) == 1                                           # another table ...
     assert run(seed) == want and len(captures) == 1                          # ... and the first again: one capture served all three

@@ -332,3 +332,27 @@ def test_advance_follows_the_counter():
     assert A(step.data_ptr(), None, None, None, 20, 6, 4, 1, _stream()) == 0        # at the limit: nothing moves
     assert A(step.data_ptr(), pos.data_ptr(), slot.data_ptr(), pos0.data_ptr(), 20, 6, 4, 0, _stream()) == 0
     assert step.tolist() == [4] and slot.tolist() == [22] * 6
+
+
+@pytest.mark.parametrize("entry, bias", [("emu_contrastive_advance", 0), ("emu_beam_advance", -1)])
+def test_the_shared_advance_through_both_entries(entry, bias):
+    """One kernel behind both exported names: the contrastive entry counts from the step counter itself, the beam entry from one
+    before it.  70 rows = one past the 64-lane stride, so the row loop takes a second trip.  Integers against integers."""
+    rows, slot0, L = 70, 20, 4
+    host0 = [5] * 33 + [9] * 37
+    step, pos0 = _i32([2]), _i32(host0)
+    pos, slot = torch.full((rows,), -7, dtype=torch.int32, device=DEV), torch.full((rows,), -7, dtype=torch.int32, device=DEV)
+    A = getattr(_lib.lib(), entry)
+    p = lambda t: t.data_ptr()
+    assert A(p(step), p(pos), p(slot), p(pos0), slot0, rows, L, 0, _stream()) == 0
+    assert slot.tolist() == [slot0 + 2 + bias] * rows and pos.tolist() == [v + 2 + bias for v in host0] and step.tolist() == [2]
+    for want in (3, 4, 4):                                                    # phase 1: counter + 1, up to the limit and no further
+        assert A(p(step), None, None, None, slot0, rows, L, 1, _stream()) == 0
+        assert step.tolist() == [want]
+    pos.fill_(-7); slot.fill_(-7)
+    assert A(p(step), p(pos), p(slot), p(pos0), slot0, rows, L, 0, _stream()) == 0          # phase 0 at the limit: writes nothing
+    assert pos.tolist() == [-7] * rows and slot.tolist() == [-7] * rows and step.tolist() == [4]
+    for args in ((None, p(slot), p(pos0)), (p(pos), None, p(pos0)), (p(pos), p(slot), None)):
+        assert A(p(step), *args, slot0, rows, L, 0, _stream()) == -22
+    assert A(p(step), p(pos), p(slot), p(pos0), slot0, 0, L, 0, _stream()) == -22
+    assert A(p(step), None, None, None, slot0, 0, L, 1, _stream()) == -22

@@ -101,13 +101,13 @@ def test_a_second_prompt_of_the_same_shape_replays_the_same_graph(tiny_model, pr
     lm = tiny_model[0].decoder.lm
     x, mask = prompts[1]
     assert torch.equal(_dev(lm, x, mask, 8, ALPHA, 4, True, eos_id=-1), free_runs[0])
-    (st,) = lm._contrastive_graphs.values()
-    g = st["graph"]
+    st = lm._loop_states["contrastive"][1]
+    g = st["captured"].graph
     assert g is not None
     got = _dev(lm, x.flip(0).contiguous(), mask.flip(0).contiguous(), 8, ALPHA, 4, True, eos_id=-1)
     assert torch.equal(got, free_runs[0].flip(0))            # prompts never interact
-    (st2,) = lm._contrastive_graphs.values()
-    assert st2 is st and st2["graph"] is g
+    st2 = lm._loop_states["contrastive"][1]
+    assert st2 is st and st2["captured"].graph is g
 
 
 def test_eos_pads_a_prompt_and_the_width_is_the_host_loops(tiny_model, prompts, free_runs, monkeypatch):

@@ -191,7 +191,7 @@ def test_beam_search_graph_replay_equals_eager_steps(tiny_model, golden_dir):
     lm.beam_graph = True
     assert outs[(True, "5.x")] == outs[(False, "5.x")] == zm["b5_new"].tolist()
     assert outs[(True, "4.31")] == outs[(False, "4.31")]
-    assert len(lm._beam_graphs) == 1 and next(iter(lm._beam_graphs.values()))["graph"] is not None
+    assert lm._loop_states["beam"][1]["captured"].graph is not None      # (one state per loop: the 4.31 call replaced the 5.x one)
     # another prompt (other length, 3 beams, ragged batch): captured anew, equal to eager
     a = m.generate_ids(_t(z["ids3"]), _t(z["mask3"]), _t(z["image"]).cuda(), max_new_tokens=6, num_beams=3, hf_semantics="5.x").cpu()
     lm.beam_graph = False
@@ -207,7 +207,7 @@ def test_beam_search_graph_replay_equals_eager_steps(tiny_model, golden_dir):
             res[(mode, sem)] = lm.beam_search_generate(x, _t(zm["b5_mask"]), 5, 12, eos_id=eos, hf_semantics=sem).cpu().tolist()
     lm.beam_graph = True
     assert res[(True, "5.x")] == res[(False, "5.x")] and res[(True, "4.31")] == res[(False, "4.31")]
-    st = next(iter(lm._beam_graphs.values()))
+    st = lm._loop_states["beam"][1]
     assert bool(st["finished"].any()) and int(st["cur"]) <= 12          # hypotheses did end with the stand-in EOS
 
 

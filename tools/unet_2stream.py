@@ -23,7 +23,7 @@ for i in range(2):
     lat = (torch.randn(1, 4, 128, 128) * 13.0).to(torch.bfloat16).to(dev)
     with torch.no_grad():
         e.denoise(lat, 3.0, use_graph=True, steps=3)
-    engs.append(e); lats.append(lat); graphs.append(e._graph[1])
+    engs.append(e); lats.append(lat); graphs.append(e._graph.graph)
 torch.cuda.synchronize()
 
 
