@@ -133,6 +133,7 @@ _PROTOS = {
     "emu_scatter_rows_bf16": (i32, [vp, vp, vp, i32, i32, vp]),
     "emu_argmax_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "emu_sample_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32, vp]),
+    "emu_token_logprob_bf16": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp]),
     "emu_patchify": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "emu_image_resample_ws_bytes": (sz, [i32, i32, i32]),
     "emu_image_resample_norm": (i32, [vp, lng, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, sz, vp]),
@@ -177,6 +178,7 @@ _PROTOS = {
     "emu_llama_greedy_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, sz, vp]),
     "emu_llama_sample_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
                                     C.POINTER(SampleParamsC), vp]),
+    "emu_llama_score_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp]),
     "emu_vit_create": (i32, [vp, C.POINTER(VitCfgC), C.POINTER(vp)]),
     "emu_vit_destroy": (None, [vp]),
     "emu_vit_set_stem": (i32, [vp, vp, vp, vp, vp]),

@@ -450,11 +450,12 @@ int decode_attn_nsplit(int ctx) { return ctx < 1 ? 1 : (ctx + DEC_CHUNK - 1) / D
 
 namespace {
 __global__ void greedy_advance_kernel(const int32_t* cur_ids, int32_t* pos, int32_t* slot, int32_t* ctx,
-                                      int32_t* step, int32_t* out_ids, int B) {
+                                      int32_t* step, int32_t* out_ids, int B, int limit) {
     const int b = threadIdx.x;
     const int st = *step;
+    if (limit > 0 && st >= limit) return;
     if (b < B) {
-        out_ids[(size_t)st * B + b] = cur_ids[b];
+        if (out_ids) out_ids[(size_t)st * B + b] = cur_ids[b];
         pos[b] += 1;
         slot[b] += 1;
     }
@@ -508,9 +509,9 @@ int launch_regress_advance(const bf16_t* src, bf16_t* out_all, bf16_t* prev, int
 }
 
 int launch_greedy_advance(const int32_t* cur_ids, int32_t* pos, int32_t* slot, int32_t* ctx, int32_t* step,
-                          int32_t* out_ids, int B, hipStream_t s) {
+                          int32_t* out_ids, int B, int limit, hipStream_t s) {
     if (B < 1 || B > 64) return -22;
-    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(64), 0, s, cur_ids, pos, slot, ctx, step, out_ids, B);
+    hipLaunchKernelGGL(greedy_advance_kernel, dim3(1), dim3(64), 0, s, cur_ids, pos, slot, ctx, step, out_ids, B, limit);
     EMU_CHECK_LAUNCH();
     return 0;
 }

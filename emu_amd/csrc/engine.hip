@@ -527,6 +527,12 @@ int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32
     return launch_sample(B(logits), ld, rows, vocab, hist, hist_ld, hist_rows, step_dev, uniforms, uni_ld, uni_rows, params, unfinished,
                          out, probs_out, ld_probs, S(s));
 }
+int emu_token_logprob_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* targets, int tgt_ld, const int32_t* step_dev,
+                           const void* ref_logits, int ref_ld, float* lp, float* lse, int32_t* top1, float* kl, int32_t* agree,
+                           int out_ld, emu_stream_t s) {
+    return launch_token_logprob(B(logits), ld, rows, vocab, targets, tgt_ld, step_dev, 0, B(ref_logits), ref_ld, lp, lse, top1, kl, agree,
+                                out_ld, nullptr, S(s));
+}
 int emu_patchify(const void* image, int image_is_f32, void* out, int Bn, int C, int HW, int patch, int Kpad, emu_stream_t s) {
     return launch_patchify(image, image_is_f32, B(out), Bn, C, HW, patch, Kpad, S(s));
 }
@@ -1583,21 +1589,26 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
     return 0;
 }
 
-// One token of the greedy and the sampling loop: embed -> layers -> logits -> select -> state advance.  The selection is the only
-// difference: `params` null = arg-max; else emu_sample_bf16's kernel, for which the ids of steps 0 .. step - 1 in out_ids are the
-// history.  Either way the selection goes to cur_ids and the advance files it at `step`.
+// One token of the greedy, the sampling and the teacher-forced loop: embed -> layers -> logits -> select -> state advance.  The
+// selection is the only difference: `score` set = the token is FORCED (targets[step, :] of score->T rows, its log-probability under
+// the logits filed at [step, :]; nothing is selected, filed or advanced once step >= T); else `params` null = arg-max; else
+// emu_sample_bf16's kernel, for which the ids of steps 0 .. step - 1 in out_ids are the history.  Either way the selection goes to
+// cur_ids and the advance files it at `step` (the forced loop has no out_ids: its tokens are the caller's).
+struct ScoreSel { const int32_t* targets; int T; float* lp; float* lse; int32_t* top1; };
 static int llama_token_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart, int32_t* ctx_dev,
                             int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden, void* logits, int ld_logits,
                             void* workspace, size_t ws_bytes, const float* uniforms, int32_t* unfinished,
-                            const emu_sample_params* params, emu_stream_t s) {
+                            const emu_sample_params* params, const ScoreSel* score, emu_stream_t s) {
     const emu_llama_cfg& c = m->cfg;
     TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
-    if (!params) TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
+    if (score) TRY(m->ctx, launch_token_logprob(B(logits), ld_logits, Bn, c.vocab, score->targets, Bn, step_dev, score->T, nullptr, 0,
+                                                score->lp, score->lse, score->top1, nullptr, nullptr, Bn, cur_ids, S(s)));
+    else if (!params) TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
     else TRY(m->ctx, launch_sample(B(logits), ld_logits, Bn, c.vocab, out_ids, Bn, max_new, step_dev, uniforms, Bn, max_new, params,
                                    unfinished, cur_ids, nullptr, 0, S(s)));
-    TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, S(s)));
+    TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, score ? score->T : 0, S(s)));
     return 0;
 }
 
@@ -1606,7 +1617,7 @@ int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
     if (!m || !m->embed) return -22;
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, 0, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, nullptr, nullptr, nullptr, s);
+                            workspace, ws_bytes, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
@@ -1616,7 +1627,17 @@ int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
     if (!m || !m->embed || !params || !unfinished || max_new < 1) return -22;
     if (m->cfg.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;           // refused before anything is launched
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, max_new, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, uniforms, unfinished, params, s);
+                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, s);
+}
+
+int emu_llama_score_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                         int32_t* ctx_dev, int32_t* step_dev, const int32_t* targets, int T, int ctx_upper, void* hidden,
+                         void* logits, int ld_logits, void* workspace, size_t ws_bytes, float* lp, float* lse, int32_t* top1,
+                         emu_stream_t s) {
+    if (!m || !m->embed || !targets || !step_dev || !ctx_dev || T < 1) return -22;
+    const ScoreSel sel{targets, T, lp, lse, top1};
+    return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, nullptr, 0, ctx_upper, hidden, logits, ld_logits,
+                            workspace, ws_bytes, nullptr, nullptr, nullptr, &sel, s);
 }
 
 }  // extern "C"

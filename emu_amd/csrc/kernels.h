@@ -253,6 +253,11 @@ int launch_argmax(const bf16_t* logits, int ld, int rows, int vocab, int suppres
 int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                   const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* p,
                   int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, hipStream_t s);
+// score.hip: emu_token_logprob_bf16 (include/emu_hip.h).  limit > 0: nothing is written once *step_dev >= limit; force_ids (may be
+// null): force_ids[row] = the row's target, 0 for an ignored one (emu_llama_score_step's next input)
+int launch_token_logprob(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* targets, int tgt_ld, const int32_t* step_dev,
+                         int limit, const bf16_t* ref_logits, int ref_ld, float* lp, float* lse, int32_t* top1, float* kl,
+                         int32_t* agree, int out_ld, int32_t* force_ids, hipStream_t s);
 // NCHW fp32/bf16 image -> [B*gh*gw, Kpad] bf16 patch matrix (k = c*p*p + i*p + j, zero padded to Kpad)
 int launch_patchify(const void* image, int image_is_f32, bf16_t* out, int B, int C, int HW, int p, int Kpad, hipStream_t s);
 // tokens [B, 1+g*g, C] (cls dropped) -> [B, (g/s)^2, C] average over s x s windows (emu.py:82-89)
@@ -334,9 +339,10 @@ struct DecodeAttnArgs {
     float scale;
 };
 int decode_attn_nsplit(int ctx);
-// out_ids[step, b] = cur_ids[b]; pos[b]++, slot[b]++; ctx++, step++   (greedy loop state, all on device)
+// out_ids[step, b] = cur_ids[b] (out_ids may be null); pos[b]++, slot[b]++; ctx++, step++   (greedy loop state, all on device).
+// limit > 0: nothing happens once step >= limit (the teacher-forced loop, whose replays past the end must change no state)
 int launch_greedy_advance(const int32_t* cur_ids, int32_t* pos, int32_t* slot, int32_t* ctx, int32_t* step,
-                          int32_t* out_ids, int B, hipStream_t s);
+                          int32_t* out_ids, int B, int limit, hipStream_t s);
 int launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
 // out_all[step[0]] = prev = src ([B, cols] bf16); pos[b]++, slot[b]++, step[0]++   (generate_image's loop state, on the device)
 int launch_regress_advance(const bf16_t* src, bf16_t* out_all, bf16_t* prev, int32_t* pos, int32_t* slot, int32_t* step, int B,

@@ -337,6 +337,46 @@ class EmuModel:
                                 eos_token_id=eos_override, min_new_tokens=min_new)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=skip_special_tokens)
 
+    # ------------------------------------------------------------------ scoring given text (no counterpart in the reference)
+    @torch.no_grad()
+    def score_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor] = None,
+                  video: Optional[torch.Tensor] = None, cont_ids: Optional[torch.Tensor] = None,
+                  cont_mask: Optional[torch.Tensor] = None, via: str = "decode", use_graph: Optional[bool] = None,
+                  reference_logits: Optional[torch.Tensor] = None, return_logits: bool = False):
+        """How probable is the continuation ``cont_ids`` [B, T] (right padded, ``cont_mask``) behind the prompt ``input_ids`` /
+        ``attention_mask`` [B, S] (left padded, as for ``generate_ids``; ``image`` / ``video`` are scattered into its placeholder
+        slots the same way): ``LlamaEngine.score``'s dict.  The reference's Emu2 has no such call."""
+        if cont_ids is None:
+            raise ValueError("score_ids: cont_ids is required")
+        B, S = input_ids.shape
+        x = self._prompt_embeds(input_ids, image, self.n_query, IMAGE_TOKEN_ID)
+        if video is not None:
+            x = self._prompt_embeds(input_ids, video, self.v_query, gIMG_TOKEN_ID, embeds=x)
+        return self.decoder.lm.score(x.view(B, S, -1), attention_mask, cont_ids, cont_mask, via=via,
+                                     use_graph=self.use_graph if use_graph is None else bool(use_graph),
+                                     reference_logits=reference_logits, return_logits=return_logits)
+
+    @torch.no_grad()
+    def score(self, text: List[str], continuation: List[str], image: Optional[torch.Tensor] = None,
+              video: Optional[torch.Tensor] = None, image_placeholder: str = DEFAULT_IMG_PLACEHOLDER,
+              video_placeholder: str = DEFAULT_VID_PLACEHOLDER, via: str = "decode", use_graph: Optional[bool] = None,
+              reference_logits: Optional[torch.Tensor] = None, return_logits: bool = False):
+        """``score_ids`` on text: the prompts are tokenised as ``generate`` tokenises them (left padded, special tokens), the
+        continuations right padded without special tokens."""
+        if len(text) != len(continuation):
+            raise ValueError(f"score: {len(text)} prompts but {len(continuation)} continuations")
+        tok = self.decoder.tokenizer
+        text = [t.replace(image_placeholder, self.image_placeholder).replace(video_placeholder, self.video_placeholder)
+                for t in text]
+        inputs = tok(text, padding="longest", return_tensors="pt")
+        side, tok.padding_side = tok.padding_side, "right"
+        try:
+            cont = tok(list(continuation), padding="longest", return_tensors="pt", add_special_tokens=False)
+        finally:
+            tok.padding_side = side
+        return self.score_ids(inputs.input_ids, inputs.attention_mask, image, video, cont.input_ids, cont.attention_mask.bool(),
+                              via=via, use_graph=use_graph, reference_logits=reference_logits, return_logits=return_logits)
+
     # ------------------------------------------------------------------ generate_image (emu.py:92-153)
     @torch.no_grad()
     def generate_image_ids(self, prompt_ids: torch.Tensor, image: Optional[torch.Tensor] = None,

@@ -23,6 +23,7 @@ from .conf.emu_conf import CLIPVisionCfg, LlamaCfg
 from .constants import EOS_TOKEN_ID, IMAGE_TOKEN_ID, PAD_TOKEN_ID
 from .device_loop import option_or_env
 from .llama import EmuHipContext, LlamaEngine
+from .scoring import reference_candidate_losses, split_segments
 from .vit import VitEngine
 
 BF16 = torch.bfloat16
@@ -272,12 +273,8 @@ class Emu:
         f = ops.layernorm(f.view(B * T, C), self.ln_w, self.ln_b, 1e-6).view(B, T, C)
         return self.cformer.forward(f)
 
-    @torch.no_grad()
-    def generate_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor] = None,
-                     num_beams: int = 5, max_new_tokens: int = 50, min_length: int = 1, length_penalty: float = 0.0,
-                     do_sample: bool = False, temperature=None, top_k=None, top_p=None, repetition_penalty: float = 1.0,
-                     penalty_alpha=None, no_repeat_ngram_size=None, num_return_sequences: int = 1,
-                     hf_semantics: Optional[str] = None):
+    def _prompt_embeds(self, input_ids: torch.Tensor, image: Optional[torch.Tensor]) -> torch.Tensor:
+        """embed_tokens + overwrite of the <image> rows with the visual tokens (modeling_emu.py:128-134): [B, S, hidden]."""
         B, S = input_ids.shape
         x = self.lm.embed_tokens(input_ids).view(B * S, -1)
         if image is not None:
@@ -287,7 +284,16 @@ class Emu:
             if rows.numel() != e.shape[0]:
                 raise ValueError(f"shape mismatch: {rows.numel()} <image> slots cannot take {e.shape[0]} visual tokens")
             ops.scatter_rows(e, rows.contiguous(), x)
-        x = x.view(B, S, -1)
+        return x.view(B, S, -1)
+
+    @torch.no_grad()
+    def generate_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor] = None,
+                     num_beams: int = 5, max_new_tokens: int = 50, min_length: int = 1, length_penalty: float = 0.0,
+                     do_sample: bool = False, temperature=None, top_k=None, top_p=None, repetition_penalty: float = 1.0,
+                     penalty_alpha=None, no_repeat_ngram_size=None, num_return_sequences: int = 1,
+                     hf_semantics: Optional[str] = None):
+        B, S = input_ids.shape
+        x = self._prompt_embeds(input_ids, image)
         # mode selection as transformers does it (modeling_emu.py:162-179 forwards every argument to lm.generate)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
         if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample:
@@ -331,3 +337,70 @@ class Emu:
                                 top_p=top_p, repetition_penalty=repetition_penalty, penalty_alpha=penalty_alpha,
                                 no_repeat_ngram_size=no_repeat_ngram_size, num_return_sequences=num_captions)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=True)
+
+    # ------------------------------------------------------------------ predict (Emu1/models/prediction_mixin.py)
+    @torch.no_grad()
+    def predict_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor],
+                    cand_ids: torch.Tensor, cand_mask: torch.Tensor, n_segments: int = 1, via: str = "prefill",
+                    return_losses: bool = False):
+        """``_predict`` (prediction_mixin.py:36-131) at the token-id level: ONE prompt ``input_ids`` / ``attention_mask`` [1, S]
+        (its <image> slots take the visual tokens of ``image``), candidates ``cand_ids`` / ``cand_mask`` [N, Tc] right padded.  The
+        loss of a candidate is the reference's (``scoring.reference_candidate_losses``: mean over ALL shifted positions of its
+        segment's padded width); positions are arange, as the reference calls ``lm(...)`` without position ids.  The prompt is
+        prefilled once, not once per candidate.  Returns the candidate indices by ascending loss, [1, N] int64 (``return_losses``:
+        also the losses [N] fp32)."""
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError(f"predict_ids: one prompt at a time, input_ids must be [1, S], got {tuple(input_ids.shape)}")
+        N = cand_ids.shape[0]
+        segments = split_segments(N, n_segments)
+        S = input_ids.shape[1]
+        x = self._prompt_embeds(input_ids, image)
+        lp, counted = self.lm.score_continuations(x, attention_mask, cand_ids, cand_mask, n_segments=n_segments, via=via,
+                                                  hf_generate_positions=False)
+        lp, counted = lp.cpu(), counted.cpu()
+        losses = torch.empty(N, dtype=torch.float32)
+        for a, b in segments:
+            m = cand_mask[a:b].to(device="cpu", dtype=torch.int64)
+            tmax = max(1, int((m * torch.arange(1, m.shape[1] + 1)[None]).max()))       # the tokenizer pads a segment to its longest
+            losses[a:b] = reference_candidate_losses(lp[a:b], counted[a:b], S, tmax)
+        ranks = torch.argsort(losses, dim=-1)[None]
+        return (ranks, losses) if return_losses else ranks
+
+    @torch.no_grad()
+    def predict(self, samples, candidates, n_segments=1):
+        """prediction_mixin.py:5-34: rank ``candidates`` (strings) as answers to ``samples["prompt"]`` / ``samples["image"]`` by LM
+        loss, best first: [1, n_cands] int64.  A list of lists of candidates = one list per sample; the results are concatenated
+        ([n_samples, n_cands]; a plain list of lists when the lists differ in length, as the reference's)."""
+        if self.tokenizer is None:
+            raise RuntimeError("set Emu.tokenizer (LlamaTokenizer + [PAD],[IMG],[/IMG],<image>) to use the text API")
+        if type(candidates[0]) in (list, tuple):
+            results = []
+            for i in range(samples["image"].size(0)):
+                one = {"image": samples["image"][i].unsqueeze(0)}
+                if "prompt" in samples.keys():
+                    one["prompt"] = [samples["prompt"][i]]
+                results.append(self._predict(one, candidates[i], n_segments))
+            try:
+                return torch.cat(results, dim=0)
+            except RuntimeError:
+                return [res.tolist()[0] for res in results]
+        return self._predict(samples, candidates, n_segments)
+
+    def _predict(self, samples, candidates, n_segments):
+        tok = self.tokenizer
+        prompt = samples["prompt"] if "prompt" in samples.keys() else getattr(self, "prompt", None)
+        if prompt is None:
+            raise ValueError('predict: samples["prompt"] is required (this class keeps no default prompt)')
+        tok.padding_side = "left"
+        enc = tok(prompt, padding="longest", return_tensors="pt", add_special_tokens=True)
+        tok.padding_side = "right"
+        N = len(candidates)
+        # the reference tokenises segment by segment, padding to the segment's longest; the ids are the same tokenised at once, and
+        # predict_ids takes each segment's padded width from the mask
+        out = tok(list(candidates), padding="longest", return_tensors="pt", add_special_tokens=False)
+        pad_id = getattr(tok, "pad_token_id", None)
+        mask = out.attention_mask.bool()
+        if pad_id is not None:
+            mask = mask & (out.input_ids != pad_id)                      # prediction_mixin.py:110-112
+        assert out.input_ids.shape[0] == N
+        return self.predict_ids(enc.input_ids[:1], enc.attention_mask[:1], samples.get("image"), out.input_ids, mask, n_segments)

@@ -18,6 +18,7 @@ from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, S
 from .conf.emu_conf import LlamaCfg
 from .device_loop import CapturedStep, run_polled, warn_once
 from .sampling import beam_draw_margin, beam_reference_select
+from .scoring import IGNORE_INDEX, split_segments
 from .tp import ShardPlan
 
 BF16 = torch.bfloat16
@@ -605,16 +606,17 @@ class LlamaEngine:
         check(lib().emu_llama_set_kv_share(self.handle, int(rows_per_prompt), int(shared_slots)), "emu_llama_set_kv_share")
         self._kv_share = rows_per_prompt > 1
 
-    def fan_out_kv(self, B: int, n: int, S: int, s_max: int) -> None:
+    def fan_out_kv(self, B: int, n: int, S: int, s_max: int, share: bool = True) -> None:
         """After a prefill of B prompts: a cache of B * n rows (n beams / candidates per prompt) that continue the prompts.
         transformers copies the prompt's keys and values to every beam (``_expand_inputs_for_generation``); here, for
         n <= 8, they stay in ONE row per prompt and the decode attention reads them from there (``set_kv_share``): no n-fold
-        copy (6 GB at S = 770, 5 beams, 60 layers) and the prompt's keys cross the memory system once per step, not n times."""
+        copy (6 GB at S = 770, 5 beams, 60 layers) and the prompt's keys cross the memory system once per step, not n times.
+        ``share=False`` copies for every n: rows that run T > 1 tokens at a time (``score_continuations``) cannot share."""
         k_old, v_old = self.kcache, self.vcache
         # no zero fill: every slot a row reads was written first (the prompt's by the copy below -- with set_kv_share only the
         # group's first row is ever read there -- and a generated slot by the step that appends it)
         self.alloc_kv(B * n, s_max, zero=False, which="beam")
-        if 2 <= n <= self.KV_SHARE_MAX:
+        if share and 2 <= n <= self.KV_SHARE_MAX:
             first = torch.arange(B, device=self.device) * n
             self.kcache[:, first, :, :S] = k_old[:, :, :, :S]
             self.vcache[:, first, :, :S] = v_old[:, :, :, :S]
@@ -848,6 +850,163 @@ class LlamaEngine:
         # a finished row emitted PAD on the device; steps between the last row's EOS and the poll that saw it are cut off here:
         # the width is one past the last step at which any row was still unfinished, the host path's rule
         return apply_eos_padding(ids, eos_id, pad_id)
+
+    # ------------------------------------------------------------------ scoring given text
+    SCORE_CHUNK_ROWS = 256     # rows of logits per lm_head call of score(via="prefill"), see there
+    SCORE_MAX_ROWS = 64        # rows of one teacher-forced step (the advance kernel's one wave of rows)
+
+    def _score_args(self, prefix_embeds, prefix_mask, cont_ids, cont_mask, via, reference_logits) -> Tuple[int, int, int]:
+        """The refusals of ``score``, before any device work; returns (B, S, T)."""
+        if via not in ("decode", "prefill"):
+            raise ValueError(f"score: via must be 'decode' or 'prefill', got {via!r}")
+        if prefix_embeds.dim() != 3 or prefix_embeds.shape[2] != self.cfg.hidden_size:
+            raise ValueError(f"score: prefix_embeds must be [B, S, {self.cfg.hidden_size}], got {tuple(prefix_embeds.shape)}")
+        B, S, _ = prefix_embeds.shape
+        if tuple(prefix_mask.shape) != (B, S):
+            raise ValueError(f"score: prefix_mask must be [{B}, {S}], got {tuple(prefix_mask.shape)}")
+        if cont_ids.dim() != 2 or cont_ids.shape[0] != B:
+            raise ValueError(f"score: cont_ids must be [{B}, T], got {tuple(cont_ids.shape)}")
+        T = cont_ids.shape[1]
+        if T < 1 or S < 1:
+            raise ValueError("score: needs at least one prefix slot and one continuation token")
+        if cont_mask is not None and tuple(cont_mask.shape) != (B, T):
+            raise ValueError(f"score: cont_mask must be [{B}, {T}], got {tuple(cont_mask.shape)}")
+        if S + T > self.cfg.max_position_embeddings:
+            raise ValueError(f"score: prefix + continuation = {S + T} exceeds max_position_embeddings "
+                             f"{self.cfg.max_position_embeddings}")
+        if via == "decode" and B > self.SCORE_MAX_ROWS:
+            raise ValueError(f"score: via='decode' steps at most {self.SCORE_MAX_ROWS} rows at a time, got {B}; use via='prefill'")
+        if reference_logits is not None and tuple(reference_logits.shape) != (B, T, self.vocab):
+            raise ValueError(f"score: reference_logits must be [{B}, {T}, {self.vocab}], got {tuple(reference_logits.shape)}")
+        return B, S, T
+
+    @torch.no_grad()
+    def score(self, prefix_embeds: torch.Tensor, prefix_mask: torch.Tensor, cont_ids: torch.Tensor,
+              cont_mask: Optional[torch.Tensor] = None, via: str = "decode", use_graph: bool = False,
+              reference_logits: Optional[torch.Tensor] = None, return_logits: bool = False) -> Dict[str, torch.Tensor]:
+        """How probable is a GIVEN continuation: per-token log-probabilities of ``cont_ids`` [B, T] (right padded) behind the prefix
+        ``prefix_embeds`` [B, S, hidden] / ``prefix_mask`` [B, S] (left padded, images already scattered in, as for ``generate``).
+        The reference has this only as the loss of ``lm(..., labels=...)`` (Emu1/models/modeling_llama.py:110-116) behind ``predict``
+        (prediction_mixin.py:36-131); what is computed per row is specified in ``emu_amd/scoring.py``.
+
+        ``cont_mask`` false, or an id outside the vocabulary, means IGNORED: ``lp = 0``, ``counted`` false, and id 0 is fed in its
+        place.  ``lp[b, 0]`` is read from the prefix's last row, ``lp[b, t]`` from the row fed ``cont_ids[b, t - 1]``.  Returns
+        ``lp`` / ``lse`` [B, T] fp32, ``counted`` [B, T] bool, ``top1`` [B, T] int64; with ``reference_logits`` [B, T, vocab] bf16
+        also ``kl`` (KL(reference || this run) per token) and ``agree`` (bool); with ``return_logits`` the ``logits`` [B, T, vocab].
+
+        ``via="decode"``: one teacher-forced ``emu_llama_score_step`` per token (a captured graph with ``use_graph``), i.e. the
+        kernels generation runs -- whatever weight stream is active (bf16, e4m3, MXFP4 narrow or wide) is the one that is scored.
+        ``via="prefill"``: ONE forward of the T - 1 fed tokens per row on top of the prefix's cache, then the head in chunks of
+        ``SCORE_CHUNK_ROWS`` rows: 256 rows keep the [rows, vocab] buffer at 16.5 MB for the 32 274-token vocabulary and are a whole
+        tile of the head's GEMM, so lm_head is streamed once per 256 rows at full matrix-core rate.  Arguments are checked before any
+        device work (ValueError)."""
+        B, S, T = self._score_args(prefix_embeds, prefix_mask, cont_ids, cont_mask, via, reference_logits)
+        s_max = self.kv_capacity(S + T)
+        targets = self._score_targets(cont_ids, cont_mask)
+        hidden, kstart, next_pos = self.prefill(prefix_embeds, prefix_mask, s_max)
+        first_logits = self.logits(hidden[:, -1, :])
+        return self._score_on_cache(first_logits, S, kstart, next_pos, targets, via, use_graph, reference_logits, return_logits)
+
+    def _score_targets(self, cont_ids: torch.Tensor, cont_mask: Optional[torch.Tensor]) -> torch.Tensor:
+        """[B, T] int32 on the device, the ignored ones as scoring.IGNORE_INDEX."""
+        t = cont_ids.to(device=self.device, dtype=torch.int64)
+        ignored = (t < 0) | (t >= self.vocab)
+        if cont_mask is not None:
+            ignored = ignored | ~cont_mask.to(device=self.device, dtype=torch.bool)
+        return t.masked_fill(ignored, IGNORE_INDEX).to(torch.int32).contiguous()
+
+    def _score_on_cache(self, first_logits: torch.Tensor, S: int, kstart: torch.Tensor, next_pos: torch.Tensor,
+                        targets: torch.Tensor, via: str, use_graph: bool, reference_logits: Optional[torch.Tensor],
+                        return_logits: bool) -> Dict[str, torch.Tensor]:
+        """``score`` after the prefill: the engine's current cache holds the S prefix slots of ``targets.shape[0]`` rows,
+        ``first_logits`` [B, vocab] are the logits of the prefix's last rows."""
+        dev = self.device
+        B, T = targets.shape
+        tgt = torch.empty(T, B, device=dev, dtype=torch.int32).copy_(targets.t())     # [T, B]: a step's targets are one row
+        res = {"lp": torch.zeros(T, B, device=dev, dtype=torch.float32), "lse": torch.zeros(T, B, device=dev, dtype=torch.float32),
+               "top1": torch.zeros(T, B, device=dev, dtype=torch.int32)}
+        keep = return_logits or reference_logits is not None
+        all_logits = torch.empty(T, B, self.vocab, device=dev, dtype=BF16) if keep else None
+        step0 = torch.zeros(1, device=dev, dtype=torch.int32)
+        ops.token_logprob(first_logits, tgt, step_dev=step0, out=res)
+        if keep:
+            all_logits[0] = first_logits
+        fed = tgt.clamp(min=0)                                           # an ignored target feeds id 0: the row is padding from there on
+        if T > 1 and via == "decode":
+            st = ScoreState(self, B, fed[0], next_pos, S, kstart, tgt, res)
+
+            def one(i):
+                st.step_graph() if use_graph else st.step()
+                if keep:
+                    all_logits[i + 1].copy_(st.logits)
+
+            run_polled(one, T - 1, T - 1, lambda: False)                 # nothing to poll for: the tokens are given
+        elif T > 1:
+            n = T - 1
+            hid = self.embed_tokens(fed[:n].t().contiguous()).reshape(B * n, self.cfg.hidden_size).contiguous()
+            ar = torch.arange(n, device=dev, dtype=torch.int32)
+            pos = (next_pos.to(torch.int32)[:, None] + ar[None]).reshape(-1).contiguous()
+            slot = (S + ar)[None].expand(B, -1).reshape(-1).contiguous()
+            self.forward(hid, B, n, pos, slot, kstart, ctx=S + n)        # no slot-order promise: T != ctx keeps the unfused sequence
+            tg = targets[:, 1:].contiguous().reshape(-1)                 # rows of `hid` are row-major [B, n]
+            flat = {k: torch.empty(B * n, device=dev, dtype=v.dtype) for k, v in res.items()}
+            buf = torch.empty(min(self.SCORE_CHUNK_ROWS, B * n), self.vocab, device=dev, dtype=BF16)
+            for r0 in range(0, B * n, self.SCORE_CHUNK_ROWS):
+                r1 = min(r0 + self.SCORE_CHUNK_ROWS, B * n)
+                lg = self.logits(hid[r0:r1], out=buf[: r1 - r0])
+                ops.token_logprob(lg, tg[r0:r1], out={k: v[r0:r1] for k, v in flat.items()})
+                if keep:
+                    rows = torch.arange(r0, r1, device=dev)
+                    all_logits[1 + rows % n, rows // n] = lg
+            for k in res:
+                res[k][1:] = flat[k].view(B, n).t()
+        self.ctx.check_p2p()
+        out = {"lp": res["lp"].t().contiguous(), "counted": targets >= 0, "lse": res["lse"].t().contiguous(),
+               "top1": res["top1"].t().to(torch.int64)}
+        if reference_logits is not None:
+            ref = reference_logits.to(device=dev, dtype=BF16).transpose(0, 1).reshape(T * B, self.vocab).contiguous()
+            kl = ops.token_logprob(all_logits.view(T * B, self.vocab), tgt.view(-1), ref_logits=ref)
+            out["kl"] = kl["kl"].view(T, B).t().contiguous()
+            out["agree"] = kl["agree"].view(T, B).t().to(torch.bool)
+        if return_logits:
+            out["logits"] = all_logits.transpose(0, 1).contiguous()
+        return out
+
+    @torch.no_grad()
+    def score_continuations(self, prefix_embeds: torch.Tensor, prefix_mask: torch.Tensor, cand_ids: torch.Tensor,
+                            cand_mask: Optional[torch.Tensor] = None, n_segments: int = 1, via: str = "prefill",
+                            hf_generate_positions: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per-token log-probabilities of N candidate continuations ``cand_ids`` [N, Tc] (right padded, ``cand_mask`` [N, Tc]) of
+        ONE prefix ``prefix_embeds`` [1, S, hidden]: what prediction_mixin.py:36-131 ranks candidate answers by.  The reference runs
+        prompt + candidate through the model for every candidate; here the prompt is prefilled once, its K / V slots are copied to
+        the rows of a segment (``fan_out_kv``'s copy), and ``score`` runs the candidates on top.  The segments are the reference's
+        (``scoring.split_segments``); each is scored to the width of its own longest candidate.  ``hf_generate_positions``: as
+        ``prefill``'s (False = arange positions, the bare ``lm(...)`` call of the reference's ``predict``).  Returns (lp [N, Tc]
+        fp32, counted [N, Tc] bool)."""
+        if prefix_embeds.dim() != 3 or prefix_embeds.shape[0] != 1:
+            raise ValueError(f"score_continuations: prefix_embeds must be [1, S, hidden], got {tuple(prefix_embeds.shape)}")
+        if cand_ids.dim() != 2 or cand_ids.shape[0] < 1:
+            raise ValueError(f"score_continuations: cand_ids must be [N, Tc], got {tuple(cand_ids.shape)}")
+        N, Tc = cand_ids.shape
+        segments = split_segments(N, n_segments)
+        for a, b in segments:                                            # every refusal before any device work
+            self._score_args(prefix_embeds.expand(b - a, -1, -1), prefix_mask.expand(b - a, -1), cand_ids[a:b],
+                             None if cand_mask is None else cand_mask[a:b], via, None)
+        S = prefix_embeds.shape[1]
+        targets = self._score_targets(cand_ids, cand_mask)
+        width = (targets >= 0).int().mul(torch.arange(1, Tc + 1, device=self.device, dtype=torch.int32)[None]).amax(dim=1)
+        widths = [max(1, int(width[a:b].max())) for a, b in segments]
+        s_max = self.kv_capacity(S + max(widths))
+        hidden, kstart, next_pos = self.prefill(prefix_embeds, prefix_mask, s_max, hf_generate_positions)
+        first_logits = self.logits(hidden[:, -1, :])
+        lp = torch.zeros(N, Tc, device=self.device, dtype=torch.float32)
+        for (a, b), w in zip(segments, widths):
+            self.alloc_kv(1, s_max)                                      # back to the prefix's cache: the source of the copy
+            self.fan_out_kv(1, b - a, S, s_max, share=False)
+            r = self._score_on_cache(first_logits.expand(b - a, -1).contiguous(), S, kstart.expand(b - a).contiguous(),
+                                     next_pos.expand(b - a).contiguous(), targets[a:b, :w].contiguous(), via, False, None, False)
+            lp[a:b, :w] = r["lp"]
+        return lp, targets >= 0
 
     # ------------------------------------------------------------------ contrastive search
     @torch.no_grad()
@@ -1533,3 +1692,24 @@ class SampleState(GreedyState):
                                           ops._p(self.uniforms), self.unfinished.data_ptr(), C.byref(self.params),
                                           ops.stream(e.device)),
               "emu_llama_sample_step", e.ctx.handle)
+
+
+class ScoreState(GreedyState):
+    """Device-resident state of the teacher-forced loop (see emu_llama_score_step): GreedyState's arrays without ``out_ids`` -- the
+    tokens are given: ``targets`` int32 [T, B], the ignored ones negative -- and the results ``lp`` / ``lse`` / ``top1`` [T, B], row 0
+    of which the caller filled from the prefill's logits.  ``step_graph`` is GreedyState's: the step index, and with it the row of
+    targets and results, comes from the device."""
+
+    def __init__(self, eng: "LlamaEngine", B: int, first_ids: torch.Tensor, next_pos: torch.Tensor, S: int, kstart: torch.Tensor,
+                 targets: torch.Tensor, res: Dict[str, torch.Tensor]):
+        super().__init__(eng, B, first_ids, next_pos, S, kstart, None)
+        self.targets, self.res, self.T = targets, res, targets.shape[0]
+
+    def step(self) -> None:
+        e = self.eng
+        check(lib().emu_llama_score_step(e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(),
+                                         self.kstart.data_ptr(), self.ctx.data_ptr(), self.step_idx.data_ptr(),
+                                         self.targets.data_ptr(), self.T, e.s_max, self.hidden.data_ptr(), self.logits.data_ptr(),
+                                         self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(), self.res["lp"].data_ptr(),
+                                         self.res["lse"].data_ptr(), self.res["top1"].data_ptr(), ops.stream(e.device)),
+              "emu_llama_score_step", e.ctx.handle)

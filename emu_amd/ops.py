@@ -325,6 +325,46 @@ def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist
     return out
 
 
+def token_logprob(logits, targets, ref_logits=None, vocab: Optional[int] = None, step_dev=None, out=None):
+    """``emu_token_logprob_bf16`` (include/emu_hip.h; specified in emu_amd/scoring.py): the log-probability of the forced target of
+    every row of bf16 ``logits`` [rows, >= vocab].  ``targets`` int32 [rows] -- or [steps, rows] with ``step_dev`` int32 [1] on the
+    device naming the row of it (and of every output) in use.  ``ref_logits`` [rows, >= vocab] bf16 adds ``kl`` and ``agree``.
+    Returns a dict of ``lp`` / ``lse`` fp32, ``top1`` int32 (and ``kl`` fp32, ``agree`` int32), shaped like ``targets``; ``out`` may
+    hand in such a dict to be written into."""
+    def flat(t, name, dtype):        # (is_contiguous, not _req's stride test: a one-element dimension may carry any stride)
+        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} GPU tensor")
+
+    _req(logits, "logits"); flat(targets, "targets", torch.int32)
+    rows = logits.shape[0]
+    vocab = logits.shape[1] if vocab is None else vocab
+    if targets.shape[-1] != rows or (targets.dim() != 1 and step_dev is None):
+        raise ValueError(f"targets must be contiguous int32 [{rows}], or [steps, {rows}] with step_dev; got {tuple(targets.shape)}")
+    if ref_logits is not None:
+        _req(ref_logits, "ref_logits")
+        if ref_logits.shape[0] != rows or ref_logits.shape[1] < vocab:
+            raise ValueError(f"ref_logits must be [{rows}, >= {vocab}], got {tuple(ref_logits.shape)}")
+    if step_dev is not None:
+        flat(step_dev, "step_dev", torch.int32)
+    if out is None:
+        out = {"lp": torch.empty(targets.shape, device=logits.device, dtype=torch.float32),
+               "lse": torch.empty(targets.shape, device=logits.device, dtype=torch.float32),
+               "top1": torch.empty(targets.shape, device=logits.device, dtype=torch.int32)}
+        if ref_logits is not None:
+            out["kl"] = torch.empty(targets.shape, device=logits.device, dtype=torch.float32)
+            out["agree"] = torch.empty(targets.shape, device=logits.device, dtype=torch.int32)
+    for name, dt in (("lp", torch.float32), ("lse", torch.float32), ("top1", torch.int32), ("kl", torch.float32), ("agree", torch.int32)):
+        if out.get(name) is not None:
+            flat(out[name], f"out[{name!r}]", dt)
+            if out[name].shape != targets.shape:
+                raise ValueError(f"out[{name!r}] must be shaped like targets")
+    check(lib().emu_token_logprob_bf16(_p(logits), logits.stride(0), rows, vocab, _p(targets), rows, _p(step_dev), _p(ref_logits),
+                                       ref_logits.stride(0) if ref_logits is not None else 0, _p(out.get("lp")), _p(out.get("lse")),
+                                       _p(out.get("top1")), _p(out.get("kl")), _p(out.get("agree")), rows, stream(logits)),
+          "emu_token_logprob_bf16")
+    return out
+
+
 def avgpool_tokens(x, grid: int, stride: int):
     """x [B, 1+grid*grid, C] -> [B, (grid/stride)^2, C] (cls dropped)."""
     _req(x, "x")

@@ -365,6 +365,23 @@ typedef struct emu_sample_params {
 int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                     const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
                     int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, emu_stream_t s);
+/* The log-probability of a FORCED token under each row of logits (the specification is emu_amd/scoring.py): what the reference's LM
+ * loss is made of (Emu1/models/modeling_llama.py:110-116: CrossEntropyLoss over shifted logits / labels) and what its `predict` ranks
+ * candidate answers by (Emu1/models/prediction_mixin.py:36-131).  Per row, in fp32: m = max x, lse = m + log(sum exp(x - m)),
+ * lp = x[t] - lse for the row's target t (a target outside [0, vocab) -- the reference's ignore value is -100 -- gives lp = 0;
+ * x[t] = -inf gives -inf), top1 = the first index of the maximum (emu_argmax_bf16's tie rule), and with a reference row r:
+ * kl = sum_j p_r[j] * (logp_r[j] - logp_x[j]) (terms with p_r[j] == 0 left out; +inf where x rules out what r allows) and
+ * agree = (top1(x) == top1(r)).
+ * logits / ref_logits: bf16 rows ld / ref_ld elements apart, any 2-byte-aligned base, any vocabulary (the row is streamed, not held
+ * in LDS).  With step = step_dev ? *step_dev : 0 (device int32[1], never a host scalar: one captured graph serves every step) the
+ * target of row r is targets[step * tgt_ld + r] and every output is written at out[step * out_ld + r].  Every output pointer may be
+ * NULL; without ref_logits, kl and agree are not written.  One workgroup per row; every sum is a fixed-order blocked sum (no
+ * floating-point atomics): the same inputs give the same bits.  No allocation, no synchronisation: capturable.
+ * -22 (nothing is launched or written): logits or targets NULL, ld < vocab, ref_logits with ref_ld < vocab, rows < 1, vocab < 1,
+ * tgt_ld < rows or out_ld < rows. */
+int emu_token_logprob_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* targets, int tgt_ld,
+                           const int32_t* step_dev, const void* ref_logits, int ref_ld, float* lp, float* lse, int32_t* top1,
+                           float* kl, int32_t* agree, int out_ld, emu_stream_t s);
 /* PatchEmbed conv as im2col (eva_vit.py:327-335): image NCHW (fp32 or bf16) -> [B*g*g, Kpad] bf16 */
 int emu_patchify(const void* image, int image_is_f32, void* out, int B, int C, int HW, int patch, int Kpad,
                  emu_stream_t s);
@@ -619,6 +636,17 @@ int emu_llama_sample_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, i
                           int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
                           int32_t* unfinished, const emu_sample_params* params, emu_stream_t s);
+/* emu_llama_greedy_step with the next token FORCED instead of chosen: one teacher-forced step of scoring a given continuation
+ * (Emu1/models/prediction_mixin.py:36-131 ranks candidates by the LM loss of Emu1/models/modeling_llama.py:110-116; here the rows run
+ * through the decode kernels, so the active weight stream -- bf16, e4m3, MXFP4 -- is the one that is scored).  With step = *step_dev:
+ * embed(cur_ids) -> layers -> logits -> emu_token_logprob_bf16 against targets[step, :] (targets int32 [T, B]; lp / lse / top1
+ * [T, B], each may be NULL, written at [step, :]) -> cur_ids = targets[step, :] with an ignored target replaced by id 0 (that row is
+ * padding from there on) -> pos / slot / ctx / step advance by one.  Once step >= T the scoring, the forcing and the advance do
+ * nothing, so a replay past the end changes no state.  Graph-capturable: one captured step replays for every token. */
+int emu_llama_score_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                         int32_t* ctx_dev, int32_t* step_dev, const int32_t* targets, int T, int ctx_upper, void* hidden,
+                         void* logits, int ld_logits, void* workspace, size_t ws_bytes, float* lp, float* lse, int32_t* top1,
+                         emu_stream_t s);
 /* One step of transformers' beam search (lm.generate(num_beams=N), Emu2/emu/emu.py:163-172,213-229: the library's BeamSearchScorer
  * logic in its vectorised form), deterministic mode, in two launches: log-softmax of the N beams' logit rows of every prompt, the 2N
  * best continuations over beams x vocabulary of (log p + running score) with EOS masked while cur < min_len, then the bookkeeping --
