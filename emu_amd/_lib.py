@@ -69,6 +69,11 @@ class SampleParamsC(C.Structure):
                 ("top_k", i32), ("top_p", f32), ("min_keep", i32), ("eos_id", i32), ("pad_id", i32)]
 
 
+class TokenTrieC(C.Structure):
+    """emu_token_trie (include/emu_hip.h): the flat tables of emu_amd.constrain.TokenTrie on the device."""
+    _fields_ = [("first", vp), ("tok", vp), ("child", vp), ("nodes", i32), ("edges", i32)]
+
+
 SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
 CONTRASTIVE_MAX_K = 8      # EMU_CONTRASTIVE_MAX_K: candidates per prompt of the contrastive-search kernels
 CONTRASTIVE_CHUNK_ROWS = 8   # EMU_CONTRASTIVE_CHUNK_ROWS: context rows per workgroup of emu_contrastive_score's first launch
@@ -133,6 +138,8 @@ _PROTOS = {
     "emu_scatter_rows_bf16": (i32, [vp, vp, vp, i32, i32, vp]),
     "emu_argmax_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "emu_sample_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32, vp]),
+    "emu_sample_trie_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32,
+                                   C.POINTER(TokenTrieC), vp, vp]),
     "emu_token_logprob_bf16": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp]),
     "emu_patchify": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "emu_image_resample_ws_bytes": (sz, [i32, i32, i32]),
@@ -167,6 +174,8 @@ _PROTOS = {
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),
     "emu_llama_set_kv_share": (i32, [vp, i32, i32]),
     "emu_beam_step_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "emu_beam_step_trie_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                      C.POINTER(TokenTrieC), vp, vp]),
     "emu_beam_step_workspace_bytes": (sz, [i32, i32, i32]),
     "emu_beam_sample_step_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                         C.POINTER(SampleParamsC), i32, vp, i32, vp, vp, lng, vp]),
@@ -178,6 +187,8 @@ _PROTOS = {
     "emu_llama_greedy_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, sz, vp]),
     "emu_llama_sample_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
                                     C.POINTER(SampleParamsC), vp]),
+    "emu_llama_sample_step_trie": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
+                                         C.POINTER(SampleParamsC), C.POINTER(TokenTrieC), vp, vp]),
     "emu_llama_score_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp]),
     "emu_vit_create": (i32, [vp, C.POINTER(VitCfgC), C.POINTER(vp)]),
     "emu_vit_destroy": (None, [vp]),

@@ -21,7 +21,12 @@
 // The step index and everything derived from it (EOS suppression below min_len, the length divisors) are read from a device counter
 // when one is given, so a captured hipGraph replays the step for every token.
 // Out: the N tokens to feed next, the beam each of them extends (flat cache row, for the KV re-order), the updated state.
+// Under a constraint (emu_beam_step_trie_bf16; BeamStepArgs::node set) every beam carries a trie node.  Kernel 1 takes the chunk's
+// statistics from the unmasked values (the library masks the LOG-PROBABILITIES, after the softmax), then sets a 1024-bit map in LDS
+// from the node's edges that fall in the chunk and puts -inf over the rest before the 2N rounds, so a chunk may hand up -inf
+// candidates: they rank by index among themselves like every tie.  Kernel 2, after the bookkeeping, moves the nodes with the beams.
 #include "beam_common.h"
+#include "trie.h"
 
 namespace {
 
@@ -54,6 +59,7 @@ __device__ __forceinline__ void block_argmax(float& v, int& i, float* red_v, int
 __global__ __launch_bounds__(NT) void beam_chunk_kernel(const BeamStepArgs a, float* part, int nchunk) {
     __shared__ float red_v[NW];
     __shared__ int red_i[NW];
+    __shared__ unsigned int allow[CHUNK / 32];         // constraint: the chunk's allowed ids
     const int c = blockIdx.x, j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cur = a.cur_dev ? *a.cur_dev : a.cur;
     if (cur >= a.L) return;                            // graph replays beyond the length limit are no-ops
@@ -85,6 +91,27 @@ __global__ __launch_bounds__(NT) void beam_chunk_kernel(const BeamStepArgs a, fl
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (suppress_eos && vi[e] == a.eos_id) x[e] = -INFINITY;
+    if (a.node) {                                      // the constraint, where the library's processor stands: after the suppress
+        if (tid < CHUNK / 32) allow[tid] = 0u;
+        __syncthreads();
+        const int base = c * CHUNK;
+        int lo, hi;
+        if (trie_edges(a.trie, a.node[(size_t)b * a.nb + j], lo, hi)) {
+            for (int e = trie_lower_bound(a.trie.tok, lo, hi, base) + tid; e < hi; e += NT) {
+                const int id = a.trie.tok[e] - base;
+                if (id >= CHUNK) break;                // ascending ids: the rest lies in later chunks
+                if (id >= 0) atomicOr(&allow[id >> 5], 1u << (id & 31));
+            }
+        } else if (tid == 0 && a.eos_id >= base && a.eos_id < base + CHUNK) {
+            allow[(a.eos_id - base) >> 5] = 1u << ((a.eos_id - base) & 31);       // exhausted: EOS alone
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int id = tid + NT * e;
+            if (!((allow[id >> 5] >> (id & 31)) & 1u)) x[e] = -INFINITY;
+        }
+    }
     const int T = 2 * a.nb;
     for (int k = 0; k < T; ++k) {
         float bv = -INFINITY; int bi = 0x7fffffff;
@@ -145,6 +172,15 @@ __global__ __launch_bounds__(NT) void beam_step_kernel(const BeamStepArgs a, con
     }
     __syncthreads();
     beam_bookkeeping<NT>(a, b, cur, top_lp, top_idx);
+    if (a.node) {                                      // the new beam tid continues an old one: its node follows, by the token it took
+        int nn = -1;
+        if (tid < nb) {                                // (next_tok / beam_flat of this entry were written by this very thread)
+            const int src = (int)(a.beam_flat[b * nb + tid] - (long)b * nb);
+            if (src >= 0 && src < nb) nn = trie_child(a.trie, a.node[(size_t)b * nb + src], a.next_tok[b * nb + tid]);
+        }
+        __syncthreads();                               // every old node is read before the first new one is written
+        if (tid < nb) a.node[(size_t)b * nb + tid] = nn;
+    }
 }
 
 // ---- the rest of a beam step that used to be host work: with this and launch_step_advance (attention.hip) the whole step {advance,
@@ -200,6 +236,7 @@ int launch_beam_step(const BeamStepArgs& a, float* ws, size_t ws_floats, hipStre
     if (a.B < 1 || a.nb < 1 || a.nb > BEAM_MAXN || a.L < 1 || a.L > BEAM_MAXL || (!a.cur_dev && (a.cur < 0 || a.cur >= a.L)) || a.V < 2 * a.nb ||
         a.min_len < 0 || !ws || ws_floats < beam_step_ws_floats(a.B, a.nb, a.V))
         return -22;
+    if (a.node && !trie_args_ok(&a.trie, a.node)) return -22;
     const int nchunk = (a.V + CHUNK - 1) / CHUNK;
     hipLaunchKernelGGL(beam_chunk_kernel, dim3(nchunk, a.nb, a.B), dim3(NT), 0, s, a, ws, nchunk);
     hipLaunchKernelGGL(beam_step_kernel, dim3(a.B), dim3(NT), 0, s, a, ws, nchunk);

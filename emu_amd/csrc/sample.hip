@@ -7,7 +7,13 @@
 // One workgroup of 1024 threads per row; the row in LDS as keys, the odd per-thread chunks, the threshold searches and the blocked sums
 // are sample_common.h's (shared with the beam rows of beam_sample.hip).  The un-normalised probabilities exp(s - max) of the owned
 // ids stay in registers.
+//
+// Under a constraint (emu_sample_trie_bf16) every thread walks the sorted edge slice of the row's trie node alongside the ids it owns
+// and writes -inf over those that are no edge, right after the suppress: the row fills the LDS at V = 40 000, so there is no room for
+// a bitmap, and from there on a thread reads only the ids it owns, so the mask needs no barrier of its own.  Thread 0 advances the
+// node by the id it files.
 #include "sample_common.h"
+#include "trie.h"
 
 namespace {
 
@@ -20,6 +26,7 @@ struct SampleArgs {
     int do_sample; float temperature; int top_k; float top_p; int min_keep;
     int eos_id; int pad_id;
     int32_t* unfinished; int32_t* out; float* probs; int ld_probs;
+    emu_token_trie trie; int32_t* node;                          // node null = no constraint
 };
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
@@ -64,6 +71,25 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
     const int i0 = tid * C;
     const int n = i0 >= V ? 0 : (V - i0 < C ? V - i0 : C);       // ids this thread owns: [i0, i0 + n)
 
+    // 3a. constraint: the ids that are no edge of the row's node -> -inf (the exhausted node allows EOS alone)
+    const int node = a.node ? a.node[row] : 0;
+    if (a.node) {
+        int lo, hi;
+        const bool live = trie_edges(a.trie, node, lo, hi);
+        int e = live && n > 0 ? trie_lower_bound(a.trie.tok, lo, hi, i0) : hi;
+        for (int j = 0; j < n; ++j) {
+            const int id = i0 + j;
+            bool ok;
+            if (live) {
+                while (e < hi && a.trie.tok[e] < id) ++e;
+                ok = e < hi && a.trie.tok[e] == id;
+            } else {
+                ok = id == a.eos_id;
+            }
+            if (!ok) score[id] = -INFINITY;
+        }
+    }
+
     // 4. greedy: first index of the maximum
     if (!a.do_sample) {
         float best = -INFINITY;
@@ -77,6 +103,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
             const int tok = bi < V ? bi : 0;
             a.out[row] = tok;
             if (a.unfinished && tok == a.eos_id) a.unfinished[row] = 0;
+            if (a.node) a.node[row] = trie_child(a.trie, node, tok);
         }
         return;
     }
@@ -153,6 +180,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
         if (tok < 0 || tok >= V) tok = 0;
         a.out[row] = tok;
         if (a.unfinished && tok == a.eos_id) a.unfinished[row] = 0;
+        if (a.node) a.node[row] = trie_child(a.trie, node, tok);
     }
 }
 
@@ -160,7 +188,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
 
 int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                   const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* p,
-                  int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, hipStream_t s) {
+                  int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, const emu_token_trie* trie, int32_t* node,
+                  hipStream_t s) {
+    if ((trie || node) && !trie_args_ok(trie, node)) return -22;
     if (!logits || !step_dev || !out || !p || rows < 1 || vocab < 1 || vocab > EMU_SAMPLE_MAX_VOCAB || ld < vocab) return -22;
     if (p->min_keep < 1 || !(p->repetition_penalty > 0.f)) return -22;
     if (p->do_sample && (!uniforms || uni_rows < 1 || uni_ld < rows || !(p->temperature > 0.f) || !(p->top_p > 0.f))) return -22;
@@ -175,6 +205,7 @@ int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32
     a.do_sample = p->do_sample; a.temperature = p->temperature; a.top_k = p->top_k; a.top_p = p->top_p; a.min_keep = p->min_keep;
     a.eos_id = p->eos_id; a.pad_id = p->pad_id;
     a.unfinished = unfinished; a.out = out; a.probs = probs_out; a.ld_probs = ld_probs;
+    a.trie = trie ? *trie : emu_token_trie{}; a.node = node;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

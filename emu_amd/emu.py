@@ -20,6 +20,7 @@ from .constants import *  # noqa: F401,F403  (re-exported like the reference mod
 from .constants import (DEFAULT_gIMG_TOKEN, DEFAULT_IMAGE_TOKEN, DEFAULT_IMG_END_TOKEN, DEFAULT_IMG_PLACEHOLDER,
                         DEFAULT_IMG_TOKEN, DEFAULT_VID_PLACEHOLDER, EOS_TOKEN_ID, IMAGE_TOKEN_ID, IMG_TOKEN_ID,
                         PAD_TOKEN_ID, VOCAB_EMU2, VOCAB_EMU2_CHAT, gIMG_TOKEN_ID, special_tokens_list)
+from .constrain import pop_constraint
 from .device_loop import CapturedStep, option_or_env
 from .llama import EmuHipContext, LlamaEngine
 
@@ -242,7 +243,8 @@ class EmuModel:
                      temperature=None, top_k=None, top_p=None, repetition_penalty: float = 1.0,
                      penalty_alpha: Optional[float] = None, no_repeat_ngram_size: int = 0,
                      num_return_sequences: int = 1, hf_semantics: Optional[str] = None,
-                     eos_token_id: Optional[int] = None, min_new_tokens: Optional[int] = None) -> torch.Tensor:
+                     eos_token_id: Optional[int] = None, min_new_tokens: Optional[int] = None,
+                     constraint=None) -> torch.Tensor:
         """``generate`` at the token-id level: returns the NEW ids [B, n] (what HF returns for inputs_embeds).  Mode
         selection as transformers does it: contrastive search (penalty_alpha > 0, top_k > 1, one beam, no sampling), beam
         search / beam sampling (num_beams > 1), sampling or penalised greedy, plain greedy (device-side loop, hipGraph).
@@ -252,7 +254,10 @@ class EmuModel:
         ``inputs_embeds``: 4.31 compares against the EMPTY id sequence (min_len new tokens), 5.x subtracts the prompt length first
         (``_prepare_generated_length``: the default min_len = 1 then enforces nothing and EOS may be the first token -- pinned by
         the real reference's ids in tests/golden/generate_beam_eos_tiny.npz).  ``eos_token_id`` / ``min_new_tokens``: the options
-        of that name the reference forwards to ``lm.generate`` through ``**kwargs`` (emu.py:175,228)."""
+        of that name the reference forwards to ``lm.generate`` through ``**kwargs`` (emu.py:175,228).  ``constraint``: an
+        ``emu_amd.constrain.TokenTrie`` (may run on the device) or a callable with the library's ``prefix_allowed_tokens_fn`` signature
+        (keeps the host loop), see ``LlamaEngine.beam_search_generate`` / ``sample_generate``; with one beam the call goes to
+        ``sample_generate``; contrastive search with a constraint is not built."""
         B, S = input_ids.shape
         sem = hf_semantics or getattr(self, "hf_semantics", "4.31")
         eos = EOS_TOKEN_ID if eos_token_id is None else int(eos_token_id)
@@ -274,6 +279,8 @@ class EmuModel:
                 and not do_sample):
             if ngram or nret != 1:
                 raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
+            if constraint is not None:
+                raise NotImplementedError("contrastive search with a constraint is not built")
             # with the option off the call is the old one
             on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
                 if getattr(self, "device_contrastive", False) else {}
@@ -292,18 +299,21 @@ class EmuModel:
                               stacklevel=2)
             # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
             on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
+            if constraint is not None:
+                on_device["constraint"] = constraint
             return self.decoder.lm.beam_search_generate(x.view(B, S, -1), attention_mask, num_beams, max_new_tokens, min_len,
                                                         length_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID,
                                                         do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
                                                         num_return_sequences=nret, hf_semantics=sem, **on_device)
-        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
+        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
             return self.decoder.lm.sample_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len, do_sample,
                                                    temperature, top_k, top_p, repetition_penalty, eos_id=eos,
                                                    pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram, num_return_sequences=nret,
                                                    # the n-gram ban is not built on the device: it keeps the host loop
                                                    device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram,
-                                                   use_graph=self.use_graph)
+                                                   use_graph=self.use_graph,
+                                                   **({} if constraint is None else dict(constraint=constraint)))
         return self.decoder.lm.greedy_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len,
                                                eos_id=eos, pad_id=PAD_TOKEN_ID, use_graph=self.use_graph,
                                                stop_on_eos=stop_on_eos)
@@ -323,6 +333,7 @@ class EmuModel:
         kwargs.pop("use_cache", None)                   # always cached
         ngram = int(kwargs.pop("no_repeat_ngram_size", 0) or 0)
         nret = int(kwargs.pop("num_return_sequences", 1) or 1)
+        constraint = pop_constraint(kwargs)
         if kwargs:
             raise TypeError(f"EmuModel.generate: unsupported generation options {sorted(kwargs)} "
                             "(the HIP engine implements greedy / beam / sampling / contrastive search with the arguments of the signature)")
@@ -334,7 +345,7 @@ class EmuModel:
                                 num_beams=num_beams, length_penalty=length_penalty, do_sample=do_sample,
                                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                 penalty_alpha=penalty_alpha, no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                eos_token_id=eos_override, min_new_tokens=min_new)
+                                eos_token_id=eos_override, min_new_tokens=min_new, constraint=constraint)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=skip_special_tokens)
 
     # ------------------------------------------------------------------ scoring given text (no counterpart in the reference)

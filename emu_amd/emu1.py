@@ -21,6 +21,7 @@ import torch
 from . import ops
 from .conf.emu_conf import CLIPVisionCfg, LlamaCfg
 from .constants import EOS_TOKEN_ID, IMAGE_TOKEN_ID, PAD_TOKEN_ID
+from .constrain import pop_constraint
 from .device_loop import option_or_env
 from .llama import EmuHipContext, LlamaEngine
 from .scoring import reference_candidate_losses, split_segments
@@ -291,7 +292,9 @@ class Emu:
                      num_beams: int = 5, max_new_tokens: int = 50, min_length: int = 1, length_penalty: float = 0.0,
                      do_sample: bool = False, temperature=None, top_k=None, top_p=None, repetition_penalty: float = 1.0,
                      penalty_alpha=None, no_repeat_ngram_size=None, num_return_sequences: int = 1,
-                     hf_semantics: Optional[str] = None):
+                     hf_semantics: Optional[str] = None, constraint=None):
+        """``constraint``: an ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature
+        (Emu1/mm_eval/models/emu.py:96-109), see ``EmuModel.generate_ids``."""
         B, S = input_ids.shape
         x = self._prompt_embeds(input_ids, image)
         # mode selection as transformers does it (modeling_emu.py:162-179 forwards every argument to lm.generate)
@@ -299,6 +302,8 @@ class Emu:
         if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample:
             if ngram or nret != 1:
                 raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
+            if constraint is not None:
+                raise NotImplementedError("contrastive search with a constraint is not built")
             # with the option off the call is the old one
             on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
                 if getattr(self, "device_contrastive", False) else {}
@@ -307,23 +312,27 @@ class Emu:
         if num_beams > 1:
             # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
             on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
+            if constraint is not None:
+                on_device["constraint"] = constraint
             return self.lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_length, length_penalty,
                                                 eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, do_sample=do_sample,
                                                 temperature=temperature, top_k=top_k, top_p=top_p,
                                                 repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
                                                 num_return_sequences=nret,
                                                 hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"), **on_device)
-        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1:
+        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
             return self.lm.sample_generate(x, attention_mask, max_new_tokens, min_length, do_sample, temperature, top_k, top_p,
                                            repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID,
                                            no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                           device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram)
+                                           device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram,
+                                           **({} if constraint is None else dict(constraint=constraint)))
         return self.lm.greedy_generate(x, attention_mask, max_new_tokens, min_length, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
 
     @torch.no_grad()
     def generate(self, samples, do_sample=False, num_beams=5, max_new_tokens=50, min_length=1, top_p=0.9,
                  repetition_penalty=1.0, length_penalty=0.0, num_captions=1, temperature=1, penalty_alpha=None, top_k=None,
                  no_repeat_ngram_size=None, **kwargs) -> List[str]:
+        constraint = pop_constraint(kwargs)
         if kwargs:
             raise TypeError(f"Emu.generate: unsupported generation options {sorted(kwargs)}")
         if self.tokenizer is None:
@@ -335,7 +344,7 @@ class Emu:
         ids = self.generate_ids(enc.input_ids, enc.attention_mask, samples.get("image"), num_beams, max_new_tokens,
                                 min_length, length_penalty, do_sample=do_sample, temperature=temperature, top_k=top_k,
                                 top_p=top_p, repetition_penalty=repetition_penalty, penalty_alpha=penalty_alpha,
-                                no_repeat_ngram_size=no_repeat_ngram_size, num_return_sequences=num_captions)
+                                no_repeat_ngram_size=no_repeat_ngram_size, num_return_sequences=num_captions, constraint=constraint)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=True)
 
     # ------------------------------------------------------------------ predict (Emu1/models/prediction_mixin.py)

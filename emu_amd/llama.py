@@ -16,6 +16,7 @@ import torch
 from . import mxfp4, ops
 from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
+from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
 from .sampling import beam_draw_margin, beam_reference_select
 from .scoring import IGNORE_INDEX, split_segments
@@ -757,7 +758,7 @@ class LlamaEngine:
                         top_p: Optional[float] = None, repetition_penalty: float = 1.0, eos_id: int = 2,
                         pad_id: int = 32000, no_repeat_ngram_size: int = 0, num_return_sequences: int = 1,
                         device_sampler: bool = False, use_graph: bool = False,
-                        uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        uniforms: Optional[torch.Tensor] = None, constraint=None) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=1)`` with logits processing: repetition penalty, min_length, then
         (when sampling) temperature / top-k / top-p warpers and a multinomial draw from torch's global CUDA generator
         (transformers' processor order).  The decoder runs on the HIP engine; the tiny per-step logits post-processing is
@@ -773,7 +774,15 @@ class LlamaEngine:
         host path's ``multinomial``, which is why this is an option.  Refused with a ValueError before any device work:
         ``no_repeat_ngram_size > 0`` (the n-gram ban keeps the host path) and tensor parallelism (the ranks would need one shared
         table of uniforms).  A vocabulary above the kernel's bound (``_lib.SAMPLE_MAX_VOCAB``, where ``emu_sample_bf16`` answers
-        -22) stays on the host path with one warning."""
+        -22) stays on the host path with one warning.
+
+        ``constraint`` (``emu_amd.constrain.TokenTrie`` or a callable (batch_id, ids generated so far) -> allowed ids, the library's
+        ``prefix_allowed_tokens_fn``): the mask stands where the library's PrefixConstrainedLogitsProcessor does, after the
+        processors and ahead of the warpers.  A trie with ``device_sampler=True`` runs on the device (``emu_sample_trie_bf16`` /
+        ``emu_llama_sample_step_trie``; ``do_sample=False`` = constrained greedy); a callable always keeps the host loop."""
+        trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
+        if device_sampler and allow_fn is not None and trie is None:
+            device_sampler = False                              # a Python callable cannot run inside a captured step
         if device_sampler:
             if int(no_repeat_ngram_size or 0) > 0:
                 raise ValueError("device_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
@@ -800,14 +809,15 @@ class LlamaEngine:
         row = hidden[:, -1, :]
         if device_sampler:
             return self._sample_device(row, B, S, kstart, pos, max_new_tokens, min_len, do_sample, temperature, top_k, top_p,
-                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms)
+                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms, trie)
         out = torch.full((B, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
         unfinished = torch.ones(B, dtype=torch.int64, device=dev)
         hid = torch.empty(B, H, device=dev, dtype=BF16)
         n = 0
         for step in range(max_new_tokens):
             scores = process_logits(self.logits(row).float(), out[:, :step], step < min_len, eos_id, do_sample, temperature,
-                                    top_k, top_p, repetition_penalty, no_repeat_ngram_size=int(no_repeat_ngram_size or 0))
+                                    top_k, top_p, repetition_penalty, no_repeat_ngram_size=int(no_repeat_ngram_size or 0),
+                                    allowed=None if allow_fn is None else allowed_mask(allow_fn, out[:, :step], 1, self.vocab))
             if do_sample:
                 nxt = torch.multinomial(torch.softmax(scores, dim=-1), num_samples=1).squeeze(1)
             else:
@@ -830,8 +840,9 @@ class LlamaEngine:
 
     def _sample_device(self, row: torch.Tensor, B: int, S: int, kstart: torch.Tensor, next_pos: torch.Tensor, max_new: int,
                        min_len: int, do_sample: bool, temperature, top_k, top_p, repetition_penalty: float, eos_id: int,
-                       pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor]) -> torch.Tensor:
-        """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill."""
+                       pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor], trie: Optional[TokenTrie] = None) -> torch.Tensor:
+        """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill.  ``trie``: the selection is
+        ``emu_sample_trie_bf16``, every row starting at the root."""
         dev = self.device
         if do_sample:
             uni = torch.rand(max_new, B, dtype=torch.float32, device=dev) if uniforms is None else \
@@ -840,7 +851,8 @@ class LlamaEngine:
             uni = None
         out_ids = torch.full((max_new, B), pad_id, device=dev, dtype=torch.int32)
         st = SampleState(self, B, next_pos, S, kstart, out_ids, uni,
-                         sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id))
+                         sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id),
+                         None if trie is None else trie.tables(dev))
         self.logits(row, out=st.logits)
         st.first()
         # the only host read: the rows' flags, every EOS_POLL steps (the launches in between stay queued ahead)
@@ -1193,7 +1205,7 @@ class LlamaEngine:
                              repetition_penalty: float = 1.0, hf_semantics: str = "4.31",
                              trace: Optional[dict] = None, no_repeat_ngram_size: int = 0,
                              num_return_sequences: int = 1, uniforms: Optional[torch.Tensor] = None,
-                             device_beam_sampler: bool = False) -> torch.Tensor:
+                             device_beam_sampler: bool = False, constraint=None) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=N, do_sample=False, early_stopping=False)`` -- the reference's
         DEFAULT decoding mode (num_beams=5, length_penalty=-1, Emu2/emu/emu.py:163-172,213-229).  Restates
         transformers' vectorised beam search: per step keep the 2N best continuations over beams x vocab, the N best
@@ -1249,7 +1261,22 @@ class LlamaEngine:
         ``trace`` (a dict, diagnostics for the tests): receives ``margin`` = the smallest gap seen between the N-th and the
         (N+1)-th running candidate at a pruning step and between the two best final results, and, with a table of uniforms,
         ``draw_margin`` = the smallest distance seen of a draw's ``u * R`` from a boundary between two entries
-        (``sampling.beam_draw_margin``)."""
+        (``sampling.beam_draw_margin``).
+
+        ``constraint`` (``emu_amd.constrain.TokenTrie`` or a callable (batch_id, ids generated so far) -> allowed ids, the library's
+        ``prefix_allowed_tokens_fn``; Emu1/mm_eval/models/emu.py:96-109 runs it with 5 beams): the per-beam log-probabilities of every
+        id that is not allowed become -inf after the processors and ahead of the warpers (the log-softmax is over the whole row).
+        Fewer than 2N candidates may then be finite, so every selection goes by the device kernels' rule -- ties, those among -inf
+        included, to the lower index (stable top-k) -- and the ``trace`` margins leave out exact ties and non-finite gaps (-inf minus
+        -inf).  A trie in the deterministic, unpenalised mode runs on the device (``emu_beam_step_trie_bf16``) within the kernel's
+        bounds, like the unconstrained search.  The host loop takes over for a callable, and for a trie together with sampling, a
+        repetition penalty, an n-gram ban or a ``trace``; ``device_beam_sampler`` is then ignored with one warning per process."""
+        trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
+        if allow_fn is not None and device_beam_sampler and (do_sample or repetition_penalty != 1.0):
+            warn_once(LlamaEngine, "_warned_beam_constraint",
+                      "emu_amd: device_beam_sampler: a constraint is not built into the device beam sampler "
+                      "(emu_beam_sample_step_bf16); staying on the host path")
+            device_beam_sampler = False
         if hf_semantics not in ("4.31", "5.x"):
             raise ValueError("hf_semantics must be '4.31' or '5.x'")
         if not 1 <= num_return_sequences <= num_beams:
@@ -1291,9 +1318,9 @@ class LlamaEngine:
         # The deterministic mode (the reference's default) runs each step's selection and bookkeeping in ONE kernel
         # (emu_beam_step_bf16); sampling, penalties, n-gram bans and the diagnostics keep the torch pipeline below.
         if (not do_sample and repetition_penalty == 1.0 and not ngram and trace is None and nb <= 8 and max_len <= 256
-                and V >= 2 * nb and hasattr(self, "handle") and logits.dtype == BF16):
+                and V >= 2 * nb and hasattr(self, "handle") and logits.dtype == BF16 and (allow_fn is None or trie is not None)):
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
-                                            int(num_return_sequences), hf_semantics == "4.31")
+                                            int(num_return_sequences), hf_semantics == "4.31", trie=trie)
         if device_beam_sampler:
             if not hasattr(self, "handle") or logits.dtype != BF16:
                 raise RuntimeError("device_beam_sampler needs the HIP engine and its bf16 logits")
@@ -1323,16 +1350,22 @@ class LlamaEngine:
         table = uniforms is not None and do_sample
         # with a table the result has to be a function of the table alone, so ties between candidates (the rule, not the exception:
         # at step 0 every beam holds the same hypothesis) go to the first in candidate order, the device kernels' rule
-        topk = torch.topk if not table else \
+        # ... and so does a constraint: it leaves fewer than 2N finite candidates, and which -inf entry a dead beam is fed must not
+        # be left to torch.topk
+        stable = table or allow_fn is not None
+        topk = torch.topk if not stable else \
             (lambda t, k: tuple(r[:, :k] for r in torch.sort(t, dim=1, descending=True, stable=True)))
-        # (such exact ties are decided alike on both sides and do not count as a margin)
-        gap = (lambda d: float(d.min())) if not table else (lambda d: float(d.masked_fill(d == 0, float("inf")).min()))
+        # (such exact ties are decided alike on both sides and do not count as a margin; nor does -inf minus -inf)
+        gap = (lambda d: float(d.min())) if not stable else \
+            (lambda d: float(d.masked_fill((d == 0) | ~torch.isfinite(d), float("inf")).min()))
         while True:
             log_probs = torch.log_softmax(lp_rows, dim=-1)
-            if do_sample or repetition_penalty != 1.0 or ngram:
-                log_probs = process_logits(log_probs.reshape(B * nb, V), running_seq[:, :, :cur].reshape(B * nb, cur), cur < min_len,
+            if do_sample or repetition_penalty != 1.0 or ngram or allow_fn is not None:
+                gen = running_seq[:, :, :cur].reshape(B * nb, cur)
+                log_probs = process_logits(log_probs.reshape(B * nb, V), gen, cur < min_len,
                                            eos_id, do_sample and not old, temperature, top_k, top_p, repetition_penalty,
-                                           min_keep=2, no_repeat_ngram_size=ngram).view(B, nb, V)
+                                           min_keep=2, no_repeat_ngram_size=ngram,
+                                           allowed=None if allow_fn is None else allowed_mask(allow_fn, gen, nb, V)).view(B, nb, V)
             elif cur < min_len:
                 log_probs = log_probs.clone()
                 log_probs[..., eos_id] = -float("inf")
@@ -1353,7 +1386,7 @@ class LlamaEngine:
                     top_lp, order = torch.sort(top_lp, descending=True, dim=1, stable=table)
                     top_idx = torch.gather(top_idx, 1, order)
             else:
-                top_lp, top_idx = torch.topk(acc, k=2 * nb)
+                top_lp, top_idx = topk(acc, k=2 * nb)
             src_beam = top_idx // V
             tok = top_idx % V
             cand_seq = gather(running_seq, src_beam)
@@ -1432,10 +1465,12 @@ class LlamaEngine:
 
     BEAM_POLL = 4          # graph-replayed beam steps between two looks at the done flags
     _warned_beam_sampler = False           # one warning per process (beam_search_generate(device_beam_sampler=True))
+    _warned_beam_constraint = False        # ... and for a constraint that makes it ignore that flag
 
     def _beam_search_device(self, logits0: torch.Tensor, B: int, S: int, nb: int, max_len: int, min_len: int,
                             length_penalty: float, eos_id: int, pad_id: int, kstart_b: torch.Tensor, pos: torch.Tensor,
-                            nret: int, v431: bool = True, sampler: Optional[tuple] = None) -> torch.Tensor:
+                            nret: int, v431: bool = True, sampler: Optional[tuple] = None,
+                            trie: Optional[TokenTrie] = None) -> torch.Tensor:
         """The loop of ``beam_search_generate`` for the deterministic mode, with nothing left on the host but the replay of a
         hipGraph: per step {``emu_beam_advance`` (slot / position of the token to feed from the device-side step counter) ->
         ``emu_llama_beam_reorder_kv`` (the generated KV slots follow the beam permutation) -> embedding gather -> the decoder
@@ -1450,14 +1485,19 @@ class LlamaEngine:
         ``sampler`` = (options, table of uniforms or None) (``beam_search_generate(device_beam_sampler=True)``): the same loop with
         ``emu_beam_sample_step_bf16`` (csrc/beam_sample.hip: beam-search sampling, penalised beam search) as its step.  The table
         is copied into a buffer the captured graph owns, so a call with another table replays the same graph; under the "4.31"
-        order with sampling all N running scores start at 0, as on the host."""
+        order with sampling all N running scores start at 0, as on the host.
+
+        ``trie`` (deterministic mode only): the same loop with ``emu_beam_step_trie_bf16`` as its step.  The beams' nodes live in the
+        state and start at the root; the state keeps the trie's tables alive, and their addresses are part of the key, so a call
+        with another trie captures anew."""
         dev, V, rows = self.device, self.vocab, B * nb
+        tables = None if trie is None else trie.tables(dev)
         L = lib()
         params = sampler[0] if sampler is not None else None
         sampling = params is not None and bool(params.do_sample)
         opts = None if params is None else (sampling, params.repetition_penalty, params.temperature, params.top_k, params.top_p)
         key = (B, nb, S, self.s_max, max_len, int(min_len), float(length_penalty), int(eos_id), bool(v431), self.kcache.data_ptr(),
-               self.mode_epoch, opts)
+               self.mode_epoch, opts, None if tables is None else tuple((t.data_ptr(), t.numel()) for t in tables))
 
         def build():
             i32 = dict(dtype=torch.int32, device=dev)
@@ -1473,6 +1513,8 @@ class LlamaEngine:
                                      dtype=torch.uint8, device=dev))
             if sampling:
                 st["uni"] = torch.empty(max_len, B, 2 * nb, dtype=torch.float32, device=dev)
+            if tables is not None:
+                st.update(tables=tables, trie=ops.trie_tables(tables), node=torch.empty(rows, **i32))
             return st
 
         st = self._loop_state("beam", key, rows, build)
@@ -1485,6 +1527,8 @@ class LlamaEngine:
             st["uni"].copy_(torch.rand(max_len, B, 2 * nb, dtype=torch.float32, device=dev) if table is None else table)
         st["beam_scores"].fill_(-1.0e9); st["finished"].zero_(); st["seq_len"].zero_(); st["still_open"].fill_(1)
         st["pos0"].copy_(pos); st["kstart"].copy_(kstart_b)
+        if tables is not None:
+            st["node"].zero_()                             # every beam starts at the root
         stream = lambda: ops.stream(self.device)           # (inside a capture the current stream is the capturing one)
 
         def beam_step(lg, ld_prompt, ld_beam, cur, cur_dev):
@@ -1493,7 +1537,10 @@ class LlamaEngine:
                      st["running_scores"].data_ptr(), st["beam_scores"].data_ptr(), st["finished"].data_ptr(),
                      st["seq_len"].data_ptr(), st["still_open"].data_ptr(), st["next_tok"].data_ptr(),
                      st["beam_flat"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel())
-            if params is None:
+            if tables is not None:
+                check(L.emu_beam_step_trie_bf16(*state, C.byref(st["trie"]), st["node"].data_ptr(), stream()),
+                      "emu_beam_step_trie_bf16", self.ctx.handle)
+            elif params is None:
                 check(L.emu_beam_step_bf16(*state, stream()), "emu_beam_step_bf16", self.ctx.handle)
             else:
                 check(L.emu_beam_sample_step_bf16(*state, params, int(sampling and v431), st["uni"].data_ptr() if sampling else None,
@@ -1532,12 +1579,14 @@ class LlamaEngine:
 
 def process_logits(scores: torch.Tensor, generated: torch.Tensor, suppress_eos: bool, eos_id: int, do_sample: bool,
                    temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                   repetition_penalty: float = 1.0, min_keep: int = 1, no_repeat_ngram_size: int = 0) -> torch.Tensor:
+                   repetition_penalty: float = 1.0, min_keep: int = 1, no_repeat_ngram_size: int = 0,
+                   allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """transformers' logits pipeline for ``generate(inputs_embeds=...)`` in its order: RepetitionPenaltyLogitsProcessor over
     the ids generated so far (with inputs_embeds the prompt contributes no ids), MinLengthLogitsProcessor (EOS -> -inf),
+    PrefixConstrainedLogitsProcessor (``allowed`` bool [B, V]: everything else -> -inf; None = no constraint),
     then -- only when sampling -- TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper.  ``scores`` [B, V] fp32,
     ``generated`` [B, n] int64.  ``min_keep`` is the warpers' min_tokens_to_keep (2 under beam search: one EOS id + 1).
-    Pure torch: pinned against the library's own processors in tests/test_host_logic.py."""
+    Pure torch: pinned against the library's own processors in tests/test_host_logic.py and tests/test_constrain_host.py."""
     if repetition_penalty != 1.0 and generated.shape[1] > 0:
         g = torch.gather(scores, 1, generated)
         g = torch.where(g < 0, g * repetition_penalty, g / repetition_penalty)
@@ -1547,9 +1596,46 @@ def process_logits(scores: torch.Tensor, generated: torch.Tensor, suppress_eos: 
     if suppress_eos:
         scores = scores.clone()
         scores[:, eos_id] = -float("inf")
+    if allowed is not None:
+        scores = scores.masked_fill(~allowed, -float("inf"))
     if do_sample:
         scores = warp_logits(scores, temperature, top_k, top_p, min_keep)
     return scores
+
+
+def resolve_constraint(constraint, vocab: int, eos_id: int, min_len: int, num_return_sequences: int = 1):
+    """``constraint`` of the generate loops -> (trie or None, callable or None).  A ``TokenTrie`` is checked against the call (a
+    ValueError before any device work) and may run on the device; a callable with the library's ``prefix_allowed_tokens_fn``
+    signature (batch_id, ids generated so far) -> list always keeps the host loop."""
+    if constraint is None:
+        return None, None
+    if isinstance(constraint, TokenTrie):
+        if constraint.vocab != int(vocab) or constraint.eos_id != int(eos_id):
+            raise ValueError(f"constraint: the trie was built for vocabulary {constraint.vocab} and EOS {constraint.eos_id}, the call "
+                             f"has vocabulary {vocab} and EOS {eos_id}")
+        if int(min_len) > constraint.min_depth:
+            raise ValueError(f"constraint: min_len {min_len} is above the trie's shortest sequence ({constraint.min_depth} tokens "
+                             "ahead of its EOS): with EOS suppressed nothing would be allowed there")
+        if int(num_return_sequences) > constraint.count:
+            raise ValueError(f"constraint: num_return_sequences {num_return_sequences} is above the trie's {constraint.count} sequences")
+        return constraint, constraint.as_callable()
+    if callable(constraint):
+        return None, constraint
+    raise TypeError("constraint must be an emu_amd.constrain.TokenTrie or a callable (batch_id, ids) -> list of allowed ids")
+
+
+def allowed_mask(fn, generated: torch.Tensor, rows_per_prompt: int, vocab: int) -> torch.Tensor:
+    """[rows, vocab] bool from ``fn(batch_id, ids)`` over the rows of ``generated`` [rows, n] (the ids generated so far; batch_id =
+    row // rows_per_prompt, as the library's PrefixConstrainedLogitsProcessor numbers the beams of a prompt).  An empty answer is
+    the library's ValueError."""
+    mask = torch.zeros(generated.shape[0], vocab, dtype=torch.bool)
+    for r, ids in enumerate(generated.cpu()):
+        ok = fn(r // rows_per_prompt, ids)
+        if len(ok) == 0:
+            raise ValueError(f"`prefix_allowed_tokens_fn` returned an empty list for batch ID {r // rows_per_prompt}. This means that "
+                             "the constraint is unsatisfiable. Please check your implementation of `prefix_allowed_tokens_fn`")
+        mask[r, torch.as_tensor(list(ok), dtype=torch.int64)] = True
+    return mask.to(generated.device)
 
 
 def ban_repeated_ngrams(scores: torch.Tensor, generated: torch.Tensor, n: int) -> torch.Tensor:
@@ -1669,8 +1755,13 @@ class SampleState(GreedyState):
     ``step_graph`` is GreedyState's: the min-length suppress and the history length, too, come from the device-side step index."""
 
     def __init__(self, eng: "LlamaEngine", B: int, next_pos: torch.Tensor, S: int, kstart: torch.Tensor, out_ids: torch.Tensor,
-                 uniforms: Optional[torch.Tensor], params: SampleParamsC):
+                 uniforms: Optional[torch.Tensor], params: SampleParamsC, trie_tables: Optional[tuple] = None):
         super().__init__(eng, B, torch.zeros(B, device=eng.device, dtype=torch.int32), next_pos, S, kstart, out_ids)
+        # constraint: the tables (kept alive here for as long as a captured graph holds their addresses), their C view, and the rows'
+        # nodes, every row at the root
+        self.trie_tables = trie_tables
+        self.trie = None if trie_tables is None else ops.trie_tables(trie_tables)
+        self.node = None if trie_tables is None else torch.zeros(B, device=eng.device, dtype=torch.int32)
         self.step_idx.zero_()                              # no token yet: first() draws it
         self.unfinished = torch.ones(B, device=eng.device, dtype=torch.int32)
         self.uniforms, self.params = uniforms, params
@@ -1679,19 +1770,21 @@ class SampleState(GreedyState):
     def first(self) -> None:
         """The first token, from ``self.logits`` (the prefill's last rows): step 0 of the table."""
         ops.sample(self.logits, self.step_idx, self.params, self.cur, hist=self.out_ids, uniforms=self.uniforms,
-                   unfinished=self.unfinished)
+                   unfinished=self.unfinished, trie=self.trie, node=self.node)
         self.out_ids[0] = self.cur
         self.step_idx.fill_(1)
 
     def step(self) -> None:
         e = self.eng
-        check(lib().emu_llama_sample_step(e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(),
-                                          self.kstart.data_ptr(), self.ctx.data_ptr(), self.step_idx.data_ptr(),
-                                          self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
-                                          self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(),
-                                          ops._p(self.uniforms), self.unfinished.data_ptr(), C.byref(self.params),
-                                          ops.stream(e.device)),
-              "emu_llama_sample_step", e.ctx.handle)
+        args = (e.handle, self.B, self.cur.data_ptr(), self.pos.data_ptr(), self.slot.data_ptr(), self.kstart.data_ptr(),
+                self.ctx.data_ptr(), self.step_idx.data_ptr(), self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
+                self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(), ops._p(self.uniforms),
+                self.unfinished.data_ptr(), C.byref(self.params))
+        if self.trie is None:
+            check(lib().emu_llama_sample_step(*args, ops.stream(e.device)), "emu_llama_sample_step", e.ctx.handle)
+        else:
+            check(lib().emu_llama_sample_step_trie(*args, C.byref(self.trie), self.node.data_ptr(), ops.stream(e.device)),
+                  "emu_llama_sample_step_trie", e.ctx.handle)
 
 
 class ScoreState(GreedyState):

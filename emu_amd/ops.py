@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import mxfp4
-from ._lib import check, lib
+from ._lib import TokenTrieC, check, lib
 
 EPI_NONE, EPI_RESID, EPI_SWIGLU, EPI_SILU, EPI_GELU, EPI_GEGLU = range(6)
 BF16 = torch.bfloat16
@@ -301,27 +301,44 @@ def argmax(logits, vocab: Optional[int] = None, suppress_id: int = -1, out=None)
     return out
 
 
+def trie_tables(tables):
+    """``_lib.TokenTrieC`` (include/emu_hip.h: emu_token_trie) over ``tables`` = (first, tok, child), int32 on the device
+    (``emu_amd.constrain.TokenTrie.tables``).  The struct holds addresses only: the caller keeps ``tables`` alive."""
+    first, tok, child = tables
+    for name, t in (("first", first), ("tok", tok), ("child", child)):
+        _req(t, name, torch.int32)
+    if first.numel() < 2 or tok.numel() != child.numel():
+        raise ValueError("trie tables: first [nodes + 1], tok [edges], child [edges]")
+    return TokenTrieC(_p(first), _p(tok), _p(child), first.numel() - 1, tok.numel())
+
+
 def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist=None, uniforms=None, unfinished=None,
-           probs_out=None):
+           probs_out=None, trie=None, node=None):
     """``emu_sample_bf16`` (include/emu_hip.h; specified in emu_amd/sampling.py): one token per row of bf16 ``logits`` [rows, >= vocab]
     under ``params`` (``_lib.SampleParamsC``).  ``step_dev`` int32 [1] on the device = the step index the kernel reads: the number of
     history rows of ``hist`` int32 [steps, rows] in use, the row of ``uniforms`` fp32 [steps, rows], the min-length comparison.
-    ``unfinished`` int32 [rows] and ``probs_out`` fp32 [rows, >= vocab] are optional.  Returns ``out`` int32 [rows]."""
+    ``unfinished`` int32 [rows] and ``probs_out`` fp32 [rows, >= vocab] are optional.  ``trie`` (``trie_tables``) with ``node``
+    int32 [rows], in/out: ``emu_sample_trie_bf16``, the selection under a constraint.  Returns ``out`` int32 [rows]."""
     _req(logits, "logits")
     rows = logits.shape[0]
     vocab = logits.shape[1] if vocab is None else vocab
     if out is None:
         out = torch.empty(rows, device=logits.device, dtype=torch.int32)
     for name, t, dt in (("step_dev", step_dev, torch.int32), ("hist", hist, torch.int32), ("uniforms", uniforms, torch.float32),
-                        ("unfinished", unfinished, torch.int32), ("probs_out", probs_out, torch.float32), ("out", out, torch.int32)):
+                        ("unfinished", unfinished, torch.int32), ("probs_out", probs_out, torch.float32), ("out", out, torch.int32),
+                        ("node", node, torch.int32)):
         if t is not None:
             _req(t, name, dt)
-    check(lib().emu_sample_bf16(_p(logits), logits.stride(0), rows, vocab, _p(hist), hist.stride(0) if hist is not None else 0,
-                                hist.shape[0] if hist is not None else 0, _p(step_dev), _p(uniforms),
-                                uniforms.stride(0) if uniforms is not None else 0, uniforms.shape[0] if uniforms is not None else 0,
-                                C.byref(params), _p(unfinished), _p(out), _p(probs_out),
-                                probs_out.stride(0) if probs_out is not None else 0, stream(logits)),
-          "emu_sample_bf16")
+    args = (_p(logits), logits.stride(0), rows, vocab, _p(hist), hist.stride(0) if hist is not None else 0,
+            hist.shape[0] if hist is not None else 0, _p(step_dev), _p(uniforms),
+            uniforms.stride(0) if uniforms is not None else 0, uniforms.shape[0] if uniforms is not None else 0,
+            C.byref(params), _p(unfinished), _p(out), _p(probs_out), probs_out.stride(0) if probs_out is not None else 0)
+    if trie is None and node is None:
+        check(lib().emu_sample_bf16(*args, stream(logits)), "emu_sample_bf16")
+    else:
+        if trie is None or node is None or node.numel() < rows:
+            raise ValueError("a constrained selection needs the trie's tables and a node per row")
+        check(lib().emu_sample_trie_bf16(*args, C.byref(trie), _p(node), stream(logits)), "emu_sample_trie_bf16")
     return out
 
 

@@ -9,6 +9,8 @@ The order is transformers' order:
 2. Repetition penalty: for every DISTINCT history id in [0, vocab): ``s = s * pen if s < 0 else s / pen`` (IEEE fp32 multiply and
    divide), once per id however often it occurs; ids outside [0, vocab) are ignored.
 3. Minimum-length suppress: ``s[suppress_id] = -inf`` (``suppress_id`` None or < 0: not applied).
+3a. Constraint (``allowed`` bool [rows, vocab], None = none; the place of the library's PrefixConstrainedLogitsProcessor):
+   ``s[~allowed] = -inf``, so everything below -- the arg-max, the thresholds, the softmax -- runs over the allowed ids.
 4. ``do_sample`` false ends here: the token is the first index of the maximum (``argmax_kernel``'s rule).
 5. Temperature: ``s = s / temperature`` (IEEE fp32 division), skipped for None or 1.
 6. Top-k: with k' = min(max(top_k, min_keep), vocab), drop ``s < (k'-th largest value)``; ties with that value stay.
@@ -43,8 +45,8 @@ def _history_rows(history: History, B: int):
 
 
 def reference_scores(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
-                     suppress_id: Optional[int] = None) -> torch.Tensor:
-    """Steps 1-3: [B, vocab] fp32 scores of bf16 (or fp32-held bf16) logit rows."""
+                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Steps 1-3a: [B, vocab] fp32 scores of bf16 (or fp32-held bf16) logit rows."""
     s = logits.float().clone()
     B, V = s.shape
     if repetition_penalty != 1.0:
@@ -57,23 +59,25 @@ def reference_scores(logits: torch.Tensor, history: History = None, repetition_p
                 s[b, idx] = torch.where(g < 0, g * pen.to(s.device), g / pen.to(s.device))
     if suppress_id is not None and 0 <= suppress_id < V:
         s[:, suppress_id] = -float("inf")
+    if allowed is not None:
+        s = s.masked_fill(~allowed.to(device=s.device, dtype=torch.bool), -float("inf"))
     return s
 
 
 def reference_greedy(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
-                     suppress_id: Optional[int] = None) -> torch.Tensor:
+                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Step 4: first index of the maximum of the penalised, suppressed scores, [B] int64."""
-    s = reference_scores(logits, history, repetition_penalty, suppress_id)
+    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed)
     first = (s == s.max(dim=-1, keepdim=True)[0]).float().argmax(dim=-1)       # argmax of a 0/1 row: the first 1
     return first
 
 
 def reference_warped(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
                      suppress_id: Optional[int] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
-                     top_p: Optional[float] = None, min_keep: int = 1, dtype: torch.dtype = torch.float32
-                     ) -> Tuple[torch.Tensor, torch.Tensor]:
+                     top_p: Optional[float] = None, min_keep: int = 1, dtype: torch.dtype = torch.float32,
+                     allowed: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Steps 1-7: (scores [B, vocab] fp32 after temperature, kept [B, vocab] bool)."""
-    s = reference_scores(logits, history, repetition_penalty, suppress_id)
+    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed)
     B, V = s.shape
     if temperature is not None and temperature != 1.0:
         s = s / torch.tensor(float(temperature), dtype=torch.float32, device=s.device)
@@ -105,13 +109,13 @@ def reference_warped(logits: torch.Tensor, history: History = None, repetition_p
 def reference_probs(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
                     suppress_id: Optional[int] = None, do_sample: bool = True, temperature: Optional[float] = None,
                     top_k: Optional[int] = None, top_p: Optional[float] = None, min_keep: int = 1,
-                    dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                    dtype: torch.dtype = torch.float32, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[B, vocab] probabilities the draw is made from (``dtype``), exactly 0 for removed tokens.  ``do_sample`` false: the one-hot
     row of the greedy token."""
     if not do_sample:
-        g = reference_greedy(logits, history, repetition_penalty, suppress_id)
+        g = reference_greedy(logits, history, repetition_penalty, suppress_id, allowed)
         return torch.zeros(logits.shape, dtype=dtype, device=logits.device).scatter_(1, g[:, None], 1.0)
-    s, kept = reference_warped(logits, history, repetition_penalty, suppress_id, temperature, top_k, top_p, min_keep, dtype)
+    s, kept = reference_warped(logits, history, repetition_penalty, suppress_id, temperature, top_k, top_p, min_keep, dtype, allowed)
     q = torch.softmax(s.masked_fill(~kept, -float("inf")).to(dtype), dim=-1)
     return q.masked_fill(~kept, 0.0)
 
@@ -170,7 +174,8 @@ def top_p_threshold_group(logits: torch.Tensor, **opts) -> Tuple[torch.Tensor, t
 # 1. ``lp = x - (m + log sum exp(x - m))`` with ``x = float32(logit)`` and m the row maximum; the subtraction is fp32, the sum is taken
 #    in ``dtype``.
 # 2. The processors act on lp: the repetition penalty of step 2 above (``lp < 0`` multiplies, otherwise divides; once per distinct
-#    history id; ids outside the vocabulary are ignored), then ``lp[eos] = -inf`` while ``cur < min_len``.
+#    history id; ids outside the vocabulary are ignored), then ``lp[eos] = -inf`` while ``cur < min_len``, then the constraint:
+#    ``lp[~allowed] = -inf`` (the log-sum-exp of step 1 is over the whole, unmasked row, as for the EOS suppress).
 # 3. The warpers are steps 5-7 above with ``min_keep = 2``.  ``order="5.x"``: they act on lp, and ``acc = warped + rs_j``;
 #    ``order="4.31"``: they act on ``lp + rs_j`` and acc is that warped row; ``do_sample=False`` (penalised beam search): no warpers,
 #    ``acc = lp + rs_j``.  All these sums are fp32; removed entries are -inf.
@@ -196,34 +201,36 @@ def _check_order(order: str) -> bool:
     return order == "4.31"
 
 
-def _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype):
-    """Steps 1-2: the penalised, EOS-suppressed log-probabilities [R, vocab] fp32."""
+def _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed=None):
+    """Steps 1-2: the penalised, EOS-suppressed, constrained log-probabilities [R, vocab] fp32."""
     x = logits.float()
     m = x.max(dim=-1, keepdim=True)[0]
     lse = m + torch.log(torch.exp((x - m).to(dtype)).sum(dim=-1, keepdim=True)).float()
-    return reference_scores(x - lse, history, repetition_penalty, eos_id if suppress_eos else None)
+    return reference_scores(x - lse, history, repetition_penalty, eos_id if suppress_eos else None, allowed)
 
 
 def beam_reference_warp_input(logits: torch.Tensor, running_scores: torch.Tensor, history: History = None,
                               repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
-                              order: str = "5.x", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                              order: str = "5.x", dtype: torch.dtype = torch.float32,
+                              allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The fp32 rows [R, vocab] the warpers act on (ahead of the temperature): steps 1-2, under ``order="4.31"`` with the running
     score added."""
-    lp = _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype)
+    lp = _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed)
     return lp + running_scores.reshape(-1, 1).float().to(lp.device) if _check_order(order) else lp
 
 
 def beam_reference_rows(logits: torch.Tensor, running_scores: torch.Tensor, history: History = None,
                         repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
                         do_sample: bool = True, temperature: Optional[float] = None, top_k: Optional[int] = None,
-                        top_p: Optional[float] = None, order: str = "5.x", dtype: torch.dtype = torch.float32) -> torch.Tensor:
+                        top_p: Optional[float] = None, order: str = "5.x", dtype: torch.dtype = torch.float32,
+                        allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Steps 1-3: acc [R, vocab] fp32 of R beam rows (bf16 or fp32-held bf16 logits [R, vocab], running scores [R] or [B, nb], one
     history per row), -inf for removed entries."""
     accumulated = _check_order(order)
     rs = running_scores.reshape(-1, 1).float().to(logits.device)
     if not do_sample:
-        return _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype) + rs
-    w = beam_reference_warp_input(logits, running_scores, history, repetition_penalty, eos_id, suppress_eos, order, dtype)
+        return _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed) + rs
+    w = beam_reference_warp_input(logits, running_scores, history, repetition_penalty, eos_id, suppress_eos, order, dtype, allowed)
     s, kept = reference_warped(w, None, 1.0, None, temperature, top_k, top_p, BEAM_MIN_KEEP, dtype)
     return (s if accumulated else s + rs).masked_fill(~kept, -float("inf"))
 
@@ -353,3 +360,22 @@ def contrastive_reference_select(ctx: torch.Tensor, ctx_valid: torch.Tensor, can
     score = (1.0 - alpha) * p.to(dtype) - alpha * pen
     first = (score == score.max(dim=-1, keepdim=True)[0]).float().argmax(dim=-1)    # argmax of a 0/1 row: the first 1
     return pen, first
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Constrained decoding (emu_amd/constrain.py: ``TokenTrie``; ``emu_sample_trie_bf16``, ``emu_beam_step_trie_bf16``).  The kernels keep
+# one trie node per row on the device and advance it by the id they select; what that state must equal is the stateless walk of the
+# row's generated ids through the trie, and what the mask must equal is the trie's answer for those ids.
+
+def constraint_allowed(trie, history: History) -> torch.Tensor:
+    """[rows, vocab] bool: the ids that may follow each row's generated ids (``history`` [rows, n] or a list of rows)."""
+    rows = _history_rows(history, len(history))
+    mask = torch.zeros(len(rows), trie.vocab, dtype=torch.bool)
+    for r, ids in enumerate(rows):
+        mask[r, torch.tensor(trie.allowed(ids), dtype=torch.int64)] = True
+    return mask
+
+
+def trie_nodes(trie, history: History) -> torch.Tensor:
+    """[rows] int32: the trie node of each row after its generated ids; -1 = off the trie or past its EOS."""
+    return torch.tensor([trie.walk(ids) for ids in _history_rows(history, len(history))], dtype=torch.int32)

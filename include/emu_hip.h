@@ -365,6 +365,30 @@ typedef struct emu_sample_params {
 int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                     const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
                     int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, emu_stream_t s);
+/* Constrained decoding: a token trie over a closed set of answers, as flat tables on the device (emu_amd/constrain.py builds them).
+ * The reference forwards **kwargs from generate to lm.generate (Emu2/emu/emu.py:175,228, Emu1/models/modeling_emu.py:116,178), and its
+ * evaluation model uses that for trie-constrained generation: a Trie over the ids of "yes." / "no." + EOS handed over as
+ * prefix_allowed_tokens_fn with 5 beams (Emu1/mm_eval/models/emu.py:96-109, Emu1/mm_eval/models/trie.py:16-79).  A Python callable
+ * cannot run inside a captured step; the tables can be read by the selection kernels.
+ * Node 0 is the root.  The edges of node n are tok[first[n] .. first[n + 1]) (ids ascending) and lead to child[...]; child -1 =
+ * "exhausted or off the trie" (an EOS edge leads there).  A row's state is one int32 node: at node n the ids tok[...] are allowed; at
+ * a node outside [0, nodes) (or one without edges) only eos_id is.  Masked ids are -inf.  After a selection the row moves to
+ * child(node, chosen id), -1 if that id is no edge.  The kernels clamp what they read from `first` to [0, edges] and take a node
+ * outside [-1, nodes) as exhausted, so no table value leads to a read out of bounds. */
+typedef struct emu_token_trie {
+    const int32_t *first, *tok, *child; /* device: int32 [nodes + 1], [edges], [edges] */
+    int nodes, edges;
+} emu_token_trie;
+/* emu_sample_bf16 under a constraint: the mask is applied to the row after the min-length suppress (the place of the library's
+ * PrefixConstrainedLogitsProcessor: after the processors, ahead of the warpers), so the arg-max, the thresholds and the softmax run
+ * over the allowed ids; the exhausted node allows params->eos_id.  node: device int32 [rows], in/out: the row's node is advanced by
+ * the selected id in the same launch; a finished row (unfinished[row] == 0) emits pad_id and keeps its node.  With every id an edge
+ * of the row's node the outputs are emu_sample_bf16's bit for bit.
+ * -22, nothing launched: emu_sample_bf16's bounds, trie or node NULL, a table NULL, nodes < 1, edges < 0. */
+int emu_sample_trie_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                         const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
+                         int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, const emu_token_trie* trie, int32_t* node,
+                         emu_stream_t s);
 /* The log-probability of a FORCED token under each row of logits (the specification is emu_amd/scoring.py): what the reference's LM
  * loss is made of (Emu1/models/modeling_llama.py:110-116: CrossEntropyLoss over shifted logits / labels) and what its `predict` ranks
  * candidate answers by (Emu1/models/prediction_mixin.py:36-131).  Per row, in fp32: m = max x, lse = m + log(sum exp(x - m)),
@@ -636,6 +660,13 @@ int emu_llama_sample_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, i
                           int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
                           int32_t* unfinished, const emu_sample_params* params, emu_stream_t s);
+/* emu_llama_sample_step with emu_sample_trie_bf16 as its selection (constrained greedy / constrained sampling with one beam, the
+ * one-beam form of Emu1/mm_eval/models/emu.py:96-109): node int32 [B] is the rows' trie state, advanced on the device.  Capturable. */
+int emu_llama_sample_step_trie(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                               int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
+                               void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
+                               int32_t* unfinished, const emu_sample_params* params, const emu_token_trie* trie, int32_t* node,
+                               emu_stream_t s);
 /* emu_llama_greedy_step with the next token FORCED instead of chosen: one teacher-forced step of scoring a given continuation
  * (Emu1/models/prediction_mixin.py:36-131 ranks candidates by the LM loss of Emu1/models/modeling_llama.py:110-116; here the rows run
  * through the decode kernels, so the active weight stream -- bf16, e4m3, MXFP4 -- is the one that is scored).  With step = *step_dev:
@@ -670,6 +701,18 @@ int emu_beam_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, 
                        float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
                        unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
                        emu_stream_t s);
+/* emu_beam_step_bf16 under a constraint (lm.generate(num_beams=5, prefix_allowed_tokens_fn=...), Emu1/mm_eval/models/emu.py:96-109):
+ * the mask acts on the per-beam LOG-PROBABILITIES -- the log-sum-exp is taken over the whole, unmasked row, exactly as for the
+ * min-length suppress -- so fewer than 2N candidates may be finite; ties, those among -inf included, go to the lower flat index
+ * beam * V + id.  node: device int32 [B * nb], in/out (all 0 = the root at step 0): beam j of prompt b is masked by node[b * nb + j],
+ * and after the bookkeeping the new beam j takes child(node[beam it continues], next_tok[j]): the state follows beam_flat.  With
+ * every id an edge of every beam's node the outputs are emu_beam_step_bf16's bit for bit.  A step with cur >= L changes nothing.
+ * -22, nothing launched: emu_beam_step_bf16's bounds, trie or node NULL, a table NULL, nodes < 1, edges < 0. */
+int emu_beam_step_trie_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int B, int nb, int L, int cur, const int32_t* cur_dev,
+                            int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                            float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                            unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                            const emu_token_trie* trie, int32_t* node, emu_stream_t s);
 
 /* One step of the library's beam-search multinomial sampling (lm.generate(num_beams=N, do_sample=True, temperature, top_k, top_p,
  * repetition_penalty): the call of the demo backend, demo/backend/pytorch_model/backend.py:179-186) and of penalised beam search
