@@ -140,6 +140,7 @@ _PROTOS = {
     "emu_sample_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32, vp]),
     "emu_sample_trie_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32,
                                    C.POINTER(TokenTrieC), vp, vp]),
+    "emu_sample_ngram_bf16": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, i32, C.POINTER(SampleParamsC), vp, vp, vp, i32, i32, vp]),
     "emu_token_logprob_bf16": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp]),
     "emu_patchify": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "emu_image_resample_ws_bytes": (sz, [i32, i32, i32]),
@@ -176,9 +177,13 @@ _PROTOS = {
     "emu_beam_step_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "emu_beam_step_trie_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                       C.POINTER(TokenTrieC), vp, vp]),
+    "emu_beam_step_ngram_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                       i32, vp]),
     "emu_beam_step_workspace_bytes": (sz, [i32, i32, i32]),
     "emu_beam_sample_step_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                         C.POINTER(SampleParamsC), i32, vp, i32, vp, vp, lng, vp]),
+    "emu_beam_sample_step_ngram_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              sz, C.POINTER(SampleParamsC), i32, vp, i32, vp, vp, lng, i32, vp]),
     "emu_beam_sample_workspace_bytes": (sz, [i32, i32, i32]),
     "emu_llama_workspace_bytes": (sz, [vp, i32, i32]),
     "emu_llama_forward": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, sz, vp]),
@@ -189,6 +194,8 @@ _PROTOS = {
                                     C.POINTER(SampleParamsC), vp]),
     "emu_llama_sample_step_trie": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
                                          C.POINTER(SampleParamsC), C.POINTER(TokenTrieC), vp, vp]),
+    "emu_llama_sample_step_ngram": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp,
+                                          C.POINTER(SampleParamsC), i32, vp]),
     "emu_llama_score_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp]),
     "emu_vit_create": (i32, [vp, C.POINTER(VitCfgC), C.POINTER(vp)]),
     "emu_vit_destroy": (None, [vp]),

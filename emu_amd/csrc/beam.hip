@@ -3,8 +3,8 @@
 // The reference's default decoding mode is lm.generate(num_beams=5, length_penalty=-1, early_stopping=False)
 // (Emu2/emu/emu.py:163-172,213-229).  emu_amd/llama.py::beam_search_generate restates the library's vectorised search in ~70
 // small torch kernels per step; on a slow host their dispatch alone is 2-3 ms of a 13 ms step (bench leg beam_search_5: 13.2 ms
-// per step on one box, 15.8 on another with the same GPU time).  This kernel is that step for the deterministic mode (no sampling,
-// repetition penalty or n-gram ban -- those keep the torch pipeline), in two launches (the first one-workgroup version walked
+// per step on one box, 15.8 on another with the same GPU time).  This kernel is that step for the deterministic mode (no sampling
+// or repetition penalty -- those keep the torch pipeline or go to beam_sample.hip), in two launches (the first one-workgroup version walked
 // global memory in every arg-max round and took 485 us; a register-resident one spilled):
 //   1. per (1024-entry vocabulary chunk, beam, prompt): the chunk's softmax statistics and its 2N best logits;
 //   2. per prompt: the beams' log-sum-exp from the chunk statistics, the 2N best continuations over beams x vocabulary of
@@ -25,8 +25,12 @@
 // statistics from the unmasked values (the library masks the LOG-PROBABILITIES, after the softmax), then sets a 1024-bit map in LDS
 // from the node's edges that fall in the chunk and puts -inf over the rest before the 2N rounds, so a chunk may hand up -inf
 // candidates: they rank by index among themselves like every tie.  Kernel 2, after the bookkeeping, moves the nodes with the beams.
+// With a no-repeat n-gram ban (emu_beam_step_ngram_bf16; BeamStepArgs::ngram > 0; ngram.h) kernel 1 masks in the same place and the
+// same way: the threads share the start positions of the beam's ids running_seq[b, j, :cur], a match whose banned id falls in the
+// chunk sets its bit in the LDS map, and the owning lanes put -inf over the marked ids.  The ids follow the beams already.
 #include "beam_common.h"
 #include "trie.h"
+#include "ngram.h"
 
 namespace {
 
@@ -59,7 +63,7 @@ __device__ __forceinline__ void block_argmax(float& v, int& i, float* red_v, int
 __global__ __launch_bounds__(NT) void beam_chunk_kernel(const BeamStepArgs a, float* part, int nchunk) {
     __shared__ float red_v[NW];
     __shared__ int red_i[NW];
-    __shared__ unsigned int allow[CHUNK / 32];         // constraint: the chunk's allowed ids
+    __shared__ unsigned int allow[CHUNK / 32];         // constraint: the chunk's allowed ids; n-gram ban: its banned ids
     const int c = blockIdx.x, j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cur = a.cur_dev ? *a.cur_dev : a.cur;
     if (cur >= a.L) return;                            // graph replays beyond the length limit are no-ops
@@ -110,6 +114,22 @@ __global__ __launch_bounds__(NT) void beam_chunk_kernel(const BeamStepArgs a, fl
         for (int e = 0; e < 4; ++e) {
             const int id = tid + NT * e;
             if (!((allow[id >> 5] >> (id & 31)) & 1u)) x[e] = -INFINITY;
+        }
+    }
+    if (a.ngram > 0 && cur + 1 >= a.ngram) {           // the n-gram ban (a mask on the log-probabilities like the two above)
+        __syncthreads();                               // (a constraint's map, were both ever set, is read by now)
+        if (tid < CHUNK / 32) allow[tid] = 0u;
+        __syncthreads();
+        const int base = c * CHUNK;
+        ngram_matches(a.running_seq + ((size_t)b * a.nb + j) * a.L, 1, cur, a.ngram, tid, NT, [&](int id) {
+            id -= base;
+            if (id >= 0 && id < CHUNK) atomicOr(&allow[id >> 5], 1u << (id & 31));
+        });
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int id = tid + NT * e;
+            if ((allow[id >> 5] >> (id & 31)) & 1u) x[e] = -INFINITY;
         }
     }
     const int T = 2 * a.nb;
@@ -237,6 +257,7 @@ int launch_beam_step(const BeamStepArgs& a, float* ws, size_t ws_floats, hipStre
         a.min_len < 0 || !ws || ws_floats < beam_step_ws_floats(a.B, a.nb, a.V))
         return -22;
     if (a.node && !trie_args_ok(&a.trie, a.node)) return -22;
+    if (a.ngram < 0) return -22;
     const int nchunk = (a.V + CHUNK - 1) / CHUNK;
     hipLaunchKernelGGL(beam_chunk_kernel, dim3(nchunk, a.nb, a.B), dim3(NT), 0, s, a, ws, nchunk);
     hipLaunchKernelGGL(beam_step_kernel, dim3(a.B), dim3(NT), 0, s, a, ws, nchunk);

@@ -15,8 +15,11 @@
 //      instead.  The "4.31" order then sorts the draws by score (stable), and beam_common.h's bookkeeping runs as in beam.hip.
 // Both kernels read the step index from the device counter when one is given and return at once from the length limit on, so a
 // captured hipGraph replays the step for every token.
+// With a no-repeat n-gram ban (emu_beam_sample_step_ngram_bf16; BeamStepArgs::ngram > 0; ngram.h) kernel A writes -inf over the id
+// behind every earlier occurrence of the beam's last n - 1 ids, between the penalty and the EOS suppress, as sample.hip does.
 #include "beam_common.h"
 #include "sample_common.h"
+#include "ngram.h"
 
 namespace {
 
@@ -67,6 +70,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void beam_rows_kernel(const BeamSam
                 score[id] = s < 0.f ? s * a.penalty : s / a.penalty;
             }
         }
+        __syncthreads();
+    }
+    // 2a. no-repeat n-gram ban over the beam's own ids
+    if (st.ngram > 0) {
+        ngram_matches(st.running_seq + row * st.L, 1, cur, st.ngram, tid, SAMPLE_THREADS, [&](int id) {
+            if (id >= 0 && id < V) score[id] = -INFINITY;
+        });
         __syncthreads();
     }
     if (st.eos_id >= 0 && st.eos_id < V && cur < st.min_len) {
@@ -293,7 +303,7 @@ int launch_beam_sample_step(const BeamSampleArgs& a, float* ws, size_t ws_floats
     if (st.B < 1 || st.nb < 1 || st.nb > BEAM_MAXN || st.L < 1 || st.L > BEAM_MAXL || (!st.cur_dev && (st.cur < 0 || st.cur >= st.L)) ||
         st.V > EMU_SAMPLE_MAX_VOCAB || st.V < 2 * st.nb || st.min_len < 0 || !ws || ws_floats < beam_sample_ws_floats(st.B, st.nb, st.V))
         return -22;
-    if (!(a.penalty > 0.f) || (a.acc_out && a.ld_acc < st.V)) return -22;
+    if (!(a.penalty > 0.f) || (a.acc_out && a.ld_acc < st.V) || st.ngram < 0) return -22;
     if (a.do_sample && (!a.uniforms || a.uni_rows < 1 || !(a.temperature > 0.f) || !(a.top_p > 0.f) || a.min_keep < 2)) return -22;
     static bool attr_set = false;
     if (!attr_set) {

@@ -525,7 +525,14 @@ int emu_sample_bf16(const void* logits, int ld, int rows, int vocab, const int32
                     const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
                     int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, emu_stream_t s) {
     return launch_sample(B(logits), ld, rows, vocab, hist, hist_ld, hist_rows, step_dev, uniforms, uni_ld, uni_rows, params, unfinished,
-                         out, probs_out, ld_probs, nullptr, nullptr, S(s));
+                         out, probs_out, ld_probs, nullptr, nullptr, 0, S(s));
+}
+int emu_sample_ngram_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                          const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
+                          int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, int ngram, emu_stream_t s) {
+    if (ngram < 0) return -22;
+    return launch_sample(B(logits), ld, rows, vocab, hist, hist_ld, hist_rows, step_dev, uniforms, uni_ld, uni_rows, params, unfinished,
+                         out, probs_out, ld_probs, nullptr, nullptr, ngram, S(s));
 }
 int emu_sample_trie_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                          const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
@@ -533,7 +540,7 @@ int emu_sample_trie_bf16(const void* logits, int ld, int rows, int vocab, const 
                          emu_stream_t s) {
     if (!trie || !node) return -22;
     return launch_sample(B(logits), ld, rows, vocab, hist, hist_ld, hist_rows, step_dev, uniforms, uni_ld, uni_rows, params, unfinished,
-                         out, probs_out, ld_probs, trie, node, S(s));
+                         out, probs_out, ld_probs, trie, node, 0, S(s));
 }
 int emu_token_logprob_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* targets, int tgt_ld, const int32_t* step_dev,
                            const void* ref_logits, int ref_ld, float* lp, float* lse, int32_t* top1, float* kl, int32_t* agree,
@@ -1485,6 +1492,19 @@ int emu_beam_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, 
                    running_scores, beam_scores, finished, seq_len, heuristic_open, next_tok, beam_flat};
     return launch_beam_step(a, reinterpret_cast<float*>(workspace), ws_bytes / sizeof(float), S(s));
 }
+int emu_beam_step_ngram_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
+                             int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                             float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                             unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                             int ngram, emu_stream_t s) {
+    if (!logits || !running_seq || !sequences || !running_scores || !beam_scores || !finished || !seq_len || !heuristic_open ||
+        !next_tok || !beam_flat || ngram < 0)
+        return -22;
+    BeamStepArgs a{B(logits), ld_prompt, ld_beam, V, Bn, nb, L, cur, cur_dev, min_len, eos_id, length_penalty, hf431, running_seq, sequences,
+                   running_scores, beam_scores, finished, seq_len, heuristic_open, next_tok, beam_flat};
+    a.ngram = ngram;
+    return launch_beam_step(a, reinterpret_cast<float*>(workspace), ws_bytes / sizeof(float), S(s));
+}
 int emu_beam_step_trie_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
                             int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
                             float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
@@ -1499,18 +1519,19 @@ int emu_beam_step_trie_bf16(const void* logits, long ld_prompt, long ld_beam, in
 }
 
 size_t emu_beam_sample_workspace_bytes(int Bn, int nb, int V) { return beam_sample_ws_floats(Bn, nb, V) * sizeof(float); }
-int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
-                              int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
-                              float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
-                              unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
-                              const emu_sample_params* params, int warp_accumulated, const float* uniforms, int uni_rows,
-                              int32_t* draws_out, float* acc_out, long ld_acc, emu_stream_t s) {
+int emu_beam_sample_step_ngram_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur,
+                                    const int32_t* cur_dev, int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq,
+                                    int32_t* sequences, float* running_scores, float* beam_scores, unsigned char* finished,
+                                    int32_t* seq_len, unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace,
+                                    size_t ws_bytes, const emu_sample_params* params, int warp_accumulated, const float* uniforms,
+                                    int uni_rows, int32_t* draws_out, float* acc_out, long ld_acc, int ngram, emu_stream_t s) {
     if (!logits || !running_seq || !sequences || !running_scores || !beam_scores || !finished || !seq_len || !heuristic_open ||
-        !next_tok || !beam_flat || !params)
+        !next_tok || !beam_flat || !params || ngram < 0)
         return -22;
     BeamSampleArgs a;
     a.st = BeamStepArgs{B(logits), ld_prompt, ld_beam, V, Bn, nb, L, cur, cur_dev, min_len, eos_id, length_penalty, hf431, running_seq,
                         sequences, running_scores, beam_scores, finished, seq_len, heuristic_open, next_tok, beam_flat};
+    a.st.ngram = ngram;
     a.penalty = params->repetition_penalty;
     a.do_sample = params->do_sample; a.temperature = params->temperature; a.top_k = params->top_k; a.top_p = params->top_p;
     a.min_keep = params->min_keep < 2 ? 2 : params->min_keep;      // the library's warpers under beam search: one EOS id + 1
@@ -1518,6 +1539,17 @@ int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, 
     a.uniforms = uniforms; a.uni_rows = uni_rows;
     a.draws_out = draws_out; a.acc_out = acc_out; a.ld_acc = ld_acc;
     return launch_beam_sample_step(a, reinterpret_cast<float*>(workspace), ws_bytes / sizeof(float), S(s));
+}
+int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
+                              int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                              float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                              unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                              const emu_sample_params* params, int warp_accumulated, const float* uniforms, int uni_rows,
+                              int32_t* draws_out, float* acc_out, long ld_acc, emu_stream_t s) {
+    return emu_beam_sample_step_ngram_bf16(logits, ld_prompt, ld_beam, V, Bn, nb, L, cur, cur_dev, min_len, eos_id, length_penalty, hf431,
+                                           running_seq, sequences, running_scores, beam_scores, finished, seq_len, heuristic_open,
+                                           next_tok, beam_flat, workspace, ws_bytes, params, warp_accumulated, uniforms, uni_rows,
+                                           draws_out, acc_out, ld_acc, 0, s);
 }
 
 int emu_regress_advance_bf16(const void* src, void* out_all, void* prev, int32_t* pos, int32_t* slot, int32_t* step_dev, int Bn,
@@ -1613,14 +1645,15 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
 // selection is the only difference: `score` set = the token is FORCED (targets[step, :] of score->T rows, its log-probability under
 // the logits filed at [step, :]; nothing is selected, filed or advanced once step >= T); else `params` null = arg-max; else
 // emu_sample_bf16's kernel, for which the ids of steps 0 .. step - 1 in out_ids are the history (with `trie` and `node`:
-// emu_sample_trie_bf16's, the rows' trie nodes advancing on the device).  Either way the selection goes to
+// emu_sample_trie_bf16's, the rows' trie nodes advancing on the device; with `ngram` > 0: emu_sample_ngram_bf16's, the no-repeat
+// n-gram ban over the same history).  Either way the selection goes to
 // cur_ids and the advance files it at `step` (the forced loop has no out_ids: its tokens are the caller's).
 struct ScoreSel { const int32_t* targets; int T; float* lp; float* lse; int32_t* top1; };
 static int llama_token_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart, int32_t* ctx_dev,
                             int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden, void* logits, int ld_logits,
                             void* workspace, size_t ws_bytes, const float* uniforms, int32_t* unfinished,
                             const emu_sample_params* params, const ScoreSel* score, const emu_token_trie* trie, int32_t* node,
-                            emu_stream_t s) {
+                            int ngram, emu_stream_t s) {
     const emu_llama_cfg& c = m->cfg;
     TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
@@ -1629,7 +1662,7 @@ static int llama_token_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos
                                                 score->lp, score->lse, score->top1, nullptr, nullptr, Bn, cur_ids, S(s)));
     else if (!params) TRY(m->ctx, launch_argmax(B(logits), ld_logits, Bn, c.vocab, -1, cur_ids, S(s)));
     else TRY(m->ctx, launch_sample(B(logits), ld_logits, Bn, c.vocab, out_ids, Bn, max_new, step_dev, uniforms, Bn, max_new, params,
-                                   unfinished, cur_ids, nullptr, 0, trie, node, S(s)));
+                                   unfinished, cur_ids, nullptr, 0, trie, node, ngram, S(s)));
     TRY(m->ctx, launch_greedy_advance(cur_ids, pos, slot, ctx_dev, step_dev, out_ids, Bn, score ? score->T : 0, S(s)));
     return 0;
 }
@@ -1639,7 +1672,7 @@ int emu_llama_greedy_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
     if (!m || !m->embed) return -22;
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, 0, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s);
+                            workspace, ws_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, s);
 }
 
 int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
@@ -1649,7 +1682,17 @@ int emu_llama_sample_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, 
     if (!m || !m->embed || !params || !unfinished || max_new < 1) return -22;
     if (m->cfg.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;           // refused before anything is launched
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, max_new, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, nullptr, nullptr, s);
+                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, nullptr, nullptr, 0, s);
+}
+
+int emu_llama_sample_step_ngram(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                                int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
+                                void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
+                                int32_t* unfinished, const emu_sample_params* params, int ngram, emu_stream_t s) {
+    if (!m || !m->embed || !params || !unfinished || max_new < 1 || ngram < 0) return -22;
+    if (m->cfg.vocab > EMU_SAMPLE_MAX_VOCAB) return -22;           // refused before anything is launched
+    return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, max_new, ctx_upper, hidden, logits, ld_logits,
+                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, nullptr, nullptr, ngram, s);
 }
 
 int emu_llama_sample_step_trie(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
@@ -1662,7 +1705,7 @@ int emu_llama_sample_step_trie(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* 
     if (!trie || !node || !trie->first || trie->nodes < 1 || trie->edges < 0 || (trie->edges > 0 && (!trie->tok || !trie->child)))
         return -22;
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, out_ids, max_new, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, trie, node, s);
+                            workspace, ws_bytes, uniforms, unfinished, params, nullptr, trie, node, 0, s);
 }
 
 int emu_llama_score_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
@@ -1672,7 +1715,7 @@ int emu_llama_score_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, i
     if (!m || !m->embed || !targets || !step_dev || !ctx_dev || T < 1) return -22;
     const ScoreSel sel{targets, T, lp, lse, top1};
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, nullptr, 0, ctx_upper, hidden, logits, ld_logits,
-                            workspace, ws_bytes, nullptr, nullptr, nullptr, &sel, nullptr, nullptr, s);
+                            workspace, ws_bytes, nullptr, nullptr, nullptr, &sel, nullptr, nullptr, 0, s);
 }
 
 }  // extern "C"

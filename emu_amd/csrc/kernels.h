@@ -249,11 +249,12 @@ int launch_embed_gather(const int32_t* ids, const bf16_t* table, bf16_t* out, in
 // out[dst_rows[i], :] = src[i, :]
 int launch_scatter_rows(const bf16_t* src, const int32_t* dst_rows, bf16_t* out, int n_rows, int hidden, hipStream_t s);
 int launch_argmax(const bf16_t* logits, int ld, int rows, int vocab, int suppress_id, int32_t* out, hipStream_t s);
-// sample.hip: emu_sample_bf16 / emu_sample_trie_bf16 (include/emu_hip.h); trie and node both null = no constraint
+// sample.hip: emu_sample_bf16 / emu_sample_trie_bf16 / emu_sample_ngram_bf16 (include/emu_hip.h); trie and node both null = no
+// constraint; ngram = the no-repeat n-gram size over hist, 0 = off
 int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                   const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* p,
                   int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, const emu_token_trie* trie, int32_t* node,
-                  hipStream_t s);
+                  int ngram, hipStream_t s);
 // score.hip: emu_token_logprob_bf16 (include/emu_hip.h).  limit > 0: nothing is written once *step_dev >= limit; force_ids (may be
 // null): force_ids[row] = the row's target, 0 for an ignored one (emu_llama_score_step's next input)
 int launch_token_logprob(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* targets, int tgt_ld, const int32_t* step_dev,
@@ -503,6 +504,7 @@ struct BeamStepArgs {
     int32_t* next_tok; long* beam_flat;        // [B * nb] out: token to feed / cache row it continues
     emu_token_trie trie = {};                  // constraint (emu_beam_step_trie_bf16), read only when node is set
     int32_t* node = nullptr;                   // [B * nb] in/out: the beams' trie nodes; null = no constraint
+    int ngram = 0;                             // no-repeat n-gram size over running_seq[b, j, :cur] (ngram.h); 0 = off
 };
 // KV re-order of a hipGraph-replayed beam step (beam.hip)
 int launch_beam_reorder(bf16_t* kc, bf16_t* vc, const long* beam_flat, const int32_t* cur_dev, int layers, int rows, int Hl, int s_max,

@@ -12,8 +12,13 @@
 // and writes -inf over those that are no edge, right after the suppress: the row fills the LDS at V = 40 000, so there is no room for
 // a bitmap, and from there on a thread reads only the ids it owns, so the mask needs no barrier of its own.  Thread 0 advances the
 // node by the id it files.
+//
+// With a no-repeat n-gram ban (emu_sample_ngram_bf16; ngram.h) the threads share the start positions of the row's history and write
+// -inf over the id behind every repetition of its last n - 1 ids, between the penalty and the suppress (the library's processor
+// order); one barrier follows, since the banned id is rarely one the writing thread owns.
 #include "sample_common.h"
 #include "trie.h"
+#include "ngram.h"
 
 namespace {
 
@@ -27,6 +32,7 @@ struct SampleArgs {
     int eos_id; int pad_id;
     int32_t* unfinished; int32_t* out; float* probs; int ld_probs;
     emu_token_trie trie; int32_t* node;                          // node null = no constraint
+    int ngram;                                                   // no-repeat n-gram size over hist; 0 = off
 };
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
@@ -58,6 +64,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
                 score[id] = s < 0.f ? s * a.penalty : s / a.penalty;
             }
         }
+        __syncthreads();
+    }
+    // 2a. no-repeat n-gram ban: the id behind every earlier occurrence of the row's last n - 1 ids -> -inf
+    if (a.hist && a.ngram > 0) {
+        const int nh = step < a.hist_rows ? step : a.hist_rows;
+        ngram_matches(a.hist + row, (size_t)a.hist_ld, nh, a.ngram, tid, SAMPLE_THREADS, [&](int id) {
+            if (id >= 0 && id < V) score[id] = -INFINITY;
+        });
         __syncthreads();
     }
     // 3. min-length suppress
@@ -189,8 +203,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(SampleArgs a) {
 int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
                   const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* p,
                   int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, const emu_token_trie* trie, int32_t* node,
-                  hipStream_t s) {
+                  int ngram, hipStream_t s) {
     if ((trie || node) && !trie_args_ok(trie, node)) return -22;
+    if (ngram < 0) return -22;
     if (!logits || !step_dev || !out || !p || rows < 1 || vocab < 1 || vocab > EMU_SAMPLE_MAX_VOCAB || ld < vocab) return -22;
     if (p->min_keep < 1 || !(p->repetition_penalty > 0.f)) return -22;
     if (p->do_sample && (!uniforms || uni_rows < 1 || uni_ld < rows || !(p->temperature > 0.f) || !(p->top_p > 0.f))) return -22;
@@ -206,6 +221,7 @@ int launch_sample(const bf16_t* logits, int ld, int rows, int vocab, const int32
     a.eos_id = p->eos_id; a.pad_id = p->pad_id;
     a.unfinished = unfinished; a.out = out; a.probs = probs_out; a.ld_probs = ld_probs;
     a.trie = trie ? *trie : emu_token_trie{}; a.node = node;
+    a.ngram = ngram;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

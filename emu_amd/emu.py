@@ -73,7 +73,7 @@ class EmuModel:
                  *, llama_cfg: Optional[LlamaCfg] = None, device="cuda", tp_rank: int = 0, tp_size: int = 1,
                  ctx: Optional[EmuHipContext] = None, vit_token_parallel: Optional[bool] = None,
                  device_sampler: Optional[bool] = None, device_beam_sampler: Optional[bool] = None,
-                 device_contrastive: Optional[bool] = None):
+                 device_contrastive: Optional[bool] = None, device_ngram_ban: Optional[bool] = None):
         """``device_sampler`` (default: the ``EMU_DEVICE_SAMPLER`` environment variable, off unless "1"): sampling and penalised
         greedy generation (one beam) keep their token loop on the device (``LlamaEngine.sample_generate(device_sampler=True)``:
         uniforms drawn once up front, so a different random stream from the default's ``torch.multinomial``).
@@ -88,6 +88,11 @@ class EmuModel:
         (``LlamaEngine.contrastive_generate(device_contrastive=True)``: candidates, degeneration penalty, selection and the KV copy
         in kernels of csrc/contrastive.hip, replayed from one hipGraph with ``use_graph``).  Its sums are fp32 in a fixed order, so
         a choice the host loop decides by less than its own rounding may fall the other way.
+
+        ``device_ngram_ban`` (default: the ``EMU_DEVICE_NGRAM_BAN`` environment variable, off unless "1"): with
+        ``no_repeat_ngram_size > 0`` the two device samplers above stay on instead of handing the call to the host loop, and the
+        deterministic beam search keeps its device loop: the ban runs inside the selection kernels
+        (``LlamaEngine.sample_generate`` / ``beam_search_generate(device_ngram_ban=True)``).  It switches no sampler on by itself.
 
         ``vit_token_parallel`` (default: the ``EMU_VIT_TOKEN_PARALLEL`` environment variable, off unless "1"): under tensor
         parallelism a prompt with ONE image splits its ViT encode across the ranks by token rows (``encode_image``) instead of every
@@ -116,6 +121,7 @@ class EmuModel:
         self.device_sampler = option_or_env(device_sampler, "EMU_DEVICE_SAMPLER")
         self.device_beam_sampler = option_or_env(device_beam_sampler, "EMU_DEVICE_BEAM_SAMPLER")
         self.device_contrastive = option_or_env(device_contrastive, "EMU_DEVICE_CONTRASTIVE")
+        self.device_ngram_ban = option_or_env(device_ngram_ban, "EMU_DEVICE_NGRAM_BAN")
         # beam-search conventions: the transformers release the reference pins (Emu2/requirements.txt:2); "5.x" = the installed
         # library's vectorised search, the one the golden fixtures can pin (LlamaEngine.beam_search_generate)
         self.hf_semantics = "4.31"
@@ -297,8 +303,11 @@ class EmuModel:
                               "tests/golden/ (the library is not installable offline).  hf_semantics='5.x' is the mode pinned to the "
                               "installed library's ids; the two differ only where a hypothesis ends on EOS (INTEGRATION.md).",
                               stacklevel=2)
-            # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
-            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
+            # the n-gram ban keeps the host loop unless device_ngram_ban is set; with the options off the call is the old one
+            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
+            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and (not ngram or ban) else {}
+            if ban:
+                on_device["device_ngram_ban"] = True
             if constraint is not None:
                 on_device["constraint"] = constraint
             return self.decoder.lm.beam_search_generate(x.view(B, S, -1), attention_mask, num_beams, max_new_tokens, min_len,
@@ -307,12 +316,13 @@ class EmuModel:
                                                         repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
                                                         num_return_sequences=nret, hf_semantics=sem, **on_device)
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
+            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
             return self.decoder.lm.sample_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len, do_sample,
                                                    temperature, top_k, top_p, repetition_penalty, eos_id=eos,
                                                    pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                                   # the n-gram ban is not built on the device: it keeps the host loop
-                                                   device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram,
-                                                   use_graph=self.use_graph,
+                                                   # the n-gram ban keeps the host loop unless device_ngram_ban is set
+                                                   device_sampler=bool(getattr(self, "device_sampler", False)) and (not ngram or ban),
+                                                   use_graph=self.use_graph, **(dict(device_ngram_ban=True) if ban else {}),
                                                    **({} if constraint is None else dict(constraint=constraint)))
         return self.decoder.lm.greedy_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len,
                                                eos_id=eos, pad_id=PAD_TOKEN_ID, use_graph=self.use_graph,

@@ -213,10 +213,12 @@ class Emu:
     def __init__(self, vision_cfg: Optional[CLIPVisionCfg] = None, llama_cfg: Optional[LlamaCfg] = None,
                  t5_cfg: Optional[T5DecoderCfg] = None, vocab: int = 32006, device="cuda", instruct: bool = False,
                  ctx: Optional[EmuHipContext] = None, device_sampler: Optional[bool] = None,
-                 device_beam_sampler: Optional[bool] = None, device_contrastive: Optional[bool] = None):
+                 device_beam_sampler: Optional[bool] = None, device_contrastive: Optional[bool] = None,
+                 device_ngram_ban: Optional[bool] = None):
         """``device_sampler`` (default: ``EMU_DEVICE_SAMPLER``, off unless "1"), ``device_beam_sampler`` (default:
-        ``EMU_DEVICE_BEAM_SAMPLER``, off unless "1") and ``device_contrastive`` (default: ``EMU_DEVICE_CONTRASTIVE``, off unless
-        "1"): as ``EmuModel``'s options of those names."""
+        ``EMU_DEVICE_BEAM_SAMPLER``, off unless "1"), ``device_contrastive`` (default: ``EMU_DEVICE_CONTRASTIVE``, off unless
+        "1") and ``device_ngram_ban`` (default: ``EMU_DEVICE_NGRAM_BAN``, off unless "1"): as ``EmuModel``'s options of those
+        names."""
         self.vision_cfg = vision_cfg or emu1_vision_cfg()
         self.llama_cfg = llama_cfg or emu1_llama_cfg()
         self.t5_cfg = t5_cfg or T5DecoderCfg()
@@ -237,6 +239,7 @@ class Emu:
         self.device_sampler = option_or_env(device_sampler, "EMU_DEVICE_SAMPLER")
         self.device_beam_sampler = option_or_env(device_beam_sampler, "EMU_DEVICE_BEAM_SAMPLER")
         self.device_contrastive = option_or_env(device_contrastive, "EMU_DEVICE_CONTRASTIVE")
+        self.device_ngram_ban = option_or_env(device_ngram_ban, "EMU_DEVICE_NGRAM_BAN")
 
     def load_state_dict(self, sd, strict: bool = True, lora_r: int = 16, lora_alpha: float = 16.0):
         """Reference key names (Emu1/models/modeling_emu.py).  The instruct checkpoint is saved with peft LoRA adapters
@@ -310,8 +313,11 @@ class Emu:
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,
                                                 repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, **on_device)
         if num_beams > 1:
-            # the n-gram ban is not built on the device: it keeps the host loop; with the option off the call is the old one
-            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and not ngram else {}
+            # the n-gram ban keeps the host loop unless device_ngram_ban is set; with the options off the call is the old one
+            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
+            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and (not ngram or ban) else {}
+            if ban:
+                on_device["device_ngram_ban"] = True
             if constraint is not None:
                 on_device["constraint"] = constraint
             return self.lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_length, length_penalty,
@@ -321,10 +327,12 @@ class Emu:
                                                 num_return_sequences=nret,
                                                 hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"), **on_device)
         if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
+            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))     # the ban keeps the host loop unless this is set
             return self.lm.sample_generate(x, attention_mask, max_new_tokens, min_length, do_sample, temperature, top_k, top_p,
                                            repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID,
                                            no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                           device_sampler=bool(getattr(self, "device_sampler", False)) and not ngram,
+                                           device_sampler=bool(getattr(self, "device_sampler", False)) and (not ngram or ban),
+                                           **(dict(device_ngram_ban=True) if ban else {}),
                                            **({} if constraint is None else dict(constraint=constraint)))
         return self.lm.greedy_generate(x, attention_mask, max_new_tokens, min_length, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
 

@@ -758,7 +758,7 @@ class LlamaEngine:
                         top_p: Optional[float] = None, repetition_penalty: float = 1.0, eos_id: int = 2,
                         pad_id: int = 32000, no_repeat_ngram_size: int = 0, num_return_sequences: int = 1,
                         device_sampler: bool = False, use_graph: bool = False,
-                        uniforms: Optional[torch.Tensor] = None, constraint=None) -> torch.Tensor:
+                        uniforms: Optional[torch.Tensor] = None, constraint=None, device_ngram_ban: bool = False) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=1)`` with logits processing: repetition penalty, min_length, then
         (when sampling) temperature / top-k / top-p warpers and a multinomial draw from torch's global CUDA generator
         (transformers' processor order).  The decoder runs on the HIP engine; the tiny per-step logits post-processing is
@@ -779,12 +779,27 @@ class LlamaEngine:
         ``constraint`` (``emu_amd.constrain.TokenTrie`` or a callable (batch_id, ids generated so far) -> allowed ids, the library's
         ``prefix_allowed_tokens_fn``): the mask stands where the library's PrefixConstrainedLogitsProcessor does, after the
         processors and ahead of the warpers.  A trie with ``device_sampler=True`` runs on the device (``emu_sample_trie_bf16`` /
-        ``emu_llama_sample_step_trie``; ``do_sample=False`` = constrained greedy); a callable always keeps the host loop."""
+        ``emu_llama_sample_step_trie``; ``do_sample=False`` = constrained greedy); a callable always keeps the host loop.
+
+        ``device_ngram_ban=True`` (opt-in, read only with ``device_sampler=True``): ``no_repeat_ngram_size > 0`` is no longer refused;
+        the ban runs inside the selection kernel (``emu_sample_ngram_bf16`` / ``emu_llama_sample_step_ngram``, specified by
+        ``sampling.banned_ngram_mask``) over the ids the row has generated, and the loop stays capturable.  The host loop takes over,
+        with one warning per process, for a ``TokenTrie`` together with the ban (not built on the device) and for a vocabulary below
+        ``max_new_tokens + 2``: the ban (at most one id per generated token) and the EOS suppress could otherwise leave a row
+        without a finite score, which the draw does not define."""
         trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
         if device_sampler and allow_fn is not None and trie is None:
             device_sampler = False                              # a Python callable cannot run inside a captured step
+        ngram = int(no_repeat_ngram_size or 0)
+        if device_sampler and ngram > 0 and device_ngram_ban:
+            why = ("a TokenTrie together with the ban is not built on the device" if trie is not None else
+                   f"vocabulary {self.vocab} is below max_new_tokens + 2 = {max_new_tokens + 2} (the ban and the EOS suppress could "
+                   "leave a row without a finite score)" if self.vocab < max_new_tokens + 2 else None)
+            if why is not None:
+                warn_once(LlamaEngine, "_warned_ngram_ban", f"emu_amd: device_ngram_ban: {why}; staying on the host path")
+                device_sampler = False
         if device_sampler:
-            if int(no_repeat_ngram_size or 0) > 0:
+            if ngram > 0 and not device_ngram_ban:
                 raise ValueError("device_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
                                  "(device_sampler=False)")
             if self.ctx.tp_size > 1:
@@ -809,7 +824,8 @@ class LlamaEngine:
         row = hidden[:, -1, :]
         if device_sampler:
             return self._sample_device(row, B, S, kstart, pos, max_new_tokens, min_len, do_sample, temperature, top_k, top_p,
-                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms, trie)
+                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms, trie,
+                                       **(dict(ngram=ngram) if ngram > 0 else {}))      # (off: the call is the old one)
         out = torch.full((B, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
         unfinished = torch.ones(B, dtype=torch.int64, device=dev)
         hid = torch.empty(B, H, device=dev, dtype=BF16)
@@ -837,12 +853,14 @@ class LlamaEngine:
         return out[:, :n]
 
     _warned_sampler_vocab = False          # one warning per process (sample_generate)
+    _warned_ngram_ban = False              # ... and for device_ngram_ban outside what the kernels take (both generate loops)
 
     def _sample_device(self, row: torch.Tensor, B: int, S: int, kstart: torch.Tensor, next_pos: torch.Tensor, max_new: int,
                        min_len: int, do_sample: bool, temperature, top_k, top_p, repetition_penalty: float, eos_id: int,
-                       pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor], trie: Optional[TokenTrie] = None) -> torch.Tensor:
+                       pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor], trie: Optional[TokenTrie] = None,
+                       ngram: int = 0) -> torch.Tensor:
         """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill.  ``trie``: the selection is
-        ``emu_sample_trie_bf16``, every row starting at the root."""
+        ``emu_sample_trie_bf16``, every row starting at the root.  ``ngram`` > 0: the selection is ``emu_sample_ngram_bf16``."""
         dev = self.device
         if do_sample:
             uni = torch.rand(max_new, B, dtype=torch.float32, device=dev) if uniforms is None else \
@@ -852,7 +870,7 @@ class LlamaEngine:
         out_ids = torch.full((max_new, B), pad_id, device=dev, dtype=torch.int32)
         st = SampleState(self, B, next_pos, S, kstart, out_ids, uni,
                          sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id),
-                         None if trie is None else trie.tables(dev))
+                         None if trie is None else trie.tables(dev), ngram)
         self.logits(row, out=st.logits)
         st.first()
         # the only host read: the rows' flags, every EOS_POLL steps (the launches in between stay queued ahead)
@@ -1205,7 +1223,7 @@ class LlamaEngine:
                              repetition_penalty: float = 1.0, hf_semantics: str = "4.31",
                              trace: Optional[dict] = None, no_repeat_ngram_size: int = 0,
                              num_return_sequences: int = 1, uniforms: Optional[torch.Tensor] = None,
-                             device_beam_sampler: bool = False, constraint=None) -> torch.Tensor:
+                             device_beam_sampler: bool = False, constraint=None, device_ngram_ban: bool = False) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., num_beams=N, do_sample=False, early_stopping=False)`` -- the reference's
         DEFAULT decoding mode (num_beams=5, length_penalty=-1, Emu2/emu/emu.py:163-172,213-229).  Restates
         transformers' vectorised beam search: per step keep the 2N best continuations over beams x vocab, the N best
@@ -1270,7 +1288,18 @@ class LlamaEngine:
         included, to the lower index (stable top-k) -- and the ``trace`` margins leave out exact ties and non-finite gaps (-inf minus
         -inf).  A trie in the deterministic, unpenalised mode runs on the device (``emu_beam_step_trie_bf16``) within the kernel's
         bounds, like the unconstrained search.  The host loop takes over for a callable, and for a trie together with sampling, a
-        repetition penalty, an n-gram ban or a ``trace``; ``device_beam_sampler`` is then ignored with one warning per process."""
+        repetition penalty, an n-gram ban or a ``trace``; ``device_beam_sampler`` is then ignored with one warning per process.
+
+        ``device_ngram_ban=True`` (opt-in) with ``no_repeat_ngram_size > 0``: the ban runs inside the selection kernels
+        (``sampling.banned_ngram_mask`` over ``running_seq[b, j, :cur]``, which follows the beams) and the loop stays on the device:
+        the deterministic, unpenalised search goes to ``_beam_search_device`` with ``emu_beam_step_ngram_bf16`` instead of the host
+        loop, and ``device_beam_sampler=True`` is no longer refused but runs ``emu_beam_sample_step_ngram_bf16``.  Without the flag
+        both are as before.  The host loop takes over -- with one warning per process where ``device_beam_sampler`` is thereby
+        ignored -- for a constraint of any kind together with the ban, for a ``trace``, and for a vocabulary below
+        ``max_new_tokens + 1 + 2 * num_beams`` (the ban takes at most one id per generated token from a beam's row, and 2N finite
+        continuations must remain beside the EOS suppress).  Under tensor parallelism the deterministic branch is not refused:
+        nothing is random and every rank holds the same ids; no multi-rank run of it has been made.  The sampler branch keeps its
+        refusal."""
         trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
         if allow_fn is not None and device_beam_sampler and (do_sample or repetition_penalty != 1.0):
             warn_once(LlamaEngine, "_warned_beam_constraint",
@@ -1286,8 +1315,21 @@ class LlamaEngine:
             raise ValueError(f"uniforms must be [max_new_tokens, prompts, 2 * num_beams] = "
                              f"[{max_new_tokens}, {embeds.shape[0]}, {2 * num_beams}], got {tuple(uniforms.shape)}")
         device_beam_sampler = bool(device_beam_sampler) and (do_sample or repetition_penalty != 1.0)
+        # the ban on the device: asked for, and within what the kernels take
+        ban_why = None
+        if ngram > 0 and device_ngram_ban:
+            ban_why = ("a constraint together with the ban is not built on the device" if allow_fn is not None else
+                       "a trace is asked for" if trace is not None else
+                       f"vocabulary {self.vocab} is below max_new_tokens + 1 + 2 * num_beams = {max_new_tokens + 1 + 2 * num_beams} "
+                       "(a beam could be left with fewer than 2N finite continuations)"
+                       if self.vocab < max_new_tokens + 1 + 2 * num_beams else None)
+        device_ban = ngram > 0 and bool(device_ngram_ban) and ban_why is None
+        if device_beam_sampler and ngram > 0 and device_ngram_ban and ban_why is not None:
+            warn_once(LlamaEngine, "_warned_ngram_ban",
+                      f"emu_amd: device_ngram_ban: {ban_why}; device_beam_sampler is ignored, staying on the host path")
+            device_beam_sampler = False
         if device_beam_sampler:
-            if ngram > 0:
+            if ngram > 0 and not device_ban:
                 raise ValueError("device_beam_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
                                  "(device_beam_sampler=False)")
             if self.ctx.tp_size > 1:
@@ -1316,18 +1358,21 @@ class LlamaEngine:
         max_len = max_new_tokens
         NEG = -1.0e9
         # The deterministic mode (the reference's default) runs each step's selection and bookkeeping in ONE kernel
-        # (emu_beam_step_bf16); sampling, penalties, n-gram bans and the diagnostics keep the torch pipeline below.
-        if (not do_sample and repetition_penalty == 1.0 and not ngram and trace is None and nb <= 8 and max_len <= 256
+        # (emu_beam_step_bf16; with device_ngram_ban its _ngram form); sampling, penalties, n-gram bans without that option and the
+        # diagnostics keep the torch pipeline below.
+        if (not do_sample and repetition_penalty == 1.0 and (not ngram or device_ban) and trace is None and nb <= 8 and max_len <= 256
                 and V >= 2 * nb and hasattr(self, "handle") and logits.dtype == BF16 and (allow_fn is None or trie is not None)):
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
-                                            int(num_return_sequences), hf_semantics == "4.31", trie=trie)
+                                            int(num_return_sequences), hf_semantics == "4.31", trie=trie,
+                                            **(dict(ngram=ngram) if device_ban else {}))      # (off: the call is the old one)
         if device_beam_sampler:
             if not hasattr(self, "handle") or logits.dtype != BF16:
                 raise RuntimeError("device_beam_sampler needs the HIP engine and its bf16 logits")
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
                                             int(num_return_sequences), hf_semantics == "4.31",
                                             sampler=(sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id,
-                                                                   min_len, eos_id, pad_id, min_keep=2), uniforms))
+                                                                   min_len, eos_id, pad_id, min_keep=2), uniforms),
+                                            **(dict(ngram=ngram) if device_ban else {}))
         logits = logits.float()
         running_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=dev)
         sequences = running_seq.clone()
@@ -1470,7 +1515,7 @@ class LlamaEngine:
     def _beam_search_device(self, logits0: torch.Tensor, B: int, S: int, nb: int, max_len: int, min_len: int,
                             length_penalty: float, eos_id: int, pad_id: int, kstart_b: torch.Tensor, pos: torch.Tensor,
                             nret: int, v431: bool = True, sampler: Optional[tuple] = None,
-                            trie: Optional[TokenTrie] = None) -> torch.Tensor:
+                            trie: Optional[TokenTrie] = None, ngram: int = 0) -> torch.Tensor:
         """The loop of ``beam_search_generate`` for the deterministic mode, with nothing left on the host but the replay of a
         hipGraph: per step {``emu_beam_advance`` (slot / position of the token to feed from the device-side step counter) ->
         ``emu_llama_beam_reorder_kv`` (the generated KV slots follow the beam permutation) -> embedding gather -> the decoder
@@ -1489,15 +1534,21 @@ class LlamaEngine:
 
         ``trie`` (deterministic mode only): the same loop with ``emu_beam_step_trie_bf16`` as its step.  The beams' nodes live in the
         state and start at the root; the state keeps the trie's tables alive, and their addresses are part of the key, so a call
-        with another trie captures anew."""
+        with another trie captures anew.
+
+        ``ngram`` > 0 (``device_ngram_ban``; not together with a trie): the step is ``emu_beam_step_ngram_bf16`` or, with ``sampler``,
+        ``emu_beam_sample_step_ngram_bf16``.  The n is a scalar of the launch, so it is part of the key."""
         dev, V, rows = self.device, self.vocab, B * nb
+        ngram = int(ngram)
+        if ngram and trie is not None:
+            raise ValueError("the n-gram ban together with a constraint is not built on the device")
         tables = None if trie is None else trie.tables(dev)
         L = lib()
         params = sampler[0] if sampler is not None else None
         sampling = params is not None and bool(params.do_sample)
         opts = None if params is None else (sampling, params.repetition_penalty, params.temperature, params.top_k, params.top_p)
         key = (B, nb, S, self.s_max, max_len, int(min_len), float(length_penalty), int(eos_id), bool(v431), self.kcache.data_ptr(),
-               self.mode_epoch, opts, None if tables is None else tuple((t.data_ptr(), t.numel()) for t in tables))
+               self.mode_epoch, opts, None if tables is None else tuple((t.data_ptr(), t.numel()) for t in tables), ngram)
 
         def build():
             i32 = dict(dtype=torch.int32, device=dev)
@@ -1540,8 +1591,14 @@ class LlamaEngine:
             if tables is not None:
                 check(L.emu_beam_step_trie_bf16(*state, C.byref(st["trie"]), st["node"].data_ptr(), stream()),
                       "emu_beam_step_trie_bf16", self.ctx.handle)
+            elif params is None and ngram:
+                check(L.emu_beam_step_ngram_bf16(*state, ngram, stream()), "emu_beam_step_ngram_bf16", self.ctx.handle)
             elif params is None:
                 check(L.emu_beam_step_bf16(*state, stream()), "emu_beam_step_bf16", self.ctx.handle)
+            elif ngram:
+                check(L.emu_beam_sample_step_ngram_bf16(*state, params, int(sampling and v431),
+                                                        st["uni"].data_ptr() if sampling else None, max_len, None, None, 0, ngram,
+                                                        stream()), "emu_beam_sample_step_ngram_bf16", self.ctx.handle)
             else:
                 check(L.emu_beam_sample_step_bf16(*state, params, int(sampling and v431), st["uni"].data_ptr() if sampling else None,
                                                   max_len, None, None, 0, stream()), "emu_beam_sample_step_bf16", self.ctx.handle)
@@ -1755,13 +1812,17 @@ class SampleState(GreedyState):
     ``step_graph`` is GreedyState's: the min-length suppress and the history length, too, come from the device-side step index."""
 
     def __init__(self, eng: "LlamaEngine", B: int, next_pos: torch.Tensor, S: int, kstart: torch.Tensor, out_ids: torch.Tensor,
-                 uniforms: Optional[torch.Tensor], params: SampleParamsC, trie_tables: Optional[tuple] = None):
+                 uniforms: Optional[torch.Tensor], params: SampleParamsC, trie_tables: Optional[tuple] = None, ngram: int = 0):
         super().__init__(eng, B, torch.zeros(B, device=eng.device, dtype=torch.int32), next_pos, S, kstart, out_ids)
         # constraint: the tables (kept alive here for as long as a captured graph holds their addresses), their C view, and the rows'
         # nodes, every row at the root
         self.trie_tables = trie_tables
         self.trie = None if trie_tables is None else ops.trie_tables(trie_tables)
         self.node = None if trie_tables is None else torch.zeros(B, device=eng.device, dtype=torch.int32)
+        # no-repeat n-gram ban (0 = off): a scalar of the step's launch, so a captured step holds it -- it is part of the graph's key
+        self.ngram = int(ngram)
+        if self.ngram and trie_tables is not None:
+            raise ValueError("the n-gram ban together with a constraint is not built on the device")
         self.step_idx.zero_()                              # no token yet: first() draws it
         self.unfinished = torch.ones(B, device=eng.device, dtype=torch.int32)
         self.uniforms, self.params = uniforms, params
@@ -1770,7 +1831,7 @@ class SampleState(GreedyState):
     def first(self) -> None:
         """The first token, from ``self.logits`` (the prefill's last rows): step 0 of the table."""
         ops.sample(self.logits, self.step_idx, self.params, self.cur, hist=self.out_ids, uniforms=self.uniforms,
-                   unfinished=self.unfinished, trie=self.trie, node=self.node)
+                   unfinished=self.unfinished, trie=self.trie, node=self.node, ngram=self.ngram or None)
         self.out_ids[0] = self.cur
         self.step_idx.fill_(1)
 
@@ -1780,11 +1841,18 @@ class SampleState(GreedyState):
                 self.ctx.data_ptr(), self.step_idx.data_ptr(), self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
                 self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(), ops._p(self.uniforms),
                 self.unfinished.data_ptr(), C.byref(self.params))
-        if self.trie is None:
+        if self.ngram:
+            check(lib().emu_llama_sample_step_ngram(*args, self.ngram, ops.stream(e.device)), "emu_llama_sample_step_ngram",
+                  e.ctx.handle)
+        elif self.trie is None:
             check(lib().emu_llama_sample_step(*args, ops.stream(e.device)), "emu_llama_sample_step", e.ctx.handle)
         else:
             check(lib().emu_llama_sample_step_trie(*args, C.byref(self.trie), self.node.data_ptr(), ops.stream(e.device)),
                   "emu_llama_sample_step_trie", e.ctx.handle)
+
+    def step_graph(self) -> None:
+        """GreedyState's, the n of the ban beside the mode epoch in the key: the captured launch holds that scalar."""
+        self.captured.step(self.step, True, (self.eng.mode_epoch, self.ngram))
 
 
 class ScoreState(GreedyState):

@@ -313,12 +313,14 @@ def trie_tables(tables):
 
 
 def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist=None, uniforms=None, unfinished=None,
-           probs_out=None, trie=None, node=None):
+           probs_out=None, trie=None, node=None, ngram: Optional[int] = None):
     """``emu_sample_bf16`` (include/emu_hip.h; specified in emu_amd/sampling.py): one token per row of bf16 ``logits`` [rows, >= vocab]
     under ``params`` (``_lib.SampleParamsC``).  ``step_dev`` int32 [1] on the device = the step index the kernel reads: the number of
     history rows of ``hist`` int32 [steps, rows] in use, the row of ``uniforms`` fp32 [steps, rows], the min-length comparison.
     ``unfinished`` int32 [rows] and ``probs_out`` fp32 [rows, >= vocab] are optional.  ``trie`` (``trie_tables``) with ``node``
-    int32 [rows], in/out: ``emu_sample_trie_bf16``, the selection under a constraint.  Returns ``out`` int32 [rows]."""
+    int32 [rows], in/out: ``emu_sample_trie_bf16``, the selection under a constraint.  ``ngram`` (not None):
+    ``emu_sample_ngram_bf16``, the no-repeat n-gram ban of that size over ``hist`` (0 = off; not built together with a trie).  Returns
+    ``out`` int32 [rows]."""
     _req(logits, "logits")
     rows = logits.shape[0]
     vocab = logits.shape[1] if vocab is None else vocab
@@ -333,7 +335,11 @@ def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist
             hist.shape[0] if hist is not None else 0, _p(step_dev), _p(uniforms),
             uniforms.stride(0) if uniforms is not None else 0, uniforms.shape[0] if uniforms is not None else 0,
             C.byref(params), _p(unfinished), _p(out), _p(probs_out), probs_out.stride(0) if probs_out is not None else 0)
-    if trie is None and node is None:
+    if ngram is not None:
+        if trie is not None or node is not None:
+            raise ValueError("the n-gram ban together with a constraint is not built on the device")
+        check(lib().emu_sample_ngram_bf16(*args, int(ngram), stream(logits)), "emu_sample_ngram_bf16")
+    elif trie is None and node is None:
         check(lib().emu_sample_bf16(*args, stream(logits)), "emu_sample_bf16")
     else:
         if trie is None or node is None or node.numel() < rows:

@@ -8,6 +8,9 @@ The order is transformers' order:
 1. ``s = float32(logit)``.
 2. Repetition penalty: for every DISTINCT history id in [0, vocab): ``s = s * pen if s < 0 else s / pen`` (IEEE fp32 multiply and
    divide), once per id however often it occurs; ids outside [0, vocab) are ignored.
+2a. No-repeat n-gram ban (``banned`` bool [rows, vocab], None = none: ``banned_ngram_mask`` of the ids generated so far; the place
+   of the library's NoRepeatNGramLogitsProcessor, after the penalty and ahead of the suppress): ``s[banned] = -inf``.  This, the
+   suppress and the constraint are masks: after the penalty their order does not matter.
 3. Minimum-length suppress: ``s[suppress_id] = -inf`` (``suppress_id`` None or < 0: not applied).
 3a. Constraint (``allowed`` bool [rows, vocab], None = none; the place of the library's PrefixConstrainedLogitsProcessor):
    ``s[~allowed] = -inf``, so everything below -- the arg-max, the thresholds, the softmax -- runs over the allowed ids.
@@ -44,8 +47,33 @@ def _history_rows(history: History, B: int):
     return [list(map(int, r)) for r in history]
 
 
+def banned_ngram_mask(history: History, n: int, vocab: int) -> torch.Tensor:
+    """Step 2a's mask, bool [rows, vocab] (``history`` [rows, nh] or a list of rows: the ids each row has generated so far; with
+    ``inputs_embeds`` the prompt contributes none).  With h[0 .. nh) a row's ids, ``banned[v]`` holds iff nh + 1 >= n and there is
+    an i in [0, nh - n + 1) with h[i .. i + n - 1) == h[nh - n + 1 .. nh) (an empty comparison for n = 1) and h[i + n - 1] == v:
+    v would complete an n-gram the row already holds.  A would-be banned id outside [0, vocab) is ignored; n < 1 means off."""
+    if isinstance(history, torch.Tensor):              # (a [rows, 0] tensor -- nothing generated yet -- has no -1 to reshape to)
+        rows = [[int(v) for v in r] for r in history.tolist()]
+    else:
+        rows = _history_rows(history, len(history))
+    mask = torch.zeros(len(rows), int(vocab), dtype=torch.bool)
+    n = int(n)
+    if n < 1:
+        return mask
+    for r, h in enumerate(rows):
+        nh = len(h)
+        if nh + 1 < n:
+            continue
+        tail = h[nh - n + 1:]
+        for i in range(nh - n + 1):
+            if h[i:i + n - 1] == tail and 0 <= h[i + n - 1] < vocab:
+                mask[r, h[i + n - 1]] = True
+    return mask
+
+
 def reference_scores(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
-                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None,
+                     banned: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Steps 1-3a: [B, vocab] fp32 scores of bf16 (or fp32-held bf16) logit rows."""
     s = logits.float().clone()
     B, V = s.shape
@@ -57,6 +85,8 @@ def reference_scores(logits: torch.Tensor, history: History = None, repetition_p
                 idx = torch.tensor(ids, dtype=torch.int64, device=s.device)
                 g = s[b, idx]
                 s[b, idx] = torch.where(g < 0, g * pen.to(s.device), g / pen.to(s.device))
+    if banned is not None:
+        s = s.masked_fill(banned.to(device=s.device, dtype=torch.bool), -float("inf"))
     if suppress_id is not None and 0 <= suppress_id < V:
         s[:, suppress_id] = -float("inf")
     if allowed is not None:
@@ -65,9 +95,10 @@ def reference_scores(logits: torch.Tensor, history: History = None, repetition_p
 
 
 def reference_greedy(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
-                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     suppress_id: Optional[int] = None, allowed: Optional[torch.Tensor] = None,
+                     banned: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Step 4: first index of the maximum of the penalised, suppressed scores, [B] int64."""
-    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed)
+    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed, banned)
     first = (s == s.max(dim=-1, keepdim=True)[0]).float().argmax(dim=-1)       # argmax of a 0/1 row: the first 1
     return first
 
@@ -75,9 +106,10 @@ def reference_greedy(logits: torch.Tensor, history: History = None, repetition_p
 def reference_warped(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
                      suppress_id: Optional[int] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
                      top_p: Optional[float] = None, min_keep: int = 1, dtype: torch.dtype = torch.float32,
-                     allowed: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     allowed: Optional[torch.Tensor] = None,
+                     banned: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Steps 1-7: (scores [B, vocab] fp32 after temperature, kept [B, vocab] bool)."""
-    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed)
+    s = reference_scores(logits, history, repetition_penalty, suppress_id, allowed, banned)
     B, V = s.shape
     if temperature is not None and temperature != 1.0:
         s = s / torch.tensor(float(temperature), dtype=torch.float32, device=s.device)
@@ -109,13 +141,15 @@ def reference_warped(logits: torch.Tensor, history: History = None, repetition_p
 def reference_probs(logits: torch.Tensor, history: History = None, repetition_penalty: float = 1.0,
                     suppress_id: Optional[int] = None, do_sample: bool = True, temperature: Optional[float] = None,
                     top_k: Optional[int] = None, top_p: Optional[float] = None, min_keep: int = 1,
-                    dtype: torch.dtype = torch.float32, allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    dtype: torch.dtype = torch.float32, allowed: Optional[torch.Tensor] = None,
+                    banned: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[B, vocab] probabilities the draw is made from (``dtype``), exactly 0 for removed tokens.  ``do_sample`` false: the one-hot
     row of the greedy token."""
     if not do_sample:
-        g = reference_greedy(logits, history, repetition_penalty, suppress_id, allowed)
+        g = reference_greedy(logits, history, repetition_penalty, suppress_id, allowed, banned)
         return torch.zeros(logits.shape, dtype=dtype, device=logits.device).scatter_(1, g[:, None], 1.0)
-    s, kept = reference_warped(logits, history, repetition_penalty, suppress_id, temperature, top_k, top_p, min_keep, dtype, allowed)
+    s, kept = reference_warped(logits, history, repetition_penalty, suppress_id, temperature, top_k, top_p, min_keep, dtype, allowed,
+                               banned)
     q = torch.softmax(s.masked_fill(~kept, -float("inf")).to(dtype), dim=-1)
     return q.masked_fill(~kept, 0.0)
 
@@ -174,8 +208,9 @@ def top_p_threshold_group(logits: torch.Tensor, **opts) -> Tuple[torch.Tensor, t
 # 1. ``lp = x - (m + log sum exp(x - m))`` with ``x = float32(logit)`` and m the row maximum; the subtraction is fp32, the sum is taken
 #    in ``dtype``.
 # 2. The processors act on lp: the repetition penalty of step 2 above (``lp < 0`` multiplies, otherwise divides; once per distinct
-#    history id; ids outside the vocabulary are ignored), then ``lp[eos] = -inf`` while ``cur < min_len``, then the constraint:
-#    ``lp[~allowed] = -inf`` (the log-sum-exp of step 1 is over the whole, unmasked row, as for the EOS suppress).
+#    history id; ids outside the vocabulary are ignored), then the n-gram ban ``lp[banned] = -inf`` (step 2a above, over the beam's own
+#    ids), then ``lp[eos] = -inf`` while ``cur < min_len``, then the constraint: ``lp[~allowed] = -inf`` (the log-sum-exp of step 1 is
+#    over the whole, unmasked row for all three).
 # 3. The warpers are steps 5-7 above with ``min_keep = 2``.  ``order="5.x"``: they act on lp, and ``acc = warped + rs_j``;
 #    ``order="4.31"``: they act on ``lp + rs_j`` and acc is that warped row; ``do_sample=False`` (penalised beam search): no warpers,
 #    ``acc = lp + rs_j``.  All these sums are fp32; removed entries are -inf.
@@ -201,21 +236,21 @@ def _check_order(order: str) -> bool:
     return order == "4.31"
 
 
-def _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed=None):
-    """Steps 1-2: the penalised, EOS-suppressed, constrained log-probabilities [R, vocab] fp32."""
+def _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed=None, banned=None):
+    """Steps 1-2: the penalised, n-gram-banned, EOS-suppressed, constrained log-probabilities [R, vocab] fp32."""
     x = logits.float()
     m = x.max(dim=-1, keepdim=True)[0]
     lse = m + torch.log(torch.exp((x - m).to(dtype)).sum(dim=-1, keepdim=True)).float()
-    return reference_scores(x - lse, history, repetition_penalty, eos_id if suppress_eos else None, allowed)
+    return reference_scores(x - lse, history, repetition_penalty, eos_id if suppress_eos else None, allowed, banned)
 
 
 def beam_reference_warp_input(logits: torch.Tensor, running_scores: torch.Tensor, history: History = None,
                               repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
                               order: str = "5.x", dtype: torch.dtype = torch.float32,
-                              allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                              allowed: Optional[torch.Tensor] = None, banned: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The fp32 rows [R, vocab] the warpers act on (ahead of the temperature): steps 1-2, under ``order="4.31"`` with the running
     score added."""
-    lp = _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed)
+    lp = _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed, banned)
     return lp + running_scores.reshape(-1, 1).float().to(lp.device) if _check_order(order) else lp
 
 
@@ -223,14 +258,15 @@ def beam_reference_rows(logits: torch.Tensor, running_scores: torch.Tensor, hist
                         repetition_penalty: float = 1.0, eos_id: Optional[int] = None, suppress_eos: bool = False,
                         do_sample: bool = True, temperature: Optional[float] = None, top_k: Optional[int] = None,
                         top_p: Optional[float] = None, order: str = "5.x", dtype: torch.dtype = torch.float32,
-                        allowed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        allowed: Optional[torch.Tensor] = None, banned: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Steps 1-3: acc [R, vocab] fp32 of R beam rows (bf16 or fp32-held bf16 logits [R, vocab], running scores [R] or [B, nb], one
     history per row), -inf for removed entries."""
     accumulated = _check_order(order)
     rs = running_scores.reshape(-1, 1).float().to(logits.device)
     if not do_sample:
-        return _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed) + rs
-    w = beam_reference_warp_input(logits, running_scores, history, repetition_penalty, eos_id, suppress_eos, order, dtype, allowed)
+        return _beam_processed(logits, history, repetition_penalty, eos_id, suppress_eos, dtype, allowed, banned) + rs
+    w = beam_reference_warp_input(logits, running_scores, history, repetition_penalty, eos_id, suppress_eos, order, dtype, allowed,
+                                  banned)
     s, kept = reference_warped(w, None, 1.0, None, temperature, top_k, top_p, BEAM_MIN_KEEP, dtype)
     return (s if accumulated else s + rs).masked_fill(~kept, -float("inf"))
 

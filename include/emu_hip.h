@@ -389,6 +389,18 @@ int emu_sample_trie_bf16(const void* logits, int ld, int rows, int vocab, const 
                          const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
                          int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, const emu_token_trie* trie, int32_t* node,
                          emu_stream_t s);
+/* emu_sample_bf16 with the library's no-repeat n-gram ban (NoRepeatNGramLogitsProcessor; Emu1's generate takes no_repeat_ngram_size
+ * and hands it to lm.generate, Emu1/models/modeling_emu.py:115,177); the specification is emu_amd/sampling.py::banned_ngram_mask.
+ * With h[0 .. nh) the row's history (nh = min(step, hist_rows) ids of hist, as for the penalty) an id v gets -inf iff
+ * nh + 1 >= ngram and the last ngram - 1 ids of the history occur earlier in it followed by v: some i in [0, nh - ngram + 1) has
+ * h[i .. i + ngram - 1) == h[nh - ngram + 1 .. nh) and h[i + ngram - 1] == v (ngram = 1: every id of the history).  A would-be
+ * banned id outside [0, vocab) is ignored.  The ban stands after the repetition penalty and ahead of the min-length suppress, the
+ * library's processor order.  ngram = 0 (or hist NULL): emu_sample_bf16's outputs bit for bit.  The caller keeps vocab large enough
+ * that the ban and the suppress together leave a finite score (at most nh + 1 ids go): a row without one has no defined draw.
+ * -22, nothing launched: ngram < 0, emu_sample_bf16's bounds. */
+int emu_sample_ngram_bf16(const void* logits, int ld, int rows, int vocab, const int32_t* hist, int hist_ld, int hist_rows,
+                          const int32_t* step_dev, const float* uniforms, int uni_ld, int uni_rows, const emu_sample_params* params,
+                          int32_t* unfinished, int32_t* out, float* probs_out, int ld_probs, int ngram, emu_stream_t s);
 /* The log-probability of a FORCED token under each row of logits (the specification is emu_amd/scoring.py): what the reference's LM
  * loss is made of (Emu1/models/modeling_llama.py:110-116: CrossEntropyLoss over shifted logits / labels) and what its `predict` ranks
  * candidate answers by (Emu1/models/prediction_mixin.py:36-131).  Per row, in fp32: m = max x, lse = m + log(sum exp(x - m)),
@@ -667,6 +679,13 @@ int emu_llama_sample_step_trie(emu_llama* m, int B, int32_t* cur_ids, int32_t* p
                                void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
                                int32_t* unfinished, const emu_sample_params* params, const emu_token_trie* trie, int32_t* node,
                                emu_stream_t s);
+/* emu_llama_sample_step with emu_sample_ngram_bf16 as its selection (lm.generate(num_beams=1, no_repeat_ngram_size=n),
+ * Emu1/models/modeling_emu.py:115,177): the history the ban reads is out_ids, the ids of steps 0 .. step - 1, as for the penalty.
+ * ngram is a scalar of the launch: a captured step holds the value it was captured with.  -22: ngram < 0, the parent's refusals. */
+int emu_llama_sample_step_ngram(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, int32_t* slot, const int32_t* kstart,
+                                int32_t* ctx_dev, int32_t* step_dev, int32_t* out_ids, int max_new, int ctx_upper, void* hidden,
+                                void* logits, int ld_logits, void* workspace, size_t ws_bytes, const float* uniforms,
+                                int32_t* unfinished, const emu_sample_params* params, int ngram, emu_stream_t s);
 /* emu_llama_greedy_step with the next token FORCED instead of chosen: one teacher-forced step of scoring a given continuation
  * (Emu1/models/prediction_mixin.py:36-131 ranks candidates by the LM loss of Emu1/models/modeling_llama.py:110-116; here the rows run
  * through the decode kernels, so the active weight stream -- bf16, e4m3, MXFP4 -- is the one that is scored).  With step = *step_dev:
@@ -713,6 +732,18 @@ int emu_beam_step_trie_bf16(const void* logits, long ld_prompt, long ld_beam, in
                             float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
                             unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
                             const emu_token_trie* trie, int32_t* node, emu_stream_t s);
+/* emu_beam_step_bf16 with the no-repeat n-gram ban (lm.generate(num_beams=N, no_repeat_ngram_size=n),
+ * Emu1/models/modeling_emu.py:115,177; the rule is emu_sample_ngram_bf16's, the history of beam j of prompt b being
+ * running_seq[b, j, :cur], which follows the beams).  Like the min-length suppress and the constraint the ban acts on the per-beam
+ * LOG-PROBABILITIES: the log-sum-exp is taken over the whole row, a banned id is -inf, and ties, those among -inf included, go to
+ * the lower flat index.  The caller keeps V >= L + 1 + 2 * nb so that every beam keeps 2N finite continuations.  ngram = 0:
+ * emu_beam_step_bf16's outputs bit for bit.  A step with cur >= L changes nothing.
+ * -22, nothing launched: ngram < 0, emu_beam_step_bf16's bounds. */
+int emu_beam_step_ngram_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int B, int nb, int L, int cur, const int32_t* cur_dev,
+                             int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences,
+                             float* running_scores, float* beam_scores, unsigned char* finished, int32_t* seq_len,
+                             unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
+                             int ngram, emu_stream_t s);
 
 /* One step of the library's beam-search multinomial sampling (lm.generate(num_beams=N, do_sample=True, temperature, top_k, top_p,
  * repetition_penalty): the call of the demo backend, demo/backend/pytorch_model/backend.py:179-186) and of penalised beam search
@@ -738,6 +769,16 @@ int emu_beam_sample_step_bf16(const void* logits, long ld_prompt, long ld_beam, 
                               unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace, size_t ws_bytes,
                               const emu_sample_params* params, int warp_accumulated, const float* uniforms, int uni_rows,
                               int32_t* draws_out, float* acc_out, long ld_acc, emu_stream_t s);
+/* emu_beam_sample_step_bf16 with the no-repeat n-gram ban (Emu1/models/modeling_emu.py:115,177; the rule is
+ * emu_sample_ngram_bf16's over running_seq[b, j, :cur]): lp[banned] = -inf after the repetition penalty and ahead of the EOS
+ * suppress, so the warpers and the draws run over what is left.  ngram = 0: emu_beam_sample_step_bf16's outputs bit for bit.
+ * -22, nothing launched or written: ngram < 0, emu_beam_sample_step_bf16's bounds. */
+int emu_beam_sample_step_ngram_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int B, int nb, int L, int cur,
+                                    const int32_t* cur_dev, int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq,
+                                    int32_t* sequences, float* running_scores, float* beam_scores, unsigned char* finished,
+                                    int32_t* seq_len, unsigned char* heuristic_open, int32_t* next_tok, long* beam_flat, void* workspace,
+                                    size_t ws_bytes, const emu_sample_params* params, int warp_accumulated, const float* uniforms,
+                                    int uni_rows, int32_t* draws_out, float* acc_out, long ld_acc, int ngram, emu_stream_t s);
 
 /* Loop state of EmuModel.generate_image (emu.py:92-153, KV-cached form: step j feeds project_up(project_down(h_{j-1}))) on the
  * device, so that {project_up, decoder step, final norm, project_down, this} is captured once and replayed n_query - 1 times:
