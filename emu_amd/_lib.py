@@ -74,6 +74,11 @@ class TokenTrieC(C.Structure):
     _fields_ = [("first", vp), ("tok", vp), ("child", vp), ("nodes", i32), ("edges", i32)]
 
 
+class Bf16PackSetC(C.Structure):
+    """emu_bf16_pack_set (include/emu_hip.h): one matrix's 13-bit packed set; rows == 0 = none."""
+    _fields_ = [("lo", vp), ("nib", vp), ("sign", vp), ("flags", vp), ("hb", i32), ("rows", i32)]
+
+
 SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
 CONTRASTIVE_MAX_K = 8      # EMU_CONTRASTIVE_MAX_K: candidates per prompt of the contrastive-search kernels
 CONTRASTIVE_CHUNK_ROWS = 8   # EMU_CONTRASTIVE_CHUNK_ROWS: context rows per workgroup of emu_contrastive_score's first launch
@@ -170,6 +175,13 @@ _PROTOS = {
     "emu_llama_use_fp4": (i32, [vp, i32]),
     "emu_llama_release_bf16": (i32, [vp]),
     "emu_llama_weight_kernel": (i32, [i32, i32, i32, i32, i32, i32]),
+    "emu_bf16_pack_rows": (i32, [i32, i32, i32, i32, i32]),
+    "emu_bf16_pack": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]),
+    "emu_linear_bf16pack": (i32, [vp, vp, C.POINTER(Bf16PackSetC), vp, vp, vp, i32, i32, i32, f32, i32, vp]),
+    "emu_llama_set_layer_bf16_pack": (i32, [vp, i32, C.POINTER(Bf16PackSetC)]),
+    "emu_llama_set_head_bf16_pack": (i32, [vp, C.POINTER(Bf16PackSetC), i32]),
+    "emu_llama_use_bf16_pack": (i32, [vp, i32]),
+    "emu_llama_pack_kernel": (i32, [i32] * 12),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),

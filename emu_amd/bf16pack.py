@@ -1,0 +1,119 @@
+"""The 13-bit lossless packing of bf16 weights that the one-row decode streams read (csrc/gemv_pack.hip), restated with torch on the
+CPU.  csrc/bf16_pack.h states the same layout for the device packer and the kernels; the GPU tests hold the two against each other
+byte for byte.
+
+A bf16 weight spends 8 of its 16 bits on an exponent and a weight matrix uses only a handful of binades, so the top 7 bits of the
+exponent field are stored as a 4-bit offset from a per-matrix base ``hb``.  A weight ``w`` (16 bits: s, e8, m7) becomes
+
+* the low byte ``w & 0xff`` (e8's lowest bit and the mantissa), verbatim,
+* the nibble ``((w >> 8) & 0x7f) - hb``, which must lie in 0..15,
+* the sign bit,
+
+13 bits instead of 16.  ``hb`` follows from the largest exponent field ``emax`` of the matrix's finite weights (``hb_rule``): the window
+is the 32 binades ``[2 hb, 2 hb + 31]`` whose top pair holds ``emax``.  A weight outside the window -- a zero or a tiny value beside
+large ones, Inf, NaN -- flags its row group (``flag_rule``); a flagged group is read from the bf16 matrix, so the planes carry no
+patches.
+
+Layout, for row groups of ``R`` (2 or 4: the rows one workgroup of the planned bf16 kernel owns) consecutive rows, the last group padded
+with zero weights, ``KV = K / 8`` 16-byte vectors per row, ``G = ceil(N / R)``:
+
+* ``lo``    uint8 [G, R/2, KV, 16]: unit (g, h, vi) = the 8 low bytes of vector vi of row 2h of the group, then those of row 2h + 1
+* ``nib``   uint8 [G, KV, R, 4]: byte b of row r = nibble of weight b | nibble of weight b + 4 << 4
+* ``sign``  uint8 [G, KV, R].  R = 2: byte r, bit j = sign of weight j of row r's vector vi.  R = 4: the bytes are one little-endian
+  32-bit word whose bit ``8 b + 7 - q`` holds the sign of weight ``4 hf + b`` of row ``r``, ``q = 2 r + hf`` (the four signs that belong
+  to one dword of high bytes sit one byte apart: one shift and one mask on the device)
+* ``flags`` int32 [ceil(G / 32)]: bit g % 32 of word g / 32 = row group g is flagged
+"""
+from __future__ import annotations
+
+from typing import Dict, Tuple
+
+import torch
+
+
+def _bits(w: torch.Tensor) -> torch.Tensor:
+    assert w.dtype == torch.bfloat16 and w.dim() == 2, (w.dtype, w.shape)
+    return w.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def hb_rule(emax: int) -> int:
+    """The exponent base of a matrix whose largest finite exponent field is ``emax``: top binade pair ``emax | 1``, 32 binades down."""
+    top = int(emax) | 1
+    return max(0, (top - 31) >> 1)
+
+
+def matrix_hb(w: torch.Tensor) -> int:
+    b = _bits(w)
+    e8 = (b >> 7) & 0xFF
+    finite = e8[e8 != 0xFF]
+    return hb_rule(int(finite.max()) if finite.numel() else 0)
+
+
+def flag_rule(w: torch.Tensor, hb: int) -> torch.Tensor:
+    """bool [N, K]: the weights that cannot be stored (nibble outside 0..15, or an Inf / NaN)."""
+    b = _bits(w)
+    d = ((b >> 8) & 0x7F) - hb
+    return (d < 0) | (d > 15) | (((b >> 7) & 0xFF) == 0xFF)
+
+
+def packed_bytes(N: int, K: int, rows: int) -> int:
+    """Bytes of the set of an [N, K] matrix: the three planes (13 bits per weight of the padded groups) and the flag words."""
+    G = (N + rows - 1) // rows
+    return G * rows * K * 13 // 8 + 4 * ((G + 31) // 32)
+
+
+def pack(w: torch.Tensor, rows: int) -> Dict[str, object]:
+    """bf16 [N, K] (K % 32 == 0) -> {"lo", "nib", "sign", "flags", "hb", "rows", "shape"} (see the module docstring)."""
+    assert rows in (2, 4)
+    N, K = w.shape
+    assert K >= 32 and K % 32 == 0, K
+    hb = matrix_hb(w)
+    G, KV = (N + rows - 1) // rows, K // 8
+    bad = flag_rule(w, hb)
+    b = torch.zeros(G * rows, K, dtype=torch.int32)
+    b[:N] = _bits(w)
+    badg = torch.zeros(G * rows, dtype=torch.bool)
+    badg[:N] = bad.any(dim=1)
+    v = b.view(G, rows, KV, 8)                                       # [g, r, vi, j]
+    lo = (v & 0xFF).view(G, rows // 2, 2, KV, 8).permute(0, 1, 3, 2, 4).reshape(G, rows // 2, KV, 16)
+    d = (((v >> 8) & 0x7F) - hb) & 15
+    nib = (d[..., :4] | (d[..., 4:] << 4)).permute(0, 2, 1, 3)       # [g, vi, r, b]
+    if rows == 2:
+        sign = ((v >> 15) << torch.arange(8, dtype=torch.int32)).sum(dim=-1).permute(0, 2, 1)
+    else:                                                            # [g, r, vi, hf, b] -> [g, vi, b, q = 2 r + hf], bit 7 - q of byte b
+        sq = (v >> 15).view(G, 4, KV, 2, 4).permute(0, 2, 4, 1, 3).reshape(G, KV, 4, 8)
+        sign = (sq << (7 - torch.arange(8, dtype=torch.int32))).sum(dim=-1)
+    fg = badg.view(G, rows).any(dim=1)
+    words = torch.zeros(((G + 31) // 32) * 32, dtype=torch.int64)
+    words[:G] = fg.to(torch.int64)
+    flags = (words.view(-1, 32) << torch.arange(32, dtype=torch.int64)).sum(dim=1)
+    flags = torch.where(flags >= 2 ** 31, flags - 2 ** 32, flags).to(torch.int32)
+    return {"lo": lo.to(torch.uint8).contiguous(), "nib": nib.to(torch.uint8).contiguous(), "sign": sign.to(torch.uint8).contiguous(),
+            "flags": flags, "hb": hb, "rows": rows, "shape": (N, K)}
+
+
+def flagged_groups(p: Dict[str, object]) -> torch.Tensor:
+    """bool [G]: the flagged row groups of a packed set."""
+    N, _ = p["shape"]
+    G = (N + p["rows"] - 1) // p["rows"]
+    f = p["flags"].to(torch.int64) & 0xFFFFFFFF
+    return (((f[:, None] >> torch.arange(32, dtype=torch.int64)) & 1).reshape(-1)[:G]).bool()
+
+
+def unpack(p: Dict[str, object]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(bf16 [N, K] decoded from the planes, bool [N]: the rows of flagged groups, whose decoded values are not to be used)."""
+    N, K = p["shape"]
+    R, hb = p["rows"], p["hb"]
+    G, KV = (N + R - 1) // R, K // 8
+    lo = p["lo"].to(torch.int32).view(G, R // 2, KV, 2, 8).permute(0, 1, 3, 2, 4).reshape(G, R, KV, 8)
+    nb = p["nib"].to(torch.int32).permute(0, 2, 1, 3)                # [g, r, vi, b]
+    d = torch.cat([nb & 15, nb >> 4], dim=-1)
+    if R == 2:
+        sg = (p["sign"].to(torch.int32).permute(0, 2, 1)[..., None] >> torch.arange(8, dtype=torch.int32)) & 1
+    else:                                                            # [g, vi, b, q] -> [g, r, vi, hf, b] -> [g, r, vi, j = 4 hf + b]
+        sq = (p["sign"].to(torch.int32)[..., None] >> (7 - torch.arange(8, dtype=torch.int32))) & 1
+        sg = sq.view(G, KV, 4, 4, 2).permute(0, 3, 1, 4, 2).reshape(G, 4, KV, 8)
+    bits = (sg << 15) | ((d + hb) << 8) | lo
+    bits = bits.reshape(G * R, K)[:N]
+    w = torch.where(bits >= 2 ** 15, bits - 2 ** 16, bits).to(torch.int16).view(torch.bfloat16)
+    return w, flagged_groups(p).repeat_interleave(R)[:N]

@@ -15,6 +15,7 @@
 
 #include "../../include/emu_hip.h"
 #include "kernels.h"
+#include "bf16_pack.h"
 
 struct emu_ctx {
     int device = 0, tp_rank = 0, tp_size = 1;
@@ -95,9 +96,11 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 }
 // ---- The weight sets of one matrix, any of them null: bf16; fp8 (e4m3) bytes + one fp32 scale per output row; MXFP4 element bytes
 // [N, K/2] + E8M0 block scales [N, K/32] at a row stride of fp4_scale_stride(K) -- and the kernel that reads them
+// -- and the 13-bit lossless packing of the bf16 matrix [pkN, pkK] (bf16_pack.h; pk.rows == 0: none)
 struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
-                 const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr; };
-enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5 };   // (ABI: emu_llama_weight_kernel)
+                 const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr;
+                 PackSet pk; int pkN = 0, pkK = 0; };
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel)
 // The one rule that picks a LLaMA projection's kernel, layers and head alike, from integers only: the modes as emu_llama_use_fp8 /
 // emu_llama_use_fp4 set them (never both), the call's rows, the shard's reduction widths.  1..2 rows: the weight streams with the
 // RMSNorm in front (gemv_fp4.hip, gemv.hip); 3..16: the MXFP4 matrix-core stream (gemv_fp4_thin.hip); 17 and more: the 4-bit GEMM
@@ -107,6 +110,16 @@ WeightKernel weight_kernel(int fp8_mode, int fp4_mode, int rows, int H, int HD, 
     if (rows <= 16) return fp4_mode >= 2 ? WeightKernel::Fp4Thin : WeightKernel::Bf16;
     if (fp4_mode == 3) return WeightKernel::Fp4Gemm;
     return fp8_mode == 2 && !(H & 127) && !(HD & 127) && !(Fl & 127) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
+}
+// The one further rule: a bf16 projection streams the 13-bit packed set (gemv_pack.hip) instead -- same bits, 13/16 of the bytes --
+// exactly when it is one activation row on the bf16 kernel, the stream is switched on, no fused-layer / decode-tail / L2-warm mode
+// is on, and the matrix has a set (pack_rows: its rows per group) for the form gemv_plan names for the shape.  Integers only.
+WeightKernel pack_kernel(WeightKernel k, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
+                         int norm, int epi, int tune) {
+    if (k != WeightKernel::Bf16 || rows != 1 || !pack_on || pack_rows <= 0 || fused_mode || tail_mode || warm_mask) return k;
+    GemvShape sh{};
+    sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm != 0; sh.w_aligned = sh.x_aligned = 1;
+    return gemv_pack_rows(gemv_plan(sh, tune), sh) == pack_rows ? WeightKernel::Bf16Pack : k;
 }
 // out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
 // pointers, which come from w (ldw in elements of the set k reads).  The MXFP4 kernels run under the GEMV profiler, the 4-bit bytes of
@@ -118,6 +131,17 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
         if (f8 ? !w.W8 || !w.s8 : !w.W) return -22;
         return linear(g.x, f8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps, g.epi, s,
                       f8 ? w.s8 : nullptr, splitk, splitk_floats, &g.warm);
+    }
+    if (k == WeightKernel::Bf16Pack) {               // the packed twin of the planned bf16 form, priced at the bytes it streams
+        if (!w.W || !w.pk.rows || g.M != 1 || g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
+        GemvShape sh{};
+        sh.M = 1; sh.N = g.N; sh.K = g.K; sh.ldx = sh.ldw = g.K; sh.epi = g.epi; sh.norm = g.norm_w != nullptr; sh.w_aligned = sh.x_aligned = 1;
+        const GemvPlan p = gemv_plan(sh, emu_gemm_tune_get());
+        if (gemv_pack_rows(p, sh) != w.pk.rows) return -22;
+        g.W = w.W;
+        const double bytes = (double)(pack_lo_bytes(g.N, g.K, w.pk.rows) + pack_nib_bytes(g.N, g.K, w.pk.rows) + pack_sign_bytes(g.N, g.K, w.pk.rows) +
+                                      4 * pack_flag_words(g.N, w.pk.rows));
+        return gemv_profiled(bytes, s, [&] { return launch_gemv_pack(g, w.pk, p.form, s); });
     }
     if (k == WeightKernel::Fp8Gemm || !w.W4 || !w.s4) return -22;
     g.W = B(w.W4); g.w4scale = w.s4;
@@ -184,6 +208,30 @@ extern "C" {
 int emu_version(void) { return 6; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local) {
     return (int)weight_kernel(fp8_mode, fp4_mode, rows, hidden, heads_dim_local, ffn_local);
+}
+
+int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
+                          int norm, int epi, int tune) {
+    if (kernel < 0 || kernel > (int)WeightKernel::Bf16Pack) return -22;
+    return (int)pack_kernel((WeightKernel)kernel, rows, pack_rows, pack_on, fused_mode, tail_mode, warm_mask, N, K, norm, epi, tune);
+}
+int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune) {
+    if (N < 1 || K < 8) return 0;
+    GemvShape sh{};
+    sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm != 0; sh.w_aligned = sh.x_aligned = 1;
+    return gemv_pack_rows(gemv_plan(sh, tune), sh);
+}
+int emu_bf16_pack(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* sign, void* flags, int* hb_out,
+                  emu_stream_t s) {
+    return launch_bf16_pack(B(w_bf16), ldw, N, K, rows, lo, nib, sign, reinterpret_cast<uint32_t*>(flags), hb_out, S(s));
+}
+int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, const void* norm_w, void* C, int N,
+                        int K, int form, float eps, int epi, emu_stream_t s) {
+    if (!A || !W || !set || !C) return -22;
+    GemvArgs g{B(A), B(W), B(norm_w), nullptr, B(res), B(C), 1, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, eps, epi, nullptr};
+    PackSet p;
+    p.lo = set->lo; p.nib = set->nib; p.sign = set->sign; p.flags = reinterpret_cast<const uint32_t*>(set->flags); p.hb = set->hb; p.rows = set->rows;
+    return launch_gemv_pack(g, p, form, S(s));
 }
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
@@ -625,6 +673,7 @@ struct emu_llama {
     bool fp4_wide = false;
     bool fp4_all = false;
     bool bf16_released = false;
+    bool bf16_pack = false;        // emu_llama_use_bf16_pack: one-row bf16 projections stream their 13-bit packed sets (pack_kernel)
     // the kernel of a projection of `rows` rows, layers and head alike: the modes above through weight_kernel
     WeightKernel kernel_for(int rows) const {
         return weight_kernel(fp8_prefill ? 2 : fp8_decode, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
@@ -864,6 +913,8 @@ struct LlamaCall {
             if (gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
             k = WeightKernel::Bf16;                      // (Fp8Gemm: a layer without fp8 weights runs bf16)
         }
+        k = pack_kernel(k, rows, W.pkN == N && W.pkK == K ? W.pk.rows : 0, m->bf16_pack, m->decode_fused, plan.decode_tail, plan.warm | (int)warm.ntouch,
+                        N, K, gain_in != nullptr, epi, emu_gemm_tune_get());
         GemvArgs g = packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi);
         if (warm.ntouch && k == WeightKernel::Bf16) { g.warm = warm; ++m->warm_launches; }
         return linear_w(k, W, g, s, w.splitk, w.splitk_floats);
@@ -1342,12 +1393,47 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
     m->fp4_all = enable == 3;
     return 0;
 }
+static int set_pack(emu_llama* m, Weights& w, const emu_bf16_pack_set& s, int N, int K, const char* what) {
+    if (!s.rows) { w.pk = PackSet{}; w.pkN = w.pkK = 0; return 0; }       // this matrix stays on bf16
+    if (!s.lo || !s.nib || !s.sign || !s.flags || (s.rows != 2 && s.rows != 4) || s.hb < 0 || s.hb > 112 || (K & 31)) return fail(m->ctx, -22, what);
+    w.pk.lo = s.lo; w.pk.nib = s.nib; w.pk.sign = s.sign; w.pk.flags = reinterpret_cast<const uint32_t*>(s.flags); w.pk.hb = s.hb; w.pk.rows = s.rows;
+    w.pkN = N; w.pkK = K;
+    return 0;
+}
+int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_set* sets4) {
+    if (!m || !sets4 || layer < 0 || layer >= m->cfg.layers) return -22;
+    if (m->bf16_released) return fail(m->ctx, -22, "emu_llama_set_layer_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    const emu_llama_cfg& c = m->cfg;
+    const int H = c.hidden, HD = c.heads_local * c.head_dim, Fl = c.ffn_local;
+    emu_llama::Layer& L = m->layers[layer];
+    const char* what = "emu_llama_set_layer_bf16_pack: a set needs its four pointers, rows 2 or 4, hb 0..112 and K % 32 == 0";
+    if (int st = set_pack(m, L.qkv, sets4[0], 3 * HD, H, what)) return st;
+    if (int st = set_pack(m, L.o, sets4[1], H, HD, what)) return st;
+    if (int st = set_pack(m, L.gu, sets4[2], 2 * Fl, H, what)) return st;
+    return set_pack(m, L.down, sets4[3], H, Fl, what);
+}
+int emu_llama_set_head_bf16_pack(emu_llama* m, const emu_bf16_pack_set* set, int rows_n) {
+    if (!m || !set || rows_n < 1) return -22;
+    if (m->bf16_released) return fail(m->ctx, -22, "emu_llama_set_head_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    return set_pack(m, m->head, *set, rows_n, m->cfg.hidden, "emu_llama_set_head_bf16_pack: a set needs its four pointers, rows 2 or 4, hb 0..112 and K % 32 == 0");
+}
+int emu_llama_use_bf16_pack(emu_llama* m, int on) {
+    if (!m) return -22;
+    if (on && m->bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack: the bf16 weights were released (emu_llama_release_bf16)");
+    m->bf16_pack = on != 0;
+    return 0;
+}
 int emu_llama_release_bf16(emu_llama* m) {
     if (!m) return -22;
     if (!m->fp4_all) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
     if (m->decode_fused) return fail(m->ctx, -22, "emu_llama_release_bf16: the fused decode modes read the bf16 weights (emu_llama_set_decode_fused(m, 0, 0) first)");
-    for (auto& l : m->layers) l.qkv.W = l.o.W = l.gu.W = l.down.W = nullptr;
+    for (auto& l : m->layers) {
+        l.qkv.W = l.o.W = l.gu.W = l.down.W = nullptr;
+        l.qkv.pk = l.o.pk = l.gu.pk = l.down.pk = PackSet{};       // (a flagged row group reads the bf16 rows: the sets go with them)
+    }
     m->head.W = nullptr;
+    m->head.pk = PackSet{};
+    m->bf16_pack = false;
     m->dl_dirty = true;
     m->bf16_released = true;
     return 0;
@@ -1612,6 +1698,8 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
     if (k == WeightKernel::Fp8Gemm || (k == WeightKernel::Fp8Rows && !m->head.W8) ||
         (k == WeightKernel::Fp4Thin && !ws_fits && !m->bf16_released)) k = WeightKernel::Bf16;
     const bool fused = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp8Rows || (k == WeightKernel::Bf16 && (M == 1 || (M <= 8 && !ws_fits)));
+    if (fused) k = pack_kernel(k, M, m->head.pkN == N && m->head.pkK == H ? m->head.pk.rows : 0, m->bf16_pack, m->decode_fused, m->decode_tail, m->l2_warm,
+                               N, H, 1, EPI_NONE, emu_gemm_tune_get());
     if (!fused) {
         if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
         TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));

@@ -1,0 +1,306 @@
+// One-row decode weight streams over the 13-bit lossless bf16 format (bf16_pack.h): the packed twins of the bf16 forms the headline
+// decode step runs (gemv.hip):
+//   head form, fused RMSNorm      gemv_kernel<4, 1, true, EPI, -1>       qkv, gate/up (SwiGLU), lm_head
+//   preload form                  gemv_kernel<2, 1, false, EPI, 4>       o_proj
+//   single round trip             gemv_rt_kernel<2, 9, false, EPI, false> down_proj
+// Same rows per workgroup, same column-to-thread partition, same order of the v_dot2c chain, same wave / LDS reductions, same epilogue
+// rounding points: only the fetch and the in-register decode in front of bf16_dot2 differ, so the outputs are the bf16 kernels' bit for
+// bit.  13/16 of the HBM bytes.  A workgroup whose row group is flagged (a weight outside the matrix's 32-binade window) streams the
+// bf16 rows through the same registers instead; the branch is workgroup-uniform.  The packed loads of the first trip / the preload
+// are requested before the flag word is back, so the flag costs an unflagged workgroup no latency.  No workgroup waits for another.
+#include "common.h"
+#include "kernels.h"
+#include "bf16_pack.h"
+
+namespace {
+
+// the registers of one fetch: R 16-byte bf16 vectors, or (packed) R/2 low units, R nibble dwords, the sign bytes
+template <int R>
+struct PackRaw { uint32_t d[4 * R]; };
+
+template <int R>
+struct PackPtrs {
+    const u32x4* lo; const uint32_t* nib; const uint8_t* sign;      // at the row group
+    const bf16_t* wrow[R];                                           // the bf16 rows (tail rows clamped)
+    int KV;
+    uint32_t hb4;
+};
+
+template <int R>
+__device__ __forceinline__ PackPtrs<R> pack_ptrs(const GemvArgs& a, const PackSet& p, int g) {
+    PackPtrs<R> q;
+    q.KV = a.K >> 3;
+    q.lo = reinterpret_cast<const u32x4*>(p.lo) + (size_t)g * (R / 2) * q.KV;
+    q.nib = reinterpret_cast<const uint32_t*>(p.nib) + (size_t)g * q.KV * R;
+    q.sign = reinterpret_cast<const uint8_t*>(p.sign) + (size_t)g * q.KV * R;
+    q.hb4 = (uint32_t)p.hb * 0x01010101u;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        int n = g * R + r;
+        n = n < a.N ? n : a.N - 1;
+        q.wrow[r] = a.W + (size_t)n * a.ldw;
+    }
+    return q;
+}
+
+template <int R>
+__device__ __forceinline__ void fetch_packed(const PackPtrs<R>& q, int vi, PackRaw<R>& w) {
+#pragma unroll
+    for (int h = 0; h < R / 2; ++h) {
+        const u32x4 v = ld_stream(q.lo + (size_t)h * q.KV + vi);
+        w.d[4 * h] = v.x; w.d[4 * h + 1] = v.y; w.d[4 * h + 2] = v.z; w.d[4 * h + 3] = v.w;
+    }
+    if constexpr (R == 4) {
+        const u32x4 n = ld_stream(reinterpret_cast<const u32x4*>(q.nib) + vi);
+        w.d[8] = n.x; w.d[9] = n.y; w.d[10] = n.z; w.d[11] = n.w;
+        w.d[12] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(q.sign) + vi);
+    } else {
+        const u32x2 n = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(q.nib) + vi);
+        w.d[4] = n.x; w.d[5] = n.y;
+        w.d[6] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(q.sign) + vi);
+    }
+}
+template <int R>
+__device__ __forceinline__ void fetch_bf16(const PackPtrs<R>& q, int vi, PackRaw<R>& w) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const u32x4 v = ld_stream(reinterpret_cast<const u32x4*>(q.wrow[r] + vi * 8));
+        w.d[4 * r] = v.x; w.d[4 * r + 1] = v.y; w.d[4 * r + 2] = v.z; w.d[4 * r + 3] = v.w;
+    }
+}
+// acc[r] += row r . xp, the bf16 kernels' chain: x, y, z, w of the row's vector in order
+template <int R>
+__device__ __forceinline__ void pack_dots(const PackPtrs<R>& q, bool flagged, const PackRaw<R>& w, const u32x4& xp, float (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t v[4];
+        if (flagged) {
+            v[0] = w.d[4 * r]; v[1] = w.d[4 * r + 1]; v[2] = w.d[4 * r + 2]; v[3] = w.d[4 * r + 3];
+        } else {
+            pack_decode_row<R>(w.d[2 * r], w.d[2 * r + 1], w.d[2 * R + r], w.d[3 * R], r, q.hb4, v);
+        }
+        float t = acc[r];
+        t = bf16_dot2(v[0], xp.x, t);
+        t = bf16_dot2(v[1], xp.y, t);
+        t = bf16_dot2(v[2], xp.z, t);
+        t = bf16_dot2(v[3], xp.w, t);
+        acc[r] = t;
+    }
+}
+
+// the one-row epilogue of gemv_kernel / gemv_rt_kernel (M == 1): fin[r] = the fp32 sums of the workgroup's rows
+template <int R, int EPI>
+__device__ __forceinline__ void pack_epilogue(const GemvArgs& a, const float* fin, int n0, int tid) {
+    if constexpr (EPI == EPI_SWIGLU) {
+        if (tid < R / 2) {
+            const int n = n0 + 2 * tid;
+            if (n + 1 < a.N) {
+                const float gt = bfround(fin[2 * tid] + (a.bias ? bf2f(a.bias[n]) : 0.f));
+                const float up = bfround(fin[2 * tid + 1] + (a.bias ? bf2f(a.bias[n + 1]) : 0.f));
+                const float act = bfround(silu(gt));
+                a.out[n >> 1] = f2bf(act * up);
+            }
+        }
+    } else {
+        if (tid < R) {
+            const int n = n0 + tid;
+            if (n < a.N) {
+                float v = fin[tid];
+                if (a.bias) v += bf2f(a.bias[n]);
+                v = bfround(v);
+                if constexpr (EPI == EPI_RESID) v = v + bf2f(a.res[n]);
+                a.out[n] = f2bf(v);
+            }
+        }
+    }
+}
+
+template <int R>
+__device__ __forceinline__ void pack_reduce(float (&acc)[R], float (*red)[R], float* fin, int tid) {
+    const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const float v = wave_sum(acc[r]);
+        if (lane == 0) red[wave][r] = v;
+    }
+    __syncthreads();
+    if (tid < R) fin[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    __syncthreads();
+}
+
+// ---- head form (gemv_kernel<4, 1, true, EPI, -1>): x, the gain and the first trip are requested before the RMSNorm statistics are
+// reduced through a raw s_barrier; trips 1..3 stream behind it through two register sets
+template <int EPI>
+__global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, const PackSet p) {
+    constexpr int R = 4;
+    __shared__ float red[4][R];
+    __shared__ float fin[R];
+    __shared__ float ssp[4];
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int KV = a.K >> 3;
+    const int n0 = blockIdx.x * R;
+    const uint32_t fw = p.flags[blockIdx.x >> 5];
+    const PackPtrs<R> q = pack_ptrs<R>(a, p, blockIdx.x);
+
+    u32x4 hx[4], hg[4];
+    PackRaw<R> hw, w1;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int vi = tid + 256 * c;
+        const int vc = vi < KV ? vi : KV - 1;
+        hx[c] = vi < KV ? ld16(a.x + vi * 8) : u32x4{0u, 0u, 0u, 0u};
+        hg[c] = ld16(a.norm_w + vc * 8);
+    }
+    const int v0 = tid < KV ? tid : KV - 1;                            // short rows (K < 2048): clamped, against a zero operand
+    fetch_packed<R>(q, v0, hw);
+    const bool flagged = (fw >> (blockIdx.x & 31)) & 1u;
+    if (flagged) fetch_bf16<R>(q, v0, hw);
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float f[8];
+        unpack8(hx[c], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) *reinterpret_cast<volatile float*>(&ssp[wave]) = ss;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const volatile float* sp = ssp;
+    const float rinv = rsqrtf((sp[0] + sp[1] + sp[2] + sp[3]) / (float)a.K + a.eps);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {                                      // hx <- bf16(g * bf16(x * rinv)), the dot2 operand
+        float xf[8], g[8];
+        unpack8(hx[c], xf);
+        unpack8(hg[c], g);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xf[j] = g[j] * bfround(xf[j] * rinv);
+        hx[c] = pack8(xf);
+    }
+
+    float acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.f;
+    auto fetch = [&](PackRaw<R>& w, int c) {
+        const int vi = tid + 256 * c;
+        if (vi < KV) {
+            if (flagged) fetch_bf16<R>(q, vi, w); else fetch_packed<R>(q, vi, w);
+        }
+    };
+    fetch(w1, 1);
+    pack_dots<R>(q, flagged, hw, hx[0], acc);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(hw, 2);
+    if (tid + 256 < KV) pack_dots<R>(q, flagged, w1, hx[1], acc);
+    __builtin_amdgcn_sched_barrier(0);
+    fetch(w1, 3);
+    if (tid + 512 < KV) pack_dots<R>(q, flagged, hw, hx[2], acc);
+    if (tid + 768 < KV) pack_dots<R>(q, flagged, w1, hx[3], acc);
+
+    pack_reduce<R>(acc, red, fin, tid);
+    pack_epilogue<R, EPI>(a, fin, n0, tid);
+}
+
+// ---- the two plain forms of two rows per workgroup, every load requested up front.  CLAMP: the preload form (gemv_kernel<2, 1, false,
+// EPI, 4>: loads past the row clamped, their trips skipped); else the single round trip (gemv_rt_kernel<2, 9, false, EPI, false>:
+// loads past the row not issued, zero registers against a zero activation)
+template <int KIT, bool CLAMP, int EPI>
+__global__ __launch_bounds__(256) void gemv_pack_rows2_kernel(const GemvArgs a, const PackSet p) {
+    constexpr int R = 2;
+    __shared__ float red[4][R];
+    __shared__ float fin[R];
+    const int tid = threadIdx.x;
+    const int KV = a.K >> 3;
+    const int n0 = blockIdx.x * R;
+    const uint32_t fw = p.flags[blockIdx.x >> 5];
+    const PackPtrs<R> q = pack_ptrs<R>(a, p, blockIdx.x);
+
+    u32x4 xv[KIT];
+    PackRaw<R> wv[KIT];
+#pragma unroll
+    for (int it = 0; it < KIT; ++it) {
+        const int vi = tid + 256 * it;
+        xv[it] = vi < KV ? ld16(a.x + vi * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int it = 0; it < KIT; ++it) {
+        const int vi = tid + 256 * it;
+        if constexpr (CLAMP) {
+            fetch_packed<R>(q, vi < KV ? vi : KV - 1, wv[it]);
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4 * R; ++d) wv[it].d[d] = 0u;
+            if (vi < KV) fetch_packed<R>(q, vi, wv[it]);
+        }
+    }
+    const bool flagged = (fw >> (blockIdx.x & 31)) & 1u;
+    if (flagged) {
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            const int vi = tid + 256 * it;
+            if constexpr (CLAMP) {
+                fetch_bf16<R>(q, vi < KV ? vi : KV - 1, wv[it]);
+            } else {
+#pragma unroll
+                for (int d = 0; d < 4 * R; ++d) wv[it].d[d] = 0u;
+                if (vi < KV) fetch_bf16<R>(q, vi, wv[it]);
+            }
+        }
+    }
+
+    float acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int it = 0; it < KIT; ++it) {
+        if (!CLAMP || tid + 256 * it < KV) pack_dots<R>(q, flagged, wv[it], xv[it], acc);
+    }
+
+    pack_reduce<R>(acc, red, fin, tid);
+    pack_epilogue<R, EPI>(a, fin, n0, tid);
+}
+
+}  // namespace
+
+// the forms the packed stream has a twin for, from the bf16 plan of the shape: rows per workgroup (the set's R), or 0
+int gemv_pack_rows(const GemvPlan& p, const GemvShape& sh) {
+    if (p.status || sh.M != 1 || sh.fp8 || sh.fp4 || (sh.K & 31) || sh.K < 32) return 0;
+    if (sh.epi != EPI_NONE && sh.epi != EPI_RESID && sh.epi != EPI_SWIGLU) return 0;
+    if (p.family == GEMV_FAM_BLOCK && p.form == GEMV_FORM_HEAD && p.rows == 4 && p.mb == 1 && sh.norm && sh.epi != EPI_RESID) return 4;
+    if (p.family == GEMV_FAM_BLOCK && p.form == GEMV_FORM_PRELOAD && p.rows == 2 && p.mb == 1 && !sh.norm && sh.epi != EPI_SWIGLU) return 2;
+    if (p.family == GEMV_FAM_RT && p.rows == 2 && p.trips == 9 && !sh.norm && sh.epi != EPI_SWIGLU) return 2;
+    return 0;
+}
+
+int launch_gemv_pack(const GemvArgs& a, const PackSet& p, int form, hipStream_t s) {
+    if (!a.x || !a.W || !a.out || !p.lo || !p.nib || !p.sign || !p.flags || a.M != 1 || a.N < 1 || a.K < 32 || (a.K & 31)) return -22;
+    if (a.ldw < a.K || (a.ldw & 7) || p.hb < 0 || p.hb > 112 || (a.epi == EPI_RESID && !a.res)) return -22;
+    const int KV = a.K >> 3;
+#define EMU_PACK_LAUNCH(KERNEL, R)                                                                                   \
+    hipLaunchKernelGGL(KERNEL, dim3((a.N + R - 1) / R), dim3(256), 0, s, a, p);                                      \
+    EMU_CHECK_LAUNCH();                                                                                              \
+    return 0;
+    if (form == GEMV_FORM_HEAD) {
+        if (p.rows != 4 || !a.norm_w || KV > 1024) return -22;
+        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH(gemv_pack_head_kernel<EPI_NONE>, 4) }
+        if (a.epi == EPI_SWIGLU && !(a.N & 1)) { EMU_PACK_LAUNCH(gemv_pack_head_kernel<EPI_SWIGLU>, 4) }
+        return -22;
+    }
+    if (p.rows != 2 || a.norm_w) return -22;
+    if (form == GEMV_FORM_PRELOAD) {
+        if (KV > 1024) return -22;
+        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<4, true, EPI_NONE>), 2) }
+        if (a.epi == EPI_RESID) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<4, true, EPI_RESID>), 2) }
+        return -22;
+    }
+    if (form == GEMV_FORM_RT) {
+        if (KV > 9 * 256) return -22;
+        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<9, false, EPI_NONE>), 2) }
+        if (a.epi == EPI_RESID) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<9, false, EPI_RESID>), 2) }
+        return -22;
+    }
+#undef EMU_PACK_LAUNCH
+    return -22;
+}

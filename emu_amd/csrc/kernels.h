@@ -60,6 +60,15 @@ int launch_gemv_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
 // emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the call waits for its own result)
 int launch_quant_mxfp4_rows(const bf16_t* w, int ldw, uint8_t* q, int ldq, uint8_t* scales, int lds, int N, int K, hipStream_t s);
 void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
+// the 13-bit lossless bf16 weight format (bf16_pack.h).  launch_bf16_pack (bf16_pack.hip): bf16 [N, ldw] -> the planes and the flag
+// bitmap for row groups of `rows` (2 / 4) rows, K % 32 == 0; *hb_out = the matrix's exponent base (the call waits for its own result).
+// gemv_pack_rows: the set's rows per group if the bf16 plan of the one-row shape is a form the packed stream has a twin for (head
+// form of 4 rows, preload form of 2, single round trip of 2 x 9 trips), else 0.  launch_gemv_pack (gemv_pack.hip): that twin; a.W = the
+// bf16 matrix (flagged row groups read it), form = the plan's GemvForm; bit-identical to launch_gemv on the bf16 matrix
+int launch_bf16_pack(const bf16_t* W, int ldw, int N, int K, int rows, void* lo, void* nib, void* sign, uint32_t* flags, int* hb_out,
+                     hipStream_t s);
+int gemv_pack_rows(const GemvPlan& p, const GemvShape& sh);
+int launch_gemv_pack(const GemvArgs& a, const struct PackSet& p, int form, hipStream_t s);
 // o_proj of a tensor-parallel shard's one-row step with the decode attention's split merge in its prologue (gemv_merge.hip):
 // x = merge of the live splits in decode_fused_kernel's workspace (batch row 0), out = epi(x W^T [+ res]); bit-identical to
 // decode_fused_combine_kernel followed by the wave-form GEMV.  K = H * 128 <= 1024, nsplit <= 8, N >= 1024 (gemv_merge_ok).

@@ -9,12 +9,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
+import time
 from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from . import mxfp4, ops
-from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
+from . import bf16pack, mxfp4, ops
+from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
@@ -334,6 +336,7 @@ class LlamaEngine:
                 self.head_rows = (r0, r1)
             else:
                 self.lm_head = self._dev(t)
+            self._drop_bf16_pack(["lm_head"])                  # (a reloaded matrix: its packed set is stale)
         elif name.startswith("model.layers."):
             rest = name[len("model.layers."):]
             idx, key = rest.split(".", 1)
@@ -352,6 +355,8 @@ class LlamaEngine:
             if self.head_rows is not None:
                 check(lib().emu_llama_set_head_shard(self.handle, self.head_rows[0], self.head_rows[1] - self.head_rows[0]),
                       "emu_llama_set_head_shard", self.ctx.handle)
+        if self.ready:
+            self._auto_pack_bf16()
         return True
 
     def _pack_layer(self, i: int, d: Dict[str, torch.Tensor]) -> None:
@@ -359,6 +364,7 @@ class LlamaEngine:
         p = self.plan.pack_layer(g("self_attn.q_proj.weight"), g("self_attn.k_proj.weight"),
                                  g("self_attn.v_proj.weight"), g("self_attn.o_proj.weight"),
                                  g("mlp.gate_proj.weight"), g("mlp.up_proj.weight"), g("mlp.down_proj.weight"))
+        self._drop_bf16_pack([f"{i}.{k}" for k in self._PACK_KINDS])       # (a reloaded layer: its packed sets are stale)
         p["ln1"] = self._dev(d["input_layernorm.weight"])
         p["ln2"] = self._dev(d["post_attention_layernorm.weight"])
         for k, v in p.items():
@@ -387,8 +393,99 @@ class LlamaEngine:
         else:
             b = 1 if getattr(self, "fp8_decode", False) else 2
             size = lambda v: v.numel() * b
-        per = sum(size(v) for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
-        return per + (size(self.lm_head) if self.lm_head is not None else 0)
+        # the 13-bit packed stream (use_bf16_pack): a matrix that has a set streams its planes and flag words instead
+        pk = getattr(self, "_pack", {}) if getattr(self, "bf16_pack_on", False) and b == 2 and not getattr(self, "fp4_decode", False) else {}
+        one = lambda k, v: bf16pack.packed_bytes(v.shape[0], v.shape[1], pk[k]["rows"]) if k in pk else size(v)
+        per = sum(one(k, v) for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
+        return per + (one("lm_head", self.lm_head) if self.lm_head is not None else 0)
+
+    # ------------------------------------------------------------------ the 13-bit lossless bf16 decode stream (on by default)
+    _PACK_KINDS = {"wqkv": (1, ops.EPI_NONE), "wo": (0, ops.EPI_RESID), "wgu": (1, ops.EPI_SWIGLU), "wdown": (0, ops.EPI_RESID)}
+
+    def _pack_keys(self):
+        return [f"{i}.{k}" for i in range(self.cfg.num_hidden_layers) for k in self._PACK_KINDS] + ["lm_head"]
+
+    def _pack_rows(self, key: str, tune: int, head_form: bool) -> int:
+        """Rows per group of the packed set of ``key`` (the form the planner names for its one-row stream), 0 = the matrix stays bf16.
+        The head form's twin (4 rows, fused RMSNorm: qkv, gate/up, lm_head) measured SLOWER than its bf16 kernel on MI355X
+        (profiles/bf16_pack.md), so those matrices get a set only when ``head_form`` asks for it."""
+        w = self.lm_head if key == "lm_head" else self._keep[key]
+        norm, epi = (1, ops.EPI_NONE) if key == "lm_head" else self._PACK_KINDS[key.split(".")[1]]
+        N, K = w.shape
+        rows = 0 if K % 32 else int(lib().emu_bf16_pack_rows(N, K, norm, epi, tune))
+        return rows if rows == 2 or head_form else 0
+
+    def _register_bf16_pack(self, keys) -> None:
+        pk = self.__dict__.setdefault("_pack", {})
+        for i in sorted({int(k.split(".")[0]) for k in keys if k != "lm_head"}):
+            sets = (Bf16PackSetC * 4)(*[ops.pack_set_c(pk.get(f"{i}.{k}")) for k in self._PACK_KINDS])
+            check(lib().emu_llama_set_layer_bf16_pack(self.handle, i, sets), "emu_llama_set_layer_bf16_pack", self.ctx.handle)
+        if "lm_head" in keys and self.lm_head is not None:
+            one = ops.pack_set_c(pk.get("lm_head"))
+            check(lib().emu_llama_set_head_bf16_pack(self.handle, C.byref(one), int(self.lm_head.shape[0])), "emu_llama_set_head_bf16_pack",
+                  self.ctx.handle)
+
+    def _drop_bf16_pack(self, keys) -> None:
+        pk = getattr(self, "_pack", None)
+        hit = [k for k in keys if pk and k in pk]
+        if hit:
+            for k in hit:
+                del pk[k]
+            self._register_bf16_pack(hit)
+            self._mode_changed()
+
+    def pack_bf16(self, tune: int = 0, head_form: bool = False) -> Tuple[int, int]:
+        """Build and register the 13-bit packed set (``emu_amd.bf16pack``) of every matrix whose one-row stream has a packed twin and
+        that has none yet; ``tune``: the emu_gemm_tune mask the streams will run under; ``head_form``: also the matrices behind a fused
+        RMSNorm (``_pack_rows``).  Returns (matrices packed, bytes of their sets).  The bf16 matrices stay: prefill, steps of more
+        rows and flagged row groups read them."""
+        if not self.ready:
+            raise RuntimeError("pack_bf16: load all weights first")
+        if self.bf16_released:
+            raise RuntimeError("pack_bf16: the bf16 weights were released (release_bf16); flagged row groups read them")
+        pk = self.__dict__.setdefault("_pack", {})
+        new, nbytes = [], 0
+        for key in self._pack_keys():
+            rows = 0 if key in pk else self._pack_rows(key, tune, head_form)
+            if rows:
+                pk[key] = ops.pack_bf16_rows(self.lm_head if key == "lm_head" else self._keep[key], rows)
+                new.append(key)
+                nbytes += bf16pack.packed_bytes(*pk[key]["shape"], rows)
+        if new:
+            self._register_bf16_pack(new)
+            self._mode_changed()
+        return len(new), nbytes
+
+    def use_bf16_pack(self, enable: bool = True) -> None:
+        """One-row decode steps on the bf16 kernels stream the packed sets (same bits, 13/16 of the bytes) or, off, the bf16 matrices
+        (invalidates captured decode graphs).  Only matrices that ``pack_bf16`` gave a set are affected."""
+        check(lib().emu_llama_use_bf16_pack(self.handle, 1 if enable else 0), "emu_llama_use_bf16_pack", self.ctx.handle)
+        self.bf16_pack_on = bool(enable)
+        self._mode_changed()
+
+    def _auto_pack_bf16(self) -> None:
+        """The default: when the engine is ready, pack and switch the stream on -- unless EMU_BF16_PACK=0, the library predates the
+        stream (a tools A/B run against an older build), no matrix has a packed twin (small models, tensor-parallel shards), or the
+        sets would take more than half of the free device memory (the KV cache and the workspaces need the rest).  EMU_BF16_PACK=all
+        packs the head-form matrices too (A/B aid)."""
+        if os.environ.get("EMU_BF16_PACK", "1") == "0" or self.bf16_released or not hasattr(lib(), "emu_llama_use_bf16_pack"):
+            return
+        pk = getattr(self, "_pack", {})
+        head_form = os.environ.get("EMU_BF16_PACK") == "all"
+        todo = [(k, self._pack_rows(k, 0, head_form)) for k in self._pack_keys() if k not in pk]
+        need = sum(bf16pack.packed_bytes(*(self.lm_head if k == "lm_head" else self._keep[k]).shape, r) for k, r in todo if r)
+        if not need:
+            return
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if 2 * need > free:
+            print(f"emu_amd: bf16 pack stream off: its sets need {need / 2**30:.1f} GiB, {free / 2**30:.1f} GiB are free", file=sys.stderr)
+            return
+        t0 = time.time()
+        n, nbytes = self.pack_bf16(head_form=head_form)
+        torch.cuda.synchronize(self.device)
+        self.use_bf16_pack(True)
+        print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s",
+              file=sys.stderr)
 
     # ------------------------------------------------------------------ optional fp8 decode stream
     def quantize_fp8(self) -> None:
@@ -535,6 +632,8 @@ class LlamaEngine:
         for key in [k for k in self._keep if k.split(".")[1] in self._FP4_KINDS]:
             del self._keep[key]
         self.lm_head = None
+        self.__dict__.pop("_pack", None)                     # (the library dropped the sets with the bf16 rows)
+        self.bf16_pack_on = False
         self._mode_changed()
 
     def fp4_dequantized(self, key: str) -> torch.Tensor:

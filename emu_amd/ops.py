@@ -128,6 +128,47 @@ def quantize_mxfp4_rows(w):
     return q, sc
 
 
+FORM_HEAD, FORM_PRELOAD, FORM_RT = 1, 2, 3          # GemvForm of the bf16 plan (include/emu_hip.h: emu_gemv_geometry_query)
+
+
+def pack_bf16_rows(w, rows: int):
+    """The 13-bit lossless packing of a bf16 weight [N, K] (K % 32 == 0) on the device, for row groups of ``rows`` (2 or 4) rows:
+    the dict of ``emu_amd.bf16pack.pack`` (planes and flags on the device), byte for byte; see emu_bf16_pack."""
+    _req(w, "w")
+    assert w.dim() == 2 and rows in (2, 4)
+    N, K = w.shape
+    G, KV = (N + rows - 1) // rows, K // 8
+    u8 = dict(device=w.device, dtype=torch.uint8)
+    p = {"lo": torch.empty(G, rows // 2, KV, 16, **u8), "nib": torch.empty(G, KV, rows, 4, **u8), "sign": torch.empty(G, KV, rows, **u8),
+         "flags": torch.empty((G + 31) // 32, device=w.device, dtype=torch.int32), "rows": rows, "shape": (N, K)}
+    hb = C.c_int(0)
+    check(lib().emu_bf16_pack(_p(w), w.stride(0), N, K, rows, _p(p["lo"]), _p(p["nib"]), _p(p["sign"]), _p(p["flags"]), C.byref(hb),
+                              stream(w)), "emu_bf16_pack")
+    p["hb"] = int(hb.value)
+    return p
+
+
+def pack_set_c(p):
+    """The emu_bf16_pack_set of a packed dict (None: the empty set, rows 0)."""
+    from ._lib import Bf16PackSetC
+    if p is None:
+        return Bf16PackSetC(None, None, None, None, 0, 0)
+    return Bf16PackSetC(_p(p["lo"]), _p(p["nib"]), _p(p["sign"]), _p(p["flags"]), p["hb"], p["rows"])
+
+
+def linear_bf16pack(x, w, p, form: int, res=None, norm_w=None, eps: float = 0.0, epi: int = EPI_NONE, out=None):
+    """One activation row over the packed set ``p`` of ``w`` in the given bf16 form (FORM_*); see emu_linear_bf16pack."""
+    _req(x, "x"); _req(w, "w")
+    assert x.dim() == 2 and x.shape[0] == 1 and w.is_contiguous() and tuple(w.shape) == tuple(p["shape"]) and x.shape[1] == w.shape[1]
+    N, K = w.shape
+    if out is None:
+        out = torch.empty(1, N // 2 if epi == EPI_SWIGLU else N, device=x.device, dtype=BF16)
+    s = pack_set_c(p)
+    check(lib().emu_linear_bf16pack(_p(x), _p(w), C.byref(s), _p(res), _p(norm_w), _p(out), N, K, form, eps, epi, stream(x)),
+          "emu_linear_bf16pack")
+    return out
+
+
 def linear_fp4w(x, w4, scales, bias=None, res=None, norm_w=None, eps: float = 0.0, epi: int = EPI_NONE, out=None):
     """``linear`` over an MXFP4 weight stream (decode rows only, M <= 2; K % 32 == 0); see emu_linear_fp4w_bf16."""
     _req(x, "x"); _req(w4, "w4", torch.uint8); _req(scales, "scales", torch.uint8)

@@ -541,6 +541,37 @@ int emu_llama_release_bf16(emu_llama* m);
  * Returns 0 bf16, 1 the fp8 stream (1..2 rows), 2 W8A8 GEMMs (17 rows and more; in the layers that have fp8 weights), 3 the MXFP4
  * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more).  The head runs 2 as bf16. */
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local);
+/* The 13-bit lossless packing of a bf16 weight matrix for the one-row decode streams; emu_amd/bf16pack.py is the definition of the
+ * format and emu_amd/csrc/bf16_pack.h states the layout once for the packer and the kernels.  A weight keeps its low byte and its
+ * sign and stores the top 7 bits of its exponent field as a 4-bit offset from a per-matrix base hb (a window of 32 binades below the
+ * matrix's largest finite exponent); a row group with a weight outside the window is flagged and read from the bf16 matrix.
+ * Lossless: the streams decode in registers and feed the bf16 kernels' arithmetic, the results are the same bits.
+ * emu_bf16_pack_rows: the rows per group (2 or 4) of the set a one-row stream over [N, K] with / without the fused RMSNorm and epilogue
+ * epi would read under the emu_gemm_tune mask `tune`, or 0 when the planner sends the shape to a form without a packed twin.
+ * emu_bf16_pack: packs bf16 [N, ldw] (K % 32 == 0, rows 2 or 4) on the device: lo ceil(N/rows)*rows*K bytes, nib half, sign an
+ * eighth of that, flags ceil(ceil(N/rows)/32) 32-bit words; *hb_out = hb.  The call waits for its own result.
+ * emu_linear_bf16pack (tests): C[1, N] = epi(norm(A) W^T [+ res]) over such a set in the given form (1 head: rows 4, norm_w set, K <=
+ * 8192, epi NONE / SWIGLU; 2 preload: rows 2, K <= 8192; 3 single round trip: rows 2, K <= 18432; both without norm, epi NONE /
+ * RESID); W = the bf16 matrix [N, K], read for flagged row groups.  Bit-identical to emu_linear_bf16 on W. */
+typedef struct emu_bf16_pack_set { const void *lo, *nib, *sign, *flags; int hb, rows; } emu_bf16_pack_set;
+int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune);
+int emu_bf16_pack(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* sign, void* flags, int* hb_out,
+                  emu_stream_t s);
+int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, const void* norm_w, void* C, int N,
+                        int K, int form, float eps, int epi, emu_stream_t s);
+/* The packed sets of a layer (sets4: qkv, o_proj, gate/up, down; rows == 0: that matrix has none and stays on bf16) and of the head
+ * (rows_n: the rows the lm_head pointer holds); refused after emu_llama_release_bf16.  emu_llama_use_bf16_pack(m, 1): projections of
+ * ONE activation row on the bf16 kernels stream their set where emu_llama_pack_kernel says so; everything else reads what it read. */
+int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_set* sets4);
+int emu_llama_set_head_bf16_pack(emu_llama* m, const emu_bf16_pack_set* set, int rows_n);
+int emu_llama_use_bf16_pack(emu_llama* m, int on);
+/* CPU test hook (tests/test_bf16_pack_rule.py): the one further rule, bf16 -> the packed stream (6), on integers.  kernel: the answer
+ * of emu_llama_weight_kernel; rows = B*T; pack_rows: the rows per group of the matrix's registered set (0: none); pack_on: the
+ * switch; fused_mode / tail_mode / warm_mask: emu_llama_set_decode_fused / _decode_tail / _l2_warm as set; [N, K], norm, epi: the
+ * projection; tune: the emu_gemm_tune mask.  Returns 6 only for kernel 0, rows 1, the switch on, all three modes 0 and
+ * emu_bf16_pack_rows(N, K, norm, epi, tune) == pack_rows; else `kernel`. */
+int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
+                          int norm, int epi, int tune);
 /* Vocabulary-sharded lm_head under tensor parallelism (the reference's lm_head is lm.lm_head of LlamaForCausalLM reached
  * from Emu2/emu/emu.py:213-229): the lm_head pointer of emu_llama_set_head holds rows [row0, row0 + rows) of the vocabulary only;
  * emu_llama_logits fills this rank's columns of the caller's [M, vocab] rows, zeroes the others and all-reduces the rows, so every

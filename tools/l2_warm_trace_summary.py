@@ -12,6 +12,10 @@ rows.sort()
 def kind(n):
     if "decode_fused_combine_kernel" in n: return "combine"
     if "decode_fused_kernel" in n: return "attn"
+    if "gemv_pack_head_kernel" in n:                  # the 13-bit packed twins (gemv_pack.hip): <EPI>
+        return "gateup" if n[n.index("gemv_pack_head_kernel<") + 22:].split(">")[0].strip() in ("2", "(int)2") else "qkv"
+    if "gemv_pack_rows2_kernel" in n:                 # <KIT, CLAMP, EPI>: 4 trips = the preload form, 9 = the single round trip
+        return "oproj" if n[n.index("gemv_pack_rows2_kernel<") + 23:].split(",")[0].strip() in ("4", "(int)4") else "down"
     if "gemv_rt_kernel" in n: return "down"
     if "gemv_kernel" in n:
         # template args <R, MB, NORM, EPI, PRE>
