@@ -81,6 +81,8 @@ class Bf16PackSetC(C.Structure):
 
 SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
 CONTRASTIVE_MAX_K = 8      # EMU_CONTRASTIVE_MAX_K: candidates per prompt of the contrastive-search kernels
+BEAM_MAX_BEAMS = 8         # emu_beam_step_bf16 / emu_beam_sample_step_bf16 (include/emu_hip.h): nb <= 8 ...
+BEAM_MAX_NEW_TOKENS = 256  # ... and L <= 256, -22 above either
 CONTRASTIVE_CHUNK_ROWS = 8   # EMU_CONTRASTIVE_CHUNK_ROWS: context rows per workgroup of emu_contrastive_score's first launch
 CONTRASTIVE_MAX_HIDDEN = 8192   # EMU_CONTRASTIVE_MAX_HIDDEN
 

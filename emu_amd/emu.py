@@ -14,7 +14,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import genroute, ops
 from .conf.emu_conf import CLIPVisionCfg, LlamaCfg, TextDecoderCfg
 from .constants import *  # noqa: F401,F403  (re-exported like the reference module does)
 from .constants import (DEFAULT_gIMG_TOKEN, DEFAULT_IMAGE_TOKEN, DEFAULT_IMG_END_TOKEN, DEFAULT_IMG_PLACEHOLDER,
@@ -251,9 +251,8 @@ class EmuModel:
                      num_return_sequences: int = 1, hf_semantics: Optional[str] = None,
                      eos_token_id: Optional[int] = None, min_new_tokens: Optional[int] = None,
                      constraint=None) -> torch.Tensor:
-        """``generate`` at the token-id level: returns the NEW ids [B, n] (what HF returns for inputs_embeds).  Mode
-        selection as transformers does it: contrastive search (penalty_alpha > 0, top_k > 1, one beam, no sampling), beam
-        search / beam sampling (num_beams > 1), sampling or penalised greedy, plain greedy (device-side loop, hipGraph).
+        """``generate`` at the token-id level: returns the NEW ids [B, n] (what HF returns for inputs_embeds).  Which engine
+        method runs, and with which of this model's opt-ins: ``genroute.model_route``.
         ``hf_semantics`` (default: ``self.hf_semantics`` = "4.31", the transformers release the reference pins): beam-search
         conventions, see ``LlamaEngine.beam_search_generate``; "5.x" = the installed library the golden fixtures come from.
         The two releases also differ in what ``min_length=min_len`` (emu.py:220) enforces when generation is driven by
@@ -261,9 +260,7 @@ class EmuModel:
         (``_prepare_generated_length``: the default min_len = 1 then enforces nothing and EOS may be the first token -- pinned by
         the real reference's ids in tests/golden/generate_beam_eos_tiny.npz).  ``eos_token_id`` / ``min_new_tokens``: the options
         of that name the reference forwards to ``lm.generate`` through ``**kwargs`` (emu.py:175,228).  ``constraint``: an
-        ``emu_amd.constrain.TokenTrie`` (may run on the device) or a callable with the library's ``prefix_allowed_tokens_fn`` signature
-        (keeps the host loop), see ``LlamaEngine.beam_search_generate`` / ``sample_generate``; with one beam the call goes to
-        ``sample_generate``; contrastive search with a constraint is not built."""
+        ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature."""
         B, S = input_ids.shape
         sem = hf_semantics or getattr(self, "hf_semantics", "4.31")
         eos = EOS_TOKEN_ID if eos_token_id is None else int(eos_token_id)
@@ -281,19 +278,13 @@ class EmuModel:
         if video is not None:
             x = self._prompt_embeds(input_ids, video, self.v_query, gIMG_TOKEN_ID, embeds=x)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
-        if (penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1
-                and not do_sample):
-            if ngram or nret != 1:
-                raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
-            if constraint is not None:
-                raise NotImplementedError("contrastive search with a constraint is not built")
-            # with the option off the call is the old one
-            on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
-                if getattr(self, "device_contrastive", False) else {}
-            return self.decoder.lm.contrastive_generate(x.view(B, S, -1), attention_mask, max_new_tokens, float(penalty_alpha),
-                                                        int(top_k), min_len, repetition_penalty, eos_id=eos,
-                                                        pad_id=PAD_TOKEN_ID, **on_device)
-        if num_beams > 1:
+        method, routing = genroute.model_route(genroute.model_flags(self), num_beams, do_sample, top_k, penalty_alpha,
+                                               repetition_penalty, ngram, nret, constraint)
+        lm, x = self.decoder.lm, x.view(B, S, -1)
+        if method == "contrastive_generate":
+            return lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_len,
+                                           repetition_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID, **routing)
+        if method == "beam_search_generate":
             if sem == "4.31" and not EmuModel._warned_431:
                 # honesty in code, not only in INTEGRATION.md: this is the DEFAULT mode (emu.py:163-172: 5 beams, length_penalty -1)
                 EmuModel._warned_431 = True
@@ -303,30 +294,16 @@ class EmuModel:
                               "tests/golden/ (the library is not installable offline).  hf_semantics='5.x' is the mode pinned to the "
                               "installed library's ids; the two differ only where a hypothesis ends on EOS (INTEGRATION.md).",
                               stacklevel=2)
-            # the n-gram ban keeps the host loop unless device_ngram_ban is set; with the options off the call is the old one
-            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
-            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and (not ngram or ban) else {}
-            if ban:
-                on_device["device_ngram_ban"] = True
-            if constraint is not None:
-                on_device["constraint"] = constraint
-            return self.decoder.lm.beam_search_generate(x.view(B, S, -1), attention_mask, num_beams, max_new_tokens, min_len,
-                                                        length_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID,
-                                                        do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                                        repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
-                                                        num_return_sequences=nret, hf_semantics=sem, **on_device)
-        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
-            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
-            return self.decoder.lm.sample_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len, do_sample,
-                                                   temperature, top_k, top_p, repetition_penalty, eos_id=eos,
-                                                   pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                                   # the n-gram ban keeps the host loop unless device_ngram_ban is set
-                                                   device_sampler=bool(getattr(self, "device_sampler", False)) and (not ngram or ban),
-                                                   use_graph=self.use_graph, **(dict(device_ngram_ban=True) if ban else {}),
-                                                   **({} if constraint is None else dict(constraint=constraint)))
-        return self.decoder.lm.greedy_generate(x.view(B, S, -1), attention_mask, max_new_tokens, min_len,
-                                               eos_id=eos, pad_id=PAD_TOKEN_ID, use_graph=self.use_graph,
-                                               stop_on_eos=stop_on_eos)
+            return lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_len, length_penalty, eos_id=eos,
+                                           pad_id=PAD_TOKEN_ID, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
+                                           num_return_sequences=nret, hf_semantics=sem, **routing)
+        if method == "sample_generate":
+            return lm.sample_generate(x, attention_mask, max_new_tokens, min_len, do_sample, temperature, top_k, top_p,
+                                      repetition_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID, no_repeat_ngram_size=ngram,
+                                      num_return_sequences=nret, use_graph=self.use_graph, **routing)
+        return lm.greedy_generate(x, attention_mask, max_new_tokens, min_len, eos_id=eos, pad_id=PAD_TOKEN_ID,
+                                  use_graph=self.use_graph, stop_on_eos=stop_on_eos)
 
     @torch.no_grad()
     def generate(self, text: List[str], image: Optional[torch.Tensor] = None, video: Optional[torch.Tensor] = None,

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import genroute, ops
 from .conf.emu_conf import CLIPVisionCfg, LlamaCfg
 from .constants import EOS_TOKEN_ID, IMAGE_TOKEN_ID, PAD_TOKEN_ID
 from .constrain import pop_constraint
@@ -297,44 +297,26 @@ class Emu:
                      penalty_alpha=None, no_repeat_ngram_size=None, num_return_sequences: int = 1,
                      hf_semantics: Optional[str] = None, constraint=None):
         """``constraint``: an ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature
-        (Emu1/mm_eval/models/emu.py:96-109), see ``EmuModel.generate_ids``."""
-        B, S = input_ids.shape
+        (Emu1/mm_eval/models/emu.py:96-109).  Which engine method runs, and with which of this model's opt-ins:
+        ``genroute.model_route`` (modeling_emu.py:162-179 forwards every argument to lm.generate)."""
         x = self._prompt_embeds(input_ids, image)
-        # mode selection as transformers does it (modeling_emu.py:162-179 forwards every argument to lm.generate)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
-        if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample:
-            if ngram or nret != 1:
-                raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
-            if constraint is not None:
-                raise NotImplementedError("contrastive search with a constraint is not built")
-            # with the option off the call is the old one
-            on_device = dict(device_contrastive=True, use_graph=bool(getattr(self, "use_graph", False))) \
-                if getattr(self, "device_contrastive", False) else {}
+        method, routing = genroute.model_route(genroute.model_flags(self), num_beams, do_sample, top_k, penalty_alpha,
+                                               repetition_penalty, ngram, nret, constraint)
+        ends = dict(eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
+        if method == "contrastive_generate":
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,
-                                                repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, **on_device)
-        if num_beams > 1:
-            # the n-gram ban keeps the host loop unless device_ngram_ban is set; with the options off the call is the old one
-            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))
-            on_device = dict(device_beam_sampler=True) if getattr(self, "device_beam_sampler", False) and (not ngram or ban) else {}
-            if ban:
-                on_device["device_ngram_ban"] = True
-            if constraint is not None:
-                on_device["constraint"] = constraint
-            return self.lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_length, length_penalty,
-                                                eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID, do_sample=do_sample,
-                                                temperature=temperature, top_k=top_k, top_p=top_p,
+                                                repetition_penalty, **ends, **routing)
+        if method == "beam_search_generate":
+            return self.lm.beam_search_generate(x, attention_mask, num_beams, max_new_tokens, min_length, length_penalty, **ends,
+                                                do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                                 repetition_penalty=repetition_penalty, no_repeat_ngram_size=ngram,
                                                 num_return_sequences=nret,
-                                                hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"), **on_device)
-        if do_sample or repetition_penalty != 1.0 or ngram or nret != 1 or constraint is not None:
-            ban = bool(ngram) and bool(getattr(self, "device_ngram_ban", False))     # the ban keeps the host loop unless this is set
+                                                hf_semantics=hf_semantics or getattr(self, "hf_semantics", "5.x"), **routing)
+        if method == "sample_generate":
             return self.lm.sample_generate(x, attention_mask, max_new_tokens, min_length, do_sample, temperature, top_k, top_p,
-                                           repetition_penalty, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID,
-                                           no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                           device_sampler=bool(getattr(self, "device_sampler", False)) and (not ngram or ban),
-                                           **(dict(device_ngram_ban=True) if ban else {}),
-                                           **({} if constraint is None else dict(constraint=constraint)))
-        return self.lm.greedy_generate(x, attention_mask, max_new_tokens, min_length, eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
+                                           repetition_penalty, **ends, no_repeat_ngram_size=ngram, num_return_sequences=nret, **routing)
+        return self.lm.greedy_generate(x, attention_mask, max_new_tokens, min_length, **ends)
 
     @torch.no_grad()
     def generate(self, samples, do_sample=False, num_beams=5, max_new_tokens=50, min_length=1, top_p=0.9,

@@ -15,8 +15,8 @@ from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from . import bf16pack, mxfp4, ops
-from ._lib import CONTRASTIVE_MAX_K, SAMPLE_MAX_VOCAB, Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
+from . import bf16pack, genroute, mxfp4, ops
+from ._lib import Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
@@ -870,45 +870,22 @@ class LlamaEngine:
         replayed from one hipGraph with ``use_graph``; the host only reads the rows' ``unfinished`` flags every ``EOS_POLL`` steps.
         What is computed is specified in ``emu_amd/sampling.py``.  The draws use ``uniforms`` [max_new_tokens, rows] fp32 in [0, 1)
         -- by default ONE ``torch.rand`` from the global generator up front: seed-stable, but a different random stream from the
-        host path's ``multinomial``, which is why this is an option.  Refused with a ValueError before any device work:
-        ``no_repeat_ngram_size > 0`` (the n-gram ban keeps the host path) and tensor parallelism (the ranks would need one shared
-        table of uniforms).  A vocabulary above the kernel's bound (``_lib.SAMPLE_MAX_VOCAB``, where ``emu_sample_bf16`` answers
-        -22) stays on the host path with one warning.
+        host path's ``multinomial``, which is why this is an option.
 
         ``constraint`` (``emu_amd.constrain.TokenTrie`` or a callable (batch_id, ids generated so far) -> allowed ids, the library's
         ``prefix_allowed_tokens_fn``): the mask stands where the library's PrefixConstrainedLogitsProcessor does, after the
-        processors and ahead of the warpers.  A trie with ``device_sampler=True`` runs on the device (``emu_sample_trie_bf16`` /
-        ``emu_llama_sample_step_trie``; ``do_sample=False`` = constrained greedy); a callable always keeps the host loop.
+        processors and ahead of the warpers (``do_sample=False`` = constrained greedy).  ``device_ngram_ban=True`` (opt-in, read only
+        with ``device_sampler=True``): the ban of ``no_repeat_ngram_size`` runs inside the selection kernel (``sampling.banned_ngram_mask``
+        over the ids the row has generated), and the loop stays capturable.
 
-        ``device_ngram_ban=True`` (opt-in, read only with ``device_sampler=True``): ``no_repeat_ngram_size > 0`` is no longer refused;
-        the ban runs inside the selection kernel (``emu_sample_ngram_bf16`` / ``emu_llama_sample_step_ngram``, specified by
-        ``sampling.banned_ngram_mask``) over the ids the row has generated, and the loop stays capturable.  The host loop takes over,
-        with one warning per process, for a ``TokenTrie`` together with the ban (not built on the device) and for a vocabulary below
-        ``max_new_tokens + 2``: the ban (at most one id per generated token) and the EOS suppress could otherwise leave a row
-        without a finite score, which the draw does not define."""
+        Which of this runs on the device, in which variant of the selection kernels, and what is refused (a ValueError before any
+        device work) or handed back to the host loop with one warning: ``genroute.sample_route``."""
         trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
-        if device_sampler and allow_fn is not None and trie is None:
-            device_sampler = False                              # a Python callable cannot run inside a captured step
         ngram = int(no_repeat_ngram_size or 0)
-        if device_sampler and ngram > 0 and device_ngram_ban:
-            why = ("a TokenTrie together with the ban is not built on the device" if trie is not None else
-                   f"vocabulary {self.vocab} is below max_new_tokens + 2 = {max_new_tokens + 2} (the ban and the EOS suppress could "
-                   "leave a row without a finite score)" if self.vocab < max_new_tokens + 2 else None)
-            if why is not None:
-                warn_once(LlamaEngine, "_warned_ngram_ban", f"emu_amd: device_ngram_ban: {why}; staying on the host path")
-                device_sampler = False
-        if device_sampler:
-            if ngram > 0 and not device_ngram_ban:
-                raise ValueError("device_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
-                                 "(device_sampler=False)")
-            if self.ctx.tp_size > 1:
-                raise ValueError("device_sampler: not built for tensor parallelism (the ranks would need one shared table of "
-                                 "uniforms); use device_sampler=False")
-            if self.vocab > SAMPLE_MAX_VOCAB:
-                warn_once(LlamaEngine, "_warned_sampler_vocab",
-                          f"emu_amd: device_sampler: vocabulary {self.vocab} is above the sample kernel's bound "
-                          f"{SAMPLE_MAX_VOCAB} (emu_sample_bf16 answers -22); staying on the host path")
-                device_sampler = False
+        route = genroute.sample_route(self.vocab, tp_size_of(self), max_new_tokens, device_sampler, ngram, device_ngram_ban,
+                                      genroute.constraint_kind(constraint))
+        if route.warning is not None:
+            warn_once(LlamaEngine, *route.warning)
         if num_return_sequences > 1:
             if not do_sample:
                 raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1")
@@ -917,21 +894,20 @@ class LlamaEngine:
         B, S, H = embeds.shape
         dev = self.device
         s_max = self.kv_capacity(S + max_new_tokens)
-        if device_sampler and uniforms is not None and tuple(uniforms.shape) != (max_new_tokens, B):
+        if route.device and uniforms is not None and tuple(uniforms.shape) != (max_new_tokens, B):
             raise ValueError(f"uniforms must be [max_new_tokens, rows] = [{max_new_tokens}, {B}], got {tuple(uniforms.shape)}")
         hidden, kstart, pos = self.prefill(embeds, attention_mask, s_max)
         row = hidden[:, -1, :]
-        if device_sampler:
+        if route.device:
             return self._sample_device(row, B, S, kstart, pos, max_new_tokens, min_len, do_sample, temperature, top_k, top_p,
-                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms, trie,
-                                       **(dict(ngram=ngram) if ngram > 0 else {}))      # (off: the call is the old one)
+                                       repetition_penalty, eos_id, pad_id, use_graph, uniforms, trie, **route.device_kw)
         out = torch.full((B, max_new_tokens), pad_id, dtype=torch.int64, device=dev)
         unfinished = torch.ones(B, dtype=torch.int64, device=dev)
         hid = torch.empty(B, H, device=dev, dtype=BF16)
         n = 0
         for step in range(max_new_tokens):
             scores = process_logits(self.logits(row).float(), out[:, :step], step < min_len, eos_id, do_sample, temperature,
-                                    top_k, top_p, repetition_penalty, no_repeat_ngram_size=int(no_repeat_ngram_size or 0),
+                                    top_k, top_p, repetition_penalty, no_repeat_ngram_size=ngram,
                                     allowed=None if allow_fn is None else allowed_mask(allow_fn, out[:, :step], 1, self.vocab))
             if do_sample:
                 nxt = torch.multinomial(torch.softmax(scores, dim=-1), num_samples=1).squeeze(1)
@@ -958,8 +934,8 @@ class LlamaEngine:
                        min_len: int, do_sample: bool, temperature, top_k, top_p, repetition_penalty: float, eos_id: int,
                        pad_id: int, use_graph: bool, uniforms: Optional[torch.Tensor], trie: Optional[TokenTrie] = None,
                        ngram: int = 0) -> torch.Tensor:
-        """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill.  ``trie``: the selection is
-        ``emu_sample_trie_bf16``, every row starting at the root.  ``ngram`` > 0: the selection is ``emu_sample_ngram_bf16``."""
+        """The device-side loop of ``sample_generate(device_sampler=True)``, after the prefill.  ``trie``: the selection's "trie"
+        variant (``ops.SELECT_ENTRY``), every row starting at the root.  ``ngram`` > 0: its "ngram" variant."""
         dev = self.device
         if do_sample:
             uni = torch.rand(max_new, B, dtype=torch.float32, device=dev) if uniforms is None else \
@@ -1161,24 +1137,15 @@ class LlamaEngine:
         ``device_contrastive=True`` (opt-in) keeps the token loop on the device: ``_contrastive_device`` (csrc/contrastive.hip,
         specified in ``emu_amd/sampling.py``: ``contrastive_reference_*``), replayed from one hipGraph with ``use_graph``.  The loop
         above stays the default and the fallback; the device's sums are fp32 in a fixed order, so a choice this loop decides by less
-        than the rounding of either may fall the other way.  Refused with a ValueError before any device work: tensor parallelism
-        (the ranks would have to agree on every selection).  The host loop takes over, with one warning per process, for
-        ``top_k > 8``, a vocabulary above ``_lib.SAMPLE_MAX_VOCAB`` or below ``top_k``, and when a ``trace`` or ``force_ids`` is
-        given."""
-        if device_contrastive:
-            if self.ctx.tp_size > 1:
-                raise ValueError("device_contrastive: not built for tensor parallelism (the ranks would have to agree on every "
-                                 "selection); use device_contrastive=False")
-            why = (f"top_k {int(top_k)} (the kernels take {CONTRASTIVE_MAX_K})" if int(top_k) > CONTRASTIVE_MAX_K else
-                   f"vocabulary {self.vocab} above the kernel's bound {SAMPLE_MAX_VOCAB}" if self.vocab > SAMPLE_MAX_VOCAB else
-                   f"vocabulary {self.vocab} below top_k" if self.vocab < int(top_k) else
-                   "a trace is asked for" if trace is not None else
-                   "a forced token path is given" if force_ids is not None else None)
-            if why is None:
-                return self._contrastive_device(embeds, attention_mask, int(max_new_tokens), float(penalty_alpha), int(top_k),
-                                                int(min_len), float(repetition_penalty), int(eos_id), int(pad_id), bool(use_graph))
-            warn_once(LlamaEngine, "_warned_contrastive",
-                      f"emu_amd: device_contrastive: {why} (the kernels answer -22 outside their range); staying on the host path")
+        than the rounding of either may fall the other way.  What is refused (a ValueError before any device work) and where the
+        host loop takes over with one warning per process: ``genroute.contrastive_route``."""
+        route = genroute.contrastive_route(self.vocab, tp_size_of(self), int(top_k), device_contrastive, trace is not None,
+                                           force_ids is not None)
+        if route.warning is not None:
+            warn_once(LlamaEngine, *route.warning)
+        if route.device:
+            return self._contrastive_device(embeds, attention_mask, int(max_new_tokens), float(penalty_alpha), int(top_k),
+                                            int(min_len), float(repetition_penalty), int(eos_id), int(pad_id), bool(use_graph))
         B, S, H = embeds.shape
         k, V, dev = int(top_k), self.vocab, self.device
         s_max = self.kv_capacity(S + max_new_tokens)
@@ -1365,15 +1332,12 @@ class LlamaEngine:
         multinomial draw from torch's global generator, as ever.  With a table, ties between candidate scores go to the first in
         candidate order (stable top-k, the device kernels' rule; ``torch.topk`` leaves them open), so that the table alone decides.
 
-        ``device_beam_sampler=True`` (opt-in) keeps the token loop of beam-search sampling and of penalised beam search
-        (``do_sample`` or ``repetition_penalty != 1``) on the device: ``_beam_search_device`` with ``emu_beam_sample_step_bf16``
-        (csrc/beam_sample.hip) in place of ``emu_beam_step_bf16``, captured and replayed in the same way.  Its draws come from
+        ``device_beam_sampler=True`` / ``device_ngram_ban=True`` (opt-ins): beam-search sampling and penalised beam search, and the ban
+        of ``no_repeat_ngram_size``, keep the token loop on the device (``_beam_search_device``).  The sampler's draws come from
         ``uniforms``, by default ONE ``torch.rand(max_new_tokens, B, 2 * num_beams)`` from the global generator up front: seed-stable,
-        but a different random stream from ``multinomial``, which is why this is an option.  Refused with a ValueError before any
-        device work: ``no_repeat_ngram_size > 0`` and tensor parallelism (the ranks would need one shared table).  The host pipeline
-        takes over, with one warning per process, for more than 8 beams, more than 256 new tokens, a vocabulary above
-        ``_lib.SAMPLE_MAX_VOCAB`` or below 2N, or when a ``trace`` is asked for.  The deterministic, unpenalised search goes to its
-        own kernel whatever this flag says.
+        but a different random stream from ``multinomial``, which is why this is an option.  Which call runs on the device, in which
+        variant of the step, what is refused (a ValueError before any device work) and where the host loop takes over, with or
+        without a warning: ``genroute.beam_route``.
 
         ``trace`` (a dict, diagnostics for the tests): receives ``margin`` = the smallest gap seen between the N-th and the
         (N+1)-th running candidate at a pruning step and between the two best final results, and, with a table of uniforms,
@@ -1385,65 +1349,18 @@ class LlamaEngine:
         id that is not allowed become -inf after the processors and ahead of the warpers (the log-softmax is over the whole row).
         Fewer than 2N candidates may then be finite, so every selection goes by the device kernels' rule -- ties, those among -inf
         included, to the lower index (stable top-k) -- and the ``trace`` margins leave out exact ties and non-finite gaps (-inf minus
-        -inf).  A trie in the deterministic, unpenalised mode runs on the device (``emu_beam_step_trie_bf16``) within the kernel's
-        bounds, like the unconstrained search.  The host loop takes over for a callable, and for a trie together with sampling, a
-        repetition penalty, an n-gram ban or a ``trace``; ``device_beam_sampler`` is then ignored with one warning per process.
-
-        ``device_ngram_ban=True`` (opt-in) with ``no_repeat_ngram_size > 0``: the ban runs inside the selection kernels
-        (``sampling.banned_ngram_mask`` over ``running_seq[b, j, :cur]``, which follows the beams) and the loop stays on the device:
-        the deterministic, unpenalised search goes to ``_beam_search_device`` with ``emu_beam_step_ngram_bf16`` instead of the host
-        loop, and ``device_beam_sampler=True`` is no longer refused but runs ``emu_beam_sample_step_ngram_bf16``.  Without the flag
-        both are as before.  The host loop takes over -- with one warning per process where ``device_beam_sampler`` is thereby
-        ignored -- for a constraint of any kind together with the ban, for a ``trace``, and for a vocabulary below
-        ``max_new_tokens + 1 + 2 * num_beams`` (the ban takes at most one id per generated token from a beam's row, and 2N finite
-        continuations must remain beside the EOS suppress).  Under tensor parallelism the deterministic branch is not refused:
-        nothing is random and every rank holds the same ids; no multi-rank run of it has been made.  The sampler branch keeps its
-        refusal."""
+        -inf)."""
         trie, allow_fn = resolve_constraint(constraint, self.vocab, eos_id, min_len, num_return_sequences)
-        if allow_fn is not None and device_beam_sampler and (do_sample or repetition_penalty != 1.0):
-            warn_once(LlamaEngine, "_warned_beam_constraint",
-                      "emu_amd: device_beam_sampler: a constraint is not built into the device beam sampler "
-                      "(emu_beam_sample_step_bf16); staying on the host path")
+        kind = genroute.constraint_kind(constraint)
+        if genroute.constraint_drops_beam_sampler(kind, device_beam_sampler, do_sample, repetition_penalty):
+            warn_once(LlamaEngine, *genroute.BEAM_CONSTRAINT_WARNING)
             device_beam_sampler = False
-        if hf_semantics not in ("4.31", "5.x"):
-            raise ValueError("hf_semantics must be '4.31' or '5.x'")
-        if not 1 <= num_return_sequences <= num_beams:
-            raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`")       # the library's own check
         ngram = int(no_repeat_ngram_size or 0)
-        if uniforms is not None and tuple(uniforms.shape) != (max_new_tokens, embeds.shape[0], 2 * num_beams):
-            raise ValueError(f"uniforms must be [max_new_tokens, prompts, 2 * num_beams] = "
-                             f"[{max_new_tokens}, {embeds.shape[0]}, {2 * num_beams}], got {tuple(uniforms.shape)}")
-        device_beam_sampler = bool(device_beam_sampler) and (do_sample or repetition_penalty != 1.0)
-        # the ban on the device: asked for, and within what the kernels take
-        ban_why = None
-        if ngram > 0 and device_ngram_ban:
-            ban_why = ("a constraint together with the ban is not built on the device" if allow_fn is not None else
-                       "a trace is asked for" if trace is not None else
-                       f"vocabulary {self.vocab} is below max_new_tokens + 1 + 2 * num_beams = {max_new_tokens + 1 + 2 * num_beams} "
-                       "(a beam could be left with fewer than 2N finite continuations)"
-                       if self.vocab < max_new_tokens + 1 + 2 * num_beams else None)
-        device_ban = ngram > 0 and bool(device_ngram_ban) and ban_why is None
-        if device_beam_sampler and ngram > 0 and device_ngram_ban and ban_why is not None:
-            warn_once(LlamaEngine, "_warned_ngram_ban",
-                      f"emu_amd: device_ngram_ban: {ban_why}; device_beam_sampler is ignored, staying on the host path")
-            device_beam_sampler = False
-        if device_beam_sampler:
-            if ngram > 0 and not device_ban:
-                raise ValueError("device_beam_sampler: no_repeat_ngram_size > 0 is not built on the device; it keeps the host path "
-                                 "(device_beam_sampler=False)")
-            if self.ctx.tp_size > 1:
-                raise ValueError("device_beam_sampler: not built for tensor parallelism (the ranks would need one shared table of "
-                                 "uniforms); use device_beam_sampler=False")
-            why = (f"{num_beams} beams (the kernel takes 8)" if num_beams > 8 else
-                   f"{max_new_tokens} new tokens (the kernel takes 256)" if max_new_tokens > 256 else
-                   f"vocabulary {self.vocab} above the kernel's bound {SAMPLE_MAX_VOCAB}" if self.vocab > SAMPLE_MAX_VOCAB else
-                   f"vocabulary {self.vocab} below 2 * num_beams" if self.vocab < 2 * num_beams else
-                   "a trace is asked for" if trace is not None else None)
-            if why is not None:
-                warn_once(LlamaEngine, "_warned_beam_sampler",
-                          f"emu_amd: device_beam_sampler: {why} (emu_beam_sample_step_bf16 answers -22 outside its range); "
-                          "staying on the host path")
-                device_beam_sampler = False
+        route = genroute.beam_route(self.vocab, tp_size_of(self), max_new_tokens, num_beams, do_sample, repetition_penalty, ngram,
+                                    device_beam_sampler, device_ngram_ban, kind, trace is not None, hasattr(self, "handle"),
+                                    hf_semantics, num_return_sequences, embeds.shape[0], None if uniforms is None else uniforms.shape)
+        if route.warning is not None:
+            warn_once(LlamaEngine, *route.warning)
         B, S, H = embeds.shape
         nb, V, dev = num_beams, self.vocab, self.device
         s_max = self.kv_capacity(S + max_new_tokens)
@@ -1456,22 +1373,19 @@ class LlamaEngine:
 
         max_len = max_new_tokens
         NEG = -1.0e9
-        # The deterministic mode (the reference's default) runs each step's selection and bookkeeping in ONE kernel
-        # (emu_beam_step_bf16; with device_ngram_ban its _ngram form); sampling, penalties, n-gram bans without that option and the
-        # diagnostics keep the torch pipeline below.
-        if (not do_sample and repetition_penalty == 1.0 and (not ngram or device_ban) and trace is None and nb <= 8 and max_len <= 256
-                and V >= 2 * nb and hasattr(self, "handle") and logits.dtype == BF16 and (allow_fn is None or trie is not None)):
+        # The deterministic mode (the reference's default) runs each step's selection and bookkeeping in ONE kernel (emu_beam_step_bf16
+        # or a variant of it); whatever the route leaves to the host, and any logits but the HIP engine's bf16, keep the torch pipeline
+        # below.
+        if route.device and not route.sampler and logits.dtype == BF16:
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
-                                            int(num_return_sequences), hf_semantics == "4.31", trie=trie,
-                                            **(dict(ngram=ngram) if device_ban else {}))      # (off: the call is the old one)
-        if device_beam_sampler:
+                                            int(num_return_sequences), hf_semantics == "4.31", trie=trie, **route.device_kw)
+        if route.sampler:
             if not hasattr(self, "handle") or logits.dtype != BF16:
                 raise RuntimeError("device_beam_sampler needs the HIP engine and its bf16 logits")
             return self._beam_search_device(logits, B, S, nb, max_len, min_len, length_penalty, eos_id, pad_id, kstart_b, pos,
                                             int(num_return_sequences), hf_semantics == "4.31",
                                             sampler=(sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id,
-                                                                   min_len, eos_id, pad_id, min_keep=2), uniforms),
-                                            **(dict(ngram=ngram) if device_ban else {}))
+                                                                   min_len, eos_id, pad_id, min_keep=2), uniforms), **route.device_kw)
         logits = logits.float()
         running_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=dev)
         sequences = running_seq.clone()
@@ -1631,12 +1545,12 @@ class LlamaEngine:
         is copied into a buffer the captured graph owns, so a call with another table replays the same graph; under the "4.31"
         order with sampling all N running scores start at 0, as on the host.
 
-        ``trie`` (deterministic mode only): the same loop with ``emu_beam_step_trie_bf16`` as its step.  The beams' nodes live in the
-        state and start at the root; the state keeps the trie's tables alive, and their addresses are part of the key, so a call
-        with another trie captures anew.
+        ``trie`` (deterministic mode only): the same loop with the step's "trie" variant (``ops.SELECT_ENTRY``).  The beams' nodes
+        live in the state and start at the root; the state keeps the trie's tables alive, and their addresses are part of the key,
+        so a call with another trie captures anew.
 
-        ``ngram`` > 0 (``device_ngram_ban``; not together with a trie): the step is ``emu_beam_step_ngram_bf16`` or, with ``sampler``,
-        ``emu_beam_sample_step_ngram_bf16``.  The n is a scalar of the launch, so it is part of the key."""
+        ``ngram`` > 0 (``device_ngram_ban``; not together with a trie): the "ngram" variant of the step, with or without ``sampler``.
+        The n is a scalar of the launch, so it is part of the key."""
         dev, V, rows = self.device, self.vocab, B * nb
         ngram = int(ngram)
         if ngram and trie is not None:
@@ -1687,20 +1601,12 @@ class LlamaEngine:
                      st["running_scores"].data_ptr(), st["beam_scores"].data_ptr(), st["finished"].data_ptr(),
                      st["seq_len"].data_ptr(), st["still_open"].data_ptr(), st["next_tok"].data_ptr(),
                      st["beam_flat"].data_ptr(), st["ws"].data_ptr(), st["ws"].numel())
-            if tables is not None:
-                check(L.emu_beam_step_trie_bf16(*state, C.byref(st["trie"]), st["node"].data_ptr(), stream()),
-                      "emu_beam_step_trie_bf16", self.ctx.handle)
-            elif params is None and ngram:
-                check(L.emu_beam_step_ngram_bf16(*state, ngram, stream()), "emu_beam_step_ngram_bf16", self.ctx.handle)
-            elif params is None:
-                check(L.emu_beam_step_bf16(*state, stream()), "emu_beam_step_bf16", self.ctx.handle)
-            elif ngram:
-                check(L.emu_beam_sample_step_ngram_bf16(*state, params, int(sampling and v431),
-                                                        st["uni"].data_ptr() if sampling else None, max_len, None, None, 0, ngram,
-                                                        stream()), "emu_beam_sample_step_ngram_bf16", self.ctx.handle)
+            variant = "trie" if tables is not None else "ngram" if ngram else "plain"
+            if params is None or tables is not None:
+                ops.select_call(L, "beam_step", variant, state, stream(), self.ctx.handle, st.get("trie"), st.get("node"), ngram)
             else:
-                check(L.emu_beam_sample_step_bf16(*state, params, int(sampling and v431), st["uni"].data_ptr() if sampling else None,
-                                                  max_len, None, None, 0, stream()), "emu_beam_sample_step_bf16", self.ctx.handle)
+                draw = (params, int(sampling and v431), st["uni"].data_ptr() if sampling else None, max_len, None, None, 0)
+                ops.select_call(L, "beam_sample_step", variant, state + draw, stream(), self.ctx.handle, ngram=ngram)
 
         def body():
             """One step, every index read on the device."""
@@ -1757,6 +1663,11 @@ def process_logits(scores: torch.Tensor, generated: torch.Tensor, suppress_eos: 
     if do_sample:
         scores = warp_logits(scores, temperature, top_k, top_p, min_keep)
     return scores
+
+
+def tp_size_of(engine) -> int:
+    """The ranks an engine is sharded over (the CPU stand-in of the tests has a context without the field: one)."""
+    return getattr(engine.ctx, "tp_size", 1)
 
 
 def resolve_constraint(constraint, vocab: int, eos_id: int, min_len: int, num_return_sequences: int = 1):
@@ -1940,14 +1851,8 @@ class SampleState(GreedyState):
                 self.ctx.data_ptr(), self.step_idx.data_ptr(), self.out_ids.data_ptr(), self.max_new, e.s_max, self.hidden.data_ptr(),
                 self.logits.data_ptr(), self.logits.stride(0), self.ws.data_ptr(), self.ws.numel(), ops._p(self.uniforms),
                 self.unfinished.data_ptr(), C.byref(self.params))
-        if self.ngram:
-            check(lib().emu_llama_sample_step_ngram(*args, self.ngram, ops.stream(e.device)), "emu_llama_sample_step_ngram",
-                  e.ctx.handle)
-        elif self.trie is None:
-            check(lib().emu_llama_sample_step(*args, ops.stream(e.device)), "emu_llama_sample_step", e.ctx.handle)
-        else:
-            check(lib().emu_llama_sample_step_trie(*args, C.byref(self.trie), self.node.data_ptr(), ops.stream(e.device)),
-                  "emu_llama_sample_step_trie", e.ctx.handle)
+        variant = "ngram" if self.ngram else "plain" if self.trie is None else "trie"
+        ops.select_call(lib(), "sample_step", variant, args, ops.stream(e.device), e.ctx.handle, self.trie, self.node, self.ngram)
 
     def step_graph(self) -> None:
         """GreedyState's, the n of the ban beside the mode epoch in the key: the captured launch holds that scalar."""

@@ -353,15 +353,36 @@ def trie_tables(tables):
     return TokenTrieC(_p(first), _p(tok), _p(child), first.numel() - 1, tok.numel())
 
 
+# The selection kernels' entry points: (step kind, selection variant) -> C symbol.  A variant is its kind's plain entry point with its
+# own arguments ahead of the stream: "trie" the constraint's tables (``trie_tables``) and the rows' nodes (int32, in/out), "ngram" the
+# size of the no-repeat n-gram ban.  The beam sampler step has no "trie" variant.
+SELECT_ENTRY = {
+    ("sample", "plain"): "emu_sample_bf16", ("sample", "trie"): "emu_sample_trie_bf16", ("sample", "ngram"): "emu_sample_ngram_bf16",
+    ("sample_step", "plain"): "emu_llama_sample_step", ("sample_step", "trie"): "emu_llama_sample_step_trie",
+    ("sample_step", "ngram"): "emu_llama_sample_step_ngram",
+    ("beam_step", "plain"): "emu_beam_step_bf16", ("beam_step", "trie"): "emu_beam_step_trie_bf16",
+    ("beam_step", "ngram"): "emu_beam_step_ngram_bf16",
+    ("beam_sample_step", "plain"): "emu_beam_sample_step_bf16", ("beam_sample_step", "ngram"): "emu_beam_sample_step_ngram_bf16",
+}
+
+
+def select_call(library, kind: str, variant: str, args: tuple, stream_ptr, ctx=None, trie=None, node=None, ngram: int = 0) -> None:
+    """Call the ``SELECT_ENTRY`` of (``kind``, ``variant``) in ``library`` (the caller's ``lib()``) with the kind's common ``args``,
+    then the variant's own, then the stream; a failure is reported under the symbol's name (``ctx``: as ``check``'s)."""
+    name = SELECT_ENTRY[kind, variant]
+    own = (C.byref(trie), _p(node)) if variant == "trie" else (int(ngram),) if variant == "ngram" else ()
+    check(getattr(library, name)(*args, *own, stream_ptr), name, ctx)
+
+
 def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist=None, uniforms=None, unfinished=None,
            probs_out=None, trie=None, node=None, ngram: Optional[int] = None):
     """``emu_sample_bf16`` (include/emu_hip.h; specified in emu_amd/sampling.py): one token per row of bf16 ``logits`` [rows, >= vocab]
     under ``params`` (``_lib.SampleParamsC``).  ``step_dev`` int32 [1] on the device = the step index the kernel reads: the number of
     history rows of ``hist`` int32 [steps, rows] in use, the row of ``uniforms`` fp32 [steps, rows], the min-length comparison.
     ``unfinished`` int32 [rows] and ``probs_out`` fp32 [rows, >= vocab] are optional.  ``trie`` (``trie_tables``) with ``node``
-    int32 [rows], in/out: ``emu_sample_trie_bf16``, the selection under a constraint.  ``ngram`` (not None):
-    ``emu_sample_ngram_bf16``, the no-repeat n-gram ban of that size over ``hist`` (0 = off; not built together with a trie).  Returns
-    ``out`` int32 [rows]."""
+    int32 [rows], in/out: the "trie" variant (``SELECT_ENTRY``), the selection under a constraint.  ``ngram`` (not None): the "ngram"
+    variant, the no-repeat n-gram ban of that size over ``hist`` (0 = off; not built together with a trie).  Returns ``out`` int32
+    [rows]."""
     _req(logits, "logits")
     rows = logits.shape[0]
     vocab = logits.shape[1] if vocab is None else vocab
@@ -376,16 +397,13 @@ def sample(logits, step_dev, params, out=None, vocab: Optional[int] = None, hist
             hist.shape[0] if hist is not None else 0, _p(step_dev), _p(uniforms),
             uniforms.stride(0) if uniforms is not None else 0, uniforms.shape[0] if uniforms is not None else 0,
             C.byref(params), _p(unfinished), _p(out), _p(probs_out), probs_out.stride(0) if probs_out is not None else 0)
-    if ngram is not None:
-        if trie is not None or node is not None:
-            raise ValueError("the n-gram ban together with a constraint is not built on the device")
-        check(lib().emu_sample_ngram_bf16(*args, int(ngram), stream(logits)), "emu_sample_ngram_bf16")
-    elif trie is None and node is None:
-        check(lib().emu_sample_bf16(*args, stream(logits)), "emu_sample_bf16")
-    else:
-        if trie is None or node is None or node.numel() < rows:
-            raise ValueError("a constrained selection needs the trie's tables and a node per row")
-        check(lib().emu_sample_trie_bf16(*args, C.byref(trie), _p(node), stream(logits)), "emu_sample_trie_bf16")
+    constrained = trie is not None or node is not None
+    if ngram is not None and constrained:
+        raise ValueError("the n-gram ban together with a constraint is not built on the device")
+    if constrained and (trie is None or node is None or node.numel() < rows):
+        raise ValueError("a constrained selection needs the trie's tables and a node per row")
+    variant = "ngram" if ngram is not None else "trie" if constrained else "plain"
+    select_call(lib(), "sample", variant, args, stream(logits), trie=trie, node=node, ngram=ngram or 0)
     return out
 
 

@@ -399,7 +399,7 @@ def contrastive_reference_select(ctx: torch.Tensor, ctx_valid: torch.Tensor, can
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Constrained decoding (emu_amd/constrain.py: ``TokenTrie``; ``emu_sample_trie_bf16``, ``emu_beam_step_trie_bf16``).  The kernels keep
+# Constrained decoding (emu_amd/constrain.py: ``TokenTrie``; the "trie" variants of ``ops.SELECT_ENTRY``).  The kernels keep
 # one trie node per row on the device and advance it by the id they select; what that state must equal is the stateless walk of the
 # row's generated ids through the trie, and what the mask must equal is the trie's answer for those ids.
 

@@ -72,13 +72,14 @@ def selection_alone(V, rounds, dev):
     sample = (lg.data_ptr(), V, 1, V, hist.data_ptr(), NB, 256, step.data_ptr(), uni1.data_ptr(), NB, 256, C.byref(chat), None,
               out.data_ptr(), None, 0)
     tail = (C.byref(demo), 0, unib.data_ptr(), 1, None, None, 0)
+    banned = lambda kind: getattr(L, ops.SELECT_ENTRY[kind, "ngram"])
     legs = {
         ("sample kernel, 1 row, chat settings", "no ban"): lambda: L.emu_sample_bf16(*sample, st()),
-        ("sample kernel, 1 row, chat settings", "ban"): lambda: L.emu_sample_ngram_bf16(*sample, N, st()),
+        ("sample kernel, 1 row, chat settings", "ban"): lambda: banned("sample")(*sample, N, st()),
         ("beam step, 5 rows, deterministic", "no ban"): lambda: L.emu_beam_step_bf16(*state, st()),
-        ("beam step, 5 rows, deterministic", "ban"): lambda: L.emu_beam_step_ngram_bf16(*state, N, st()),
+        ("beam step, 5 rows, deterministic", "ban"): lambda: banned("beam_step")(*state, N, st()),
         ("beam sample step, 5 rows, demo settings", "no ban"): lambda: L.emu_beam_sample_step_bf16(*state, *tail, st()),
-        ("beam sample step, 5 rows, demo settings", "ban"): lambda: L.emu_beam_sample_step_ngram_bf16(*state, *tail, N, st()),
+        ("beam sample step, 5 rows, demo settings", "ban"): lambda: banned("beam_sample_step")(*state, *tail, N, st()),
     }
     times = {k: [] for k in legs}
     for rnd in range(rounds + 1):                                 # round 0 is the warm-up
