@@ -69,6 +69,11 @@ class SampleParamsC(C.Structure):
                 ("top_k", i32), ("top_p", f32), ("min_keep", i32), ("eos_id", i32), ("pad_id", i32)]
 
 
+class GemvFp8ThinPlanC(C.Structure):
+    """emu_gemv_fp8_thin_plan_t (include/emu_hip.h)."""
+    _fields_ = [(n, i32) for n in ("status", "rows", "mb", "kc", "stages", "lds_bytes", "grid", "block")]
+
+
 class TokenTrieC(C.Structure):
     """emu_token_trie (include/emu_hip.h): the flat tables of emu_amd.constrain.TokenTrie on the device."""
     _fields_ = [("first", vp), ("tok", vp), ("child", vp), ("nodes", i32), ("edges", i32)]
@@ -122,8 +127,10 @@ _PROTOS = {
     "emu_gemm_tune": (None, [i32]),
     "emu_gemm_plan": (i32, [vp, i32, i32, vp, C.POINTER(i32)]),
     "emu_gemv_plan": (i32, [vp, i32, vp]),
+    "emu_gemv_fp8_thin_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "emu_linear_fp8w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_mxfp4_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
     "emu_linear_fp4w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

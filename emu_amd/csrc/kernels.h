@@ -100,6 +100,13 @@ int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s, bool tail_ok = false)
 // fp4_mfma_ok(a, 17, INT_MAX, tail_ok)
 bool gemm_fp4_ok(const GemvArgs& a);
 int launch_gemm_fp4(const GemvArgs& a, hipStream_t s, bool tail_ok = false);
+// fp8 weights (a.wscale set; W = e4m3 bytes, ldw in bytes) for 1..16 rows on the matrix cores (gemv_fp8_thin.hip): LDS-DMA stages,
+// the bytes converted in registers, v_mfma_f32_16x16x32_bf16, the row scale and store_c4 in the epilogue.  gemv_fp8_thin_plan is the
+// launch geometry from integers (status -22: K < 256 or K % 256, ldw % 16, ldx % 8, M outside 1..16, an epilogue other than NONE /
+// RESID / SWIGLU); gemv_fp8_thin_ok adds what only the argument block knows (16-byte aligned W and x, no fused norm, res for RESID)
+emu_gemv_fp8_thin_plan_t gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune);
+bool gemv_fp8_thin_ok(const GemvArgs& a);
+int launch_gemv_fp8_thin(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

@@ -510,13 +510,25 @@ class LlamaEngine:
         self._fp8["lm_head"] = (q, sc)
         check(lib().emu_llama_set_head_fp8(self.handle, q.data_ptr(), sc.data_ptr()), "emu_llama_set_head_fp8")
 
-    def use_fp8(self, enable: bool = True, prefill: bool = False) -> None:
-        """Switch the decode stream between the bf16 and the fp8 weights (invalidates captured decode graphs).
-        ``prefill=True`` also runs the prefill GEMMs W8A8 on the block-scaled fp8 MFMA (activations quantised per row)."""
+    def use_fp8(self, enable: bool = True, prefill: bool = False, wide: bool = False) -> None:
+        """Switch the decode stream between the bf16 and the fp8 weights (invalidates captured decode graphs).  The matrices are
+        quantised on the device first (``quantize_fp8``).  Exclusive with ``use_fp4``.
+
+        ``use_fp8(True)``: steps of B*T <= 2 rows (greedy / sampled decode) stream the fp8 set; everything else streams bf16.
+        ``prefill=True`` also runs the prefill GEMMs (17 rows and more) W8A8 on the block-scaled fp8 MFMA (activations quantised per
+        row).
+        ``wide=True``: steps of 3..16 rows (the default 5-beam search, a batch of prompts, contrastive search, ``score(via="decode")``
+        on a few candidates) stream the fp8 set as well, through the matrix-core kernel (csrc/gemv_fp8_thin.hip; weight-only: the
+        activations stay bf16, as at 1..2 rows); needs hidden, heads_local * head_dim and ffn_local to be multiples of 256 (the
+        library refuses otherwise and says why: every TP = 1 / 2 sharding of the 33B shapes runs, the TP = 4 / 8 shards do not).
+        Without ``wide`` those steps stream bf16, as they always did.  Not a reference feature; quality on a trained checkpoint is
+        unmeasured."""
         if enable and not self.bf16_released:   # (after release_bf16 the library refuses and says why)
             self.quantize_fp8()
-        check(lib().emu_llama_use_fp8(self.handle, (2 if prefill else 1) if enable else 0), "emu_llama_use_fp8", self.ctx.handle)
+        mode = ((2 if prefill else 1) + (2 if wide else 0)) if enable else 0
+        check(lib().emu_llama_use_fp8(self.handle, mode), "emu_llama_use_fp8", self.ctx.handle)
         self.fp8_decode = bool(enable)
+        self.fp8_wide = bool(enable and wide)
         self._mode_changed()
 
     def fp8_dequantized(self, key: str) -> torch.Tensor:

@@ -117,6 +117,16 @@ typedef struct {
     int grid, block, partition;
 } emu_gemv_plan_t;
 int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
+/* CPU test hook (tests/test_fp8_wide_host.py): what emu_linear_fp8w_thin_bf16 would launch for M rows over an fp8 matrix [N, K]
+ * (ldx in bf16 elements, ldw in bytes) under tune (emu_gemm_tune) -- host arithmetic only.  rows: weight rows per workgroup (16 / 32;
+ * grid = ceil(N / rows)); mb: the built activation-row bucket (8 / 16); kc: k per stage; stages: depth of the LDS ring; lds_bytes =
+ * stages * (rows * kc + mb * kc * 2); block = 256.  Returns the status the launch would: 0, or -22 (then the other fields are 0)
+ * for M outside 1..16, K < 256 or K % 256 != 0, ldw % 16 != 0, ldx % 8 != 0, a stride below K, an epilogue other than NONE / RESID /
+ * SWIGLU, or an odd N under SWIGLU. */
+typedef struct {
+    int status, rows, mb, kc, stages, lds_bytes, grid, block;
+} emu_gemv_fp8_thin_plan_t;
+int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out);
 /* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bits 0, 4, 5, 14, 17 and 18: retired,
  * ignored.  Bit 1: the K-slice workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before
  * round 3) instead of the XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip)
@@ -133,7 +143,8 @@ int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
  * 256x256 configuration, whatever epilogue, slices and raggedness), 23 = its fp32 K-slices leave by direct stores instead of
  * through LDS; bits 24-25 (the MXFP4 weight stream, gemv_fp4.hip; tools/fp4_time.py --ab): 1 / 2 / 3 = 1 / 2 / 4 row sets per
  * workgroup instead of the planned number, bits 26-27: 1 / 2 = 4 / 8 weight rows per lane; bits 28-29 (the few-row MXFP4 stream,
- * gemv_fp4_thin.hip; tools/fp4_wide_time.py --ab): 1 / 2 = 16 / 32 weight rows per workgroup instead of the heuristic;
+ * gemv_fp4_thin.hip; tools/fp4_wide_time.py --ab) and the few-row fp8 stream (gemv_fp8_thin.hip; tools/fp8_wide_time.py --ab): 1 / 2 =
+ * 16 / 32 weight rows per workgroup instead of the heuristic;
  * bit 17 (tests): one-row bf16 streams skip the wave and single-round-trip forms, so a small matrix reaches the block kernel's head /
  * preload form; bit 30: no L2 warming anywhere (emu_llama_set_l2_warm's plans are all empty: the same-build twin of a warmed run). */
 void emu_gemm_tune(int mask);
@@ -188,6 +199,16 @@ int emu_linear_fp8_bf16(const void* A8, const float* a_scale, const void* W8, co
 int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res,
                          const void* norm_w, void* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc,
                          float eps, int epi, emu_stream_t s);
+/* The same weights for 1 <= M <= 16 rows on the matrix cores (gemv_fp8_thin.hip: LDS-DMA stages, the e4m3 bytes converted to bf16
+ * in registers -- lossless --, v_mfma_f32_16x16x32_bf16, fp32 accumulation; the activations stay bf16):
+ *   C[m, n] = epi(bf16(wscale[n] * sum_k fp8(W8[n,k]) * A[m,k] + bias[n]))
+ * epi in {NONE, RESID, SWIGLU}; the row scale is multiplied in fp32 ahead of the bias, the sum is rounded to bf16 after the bias, then
+ * the residual is added or SiLU(gate) * up formed (the rounding points of the bf16 few-row stream; they may differ in the last bit from
+ * emu_linear_fp8w_bf16's kernel).  No fused RMSNorm (normalise first).  N >= 1, K >= 256 and K % 256 == 0, ldw % 16 == 0 (bytes),
+ * lda % 8 == 0, both at least K, A / W8 16-byte aligned, N even under SWIGLU; anything else -22, nothing is launched and nothing
+ * falls back.  emu_linear_fp8w_bf16 keeps answering -22 for M > 2.  Not a reference feature. */
+int emu_linear_fp8w_thin_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C,
+                              int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s);
 /* MXFP4 (OCP microscaling) weights, the 4-bit weight-only stream; emu_amd/mxfp4.py is the definition of the format.
  *   elements  uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j+1 in the high nibble; a code is a sign bit (8) and an
  *             E2M1 magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}
@@ -501,7 +522,13 @@ int emu_llama_set_layer(emu_llama* m, int layer, const void* wqkv, const void* w
  * layout as the bf16 weight; scale: fp32 [rows], W ~= fp8 * scale[row].  emu_llama_use_fp8(m, 1): decode rows (B*T <= 2)
  * stream them, prefill keeps the bf16 weights; (m, 2): prefill rows (B*T > 16) run W8A8 GEMMs as well -- activations
  * quantised per row ahead of every GEMM, emu_linear_fp8_bf16 -- when hidden, heads_local*head_dim and ffn_local are
- * multiples of 128 (BASELINE.json configs[4], "fp8 MFMA weights"); (m, 0): bf16.  Fails if the fp8 tensors were not registered. */
+ * multiples of 128 (BASELINE.json configs[4], "fp8 MFMA weights"); (m, 0): bf16.  Fails if the fp8 tensors were not registered.
+ * emu_llama_use_fp8(m, 3) is mode 1 and (m, 4) is mode 2 plus: every forward / logits call of 3 <= B*T <= 16 rows (a 5-beam step, a
+ * batch of prompts, contrastive search) streams the fp8 set through emu_linear_fp8w_thin_bf16's kernel -- qkv, o_proj, gate/up, down
+ * and the head where it has an fp8 copy (whole or emu_llama_set_head_shard rows); the RMSNorm launches of the bf16 few-row path stay,
+ * attention is untouched.  Modes 3 and 4 fail (-22, with a message) unless hidden, heads_local*head_dim and ffn_local are multiples
+ * of 256 (every TP = 1 / 2 sharding of the 33B shapes; the TP = 4 / 8 shards are refused).  Modes 0..2 are what they were.
+ * Accuracy on a trained checkpoint is unmeasured. */
 int emu_llama_set_layer_fp8(emu_llama* m, int layer, const void* wqkv8, const float* sqkv, const void* wo8,
                             const float* so, const void* wgu8, const float* sgu, const void* wdown8,
                             const float* sdown);
@@ -536,10 +563,12 @@ int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_sc
 int emu_llama_use_fp4(emu_llama* m, int enable);
 int emu_llama_release_bf16(emu_llama* m);
 /* CPU test hook (tests/test_llama_weight_kernel.py): the one rule by which emu_llama_forward and emu_llama_logits pick a projection's
- * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..2 / fp4_mode 0..3 as emu_llama_use_fp8 /
+ * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..4 / fp4_mode 0..3 as emu_llama_use_fp8 /
  * emu_llama_use_fp4 take them (never both non-zero), rows = B*T of the call, the shard's hidden, heads_local*head_dim and ffn_local.
  * Returns 0 bf16, 1 the fp8 stream (1..2 rows), 2 W8A8 GEMMs (17 rows and more; in the layers that have fp8 weights), 3 the MXFP4
- * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more).  The head runs 2 as bf16. */
+ * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more), 7 the fp8 matrix-core
+ * stream (3..16 rows in fp8 modes 3 / 4 when the three widths are multiples of 256; other widths: 0 there) -- 6 is
+ * emu_llama_pack_kernel's.  The head runs 2 as bf16. */
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local);
 /* The 13-bit lossless packing of a bf16 weight matrix for the one-row decode streams; emu_amd/bf16pack.py is the definition of the
  * format and emu_amd/csrc/bf16_pack.h states the layout once for the packer and the kernels.  A weight keeps its low byte and its

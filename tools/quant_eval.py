@@ -3,7 +3,7 @@
 decode kernels (``LlamaEngine.score(via="decode")``), bf16 first, then each mode asked for with the bf16 logits as the reference
 (needs a GPU):
 
-    python tools/quant_eval.py [--checkpoint PATH] [--prompts FILE.jsonl] [--modes fp8,fp4,fp4-wide] [--out profiles/quant_eval.md]
+    python tools/quant_eval.py [--checkpoint PATH] [--prompts FILE.jsonl] [--modes fp8,fp8-wide,fp4,fp4-wide] [--out profiles/quant_eval.md]
 
 Per mode: mean NLL per scored token and its difference from bf16, mean and max KL(bf16 || mode), top-1 agreement with bf16, and
 ms per scored token (hipGraph-replayed steps, host clock between device synchronisations, the second of two runs).
@@ -15,9 +15,9 @@ a mode moves random-init logits; they say NOTHING about a trained checkpoint.
 ``--n`` synthetic prompts of ``--prompt-len`` random ids with ``--cont-len`` continuation ids: half of each continuation is the
 bf16 run's own greedy choice (tokens a model finds likely), half random ids (tokens it finds unlikely).
 
-Rows per step follow the stream under test: fp8 and fp4 stream one-row steps (``use_fp8`` / ``use_fp4(True)``: 1-2 rows), fp4-wide
-the 3-16-row steps (``use_fp4(True, wide=True)``), so that mode scores ``--wide-rows`` prompts at a time; bf16 is run at the same
-row count for each.
+Rows per step follow the stream under test: fp8 and fp4 stream one-row steps (``use_fp8`` / ``use_fp4(True)``: 1-2 rows), fp8-wide
+and fp4-wide the 3-16-row steps (``use_fp8(True, wide=True)`` / ``use_fp4(True, wide=True)``), so those modes score ``--wide-rows``
+prompts at a time; bf16 is run at the same row count for each.
 """
 import argparse
 import json
@@ -44,12 +44,14 @@ def set_mode(lm, mode):
         lm.use_fp4(False)
     if mode == "fp8":
         lm.use_fp8(True)
+    elif mode == "fp8-wide":
+        lm.use_fp8(True, wide=True)
     elif mode == "fp4":
         lm.use_fp4(True)
     elif mode == "fp4-wide":
         lm.use_fp4(True, wide=True)
     elif mode != "bf16":
-        raise SystemExit(f"unknown mode {mode!r}: fp8, fp4, fp4-wide")
+        raise SystemExit(f"unknown mode {mode!r}: fp8, fp8-wide, fp4, fp4-wide")
 
 
 def batches(items, rows):
@@ -97,7 +99,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--prompts", default=None)
-    ap.add_argument("--modes", default="fp8,fp4,fp4-wide")
+    ap.add_argument("--modes", default="fp8,fp8-wide,fp4,fp4-wide")
     ap.add_argument("--layers", type=int, default=8, help="synthetic weights only: decoder layers at the 33B widths")
     ap.add_argument("--n", type=int, default=8)
     ap.add_argument("--prompt-len", type=int, default=48)
@@ -108,7 +110,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("quant_eval.py measures on a GPU; none found")
     if not 3 <= a.wide_rows <= 16:
-        sys.exit("--wide-rows must be in 3..16 (the row counts the wide MXFP4 stream serves)")
+        sys.exit("--wide-rows must be in 3..16 (the row counts the wide fp8 and MXFP4 streams serve)")
     modes = [m for m in a.modes.split(",") if m]
     dev = torch.device("cuda", torch.cuda.current_device())
     lcfg = LlamaCfg() if a.checkpoint else LlamaCfg(num_hidden_layers=a.layers)
@@ -122,7 +124,7 @@ def main():
         weights = f"SYNTHETIC weights (seed 0), {a.layers} layers at the 33B widths"
     if not lm.ready:
         sys.exit("the LLaMA weights are incomplete")
-    if "fp8" in modes:
+    if "fp8" in modes or "fp8-wide" in modes:
         lm.quantize_fp8()
 
     if a.prompts:
@@ -151,7 +153,7 @@ def main():
               "|---|---|---|---|---|---|---|---|---|"]
     base = {}
     for mode in modes:
-        rows = a.wide_rows if mode == "fp4-wide" else 1
+        rows = a.wide_rows if mode in ("fp8-wide", "fp4-wide") else 1
         if rows not in base:
             set_mode(lm, "bf16")
             res, ms = run(lm, items, rows, keep_logits=True)
