@@ -117,3 +117,23 @@ def unpack(p: Dict[str, object]) -> Tuple[torch.Tensor, torch.Tensor]:
     bits = bits.reshape(G * R, K)[:N]
     w = torch.where(bits >= 2 ** 15, bits - 2 ** 16, bits).to(torch.int16).view(torch.bfloat16)
     return w, flagged_groups(p).repeat_interleave(R)[:N]
+
+
+def default_pack(env, world_size: int, bf16_released: bool, need: int, free: int) -> str:
+    """Which matrices of a loaded model get a packed set by default -> "off" | "plain" | "all".  "plain": o_proj and down (the two-row
+    streams, what ``LlamaEngine`` packs by itself at load); "all": qkv, gate/up and lm_head too (the head form, 8 rows per workgroup:
+    profiles/bf16_pack_head8.md).  A pure function of scalars, so a CPU test can enumerate it (tests/test_pack_default_rule.py).
+
+    ``env``: the value of EMU_BF16_PACK or None ("0" = off, "plain", "all" or unset = all; anything else is read as unset);
+    ``world_size``: tensor-parallel ranks -- more than one stays plain: a shard's qkv and gate/up do take the head form, but nothing at
+    TP has been timed on hardware; ``bf16_released``: flagged row groups read the bf16 matrices, so nothing is packed without them;
+    ``need`` / ``free``: bytes of the head-form sets still missing and free device bytes -- sets that would take more than half of what
+    is free are not added (the KV cache and the workspaces need the rest), which leaves what the engine's own rule, the same one over
+    the plain sets, decided at load."""
+    if env == "0" or bf16_released:
+        return "off"
+    if env == "plain" or world_size > 1:
+        return "plain"
+    if 2 * int(need) > int(free):
+        return "plain"
+    return "all"

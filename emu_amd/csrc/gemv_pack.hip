@@ -3,9 +3,9 @@
 //   head form, fused RMSNorm      gemv_kernel<4, 1, true, EPI, -1>       qkv, gate/up (SwiGLU), lm_head
 //   preload form                  gemv_kernel<2, 1, false, EPI, 4>       o_proj
 //   single round trip             gemv_rt_kernel<2, 9, false, EPI, false> down_proj
-// Same rows per workgroup, same column-to-thread partition, same order of the v_dot2c chain, same wave / LDS reductions, same epilogue
-// rounding points: only the fetch and the in-register decode in front of bf16_dot2 differ, so the outputs are the bf16 kernels' bit for
-// bit.  13/16 of the HBM bytes.  A workgroup whose row group is flagged (a weight outside the matrix's 32-binade window) streams the
+// Same rows per workgroup (the head form: two of the bf16 kernel's 4-row groups, so half as many workgroups normalise x), same
+// column-to-thread partition, same order of the v_dot2c chain, same wave / LDS reductions, same epilogue rounding points: only the
+// fetch and the in-register decode in front of bf16_dot2 differ, so the outputs are the bf16 kernels' bit for bit.  13/16 of the HBM bytes.  A workgroup whose row group is flagged (a weight outside the matrix's 32-binade window) streams the
 // bf16 rows through the same registers instead; the branch is workgroup-uniform.  The packed loads of the first trip / the preload
 // are requested before the flag word is back, so the flag costs an unflagged workgroup no latency.  No workgroup waits for another.
 #include "common.h"
@@ -129,22 +129,30 @@ __device__ __forceinline__ void pack_reduce(float (&acc)[R], float (*red)[R], fl
 }
 
 // ---- head form (gemv_kernel<4, 1, true, EPI, -1>): x, the gain and the first trip are requested before the RMSNorm statistics are
-// reduced through a raw s_barrier; trips 1..3 stream behind it through two register sets
-template <int EPI>
-__global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, const PackSet p) {
+// reduced through a raw s_barrier; trips 1..3 stream behind it through two register sets.  A workgroup owns G adjacent 4-row groups
+// of the R = 4 set (groups G b .. G b + G - 1): the column-to-thread partition, every row's v_dot2c chain over trips 0..3, the wave and
+// 4-wave reductions and the epilogue rounding points are the 4-row kernel's, only the number of rows that share one normalisation of
+// x differs, so the outputs stay the bf16 kernel's bits.  A group past the last one (an odd group count) is clamped to the last group
+// for every load and its rows fail the epilogue's n < N.  G = 2: a workgroup with a flagged group streams the bf16 rows of all 8, one
+// trip at a time through the registers of both sets (8 rows x 4 dwords do not fit one); rare, it only has to be exact.
+template <int EPI, int G>
+__global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, const PackSet p, const int groups) {
     constexpr int R = 4;
-    __shared__ float red[4][R];
-    __shared__ float fin[R];
+    __shared__ float red[4][R * G];
+    __shared__ float fin[R * G];
     __shared__ float ssp[4];
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int KV = a.K >> 3;
-    const int n0 = blockIdx.x * R;
-    const uint32_t fw = p.flags[blockIdx.x >> 5];
-    const PackPtrs<R> q = pack_ptrs<R>(a, p, blockIdx.x);
+    const int n0 = blockIdx.x * R * G;
+    const int g0 = blockIdx.x * G;                                     // (G = 2: g0 is even, so both groups' flags share a word)
+    const uint32_t fw = p.flags[g0 >> 5];
+    PackPtrs<R> q[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) q[j] = pack_ptrs<R>(a, p, g0 + j < groups ? g0 + j : groups - 1);
 
     u32x4 hx[4], hg[4];
-    PackRaw<R> hw, w1;
+    PackRaw<R> hw[G], w1[G];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int vi = tid + 256 * c;
@@ -153,9 +161,15 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
         hg[c] = ld16(a.norm_w + vc * 8);
     }
     const int v0 = tid < KV ? tid : KV - 1;                            // short rows (K < 2048): clamped, against a zero operand
-    fetch_packed<R>(q, v0, hw);
-    const bool flagged = (fw >> (blockIdx.x & 31)) & 1u;
-    if (flagged) fetch_bf16<R>(q, v0, hw);
+#pragma unroll
+    for (int j = 0; j < G; ++j) fetch_packed<R>(q[j], v0, hw[j]);
+    bool flagged = false;
+#pragma unroll
+    for (int j = 0; j < G; ++j) flagged = flagged || (g0 + j < groups && ((fw >> ((g0 + j) & 31)) & 1u));
+    if (flagged) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) fetch_bf16<R>(q[j], v0, hw[j]);
+    }
     float ss = 0.f;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -180,27 +194,52 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
         hx[c] = pack8(xf);
     }
 
-    float acc[R];
+    float acc[G][R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.f;
-    auto fetch = [&](PackRaw<R>& w, int c) {
-        const int vi = tid + 256 * c;
-        if (vi < KV) {
-            if (flagged) fetch_bf16<R>(q, vi, w); else fetch_packed<R>(q, vi, w);
-        }
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[j][r] = 0.f;
+    auto dots = [&](bool fl, const PackRaw<R> (&w)[G], const u32x4& xp) {
+#pragma unroll
+        for (int j = 0; j < G; ++j) pack_dots<R>(q[j], fl, w[j], xp, acc[j]);
     };
-    fetch(w1, 1);
-    pack_dots<R>(q, flagged, hw, hx[0], acc);
-    __builtin_amdgcn_sched_barrier(0);
-    fetch(hw, 2);
-    if (tid + 256 < KV) pack_dots<R>(q, flagged, w1, hx[1], acc);
-    __builtin_amdgcn_sched_barrier(0);
-    fetch(w1, 3);
-    if (tid + 512 < KV) pack_dots<R>(q, flagged, hw, hx[2], acc);
-    if (tid + 768 < KV) pack_dots<R>(q, flagged, w1, hx[3], acc);
+    if (flagged) {
+        dots(true, hw, hx[0]);
+#pragma unroll
+        for (int c = 1; c < 4; ++c) {
+            const int vi = tid + 256 * c;
+            if (vi < KV) {
+#pragma unroll
+                for (int j = 0; j < G; ++j) fetch_bf16<R>(q[j], vi, hw[j]);
+                dots(true, hw, hx[c]);
+            }
+        }
+    } else {
+        auto fetch = [&](PackRaw<R> (&w)[G], int c) {
+            const int vi = tid + 256 * c;
+            if (vi < KV) {
+#pragma unroll
+                for (int j = 0; j < G; ++j) fetch_packed<R>(q[j], vi, w[j]);
+            }
+        };
+        fetch(w1, 1);
+        dots(false, hw, hx[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(hw, 2);
+        if (tid + 256 < KV) dots(false, w1, hx[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(w1, 3);
+        if (tid + 512 < KV) dots(false, hw, hx[2]);
+        if (tid + 768 < KV) dots(false, w1, hx[3]);
+    }
 
-    pack_reduce<R>(acc, red, fin, tid);
-    pack_epilogue<R, EPI>(a, fin, n0, tid);
+    float accf[R * G];
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int r = 0; r < R; ++r) accf[j * R + r] = acc[j][r];
+    pack_reduce<R * G>(accf, red, fin, tid);
+    pack_epilogue<R * G, EPI>(a, fin, n0, tid);
 }
 
 // ---- the two plain forms of two rows per workgroup, every load requested up front.  CLAMP: the preload form (gemv_kernel<2, 1, false,
@@ -284,9 +323,15 @@ int launch_gemv_pack(const GemvArgs& a, const PackSet& p, int form, hipStream_t 
     return 0;
     if (form == GEMV_FORM_HEAD) {
         if (p.rows != 4 || !a.norm_w || KV > 1024) return -22;
-        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH(gemv_pack_head_kernel<EPI_NONE>, 4) }
-        if (a.epi == EPI_SWIGLU && !(a.N & 1)) { EMU_PACK_LAUNCH(gemv_pack_head_kernel<EPI_SWIGLU>, 4) }
-        return -22;
+        if (a.epi != EPI_NONE && (a.epi != EPI_SWIGLU || (a.N & 1))) return -22;
+        const int groups = (int)pack_groups(a.N, 4);                 // two groups (8 rows) per workgroup
+#define EMU_PACK_HEAD(EPI)                                                                                           \
+    hipLaunchKernelGGL((gemv_pack_head_kernel<EPI, 2>), dim3((groups + 1) / 2), dim3(256), 0, s, a, p, groups);      \
+    EMU_CHECK_LAUNCH();                                                                                              \
+    return 0;
+        if (a.epi == EPI_NONE) { EMU_PACK_HEAD(EPI_NONE) }
+        EMU_PACK_HEAD(EPI_SWIGLU)
+#undef EMU_PACK_HEAD
     }
     if (p.rows != 2 || a.norm_w) return -22;
     if (form == GEMV_FORM_PRELOAD) {

@@ -162,6 +162,8 @@ class EmuModel:
             missing.append("visual.*")
         if not self.decoder.lm.ready:
             missing.append("decoder.lm.*")
+        else:
+            self.decoder.lm.pack_bf16_default()                # the 13-bit sets of qkv, gate/up and lm_head (bf16pack.default_pack)
         if self.project_up is None:
             missing.append("project_up.weight")
         if self.project_down is None:

@@ -265,6 +265,8 @@ class Emu:
         missing = [n for n, ok in (("visual.*", self.visual.ready), ("cformer.*", self.cformer.ready),
                                    ("decoder.lm.*", self.lm.ready), ("ln_visual.*", self.ln_w is not None and self.ln_b is not None))
                    if not ok]
+        if self.lm.ready:
+            self.lm.pack_bf16_default()                        # the 13-bit sets of qkv, gate/up and lm_head (bf16pack.default_pack)
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for Emu: missing {missing}, unexpected {unexpected[:5]}")
         return missing, unexpected

@@ -407,8 +407,8 @@ class LlamaEngine:
 
     def _pack_rows(self, key: str, tune: int, head_form: bool) -> int:
         """Rows per group of the packed set of ``key`` (the form the planner names for its one-row stream), 0 = the matrix stays bf16.
-        The head form's twin (4 rows, fused RMSNorm: qkv, gate/up, lm_head) measured SLOWER than its bf16 kernel on MI355X
-        (profiles/bf16_pack.md), so those matrices get a set only when ``head_form`` asks for it."""
+        The head form's matrices (sets of 4 rows, fused RMSNorm: qkv, gate/up, lm_head) get a set only when ``head_form`` asks for it:
+        the engine by itself packs the two plain streams, ``pack_bf16_default`` adds these (profiles/bf16_pack_head8.md)."""
         w = self.lm_head if key == "lm_head" else self._keep[key]
         norm, epi = (1, ops.EPI_NONE) if key == "lm_head" else self._PACK_KINDS[key.split(".")[1]]
         N, K = w.shape
@@ -467,7 +467,7 @@ class LlamaEngine:
         """The default: when the engine is ready, pack and switch the stream on -- unless EMU_BF16_PACK=0, the library predates the
         stream (a tools A/B run against an older build), no matrix has a packed twin (small models, tensor-parallel shards), or the
         sets would take more than half of the free device memory (the KV cache and the workspaces need the rest).  EMU_BF16_PACK=all
-        packs the head-form matrices too (A/B aid)."""
+        packs the head-form matrices here too; a model's loader adds them by default (``pack_bf16_default``)."""
         if os.environ.get("EMU_BF16_PACK", "1") == "0" or self.bf16_released or not hasattr(lib(), "emu_llama_use_bf16_pack"):
             return
         pk = getattr(self, "_pack", {})
@@ -486,6 +486,33 @@ class LlamaEngine:
         self.use_bf16_pack(True)
         print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s",
               file=sys.stderr)
+
+    def pack_bf16_default(self) -> str:
+        """The model-level default (``EmuModel.load_weights`` / ``Emu.load_state_dict`` call it once the engine is ready): on top of
+        what ``_auto_pack_bf16`` packed at load, the head-form matrices (qkv, gate/up, lm_head), whose packed twin of 8 rows per
+        workgroup beats the bf16 kernel (profiles/bf16_pack_head8.md) -- where ``bf16pack.default_pack`` says "all".  Packs what is
+        missing, so a second call packs nothing and a reloaded matrix (its stale set dropped) gets a fresh one.  Returns the rule's
+        answer."""
+        if not self.ready or not hasattr(lib(), "emu_llama_use_bf16_pack"):
+            return "off"
+        pk = getattr(self, "_pack", {})
+        todo = [(k, self._pack_rows(k, 0, True)) for k in self._pack_keys() if k not in pk] if not self.bf16_released else []
+        need = sum(bf16pack.packed_bytes(*(self.lm_head if k == "lm_head" else self._keep[k]).shape, r) for k, r in todo if r)
+        free = torch.cuda.mem_get_info(self.device)[0] if need else 0
+        rule = bf16pack.default_pack(os.environ.get("EMU_BF16_PACK"), self.ctx.tp_size, self.bf16_released, need, free)
+        if rule != "all" or not need:
+            if rule == "plain" and need and self.ctx.tp_size == 1 and os.environ.get("EMU_BF16_PACK") != "plain":
+                print(f"emu_amd: bf16 pack stream: the head-form sets need {need / 2**30:.1f} GiB, {free / 2**30:.1f} GiB are free; "
+                      "qkv, gate/up and lm_head stay bf16", file=sys.stderr)
+            return rule
+        t0 = time.time()
+        n, nbytes = self.pack_bf16(head_form=True)
+        torch.cuda.synchronize(self.device)
+        self.use_bf16_pack(True)
+        total = sum(bf16pack.packed_bytes(*v["shape"], v["rows"]) for v in self._pack.values())
+        print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s"
+              f"; {len(self._pack)} matrices, {total / 2**30:.2f} GiB of sets in all", file=sys.stderr)
+        return rule
 
     # ------------------------------------------------------------------ optional fp8 decode stream
     def quantize_fp8(self) -> None:
