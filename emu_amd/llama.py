@@ -20,7 +20,7 @@ from ._lib import Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, li
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
-from .sampling import beam_draw_margin, beam_reference_select
+from .sampling import beam_draw_margin, beam_reference_select, beam_scorer_step, beam_start_state, beam_topk
 from .scoring import IGNORE_INDEX, split_segments
 from .tp import ShardPlan
 
@@ -1411,7 +1411,6 @@ class LlamaEngine:
         pos = next_pos.repeat_interleave(nb).contiguous()
 
         max_len = max_new_tokens
-        NEG = -1.0e9
         # The deterministic mode (the reference's default) runs each step's selection and bookkeeping in ONE kernel (emu_beam_step_bf16
         # or a variant of it); whatever the route leaves to the host, and any logits but the HIP engine's bf16, keep the torch pipeline
         # below.
@@ -1426,50 +1425,26 @@ class LlamaEngine:
                                             sampler=(sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id,
                                                                    min_len, eos_id, pad_id, min_keep=2), uniforms), **route.device_kw)
         logits = logits.float()
-        running_seq = torch.full((B, nb, max_len), pad_id, dtype=torch.int64, device=dev)
-        sequences = running_seq.clone()
-        running_scores = torch.zeros(B, nb, device=dev)
-        if not (do_sample and hf_semantics == "4.31"):
-            running_scores[:, 1:] = NEG             # 4.31's beam_sample starts EVERY beam at 0 (the draws tell them apart)
-        beam_scores = torch.full((B, nb), NEG, device=dev)
-        finished = torch.zeros(B, nb, dtype=torch.bool, device=dev)
-        seq_len = torch.zeros(B, nb, dtype=torch.int64, device=dev)                     # generated length of kept results
-        heuristic_open = torch.ones(B, 1, dtype=torch.bool, device=dev)
-        top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
-        gather = lambda t, idx: torch.gather(t, 1, idx.reshape(B, -1, *([1] * (t.dim() - 2))).expand(-1, -1, *t.shape[2:]))
+        v431 = hf_semantics == "4.31"
+        old = do_sample and v431
+        st = beam_start_state(B, nb, max_len, pad_id, dev, equal_start=old)     # (4.31's beam_sample starts EVERY beam at 0)
         hid = torch.empty(B * nb, H, device=dev, dtype=BF16)
 
         cur = 0
         lp_rows = logits[:, None, :].expand(B, nb, V)                                   # step 0: every beam = the prompt
         margin = draw_margin = float("inf")
-        v431 = hf_semantics == "4.31"
-        old = do_sample and v431
         table = uniforms is not None and do_sample
         # with a table the result has to be a function of the table alone, so ties between candidates (the rule, not the exception:
         # at step 0 every beam holds the same hypothesis) go to the first in candidate order, the device kernels' rule
         # ... and so does a constraint: it leaves fewer than 2N finite candidates, and which -inf entry a dead beam is fed must not
         # be left to torch.topk
         stable = table or allow_fn is not None
-        topk = torch.topk if not stable else \
-            (lambda t, k: tuple(r[:, :k] for r in torch.sort(t, dim=1, descending=True, stable=True)))
         # (such exact ties are decided alike on both sides and do not count as a margin; nor does -inf minus -inf)
         gap = (lambda d: float(d.min())) if not stable else \
             (lambda d: float(d.masked_fill((d == 0) | ~torch.isfinite(d), float("inf")).min()))
         while True:
-            log_probs = torch.log_softmax(lp_rows, dim=-1)
-            if do_sample or repetition_penalty != 1.0 or ngram or allow_fn is not None:
-                gen = running_seq[:, :, :cur].reshape(B * nb, cur)
-                log_probs = process_logits(log_probs.reshape(B * nb, V), gen, cur < min_len,
-                                           eos_id, do_sample and not old, temperature, top_k, top_p, repetition_penalty,
-                                           min_keep=2, no_repeat_ngram_size=ngram,
-                                           allowed=None if allow_fn is None else allowed_mask(allow_fn, gen, nb, V)).view(B, nb, V)
-            elif cur < min_len:
-                log_probs = log_probs.clone()
-                log_probs[..., eos_id] = -float("inf")
-            acc = log_probs + running_scores[:, :, None]
-            if old:                                    # 4.31 beam_sample: the warpers see the ACCUMULATED scores
-                acc = warp_logits(acc.reshape(B * nb, V), temperature, top_k, top_p, min_keep=2).view(B, nb, V)
-            acc = acc.reshape(B, nb * V)
+            acc = beam_host_scores(lp_rows, st["running_scores"], st["running_seq"], cur, min_len, eos_id, do_sample, old, temperature,
+                                   top_k, top_p, repetition_penalty, ngram, allow_fn).reshape(B, nb * V)
             if do_sample:
                 if table:                              # the draws of step cur from row cur of the table (emu_amd/sampling.py)
                     u = uniforms[cur].to(torch.float32)
@@ -1483,71 +1458,29 @@ class LlamaEngine:
                     top_lp, order = torch.sort(top_lp, descending=True, dim=1, stable=table)
                     top_idx = torch.gather(top_idx, 1, order)
             else:
-                top_lp, top_idx = topk(acc, k=2 * nb)
-            src_beam = top_idx // V
-            tok = top_idx % V
-            cand_seq = gather(running_seq, src_beam)
-            cand_seq[:, :, cur] = tok
-            at_limit = cur + 1 >= max_len
-            # 4.31: at the length limit the non-EOS candidates still become running beams (finalize adds them below)
-            hits = (tok == eos_id) if v431 else (tok == eos_id) | at_limit
-            # running beams for the next step: best N non-finished candidates
-            run_lp = top_lp + hits.float() * NEG
-            nxt = topk(run_lp, k=nb)[1]
-            if trace is not None and cur + 1 < max_len:
+                top_lp, top_idx = beam_topk(acc, 2 * nb, stable)
+            toks, flat, _, run_lp = beam_scorer_step(st, top_lp, top_idx, V, cur, max_len, length_penalty, eos_id, v431, stable)
+            cur += 1
+            if trace is not None and cur < max_len:
                 srt = torch.sort(run_lp, dim=1, descending=True)[0]
                 margin = min(margin, gap(srt[:, nb - 1] - srt[:, nb]))
-            running_seq = gather(cand_seq, nxt)
-            running_scores = torch.gather(run_lp, 1, nxt)
-            beam_idx = torch.gather(src_beam, 1, nxt)                                   # which old beam each new beam extends
-            # finished results: only the top-N candidates may finish; merge with the kept ones
-            # 4.31 BeamHypotheses.add: an EOS hypothesis is scored over the cur tokens ahead of the EOS
-            fin_lp = top_lp / float((cur if (v431 and cur > 0) else cur + 1) ** length_penalty)
-            fin_lp = fin_lp + (~heuristic_open).float() * NEG
-            just = hits & top_mask[None, :]
-            fin_lp = fin_lp + (~just).float() * NEG
-            m_seq = torch.cat((sequences, cand_seq), dim=1)
-            m_sc = torch.cat((beam_scores, fin_lp), dim=1)
-            m_fin = torch.cat((finished, just), dim=1)
-            m_len = torch.cat((seq_len, torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1)
-            keep = topk(m_sc, k=nb)[1]
-            sequences = gather(m_seq, keep)
-            beam_scores = torch.gather(m_sc, 1, keep)
-            finished = torch.gather(m_fin, 1, keep)
-            seq_len = torch.gather(m_len, 1, keep)
-            cur += 1
-            # early-stop heuristic (early_stopping=False): can the best running beam still beat the worst kept result?
-            # (4.31 is_done: the best of all 2N candidates, an EOS one included)
-            best_run = (top_lp[:, :1] if v431 else running_scores[:, :1]) / float(cur ** length_penalty)
-            worst_fin = torch.where(finished, beam_scores.min(dim=1, keepdim=True)[0], torch.full_like(beam_scores, NEG))
-            heuristic_open = heuristic_open & (best_run > worst_fin).any(dim=-1, keepdim=True)
-            if v431 and cur >= max_len:
-                # 4.31 finalize: the running beams (now L tokens) join the kept results at L ** length_penalty unless done
-                fin2 = running_scores / float(cur ** length_penalty) + (~heuristic_open).float() * NEG
-                m_sc = torch.cat((beam_scores, fin2), dim=1)
-                keep = topk(m_sc, k=nb)[1]
-                sequences = gather(torch.cat((sequences, running_seq), dim=1), keep)
-                beam_scores = torch.gather(m_sc, 1, keep)
-                finished = torch.gather(torch.cat((finished, torch.ones_like(finished)), dim=1), 1, keep)
-                seq_len = torch.gather(torch.cat((seq_len, torch.full((B, nb), cur, dtype=torch.int64, device=dev)), dim=1), 1, keep)
             # (every candidate is a hit exactly when the length limit is reached: a beam contributes EOS at most once, so the 2N
             # candidates are never all EOS -- known on the host, one device read per step instead of two)
-            if cur >= max_len or not bool(heuristic_open.any()):
+            if cur >= max_len or not bool(st["open"].any()):
                 break
             # advance the model: reorder the cache rows by beam, feed the chosen tokens
-            flat = (beam_idx + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
             ctx = S + cur - 1
             # beams of one prompt share the prompt's KV slots, so only the generated slots [S, ctx) move with the beam
             # permutation -- a few KB per layer instead of the whole live cache
             if ctx > S:
                 self.kcache[:, :, :, S:ctx] = self.kcache[:, flat, :, S:ctx]
                 self.vcache[:, :, :, S:ctx] = self.vcache[:, flat, :, S:ctx]
-            toks = running_seq[:, :, cur - 1].reshape(-1).to(torch.int32).contiguous()
-            ops.embed_gather(toks, self.embed, out=hid)
+            ops.embed_gather(toks.to(torch.int32).contiguous(), self.embed, out=hid)
             slot = torch.full((B * nb,), ctx, device=dev, dtype=torch.int32)
             self.forward(hid, B * nb, 1, pos, slot, kstart_b, ctx=ctx + 1)
             pos = pos + 1
             lp_rows = self.logits(hid).float().view(B, nb, V)
+        sequences, beam_scores, seq_len = st["sequences"], st["beam_scores"], st["seq_len"]
         self.set_kv_share(0, 0)
         nret = int(num_return_sequences)
         out_len = int(seq_len[:, :nret].max().item())
@@ -1702,6 +1635,32 @@ def process_logits(scores: torch.Tensor, generated: torch.Tensor, suppress_eos: 
     if do_sample:
         scores = warp_logits(scores, temperature, top_k, top_p, min_keep)
     return scores
+
+
+def beam_host_scores(lp_rows: torch.Tensor, running_scores: torch.Tensor, running_seq: torch.Tensor, cur: int, min_len: int,
+                     eos_id: int, do_sample: bool = False, old: bool = False, temperature: Optional[float] = None,
+                     top_k: Optional[int] = None, top_p: Optional[float] = None, repetition_penalty: float = 1.0, ngram: int = 0,
+                     allow_fn=None) -> torch.Tensor:
+    """The score half of a beam-search step on the host, ``acc`` [B, nb, V] fp32: log-softmax of the beams' logit rows ``lp_rows``
+    [B, nb, V], ``process_logits`` (min_keep = 2) over the ``cur`` ids every beam has generated (``running_seq`` [B, nb, >= cur]), the
+    running scores added.  ``old`` (4.31's ``beam_sample``): the warpers act on the ACCUMULATED scores instead of the log-probabilities.
+    With no processor on, the pipeline is skipped and only the min-length suppress of EOS remains.  ``allow_fn``: the constraint as
+    a callable (batch_id, ids) -> allowed ids, ``resolve_constraint``'s."""
+    B, nb, V = lp_rows.shape
+    log_probs = torch.log_softmax(lp_rows, dim=-1)
+    if do_sample or repetition_penalty != 1.0 or ngram or allow_fn is not None:
+        gen = running_seq[:, :, :cur].reshape(B * nb, cur)
+        log_probs = process_logits(log_probs.reshape(B * nb, V), gen, cur < min_len,
+                                   eos_id, do_sample and not old, temperature, top_k, top_p, repetition_penalty,
+                                   min_keep=2, no_repeat_ngram_size=ngram,
+                                   allowed=None if allow_fn is None else allowed_mask(allow_fn, gen, nb, V)).view(B, nb, V)
+    elif cur < min_len:
+        log_probs = log_probs.clone()
+        log_probs[..., eos_id] = -float("inf")
+    acc = log_probs + running_scores[:, :, None]
+    if old:                                    # 4.31 beam_sample: the warpers see the ACCUMULATED scores
+        acc = warp_logits(acc.reshape(B * nb, V), temperature, top_k, top_p, min_keep=2).view(B, nb, V)
+    return acc
 
 
 def tp_size_of(engine) -> int:

@@ -225,7 +225,8 @@ def top_p_threshold_group(logits: torch.Tensor, **opts) -> Tuple[torch.Tensor, t
 #   cannot supply ten tokens) the draw takes the lowest not-yet-drawn flat index whose acc is finite; removed entries are never drawn
 #   (with ``min_keep = 2`` there are always at least 2N finite entries).  Under ``order="4.31"`` the 2N draws are then sorted by score,
 #   descending, stably: equal scores keep draw order.
-# * The results are ``top_idx`` and ``top_lp = acc[top_idx]``, which the scorer's bookkeeping consumes unchanged.
+# * The results are ``top_idx`` and ``top_lp = acc[top_idx]``, which the scorer's bookkeeping (``beam_scorer_step`` below) consumes
+#   unchanged.
 
 BEAM_MIN_KEEP = 2          # the library's min_tokens_to_keep under beam search: one EOS id + 1
 
@@ -359,6 +360,114 @@ def beam_draw_margin(acc: torch.Tensor, nb: int, uniforms: torch.Tensor, draws: 
             t = float(torch.tensor(float(uniforms[b, k]), dtype=torch.float64) * R)
             out[b, k] = float((pos[:-1] - t).abs().min())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The beam scorer's bookkeeping (the second half of ``emu_beam_step_bf16`` / ``emu_beam_sample_step_bf16`` and of their trie and
+# n-gram variants): what one step does with the 2N candidates ``top_lp`` / ``top_idx`` of every prompt, whichever selection made them.
+# ``beam_scorer_step`` IS the host loop's step (``LlamaEngine.beam_search_generate`` calls it) and the kernels are tested against it;
+# tests/golden/beam_scorer_steps.npz pins it bit for bit to the statements as they stood inline in that loop.
+#
+# State per prompt (``beam_start_state``): N running beams (ids ``running_seq``, summed log-probabilities ``running_scores``), N kept
+# results (``sequences``, ``beam_scores`` = score / len ** length_penalty, ``finished``, ``seq_len``), and ``open``: may a running beam
+# still beat the worst kept result?  -1e9 (``BEAM_NEG``) marks an empty slot; it is ADDED to a score to take a candidate out.
+#
+# 1. Candidate k continues beam ``top_idx // V`` with token ``top_idx % V``.  It is a hit if the token is EOS or -- 5.x only -- the step
+#    is the last one.
+# 2. The N best non-hits, in candidate order among equals, are the running beams of the next step.
+# 3. A hit among the FIRST N candidates competes with the kept results at ``top_lp / n ** length_penalty``, n = cur + 1 tokens (4.31:
+#    the cur tokens ahead of the EOS, 1 at step 0), unless the prompt is closed; the N best of kept + new stay.
+# 4. ``open`` stays set while a kept slot is still empty or ``best / (cur + 1) ** length_penalty`` beats the worst kept result, best =
+#    the first running beam (4.31: the first candidate, an EOS one included).
+# 5. 4.31, last step: the running beams join the kept results at ``score / L ** length_penalty`` unless the prompt is closed (``finalize``).
+#
+# Every top-k is over at most 3N entries; ``stable`` settles its ties by position (the kernels' rule), otherwise ``torch.topk`` does.
+
+BEAM_NEG = -1.0e9
+
+
+def beam_start_state(B: int, nb: int, L: int, pad_id: int, device=None, equal_start: bool = False) -> dict:
+    """The state a search of B prompts x nb beams over at most L tokens starts from.  Beam 0 alone carries score 0 (at step 0 every
+    beam holds the same hypothesis); ``equal_start``: all do (4.31's ``beam_sample``: the draws tell them apart).  ``top_mask`` is the
+    constant "only the first N candidates may finish" of step 3."""
+    st = dict(running_seq=torch.full((B, nb, L), pad_id, dtype=torch.int64, device=device),
+              running_scores=torch.zeros(B, nb, device=device), beam_scores=torch.full((B, nb), BEAM_NEG, device=device),
+              finished=torch.zeros(B, nb, dtype=torch.bool, device=device), seq_len=torch.zeros(B, nb, dtype=torch.int64, device=device),
+              open=torch.ones(B, 1, dtype=torch.bool, device=device))
+    st["sequences"] = st["running_seq"].clone()
+    if not equal_start:
+        st["running_scores"][:, 1:] = BEAM_NEG
+    st["top_mask"] = torch.cat([torch.ones(nb, dtype=torch.bool, device=device), torch.zeros(nb, dtype=torch.bool, device=device)])
+    return st
+
+
+def beam_topk(t: torch.Tensor, k: int, stable: bool = True):
+    """(values, indices) [B, k] of the k largest per row of ``t`` [B, n], descending.  ``stable``: equal values keep ascending index (the
+    kernels' rule); otherwise ``torch.topk``, which leaves ties open."""
+    if not stable:
+        return torch.topk(t, k)
+    return tuple(r[:, :k] for r in torch.sort(t, dim=1, descending=True, stable=True))
+
+
+def beam_scorer_step(st: dict, top_lp: torch.Tensor, top_idx: torch.Tensor, V: int, cur: int, max_len: int, length_penalty: float,
+                     eos_id: int, v431: bool, stable: bool = True):
+    """Steps 1-5 for step ``cur`` on the candidates ``top_lp`` / ``top_idx`` [B, 2 nb]; updates ``st`` in place.  Returns (the tokens to
+    feed [B * nb] int64, the cache rows they continue [B * nb], the beam each new beam continues [B, nb], the candidates' scores with
+    the hits taken out [B, 2 nb]).  No host read."""
+    B, nb = st["running_scores"].shape
+    dev, NEG = top_lp.device, BEAM_NEG
+    running_seq, sequences, beam_scores, finished, seq_len, heuristic_open = (
+        st["running_seq"], st["sequences"], st["beam_scores"], st["finished"], st["seq_len"], st["open"])
+    topk = lambda t, k: beam_topk(t, k, stable)
+    gather = lambda t, idx: torch.gather(t, 1, idx.reshape(B, -1, *([1] * (t.dim() - 2))).expand(-1, -1, *t.shape[2:]))
+    src_beam = top_idx // V
+    tok = top_idx % V
+    cand_seq = gather(running_seq, src_beam)
+    cand_seq[:, :, cur] = tok
+    at_limit = cur + 1 >= max_len
+    # 4.31: at the length limit the non-EOS candidates still become running beams (finalize adds them below)
+    hits = (tok == eos_id) if v431 else (tok == eos_id) | at_limit
+    # running beams for the next step: best N non-finished candidates
+    run_lp = top_lp + hits.float() * NEG
+    nxt = topk(run_lp, k=nb)[1]
+    running_seq = gather(cand_seq, nxt)
+    running_scores = torch.gather(run_lp, 1, nxt)
+    beam_idx = torch.gather(src_beam, 1, nxt)                                   # which old beam each new beam extends
+    # finished results: only the top-N candidates may finish; merge with the kept ones
+    # 4.31 BeamHypotheses.add: an EOS hypothesis is scored over the cur tokens ahead of the EOS
+    fin_lp = top_lp / float((cur if (v431 and cur > 0) else cur + 1) ** length_penalty)
+    fin_lp = fin_lp + (~heuristic_open).float() * NEG
+    just = hits & st["top_mask"][None, :]
+    fin_lp = fin_lp + (~just).float() * NEG
+    m_seq = torch.cat((sequences, cand_seq), dim=1)
+    m_sc = torch.cat((beam_scores, fin_lp), dim=1)
+    m_fin = torch.cat((finished, just), dim=1)
+    m_len = torch.cat((seq_len, torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1)
+    keep = topk(m_sc, k=nb)[1]
+    sequences = gather(m_seq, keep)
+    beam_scores = torch.gather(m_sc, 1, keep)
+    finished = torch.gather(m_fin, 1, keep)
+    seq_len = torch.gather(m_len, 1, keep)
+    cur += 1
+    # early-stop heuristic (early_stopping=False): can the best running beam still beat the worst kept result?
+    # (4.31 is_done: the best of all 2N candidates, an EOS one included)
+    best_run = (top_lp[:, :1] if v431 else running_scores[:, :1]) / float(cur ** length_penalty)
+    worst_fin = torch.where(finished, beam_scores.min(dim=1, keepdim=True)[0], torch.full_like(beam_scores, NEG))
+    heuristic_open = heuristic_open & (best_run > worst_fin).any(dim=-1, keepdim=True)
+    if v431 and cur >= max_len:
+        # 4.31 finalize: the running beams (now L tokens) join the kept results at L ** length_penalty unless done
+        fin2 = running_scores / float(cur ** length_penalty) + (~heuristic_open).float() * NEG
+        m_sc = torch.cat((beam_scores, fin2), dim=1)
+        keep = topk(m_sc, k=nb)[1]
+        sequences = gather(torch.cat((sequences, running_seq), dim=1), keep)
+        beam_scores = torch.gather(m_sc, 1, keep)
+        finished = torch.gather(torch.cat((finished, torch.ones_like(finished)), dim=1), 1, keep)
+        seq_len = torch.gather(torch.cat((seq_len, torch.full((B, nb), cur, dtype=torch.int64, device=dev)), dim=1), 1, keep)
+    st.update(running_seq=running_seq, running_scores=running_scores, sequences=sequences, beam_scores=beam_scores, finished=finished,
+              seq_len=seq_len, open=heuristic_open)
+    flat = (beam_idx + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
+    toks = running_seq[:, :, cur - 1].reshape(-1)
+    return toks, flat, beam_idx, run_lp
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -6,11 +6,10 @@ import functools
 import torch
 
 from emu_amd import sampling
-from emu_amd.llama import process_logits
+from emu_amd.llama import beam_host_scores
 
 EOS, PAD = 2, 32000
 BF16 = torch.bfloat16
-NEG = -1.0e9
 THREADS = 1024                                        # the sample kernel's workgroup
 CHAT = dict(temperature=0.7, top_p=0.9)               # the chat demo's options
 PEN = dict(repetition_penalty=1.3, top_k=50, top_p=0.9)
@@ -79,70 +78,13 @@ def magnets(V):
     return [5, 17000, 32270] if V == 32274 else [5, V // 2, V - 4]
 
 
-def topk_stable(x, k):
-    v, i = torch.sort(x, dim=-1, descending=True, stable=True)
-    return v[..., :k], i[..., :k]
-
-
 def torch_step(st, lp_rows, cur, min_len, max_len, length_penalty, eos_id, v431=False, ngram=0):
-    """tests/test_gpu_beam.py::torch_step (one iteration of the torch pipeline of emu_amd/llama.py::beam_search_generate, its top-k
-    calls stable) with the host loop's ``process_logits(..., no_repeat_ngram_size=ngram)`` on the log-probabilities."""
+    """tests/test_gpu_beam.py::torch_step (one iteration of the host loop of emu_amd/llama.py::beam_search_generate, the stable
+    top-2N) with the host loop's ``process_logits(..., no_repeat_ngram_size=ngram)`` on the log-probabilities."""
     B, nb, V = lp_rows.shape
-    dev = lp_rows.device
-    gather = lambda t, idx: torch.gather(t, 1, idx.reshape(B, -1, *([1] * (t.dim() - 2))).expand(-1, -1, *t.shape[2:]))
-    log_probs = torch.log_softmax(lp_rows, dim=-1)
-    gen = st["running_seq"][:, :, :cur].reshape(B * nb, cur)
-    log_probs = process_logits(log_probs.reshape(B * nb, V), gen, cur < min_len, eos_id, False, no_repeat_ngram_size=ngram).view(B, nb, V)
-    acc = (log_probs + st["running_scores"][:, :, None]).reshape(B, nb * V)
-    top_lp, top_idx = topk_stable(acc, 2 * nb)
-    src_beam, tok = top_idx // V, top_idx % V
-    cand_seq = gather(st["running_seq"], src_beam)
-    cand_seq[:, :, cur] = tok
-    hits = (tok == eos_id) if v431 else (tok == eos_id) | (cur + 1 >= max_len)
-    run_lp = top_lp + hits.float() * NEG
-    nxt = topk_stable(run_lp, nb)[1]
-    st["running_seq"] = gather(cand_seq, nxt)
-    st["running_scores"] = torch.gather(run_lp, 1, nxt)
-    beam_idx = torch.gather(src_beam, 1, nxt)
-    fin_lp = top_lp / float((cur if (v431 and cur > 0) else cur + 1) ** length_penalty)
-    fin_lp = fin_lp + (~st["open"]).float() * NEG
-    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
-    just = hits & top_mask[None, :]
-    fin_lp = fin_lp + (~just).float() * NEG
-    m_seq = torch.cat((st["sequences"], cand_seq), dim=1)
-    m_sc = torch.cat((st["beam_scores"], fin_lp), dim=1)
-    m_fin = torch.cat((st["finished"], just), dim=1)
-    m_len = torch.cat((st["seq_len"], torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1)
-    keep = topk_stable(m_sc, nb)[1]
-    st["sequences"] = gather(m_seq, keep)
-    st["beam_scores"] = torch.gather(m_sc, 1, keep)
-    st["finished"] = torch.gather(m_fin, 1, keep)
-    st["seq_len"] = torch.gather(m_len, 1, keep)
-    best_run = (top_lp[:, :1] if v431 else st["running_scores"][:, :1]) / float((cur + 1) ** length_penalty)
-    worst_fin = torch.where(st["finished"], st["beam_scores"].min(dim=1, keepdim=True)[0], torch.full_like(st["beam_scores"], NEG))
-    st["open"] = st["open"] & (best_run > worst_fin).any(dim=-1, keepdim=True)
-    toks = st["running_seq"][:, :, cur].reshape(-1)
-    if v431 and cur + 1 >= max_len:                # finalize: the running beams join at L ** length_penalty unless the prompt is done
-        fin2 = st["running_scores"] / float((cur + 1) ** length_penalty) + (~st["open"]).float() * NEG
-        m_sc = torch.cat((st["beam_scores"], fin2), dim=1)
-        keep = topk_stable(m_sc, nb)[1]
-        st["sequences"] = gather(torch.cat((st["sequences"], st["running_seq"]), dim=1), keep)
-        st["beam_scores"] = torch.gather(m_sc, 1, keep)
-        st["finished"] = torch.gather(torch.cat((st["finished"], torch.ones_like(st["finished"])), dim=1), 1, keep)
-        st["seq_len"] = torch.gather(torch.cat((st["seq_len"], torch.full((B, nb), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, keep)
-    flat = (beam_idx + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
-    return toks, flat
-
-
-def beam_start(B, nb, L, start_equal=False):
-    """The state a search starts from, as the torch pipeline holds it."""
-    st = dict(running_seq=torch.full((B, nb, L), PAD, dtype=torch.int64), running_scores=torch.zeros(B, nb),
-              beam_scores=torch.full((B, nb), NEG), finished=torch.zeros(B, nb, dtype=torch.bool),
-              seq_len=torch.zeros(B, nb, dtype=torch.int64), open=torch.ones(B, 1, dtype=torch.bool))
-    st["sequences"] = st["running_seq"].clone()
-    if not start_equal:
-        st["running_scores"][:, 1:] = NEG
-    return st
+    acc = beam_host_scores(lp_rows, st["running_scores"], st["running_seq"], cur, min_len, eos_id, ngram=ngram)
+    top_lp, top_idx = sampling.beam_reference_select(acc, nb, None, False)
+    return sampling.beam_scorer_step(st, top_lp, top_idx, V, cur, max_len, length_penalty, eos_id, v431)[:2]
 
 
 # shape -> seed, screened with the torch pipeline on the CPU (the first of 0, 1, 2, ... to qualify): for n = 1, 2, 3 and both scorer
@@ -171,7 +113,7 @@ BEAM_MIN_LEN, BEAM_LP = 1, 0.0
 def beam_scenario(B, nb, V, L, n, v431):
     """The deterministic search of ``beam_logits`` under the ban n, by the torch pipeline on the CPU: per step (logits, state after
     it, tokens to feed, cache rows, number of beam rows with a non-empty banned set), computed once and shared."""
-    st = beam_start(B, nb, L)
+    st = sampling.beam_start_state(B, nb, L, PAD)
     steps = []
     for cur, lg in enumerate(beam_logits(B, nb, V, L)):
         rows = lg.float()[:, None, :].expand(B, nb, V) if cur == 0 else lg.float().view(B, nb, V)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from emu_amd import sampling
-from emu_amd.llama import LlamaEngine, process_logits, warp_logits
+from emu_amd.llama import LlamaEngine, beam_host_scores, process_logits
 from tests import beam_sampler_cases as bc
 
 NEG_INF = -float("inf")
@@ -17,22 +17,19 @@ NEG_INF = -float("inf")
 
 # ------------------------------------------------------------------------------------------------ 1. spec against the host pipeline
 def host_acc(x, rs, o, order, B, nb):
-    """The accumulated scores of ``beam_search_generate``'s torch pipeline, [B, nb, V]: log_softmax -> process_logits(min_keep=2)
-    / warp_logits in the order's sequence.  The pipeline gathers by history id, so every row gets its in-range ids only."""
+    """The accumulated scores of ``beam_search_generate``'s host step, [B, nb, V]: ``llama.beam_host_scores`` (log_softmax ->
+    process_logits(min_keep=2) / warp_logits in the order's sequence), row by row.  The pipeline gathers by history id, so every row
+    gets its in-range ids only."""
     V = x.shape[1]
-    lp = torch.log_softmax(x.float(), dim=-1)
-    old = order == "4.31"
     hist = o.get("history")
-    warp = (o.get("temperature"), o.get("top_k"), o.get("top_p"))
     out = []
     for r in range(B * nb):
         ids = [i for i in (hist[r].tolist() if hist is not None else []) if 0 <= i < V]
-        out.append(process_logits(lp[r:r + 1], torch.tensor([ids], dtype=torch.int64), o["suppress_eos"], o["eos_id"], not old, *warp,
-                                  o.get("repetition_penalty", 1.0), min_keep=2))
-    acc = torch.cat(out).view(B, nb, V) + rs[:, :, None]
-    if old:
-        acc = warp_logits(acc.reshape(B * nb, V), *warp, min_keep=2).view(B, nb, V)
-    return acc
+        min_len = len(ids) + 1 if o["suppress_eos"] else 0                  # (the step suppresses EOS while cur < min_len)
+        out.append(beam_host_scores(x[r].float().view(1, 1, V), rs.reshape(-1)[r].view(1, 1), torch.tensor([[ids]], dtype=torch.int64),
+                                    len(ids), min_len, o["eos_id"], True, order == "4.31", o.get("temperature"), o.get("top_k"),
+                                    o.get("top_p"), o.get("repetition_penalty", 1.0)))
+    return torch.cat(out).view(B, nb, V)
 
 
 def spec_acc(x, rs, o, order, dtype=torch.float32, do_sample=True):

@@ -10,11 +10,11 @@ import torch
 from emu_amd import sampling
 from tests import beam_sampler_cases as bc
 from tests import tiny
+from tests.beam_step_common import BeamBuffers, assert_beam_state
 from tests.test_beam_sampling_host import spec_acc
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-NEG = -1.0e9
 NEG_INF = -float("inf")
 DEV = torch.device("cuda", 0)
 _t = lambda a: torch.from_numpy(np.asarray(a))
@@ -23,34 +23,19 @@ _t = lambda a: torch.from_numpy(np.asarray(a))
 BEAM_DRAW_TOL = (58 + 59 + 1) * 2.0 ** -24 + 2 * (2 * 2.0 ** -22 + 2.0 ** -24 * 12.7)
 
 
-class Step:
+class Step(BeamBuffers):
     """State and buffers of emu_beam_sample_step_bf16 for B prompts x nb beams, and one call of it."""
 
     def __init__(self, B, nb, V, L, order="5.x", sample=True, ld=None, ld_acc=None):
         from emu_amd._lib import lib
-        self.B, self.nb, self.V, self.L, self.order, self.sample = B, nb, V, L, order, sample
-        i32 = dict(dtype=torch.int32, device=DEV)
-        self.run = torch.full((B, nb, L), 32000, **i32)
-        self.seq = self.run.clone()
-        self.rs = torch.zeros(B, nb, device=DEV)
-        if not (sample and order == "4.31"):
-            self.rs[:, 1:] = NEG
-        self.bs = torch.full((B, nb), NEG, device=DEV)
-        self.fin = torch.zeros(B, nb, dtype=torch.uint8, device=DEV)
-        self.len = torch.zeros(B, nb, **i32)
-        self.open = torch.ones(B, dtype=torch.uint8, device=DEV)
-        self.tok = torch.full((B * nb,), -1, **i32)
-        self.flat = torch.full((B * nb,), -1, dtype=torch.int64, device=DEV)
+        super().__init__(sampling.beam_start_state(B, nb, L, 32000, equal_start=sample and order == "4.31"), DEV, fill=-1)
+        self.V, self.order, self.sample = V, order, sample
         self.ws = torch.empty(lib().emu_beam_sample_workspace_bytes(B, nb, V), dtype=torch.uint8, device=DEV)
-        self.draws = torch.full((B, 2 * nb), -1, **i32)
+        self.draws = torch.full((B, 2 * nb), -1, dtype=torch.int32, device=DEV)
         self.ld = ld or V
         self.ld_acc = ld_acc or V
         self.lg = torch.zeros(B * nb * self.ld + 1, dtype=BF16, device=DEV)          # rows start at element 1: an odd base offset
         self.acc = torch.full((B * nb, self.ld_acc), 7.0, device=DEV)
-        self.cur_dev = torch.zeros(1, **i32)
-
-    def state(self):
-        return (self.run, self.seq, self.rs, self.bs, self.fin, self.len, self.open, self.tok, self.flat)
 
     def outputs(self):
         return self.state() + (self.draws, self.acc)
@@ -62,22 +47,20 @@ class Step:
         view[:, :self.V] = x.to(DEV)
         self.ldp, self.ldb = (self.ld, 0) if shared else (self.nb * self.ld, self.ld)
 
-    def call(self, o, cur, min_len=0, lp=1.0, hf431=0, u=None, eos=bc.EOS, device_counter=False, want=0, **override):
-        from emu_amd import ops
-        from emu_amd._lib import lib
+    def args(self, o, cur, min_len=0, lp=1.0, hf431=0, u=None, eos=bc.EOS, device_counter=False, **override):
+        """The arguments of emu_beam_sample_step_bf16 ahead of the stream: the beam step's common list, then the sampler's."""
         from emu_amd.llama import sample_params
         params = sample_params(self.sample, o.get("temperature"), o.get("top_k"), o.get("top_p"), o.get("repetition_penalty", 1.0),
                                eos, min_len, eos, 32000, min_keep=1)                    # (the call forces min_keep to 2)
-        self.cur_dev.fill_(cur)
-        a = dict(V=self.V, B=self.B, nb=self.nb, L=self.L, ws=self.ws.data_ptr(), ws_bytes=self.ws.numel(), run=self.run.data_ptr(),
-                 uni=None if u is None else u.data_ptr())
-        a.update(override)
-        rc = lib().emu_beam_sample_step_bf16(
-            self.lg.data_ptr() + 2, self.ldp, self.ldb, a["V"], a["B"], a["nb"], a["L"], -7 if device_counter else cur,
-            self.cur_dev.data_ptr() if device_counter else None, min_len, eos, lp, hf431, a["run"], self.seq.data_ptr(),
-            self.rs.data_ptr(), self.bs.data_ptr(), self.fin.data_ptr(), self.len.data_ptr(), self.open.data_ptr(),
-            self.tok.data_ptr(), self.flat.data_ptr(), a["ws"], a["ws_bytes"], params, int(self.sample and self.order == "4.31"),
-            a["uni"], 1, self.draws.data_ptr(), self.acc.data_ptr(), self.ld_acc, ops.stream(DEV))
+        uni = override.pop("uni") if "uni" in override else (None if u is None else u.data_ptr())
+        return (*self.step_args(self.lg.data_ptr() + 2, self.ldp, self.ldb, override.pop("V", self.V), cur, min_len, eos, lp, hf431,
+                                self.ws, device_counter, override),
+                params, int(self.sample and self.order == "4.31"), uni, 1, self.draws.data_ptr(), self.acc.data_ptr(), self.ld_acc)
+
+    def call(self, o, cur, want=0, **kw):
+        from emu_amd import ops
+        from emu_amd._lib import lib
+        rc = lib().emu_beam_sample_step_bf16(*self.args(o, cur, **kw), ops.stream(DEV))
         assert rc == want, rc
         torch.cuda.synchronize()
 
@@ -207,58 +190,10 @@ def test_zero_mass_fallback_on_the_device():
 
 
 def s_rs0(B, nb):
-    rs = torch.zeros(B, nb)
-    rs[:, 1:] = NEG
-    return rs
+    return sampling.beam_start_state(B, nb, 1, 32000)["running_scores"]
 
 
 # ------------------------------------------------------------------------------------------------ 7. bookkeeping
-def bookkeeping(st, top_lp, top_idx, V, cur, max_len, length_penalty, eos_id, v431):
-    """The torch pipeline's bookkeeping (emu_amd/llama.py::beam_search_generate) on a dict of state, fed its candidates; its top-k
-    calls made stable, as in tests/test_gpu_beam.py."""
-    from tests.test_gpu_beam import topk_stable
-    B, nb = st["running_scores"].shape
-    dev = top_lp.device
-    gather = lambda t, idx: torch.gather(t, 1, idx.reshape(B, -1, *([1] * (t.dim() - 2))).expand(-1, -1, *t.shape[2:]))
-    src_beam, tok = top_idx // V, top_idx % V
-    cand_seq = gather(st["running_seq"], src_beam)
-    cand_seq[:, :, cur] = tok
-    hits = (tok == eos_id) if v431 else (tok == eos_id) | (cur + 1 >= max_len)
-    run_lp = top_lp + hits.float() * NEG
-    nxt = topk_stable(run_lp, nb)[1]
-    st["running_seq"] = gather(cand_seq, nxt)
-    st["running_scores"] = torch.gather(run_lp, 1, nxt)
-    beam_idx = torch.gather(src_beam, 1, nxt)
-    fin_lp = top_lp / float((cur if (v431 and cur > 0) else cur + 1) ** length_penalty)
-    fin_lp = fin_lp + (~st["open"]).float() * NEG
-    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
-    just = hits & top_mask[None, :]
-    fin_lp = fin_lp + (~just).float() * NEG
-    m_seq = torch.cat((st["sequences"], cand_seq), dim=1)
-    m_sc = torch.cat((st["beam_scores"], fin_lp), dim=1)
-    m_fin = torch.cat((st["finished"], just), dim=1)
-    m_len = torch.cat((st["seq_len"], torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1)
-    keep = topk_stable(m_sc, nb)[1]
-    st["sequences"] = gather(m_seq, keep)
-    st["beam_scores"] = torch.gather(m_sc, 1, keep)
-    st["finished"] = torch.gather(m_fin, 1, keep)
-    st["seq_len"] = torch.gather(m_len, 1, keep)
-    best_run = (top_lp[:, :1] if v431 else st["running_scores"][:, :1]) / float((cur + 1) ** length_penalty)
-    worst_fin = torch.where(st["finished"], st["beam_scores"].min(dim=1, keepdim=True)[0], torch.full_like(st["beam_scores"], NEG))
-    st["open"] = st["open"] & (best_run > worst_fin).any(dim=-1, keepdim=True)
-    toks = st["running_seq"][:, :, cur].reshape(-1)
-    if v431 and cur + 1 >= max_len:
-        fin2 = st["running_scores"] / float((cur + 1) ** length_penalty) + (~st["open"]).float() * NEG
-        m_sc = torch.cat((st["beam_scores"], fin2), dim=1)
-        keep = topk_stable(m_sc, nb)[1]
-        st["sequences"] = gather(torch.cat((st["sequences"], st["running_seq"]), dim=1), keep)
-        st["beam_scores"] = torch.gather(m_sc, 1, keep)
-        st["finished"] = torch.gather(torch.cat((st["finished"], torch.ones_like(st["finished"])), dim=1), 1, keep)
-        st["seq_len"] = torch.gather(torch.cat((st["seq_len"], torch.full((B, nb), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, keep)
-    flat = (beam_idx + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
-    return toks, flat
-
-
 @pytest.mark.parametrize("sample", [True, False])
 @pytest.mark.parametrize("v431", [False, True])
 @pytest.mark.parametrize("B,nb,V,max_len,min_len,lp,eos_boost", [
@@ -268,17 +203,15 @@ def bookkeeping(st, top_lp, top_idx, V, cur, max_len, length_penalty, eos_id, v4
 ])
 def test_bookkeeping_equals_the_torch_pipeline(B, nb, V, max_len, min_len, lp, eos_boost, v431, sample):
     """Multi-step scenarios in the manner of test_beam_step_kernel_equals_the_torch_pipeline: random bf16 logits with the EOS logit
-    raised, so that hypotheses finish and the heuristic closes.  After every step the kernel's state and outputs equal a torch step
-    whose scores are the spec's (from the torch state's own histories and running scores) and whose candidates are the kernel's own
-    draws_out (sorted by the spec's scores under "4.31"); scores to 1e-4.  Without sampling (penalised beam search) the kernel's
+    raised, so that hypotheses finish and the heuristic closes.  After every step the kernel's state and outputs equal a step of the
+    host loop's own bookkeeping (``sampling.beam_scorer_step``) whose scores are the spec's (from the torch state's own histories and
+    running scores) and whose candidates are the kernel's own draws_out (sorted by the spec's scores under "4.31"); scores to 1e-4.  Without sampling (penalised beam search) the kernel's
     candidates must BE the stable top-2N of the spec's scores.  Under v431 the step index comes from a device counter, and a call
     at cur = L leaves everything untouched."""
     order = "4.31" if v431 else "5.x"
     o = dict(temperature=0.7, top_k=3, top_p=0.9, repetition_penalty=1.2) if sample else dict(repetition_penalty=1.3)
     s = Step(B, nb, V, max_len, order, sample)
-    ref = dict(running_seq=s.run.long().cpu(), sequences=s.seq.long().cpu(), running_scores=s.rs.cpu(), beam_scores=s.bs.cpu(),
-               finished=torch.zeros(B, nb, dtype=torch.bool), seq_len=torch.zeros(B, nb, dtype=torch.int64),
-               open=torch.ones(B, 1, dtype=torch.bool))
+    ref = sampling.beam_start_state(B, nb, max_len, 32000, equal_start=sample and v431)
     g = torch.Generator().manual_seed(B * 1000 + nb * 10 + max_len)
     for cur in range(max_len):
         x = (torch.randn(B if cur == 0 else B * nb, V, generator=g) * 3.0).to(BF16)
@@ -299,17 +232,8 @@ def test_bookkeeping_equals_the_torch_pipeline(B, nb, V, max_len, min_len, lp, e
         if sample and v431:
             top_lp, srt = torch.sort(top_lp, descending=True, dim=1, stable=True)
             top_idx = top_idx.gather(1, srt)
-        toks, flat = bookkeeping(ref, top_lp, top_idx, V, cur, max_len, lp, bc.EOS, v431)
-        assert s.run.long().tolist() == ref["running_seq"].tolist(), what
-        assert s.seq.long().tolist() == ref["sequences"].tolist(), what
-        assert s.tok.long().tolist() == toks.tolist() and s.flat.tolist() == flat.tolist(), what
-        assert s.fin.bool().tolist() == ref["finished"].tolist() and s.len.long().tolist() == ref["seq_len"].tolist(), what
-        assert s.open.bool().tolist() == ref["open"].view(-1).tolist(), what
-        for a_, b_ in ((s.rs.cpu(), ref["running_scores"]), (s.bs.cpu(), ref["beam_scores"])):
-            live = b_ > -1.0e8                                              # (entries at -1e9 are compared as such)
-            assert torch.equal(a_ > -1.0e8, live), what
-            if bool(live.any()):
-                assert float((a_[live] - b_[live]).abs().max()) < 1e-4, what
+        toks, flat = sampling.beam_scorer_step(ref, top_lp, top_idx, V, cur, max_len, lp, bc.EOS, v431)[:2]
+        assert_beam_state(s, ref, toks, flat, what)
     assert bool(ref["finished"].any())                                       # the scenario did finish hypotheses
     snap = [t_.clone() for t_ in s.outputs()]
     s.call(o, max_len, min_len=min_len, lp=lp, hf431=int(v431), u=u, device_counter=True)

@@ -13,63 +13,14 @@ from emu_amd.constrain import TokenTrie
 from tests import beam_sampler_cases as bc
 from tests import constrain_cases as cc
 from tests import tiny
+from tests.beam_step_common import BeamBuffers, assert_beam_state, logit_strides
 from tests.test_gpu_sampler import DRAW_TOL
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-NEG = -1.0e9
 EOS, PAD = cc.EOS, cc.PAD
 BEAM_SHAPES = [(1, 2, 64), (3, 3, 1000), (2, 8, 4099), (2, 5, 32274)]
 assert all(s in bc.GPU_SHAPES for s in BEAM_SHAPES)
-
-
-def topk_stable(x, k):
-    v, i = torch.sort(x, dim=-1, descending=True, stable=True)
-    return v[..., :k], i[..., :k]
-
-
-def spec_bookkeeping(st, acc, cur, max_len, length_penalty, eos_id, v431):
-    """The scorer's bookkeeping of one step on ``acc`` [B, nb, V] (``sampling.beam_reference_rows``): the statements of
-    emu_amd/llama.py::beam_search_generate with its top-k calls stable, as a constrained call makes them.  Returns (tokens to feed,
-    cache rows they continue, the beam each new beam continues)."""
-    B, nb, V = acc.shape
-    dev = acc.device
-    gather = lambda t, idx: torch.gather(t, 1, idx.reshape(B, -1, *([1] * (t.dim() - 2))).expand(-1, -1, *t.shape[2:]))
-    top_lp, top_idx = sampling.beam_reference_select(acc, nb, None, False)
-    src_beam, tok = top_idx // V, top_idx % V
-    cand_seq = gather(st["running_seq"], src_beam)
-    cand_seq[:, :, cur] = tok
-    hits = (tok == eos_id) if v431 else (tok == eos_id) | (cur + 1 >= max_len)
-    run_lp = top_lp + hits.float() * NEG
-    nxt = topk_stable(run_lp, nb)[1]
-    st["running_seq"] = gather(cand_seq, nxt)
-    st["running_scores"] = torch.gather(run_lp, 1, nxt)
-    beam_idx = torch.gather(src_beam, 1, nxt)
-    fin_lp = top_lp / float((cur if (v431 and cur > 0) else cur + 1) ** length_penalty)
-    fin_lp = fin_lp + (~st["open"]).float() * NEG
-    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(nb, dtype=torch.bool)]).to(dev)
-    just = hits & top_mask[None, :]
-    fin_lp = fin_lp + (~just).float() * NEG
-    m_sc = torch.cat((st["beam_scores"], fin_lp), dim=1)
-    keep = topk_stable(m_sc, nb)[1]
-    st["sequences"] = gather(torch.cat((st["sequences"], cand_seq), dim=1), keep)
-    st["beam_scores"] = torch.gather(m_sc, 1, keep)
-    st["finished"] = torch.gather(torch.cat((st["finished"], just), dim=1), 1, keep)
-    st["seq_len"] = torch.gather(torch.cat((st["seq_len"], torch.full((B, 2 * nb), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, keep)
-    best_run = (top_lp[:, :1] if v431 else st["running_scores"][:, :1]) / float((cur + 1) ** length_penalty)
-    worst_fin = torch.where(st["finished"], st["beam_scores"].min(dim=1, keepdim=True)[0], torch.full_like(st["beam_scores"], NEG))
-    st["open"] = st["open"] & (best_run > worst_fin).any(dim=-1, keepdim=True)
-    toks = st["running_seq"][:, :, cur].reshape(-1)
-    if v431 and cur + 1 >= max_len:
-        fin2 = st["running_scores"] / float((cur + 1) ** length_penalty) + (~st["open"]).float() * NEG
-        m_sc = torch.cat((st["beam_scores"], fin2), dim=1)
-        keep = topk_stable(m_sc, nb)[1]
-        st["sequences"] = gather(torch.cat((st["sequences"], st["running_seq"]), dim=1), keep)
-        st["beam_scores"] = torch.gather(m_sc, 1, keep)
-        st["finished"] = torch.gather(torch.cat((st["finished"], torch.ones_like(st["finished"])), dim=1), 1, keep)
-        st["seq_len"] = torch.gather(torch.cat((st["seq_len"], torch.full((B, nb), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, keep)
-    flat = (beam_idx + torch.arange(B, device=dev)[:, None] * nb).reshape(-1)
-    return toks, flat, beam_idx
 
 
 def _beam_cases(V, nb):
@@ -82,33 +33,26 @@ def _beam_cases(V, nb):
 
 
 class _BeamState:
-    """The state of a search under way at step ``cur`` (CPU reference and device copy), for both conventions."""
+    """The state of a search under way at step ``cur`` (CPU reference ``ref`` and device copy ``dev``), for both conventions."""
 
     def __init__(self, B, nb, V, L, cur, seed):
         g = torch.Generator().manual_seed(seed)
-        self.ref = dict(running_seq=torch.full((B, nb, L), PAD, dtype=torch.int64), sequences=torch.full((B, nb, L), PAD, dtype=torch.int64),
-                        running_scores=bc.running_scores(B, nb, "5.x") if cur else torch.tensor([[0.0] + [NEG] * (nb - 1)] * B),
-                        beam_scores=torch.full((B, nb), NEG), finished=torch.zeros(B, nb, dtype=torch.bool),
-                        seq_len=torch.zeros(B, nb, dtype=torch.int64), open=torch.ones(B, 1, dtype=torch.bool))
+        self.ref = sampling.beam_start_state(B, nb, L, PAD)
+        if cur:
+            self.ref["running_scores"] = bc.running_scores(B, nb, "5.x")
         self.ref["running_seq"][:, :, :cur] = torch.randint(3, V, (B, nb, cur), generator=g)
         if cur:                                                              # one kept result per prompt, to merge against
             self.ref["sequences"][:, 0, :2] = torch.tensor([5, EOS])
             self.ref["beam_scores"][:, 0] = -9.5
             self.ref["finished"][:, 0] = True
             self.ref["seq_len"][:, 0] = 2
-        d = lambda t, dt: t.to(dt).cuda().contiguous()
-        r = self.ref
-        self.dev = [d(r["running_seq"], torch.int32), d(r["sequences"], torch.int32), d(r["running_scores"], torch.float32),
-                    d(r["beam_scores"], torch.float32), d(r["finished"], torch.uint8), d(r["seq_len"], torch.int32),
-                    d(r["open"].view(-1), torch.uint8), torch.zeros(B * nb, dtype=torch.int32, device="cuda"),
-                    torch.zeros(B * nb, dtype=torch.int64, device="cuda")]
+        self.dev = BeamBuffers(self.ref)
 
 
-def _beam_call(lg, ld_prompt, ld_beam, V, B, nb, L, cur, cur_dev, min_len, lp, v431, bufs, ws, trie=None, node=None):
+def _beam_call(lg, V, cur, counter, min_len, lp, v431, bufs, ws, trie=None, node=None, **override):
     from emu_amd import ops
     from emu_amd._lib import lib
-    args = (lg.data_ptr(), ld_prompt, ld_beam, V, B, nb, L, cur, None if cur_dev is None else cur_dev.data_ptr(), min_len, EOS, lp, int(v431),
-            *[t.data_ptr() for t in bufs], ws.data_ptr(), ws.numel())
+    args = bufs.step_args(lg.data_ptr(), *logit_strides(lg, bufs.B, bufs.nb), V, cur, min_len, EOS, lp, v431, ws, counter, override)
     if trie is None:
         return lib().emu_beam_step_bf16(*args, ops.stream(lg.device))
     return lib().emu_beam_step_trie_bf16(*args, C.byref(trie), node.data_ptr(), ops.stream(lg.device))
@@ -132,7 +76,6 @@ def test_beam_step_trie_equals_the_specification(B, nb, V, v431):
         x = (torch.randn(B if cur == 0 else B * nb, V, generator=g) * 3.0).to(BF16)
         x[:, EOS] += 6.0                                                     # where EOS is allowed, hypotheses end
         lg = x.cuda()
-        ld_prompt, ld_beam = (lg.stride(0), 0) if cur == 0 else (nb * lg.stride(0), lg.stride(0))
         rows = x[:, None, :].expand(B, nb, V).reshape(B * nb, V) if cur == 0 else x
         for name, (trie, node_of) in _beam_cases(V, nb).items():
             min_len = 0 if name in ("exhausted", "mixed") else 1             # (EOS alone under the suppress is refused on the host)
@@ -147,40 +90,27 @@ def test_beam_step_trie_equals_the_specification(B, nb, V, v431):
                                                    do_sample=False, allowed=allowed).view(B, nb, V)
                 if name in ("fan1", "fan2", "fan2N-1", "exhausted"):             # fewer candidates than 2N outside the -1e9 / -inf tail
                     assert int((acc > -1.0e8).view(B, -1).sum(1).min()) < 2 * nb, what
-                toks, flat, beam_idx = spec_bookkeeping(st.ref, acc, cur, L_, lp, EOS, v431)
+                top_lp, top_idx = sampling.beam_reference_select(acc, nb, None, False)
+                toks, flat, beam_idx = sampling.beam_scorer_step(st.ref, top_lp, top_idx, V, cur, L_, lp, EOS, v431)[:3]
                 want_node = [trie.child(int(node0[b * nb + int(beam_idx[b, j])]), int(toks[b * nb + j])) for b in range(B) for j in range(nb)]
                 node = node0.cuda()
-                cur_dev = torch.tensor([cur], dtype=torch.int32, device="cuda") if counter == "device" else None
                 tt = ops.trie_tables(trie.tables("cuda"))
-                rc = _beam_call(lg, ld_prompt, ld_beam, V, B, nb, L_, -7 if cur_dev is not None else cur, cur_dev, min_len, lp, v431,
-                                st.dev, ws, tt, node)
+                rc = _beam_call(lg, V, cur, counter == "device", min_len, lp, v431, st.dev, ws, tt, node)
                 torch.cuda.synchronize()
                 assert rc == 0, what
-                k_run, k_seq, k_rs, k_bs, k_fin, k_len, k_open, k_tok, k_flat = [t.cpu() for t in st.dev]
-                assert k_tok.long().tolist() == toks.tolist() and k_flat.tolist() == flat.tolist(), what
                 assert node.cpu().tolist() == want_node, what
-                assert k_run.long().tolist() == st.ref["running_seq"].tolist() and k_seq.long().tolist() == st.ref["sequences"].tolist(), what
-                assert k_fin.bool().tolist() == st.ref["finished"].tolist() and k_len.long().tolist() == st.ref["seq_len"].tolist(), what
-                assert k_open.bool().tolist() == st.ref["open"].view(-1).tolist(), what
-                for a_, b_ in ((k_rs, st.ref["running_scores"]), (k_bs, st.ref["beam_scores"])):
-                    assert not bool(torch.isnan(a_).any()), what
-                    live = b_ > -1.0e8
-                    assert torch.equal(a_ > -1.0e8, live) and torch.equal(torch.isinf(a_), torch.isinf(b_)), what
-                    if bool(live.any()):
-                        assert float((a_[live] - b_[live]).abs().max()) < 1e-4, what
+                assert_beam_state(st.dev, st.ref, toks, flat, what)
                 if name == "all":                                            # nothing is masked: the unconstrained kernel's bits
                     base = _BeamState(B, nb, V, L_, cur, seed=7)
-                    assert _beam_call(lg, ld_prompt, ld_beam, V, B, nb, L_, -7 if cur_dev is not None else cur, cur_dev, min_len, lp,
-                                      v431, base.dev, ws) == 0
+                    assert _beam_call(lg, V, cur, counter == "device", min_len, lp, v431, base.dev, ws) == 0
                     torch.cuda.synchronize()
-                    for a_, b_ in zip(st.dev, base.dev):
+                    for a_, b_ in zip(st.dev.state(), base.dev.state()):
                         assert torch.equal(a_.view(torch.uint8), b_.view(torch.uint8)), what
     # a replay at the length limit changes nothing, the nodes included
-    snap = [t.clone() for t in st.dev] + [node.clone()]
-    cur_dev = torch.tensor([L_], dtype=torch.int32, device="cuda")
-    assert _beam_call(lg, ld_prompt, ld_beam, V, B, nb, L_, -7, cur_dev, 0, lp, v431, st.dev, ws, tt, node) == 0
+    snap = [t.clone() for t in st.dev.state()] + [node.clone()]
+    assert _beam_call(lg, V, L_, True, 0, lp, v431, st.dev, ws, tt, node) == 0
     torch.cuda.synchronize()
-    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.dev + [node]))
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, list(st.dev.state()) + [node]))
 
 
 def test_trie_entry_points_refuse_bad_tables_before_any_launch():
@@ -192,7 +122,7 @@ def test_trie_entry_points_refuse_bad_tables_before_any_launch():
     first, tok, child = trie.tables("cuda")
     good = ops.trie_tables((first, tok, child))
     st = _BeamState(1, 2, V, 8, 0, seed=1)
-    snap = [t.clone() for t in st.dev]
+    snap = [t.clone() for t in st.dev.state()]
     lg = torch.zeros(1, V, dtype=BF16, device="cuda")
     ws = torch.empty(lib().emu_beam_step_workspace_bytes(1, 2, V), dtype=torch.uint8, device="cuda")
     node = torch.zeros(2, dtype=torch.int32, device="cuda")
@@ -205,12 +135,12 @@ def test_trie_entry_points_refuse_bad_tables_before_any_launch():
     sample = lambda t, n: lib().emu_sample_trie_bf16(lg.data_ptr(), V, 1, V, None, 0, 0, step.data_ptr(), None, 0, 0, C.byref(p), None,
                                                      out.data_ptr(), None, 0, t, n, ops.stream(lg.device))
     for t in bad:
-        assert _beam_call(lg, V, 0, V, 1, 2, 8, 0, None, 0, 1.0, False, st.dev, ws, t, node) == -22
+        assert _beam_call(lg, V, 0, False, 0, 1.0, False, st.dev, ws, t, node) == -22
         assert sample(C.byref(t), node.data_ptr()) == -22
     assert sample(None, node.data_ptr()) == -22 and sample(C.byref(good), None) == -22
-    assert _beam_call(lg, V, 0, V, 1, 9, 8, 0, None, 0, 1.0, False, st.dev, ws, good, node) == -22       # the base entry point's bounds
+    assert _beam_call(lg, V, 0, False, 0, 1.0, False, st.dev, ws, good, node, nb=9) == -22                # the base entry point's bounds
     torch.cuda.synchronize()
-    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.dev)) and out.cpu().tolist() == [-7] and node.cpu().tolist() == [0, 0]
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.dev.state())) and out.cpu().tolist() == [-7] and node.cpu().tolist() == [0, 0]
     # a node outside [-1, nodes) at entry is the exhausted node, not an address
     node = torch.tensor([7, -5], dtype=torch.int32, device="cuda")
     lg2 = torch.zeros(2, V, dtype=BF16, device="cuda")

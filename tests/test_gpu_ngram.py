@@ -13,7 +13,8 @@ from tests import beam_sampler_cases as bc
 from tests import constrain_cases as cc
 from tests import ngram_cases as nc
 from tests import tiny
-from tests.test_gpu_beam_sampler import Step, bookkeeping
+from tests.beam_step_common import BeamBuffers, assert_beam_state, logit_strides
+from tests.test_gpu_beam_sampler import Step
 from tests.test_gpu_sampler import DRAW_TOL
 
 pytestmark = pytest.mark.gpu
@@ -205,48 +206,24 @@ def test_sample_without_a_ban_equals_the_parent_bit_for_bit(V, rows):
 
 
 # ------------------------------------------------------------------------------------------------ the beam kernels, step by step
-class _DetState:
+class _DetState(BeamBuffers):
     """Device state of ``emu_beam_step_bf16`` at the start of a search, and one call of it (``ngram`` None = the parent)."""
 
     def __init__(self, B, nb, V, L):
         from emu_amd._lib import lib
-        dev, i32 = torch.device("cuda", 0), dict(dtype=torch.int32, device="cuda")
-        self.B, self.nb, self.V, self.L = B, nb, V, L
-        self.run = torch.full((B, nb, L), PAD, **i32)
-        self.seq = self.run.clone()
-        self.rs = torch.zeros(B, nb, device=dev)
-        self.rs[:, 1:] = nc.NEG
-        self.bs = torch.full((B, nb), nc.NEG, device=dev)
-        self.fin = torch.zeros(B, nb, dtype=torch.uint8, device=dev)
-        self.len = torch.zeros(B, nb, **i32)
-        self.open = torch.ones(B, dtype=torch.uint8, device=dev)
-        self.tok = torch.zeros(B * nb, **i32)
-        self.flat = torch.zeros(B * nb, dtype=torch.int64, device=dev)
-        self.ws = torch.empty(lib().emu_beam_step_workspace_bytes(B, nb, V), dtype=torch.uint8, device=dev)
-        self.cur_dev = torch.zeros(1, **i32)
-
-    def all(self):
-        return (self.run, self.seq, self.rs, self.bs, self.fin, self.len, self.open, self.tok, self.flat)
+        super().__init__(sampling.beam_start_state(B, nb, L, PAD))
+        self.V = V
+        self.ws = torch.empty(lib().emu_beam_step_workspace_bytes(B, nb, V), dtype=torch.uint8, device="cuda")
 
     def call(self, lg, cur, v431, ngram, counter):
         from emu_amd import ops
         from emu_amd._lib import lib
-        ld_prompt, ld_beam = (lg.stride(0), 0) if lg.shape[0] == self.B else (self.nb * lg.stride(0), lg.stride(0))
-        self.cur_dev.fill_(cur)
-        args = (lg.data_ptr(), ld_prompt, ld_beam, self.V, self.B, self.nb, self.L, -7 if counter else cur,
-                self.cur_dev.data_ptr() if counter else None, nc.BEAM_MIN_LEN, EOS, nc.BEAM_LP, int(v431),
-                *[t.data_ptr() for t in self.all()], self.ws.data_ptr(), self.ws.numel())
+        args = self.step_args(lg.data_ptr(), *logit_strides(lg, self.B, self.nb), self.V, cur, nc.BEAM_MIN_LEN, EOS, nc.BEAM_LP, v431,
+                              self.ws, counter)
         rc = lib().emu_beam_step_bf16(*args, ops.stream(lg.device)) if ngram is None else \
             lib().emu_beam_step_ngram_bf16(*args, ngram, ops.stream(lg.device))
         torch.cuda.synchronize()
         return rc
-
-
-def _same_scores(got, want, what):
-    live = want > -1.0e8                                   # (entries at -1e9 are compared as such)
-    assert not bool(torch.isnan(got).any()) and torch.equal(got > -1.0e8, live), what
-    if bool(live.any()):
-        assert float((got[live] - want[live]).abs().max()) < 1e-4, what
 
 
 @pytest.mark.parametrize("v431", [False, True])
@@ -265,41 +242,27 @@ def test_beam_step_ngram_equals_the_torch_pipeline(B, nb, V, L, n, v431):
         lg = s["lg"].cuda()
         assert st.call(lg, cur, v431, n, counter=v431) == 0 and zero.call(lg, cur, v431, 0, counter=v431) == 0
         assert parent.call(lg, cur, v431, None, counter=v431) == 0
-        ref, what = s["state"], f"step {cur}"
-        assert st.run.cpu().long().tolist() == ref["running_seq"].tolist() and st.seq.cpu().long().tolist() == ref["sequences"].tolist(), what
-        assert st.tok.cpu().long().tolist() == s["toks"].tolist() and st.flat.cpu().tolist() == s["flat"].tolist(), what
-        assert st.fin.cpu().bool().tolist() == ref["finished"].tolist() and st.len.cpu().long().tolist() == ref["seq_len"].tolist(), what
-        assert st.open.cpu().bool().tolist() == ref["open"].view(-1).tolist(), what
-        _same_scores(st.rs.cpu(), ref["running_scores"], what)
-        _same_scores(st.bs.cpu(), ref["beam_scores"], what)
-        for a_, b_ in zip(zero.all(), parent.all()):
+        what = f"step {cur}"
+        assert_beam_state(st, s["state"], s["toks"], s["flat"], what)
+        for a_, b_ in zip(zero.state(), parent.state()):
             assert torch.equal(a_.view(torch.uint8), b_.view(torch.uint8)), what
     assert st.seq.cpu().tolist() != zero.seq.cpu().tolist()
     assert not any(nc.has_repeated_ngram(r, n) for r in st.seq.cpu().view(-1, L).tolist())
     assert any(nc.has_repeated_ngram(r, n) for r in zero.seq.cpu().view(-1, L).tolist())
-    snap = [t.clone() for t in st.all()]
+    snap = [t.clone() for t in st.state()]
     assert st.call(lg, L, v431, n, counter=True) == 0
-    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.all()))
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.state()))
     assert st.call(lg, 0, v431, -1, counter=False) == -22
-    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.all()))
+    assert all(torch.equal(a_, b_) for a_, b_ in zip(snap, st.state()))
 
 
 class _NgramStep(Step):
     """tests/test_gpu_beam_sampler.py's Step calling ``emu_beam_sample_step_ngram_bf16`` (``ngram`` None: the parent)."""
 
-    def call(self, o, cur, min_len=0, lp=1.0, hf431=0, u=None, eos=bc.EOS, device_counter=False, want=0, ngram=None):
+    def call(self, o, cur, want=0, ngram=None, **kw):
         from emu_amd import ops
         from emu_amd._lib import lib
-        from emu_amd.llama import sample_params
-        params = sample_params(self.sample, o.get("temperature"), o.get("top_k"), o.get("top_p"), o.get("repetition_penalty", 1.0),
-                               eos, min_len, eos, 32000, min_keep=1)
-        self.cur_dev.fill_(cur)
-        args = (self.lg.data_ptr() + 2, self.ldp, self.ldb, self.V, self.B, self.nb, self.L, -7 if device_counter else cur,
-                self.cur_dev.data_ptr() if device_counter else None, min_len, eos, lp, hf431, self.run.data_ptr(), self.seq.data_ptr(),
-                self.rs.data_ptr(), self.bs.data_ptr(), self.fin.data_ptr(), self.len.data_ptr(), self.open.data_ptr(),
-                self.tok.data_ptr(), self.flat.data_ptr(), self.ws.data_ptr(), self.ws.numel(), params,
-                int(self.sample and self.order == "4.31"), None if u is None else u.data_ptr(), 1, self.draws.data_ptr(),
-                self.acc.data_ptr(), self.ld_acc)
+        args = self.args(o, cur, **kw)
         rc = lib().emu_beam_sample_step_bf16(*args, ops.stream(self.lg.device)) if ngram is None else \
             lib().emu_beam_sample_step_ngram_bf16(*args, ngram, ops.stream(self.lg.device))
         assert rc == want, rc
@@ -323,9 +286,7 @@ def test_beam_sample_step_ngram_equals_the_specification(B, nb, V, L, n, v431, s
     # step -- 5000-fold over 24 steps, beyond any absolute bound on the scores; that order is run at temperature 1)
     o = dict(temperature=1.0 if v431 else 0.7, top_k=3, top_p=0.9, repetition_penalty=1.2) if sample else dict(repetition_penalty=1.3)
     s, zero, parent = (_NgramStep(B, nb, V, L, order, sample) for _ in range(3))
-    ref = dict(running_seq=s.run.long().cpu(), sequences=s.seq.long().cpu(), running_scores=s.rs.cpu(), beam_scores=s.bs.cpu(),
-               finished=torch.zeros(B, nb, dtype=torch.bool), seq_len=torch.zeros(B, nb, dtype=torch.int64),
-               open=torch.ones(B, 1, dtype=torch.bool))
+    ref = sampling.beam_start_state(B, nb, L, 32000, equal_start=sample and v431)
     g = torch.Generator().manual_seed(B * 1000 + nb * 10 + L + n)
     fired = 0
     for cur, x in enumerate(nc.beam_logits(B, nb, V, L)):
@@ -356,13 +317,8 @@ def test_beam_sample_step_ngram_equals_the_specification(B, nb, V, L, n, v431, s
         if sample and v431:
             top_lp, srt = torch.sort(top_lp, descending=True, dim=1, stable=True)
             top_idx = top_idx.gather(1, srt)
-        toks, flat = bookkeeping(ref, top_lp, top_idx, V, cur, L, 1.0, bc.EOS, v431)
-        assert s.run.long().tolist() == ref["running_seq"].tolist() and s.seq.long().tolist() == ref["sequences"].tolist(), what
-        assert s.tok.long().tolist() == toks.tolist() and s.flat.tolist() == flat.tolist(), what
-        assert s.fin.bool().tolist() == ref["finished"].tolist() and s.len.long().tolist() == ref["seq_len"].tolist(), what
-        assert s.open.bool().tolist() == ref["open"].view(-1).tolist(), what
-        _same_scores(s.rs.cpu(), ref["running_scores"], what)
-        _same_scores(s.bs.cpu(), ref["beam_scores"], what)
+        toks, flat = sampling.beam_scorer_step(ref, top_lp, top_idx, V, cur, L, 1.0, bc.EOS, v431)[:2]
+        assert_beam_state(s, ref, toks, flat, what)
         for a_, b_ in zip(zero.outputs(), parent.outputs()):
             assert torch.equal(a_.view(torch.uint8), b_.view(torch.uint8)), what
     print(f"{(B, nb, V, L)} n={n} {order} sample={sample}: banned rows over the search {fired}")
