@@ -127,6 +127,7 @@ _PROTOS = {
     "emu_gemm_tune": (None, [i32]),
     "emu_gemm_plan": (i32, [vp, i32, i32, vp, C.POINTER(i32)]),
     "emu_gemv_plan": (i32, [vp, i32, vp]),
+    "emu_gemv_thin_plan": (i32, [vp, i32, vp]),
     "emu_gemv_fp8_thin_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),

@@ -125,3 +125,13 @@ __device__ __forceinline__ u32x4 ld16(const void* p) { return *reinterpret_cast<
 __device__ __forceinline__ void st16(void* p, const u32x4& v) { *reinterpret_cast<u32x4*>(p) = v; }
 
 #define EMU_CHECK_LAUNCH() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+// the body of a launcher that switches a.epi (EmuEpilogue, kernels.h) to a template argument: CASE(E) launches the instantiation for E
+#define EMU_EPI_LAUNCH(...)                                                                                          \
+    switch (a.epi) {                                                                                                 \
+        __VA_ARGS__                                                                                                  \
+        default: return -22;                                                                                         \
+    }                                                                                                                \
+    EMU_CHECK_LAUNCH();                                                                                              \
+    return 0;
+#define EMU_EPI3(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU))
+#define EMU_EPI5(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU) CASE(EPI_SILU) CASE(EPI_GELU))

@@ -5,7 +5,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,8 +119,7 @@ WeightKernel weight_kernel(int fp8_mode, int fp4_mode, int rows, int H, int HD, 
 WeightKernel pack_kernel(WeightKernel k, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
                          int norm, int epi, int tune) {
     if (k != WeightKernel::Bf16 || rows != 1 || !pack_on || pack_rows <= 0 || fused_mode || tail_mode || warm_mask) return k;
-    GemvShape sh{};
-    sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm != 0; sh.w_aligned = sh.x_aligned = 1;
+    const GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
     return gemv_pack_rows(gemv_plan(sh, tune), sh) == pack_rows ? WeightKernel::Bf16Pack : k;
 }
 // out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
@@ -129,12 +127,12 @@ WeightKernel pack_kernel(WeightKernel k, int rows, int pack_rows, int pack_on, i
 // the matrix once.  The row range follows from k, a row count outside it is refused: Fp4Rows 1..2 (fused norm allowed), Fp4Thin 1..16,
 // Fp4Gemm 17 and more (no fused norm; K >= 256, K % 32 == 0).  Fp8Gemm needs the caller's quantised rows (linear_q8): not served here.
 // Fp8Thin: 1..16 rows of the fp8 set on the matrix cores (no fused norm; K >= 256, K % 256 == 0), priced at its N * K bytes.
+// Fp8Thin and Fp4Thin go through launch_gemv_thin_stream (gemv.hip: shape, gemv_thin_plan, pointer checks, launch), which refuses.
 int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
     if (k == WeightKernel::Fp8Thin) {
         if (!w.W8 || !w.s8) return -22;
         g.W = B(w.W8); g.wscale = w.s8;
-        if (!gemv_fp8_thin_ok(g)) return -22;
-        return gemv_profiled((double)g.N * (double)g.K, s, [&] { return launch_gemv_fp8_thin(g, s); });
+        return gemv_profiled((double)g.N * (double)g.K, s, [&] { return launch_gemv_thin_stream(g, s); });
     }
     if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows) {
         const bool f8 = k == WeightKernel::Fp8Rows;
@@ -144,8 +142,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
     }
     if (k == WeightKernel::Bf16Pack) {               // the packed twin of the planned bf16 form, priced at the bytes it streams
         if (!w.W || !w.pk.rows || g.M != 1 || g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
-        GemvShape sh{};
-        sh.M = 1; sh.N = g.N; sh.K = g.K; sh.ldx = sh.ldw = g.K; sh.epi = g.epi; sh.norm = g.norm_w != nullptr; sh.w_aligned = sh.x_aligned = 1;
+        const GemvShape sh = gemv_one_row_shape(g.N, g.K, g.norm_w != nullptr, g.epi);
         const GemvPlan p = gemv_plan(sh, emu_gemm_tune_get());
         if (gemv_pack_rows(p, sh) != w.pk.rows) return -22;
         g.W = w.W;
@@ -158,9 +155,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
     const double bytes = (double)g.N * (double)(g.K / 2 + g.K / 32);
     if (k == WeightKernel::Fp4Rows)
         return g.M > 2 || (g.K & 31) ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv(g, s); });
-    const bool thin = k == WeightKernel::Fp4Thin;
-    if (!fp4_mfma_ok(g, thin ? 1 : 17, thin ? 16 : INT_MAX, true)) return -22;
-    return gemv_profiled(bytes, s, [&] { return thin ? launch_gemv_fp4_thin(g, s, true) : launch_gemm_fp4(g, s, true); });
+    return gemv_profiled(bytes, s, [&] { return k == WeightKernel::Fp4Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp4(g, s); });
 }
 // linear_w's launch block for a packed [N, K] matrix of the engines (rows of K elements: K bf16 / fp8 bytes, K / 2 MXFP4 bytes, scale
 // rows at fp4_scale_stride(K)), no bias; norm_w: the RMSNorm fused in front (eps), or null
@@ -227,8 +222,7 @@ int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int 
 }
 int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune) {
     if (N < 1 || K < 8) return 0;
-    GemvShape sh{};
-    sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm != 0; sh.w_aligned = sh.x_aligned = 1;
+    const GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
     return gemv_pack_rows(gemv_plan(sh, tune), sh);
 }
 int emu_bf16_pack(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* sign, void* flags, int* hb_out,
@@ -478,9 +472,7 @@ int emu_linear_fp4w_mfma_bf16(const void* A, const void* W4, const void* scales,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     return linear_fp4w(M <= 16 ? WeightKernel::Fp4Thin : WeightKernel::Fp4Gemm, A, W4, scales, bias, res, nullptr, C, M, N, K, lda, ldw, lds, ldres, ldc, 0.f, epi, s);
 }
-// the two older entry points keep K in whole stages (K % 256 == 0), refused here: the launchers pick the partial-stage (TAIL)
-// instantiation from K % 256 itself, never from tail_ok, which only widens the argument check -- so a K of whole stages launches
-// exactly what tail_ok = false launched
+// the two older entry points keep K in whole stages (K % 256 == 0), refused here: the launchers behind them take a partial last stage
 int emu_linear_fp4w_thin_bf16(const void* A, const void* W4, const void* scales, const void* bias, const void* res, void* C, int M, int N,
                               int K, int lda, int ldw, int lds, int ldres, int ldc, int epi, emu_stream_t s) {
     return K & 255 ? -22 : linear_fp4w(WeightKernel::Fp4Thin, A, W4, scales, bias, res, nullptr, C, M, N, K, lda, ldw, lds, ldres, ldc, 0.f, epi, s);

@@ -25,7 +25,6 @@
 // from L2 / the Infinity Cache.  Ragged M and N: rows and columns are clamped on load and masked on store.
 // No fused RMSNorm, no RoPE epilogue, no K-slicing.  The result is what the bf16 GEMM computes on the dequantised weights, up to
 // fp32 summation order.
-#include <climits>
 #include <type_traits>
 
 #include "common.h"
@@ -170,16 +169,14 @@ int launch_fp4_gemm(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool gemm_fp4_ok(const GemvArgs& a) { return fp4_mfma_ok(a, 17, INT_MAX); }
-
-// The same tiles whether or not K ends in a partial stage (tail_ok admits one; a K of whole stages runs the kernels without it).
+// The same tiles whether or not K ends in a partial stage (a K of whole stages runs the kernels without it).
 template <bool TAIL>
 static int dispatch_fp4_gemm(const GemvArgs& a, hipStream_t s) {
     if (a.M <= 32) return launch_fp4_gemm<1, 2, 4, 1, 3, true, TAIL>(a, s);
     if (a.M <= 64) return launch_fp4_gemm<1, 4, 4, 1, 3, true, TAIL>(a, s);
     return launch_fp4_gemm<2, 4, 2, 2, 2, false, TAIL>(a, s);
 }
-int launch_gemm_fp4(const GemvArgs& a, hipStream_t s, bool tail_ok) {
-    if (!fp4_mfma_ok(a, 17, INT_MAX, tail_ok)) return -22;
+int launch_gemm_fp4(const GemvArgs& a, hipStream_t s) {
+    if (!fp4_mfma_ok(a)) return -22;
     return a.K % KC ? dispatch_fp4_gemm<true>(a, s) : dispatch_fp4_gemm<false>(a, s);
 }

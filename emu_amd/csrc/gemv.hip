@@ -1,11 +1,13 @@
 // Decode-shape (M <= 16 rows) weight streams:  out[m, n] = epilogue( sum_k xeff[m, k] * W[n, k] )
 //
 // HBM-bound: every weight byte is read exactly once per call (PMC: traffic / algorithmic = 1.0013) with non-temporal
-// loads; the activations (a few KB) come from L1/L2.  launch_gemv() is three steps: the shape of the argument block (GemvShape:
+// loads; the activations (a few KB) come from L1/L2.  launch_gemv() is three steps: the shape of the argument block (gemv_shape_of:
 // integers and flags), gemv_plan() -- the one place that decides the kernel family, its form, rows per workgroup, waves, trips, grid
 // -- and launch_planned(), which maps the plan's values to template arguments.  The planner is pure host arithmetic (no HIP call,
 // no global; the emu_gemm_tune mask is an argument), exported as emu_gemv_plan and held against recorded launches by
-// tests/test_gemv_plan.py; emu_gemv_geometry / emu_gemv_partition are views of the same plan.  The families:
+// tests/test_gemv_plan.py; emu_gemv_geometry / emu_gemv_partition are views of the same plan.  gemv_thin_plan() is the part of it
+// that plans the three matrix-core few-row streams (bf16, fp8, MXFP4), exported as emu_gemv_thin_plan (tests/test_thin_plan.py);
+// gemv_plan asks it for bf16 from 4 rows on, launch_gemv_thin_stream() launches whatever it answers.  The families:
 //   block (gemv_kernel)      1..8 rows.  One 256-thread workgroup owns R (16/8/4/2) consecutive weight rows and splits K across its
 //                    4 waves (thread t owns 16-byte vectors t, t+256, ...), N/R workgroups >> 256 CUs.  Inner product on
 //                    v_dot2c_f32_bf16 (weights consumed unpacked), wave reductions on DPP.  Optional fused prologue: LLaMA
@@ -18,6 +20,8 @@
 //   thin stream (gemv_thin.hip)            4..16 rows, K in whole 256-wide stages: LDS-DMA stages + MFMA.
 //   fp8 block (gemv_fp8_kernel)            optional e4m3 weight stream (per-row scale), 1..2 rows, 8- or 16-byte weight loads.
 //   MXFP4 rows (gemv_fp4.hip)              optional MXFP4 weight stream (4-bit elements, one E8M0 scale per 32), M <= 2.
+//   fp8 thin (gemv_fp8_thin.hip), MXFP4 thin (gemv_fp4_thin.hip)   the thin stream fed from e4m3 / 4-bit bytes, 1..16 rows; reached
+//                    through launch_gemv_thin_stream only (the engine's 3..16-row steps), never through gemv_plan.
 //
 // Replaces (reference call sites): LlamaDecoderLayer linears + RMSNorm reached from Emu2/emu/emu.py:133-138
 // and :213-229 at S=1 (greedy: 1 row; beam search: num_beams rows), project_up/project_down emu.py:131,147.
@@ -712,15 +716,6 @@ __global__ __launch_bounds__(NW * 64) void gemv_fp8_kernel(const GemvArgs a) {
 }
 
 // ---- the launchers: plan values -> template arguments.  Grid and workgroup size come from the plan; nothing below tests a shape.
-#define EMU_EPI_LAUNCH(...)                                                                                          \
-    switch (a.epi) {                                                                                                 \
-        __VA_ARGS__                                                                                                  \
-        default: return -22;                                                                                         \
-    }                                                                                                                \
-    EMU_CHECK_LAUNCH();                                                                                              \
-    return 0;
-#define EMU_EPI3(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU))
-#define EMU_EPI5(CASE) EMU_EPI_LAUNCH(CASE(EPI_NONE) CASE(EPI_RESID) CASE(EPI_SWIGLU) CASE(EPI_SILU) CASE(EPI_GELU))
 
 template <int R, int MB, bool NORM, int PRE>
 int launch_block_epi(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
@@ -824,6 +819,8 @@ int launch_planned(const GemvPlan& p, const GemvArgs& a, hipStream_t s) {
             if (p.mb == 1) return p.waves == 2 ? launch_fp8<4, 1, 2, 16>(p, a, s) : launch_fp8<4, 1, 4, 16>(p, a, s);
             return p.rows == 4 ? launch_fp8<4, 2, 2, 16>(p, a, s) : launch_fp8<8, 2, 2, 16>(p, a, s);
         case GEMV_FAM_FP4_ROWS: return launch_gemv_fp4(a, p, s);
+        case GEMV_FAM_FP8_THIN: return launch_gemv_fp8_thin(a, p, s);
+        case GEMV_FAM_FP4_THIN: return launch_gemv_fp4_thin(a, p, s);
         default: return -22;
     }
 }
@@ -886,12 +883,15 @@ GemvPlan plan_one_row(const GemvShape& sh, int tune) {
     return planned(sh, GEMV_FAM_BLOCK, form, R, 1, 4, form == GEMV_FORM_PRELOAD ? 4 : form == GEMV_FORM_HEAD ? -1 : 0);
 }
 
-// 2..16 rows through LDS-DMA stages (gemv_thin.hip): whole 256-wide k stages, no fused norm, bf16 weights, 16-byte aligned operands
-bool gemv_thin_ok(const GemvShape& sh) {
-    return sh.M >= 2 && sh.M <= 16 && !sh.norm && !sh.fp8 && sh.K >= 256 && (sh.K % 256) == 0 && (sh.ldw & 7) == 0 && (sh.ldx & 7) == 0 &&
-           sh.w_aligned && sh.x_aligned;
+// ---- the three matrix-core few-row streams (gemv_thin.hip, gemv_fp8_thin.hip, gemv_fp4_thin.hip): rows weight rows per workgroup of
+// 4 waves, the activation rows in a bucket of mb = 8 (up to 8 rows) or 16, K walked in stages of kch 16-byte slots per weight row
+// through a ring of `stages` stages in LDS
+GemvPlan thin_planned(const GemvShape& sh, int family, int rows, int stages, int kch) {
+    GemvPlan p = planned(sh, family, 0, rows, sh.M <= 8 ? 8 : 16, 4, 0);
+    p.stages = stages; p.kch = kch;
+    return p;
 }
-// 16 weight rows per workgroup (three co-resident workgroups per CU at <= 8 rows): measured at 5 rows against 32-row
+// bf16: 16 weight rows per workgroup (three co-resident workgroups per CU at <= 8 rows): measured at 5 rows against 32-row
 // workgroups and 512-k stages (tools/thin_ab.py, profiles/r03_thin_stream_ab.log): qkv 42.1 vs 45.5 / 47.1 us.
 // emu_gemm_tune bits 8-11 pick the other variants (A/B aid).
 GemvPlan plan_thin(const GemvShape& sh, int tune) {
@@ -901,9 +901,49 @@ GemvPlan plan_thin(const GemvShape& sh, int tune) {
     if (variant == 1 && (sh.N + 31) / 32 >= 512) { rn = 32; nstg = 3; }
     else if (variant == 2) nstg = rows8 ? 6 : 3;
     else if (variant == 3 && rows8 && sh.K % 512 == 0) { nstg = 3; kch = 64; }
-    GemvPlan p = planned(sh, GEMV_FAM_THIN, 0, rn, rows8 ? 8 : 16, 4, 0);
-    p.stages = nstg; p.kch = kch;
-    return p;
+    return thin_planned(sh, GEMV_FAM_THIN, rn, nstg, kch);
+}
+// the epilogues the byte-fed kernels are built with (store_c4, fp4_tile.h)
+bool epi3_ok(const GemvShape& sh) {
+    return sh.epi == EPI_NONE || sh.epi == EPI_RESID || (sh.epi == EPI_SWIGLU && !(sh.N & 1));
+}
+// what both MXFP4 matrix-core kernels (gemv_fp4_thin.hip: 1..16 rows, gemm_fp4.hip: 17 and more) ask of a shape, the row count
+// aside: K >= 256 in whole MX blocks (K % 256 != 0: the last stage partial, the TAIL instantiations), 16-byte element rows, scale
+// rows of whole stages (fp4_scale_stride) fetched 4 bytes at a time, 16-byte aligned W and x, no fused norm
+bool fp4_mfma_shape_ok(const GemvShape& sh) {
+    return sh.fp4 && !sh.fp8 && !sh.norm && sh.w_aligned && sh.x_aligned && sh.N >= 1 && sh.K >= 256 && (sh.K & 31) == 0 &&
+           (sh.ldw & 15) == 0 && (sh.ldx & 7) == 0 && (sh.lds & 3) == 0 && sh.ldw >= sh.K / 2 && sh.ldx >= sh.K &&
+           sh.lds >= fp4_scale_stride(sh.K) && epi3_ok(sh);
+}
+// The matrix-core few-row plan of the shape's weight kind (sh.fp8 / sh.fp4; neither: bf16), or status -22.
+//   bf16   2..16 rows, whole 256-wide k stages, no fused norm, 16-byte aligned operands, epilogues NONE .. GELU: plan_thin.
+//   fp8    1..16 rows, whole 256-wide k stages (kch 16).  32 weight rows per workgroup halve what a workgroup re-stages of the
+//          activations per weight byte (mb * 512 against rows * 256 bytes per stage); 16 where 32 would leave fewer than 128
+//          workgroups, half the CUs of the device (short shards, the tests' small N).  The ring is as deep as 48 KiB hold: three
+//          workgroups share a CU's LDS.
+//   MXFP4  1..16 rows (kch 8).  32 weight rows per workgroup: measured against 16 at the five LLaMA-33B shapes (tools/fp4_wide_time.py
+//          --ab), 32 rows win everywhere, also where they leave CUs without a workgroup -- qkv 28.1 vs 42.0 us, o_proj 13.1 vs
+//          17.6, down 25.5 vs 38.6 at 5 rows: the activation rows a workgroup re-stages from L2 weigh twice the 4-bit bytes of 16
+//          weight rows.  Ring depth by (rows, mb) as built: 32/8: 5, 16/8: 6, 32/16 and 16/16: 4 (32/16/4 is 53248 bytes, not the
+//          48 KiB of the others).  The same tiles whether or not K ends in a partial stage.
+// emu_gemm_tune bits 28-29 pin the weight rows of the two byte-fed streams to 16 / 32 (1 / 2).
+GemvPlan gemv_thin_plan(const GemvShape& sh, int tune) {
+    GemvPlan refused{};
+    refused.status = -22;
+    const int pin = (tune >> 28) & 3;
+    if (sh.fp4) {
+        if (sh.M < 1 || sh.M > 16 || !fp4_mfma_shape_ok(sh)) return refused;
+        const int rows = pin == 1 ? 16 : 32;
+        return thin_planned(sh, GEMV_FAM_FP4_THIN, rows, sh.M > 8 ? 4 : rows == 32 ? 5 : 6, 8);
+    }
+    if (sh.norm || !sh.w_aligned || !sh.x_aligned || sh.M > 16 || sh.N < 1 || sh.K < 256 || (sh.K % 256) || (sh.ldx & 7)) return refused;
+    if (sh.fp8) {
+        if (sh.M < 1 || (sh.ldw & 15) || sh.ldw < sh.K || sh.ldx < sh.K || !epi3_ok(sh)) return refused;
+        const int rows = pin == 1 ? 16 : pin == 2 ? 32 : (sh.N + 31) / 32 >= 128 ? 32 : 16;
+        return thin_planned(sh, GEMV_FAM_FP8_THIN, rows, 49152 / (rows * 256 + (sh.M <= 8 ? 8 : 16) * 512), 16);
+    }
+    if (sh.M < 2 || (sh.ldw & 7) || sh.epi < EPI_NONE || sh.epi > EPI_GELU || (sh.epi == EPI_SWIGLU && (sh.N & 1))) return refused;
+    return plan_thin(sh, tune);
 }
 
 // the MXFP4 weight stream (gemv_fp4.hip): 16-byte loads of whole blocks, 32-bit row offsets; emu_gemm_tune bits 24-25 set the row
@@ -958,7 +998,8 @@ GemvPlan gemv_plan(const GemvShape& sh, int tune) {
     // (tools/thin_ab.py, profiles/r03_thin_stream_ab.log): 5 rows 42.7 / 17.9 / 74.6 / 42.6 us (qkv / o / gate-up / down) against
     // 46.4 / 21.7 / 77.4 / 47.6 on the v_dot2c kernel, 8 rows 43.7 vs 60.7, 16 rows 49.2 vs 92.0 (register-fed MFMA); at 2-3
     // rows the v_dot2c kernel is level or ahead (qkv 40.6 vs 41.0).  emu_gemm_tune bit 2 switches it off (A/B).
-    if (sh.M >= 4 && !(tune & 4) && gemv_thin_ok(sh)) return plan_thin(sh, tune);
+    if (sh.M >= 4 && !(tune & 4) && !f8)
+        if (const GemvPlan p = gemv_thin_plan(sh, tune); !p.status) return p;
     // 9..16 rows: the register-fed 16x16x32 MFMA stream.  Up to 8 rows the v_dot2c block kernel is faster (M = 2: 6.4 vs 4.1 TB/s,
     // M = 5: 4.5 vs 3.9, M = 8: 3.7 vs 3.5; tools/kbench.py --filter rows): its row-contiguous 1 KiB loads use HBM better
     // than the MFMA fragment's 64 bytes per row.
@@ -985,10 +1026,13 @@ GemvPlan gemv_plan(const GemvShape& sh, int tune) {
 
 // the one-row views of the plan (the successor's geometry for l2_warm.h and the persistent engine's column partition come from the
 // same place as the launch)
-static GemvPlan one_row_view(int N, int K, bool norm, int epi) {
+GemvShape gemv_one_row_shape(int N, int K, bool norm, int epi) {
     GemvShape sh{};
     sh.M = 1; sh.N = N; sh.K = K; sh.ldx = sh.ldw = K; sh.epi = epi; sh.norm = norm; sh.w_aligned = sh.x_aligned = 1;
-    return plan_one_row(sh, emu_gemm_tune_get());
+    return sh;
+}
+static GemvPlan one_row_view(int N, int K, bool norm, int epi) {
+    return plan_one_row(gemv_one_row_shape(N, K, norm, epi), emu_gemm_tune_get());
 }
 GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi) {
     const GemvPlan p = one_row_view(N, K, norm, epi);
@@ -996,17 +1040,41 @@ GemvGeom emu_gemv_geometry(int N, int K, bool norm, int epi) {
 }
 int emu_gemv_partition(int N, int K, bool norm, int epi) { return one_row_view(N, K, norm, epi).partition; }
 
-int launch_gemv(const GemvArgs& a, hipStream_t s) {
+GemvShape gemv_shape_of(const GemvArgs& a) {
     GemvShape sh{};
     sh.M = a.M; sh.N = a.N; sh.K = a.K; sh.ldx = a.ldx; sh.ldw = a.ldw; sh.lds = a.lds; sh.epi = a.epi;
     sh.norm = a.norm_w != nullptr; sh.fp8 = a.wscale != nullptr; sh.fp4 = a.w4scale != nullptr;
     sh.w_aligned = (reinterpret_cast<size_t>(a.W) & 15) == 0; sh.x_aligned = (reinterpret_cast<size_t>(a.x) & 15) == 0;
-    return launch_planned(gemv_plan(sh, emu_gemm_tune_get()), a, s);
+    return sh;
+}
+int launch_gemv(const GemvArgs& a, hipStream_t s) {
+    return launch_planned(gemv_plan(gemv_shape_of(a), emu_gemm_tune_get()), a, s);
 }
 
-// C-ABI test hook (include/emu_hip.h)
+// what only the pointers of an argument block can answer for the matrix-core kernels (the scale pointer of the weight kind is what
+// names the kind in gemv_shape_of, so it is there)
+static bool mfma_pointers_ok(const GemvArgs& a) {
+    return a.x && a.W && a.out && (a.epi != EPI_RESID || a.res) && (reinterpret_cast<size_t>(a.w4scale) & 3) == 0;
+}
+int launch_gemv_thin_stream(const GemvArgs& a, hipStream_t s) {
+    const GemvPlan p = gemv_thin_plan(gemv_shape_of(a), emu_gemm_tune_get());
+    return p.status || !mfma_pointers_ok(a) ? -22 : launch_planned(p, a, s);
+}
+bool fp4_mfma_ok(const GemvArgs& a) { return a.M >= 17 && fp4_mfma_shape_ok(gemv_shape_of(a)) && mfma_pointers_ok(a); }
+
+// C-ABI test hooks (include/emu_hip.h)
 int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
-    if (!shape || !out) return -22;
-    *out = gemv_plan(*shape, tune);
-    return out->status;
+    return shape && out ? (*out = gemv_plan(*shape, tune)).status : -22;
+}
+int emu_gemv_thin_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
+    return shape && out ? (*out = gemv_thin_plan(*shape, tune)).status : -22;
+}
+// the older view of the fp8 few-row plan: row-contiguous or strided operands on aligned buffers, no fused norm
+int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out) {
+    if (!out) return -22;
+    GemvShape sh{};
+    sh.M = M; sh.N = N; sh.K = K; sh.ldx = ldx; sh.ldw = ldw; sh.epi = epi; sh.fp8 = sh.w_aligned = sh.x_aligned = 1;
+    const GemvPlan p = gemv_thin_plan(sh, tune);                     // refused: every field but the status is 0
+    *out = {p.status, p.rows, p.mb, p.status ? 0 : 256, p.stages, p.stages * (p.rows * 256 + p.mb * 512), p.grid, p.block};
+    return p.status;
 }

@@ -20,6 +20,9 @@
 //     then residual or SiLU(gate) * up -- thin_stream_kernel's rounding points), the one the 4-bit GEMM uses.  No fused RMSNorm:
 //     callers normalise first.
 // Algorithmic bytes per call = N * (K/2 + K/32).  Activations add MR * 512 / (RN * 136) of that as L2 -> LDS traffic.
+// Which tile, which grid, which arguments are acceptable: gemv.hip::gemv_thin_plan (weight kind MXFP4, family GEMV_FAM_FP4_THIN), the
+// one host planner of the three few-row matrix-core streams; launch_gemv_fp4_thin below is only the switch from its answer (and
+// K % 256: TAIL) to template arguments, and callers come through gemv.hip::launch_gemv_thin_stream.
 //
 // Conversion semantics on the device (pinned by tests/test_gpu_fp4_wide.py::test_decode_exhaustive_mfma): low nibble -> element 0;
 // the scale operand contributes 2^(its exponent field - 127).  With scale bytes 1 and 2 some products lie below 2^-126 (bf16
@@ -148,44 +151,24 @@ __global__ __launch_bounds__(256) void fp4_thin_kernel(const GemvArgs a) {
 }
 
 template <int RN, int MR, int NSTG, bool TAIL>
-int launch_fp4_thin(const GemvArgs& a, hipStream_t s) {
-    const dim3 grid((a.N + RN - 1) / RN), block(256);
-#define EMU_F4T_CASE(E) case E: hipLaunchKernelGGL((fp4_thin_kernel<E, RN, MR, NSTG, TAIL>), grid, block, 0, s, a); break;
-    switch (a.epi) {
-        EMU_F4T_CASE(EPI_NONE)
-        EMU_F4T_CASE(EPI_RESID)
-        EMU_F4T_CASE(EPI_SWIGLU)
-        default: return -22;
-    }
+int launch_fp4_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+#define EMU_F4T_CASE(E) case E: hipLaunchKernelGGL((fp4_thin_kernel<E, RN, MR, NSTG, TAIL>), dim3(p.grid), dim3(p.block), 0, s, a); break;
+    EMU_EPI3(EMU_F4T_CASE)
 #undef EMU_F4T_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // namespace
 
-bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows, bool tail_ok) {
-    return a.w4scale && a.x && a.W && a.out && !a.norm_w && !a.wscale && a.M >= min_rows && a.M <= max_rows && a.N >= 1 && a.K >= 256 &&
-           (a.K % (tail_ok ? 32 : 256)) == 0 && (a.ldw & 15) == 0 && (a.ldx & 7) == 0 && (a.lds & 3) == 0 && a.ldw >= a.K / 2 && a.ldx >= a.K &&
-           a.lds >= fp4_scale_stride(a.K) && (reinterpret_cast<size_t>(a.W) & 15) == 0 && (reinterpret_cast<size_t>(a.x) & 15) == 0 &&
-           (reinterpret_cast<size_t>(a.w4scale) & 3) == 0 &&
-           (a.epi == EPI_NONE || (a.epi == EPI_RESID && a.res) || (a.epi == EPI_SWIGLU && !(a.N & 1)));
-}
-bool gemv_fp4_thin_ok(const GemvArgs& a) { return fp4_mfma_ok(a, 1, 16); }
-
-// 32 weight rows per workgroup: measured against 16 at the five LLaMA-33B shapes (tools/fp4_wide_time.py --ab, emu_gemm_tune bits
-// 28-29: 1 / 2 = 16 / 32), 32 rows win everywhere, also where they leave CUs without a workgroup -- qkv 28.1 vs 42.0 us, o_proj 13.1
-// vs 17.6, down 25.5 vs 38.6 at 5 rows: the activation rows a workgroup re-stages from L2 weigh twice the 4-bit bytes of 16 weight
-// rows.  The ring is as deep as lets three workgroups share a CU's LDS.
-// The same tiles whether or not K ends in a partial stage (tail_ok admits one; a K of whole stages runs the kernels without it).
-template <bool TAIL>
-static int dispatch_fp4_thin(const GemvArgs& a, hipStream_t s) {
-    const int pin = (emu_gemm_tune_get() >> 28) & 3;
-    const bool rn32 = pin != 1;
-    if (a.M <= 8) return rn32 ? launch_fp4_thin<32, 8, 5, TAIL>(a, s) : launch_fp4_thin<16, 8, 6, TAIL>(a, s);
-    return rn32 ? launch_fp4_thin<32, 16, 4, TAIL>(a, s) : launch_fp4_thin<16, 16, 4, TAIL>(a, s);
-}
-int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s, bool tail_ok) {
-    if (!fp4_mfma_ok(a, 1, 16, tail_ok)) return -22;
-    return a.K % KC ? dispatch_fp4_thin<true>(a, s) : dispatch_fp4_thin<false>(a, s);
+// the built (weight rows, activation rows, ring depth) combinations, each with and without the partial last stage (TAIL: K % 256 != 0);
+// gemv.hip::gemv_thin_plan picks among them
+int launch_gemv_fp4_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
+#define EMU_F4T_TILE(RN, MR, NSTG) return a.K % KC ? launch_fp4_thin<RN, MR, NSTG, true>(a, p, s) : launch_fp4_thin<RN, MR, NSTG, false>(a, p, s);
+    switch ((p.rows * 100 + p.mb) * 10 + p.stages) {   // digits: rows, mb (two), stages
+        case 32085: EMU_F4T_TILE(32, 8, 5)
+        case 16086: EMU_F4T_TILE(16, 8, 6)
+        case 32164: EMU_F4T_TILE(32, 16, 4)
+        case 16164: EMU_F4T_TILE(16, 16, 4)
+        default: return -22;
+    }
+#undef EMU_F4T_TILE
 }

@@ -31,6 +31,9 @@
 //     RN 32, MR  8, 4 stages:  40 VGPRs + 8 AGPRs, 49152 bytes LDS        RN 32, MR 16, 3 stages:  40 VGPRs + 8 AGPRs, 49152 bytes LDS
 //     RN 16, MR  8, 6 stages:  32 VGPRs + 4 AGPRs, 49152 bytes LDS        RN 16, MR 16, 4 stages:  36 VGPRs + 4 AGPRs, 49152 bytes LDS
 // (the LDS ring, not the registers, sets the occupancy: three workgroups per CU)
+// Which instantiation, which grid, which arguments are acceptable: gemv.hip::gemv_thin_plan (weight kind fp8, family GEMV_FAM_FP8_THIN),
+// the one host planner of the three few-row matrix-core streams; launch_gemv_fp8_thin below is only the switch from its answer to
+// template arguments, and callers come through gemv.hip::launch_gemv_thin_stream.
 #include "common.h"
 #include "kernels.h"
 #include "fp4_tile.h"
@@ -138,53 +141,16 @@ __global__ __launch_bounds__(256) void fp8_thin_kernel(const GemvArgs a) {
 }
 
 template <int RN, int MR, int NSTG>
-int launch_fp8_thin(const GemvArgs& a, const emu_gemv_fp8_thin_plan_t& p, hipStream_t s) {
+int launch_fp8_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
 #define EMU_F8T_CASE(E) case E: hipLaunchKernelGGL((fp8_thin_kernel<E, RN, MR, NSTG>), dim3(p.grid), dim3(p.block), 0, s, a); break;
-    switch (a.epi) {
-        EMU_F8T_CASE(EPI_NONE)
-        EMU_F8T_CASE(EPI_RESID)
-        EMU_F8T_CASE(EPI_SWIGLU)
-        default: return -22;
-    }
+    EMU_EPI3(EMU_F8T_CASE)
 #undef EMU_F8T_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // namespace
 
-// The launch geometry, from integers only (no HIP call, no global: the emu_gemm_tune mask is an argument); the C-ABI hook
-// emu_gemv_fp8_thin_plan returns the same.  Activation-row bucket 8 up to 8 rows, else 16.  32 weight rows per workgroup halve what
-// a workgroup re-stages of the activations per weight byte (MR * 512 against RN * 256 bytes per stage); 16 where 32 would leave
-// fewer than 128 workgroups, half the CUs of the device (short shards, the tests' small N).  emu_gemm_tune bits 28-29 pin 16 / 32
-// (1 / 2), as for the MXFP4 few-row stream.  The ring is as deep as 48 KiB hold: three workgroups share a CU's LDS.
-emu_gemv_fp8_thin_plan_t gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune) {
-    emu_gemv_fp8_thin_plan_t p{};
-    p.status = -22;
-    if (M < 1 || M > 16 || N < 1 || K < F8_KC || (K % F8_KC) || (ldw & 15) || (ldx & 7) || ldw < K || ldx < K) return p;
-    if ((epi != EPI_NONE && epi != EPI_RESID && epi != EPI_SWIGLU) || (epi == EPI_SWIGLU && (N & 1))) return p;
-    const int pin = (tune >> 28) & 3;
-    p.rows = pin == 1 ? 16 : pin == 2 ? 32 : (N + 31) / 32 >= 128 ? 32 : 16;
-    p.mb = M <= 8 ? 8 : 16;
-    p.kc = F8_KC;
-    const int stage = p.rows * F8_WROW + p.mb * F8_XROW;
-    p.stages = 49152 / stage;
-    p.lds_bytes = p.stages * stage;
-    p.grid = (N + p.rows - 1) / p.rows;
-    p.block = 256;
-    p.status = 0;
-    return p;
-}
-
-bool gemv_fp8_thin_ok(const GemvArgs& a) {
-    return a.wscale && !a.w4scale && a.x && a.W && a.out && !a.norm_w && (reinterpret_cast<size_t>(a.W) & 15) == 0 &&
-           (reinterpret_cast<size_t>(a.x) & 15) == 0 && (a.epi != EPI_RESID || a.res) &&
-           gemv_fp8_thin_plan(a.M, a.N, a.K, a.ldx, a.ldw, a.epi, 0).status == 0;
-}
-
-int launch_gemv_fp8_thin(const GemvArgs& a, hipStream_t s) {
-    if (!gemv_fp8_thin_ok(a)) return -22;
-    const emu_gemv_fp8_thin_plan_t p = gemv_fp8_thin_plan(a.M, a.N, a.K, a.ldx, a.ldw, a.epi, emu_gemm_tune_get());
+// the built (weight rows, activation rows, ring depth) combinations; gemv.hip::gemv_thin_plan picks among them
+int launch_gemv_fp8_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     switch ((p.rows * 100 + p.mb) * 10 + p.stages) {   // digits: rows, mb (two), stages
         case 32084: return launch_fp8_thin<32, 8, 4>(a, p, s);
         case 32163: return launch_fp8_thin<32, 16, 3>(a, p, s);
@@ -192,11 +158,4 @@ int launch_gemv_fp8_thin(const GemvArgs& a, hipStream_t s) {
         case 16164: return launch_fp8_thin<16, 16, 4>(a, p, s);
         default: return -22;
     }
-}
-
-// C-ABI test hook (include/emu_hip.h)
-extern "C" int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out) {
-    if (!out) return -22;
-    *out = gemv_fp8_thin_plan(M, N, K, ldx, ldw, epi, tune);
-    return out->status;
 }

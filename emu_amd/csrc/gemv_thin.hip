@@ -13,6 +13,8 @@
 //   * wave w multiplies k-steps 2w, 2w + 1 of every stage (A = weight rows, B = activation rows, columns >= M repeat row M - 1
 //     and are dropped), so the VALU does nothing in the loop; the four partial 16 x 16 products meet in LDS at the end.
 // Algorithmic bytes per call = 2*N*K; the activations add MR / RN of that in L2 -> LDS traffic, nothing in HBM.
+// Which instantiation, which grid: gemv.hip::gemv_thin_plan, the one host planner of this stream and its fp8 and MXFP4 siblings
+// (gemv_fp8_thin.hip, gemv_fp4_thin.hip); launch_gemv_thin below is only the switch from its answer to template arguments.
 #include "common.h"
 #include "kernels.h"
 #include "gemm_tile.h"
@@ -144,22 +146,13 @@ __global__ __launch_bounds__(256) void thin_stream_kernel(const GemvArgs a) {
 template <int RN, int MR, int NSTG, int KCH>
 int launch_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
 #define EMU_TH_CASE(E) case E: hipLaunchKernelGGL((thin_stream_kernel<E, RN, MR, NSTG, KCH>), dim3(p.grid), dim3(p.block), 0, s, a); break;
-    switch (a.epi) {
-        EMU_TH_CASE(EPI_NONE)
-        EMU_TH_CASE(EPI_RESID)
-        EMU_TH_CASE(EPI_SWIGLU)
-        EMU_TH_CASE(EPI_SILU)
-        EMU_TH_CASE(EPI_GELU)
-        default: return -22;
-    }
+    EMU_EPI5(EMU_TH_CASE)
 #undef EMU_TH_CASE
-    EMU_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // namespace
 
-// the built (weight rows, activation rows, ring depth, slots per row and stage) combinations; gemv.hip::plan_thin picks among them
+// the built (weight rows, activation rows, ring depth, slots per row and stage) combinations; gemv.hip::gemv_thin_plan picks among them
 int launch_gemv_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s) {
     switch (((p.rows * 100 + p.mb) * 10 + p.stages) * 100 + p.kch) {       // digits: rows, mb (two), stages ' kch
         case 16084'32: return launch_thin<16, 8, 4, 32>(a, p, s);

@@ -31,16 +31,23 @@ struct GemvArgs {
     WarmPlan warm;
 };
 // The stream plan (gemv.hip): gemv_plan is everything launch_gemv decides between a shape and a launch -- pure host arithmetic, no
-// HIP call, no global read (tune: the emu_gemm_tune mask) -- and launch_gemv is shape -> gemv_plan -> one launch of the plan.  The
-// C-ABI test hook emu_gemv_plan returns the same (include/emu_hip.h describes the fields).
+// HIP call, no global read (tune: the emu_gemm_tune mask) -- and launch_gemv is shape (gemv_shape_of) -> gemv_plan -> one launch of
+// the plan.  The three matrix-core few-row streams (bf16 gemv_thin.hip, fp8 gemv_fp8_thin.hip, MXFP4 gemv_fp4_thin.hip) have one
+// planner of the same kind inside it, gemv_thin_plan, which picks the kind from the shape's fp8 / fp4 flags: gemv_plan asks it for
+// bf16 from 4 rows on, and launch_gemv_thin_stream is shape -> gemv_thin_plan -> the checks only pointers can answer (x, W, out,
+// res under RESID, a 4-byte aligned w4scale) -> one launch of the plan, for any of the three kinds.  The C-ABI test hooks
+// emu_gemv_plan / emu_gemv_thin_plan return the same (include/emu_hip.h describes the fields).
 using GemvShape = emu_gemv_shape;
 using GemvPlan = emu_gemv_plan_t;
 enum GemvFamily { GEMV_FAM_BLOCK = 0, GEMV_FAM_RT = 1, GEMV_FAM_WAVE = 2, GEMV_FAM_MFMA = 3, GEMV_FAM_THIN = 4, GEMV_FAM_FP8_BLOCK = 5,
-                  GEMV_FAM_FP8_RT = 6, GEMV_FAM_FP4_ROWS = 7 };
+                  GEMV_FAM_FP8_RT = 6, GEMV_FAM_FP4_ROWS = 7, GEMV_FAM_FP8_THIN = 8, GEMV_FAM_FP4_THIN = 9 };
 // the form of a one-row bf16 stream; workgroup j reads weight rows [j * rows, j * rows + rows)  (GEMV_FORM_WAVE: 4 waves x 4 whole rows)
 enum GemvForm { GEMV_FORM_ROLLING = 0, GEMV_FORM_HEAD = 1, GEMV_FORM_PRELOAD = 2, GEMV_FORM_RT = 3, GEMV_FORM_WAVE = 4 };
+GemvShape gemv_shape_of(const GemvArgs& a);
+GemvShape gemv_one_row_shape(int N, int K, bool norm, int epi);   // one bf16 row on aligned, row-contiguous operands
 GemvPlan gemv_plan(const GemvShape& shape, int tune);
 int launch_gemv(const GemvArgs& a, hipStream_t s);
+int launch_gemv_thin_stream(const GemvArgs& a, hipStream_t s);
 // the plan of a one-row bf16 stream on aligned, row-contiguous operands under the current emu_gemm_tune mask, projected to
 // {form, rows} (the successor geometry of l2_warm.h)
 struct GemvGeom { int form, rows; };
@@ -50,12 +57,16 @@ inline bool gemv_form_warms(int form) { return form == GEMV_FORM_HEAD || form ==
 // 9..16 rows reach the stream family (the register-fed MFMA kernel, or the thin stream ahead of it) exactly when this holds; the
 // callers that choose between launch_gemv and a GEMM ask here
 bool gemv_rows_9_16_ok(int M, int K, int ldx, int ldw, bool norm, bool fp8, int epi);
-// the family launchers of the other files, called by launch_gemv with a plan of their family: the MXFP4 weight stream (gemv_fp4.hip;
-// plan_fp4: threads per row set and row sets per workgroup for rows of KB blocks) and the thin LDS-DMA stream (gemv_thin.hip)
+// the family launchers of the other files, called with a plan of their family, each only the switch from plan fields to template
+// arguments (-22: a combination that is not built): the MXFP4 weight stream of 1..2 rows (gemv_fp4.hip; plan_fp4: threads per row set
+// and row sets per workgroup for rows of KB blocks) and the three LDS-DMA streams on the matrix cores (gemv_thin.hip,
+// gemv_fp8_thin.hip: a.wscale set, W = e4m3 bytes, ldw in bytes; gemv_fp4_thin.hip: a.w4scale set, W = element bytes, ldw in bytes)
 constexpr int GEMV_FP4_MAX_SETS = 16;
 int launch_gemv_fp4(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
 void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
 int launch_gemv_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
+int launch_gemv_fp8_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
+int launch_gemv_fp4_thin(const GemvArgs& a, const GemvPlan& p, hipStream_t s);
 // the MXFP4 quantiser: bf16 [N, ldw] -> element bytes [N, ldq] + E8M0 scales [N, lds], bit-exact with
 // emu_amd/mxfp4.py::quantize_rows; -22 for non-finite weights (the call waits for its own result)
 int launch_quant_mxfp4_rows(const bf16_t* w, int ldw, uint8_t* q, int ldq, uint8_t* scales, int lds, int N, int K, hipStream_t s);
@@ -89,24 +100,13 @@ int launch_gemv_merge(const GemvMergeArgs& a, hipStream_t s);
 // row by 4-byte LDS-DMA, so a scale row spans whole stages: fp4_scale_stride(K) bytes at least -- K / 32 where K % 256 == 0, else
 // 8 per started stage (K = 896: 32, K = 2240: 72); the padding bytes are read and never used (emu_amd/mxfp4.py::scale_stride).
 inline int fp4_scale_stride(int K) { return K % 256 == 0 ? K / 32 : 8 * ((K + 255) / 256); }
-// fp4_mfma_ok is the one argument check of both kernels: min_rows <= M <= max_rows, K >= 256 and K % 256 == 0 (tail_ok: K % 32 == 0,
-// the last stage partial), lds % 4 == 0 and lds >= fp4_scale_stride(K), 16-byte aligned W and x, no fused norm; epi NONE / RESID /
-// SWIGLU
-bool fp4_mfma_ok(const GemvArgs& a, int min_rows, int max_rows, bool tail_ok = false);
-// 1..16 rows: a weight stream, every converted fragment used by one MFMA (gemv_fp4_thin.hip); fp4_mfma_ok(a, 1, 16, tail_ok)
-bool gemv_fp4_thin_ok(const GemvArgs& a);
-int launch_gemv_fp4_thin(const GemvArgs& a, hipStream_t s, bool tail_ok = false);
-// 17 rows and more: a two-dimensional tile, each converted weight fragment feeding several MFMAs (gemm_fp4.hip); ragged M and N;
-// fp4_mfma_ok(a, 17, INT_MAX, tail_ok)
-bool gemm_fp4_ok(const GemvArgs& a);
-int launch_gemm_fp4(const GemvArgs& a, hipStream_t s, bool tail_ok = false);
-// fp8 weights (a.wscale set; W = e4m3 bytes, ldw in bytes) for 1..16 rows on the matrix cores (gemv_fp8_thin.hip): LDS-DMA stages,
-// the bytes converted in registers, v_mfma_f32_16x16x32_bf16, the row scale and store_c4 in the epilogue.  gemv_fp8_thin_plan is the
-// launch geometry from integers (status -22: K < 256 or K % 256, ldw % 16, ldx % 8, M outside 1..16, an epilogue other than NONE /
-// RESID / SWIGLU); gemv_fp8_thin_ok adds what only the argument block knows (16-byte aligned W and x, no fused norm, res for RESID)
-emu_gemv_fp8_thin_plan_t gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune);
-bool gemv_fp8_thin_ok(const GemvArgs& a);
-int launch_gemv_fp8_thin(const GemvArgs& a, hipStream_t s);
+// 1..16 rows: a weight stream, every converted fragment used by one MFMA (gemv_fp4_thin.hip), planned by gemv_thin_plan.
+// 17 rows and more: a two-dimensional tile, each converted weight fragment feeding several MFMAs (gemm_fp4.hip); ragged M and N.
+// fp4_mfma_ok (gemv.hip) is its argument check: the shape conditions of the few-row plan but for the row count -- K >= 256 and
+// K % 32 == 0 (K % 256 != 0: the last stage partial), lds % 4 == 0 and lds >= fp4_scale_stride(K), 16-byte aligned W and x, no fused
+// norm, epi NONE / RESID / SWIGLU -- and the same pointer checks
+bool fp4_mfma_ok(const GemvArgs& a);
+int launch_gemm_fp4(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

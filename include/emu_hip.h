@@ -117,12 +117,26 @@ typedef struct {
     int grid, block, partition;
 } emu_gemv_plan_t;
 int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
-/* CPU test hook (tests/test_fp8_wide_host.py): what emu_linear_fp8w_thin_bf16 would launch for M rows over an fp8 matrix [N, K]
- * (ldx in bf16 elements, ldw in bytes) under tune (emu_gemm_tune) -- host arithmetic only.  rows: weight rows per workgroup (16 / 32;
- * grid = ceil(N / rows)); mb: the built activation-row bucket (8 / 16); kc: k per stage; stages: depth of the LDS ring; lds_bytes =
- * stages * (rows * kc + mb * kc * 2); block = 256.  Returns the status the launch would: 0, or -22 (then the other fields are 0)
- * for M outside 1..16, K < 256 or K % 256 != 0, ldw % 16 != 0, ldx % 8 != 0, a stride below K, an epilogue other than NONE / RESID /
- * SWIGLU, or an odd N under SWIGLU. */
+/* CPU test hook (tests/test_thin_plan.py): the one planner of the three few-row weight streams on the matrix cores -- what the
+ * 3..16-row steps of a generation (emu_linear_fp8w_thin_bf16, emu_linear_fp4w_mfma_bf16 / emu_linear_fp4w_thin_bf16 up to 16 rows,
+ * and emu_linear_bf16 where emu_gemv_plan answers family 4) launch for an argument block of this shape under tune -- host arithmetic
+ * only.  The shape's fp8 / fp4 flags pick the weight kind (both: refused).  In the plan, family is 4 (bf16), 8 (fp8) or 9 (MXFP4);
+ * rows: weight rows per workgroup (16 / 32; grid = ceil(N / rows)); mb: the built activation-row bucket (8 up to 8 rows, else 16);
+ * stages: depth of the LDS ring; kch: 16-byte slots per staged weight row (bf16 32 / 64, fp8 16, MXFP4 8; a stage is kch * 8 * 2 /
+ * bytes-per-weight = 256 k, 512 for kch 64); waves 4, block 256; the other fields 0.  LDS bytes of the ring: stages * (rows + mb) *
+ * kch * 16 (bf16), stages * (rows * 256 + mb * 512) (fp8), stages * (rows * 128 + mb * 512 + 1024) (MXFP4, whose instantiation with
+ * a partial last stage is the one launched iff K % 256 != 0).  tune: bits 8-11 (bf16 variants) and 28-29 (fp8 / MXFP4: 1 / 2 pin
+ * 16 / 32 weight rows); no other bit is read -- bit 2 is emu_gemv_plan's routing.  Returns 0, or -22 (then the other fields are 0):
+ *   bf16   M outside 2..16, K < 256 or K % 256 != 0, ldw % 8 or ldx % 8 != 0, an epilogue outside NONE .. GELU;
+ *   fp8    M outside 1..16, K < 256 or K % 256 != 0, ldw % 16 or ldx % 8 != 0, a stride below K, an epilogue other than NONE /
+ *          RESID / SWIGLU;
+ *   MXFP4  M outside 1..16, K < 256 or K % 32 != 0, ldw % 16, ldx % 8 or lds % 4 != 0, ldw < K / 2, ldx < K, lds below 8 bytes per
+ *          started 256-wide stage (K / 32 where K % 256 == 0), an epilogue other than NONE / RESID / SWIGLU;
+ *   all    N < 1, a fused norm, W or x off a 16-byte boundary, an odd N under SWIGLU. */
+int emu_gemv_thin_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
+/* The older view of the fp8 branch of emu_gemv_thin_plan (tests/test_fp8_wide_host.py): M rows over an fp8 matrix [N, K] (ldx in bf16
+ * elements, ldw in bytes) on aligned buffers.  rows, mb, stages, grid, block: the plan's; kc = 256: k per stage; lds_bytes = stages *
+ * (rows * kc + mb * kc * 2).  Returns 0, or -22 (then the other fields are 0). */
 typedef struct {
     int status, rows, mb, kc, stages, lds_bytes, grid, block;
 } emu_gemv_fp8_thin_plan_t;
