@@ -894,7 +894,206 @@ void launch_combine(const DecodeFusedArgs& a, int ns, hipStream_t s) {
     else
         hipLaunchKernelGGL((decode_fused_combine_kernel<D, 0>), grid, block, 0, s, a.ws, a.slot, a.o, a.o_sb, a.o_sh, a.H, ns, wp);
 }
+
+// One 128-key split of sequence b against the T (<= NT) rows of a chunk step (DecodeChunkArgs): decode_shared_split's scheme -- the
+// split's K / V rows are loaded once and stay in registers, every row's split state is formed with the arithmetic and the summation
+// order of the one-row path -- with validity PER ROW (row i sees keys <= slot0 + i) and with the chunk's own slots taken from the
+// freshly rotated rows in LDS, never read back from the cache this launch writes.  The states go to the workspace per (row, head,
+// split), row = b * T + i, and `rowslot` gets every row's slot: decode_fused_combine_kernel merges them as it merges B * T rows.
+template <int D, int NT>
+__global__ __launch_bounds__(256) void decode_chunk_kernel(const DecodeChunkArgs a, int nsplit, int32_t* rowslot) {
+    constexpr int LPK = D / 8, KPI = 64 / LPK, ITER = (DF_CHUNK / 4) / KPI, NP = 4 * KPI, half = D / 2;
+    constexpr int ST_BYTES = NT * NP * (D + 2) * 4, PRE_BYTES = 3 * NT * D * 4;
+    // the rotated q / new k / new v rows are dead once every lane holds its scores and sums: the states take their place
+    __shared__ __attribute__((aligned(16))) char smem[ST_BYTES > PRE_BYTES ? ST_BYTES : PRE_BYTES];
+    float (*st)[NP][D + 2] = reinterpret_cast<float (*)[NP][D + 2]>(smem);
+    float (*qs)[D] = reinterpret_cast<float (*)[D]>(smem);
+    float (*ks)[D] = qs + NT;
+    float (*vs)[D] = ks + NT;
+    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int g = lane / LPK, dl = lane % LPK, d0 = dl * 8;
+    const int T = a.T;
+    const int slot0 = a.slot0[b], pos0 = a.pos0[b];
+    const int kstart = a.kstart ? a.kstart[b] : 0;
+    const int k0 = split * DF_CHUNK, last = slot0 + T - 1;
+    if (split == 0 && h == 0 && tid < T) rowslot[b * T + tid] = slot0 + tid;   // (split 0 is live for every row)
+    if (k0 > last) return;                             // split beyond the chunk's last row: no work, nobody reads its states
+    const size_t hb = ((size_t)b * a.H + h) * a.S_max;
+    const bf16_t* kc = a.kcache + hb * D;
+    const bf16_t* vc = a.vcache + hb * D;
+    // ---- loads first: lane group tid / LPK rotates row ri's q and new key (slice tid % LPK), then this wave's 32 keys
+    const bool rl = tid < T * LPK;
+    const int ri = rl ? tid / LPK : 0, rd0 = (tid % LPK) * 8;
+    const int rdp = (rd0 + half) % D, rdc = rd0 % half;
+    const bf16_t* qh = a.qkv + (size_t)(b * T + ri) * 3 * a.H * D + (size_t)h * D;
+    const bf16_t* kh = qh + (size_t)a.H * D;
+    const bf16_t* vh = kh + (size_t)a.H * D;
+    const u32x4 cv = ld16(a.cos + (size_t)(pos0 + ri) * D + rdc), sv = ld16(a.sin + (size_t)(pos0 + ri) * D + rdc);
+    const u32x4 q1v = ld16(qh + rd0), q2v = ld16(qh + rdp), k1v = ld16(kh + rd0), k2v = ld16(kh + rdp), nvv = ld16(vh + rd0);
+    u32x4 kr[ITER], vr[ITER];
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int key = k0 + wave * (DF_CHUNK / 4) + it * KPI + g;
+        const int kc_i = key < a.S_max ? key : a.S_max - 1;                  // clamped, not predicated (decode_fused_kernel)
+        kr[it] = ld16(kc + (size_t)kc_i * D + d0);
+        vr[it] = ld16(vc + (size_t)kc_i * D + d0);
+    }
+    if (rl) {
+        float c[8], sn[8], x1[8], x2[8], rq[8], nk[8], nv[8];
+        unpack8(cv, c); unpack8(sv, sn);
+        const float sgn = rd0 < half ? -1.f : 1.f;
+        unpack8(q1v, x1); unpack8(q2v, x2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rq[j] = bfround(bfround(x1[j] * c[j]) + bfround(sgn * x2[j] * sn[j]));
+        unpack8(k1v, x1); unpack8(k2v, x2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) nk[j] = bfround(bfround(x1[j] * c[j]) + bfround(sgn * x2[j] * sn[j]));
+        unpack8(nvv, nv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { qs[ri][rd0 + j] = rq[j]; ks[ri][rd0 + j] = nk[j]; vs[ri][rd0 + j] = nv[j]; }
+        // Append row ri at its slot (once: by the split that owns the slot).  A speculative step appends all T rows although the
+        // rows behind the first rejected draft are wrong: their slots lie past the accepted ones, the next chunk starts at the first
+        // of them and appends its own rows there in this very place -- and takes its own slots from LDS, not from the cache -- before
+        // any query can see them, and no query sees a key above its own slot.  So nothing is rolled back.
+        const int slot = slot0 + ri;
+        if (split == slot / DF_CHUNK && slot < a.S_max) {
+            st16(a.kcache + (hb + slot) * D + rd0, pack8(nk));
+            st16(a.vcache + (hb + slot) * D + rd0, pack8(nv));
+        }
+    }
+    __syncthreads();
+    float q[NT][8];
+#pragma unroll
+    for (int jb = 0; jb < NT; ++jb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) q[jb][j] = jb < T ? qs[jb][d0 + j] : 0.f;
+    // a split below the chunk's first slot: every row sees the same keys (decode_shared_split's case)
+    const bool mixed = k0 + DF_CHUNK > slot0;
+    float sd[NT][ITER], m[NT];
+#pragma unroll
+    for (int jb = 0; jb < NT; ++jb) m[jb] = -INFINITY;
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int key = k0 + wave * (DF_CHUNK / 4) + it * KPI + g;
+        const bool any = key <= last && key >= kstart;                       // visible to the last row at least
+        float kf[8];
+        unpack8(kr[it], kf);
+        if (mixed) {
+            const bool own = key >= slot0 && key <= last;
+            const float* kn = ks[own ? key - slot0 : 0] + d0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) kf[j] = own ? kn[j] : kf[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) kf[j] = any ? kf[j] : 0.f;
+#pragma unroll
+        for (int jb = 0; jb < NT; ++jb) {
+            float t = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) t = fmaf(kf[j], q[jb][j], t);
+            t = LPK == 16 ? row16_sum(t) : row8_sum(t);
+            const bool valid = any && key <= slot0 + jb && jb < T;
+            sd[jb][it] = valid ? t * a.scale : -INFINITY;
+            m[jb] = fmaxf(m[jb], sd[jb][it]);
+        }
+    }
+    float l[NT], acc[NT][8];
+#pragma unroll
+    for (int jb = 0; jb < NT; ++jb) {
+        l[jb] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[jb][j] = 0.f;
+    }
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+        const int key = k0 + wave * (DF_CHUNK / 4) + it * KPI + g;
+        const bool any = key <= last && key >= kstart;
+        float vf[8];
+        unpack8(vr[it], vf);
+        if (mixed) {
+            const bool own = key >= slot0 && key <= last;
+            const float* vn = vs[own ? key - slot0 : 0] + d0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) vf[j] = own ? vn[j] : vf[j];
+        }
+        // (a masked key's V row is selected away, never multiplied by its zero weight: the slot may hold anything)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vf[j] = any ? vf[j] : 0.f;
+#pragma unroll
+        for (int jb = 0; jb < NT; ++jb) {
+            const bool dead = sd[jb][it] == -INFINITY;
+            const float p = dead ? 0.f : __expf(sd[jb][it] - m[jb]);
+            l[jb] += p;
+            if (mixed) {                               // a key of a later row: this row takes a zero, as the one-row path does
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[jb][j] = fmaf(p, dead ? 0.f : vf[j], acc[jb][j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[jb][j] = fmaf(p, vf[j], acc[jb][j]);
+            }
+        }
+    }
+    __syncthreads();                                   // every lane is done with qs / ks / vs: the states overwrite them
+#pragma unroll
+    for (int jb = 0; jb < NT; ++jb) {
+        float* dst = st[jb][wave * KPI + g];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dst[d0 + j] = acc[jb][j];
+        if (dl == 0) { dst[D] = m[jb]; dst[D + 1] = l[jb]; }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < T * D; idx += 256) {
+        const int jb = idx / D, d = idx - jb * D;
+        if (k0 > slot0 + jb) continue;                 // the split lies beyond this row's context: not counted by the merge
+        float num = 0.f, den = 0.f, mt = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < NP; ++w) mt = fmaxf(mt, st[jb][w][D]);
+#pragma unroll
+        for (int w = 0; w < NP; ++w) {
+            const float f = (st[jb][w][D] == -INFINITY) ? 0.f : __expf(st[jb][w][D] - mt);
+            num = fmaf(f, st[jb][w][d], num);
+            den = fmaf(f, st[jb][w][D + 1], den);
+        }
+        float* wout = a.ws + (((size_t)(b * T + jb) * a.H + h) * nsplit + split) * (D + 2);
+        wout[d] = num;
+        if (d == 0) { wout[D] = mt; wout[D + 1] = den; }
+    }
+}
 }  // namespace
+
+size_t decode_chunk_ws_floats(int B, int T, int H, int D, int ctx_max) {
+    // the split states of B * T rows, then the rows' slots (int32) for the merge
+    return decode_fused_ws_floats(B * T, H, D, ctx_max) + (size_t)B * T;
+}
+
+int launch_decode_chunk(const DecodeChunkArgs& a, hipStream_t s) {
+    if (a.T < 2 || a.T > DECODE_CHUNK_MAX || a.B < 1 || a.H < 1 || (a.D != 64 && a.D != 128)) return -22;
+    if (a.ctx_max < 1 || a.ctx_max > a.S_max) return -22;
+    const int ns = (a.ctx_max + DF_CHUNK - 1) / DF_CHUNK;
+    int32_t* rowslot = reinterpret_cast<int32_t*>(a.ws + decode_fused_ws_floats(a.B * a.T, a.H, a.D, a.ctx_max));
+    const dim3 grid(ns, a.H, a.B);
+#define EMU_CHUNK_CASE(DD, NTT) hipLaunchKernelGGL((decode_chunk_kernel<DD, NTT>), grid, dim3(256), 0, s, a, ns, rowslot)
+    if (a.D == 128) {
+        if (a.T <= 2) EMU_CHUNK_CASE(128, 2);
+        else if (a.T <= 4) EMU_CHUNK_CASE(128, 4);
+        else if (a.T <= 5) EMU_CHUNK_CASE(128, 5);
+        else EMU_CHUNK_CASE(128, 8);
+    } else {
+        if (a.T <= 2) EMU_CHUNK_CASE(64, 2);
+        else if (a.T <= 4) EMU_CHUNK_CASE(64, 4);
+        else if (a.T <= 5) EMU_CHUNK_CASE(64, 5);
+        else EMU_CHUNK_CASE(64, 8);
+    }
+#undef EMU_CHUNK_CASE
+    // the one-row path's merge over B * T rows, each with its own slot
+    DecodeFusedArgs c{};
+    c.ws = a.ws; c.slot = rowslot; c.o = a.o; c.o_sb = a.o_sb; c.o_sh = a.o_sh; c.H = a.H; c.B = a.B * a.T; c.D = a.D;
+    if (a.D == 128) launch_combine<128>(c, ns, s);
+    else launch_combine<64>(c, ns, s);
+    EMU_CHECK_LAUNCH();
+    return 0;
+}
 
 size_t decode_fused_ws_floats(int B, int H, int D, int ctx_max) {
     const int ns = ctx_max < 1 ? 1 : (ctx_max + DF_CHUNK - 1) / DF_CHUNK;

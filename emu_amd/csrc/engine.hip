@@ -660,6 +660,15 @@ int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, con
     a.warm = g_test_warm;                            // (emu_l2_warm_test_plan; the launch ignores a plan that does not fit it)
     return launch_decode_fused(a, S(s));
 }
+size_t emu_decode_chunk_ws_bytes(int Bn, int T, int H, int D, int ctx_max) { return decode_chunk_ws_floats(Bn, T, H, D, ctx_max) * sizeof(float); }
+int emu_decode_chunk_bf16(const void* qkv, const void* cos, const void* sin, const int32_t* pos0, const int32_t* slot0, void* kcache,
+                          void* vcache, void* o, long o_sb, long o_sh, const int32_t* kstart, void* ws, int Bn, int T, int H, int D,
+                          int S_max, int ctx_max, float scale, emu_stream_t s) {
+    if (!qkv || !cos || !sin || !pos0 || !slot0 || !kcache || !vcache || !o || !ws) return -22;
+    DecodeChunkArgs a{B(qkv), B(cos), B(sin), pos0, slot0, B(kcache), B(vcache), B(o), o_sb, o_sh, kstart,
+                      reinterpret_cast<float*>(ws), Bn, T, H, D, S_max, ctx_max, scale};
+    return launch_decode_chunk(a, S(s));
+}
 
 }  // extern "C"
 
@@ -737,7 +746,8 @@ struct LlamaWs {
     float* splitk2;         // ... and K-slice scratch (the lanes' GEMMs run concurrently)
     size_t total;
 };
-LlamaWs llama_ws(const emu_llama* m, int Bn, int T, void* base) {
+// chunk: a chunk step of Bn x T rows (emu_llama_forward_chunk) -- no V^T, the split states of every row and the rows' slots
+LlamaWs llama_ws(const emu_llama* m, int Bn, int T, void* base, bool chunk = false) {
     const emu_llama_cfg& c = m->cfg;
     const size_t M = (size_t)Bn * T, HD = (size_t)c.heads_local * c.head_dim;
     char* p = reinterpret_cast<char*>(base);
@@ -750,8 +760,9 @@ LlamaWs llama_ws(const emu_llama* m, int Bn, int T, void* base) {
     w.attn = (bf16_t*)take(M * HD * 2);
     w.act = (bf16_t*)take(M * (size_t)c.ffn_local * 2);
     const size_t spad = (size_t)((m->s_max + 63) / 64) * 64;
-    w.vt = (bf16_t*)take(T > 1 ? (size_t)Bn * HD * spad * 2 : 0);
-    w.dec = (float*)take(decode_fused_ws_floats(Bn, c.heads_local, c.head_dim, m->s_max > 0 ? m->s_max : 1) * sizeof(float));
+    w.vt = (bf16_t*)take(T > 1 && !chunk ? (size_t)Bn * HD * spad * 2 : 0);
+    w.dec = (float*)take((chunk ? decode_chunk_ws_floats(Bn, T, c.heads_local, c.head_dim, m->s_max > 0 ? m->s_max : 1)
+                                : decode_fused_ws_floats(Bn, c.heads_local, c.head_dim, m->s_max > 0 ? m->s_max : 1)) * sizeof(float));
     w.splitk_floats = M > 16 ? EMU_SPLITK_SCRATCH_FLOATS : 0;
     w.splitk = (float*)take(w.splitk_floats * sizeof(float));
     const size_t kmax = std::max<size_t>(std::max<size_t>(c.hidden, HD), c.ffn_local);
@@ -833,6 +844,17 @@ struct LlamaCall {
     float scale, eps; size_t kv_layer;
     LlamaPlan plan;
     bool xn_ready;                               // the down projection of the layer before left this layer's normalised rows in w.xn
+    bool chunk = false;                          // emu_llama_forward_chunk: pos / slot are pos0 / slot0 [Bn], row i of a sequence sits i behind them
+
+    // The chunk step's plan: the per-layer launches, the projections by whatever kernel_for(Bn * T) plans, no fusion that belongs to
+    // the prompt or to the one-row step.
+    void plan_chunk() {
+        LlamaPlan& p = plan = LlamaPlan{};
+        p.path = LlamaPath::Launches;
+        p.kernel = m->kernel_for(M);
+        p.fuse_rope = p.fuse_norm = p.decode_tail = p.merge_o = false;
+        p.norm_in_gemv = p.kernel == WeightKernel::Fp8Rows || p.kernel == WeightKernel::Fp4Rows;
+    }
 
     // Decides the call's schedule and fusions; launches, zeroes and uploads nothing.  Precedence: the engine, whole layers per launch,
     // the two-lane prefill, the per-layer launches -- a schedule whose guard fails falls through to the next.
@@ -994,7 +1016,7 @@ struct LlamaCall {
             TRY(cx, project(w, win.s, plan.norm_in_gemv ? win.x : w.xn, L.qkv, nullptr, plan.norm_in_gemv ? L.ln1 : nullptr,
                             nullptr, w.qkv, rows, 3 * HD, H, EPI_NONE, wp));
         }
-        if (T == 1) return 0;                            // single-token step: the attention launch rotates and appends
+        if (T == 1 || chunk) return 0;                   // single-token and chunk steps: the attention launch rotates and appends
         if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: shared-prefix KV rows serve single-token steps only");
         if (plan.fuse_rope) return 0;
         RopeKvArgs r{w.qkv, m->cos, m->sin, win.pos, win.slot, kc, vc, Bn, win.T, Hl, D, m->s_max};
@@ -1007,7 +1029,12 @@ struct LlamaCall {
         const emu_llama::Layer& L = m->layers[l];
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
-        if (T == 1) {
+        if (chunk) {
+            // the same for T rows per sequence at consecutive slots (attention.hip: decode_chunk_kernel)
+            DecodeChunkArgs a{w.qkv, m->cos, m->sin, win.pos, win.slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec,
+                              Bn, win.T, Hl, D, m->s_max, ctx, scale};
+            TRY(cx, launch_decode_chunk(a, win.s));
+        } else if (T == 1) {
             // RoPE + KV append + attention in one launch; context = slot + 1 is read on the device (graph replay)
             DecodeFusedArgs a{w.qkv, m->cos, m->sin, win.pos, win.slot, kc, vc, w.attn, (long)HD, (long)D, kstart, w.dec,
                               Bn, Hl, D, m->s_max, ctx, scale, m->kv_share_nb, m->kv_share_len};
@@ -1585,6 +1612,37 @@ int emu_llama_forward(emu_llama* m, void* hidden, int Bn, int T, const int32_t* 
     return -22;                                  // (not reached: every path returns above)
 }
 
+size_t emu_llama_chunk_workspace_bytes(const emu_llama* m, int Bn, int T) {
+    if (!m) return 0;
+    return llama_ws(m, Bn, T, nullptr, true).total;
+}
+
+int emu_llama_forward_chunk(emu_llama* m, void* hidden, int Bn, int T, const int32_t* pos0, const int32_t* slot0, const int32_t* kstart,
+                            const int32_t* ctx_dev, int ctx_upper, void* workspace, size_t ws_bytes, emu_stream_t s_) {
+    (void)ctx_dev;                               // (every row's context follows from slot0 on the device; kept for the callers' symmetry)
+    if (!m || !hidden || !pos0 || !slot0) return -22;
+    emu_ctx* cx = m->ctx;
+    const emu_llama_cfg& c = m->cfg;
+    if (T < 2 || T > DECODE_CHUNK_MAX || Bn < 1 || Bn * T > 16) return fail(cx, -22, "emu_llama_forward_chunk: T in 2..8 and B * T <= 16");
+    if (cx->tp_size > 1 || cx->comm != nullptr || cx->p2p_on) return fail(cx, -22, "emu_llama_forward_chunk: no tensor-parallel form");
+    if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward_chunk: shared-prefix KV rows serve single-token steps only");
+    if (m->decode_fused) return fail(cx, -22, "emu_llama_forward_chunk: the fused decode modes 1-4 are one-row steps (emu_llama_set_decode_fused(m, 0, 0) first)");
+    if (!m->kcache || Bn != m->kv_batch) return fail(cx, -22, "emu_llama_forward_chunk: KV cache not set for this batch size");
+    if (ctx_upper < 1 || ctx_upper > m->s_max) return fail(cx, -22, "emu_llama_forward_chunk: ctx out of range");
+    if (!m->cos) return fail(cx, -22, "emu_llama_forward_chunk: rope tables not set");
+    LlamaCall f{};
+    f.m = m; f.cx = cx; f.ws = llama_ws(m, Bn, T, workspace, true);
+    if (f.ws.total > ws_bytes) return fail(cx, -12, "emu_llama_forward_chunk: workspace too small");
+    f.hA = B(hidden); f.pos = pos0; f.slot = slot0; f.kstart = kstart; f.s = S(s_);
+    f.Bn = Bn; f.T = T; f.M = Bn * T; f.ctx = ctx_upper; f.spad = (ctx_upper + 63) / 64 * 64; f.l_end = m->l1 < 0 ? c.layers : m->l1;
+    f.H = c.hidden; f.Hl = c.heads_local; f.D = c.head_dim; f.HD = f.Hl * f.D; f.Fl = c.ffn_local;
+    f.tp = false; f.epi_res = EPI_RESID;
+    f.scale = 1.0f / sqrtf((float)f.D); f.eps = c.rms_eps; f.kv_layer = (size_t)Bn * f.Hl * m->s_max * f.D;
+    f.chunk = true;
+    f.plan_chunk();
+    return f.run_launches();
+}
+
 size_t emu_beam_step_workspace_bytes(int Bn, int nb, int V) { return beam_step_ws_floats(Bn, nb, V) * sizeof(float); }
 int emu_beam_step_bf16(const void* logits, long ld_prompt, long ld_beam, int V, int Bn, int nb, int L, int cur, const int32_t* cur_dev,
                        int min_len, int eos_id, float length_penalty, int hf431, int32_t* running_seq, int32_t* sequences, float* running_scores, float* beam_scores,
@@ -1823,6 +1881,37 @@ int emu_llama_score_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos, i
     const ScoreSel sel{targets, T, lp, lse, top1};
     return llama_token_step(m, Bn, cur_ids, pos, slot, kstart, ctx_dev, step_dev, nullptr, 0, ctx_upper, hidden, logits, ld_logits,
                             workspace, ws_bytes, nullptr, nullptr, nullptr, &sel, nullptr, nullptr, 0, s);
+}
+
+int emu_lookup_select_bf16(const void* logits, int ld, int V, int T, int32_t* amax, int32_t* cur, int32_t* st, int32_t* pos0,
+                           int32_t* slot0, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                           int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, emu_stream_t s) {
+    const LookupArgs a{B(logits), ld, V, T, amax, cur, st, pos0, slot0, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram, max_new,
+                       min_len, eos_id, stop_on_eos};
+    int e = launch_lookup_argmax(a, S(s));
+    if (e) return e;
+    return launch_lookup_select(a, S(s));
+}
+
+// One step of the prompt-lookup loop: embed the T = 1 + k ids of `cur` (the last emitted id, then the draft) -> chunk forward -> final
+// norm + logits on the T rows -> arg-maxes -> accept / append / next draft / state advance (lookup.hip).  Capturable.
+int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                          const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                          int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
+    if (!m || !m->embed || !cur || !hidden || !logits) return -22;
+    const emu_llama_cfg& c = m->cfg;
+    const LookupArgs a{B(logits), ld_logits, c.vocab, T, amax, cur, st, pos0, slot0, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram,
+                       max_new, min_len, eos_id, stop_on_eos};
+    if (T < 2 || T > DECODE_CHUNK_MAX || !amax || !st || !pos0 || !slot0 || !ctx_dev || !out_ids || !hist || max_new < 1 || max_ngram < 1 ||
+        hist_cap < 1)
+        return -22;                                  // refused before anything is launched
+    TRY(m->ctx, launch_embed_gather(cur, m->embed, B(hidden), T, c.hidden, c.vocab, S(s)));
+    TRY(m->ctx, emu_llama_forward_chunk(m, hidden, 1, T, pos0, slot0, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
+    TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, T, logits, ld_logits, workspace, ws_bytes, s));
+    TRY(m->ctx, launch_lookup_argmax(a, S(s)));
+    TRY(m->ctx, launch_lookup_select(a, S(s)));
+    return 0;
 }
 
 }  // extern "C"

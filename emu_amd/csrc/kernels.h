@@ -403,6 +403,45 @@ constexpr int DECODE_SHARE_MAX = 8;            // beams per group the shared-pre
 size_t decode_fused_ws_floats(int B, int H, int D, int ctx_max);
 int launch_decode_fused(const DecodeFusedArgs& a, hipStream_t s);
 
+// Chunk step (prompt-lookup speculative decoding): B sequences of T rows each (2 <= T <= DECODE_CHUNK_MAX) on top of the cache.  Row i
+// of sequence b sits at cache slot slot0[b] + i and RoPE position pos0[b] + i and sees the keys kstart[b] <= key <= slot0[b] + i.
+// One launch rotates the T queries and new keys, appends the T K / V rows and forms every row's 128-key split states with the
+// arithmetic and summation order of the one-row path (a split's cache rows are loaded once for all T queries); the one-row path's
+// combine launch merges them.  Row i's output and the cache rows have the bits of T successive launch_decode_fused calls.
+struct DecodeChunkArgs {
+    const bf16_t* qkv;                         // [B*T, 3*H*D] projection rows (q | k | v), not yet rotated
+    const bf16_t* cos; const bf16_t* sin;      // [max_pos, D]
+    const int32_t* pos0;                       // [B] RoPE position of row 0
+    const int32_t* slot0;                      // [B] cache slot of row 0 (slot0 + T <= ctx_max: the caller's reservation)
+    bf16_t* kcache; bf16_t* vcache;            // [B, H, S_max, D]
+    bf16_t* o; long o_sb, o_sh;                // o[(b*T + i)*o_sb + h*o_sh + d]
+    const int32_t* kstart;                     // [B] or null
+    float* ws;                                 // decode_chunk_ws_floats(B, T, H, D, ctx_max)
+    int B, T, H, D, S_max, ctx_max;            // ctx_max sizes the launch (>= max slot0 + T)
+    float scale;
+};
+constexpr int DECODE_CHUNK_MAX = 8;
+size_t decode_chunk_ws_floats(int B, int T, int H, int D, int ctx_max);
+int launch_decode_chunk(const DecodeChunkArgs& a, hipStream_t s);
+
+// Prompt-lookup speculative greedy decoding, one sequence (lookup.hip; what is computed: emu_amd/speculate.py).  st: the loop's
+// scalars on the device, indexed by LOOKUP_*.
+enum { LOOKUP_STEP = 0, LOOKUP_FINISHED = 1, LOOKUP_NDRAFT = 2, LOOKUP_HIST_LEN = 3, LOOKUP_STEPS_RUN = 4, LOOKUP_EMITTED = 5, LOOKUP_STATE_INTS = 8 };
+struct LookupArgs {
+    const bf16_t* logits; int ld, V;           // [T, V] rows of the chunk step
+    int T;                                     // rows = 1 + k
+    int32_t* amax;                             // [T] scratch: the rows' arg-maxes
+    int32_t* cur;                              // [T] ids the next step feeds: the last emitted id, then the draft (0 beyond n_draft)
+    int32_t* st;                               // [LOOKUP_STATE_INTS]
+    int32_t *pos0, *slot0, *ctx;               // [1] each
+    int32_t* out_ids;                          // [max_new]
+    int32_t* hist; int hist_cap;               // the prompt's real ids followed by the generated ones
+    const int32_t* drafts;                     // [max_new, T - 1] or null: row `step` replaces the lookup (tests, timing)
+    int max_ngram, max_new, min_len, eos_id, stop_on_eos;
+};
+int launch_lookup_argmax(const LookupArgs& a, hipStream_t s);
+int launch_lookup_select(const LookupArgs& a, hipStream_t s);
+
 struct EmuP2p;
 // ---- whole decoder layers of a single-row decode step in ONE launch (decode_layer.hip): qkv projection (+RMSNorm) -> RoPE / KV
 // append / split attention + merge -> o_proj (+residual) -> [all-reduce] -> gate/up (+RMSNorm, SwiGLU) -> down (+residual) ->

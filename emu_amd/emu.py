@@ -22,7 +22,7 @@ from .constants import (DEFAULT_gIMG_TOKEN, DEFAULT_IMAGE_TOKEN, DEFAULT_IMG_END
                         PAD_TOKEN_ID, VOCAB_EMU2, VOCAB_EMU2_CHAT, gIMG_TOKEN_ID, special_tokens_list)
 from .constrain import pop_constraint
 from .device_loop import CapturedStep, option_or_env
-from .llama import EmuHipContext, LlamaEngine
+from .llama import EmuHipContext, LlamaEngine, tp_size_of
 
 BF16 = torch.bfloat16
 
@@ -252,7 +252,7 @@ class EmuModel:
                      penalty_alpha: Optional[float] = None, no_repeat_ngram_size: int = 0,
                      num_return_sequences: int = 1, hf_semantics: Optional[str] = None,
                      eos_token_id: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                     constraint=None) -> torch.Tensor:
+                     constraint=None, prompt_lookup_num_tokens: int = 0, max_matching_ngram_size: int = 2) -> torch.Tensor:
         """``generate`` at the token-id level: returns the NEW ids [B, n] (what HF returns for inputs_embeds).  Which engine
         method runs, and with which of this model's opt-ins: ``genroute.model_route``.
         ``hf_semantics`` (default: ``self.hf_semantics`` = "4.31", the transformers release the reference pins): beam-search
@@ -262,8 +262,16 @@ class EmuModel:
         (``_prepare_generated_length``: the default min_len = 1 then enforces nothing and EOS may be the first token -- pinned by
         the real reference's ids in tests/golden/generate_beam_eos_tiny.npz).  ``eos_token_id`` / ``min_new_tokens``: the options
         of that name the reference forwards to ``lm.generate`` through ``**kwargs`` (emu.py:175,228).  ``constraint``: an
-        ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature."""
+        ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature.
+        ``prompt_lookup_num_tokens`` = k > 0 (with ``max_matching_ngram_size``; the library's options of these names, off by default):
+        prompt-lookup speculative greedy decoding, ``LlamaEngine.lookup_generate`` -- one prompt, plain greedy search, 1 <= k <= 7, no
+        tensor parallelism; anything else is ``genroute.lookup_route``'s ValueError, before any device work."""
         B, S = input_ids.shape
+        lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size)) \
+            if prompt_lookup_num_tokens else {}
+        if lookup:
+            genroute.lookup_route(int(prompt_lookup_num_tokens), B, tp_size_of(self.decoder.lm), num_beams, do_sample, top_k, penalty_alpha,
+                                  repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint)
         sem = hf_semantics or getattr(self, "hf_semantics", "4.31")
         eos = EOS_TOKEN_ID if eos_token_id is None else int(eos_token_id)
         if min_new_tokens is not None:
@@ -281,8 +289,11 @@ class EmuModel:
             x = self._prompt_embeds(input_ids, video, self.v_query, gIMG_TOKEN_ID, embeds=x)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
         method, routing = genroute.model_route(genroute.model_flags(self), num_beams, do_sample, top_k, penalty_alpha,
-                                               repetition_penalty, ngram, nret, constraint)
+                                               repetition_penalty, ngram, nret, constraint, **lookup)
         lm, x = self.decoder.lm, x.view(B, S, -1)
+        if method == "lookup_generate":
+            return lm.lookup_generate(x, attention_mask, input_ids, max_new_tokens, min_len=min_len, eos_id=eos, pad_id=PAD_TOKEN_ID,
+                                      stop_on_eos=stop_on_eos, **routing)
         if method == "contrastive_generate":
             return lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_len,
                                            repetition_penalty, eos_id=eos, pad_id=PAD_TOKEN_ID, **routing)
@@ -323,6 +334,7 @@ class EmuModel:
         ngram = int(kwargs.pop("no_repeat_ngram_size", 0) or 0)
         nret = int(kwargs.pop("num_return_sequences", 1) or 1)
         constraint = pop_constraint(kwargs)
+        lookup = {name: int(kwargs.pop(name)) for name in ("prompt_lookup_num_tokens", "max_matching_ngram_size") if name in kwargs}
         if kwargs:
             raise TypeError(f"EmuModel.generate: unsupported generation options {sorted(kwargs)} "
                             "(the HIP engine implements greedy / beam / sampling / contrastive search with the arguments of the signature)")
@@ -334,7 +346,7 @@ class EmuModel:
                                 num_beams=num_beams, length_penalty=length_penalty, do_sample=do_sample,
                                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                 penalty_alpha=penalty_alpha, no_repeat_ngram_size=ngram, num_return_sequences=nret,
-                                eos_token_id=eos_override, min_new_tokens=min_new, constraint=constraint)
+                                eos_token_id=eos_override, min_new_tokens=min_new, constraint=constraint, **lookup)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=skip_special_tokens)
 
     # ------------------------------------------------------------------ scoring given text (no counterpart in the reference)

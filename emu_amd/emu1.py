@@ -23,7 +23,7 @@ from .conf.emu_conf import CLIPVisionCfg, LlamaCfg
 from .constants import EOS_TOKEN_ID, IMAGE_TOKEN_ID, PAD_TOKEN_ID
 from .constrain import pop_constraint
 from .device_loop import option_or_env
-from .llama import EmuHipContext, LlamaEngine
+from .llama import EmuHipContext, LlamaEngine, tp_size_of
 from .scoring import reference_candidate_losses, split_segments
 from .vit import VitEngine
 
@@ -297,15 +297,24 @@ class Emu:
                      num_beams: int = 5, max_new_tokens: int = 50, min_length: int = 1, length_penalty: float = 0.0,
                      do_sample: bool = False, temperature=None, top_k=None, top_p=None, repetition_penalty: float = 1.0,
                      penalty_alpha=None, no_repeat_ngram_size=None, num_return_sequences: int = 1,
-                     hf_semantics: Optional[str] = None, constraint=None):
+                     hf_semantics: Optional[str] = None, constraint=None, prompt_lookup_num_tokens: int = 0,
+                     max_matching_ngram_size: int = 2):
         """``constraint``: an ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature
         (Emu1/mm_eval/models/emu.py:96-109).  Which engine method runs, and with which of this model's opt-ins:
-        ``genroute.model_route`` (modeling_emu.py:162-179 forwards every argument to lm.generate)."""
+        ``genroute.model_route`` (modeling_emu.py:162-179 forwards every argument to lm.generate).  ``prompt_lookup_num_tokens`` > 0:
+        prompt-lookup speculative greedy decoding (``LlamaEngine.lookup_generate``; ``genroute.lookup_route`` says what it takes)."""
+        lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size)) \
+            if prompt_lookup_num_tokens else {}
+        if lookup:                                         # refused before any device work
+            genroute.lookup_route(int(prompt_lookup_num_tokens), input_ids.shape[0], tp_size_of(self.lm), num_beams, do_sample, top_k,
+                                  penalty_alpha, repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint)
         x = self._prompt_embeds(input_ids, image)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
         method, routing = genroute.model_route(genroute.model_flags(self), num_beams, do_sample, top_k, penalty_alpha,
-                                               repetition_penalty, ngram, nret, constraint)
+                                               repetition_penalty, ngram, nret, constraint, **lookup)
         ends = dict(eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
+        if method == "lookup_generate":
+            return self.lm.lookup_generate(x, attention_mask, input_ids, max_new_tokens, min_len=min_length, **ends, **routing)
         if method == "contrastive_generate":
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,
                                                 repetition_penalty, **ends, **routing)
@@ -325,6 +334,7 @@ class Emu:
                  repetition_penalty=1.0, length_penalty=0.0, num_captions=1, temperature=1, penalty_alpha=None, top_k=None,
                  no_repeat_ngram_size=None, **kwargs) -> List[str]:
         constraint = pop_constraint(kwargs)
+        lookup = {name: int(kwargs.pop(name)) for name in ("prompt_lookup_num_tokens", "max_matching_ngram_size") if name in kwargs}
         if kwargs:
             raise TypeError(f"Emu.generate: unsupported generation options {sorted(kwargs)}")
         if self.tokenizer is None:
@@ -336,7 +346,8 @@ class Emu:
         ids = self.generate_ids(enc.input_ids, enc.attention_mask, samples.get("image"), num_beams, max_new_tokens,
                                 min_length, length_penalty, do_sample=do_sample, temperature=temperature, top_k=top_k,
                                 top_p=top_p, repetition_penalty=repetition_penalty, penalty_alpha=penalty_alpha,
-                                no_repeat_ngram_size=no_repeat_ngram_size, num_return_sequences=num_captions, constraint=constraint)
+                                no_repeat_ngram_size=no_repeat_ngram_size, num_return_sequences=num_captions, constraint=constraint,
+                                **lookup)
         return tok.batch_decode(ids.cpu(), skip_special_tokens=True)
 
     # ------------------------------------------------------------------ predict (Emu1/models/prediction_mixin.py)

@@ -15,7 +15,7 @@ from typing import Dict, Iterable, Optional, Tuple
 
 import torch
 
-from . import bf16pack, genroute, mxfp4, ops
+from . import bf16pack, genroute, mxfp4, ops, speculate
 from ._lib import Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
@@ -788,6 +788,42 @@ class LlamaEngine:
               "emu_llama_forward", self.ctx.handle)
         return hidden
 
+    CHUNK_MAX = 8                                      # DECODE_CHUNK_MAX of the chunk attention kernel
+
+    def forward_chunk(self, hidden: torch.Tensor, B: int, T: int, pos0: torch.Tensor, slot0: torch.Tensor,
+                      kstart: Optional[torch.Tensor], ctx: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """All decoder layers in place on ``hidden`` [B*T, hidden] for a chunk of T rows per sequence on top of the cache
+        (include/emu_hip.h: emu_llama_forward_chunk): row i of sequence b at cache slot ``slot0[b] + i`` and position
+        ``pos0[b] + i`` (int32 [B] on the device), ``ctx`` >= max slot0 + T sizes the launches.  What the engine cannot run this way
+        is a ``ValueError`` before any device work."""
+        if not 2 <= T <= self.CHUNK_MAX or B < 1 or B * T > 16:
+            raise ValueError(f"forward_chunk: T in 2..{self.CHUNK_MAX} and B * T <= 16, got B = {B}, T = {T}")
+        if tp_size_of(self) > 1:
+            raise ValueError("forward_chunk: no tensor-parallel form")
+        if getattr(self, "_kv_share", False):
+            raise ValueError("forward_chunk: shared-prefix KV rows serve single-token steps only")
+        if getattr(self, "decode_fused", 0):
+            raise ValueError("forward_chunk: the fused decode modes 1-4 are one-row steps (set_decode_fused(0) first)")
+        assert hidden.is_contiguous() and hidden.dtype == BF16 and hidden.shape == (B * T, self.cfg.hidden_size)
+        assert pos0.dtype == torch.int32 and slot0.dtype == torch.int32 and pos0.numel() == B and slot0.numel() == B
+        if ws is None:
+            ws = self._workspace_chunk(B, T)
+        try:
+            check(lib().emu_llama_forward_chunk(self.handle, hidden.data_ptr(), B, T, pos0.data_ptr(), slot0.data_ptr(), ops._p(kstart),
+                                                None, int(ctx), ws.data_ptr(), ws.numel(), ops.stream(self.device)),
+                  "emu_llama_forward_chunk", self.ctx.handle)
+        except EmuHipError as e:
+            if "status -22" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        return hidden
+
+    def _workspace_chunk(self, B: int, T: int) -> torch.Tensor:
+        """A workspace of its own for the chunk step of B x T rows (and the logits of its rows): a captured step holds its address."""
+        need = max(int(lib().emu_llama_chunk_workspace_bytes(self.handle, B, T)), int(lib().emu_llama_workspace_bytes(self.handle, B * T, 1)),
+                   B * T * self.cfg.hidden_size * 2)
+        return torch.empty(need, device=self.device, dtype=torch.uint8)
+
     def set_layer_range(self, l0: int = 0, l1: int = -1) -> None:
         """Parity hook (include/emu_hip.h: emu_llama_set_layer_range): ``forward`` / ``prefill`` run layers [l0, l1) only;
         (0, -1) restores the whole stack.  Tests only."""
@@ -888,6 +924,108 @@ class LlamaEngine:
             return ids
         return apply_eos_padding(ids, eos_id, pad_id)
 
+    LOOKUP_POLL = 4        # lookup decode: steps between two host looks at the step counter and the finished flag
+
+    @torch.no_grad()
+    def lookup_generate(self, embeds: torch.Tensor, attention_mask: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int,
+                        num_tokens: int, max_ngram: int = 2, min_len: int = 1, eos_id: int = 2, pad_id: int = 32000,
+                        use_graph: bool = False, stop_on_eos: bool = True, drafts: Optional[torch.Tensor] = None,
+                        stats: Optional[dict] = None) -> torch.Tensor:
+        """``lm.generate(inputs_embeds=..., prompt_lookup_num_tokens=num_tokens, max_matching_ngram_size=max_ngram)``: greedy
+        decoding that verifies up to ``num_tokens`` guessed ids per step (``emu_amd/speculate.py``), one sequence.  The guess is the
+        continuation of the last n-gram's earlier occurrence in ``prompt_ids`` [1, S] (the ids behind ``embeds``; where
+        ``attention_mask`` is 0 they are not history) followed by the generated ids.  A step is one ``emu_llama_lookup_step``:
+        embed of 1 + k ids, the chunk forward, logits of the 1 + k rows, accept / append / next draft / state advance on the
+        device; replayed from one hipGraph with ``use_graph``.  The host reads the step counter and the finished flag every
+        ``LOOKUP_POLL`` steps.  Every emitted id is the arg-max of the model's own logits, through the few-row weight streams:
+        the ids can differ from ``greedy_generate``'s only where a top-2 margin is inside bf16 rounding.
+
+        ``drafts`` int [max_new_tokens, num_tokens]: row ``step`` (the number of ids emitted so far) is the draft, in place of
+        the lookup -- tests and timing only.  ``stats``: a dict that receives ``steps_run`` and ``tokens_emitted`` (the ids the
+        steps emitted: all but the first).  Rejected drafts leave stale K / V rows behind the accepted ones; the next step
+        overwrites them before any query sees them, so the cache needs ``num_tokens`` slots beyond prompt + max_new_tokens."""
+        B, S, H = embeds.shape
+        k, max_new = int(num_tokens), int(max_new_tokens)
+        genroute.lookup_route(k, B, tp_size_of(self))                          # a ValueError before any device work
+        if max_ngram < 1 or max_new < 1:
+            raise ValueError(f"lookup_generate: max_matching_ngram_size and max_new_tokens must be at least 1, got {max_ngram}, {max_new}")
+        if S + max_new + k > self.cfg.max_position_embeddings:
+            raise ValueError(f"lookup_generate: prompt + max_new_tokens + prompt_lookup_num_tokens = {S + max_new + k} exceeds "
+                             f"max_position_embeddings {self.cfg.max_position_embeddings}")
+        if tuple(prompt_ids.shape) != (B, S):
+            raise ValueError(f"lookup_generate: prompt_ids must be [{B}, {S}], got {tuple(prompt_ids.shape)}")
+        if drafts is not None and tuple(drafts.shape) != (max_new, k):
+            raise ValueError(f"lookup_generate: drafts must be [max_new_tokens, num_tokens] = [{max_new}, {k}], got {tuple(drafts.shape)}")
+        if getattr(self, "decode_fused", 0):
+            raise ValueError("lookup_generate: the fused decode modes 1-4 are one-row steps (set_decode_fused(0) first)")
+        T, dev, V = k + 1, self.device, self.vocab
+        s_max = self.kv_capacity(S + max_new + k)
+        hidden, kstart, next_pos = self.prefill(embeds, attention_mask, s_max)
+        first = int(ops.argmax(self.logits(hidden[:, -1, :]), suppress_id=eos_id if min_len >= 1 else -1)[0])
+        hist0 = [int(t) for t in prompt_ids[0][attention_mask[0].to(prompt_ids.device) != 0]] + [first]
+        finished0 = max_new <= 1 or (stop_on_eos and first == eos_id)
+        if finished0:
+            d0 = []
+        elif drafts is not None:
+            d0 = [int(t) for t in drafts[1]]
+        else:
+            d0 = speculate.lookup_draft(hist0, k, max_ngram)
+        key = (T, self.s_max, max_new, int(max_ngram), int(min_len), int(eos_id), bool(stop_on_eos), drafts is not None,
+               self.kcache.data_ptr(), self.mode_epoch)
+
+        def build():
+            i32 = dict(dtype=torch.int32, device=dev)
+            return dict(cur=torch.zeros(T, **i32), amax=torch.zeros(T, **i32), st=torch.zeros(ops.LOOKUP_STATE_INTS, **i32),
+                        pos0=torch.zeros(1, **i32), slot0=torch.zeros(1, **i32), ctx=torch.zeros(1, **i32),
+                        out_ids=torch.zeros(max_new, **i32), hist=torch.zeros(self.s_max, **i32), kstart=torch.zeros(1, **i32),
+                        drafts=None if drafts is None else torch.zeros(max_new, k, **i32),
+                        hid=torch.empty(T, H, device=dev, dtype=BF16), lg=torch.empty(T, V, device=dev, dtype=BF16),
+                        cws=self._workspace_chunk(1, T))
+
+        st = self._loop_state("lookup", key, T, build)
+        i32c = lambda v: torch.tensor(v, dtype=torch.int32)
+        st["cur"].copy_(i32c([first] + d0 + [0] * (k - len(d0))))
+        st["st"].copy_(i32c([1, int(finished0), len(d0), len(hist0), 0, 0, 0, 0]))
+        st["pos0"].copy_(next_pos); st["slot0"].fill_(S); st["ctx"].fill_(S + 1); st["kstart"].copy_(kstart)
+        st["out_ids"].fill_(pad_id); st["out_ids"][0] = first
+        st["hist"][:len(hist0)] = i32c(hist0).to(dev)
+        if drafts is not None:
+            st["drafts"].copy_(drafts.to(torch.int32))
+        p = lambda name: None if st[name] is None else st[name].data_ptr()
+        Lb = lib()
+
+        def body():
+            check(Lb.emu_llama_lookup_step(self.handle, T, p("cur"), p("amax"), p("st"), p("pos0"), p("slot0"), p("kstart"), p("ctx"),
+                                           p("out_ids"), p("hist"), st["hist"].numel(), p("drafts"), int(max_ngram), max_new, int(min_len),
+                                           int(eos_id), int(bool(stop_on_eos)), self.s_max, p("hid"), p("lg"), st["lg"].stride(0),
+                                           p("cws"), st["cws"].numel(), ops.stream(self.device)), "emu_llama_lookup_step", self.ctx.handle)
+
+        def finished() -> bool:
+            step, fin = st["st"][:2].tolist()                                  # the one host read
+            return bool(fin) or step >= max_new
+
+        launched = [0]
+
+        def one(i):
+            st["captured"].step(body, use_graph, key)
+            launched[0] += 1
+
+        timing = stats is not None and stats.get("timing")          # tools: time the loop alone (two device synchronisations)
+        if timing:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        if not finished0:
+            run_polled(one, max_new - 1, self.LOOKUP_POLL, finished)
+        if stats is not None:
+            vals = st["st"].tolist()
+            stats.update(steps_run=vals[4], tokens_emitted=vals[5])
+            if timing:                                             # steps_launched includes the no-op replays behind the end
+                stats.update(loop_seconds=time.perf_counter() - t0, steps_launched=launched[0])
+        ids = st["out_ids"][None].to(torch.int64)                               # [1, max_new]
+        self.ctx.check_p2p()
+        if not stop_on_eos:
+            return ids
+        return apply_eos_padding(ids, eos_id, pad_id)
 
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()

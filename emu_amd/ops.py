@@ -582,6 +582,54 @@ def decode_fused(qkv, cos, sin, pos, slot, kcache, vcache, H: int, ctx_max: int,
     return o
 
 
+def decode_chunk(qkv, cos, sin, pos0, slot0, kcache, vcache, H: int, T: int, ctx_max: int, scale: float, kstart=None, ws=None):
+    """The chunk step's attention launch (emu_decode_chunk_bf16): qkv [B*T, 3*H*D] (not rotated), T rows per sequence at the
+    consecutive cache slots slot0[b] + i and positions pos0[b] + i (``pos0`` / ``slot0`` int32 [B]); the T rotated keys and values
+    are appended -> o [B*T, H, D].  ``ws``: the fp32 workspace (emu_decode_chunk_ws_bytes), allocated here unless brought."""
+    _req(qkv, "qkv"); _req(cos, "cos"); _req(sin, "sin"); _req(kcache, "kcache"); _req(vcache, "vcache")
+    _req(pos0, "pos0", torch.int32); _req(slot0, "slot0", torch.int32)
+    assert qkv.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous() and kcache.shape == vcache.shape
+    B, _, S_max, D = kcache.shape
+    assert qkv.shape == (B * T, 3 * H * D) and kcache.shape[1] == H, (qkv.shape, kcache.shape)
+    assert pos0.numel() == B and slot0.numel() == B
+    need = lib().emu_decode_chunk_ws_bytes(B, T, H, D, ctx_max) // 4
+    if ws is None:
+        ws = torch.empty(max(need, 1), device=qkv.device, dtype=torch.float32)
+    _req(ws, "ws", torch.float32)
+    assert ws.is_contiguous() and ws.numel() >= need, (ws.numel(), need)
+    if kstart is not None:
+        _req(kstart, "kstart", torch.int32)
+    o = torch.empty(B * T, H, D, device=qkv.device, dtype=BF16)
+    check(lib().emu_decode_chunk_bf16(_p(qkv), _p(cos), _p(sin), _p(pos0), _p(slot0), _p(kcache), _p(vcache), _p(o), o.stride(0),
+                                      o.stride(1), _p(kstart), _p(ws), B, T, H, D, S_max, ctx_max, float(scale), stream(qkv)),
+          "emu_decode_chunk_bf16")
+    return o
+
+
+LOOKUP_STATE_INTS = 8          # st of emu_lookup_select_bf16: step, finished, n_draft, hist_len, steps_run, tokens_emitted, -, -
+
+
+def lookup_select(logits, cur, st, pos0, slot0, ctx, out_ids, hist, max_ngram: int, max_new: int, min_len: int, eos_id: int,
+                  stop_on_eos: bool = True, drafts=None, amax=None):
+    """The selection behind a chunk step (emu_lookup_select_bf16; ``emu_amd/speculate.py``): logits [T, V] bf16; every other
+    tensor int32 on the device and updated in place.  Returns the rows' arg-maxes [T]."""
+    _req(logits, "logits")
+    T, V = logits.shape
+    for name, t in (("cur", cur), ("st", st), ("pos0", pos0), ("slot0", slot0), ("ctx", ctx), ("out_ids", out_ids), ("hist", hist)):
+        _req(t, name, torch.int32)
+        assert t.is_contiguous(), name
+    assert cur.numel() == T and st.numel() >= LOOKUP_STATE_INTS and out_ids.numel() >= max_new and logits.stride(1) == 1
+    if drafts is not None:
+        _req(drafts, "drafts", torch.int32)
+        assert drafts.is_contiguous() and tuple(drafts.shape) == (max_new, T - 1), (drafts.shape, max_new, T)
+    if amax is None:
+        amax = torch.empty(T, device=logits.device, dtype=torch.int32)
+    check(lib().emu_lookup_select_bf16(_p(logits), logits.stride(0), V, T, _p(amax), _p(cur), _p(st), _p(pos0), _p(slot0), _p(ctx),
+                                       _p(out_ids), _p(hist), hist.numel(), _p(drafts), int(max_ngram), int(max_new), int(min_len),
+                                       int(eos_id), int(bool(stop_on_eos)), stream(logits)), "emu_lookup_select_bf16")
+    return amax
+
+
 CONV_3X3, CONV_3X3_S2, CONV_3X3_UP2 = 1, 2, 3
 
 

@@ -514,6 +514,27 @@ int emu_decode_fused_bf16(const void* qkv, const void* cos, const void* sin, con
                           void* kcache, void* vcache, void* o, long o_sb, long o_sh, const int32_t* kstart, void* ws, int B,
                           int H, int D, int S_max, int ctx_max, float scale, int share_nb, int share_len, int32_t* arrive,
                           emu_stream_t s);
+/* The same for a CHUNK of T rows per sequence (2 <= T <= 8; the verify step of prompt-lookup speculative decoding): qkv [B*T, 3*H*D];
+ * row i of sequence b has cache slot slot0[b] + i and RoPE position pos0[b] + i (slot0, pos0: device int32 [B], so a captured launch
+ * replays while the context grows) and attends over kstart[b] <= key <= slot0[b] + i.  One launch rotates the T queries and new keys,
+ * appends the T K / V rows and forms every row's split states (a split's cache rows are loaded once for all T rows; the chunk's own
+ * slots are taken from the freshly rotated rows, never read back); the one-row merge launch follows.  o[(b*T + i)*o_sb + h*o_sh + d].
+ * Row i's output bits and the cache rows equal those of T successive emu_decode_fused_bf16 launches with slot = slot0 + i.  The caller
+ * guarantees slot0[b] + T <= ctx_max <= S_max.  -22: refused (T outside 2..8, D not 64 / 128, ctx_max outside [1, S_max]), nothing
+ * was launched. */
+size_t emu_decode_chunk_ws_bytes(int B, int T, int H, int D, int ctx_max);
+int emu_decode_chunk_bf16(const void* qkv, const void* cos, const void* sin, const int32_t* pos0, const int32_t* slot0, void* kcache,
+                          void* vcache, void* o, long o_sb, long o_sh, const int32_t* kstart, void* ws, int B, int T, int H, int D,
+                          int S_max, int ctx_max, float scale, emu_stream_t s);
+/* The selection behind a chunk step of T = 1 + k rows, one sequence (csrc/lookup.hip; specified in emu_amd/speculate.py): the rows'
+ * arg-maxes (EOS suppressed in row i while step + i < min_len), then ONE workgroup accepts the draft's leading matches, appends the
+ * emitted ids to out_ids [max_new] and to hist (the prompt's real ids, then the generated ones; hist_cap ints), finds the next draft
+ * (or takes row `step` of drafts [max_new, k] when that is not NULL: tests and timing) and advances cur [T] (last emitted id, then the
+ * draft, 0 beyond it), pos0 / slot0 / ctx_dev [1] and st.  st: int32 [8] = {step, finished, n_draft, hist_len, steps_run,
+ * tokens_emitted, -, -}.  amax: int32 [T] scratch.  A call at step >= max_new or after finished changes nothing. */
+int emu_lookup_select_bf16(const void* logits, int ld, int V, int T, int32_t* amax, int32_t* cur, int32_t* st, int32_t* pos0,
+                           int32_t* slot0, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                           int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, emu_stream_t s);
 
 /* ---- LLaMA decoder engine ------------------------------------------------------------------------------
  * transformers LlamaModel / LlamaForCausalLM as used by EmuModel.generate / generate_image
@@ -771,6 +792,22 @@ int emu_llama_score_step(emu_llama* m, int B, int32_t* cur_ids, int32_t* pos, in
                          int32_t* ctx_dev, int32_t* step_dev, const int32_t* targets, int T, int ctx_upper, void* hidden,
                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, float* lp, float* lse, int32_t* top1,
                          emu_stream_t s);
+/* The layer body for a chunk of T rows per sequence on top of the cache (2 <= T <= 8, B * T <= 16): hidden [B*T, hidden] in place;
+ * pos0 / slot0 device int32 [B] (row i: + i); the projections take whatever kernel the engine plans for B * T rows (bf16, fp8-wide,
+ * MXFP4-wide), the attention is emu_decode_chunk_bf16's launch.  ctx_upper sizes the launches (>= max slot0 + T); ctx_dev is not read.
+ * workspace: emu_llama_chunk_workspace_bytes.  Refused with -22 and a message: shared-prefix KV rows, the fused decode modes 1-4,
+ * B * T > 16, tensor parallelism.  emu_llama_forward is not involved. */
+size_t emu_llama_chunk_workspace_bytes(const emu_llama* m, int B, int T);
+int emu_llama_forward_chunk(emu_llama* m, void* hidden, int B, int T, const int32_t* pos0, const int32_t* slot0, const int32_t* kstart,
+                            const int32_t* ctx_dev, int ctx_upper, void* workspace, size_t ws_bytes, emu_stream_t s);
+/* One step of prompt-lookup speculative greedy decoding (lm.generate(prompt_lookup_num_tokens=k), reached through the **kwargs of
+ * Emu2/emu/emu.py:175,228), one sequence: embed(cur [T = 1 + k]) -> emu_llama_forward_chunk -> final norm + logits on the T rows
+ * (logits [T, ld_logits], hidden [T, hidden]) -> emu_lookup_select_bf16.  Every emitted id is the arg-max of the model's own logits.
+ * Graph-capturable: every index is read from the device, one captured step replays for every iteration. */
+int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                          const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                          int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s);
 /* One step of transformers' beam search (lm.generate(num_beams=N), Emu2/emu/emu.py:163-172,213-229: the library's BeamSearchScorer
  * logic in its vectorised form), deterministic mode, in two launches: log-softmax of the N beams' logit rows of every prompt, the 2N
  * best continuations over beams x vocabulary of (log p + running score) with EOS masked while cur < min_len, then the bookkeeping --
