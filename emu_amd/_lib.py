@@ -222,10 +222,14 @@ _PROTOS = {
     "emu_decode_chunk_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
     "emu_decode_chunk_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, lng, lng, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp]),
     "emu_lookup_select_bf16": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "emu_lookup_sample_bf16": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32,
+                                     C.POINTER(SampleParamsC), vp, i32, vp]),
     "emu_llama_chunk_workspace_bytes": (sz, [vp, i32, i32]),
     "emu_llama_forward_chunk": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, sz, vp]),
     "emu_llama_lookup_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32,
                                     vp, sz, vp]),
+    "emu_llama_lookup_sample_step": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32,
+                                           vp, sz, C.POINTER(SampleParamsC), vp, i32, vp]),
     "emu_vit_create": (i32, [vp, C.POINTER(VitCfgC), C.POINTER(vp)]),
     "emu_vit_destroy": (None, [vp]),
     "emu_vit_set_stem": (i32, [vp, vp, vp, vp, vp]),

@@ -1893,12 +1893,26 @@ int emu_lookup_select_bf16(const void* logits, int ld, int V, int T, int32_t* am
     return launch_lookup_select(a, S(s));
 }
 
+int emu_lookup_sample_bf16(const void* logits, int ld, int V, int T, int32_t* amax, int32_t* cur, int32_t* st, int32_t* pos0,
+                           int32_t* slot0, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                           int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, const emu_sample_params* params,
+                           const float* uniforms, int uni_rows, emu_stream_t s) {
+    const LookupArgs a{B(logits), ld, V, T, amax, cur, st, pos0, slot0, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram, max_new,
+                       min_len, eos_id, stop_on_eos};
+    if (!pos0 || !slot0 || !ctx_dev || !hist || max_ngram < 1 || hist_cap < 1) return -22;       // the select launch's, before the first
+    int e = launch_lookup_sample(a, params, uniforms, uni_rows, S(s));
+    if (e) return e;
+    return launch_lookup_select(a, S(s));
+}
+
 // One step of the prompt-lookup loop: embed the T = 1 + k ids of `cur` (the last emitted id, then the draft) -> chunk forward -> final
-// norm + logits on the T rows -> arg-maxes -> accept / append / next draft / state advance (lookup.hip).  Capturable.
-int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
-                          const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
-                          int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper, void* hidden,
-                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
+// norm + logits on the T rows -> the rows' ids (params null: arg-maxes; else the sampler's selection, row i as output index step + i)
+// -> accept / append / next draft / state advance (lookup.hip).  Capturable.
+static int llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                             const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap,
+                             const int32_t* drafts, int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper,
+                             void* hidden, void* logits, int ld_logits, void* workspace, size_t ws_bytes,
+                             const emu_sample_params* params, const float* uniforms, int uni_rows, emu_stream_t s) {
     if (!m || !m->embed || !cur || !hidden || !logits) return -22;
     const emu_llama_cfg& c = m->cfg;
     const LookupArgs a{B(logits), ld_logits, c.vocab, T, amax, cur, st, pos0, slot0, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram,
@@ -1906,12 +1920,34 @@ int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int3
     if (T < 2 || T > DECODE_CHUNK_MAX || !amax || !st || !pos0 || !slot0 || !ctx_dev || !out_ids || !hist || max_new < 1 || max_ngram < 1 ||
         hist_cap < 1)
         return -22;                                  // refused before anything is launched
+    if (params && (ld_logits < c.vocab || !lookup_sample_ok(c.vocab, params, uniforms, uni_rows))) return -22;       // likewise
     TRY(m->ctx, launch_embed_gather(cur, m->embed, B(hidden), T, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward_chunk(m, hidden, 1, T, pos0, slot0, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, T, logits, ld_logits, workspace, ws_bytes, s));
-    TRY(m->ctx, launch_lookup_argmax(a, S(s)));
+    if (params) TRY(m->ctx, launch_lookup_sample(a, params, uniforms, uni_rows, S(s)));
+    else TRY(m->ctx, launch_lookup_argmax(a, S(s)));
     TRY(m->ctx, launch_lookup_select(a, S(s)));
     return 0;
+}
+
+int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                          const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                          int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper, void* hidden,
+                          void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s) {
+    return llama_lookup_step(m, T, cur, amax, st, pos0, slot0, kstart, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram, max_new,
+                             min_len, eos_id, stop_on_eos, ctx_upper, hidden, logits, ld_logits, workspace, ws_bytes, nullptr, nullptr, 0,
+                             s);
+}
+
+int emu_llama_lookup_sample_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                                 const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap,
+                                 const int32_t* drafts, int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos,
+                                 int ctx_upper, void* hidden, void* logits, int ld_logits, void* workspace, size_t ws_bytes,
+                                 const emu_sample_params* params, const float* uniforms, int uni_rows, emu_stream_t s) {
+    if (!params) return -22;
+    return llama_lookup_step(m, T, cur, amax, st, pos0, slot0, kstart, ctx_dev, out_ids, hist, hist_cap, drafts, max_ngram, max_new,
+                             min_len, eos_id, stop_on_eos, ctx_upper, hidden, logits, ld_logits, workspace, ws_bytes, params, uniforms,
+                             uni_rows, s);
 }
 
 }  // extern "C"

@@ -441,6 +441,11 @@ struct LookupArgs {
 };
 int launch_lookup_argmax(const LookupArgs& a, hipStream_t s);
 int launch_lookup_select(const LookupArgs& a, hipStream_t s);
+// sample.hip: the place of launch_lookup_argmax when the loop samples or penalises (emu_lookup_sample_bf16): one sampler workgroup
+// per chunk row, amax[i] = the id row i picks as output index step + i with uniforms[min(step + i, uni_rows - 1)]; reads cur, st and
+// out_ids.  lookup_sample_ok: what it takes (the vocabulary bound, the options, uniforms when sampling).
+bool lookup_sample_ok(int vocab, const emu_sample_params* p, const float* uniforms, int uni_rows);
+int launch_lookup_sample(const LookupArgs& a, const emu_sample_params* p, const float* uniforms, int uni_rows, hipStream_t s);
 
 struct EmuP2p;
 // ---- whole decoder layers of a single-row decode step in ONE launch (decode_layer.hip): qkv projection (+RMSNorm) -> RoPE / KV

@@ -265,13 +265,15 @@ class EmuModel:
         ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature.
         ``prompt_lookup_num_tokens`` = k > 0 (with ``max_matching_ngram_size``; the library's options of these names, off by default):
         prompt-lookup speculative greedy decoding, ``LlamaEngine.lookup_generate`` -- one prompt, plain greedy search, 1 <= k <= 7, no
-        tensor parallelism; anything else is ``genroute.lookup_route``'s ValueError, before any device work."""
+        tensor parallelism; anything else is ``genroute.lookup_route``'s ValueError, before any device work.  On a model made with
+        ``device_sampler=True`` it also takes one beam that samples or carries a repetition penalty (``speculate.row_select``)."""
         B, S = input_ids.shape
         lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size)) \
             if prompt_lookup_num_tokens else {}
         if lookup:
             genroute.lookup_route(int(prompt_lookup_num_tokens), B, tp_size_of(self.decoder.lm), num_beams, do_sample, top_k, penalty_alpha,
-                                  repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint)
+                                  repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint,
+                                  device_sampler=genroute.model_flags(self)["device_sampler"])
         sem = hf_semantics or getattr(self, "hf_semantics", "4.31")
         eos = EOS_TOKEN_ID if eos_token_id is None else int(eos_token_id)
         if min_new_tokens is not None:
@@ -292,6 +294,8 @@ class EmuModel:
                                                repetition_penalty, ngram, nret, constraint, **lookup)
         lm, x = self.decoder.lm, x.view(B, S, -1)
         if method == "lookup_generate":
+            if "do_sample" in routing:                         # one beam that samples or penalises (device_sampler): the warpers' values
+                routing.update(temperature=temperature, top_k=top_k, top_p=top_p)
             return lm.lookup_generate(x, attention_mask, input_ids, max_new_tokens, min_len=min_len, eos_id=eos, pad_id=PAD_TOKEN_ID,
                                       stop_on_eos=stop_on_eos, **routing)
         if method == "contrastive_generate":

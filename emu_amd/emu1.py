@@ -302,18 +302,22 @@ class Emu:
         """``constraint``: an ``emu_amd.constrain.TokenTrie`` or a callable with the library's ``prefix_allowed_tokens_fn`` signature
         (Emu1/mm_eval/models/emu.py:96-109).  Which engine method runs, and with which of this model's opt-ins:
         ``genroute.model_route`` (modeling_emu.py:162-179 forwards every argument to lm.generate).  ``prompt_lookup_num_tokens`` > 0:
-        prompt-lookup speculative greedy decoding (``LlamaEngine.lookup_generate``; ``genroute.lookup_route`` says what it takes)."""
+        prompt-lookup speculative decoding (``LlamaEngine.lookup_generate``; ``genroute.lookup_route`` says what it takes: plain greedy
+        search, and with this model's ``device_sampler`` on also one beam that samples or carries a repetition penalty)."""
         lookup = dict(prompt_lookup_num_tokens=int(prompt_lookup_num_tokens), max_matching_ngram_size=int(max_matching_ngram_size)) \
             if prompt_lookup_num_tokens else {}
         if lookup:                                         # refused before any device work
             genroute.lookup_route(int(prompt_lookup_num_tokens), input_ids.shape[0], tp_size_of(self.lm), num_beams, do_sample, top_k,
-                                  penalty_alpha, repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint)
+                                  penalty_alpha, repetition_penalty, int(no_repeat_ngram_size or 0), int(num_return_sequences), constraint,
+                                  device_sampler=genroute.model_flags(self)["device_sampler"])
         x = self._prompt_embeds(input_ids, image)
         ngram, nret = int(no_repeat_ngram_size or 0), int(num_return_sequences)
         method, routing = genroute.model_route(genroute.model_flags(self), num_beams, do_sample, top_k, penalty_alpha,
                                                repetition_penalty, ngram, nret, constraint, **lookup)
         ends = dict(eos_id=EOS_TOKEN_ID, pad_id=PAD_TOKEN_ID)
         if method == "lookup_generate":
+            if "do_sample" in routing:                     # one beam that samples or penalises (device_sampler): the warpers' values
+                routing.update(temperature=temperature, top_k=top_k, top_p=top_p)
             return self.lm.lookup_generate(x, attention_mask, input_ids, max_new_tokens, min_len=min_length, **ends, **routing)
         if method == "contrastive_generate":
             return self.lm.contrastive_generate(x, attention_mask, max_new_tokens, float(penalty_alpha), int(top_k), min_length,

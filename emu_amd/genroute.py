@@ -29,12 +29,16 @@ def model_route(flags: dict, num_beams: int, do_sample: bool, top_k, penalty_alp
     off adds no keyword: the call is then the one made before the option existed.  An n-gram ban takes the device samplers out
     unless ``device_ngram_ban`` is on, which alone switches no sampler on.  A ``constraint`` is handed on as it is.
     ``prompt_lookup_num_tokens`` > 0 (the library's option of that name; 0 = every call is what it was): ``lookup_generate``, for a
-    call that is otherwise plain greedy -- anything else is ``lookup_route``'s ValueError."""
+    call that is otherwise plain greedy and, with ``device_sampler`` on, for one beam that samples or penalises (then with the
+    keywords ``do_sample`` and ``repetition_penalty``; the caller adds the warpers' values) -- anything else is ``lookup_route``'s
+    ValueError."""
     if prompt_lookup_num_tokens:
         lookup_route(prompt_lookup_num_tokens, 1, 1, num_beams, do_sample, top_k, penalty_alpha, repetition_penalty, ngram,
-                     num_return_sequences, constraint)
+                     num_return_sequences, constraint, device_sampler=flags["device_sampler"])
+        selection = dict(do_sample=bool(do_sample), repetition_penalty=float(repetition_penalty)) \
+            if do_sample or repetition_penalty != 1.0 else {}
         return "lookup_generate", dict(num_tokens=int(prompt_lookup_num_tokens), max_ngram=int(max_matching_ngram_size),
-                                       use_graph=flags["use_graph"])
+                                       use_graph=flags["use_graph"], **selection)
     if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample:
         if ngram or num_return_sequences != 1:
             raise NotImplementedError("contrastive search with no_repeat_ngram_size / several returned sequences is not built")
@@ -198,24 +202,29 @@ LOOKUP_MAX_TOKENS = 7          # a chunk step has 1 + k <= 8 rows (the chunk att
 
 
 def lookup_route(k: int, prompts: int, tp_size: int, num_beams: int = 1, do_sample: bool = False, top_k=None, penalty_alpha=None,
-                 repetition_penalty: float = 1.0, ngram: int = 0, num_return_sequences: int = 1, constraint=None) -> Route:
+                 repetition_penalty: float = 1.0, ngram: int = 0, num_return_sequences: int = 1, constraint=None,
+                 device_sampler: bool = False) -> Route:
     """``prompt_lookup_num_tokens = k``.  k == 0: off, nothing is decided here.  Else the device loop of ``lookup_generate`` runs when
     the call is otherwise plain greedy, one prompt (the library refuses assisted decoding for a batch, and so does this), 1 <= k <=
     ``LOOKUP_MAX_TOKENS`` and no tensor parallelism; together with contrastive search, beams, sampling, a repetition penalty, an
-    n-gram ban, several returned sequences or a constraint it is a ValueError that names the mode, before any device work."""
+    n-gram ban, several returned sequences or a constraint it is a ValueError that names the mode, before any device work.
+    ``device_sampler`` on: one beam that samples or carries a repetition penalty runs on the device too (the chunk rows are picked
+    by the sampler's kernel, ``speculate.row_select``); every other refusal stands."""
     k = int(k)
     if k == 0:
         return Route(False)
     contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and num_beams == 1 and not do_sample
     mode = ("contrastive search (penalty_alpha with top_k)" if contrastive else
             f"beam search (num_beams = {num_beams})" if num_beams > 1 else
-            "sampling (do_sample)" if do_sample else
-            f"a repetition penalty ({repetition_penalty})" if repetition_penalty != 1.0 else
+            "sampling (do_sample)" if do_sample and not device_sampler else
+            f"a repetition penalty ({repetition_penalty})" if repetition_penalty != 1.0 and not device_sampler else
             f"an n-gram ban (no_repeat_ngram_size = {ngram})" if ngram else
             f"num_return_sequences = {num_return_sequences}" if num_return_sequences != 1 else
             "a constraint" if constraint is not None else None)
     if mode is not None:
-        raise ValueError(f"prompt_lookup_num_tokens: speculative decoding is built for plain greedy search only, not together with {mode}")
+        unless = " unless device_sampler is on" if mode.startswith(("sampling", "a repetition penalty")) else ""
+        raise ValueError(f"prompt_lookup_num_tokens: speculative decoding is built for plain greedy search only, not together with "
+                         f"{mode}{unless}")
     if not 1 <= k <= LOOKUP_MAX_TOKENS:
         raise ValueError(f"prompt_lookup_num_tokens must be in 1..{LOOKUP_MAX_TOKENS} (a step verifies at most {LOOKUP_MAX_TOKENS + 1} "
                          f"rows), got {k}")

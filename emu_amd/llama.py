@@ -16,7 +16,7 @@ from typing import Dict, Iterable, Optional, Tuple
 import torch
 
 from . import bf16pack, genroute, mxfp4, ops, speculate
-from ._lib import Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
+from ._lib import SAMPLE_MAX_VOCAB, Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
@@ -930,7 +930,9 @@ class LlamaEngine:
     def lookup_generate(self, embeds: torch.Tensor, attention_mask: torch.Tensor, prompt_ids: torch.Tensor, max_new_tokens: int,
                         num_tokens: int, max_ngram: int = 2, min_len: int = 1, eos_id: int = 2, pad_id: int = 32000,
                         use_graph: bool = False, stop_on_eos: bool = True, drafts: Optional[torch.Tensor] = None,
-                        stats: Optional[dict] = None) -> torch.Tensor:
+                        stats: Optional[dict] = None, do_sample: bool = False, temperature: Optional[float] = None,
+                        top_k: Optional[int] = None, top_p: Optional[float] = None, repetition_penalty: float = 1.0,
+                        uniforms: Optional[torch.Tensor] = None, trace: Optional[list] = None) -> torch.Tensor:
         """``lm.generate(inputs_embeds=..., prompt_lookup_num_tokens=num_tokens, max_matching_ngram_size=max_ngram)``: greedy
         decoding that verifies up to ``num_tokens`` guessed ids per step (``emu_amd/speculate.py``), one sequence.  The guess is the
         continuation of the last n-gram's earlier occurrence in ``prompt_ids`` [1, S] (the ids behind ``embeds``; where
@@ -943,10 +945,30 @@ class LlamaEngine:
         ``drafts`` int [max_new_tokens, num_tokens]: row ``step`` (the number of ids emitted so far) is the draft, in place of
         the lookup -- tests and timing only.  ``stats``: a dict that receives ``steps_run`` and ``tokens_emitted`` (the ids the
         steps emitted: all but the first).  Rejected drafts leave stale K / V rows behind the accepted ones; the next step
-        overwrites them before any query sees them, so the cache needs ``num_tokens`` slots beyond prompt + max_new_tokens."""
+        overwrites them before any query sees them, so the cache needs ``num_tokens`` slots beyond prompt + max_new_tokens.
+
+        ``do_sample`` or ``repetition_penalty`` != 1 (the library's assisted decoding with a candidate generator that has no logits):
+        every row picks its id with the device sampler's kernel, row i exactly as ``sample_generate(device_sampler=True)`` picks output
+        index step + i -- the history extended by the draft ids before the row, the uniform ``uniforms[step + i]``
+        (``speculate.row_select``; one ``emu_llama_lookup_sample_step`` per step, a loop state and a captured graph of its own) -- and
+        the draft is kept for as long as each picked id equals the next draft id.  The first id is ``emu_sample_bf16``'s at step 0.
+        ``uniforms`` fp32 [max_new_tokens] or [max_new_tokens, 1], by default ONE ``torch.rand`` from the global generator up front.
+        With the same uniforms the ids are those of the one-row device loop wherever both see the same logits: the few-row streams
+        round differently from the one-row ones, so a draw within that rounding of an interval's boundary (or an arg-max within it of
+        the runner-up) may fall the other way.  ``trace``: a list that receives one host record per step (``step``, ``n_draft``,
+        ``cur`` = the fed ids, ``logits`` = a CPU copy of the step's [T, V] rows, ``n_emit``); eager runs only."""
         B, S, H = embeds.shape
         k, max_new = int(num_tokens), int(max_new_tokens)
-        genroute.lookup_route(k, B, tp_size_of(self))                          # a ValueError before any device work
+        select = bool(do_sample) or float(repetition_penalty) != 1.0
+        genroute.lookup_route(k, B, tp_size_of(self), do_sample=bool(do_sample), repetition_penalty=float(repetition_penalty),
+                              device_sampler=True)                             # a ValueError before any device work
+        if select and self.vocab > SAMPLE_MAX_VOCAB:
+            raise ValueError(f"lookup_generate: vocabulary {self.vocab} is above the sample kernel's bound {SAMPLE_MAX_VOCAB}")
+        if uniforms is not None and tuple(uniforms.shape) not in ((max_new,), (max_new, 1)):
+            raise ValueError(f"lookup_generate: uniforms must be [max_new_tokens] or [max_new_tokens, 1] = [{max_new}], "
+                             f"got {tuple(uniforms.shape)}")
+        if trace is not None and use_graph:
+            raise ValueError("lookup_generate: trace reads every step's logits on the host; not together with use_graph")
         if max_ngram < 1 or max_new < 1:
             raise ValueError(f"lookup_generate: max_matching_ngram_size and max_new_tokens must be at least 1, got {max_ngram}, {max_new}")
         if S + max_new + k > self.cfg.max_position_embeddings:
@@ -961,7 +983,15 @@ class LlamaEngine:
         T, dev, V = k + 1, self.device, self.vocab
         s_max = self.kv_capacity(S + max_new + k)
         hidden, kstart, next_pos = self.prefill(embeds, attention_mask, s_max)
-        first = int(ops.argmax(self.logits(hidden[:, -1, :]), suppress_id=eos_id if min_len >= 1 else -1)[0])
+        if select:
+            params = sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, eos_id, min_len, eos_id, pad_id)
+            uni = None if not do_sample else torch.rand(max_new, dtype=torch.float32, device=dev) if uniforms is None else \
+                uniforms.to(device=dev, dtype=torch.float32).reshape(max_new).contiguous()
+            i32z = torch.zeros(1, dtype=torch.int32, device=dev)
+            first = int(ops.sample(self.logits(hidden[:, -1, :]), i32z, params, hist=torch.zeros(max_new, 1, dtype=torch.int32, device=dev),
+                                   uniforms=None if uni is None else uni.view(max_new, 1))[0])
+        else:
+            first = int(ops.argmax(self.logits(hidden[:, -1, :]), suppress_id=eos_id if min_len >= 1 else -1)[0])
         hist0 = [int(t) for t in prompt_ids[0][attention_mask[0].to(prompt_ids.device) != 0]] + [first]
         finished0 = max_new <= 1 or (stop_on_eos and first == eos_id)
         if finished0:
@@ -972,6 +1002,8 @@ class LlamaEngine:
             d0 = speculate.lookup_draft(hist0, k, max_ngram)
         key = (T, self.s_max, max_new, int(max_ngram), int(min_len), int(eos_id), bool(stop_on_eos), drafts is not None,
                self.kcache.data_ptr(), self.mode_epoch)
+        if select:                                                 # the launch holds the options: they are part of the graph's key
+            key += tuple(getattr(params, name) for name, _ in params._fields_)
 
         def build():
             i32 = dict(dtype=torch.int32, device=dev)
@@ -980,9 +1012,9 @@ class LlamaEngine:
                         out_ids=torch.zeros(max_new, **i32), hist=torch.zeros(self.s_max, **i32), kstart=torch.zeros(1, **i32),
                         drafts=None if drafts is None else torch.zeros(max_new, k, **i32),
                         hid=torch.empty(T, H, device=dev, dtype=BF16), lg=torch.empty(T, V, device=dev, dtype=BF16),
-                        cws=self._workspace_chunk(1, T))
+                        cws=self._workspace_chunk(1, T), uni=torch.zeros(max_new, dtype=torch.float32, device=dev) if select else None)
 
-        st = self._loop_state("lookup", key, T, build)
+        st = self._loop_state("lookup_sample" if select else "lookup", key, T, build)
         i32c = lambda v: torch.tensor(v, dtype=torch.int32)
         st["cur"].copy_(i32c([first] + d0 + [0] * (k - len(d0))))
         st["st"].copy_(i32c([1, int(finished0), len(d0), len(hist0), 0, 0, 0, 0]))
@@ -991,14 +1023,20 @@ class LlamaEngine:
         st["hist"][:len(hist0)] = i32c(hist0).to(dev)
         if drafts is not None:
             st["drafts"].copy_(drafts.to(torch.int32))
+        if select and uni is not None:
+            st["uni"].copy_(uni)
         p = lambda name: None if st[name] is None else st[name].data_ptr()
         Lb = lib()
 
         def body():
-            check(Lb.emu_llama_lookup_step(self.handle, T, p("cur"), p("amax"), p("st"), p("pos0"), p("slot0"), p("kstart"), p("ctx"),
-                                           p("out_ids"), p("hist"), st["hist"].numel(), p("drafts"), int(max_ngram), max_new, int(min_len),
-                                           int(eos_id), int(bool(stop_on_eos)), self.s_max, p("hid"), p("lg"), st["lg"].stride(0),
-                                           p("cws"), st["cws"].numel(), ops.stream(self.device)), "emu_llama_lookup_step", self.ctx.handle)
+            args = (self.handle, T, p("cur"), p("amax"), p("st"), p("pos0"), p("slot0"), p("kstart"), p("ctx"), p("out_ids"), p("hist"),
+                    st["hist"].numel(), p("drafts"), int(max_ngram), max_new, int(min_len), int(eos_id), int(bool(stop_on_eos)), self.s_max,
+                    p("hid"), p("lg"), st["lg"].stride(0), p("cws"), st["cws"].numel())
+            if select:
+                check(Lb.emu_llama_lookup_sample_step(*args, C.byref(params), p("uni") if do_sample else None, max_new,
+                                                      ops.stream(self.device)), "emu_llama_lookup_sample_step", self.ctx.handle)
+            else:
+                check(Lb.emu_llama_lookup_step(*args, ops.stream(self.device)), "emu_llama_lookup_step", self.ctx.handle)
 
         def finished() -> bool:
             step, fin = st["st"][:2].tolist()                                  # the one host read
@@ -1007,8 +1045,14 @@ class LlamaEngine:
         launched = [0]
 
         def one(i):
+            if trace is not None:
+                before = st["st"].tolist()
+                fed = st["cur"].tolist()
             st["captured"].step(body, use_graph, key)
             launched[0] += 1
+            if trace is not None and not before[1] and before[0] < max_new:
+                trace.append(dict(step=before[0], n_draft=before[2], cur=fed, logits=st["lg"].cpu(),
+                                  n_emit=int(st["st"][0]) - before[0]))
 
         timing = stats is not None and stats.get("timing")          # tools: time the loop alone (two device synchronisations)
         if timing:

@@ -630,7 +630,34 @@ def lookup_select(logits, cur, st, pos0, slot0, ctx, out_ids, hist, max_ngram: i
     return amax
 
 
-CONV_3X3, CONV_3X3_S2, CONV_3X3_UP2 = 1, 2, 3
+def lookup_sample(logits, cur, st, pos0, slot0, ctx, out_ids, hist, max_ngram: int, max_new: int, min_len: int, eos_id: int, params,
+                  uniforms=None, stop_on_eos: bool = True, drafts=None, amax=None):
+    """``lookup_select`` with the sampler's selection in the place of the arg-maxes (emu_lookup_sample_bf16;
+    ``emu_amd/speculate.py``: ``row_select``): row i <= n_draft picks its id as ``sample`` picks output index step + i, with the
+    history ``out_ids[:step]`` + ``cur[1:1 + i]`` and ``uniforms[min(step + i, rows - 1)]`` (fp32 [rows] or [rows, 1]; None without
+    ``do_sample``).  ``params``: ``_lib.SampleParamsC``.  Returns the picked ids [T]; the entries behind the draft are not written."""
+    _req(logits, "logits")
+    T, V = logits.shape
+    for name, t in (("cur", cur), ("st", st), ("pos0", pos0), ("slot0", slot0), ("ctx", ctx), ("out_ids", out_ids), ("hist", hist)):
+        _req(t, name, torch.int32)
+        assert t.is_contiguous(), name
+    assert cur.numel() == T and st.numel() >= LOOKUP_STATE_INTS and out_ids.numel() >= max_new and logits.stride(1) == 1
+    if drafts is not None:
+        _req(drafts, "drafts", torch.int32)
+        assert drafts.is_contiguous() and tuple(drafts.shape) == (max_new, T - 1), (drafts.shape, max_new, T)
+    if uniforms is not None:
+        _req(uniforms, "uniforms", torch.float32)
+        assert uniforms.is_contiguous() and uniforms.numel() >= 1 and uniforms.numel() == uniforms.shape[0]
+    if amax is None:
+        amax = torch.zeros(T, device=logits.device, dtype=torch.int32)
+    check(lib().emu_lookup_sample_bf16(_p(logits), logits.stride(0), V, T, _p(amax), _p(cur), _p(st), _p(pos0), _p(slot0), _p(ctx),
+                                       _p(out_ids), _p(hist), hist.numel(), _p(drafts), int(max_ngram), int(max_new), int(min_len),
+                                       int(eos_id), int(bool(stop_on_eos)), C.byref(params), _p(uniforms),
+                                       0 if uniforms is None else uniforms.numel(), stream(logits)), "emu_lookup_sample_bf16")
+    return amax
+
+
+CONV_3X3,CONV_3X3_S2, CONV_3X3_UP2 = 1, 2, 3
 
 
 def groupnorm_nhwc(x, gamma, beta, groups: int, eps: float, silu: bool = False):

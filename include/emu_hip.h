@@ -535,6 +535,22 @@ int emu_decode_chunk_bf16(const void* qkv, const void* cos, const void* sin, con
 int emu_lookup_select_bf16(const void* logits, int ld, int V, int T, int32_t* amax, int32_t* cur, int32_t* st, int32_t* pos0,
                            int32_t* slot0, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
                            int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, emu_stream_t s);
+/* emu_lookup_select_bf16 with emu_sample_bf16's selection in the place of the arg-maxes (prompt lookup together with do_sample or a
+ * repetition penalty: transformers' _assisted_decoding runs the processors and warpers on every row with the history extended by the
+ * draft ids before it, draws one token per row and keeps the draft while each drawn token equals the next draft id; specified in
+ * emu_amd/speculate.py: row_select).  One 1024-thread workgroup per chunk row i <= n_draft picks amax[i] exactly as emu_sample_bf16
+ * picks output index step + i: history = out_ids[0 .. step) followed by cur[1 .. 1 + i) (the penalty acts once per distinct id, from
+ * the original logit; ids outside [0, V) are ignored), params->suppress_id suppressed while step + i < params->min_len, the uniform
+ * uniforms[min(step + i, uni_rows - 1)] (fp32 [uni_rows], one per output index; may be NULL without do_sample).  No unfinished flags,
+ * no constraint, no n-gram ban.  With the same uniforms the loop therefore emits the ids the one-row loop of emu_llama_sample_step
+ * emits, wherever both see the same logits.  Then emu_lookup_select_bf16's one workgroup, unchanged.  A call at step >= max_new or
+ * after finished changes nothing; rows behind the draft are not written (amax there is never read).  No floating-point atomics:
+ * results repeat bit for bit.  -22, nothing launched: V > EMU_SAMPLE_MAX_VOCAB, do_sample without uniforms, options emu_sample_bf16
+ * refuses, emu_lookup_select_bf16's own refusals. */
+int emu_lookup_sample_bf16(const void* logits, int ld, int V, int T, int32_t* amax, int32_t* cur, int32_t* st, int32_t* pos0,
+                           int32_t* slot0, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
+                           int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, const emu_sample_params* params,
+                           const float* uniforms, int uni_rows, emu_stream_t s);
 
 /* ---- LLaMA decoder engine ------------------------------------------------------------------------------
  * transformers LlamaModel / LlamaForCausalLM as used by EmuModel.generate / generate_image
@@ -808,6 +824,15 @@ int emu_llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int3
                           const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap, const int32_t* drafts,
                           int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos, int ctx_upper, void* hidden,
                           void* logits, int ld_logits, void* workspace, size_t ws_bytes, emu_stream_t s);
+/* emu_llama_lookup_step with emu_lookup_sample_bf16 as its selection: one step of prompt-lookup speculative decoding under sampling
+ * or a repetition penalty (lm.generate(prompt_lookup_num_tokens=k, do_sample=True, temperature, top_p, ...), the chat demo's mode,
+ * Emu2/emu/chat.py:86-148).  uniforms: fp32 [uni_rows], indexed by output position.  Graph-capturable like its parent.  -22, nothing
+ * launched: params NULL, the vocabulary above EMU_SAMPLE_MAX_VOCAB, do_sample without uniforms, the parent's refusals. */
+int emu_llama_lookup_sample_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, int32_t* st, int32_t* pos0, int32_t* slot0,
+                                 const int32_t* kstart, int32_t* ctx_dev, int32_t* out_ids, int32_t* hist, int hist_cap,
+                                 const int32_t* drafts, int max_ngram, int max_new, int min_len, int eos_id, int stop_on_eos,
+                                 int ctx_upper, void* hidden, void* logits, int ld_logits, void* workspace, size_t ws_bytes,
+                                 const emu_sample_params* params, const float* uniforms, int uni_rows, emu_stream_t s);
 /* One step of transformers' beam search (lm.generate(num_beams=N), Emu2/emu/emu.py:163-172,213-229: the library's BeamSearchScorer
  * logic in its vectorised form), deterministic mode, in two launches: log-softmax of the N beams' logit rows of every prompt, the 2N
  * best continuations over beams x vocabulary of (log p + running score) with EOS masked while cur < min_len, then the bookkeeping --
