@@ -128,6 +128,7 @@ _PROTOS = {
     "emu_gemm_plan": (i32, [vp, i32, i32, vp, C.POINTER(i32)]),
     "emu_gemv_plan": (i32, [vp, i32, vp]),
     "emu_gemv_thin_plan": (i32, [vp, i32, vp]),
+    "emu_gemv_pack_thin_plan": (i32, [vp, i32, i32, vp]),
     "emu_gemv_fp8_thin_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
@@ -192,6 +193,9 @@ _PROTOS = {
     "emu_llama_set_head_bf16_pack": (i32, [vp, C.POINTER(Bf16PackSetC), i32]),
     "emu_llama_use_bf16_pack": (i32, [vp, i32]),
     "emu_llama_pack_kernel": (i32, [i32] * 12),
+    "emu_linear_bf16pack_thin": (i32, [vp, vp, C.POINTER(Bf16PackSetC), vp, vp, i32, i32, i32, i32, vp]),
+    "emu_llama_use_bf16_pack_wide": (i32, [vp, i32]),
+    "emu_llama_pack_thin_kernel": (i32, [i32] * 12),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),

@@ -99,7 +99,7 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
                  const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr;
                  PackSet pk; int pkN = 0, pkK = 0; };
-enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel)
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel, emu_llama_pack_thin_kernel)
 // The one rule that picks a LLaMA projection's kernel, layers and head alike, from integers only: the modes as emu_llama_use_fp8 /
 // emu_llama_use_fp4 set them (never both), the call's rows, the shard's reduction widths.  1..2 rows: the weight streams with the
 // RMSNorm in front (gemv_fp4.hip, gemv.hip); 3..16: the MXFP4 matrix-core stream (gemv_fp4_thin.hip), or the fp8 one
@@ -121,6 +121,16 @@ WeightKernel pack_kernel(WeightKernel k, int rows, int pack_rows, int pack_on, i
     if (k != WeightKernel::Bf16 || rows != 1 || !pack_on || pack_rows <= 0 || fused_mode || tail_mode || warm_mask) return k;
     const GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
     return gemv_pack_rows(gemv_plan(sh, tune), sh) == pack_rows ? WeightKernel::Bf16Pack : k;
+}
+// And the rule behind it, for the steps of 4..16 rows: a projection the two rules above left on bf16 streams the same packed set through
+// the matrix-core twin (gemv_pack_thin.hip) exactly when the pack stream and its wide switch (emu_llama_use_bf16_pack_wide) are on,
+// the matrix has a set (pack_rows) of its own N and K, and gemv_pack_thin_plan has a twin for the shape.  Integers only.
+WeightKernel pack_thin_kernel(WeightKernel k, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
+                              int epi, int tune) {
+    if (k != WeightKernel::Bf16 || !pack_on || !wide_on || pack_rows <= 0 || set_n != N || set_k != K || rows < 4 || rows > 16) return k;
+    GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
+    sh.M = rows;
+    return gemv_pack_thin_plan(sh, pack_rows, tune).status ? k : WeightKernel::Bf16PackThin;
 }
 // out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
 // pointers, which come from w (ldw in elements of the set k reads).  The MXFP4 kernels run under the GEMV profiler, the 4-bit bytes of
@@ -149,6 +159,15 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
         const double bytes = (double)(pack_lo_bytes(g.N, g.K, w.pk.rows) + pack_nib_bytes(g.N, g.K, w.pk.rows) + pack_sign_bytes(g.N, g.K, w.pk.rows) +
                                       4 * pack_flag_words(g.N, w.pk.rows));
         return gemv_profiled(bytes, s, [&] { return launch_gemv_pack(g, w.pk, p.form, s); });
+    }
+    if (k == WeightKernel::Bf16PackThin) {           // the packed twin of the bf16 thin stream, priced at the bytes it streams
+        if (!w.W || !w.pk.rows || g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
+        g.W = w.W;
+        const GemvPlan p = gemv_pack_thin_plan(gemv_shape_of(g), w.pk.rows, emu_gemm_tune_get());
+        if (p.status) return -22;
+        const double bytes = (double)(pack_lo_bytes(g.N, g.K, w.pk.rows) + pack_nib_bytes(g.N, g.K, w.pk.rows) + pack_sign_bytes(g.N, g.K, w.pk.rows) +
+                                      4 * pack_flag_words(g.N, w.pk.rows));
+        return gemv_profiled(bytes, s, [&] { return launch_gemv_pack_thin(g, w.pk, p, s); });
     }
     if (k == WeightKernel::Fp8Gemm || !w.W4 || !w.s4) return -22;
     g.W = B(w.W4); g.w4scale = w.s4;
@@ -220,6 +239,11 @@ int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int 
     if (kernel < 0 || kernel > (int)WeightKernel::Fp8Thin) return -22;
     return (int)pack_kernel((WeightKernel)kernel, rows, pack_rows, pack_on, fused_mode, tail_mode, warm_mask, N, K, norm, epi, tune);
 }
+int emu_llama_pack_thin_kernel(int kernel, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
+                               int epi, int tune) {
+    if (kernel < 0 || kernel > (int)WeightKernel::Bf16PackThin) return -22;
+    return (int)pack_thin_kernel((WeightKernel)kernel, rows, pack_rows, set_n, set_k, pack_on, wide_on, N, K, norm, epi, tune);
+}
 int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune) {
     if (N < 1 || K < 8) return 0;
     const GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
@@ -236,6 +260,15 @@ int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* s
     PackSet p;
     p.lo = set->lo; p.nib = set->nib; p.sign = set->sign; p.flags = reinterpret_cast<const uint32_t*>(set->flags); p.hb = set->hb; p.rows = set->rows;
     return launch_gemv_pack(g, p, form, S(s));
+}
+int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, void* C, int M, int N, int K,
+                             int epi, emu_stream_t s) {
+    if (!A || !W || !set || !C) return -22;
+    GemvArgs g{B(A), B(W), nullptr, nullptr, B(res), B(C), M, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, 0.f, epi, nullptr};
+    PackSet p;
+    p.lo = set->lo; p.nib = set->nib; p.sign = set->sign; p.flags = reinterpret_cast<const uint32_t*>(set->flags); p.hb = set->hb; p.rows = set->rows;
+    const GemvPlan pl = gemv_pack_thin_plan(gemv_shape_of(g), p.rows, emu_gemm_tune_get());
+    return pl.status ? -22 : launch_gemv_pack_thin(g, p, pl, S(s));
 }
 
 void emu_set_splitk_scratch(void* ptr, size_t bytes) { emu_gemm_set_splitk_scratch(reinterpret_cast<float*>(ptr), bytes / sizeof(float)); }
@@ -692,6 +725,7 @@ struct emu_llama {
     bool fp4_all = false;
     bool bf16_released = false;
     bool bf16_pack = false;        // emu_llama_use_bf16_pack: one-row bf16 projections stream their 13-bit packed sets (pack_kernel)
+    bool bf16_pack_wide = false;   // emu_llama_use_bf16_pack_wide: so do their 4..16-row steps (pack_thin_kernel)
     // the kernel of a projection of `rows` rows, layers and head alike: the modes above through weight_kernel
     WeightKernel kernel_for(int rows) const {
         return weight_kernel(fp8_decode ? 1 + (fp8_prefill ? 1 : 0) + (fp8_wide ? 2 : 0) : 0, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
@@ -946,6 +980,7 @@ struct LlamaCall {
         }
         k = pack_kernel(k, rows, W.pkN == N && W.pkK == K ? W.pk.rows : 0, m->bf16_pack, m->decode_fused, plan.decode_tail, plan.warm | (int)warm.ntouch,
                         N, K, gain_in != nullptr, epi, emu_gemm_tune_get());
+        k = pack_thin_kernel(k, rows, W.pk.rows, W.pkN, W.pkK, m->bf16_pack, m->bf16_pack_wide, N, K, gain_in != nullptr, epi, emu_gemm_tune_get());
         GemvArgs g = packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi);
         if (warm.ntouch && k == WeightKernel::Bf16) { g.warm = warm; ++m->warm_launches; }
         return linear_w(k, W, g, s, w.splitk, w.splitk_floats);
@@ -1460,6 +1495,12 @@ int emu_llama_use_bf16_pack(emu_llama* m, int on) {
     m->bf16_pack = on != 0;
     return 0;
 }
+int emu_llama_use_bf16_pack_wide(emu_llama* m, int on) {
+    if (!m) return -22;
+    if (on && m->bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack_wide: the bf16 weights were released (emu_llama_release_bf16)");
+    m->bf16_pack_wide = on != 0;
+    return 0;
+}
 int emu_llama_release_bf16(emu_llama* m) {
     if (!m) return -22;
     if (!m->fp4_all) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
@@ -1470,7 +1511,7 @@ int emu_llama_release_bf16(emu_llama* m) {
     }
     m->head.W = nullptr;
     m->head.pk = PackSet{};
-    m->bf16_pack = false;
+    m->bf16_pack = m->bf16_pack_wide = false;
     m->dl_dirty = true;
     m->bf16_released = true;
     return 0;
@@ -1779,6 +1820,7 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
                                N, H, 1, EPI_NONE, emu_gemm_tune_get());
     if (!fused) {
         if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
+        k = pack_thin_kernel(k, M, m->head.pk.rows, m->head.pkN, m->head.pkK, m->bf16_pack, m->bf16_pack_wide, N, H, 0, EPI_NONE, emu_gemm_tune_get());
         TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
     }
     return linear_w(k, m->head, packed(k, fused ? hidden : ws, fused ? ldh : H, fused ? m->final_norm : nullptr, c.rms_eps, nullptr, 0, out, ld,

@@ -1062,7 +1062,40 @@ int launch_gemv_thin_stream(const GemvArgs& a, hipStream_t s) {
 }
 bool fp4_mfma_ok(const GemvArgs& a) { return a.M >= 17 && fp4_mfma_shape_ok(gemv_shape_of(a)) && mfma_pointers_ok(a); }
 
+// The 13-bit packed twin of the bf16 thin stream (gemv_pack_thin.hip), from the bf16 plan of the same shape: it exists for kch 32.
+// The built tiles, as (weight rows, ring depth: workgroups that share a CU's LDS): up to 8 activation rows (16, 4: 3), (32, 4: 2),
+// (16, 6: 2), (32, 3: 3); up to 16 (16, 3: 3), (32, 3: 2), (16, 5: 2).  The plan is the tile whose grid fills the largest share of its
+// whole rounds of 256 x (workgroups per CU) places, the first of equals in that order, which is the measured one.
+// Measured at 5 rows (tools/pack_wide_time.py --ab, us, 16 / 32 weight rows): lm_head, 1009 workgroups of 32 on 2 x 512 places, 65.5 /
+// 60.3 (a tie with 2018 of 16 at six stages); qkv, a tie of 1248 on 2 x 768 and 624 on 768, 37.1 / 44.6; down_proj, 416 on 512 at six stages, 41.4 / 40.0.  At 9..16 rows
+// the rule leaves gate/up on 16 rows (85.2 us) where 32 measure 78.7: there the activation rows a workgroup re-stages outweigh the fill.
+// emu_gemm_tune bits 28-29 pin 16 / 32 weight rows as for the byte-fed streams.
+GemvPlan gemv_pack_thin_plan(const GemvShape& sh, int set_rows, int tune) {
+    GemvPlan refused{};
+    refused.status = -22;
+    if (sh.fp8 || sh.fp4 || sh.norm || sh.M < 4 || sh.M > 16 || (set_rows != 2 && set_rows != 4)) return refused;
+    if (sh.epi != EPI_NONE && sh.epi != EPI_RESID && sh.epi != EPI_SWIGLU) return refused;
+    const GemvPlan b = gemv_plan(sh, tune);
+    if (b.status || b.family != GEMV_FAM_THIN || b.kch != 32) return refused;
+    struct Tile { int rows, stages, per_cu; };
+    static const Tile tiles8[] = {{16, 4, 3}, {32, 4, 2}, {16, 6, 2}, {32, 3, 3}}, tiles16[] = {{16, 3, 3}, {32, 3, 2}, {16, 5, 2}};
+    const Tile* tiles = sh.M <= 8 ? tiles8 : tiles16;
+    const int ntiles = sh.M <= 8 ? 4 : 3, pin = (tune >> 28) & 3;
+    const Tile* best = nullptr;
+    long best_num = 0, best_den = 1;                                   // the filled share grid / (rounds * places), as a fraction
+    for (int t = 0; t < ntiles; ++t) {
+        if ((pin == 1 && tiles[t].rows != 16) || (pin == 2 && tiles[t].rows != 32)) continue;
+        const long grid = (sh.N + tiles[t].rows - 1) / tiles[t].rows, places = 256L * tiles[t].per_cu;
+        const long den = (grid + places - 1) / places * places;
+        if (!best || grid * best_den > best_num * den) { best = &tiles[t]; best_num = grid; best_den = den; }
+    }
+    return thin_planned(sh, GEMV_FAM_PACK_THIN, best->rows, best->stages, 32);
+}
+
 // C-ABI test hooks (include/emu_hip.h)
+int emu_gemv_pack_thin_plan(const emu_gemv_shape* shape, int set_rows, int tune, emu_gemv_plan_t* out) {
+    return shape && out ? (*out = gemv_pack_thin_plan(*shape, set_rows, tune)).status : -22;
+}
 int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
     return shape && out ? (*out = gemv_plan(*shape, tune)).status : -22;
 }

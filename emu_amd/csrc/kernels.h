@@ -40,7 +40,7 @@ struct GemvArgs {
 using GemvShape = emu_gemv_shape;
 using GemvPlan = emu_gemv_plan_t;
 enum GemvFamily { GEMV_FAM_BLOCK = 0, GEMV_FAM_RT = 1, GEMV_FAM_WAVE = 2, GEMV_FAM_MFMA = 3, GEMV_FAM_THIN = 4, GEMV_FAM_FP8_BLOCK = 5,
-                  GEMV_FAM_FP8_RT = 6, GEMV_FAM_FP4_ROWS = 7, GEMV_FAM_FP8_THIN = 8, GEMV_FAM_FP4_THIN = 9 };
+                  GEMV_FAM_FP8_RT = 6, GEMV_FAM_FP4_ROWS = 7, GEMV_FAM_FP8_THIN = 8, GEMV_FAM_FP4_THIN = 9, GEMV_FAM_PACK_THIN = 10 };
 // the form of a one-row bf16 stream; workgroup j reads weight rows [j * rows, j * rows + rows)  (GEMV_FORM_WAVE: 4 waves x 4 whole rows)
 enum GemvForm { GEMV_FORM_ROLLING = 0, GEMV_FORM_HEAD = 1, GEMV_FORM_PRELOAD = 2, GEMV_FORM_RT = 3, GEMV_FORM_WAVE = 4 };
 GemvShape gemv_shape_of(const GemvArgs& a);
@@ -80,6 +80,13 @@ int launch_bf16_pack(const bf16_t* W, int ldw, int N, int K, int rows, void* lo,
                      hipStream_t s);
 int gemv_pack_rows(const GemvPlan& p, const GemvShape& sh);
 int launch_gemv_pack(const GemvArgs& a, const struct PackSet& p, int form, hipStream_t s);
+// the few-row (4..16) twin (gemv_pack_thin.hip): the same sets through the bf16 thin stream's arithmetic at kch 32.  gemv_pack_thin_plan
+// (gemv.hip): family GEMV_FAM_PACK_THIN with rows, mb, stages, kch, grid, block exactly when gemv_plan sends the bf16 shape (no fused
+// norm) to GEMV_FAM_THIN with a kch that has a twin, set_rows is 2 or 4, 4 <= M <= 16 and the epilogue is NONE / RESID / SWIGLU; else
+// status -22 and every other field 0.  launch_gemv_pack_thin: that plan's launch; a.W = the bf16 matrix (flagged workgroups stream
+// it); bit-identical to launch_gemv on the bf16 matrix
+GemvPlan gemv_pack_thin_plan(const GemvShape& shape, int set_rows, int tune);
+int launch_gemv_pack_thin(const GemvArgs& a, const struct PackSet& p, const GemvPlan& plan, hipStream_t s);
 // o_proj of a tensor-parallel shard's one-row step with the decode attention's split merge in its prologue (gemv_merge.hip):
 // x = merge of the live splits in decode_fused_kernel's workspace (batch row 0), out = epi(x W^T [+ res]); bit-identical to
 // decode_fused_combine_kernel followed by the wave-form GEMV.  K = H * 128 <= 1024, nsplit <= 8, N >= 1024 (gemv_merge_ok).

@@ -463,6 +463,21 @@ class LlamaEngine:
         self.bf16_pack_on = bool(enable)
         self._mode_changed()
 
+    def use_bf16_pack_wide(self, enable: bool = True) -> None:
+        """Steps of 4..16 rows (beam search, small batches, contrastive search, the lookup chunk step) stream the packed sets too,
+        through the matrix-core twin of the bf16 few-row stream: same bits, 13/16 of the bytes.  Off by default
+        (profiles/bf16_pack_wide.md); needs ``use_bf16_pack`` on.  Invalidates captured graphs."""
+        if enable and not self.bf16_released and not getattr(self, "bf16_pack_on", False):
+            raise RuntimeError("use_bf16_pack_wide: switch the packed stream on first (use_bf16_pack)")
+        check(lib().emu_llama_use_bf16_pack_wide(self.handle, 1 if enable else 0), "emu_llama_use_bf16_pack_wide", self.ctx.handle)
+        self.bf16_pack_wide = bool(enable)
+        self._mode_changed()
+
+    def _pack_wide_default(self) -> None:
+        """EMU_BF16_PACK_WIDE=1 switches the few-row stream on where the default packing has switched the one-row stream on."""
+        if os.environ.get("EMU_BF16_PACK_WIDE") == "1" and not getattr(self, "bf16_pack_wide", False) and hasattr(lib(), "emu_llama_use_bf16_pack_wide"):
+            self.use_bf16_pack_wide(True)
+
     def _auto_pack_bf16(self) -> None:
         """The default: when the engine is ready, pack and switch the stream on -- unless EMU_BF16_PACK=0, the library predates the
         stream (a tools A/B run against an older build), no matrix has a packed twin (small models, tensor-parallel shards), or the
@@ -484,6 +499,7 @@ class LlamaEngine:
         n, nbytes = self.pack_bf16(head_form=head_form)
         torch.cuda.synchronize(self.device)
         self.use_bf16_pack(True)
+        self._pack_wide_default()
         print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s",
               file=sys.stderr)
 
@@ -509,6 +525,7 @@ class LlamaEngine:
         n, nbytes = self.pack_bf16(head_form=True)
         torch.cuda.synchronize(self.device)
         self.use_bf16_pack(True)
+        self._pack_wide_default()
         total = sum(bf16pack.packed_bytes(*v["shape"], v["rows"]) for v in self._pack.values())
         print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s"
               f"; {len(self._pack)} matrices, {total / 2**30:.2f} GiB of sets in all", file=sys.stderr)
@@ -672,7 +689,7 @@ class LlamaEngine:
             del self._keep[key]
         self.lm_head = None
         self.__dict__.pop("_pack", None)                     # (the library dropped the sets with the bf16 rows)
-        self.bf16_pack_on = False
+        self.bf16_pack_on = self.bf16_pack_wide = False
         self._mode_changed()
 
     def fp4_dequantized(self, key: str) -> torch.Tensor:

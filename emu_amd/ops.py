@@ -169,6 +169,22 @@ def linear_bf16pack(x, w, p, form: int, res=None, norm_w=None, eps: float = 0.0,
     return out
 
 
+def linear_bf16pack_thin(x, w, p, res=None, epi: int = EPI_NONE, out=None):
+    """4..16 activation rows over the packed set ``p`` of ``w`` on the matrix cores, the bits of ``linear(x, w)``; the library
+    refuses (-22) what has no packed twin; see emu_linear_bf16pack_thin."""
+    _req(x, "x"); _req(w, "w")
+    assert x.dim() == 2 and x.is_contiguous() and w.is_contiguous() and tuple(w.shape) == tuple(p["shape"]) and x.shape[1] == w.shape[1]
+    M, (N, K) = x.shape[0], w.shape
+    if out is None:
+        out = torch.empty(M, N // 2 if epi == EPI_SWIGLU else N, device=x.device, dtype=BF16)
+    _req(out, "out")
+    assert out.is_contiguous() and (res is None or (res.is_contiguous() and tuple(res.shape) == (M, N)))
+    s = pack_set_c(p)
+    check(lib().emu_linear_bf16pack_thin(_p(x), _p(w), C.byref(s), _p(res), _p(out), M, N, K, int(epi), stream(x)),
+          "emu_linear_bf16pack_thin")
+    return out
+
+
 def linear_fp4w(x, w4, scales, bias=None, res=None, norm_w=None, eps: float = 0.0, epi: int = EPI_NONE, out=None):
     """``linear`` over an MXFP4 weight stream (decode rows only, M <= 2; K % 32 == 0); see emu_linear_fp4w_bf16."""
     _req(x, "x"); _req(w4, "w4", torch.uint8); _req(scales, "scales", torch.uint8)

@@ -134,6 +134,17 @@ int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
  *          started 256-wide stage (K / 32 where K % 256 == 0), an epilogue other than NONE / RESID / SWIGLU;
  *   all    N < 1, a fused norm, W or x off a 16-byte boundary, an odd N under SWIGLU. */
 int emu_gemv_thin_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out);
+/* CPU test hook (tests/test_pack_thin_plan.py): the plan of the 13-bit packed twin of the bf16 few-row stream (family 4 above) for
+ * a set of set_rows (2 / 4) rows per group -- what emu_linear_bf16pack_thin and the engine's 4..16-row steps under
+ * emu_llama_use_bf16_pack_wide launch.  Succeeds exactly when emu_gemv_plan sends the shape (bf16, no fused norm) to family 4 with
+ * a kch that has a twin (32), set_rows is 2 or 4, 4 <= M <= 16 and the epilogue is NONE / RESID / SWIGLU.  The plan: family 10;
+ * mb 8 / 16; kch 32; waves 4, block 256; (rows = weight rows per workgroup, stages) one of the built tiles, listed with the
+ * workgroups that share a CU's LDS -- mb 8: (16, 4: 3), (32, 4: 2), (16, 6: 2), (32, 3: 3); mb 16: (16, 3: 3), (32, 3: 2), (16, 5: 2) --
+ * namely the one whose grid = ceil(N / rows) fills the largest share of its whole rounds of 256 x (workgroups per CU) places, the
+ * first of equals in that order; tune bits 28-29 = 1 / 2 leave only the tiles of 16 / 32 rows; the other fields 0.  LDS bytes: the
+ * larger of stages * (rows / 4 + rows / 8 + 1 + mb / 2) KiB and the bf16 ring of a flagged workgroup, 3 stages of (rows + mb) * 512
+ * bytes where they fit the former, else 2.  Returns 0, or -22 (then the other fields are 0). */
+int emu_gemv_pack_thin_plan(const emu_gemv_shape* shape, int set_rows, int tune, emu_gemv_plan_t* out);
 /* The older view of the fp8 branch of emu_gemv_thin_plan (tests/test_fp8_wide_host.py): M rows over an fp8 matrix [N, K] (ldx in bf16
  * elements, ldw in bytes) on aligned buffers.  rows, mb, stages, grid, block: the plan's; kc = 256: k per stage; lds_bytes = stages *
  * (rows * kc + mb * kc * 2).  Returns 0, or -22 (then the other fields are 0). */
@@ -652,6 +663,22 @@ int emu_llama_use_bf16_pack(emu_llama* m, int on);
  * emu_bf16_pack_rows(N, K, norm, epi, tune) == pack_rows; else `kernel`. */
 int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
                           int norm, int epi, int tune);
+/* The same sets under steps of 4..16 activation rows: the matrix-core twin of the bf16 few-row stream (gemv_pack_thin.hip), whose
+ * outputs are that stream's bit for bit at 13/16 of its bytes.
+ * emu_linear_bf16pack_thin (tests): C[M, N] = epi(A W^T [+ res]) for 4 <= M <= 16 rows of K contiguous elements over the set of the
+ * bf16 matrix W [N, K] (read for flagged row groups); epi NONE / RESID (res [M, N]) / SWIGLU (C [M, N / 2]).  -22, nothing
+ * written, where emu_gemv_pack_thin_plan refuses or a pointer is missing or a plane is off a 16-byte boundary.
+ * emu_llama_use_bf16_pack_wide(m, 1): OFF by default; with emu_llama_use_bf16_pack on, projections and the head at 4..16 rows that
+ * are on the bf16 kernels stream their set where emu_llama_pack_thin_kernel says so.  Refused after emu_llama_release_bf16.
+ * emu_llama_pack_thin_kernel (CPU test hook, tests/test_pack_thin_plan.py): that rule on integers.  kernel: the answer of
+ * emu_llama_pack_kernel; rows = B*T; pack_rows, set_n, set_k: the registered set's rows per group (0: none) and shape; pack_on /
+ * wide_on: the two switches; [N, K], norm, epi: the projection; tune: the emu_gemm_tune mask.  Returns 8 only for kernel 0, both
+ * switches on, a set of this N and K, 4 <= rows <= 16 and a plan from emu_gemv_pack_thin_plan; else `kernel`. */
+int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, void* C, int M, int N, int K,
+                             int epi, emu_stream_t s);
+int emu_llama_use_bf16_pack_wide(emu_llama* m, int on);
+int emu_llama_pack_thin_kernel(int kernel, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
+                               int epi, int tune);
 /* Vocabulary-sharded lm_head under tensor parallelism (the reference's lm_head is lm.lm_head of LlamaForCausalLM reached
  * from Emu2/emu/emu.py:213-229): the lm_head pointer of emu_llama_set_head holds rows [row0, row0 + rows) of the vocabulary only;
  * emu_llama_logits fills this rank's columns of the caller's [M, vocab] rows, zeroes the others and all-reduces the rows, so every
