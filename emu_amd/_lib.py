@@ -168,6 +168,8 @@ _PROTOS = {
     "emu_transpose_v_bf16": (i32, [vp, lng, lng, lng, vp, i32, i32, i32, i32, i32, vp]),
     "emu_flash_attn_bf16": (i32, [vp, lng, lng, lng, vp, lng, lng, lng, vp, vp, lng, lng, lng, vp,
                                   i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "emu_flash_attn_prefix_bf16": (i32, [vp, lng, lng, lng, vp, lng, lng, vp, vp, lng, lng, lng, vp, vp, lng, lng, lng,
+                                         i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
     "emu_decode_attn_ws_bytes": (sz, [i32, i32, i32, i32]),
     "emu_decode_attn_bf16": (i32, [vp, lng, lng, vp, vp, vp, lng, lng, vp, vp, i32, i32, vp, i32, i32, i32, i32, f32, vp]),
     "emu_decode_fused_ws_bytes": (sz, [i32, i32, i32, i32]),
@@ -200,6 +202,7 @@ _PROTOS = {
     "emu_llama_set_head_shard": (i32, [vp, i32, i32]),
     "emu_llama_set_kv": (i32, [vp, vp, vp, i32, i32]),
     "emu_llama_set_kv_share": (i32, [vp, i32, i32]),
+    "emu_llama_set_kv_prefix": (i32, [vp, vp, vp, i32, i32]),
     "emu_beam_step_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "emu_beam_step_trie_bf16": (i32, [vp, lng, lng, i32, i32, i32, i32, i32, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                                       C.POINTER(TokenTrieC), vp, vp]),

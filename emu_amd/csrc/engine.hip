@@ -673,6 +673,14 @@ int emu_flash_attn_bf16(const void* q, long q_sb, long q_sh, long q_ss, const vo
                 Bn, H, Sq, Sk, Sk_pad, D, causal, scale};
     return launch_flash_attn(a, S(s));
 }
+int emu_flash_attn_prefix_bf16(const void* q, long q_sb, long q_sh, long q_ss, const void* kprefix, long kp_sh, long kp_ss,
+                               const void* vtprefix, const void* k, long k_sb, long k_sh, long k_ss, const void* vt, void* o, long o_sb,
+                               long o_sh, long o_ss, int kstart, int Bn, int H, int Sq, int P, int P_pad, int Sk, int Sk_pad, int D,
+                               float scale, emu_stream_t s) {
+    FlashPrefixArgs a{B(q), q_sb, q_sh, q_ss, B(kprefix), kp_sh, kp_ss, B(vtprefix), B(k), k_sb, k_sh, k_ss, B(vt),
+                      B(o), o_sb, o_sh, o_ss, nullptr, kstart, Bn, H, Sq, P, P_pad, Sk, Sk_pad, D, scale};
+    return launch_flash_attn_prefix(a, S(s));
+}
 size_t emu_decode_attn_ws_bytes(int Bn, int H, int D, int ctx_max) {
     return (size_t)Bn * H * decode_attn_nsplit(ctx_max) * (D + 2) * sizeof(float);
 }
@@ -738,6 +746,10 @@ struct emu_llama {
     bf16_t *kcache = nullptr, *vcache = nullptr;
     int kv_batch = 0, s_max = 0;
     int kv_share_nb = 0, kv_share_len = 0;       // emu_llama_set_kv_share: beams of a prompt share its cache slots
+    // emu_llama_set_kv_prefix: T > 1 rows attend prefix[kstart .. prefix_len) of these read-only caches [layer, 1, Hl, prefix_s_max, D]
+    // plus their own slots of kcache / vcache (attention_prefix.hip); prefix_len = 0: off
+    const bf16_t *kprefix = nullptr, *vprefix = nullptr;
+    int prefix_s_max = 0, prefix_len = 0;
     int l0 = 0, l1 = -1;                         // emu_llama_set_layer_range: layers [l0, l1) run (l1 < 0: all)
     bool fuse_norm_on = false;                   // sticky: o_proj / down_proj K-slice sums apply the RMSNorm behind them (M > 16, no TP)
     bool prefill_fusion = false;                 // emu_llama_set_prefill_fusion: RoPE + KV append + V^T in the qkv GEMM's epilogue (one-shot: the next T > 1 forward consumes it)
@@ -778,6 +790,7 @@ struct LlamaWs {
     size_t splitk_floats;
     bf16_t* vt2;            // two-lane tensor-parallel prefill (emu_llama_set_tp_overlap): the second lane's own V^T ...
     float* splitk2;         // ... and K-slice scratch (the lanes' GEMMs run concurrently)
+    bf16_t* pvt;            // emu_llama_set_kv_prefix: the current layer's prefix V^T [Hl, D, pad64(prefix_len)], one row for all Bn
     size_t total;
 };
 // chunk: a chunk step of Bn x T rows (emu_llama_forward_chunk) -- no V^T, the split states of every row and the rows' slots
@@ -805,6 +818,7 @@ LlamaWs llama_ws(const emu_llama* m, int Bn, int T, void* base, bool chunk = fal
     const bool lanes = m->tp_overlap_rows > 0 && Bn == 1 && T >= m->tp_overlap_rows;
     w.vt2 = (bf16_t*)take(lanes ? HD * spad * 2 : 0);
     w.splitk2 = (float*)take(lanes ? w.splitk_floats * sizeof(float) : 0);
+    w.pvt = (bf16_t*)take(m->prefix_len > 0 && T > 1 && !chunk ? HD * (size_t)((m->prefix_len + 63) / 64 * 64) * 2 : 0);
     w.total = off;
     return w;
 }
@@ -899,7 +913,8 @@ struct LlamaCall {
         // the caller promised (emu_llama_set_prefill_fusion) that the rows of the one batch element are the whole context in slot
         // order, slot[i] = i.  The promise is per call: emu_llama_forward consumed it, so a later forward with rows in another slot
         // order (any caller that did not renew it) runs the unfused sequence, which honours slot[] everywhere.
-        const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv;
+        // (a KV prefix: the rows are a continuation behind the prefix, whatever T == ctx and slots 0 .. T - 1 look like -- never fused)
+        const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv && m->prefix_len == 0;
         // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
         // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
         p.kernel = m->kernel_for(M);
@@ -1086,11 +1101,25 @@ struct LlamaCall {
                 TRY(cx, launch_transpose_v(tv, win.s));      // keys [0, kend) key-contiguous, zero up to spad
             }
             if (after_vt) TRY(cx, after_vt());
-            FlashArgs fa{w.qkv, (long)win.T * 3 * HD, (long)D, (long)3 * HD,
-                         kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D,
-                         w.vt, w.attn, (long)win.T * HD, (long)D, (long)HD, kstart,
-                         Bn, Hl, win.T, win.kend, spad, D, 1, scale};              // query i of the window sees keys <= r0 + i
-            TRY(cx, launch_flash_attn(fa, win.s));
+            if (m->prefix_len > 0) {
+                // two segments: the prefix's keys from its own cache (V^T of ONE row, once per layer), then the rows' own slots [0, kend)
+                const int P = m->prefix_len, ppad = (P + 63) / 64 * 64;
+                const size_t pl = (size_t)Hl * m->prefix_s_max * D;
+                TransposeVArgs tp_{m->vprefix + l * pl, (long)pl, (long)m->prefix_s_max * D, (long)D, w.pvt, 1, Hl, P, D, ppad};
+                TRY(cx, launch_transpose_v(tp_, win.s));
+                FlashPrefixArgs pa{w.qkv, (long)win.T * 3 * HD, (long)D, (long)3 * HD,
+                                   m->kprefix + l * pl, (long)m->prefix_s_max * D, (long)D, w.pvt,
+                                   kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D, w.vt,
+                                   w.attn, (long)win.T * HD, (long)D, (long)HD, kstart, 0,
+                                   Bn, Hl, win.T, P, ppad, win.kend, spad, D, scale};
+                TRY(cx, launch_flash_attn_prefix(pa, win.s));
+            } else {
+                FlashArgs fa{w.qkv, (long)win.T * 3 * HD, (long)D, (long)3 * HD,
+                             kc, (long)Hl * m->s_max * D, (long)m->s_max * D, (long)D,
+                             w.vt, w.attn, (long)win.T * HD, (long)D, (long)HD, kstart,
+                             Bn, Hl, win.T, win.kend, spad, D, 1, scale};          // query i of the window sees keys <= r0 + i
+                TRY(cx, launch_flash_attn(fa, win.s));
+            }
         }
         if (plan.merge_o) {
             GemvMergeArgs g{w.dec, win.slot, (ctx + 127) / 128, Hl, L.o.W, win.x, w.hB, H, HD, HD, epi_res, nullptr};
@@ -1592,16 +1621,29 @@ int emu_llama_set_kv(emu_llama* m, void* kcache, void* vcache, int batch, int s_
     if (!kcache && !vcache) {                    // detach: the caller freed the caches; every later forward fails with -22 until new ones are set
         m->kcache = m->vcache = nullptr; m->kv_batch = m->s_max = 0;
         m->kv_share_nb = m->kv_share_len = 0;
+        m->kprefix = m->vprefix = nullptr; m->prefix_s_max = m->prefix_len = 0;
         return 0;
     }
     if (!kcache || !vcache || batch < 1 || s_max < 1) return -22;
     m->kcache = B(kcache); m->vcache = B(vcache); m->kv_batch = batch; m->s_max = s_max;
     m->kv_share_nb = m->kv_share_len = 0;
+    m->kprefix = m->vprefix = nullptr; m->prefix_s_max = m->prefix_len = 0;
+    return 0;
+}
+int emu_llama_set_kv_prefix(emu_llama* m, const void* kprefix, const void* vprefix, int prefix_s_max, int prefix_len) {
+    if (!m) return -22;
+    if (!kprefix || !vprefix || prefix_len == 0) { m->kprefix = m->vprefix = nullptr; m->prefix_s_max = m->prefix_len = 0; return 0; }
+    if (prefix_len < 0 || prefix_len > prefix_s_max) return fail(m->ctx, -22, "emu_llama_set_kv_prefix: prefix_len within the prefix caches' capacity");
+    if (m->cfg.head_dim != 128) return fail(m->ctx, -22, "emu_llama_set_kv_prefix: the two-segment attention has head_dim 128 only");
+    if (!m->kcache) return fail(m->ctx, -22, "emu_llama_set_kv_prefix: set the rows' own cache first (emu_llama_set_kv)");
+    if (m->kv_share_nb > 1) return fail(m->ctx, -22, "emu_llama_set_kv_prefix: not together with emu_llama_set_kv_share");
+    m->kprefix = B(kprefix); m->vprefix = B(vprefix); m->prefix_s_max = prefix_s_max; m->prefix_len = prefix_len;
     return 0;
 }
 int emu_llama_set_kv_share(emu_llama* m, int beams, int shared_slots) {
     if (!m) return -22;
     if (beams <= 1) { m->kv_share_nb = m->kv_share_len = 0; return 0; }
+    if (m->prefix_len > 0) return fail(m->ctx, -22, "emu_llama_set_kv_share: not while a KV prefix is set (emu_llama_set_kv_prefix)");
     if (beams > DECODE_SHARE_MAX || !m->kcache || m->kv_batch % beams || shared_slots < 0 || shared_slots > m->s_max)
         return fail(m->ctx, -22, "emu_llama_set_kv_share: 2..8 beams dividing the cache batch, shared slots within the capacity");
     m->kv_share_nb = beams; m->kv_share_len = shared_slots;
@@ -1631,6 +1673,13 @@ int emu_llama_forward(emu_llama* m, void* hidden, int Bn, int T, const int32_t* 
     if (!m->kcache || Bn != m->kv_batch) return fail(cx, -22, "emu_llama_forward: KV cache not set for this batch size");
     if (ctx < 1 || ctx > m->s_max) return fail(cx, -22, "emu_llama_forward: ctx out of range");
     if (!m->cos) return fail(cx, -22, "emu_llama_forward: rope tables not set");
+    if (m->prefix_len > 0) {                     // every refusal of the two-segment form, before any launch
+        if (T == 1) return fail(cx, -22, "emu_llama_forward: a KV prefix serves T > 1 rows only (emu_llama_set_kv_prefix(m, NULL, NULL, 0, 0) first)");
+        if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward: a KV prefix and emu_llama_set_kv_share exclude each other");
+        if (m->decode_fused) return fail(cx, -22, "emu_llama_forward: a KV prefix and the fused decode modes exclude each other");
+        if (m->tp_overlap_rows > 0) return fail(cx, -22, "emu_llama_forward: a KV prefix has no two-lane tensor-parallel prefill (emu_llama_set_tp_overlap(m, 0) first)");
+        if (c.head_dim != 128) return fail(cx, -22, "emu_llama_forward: a KV prefix needs head_dim 128");
+    }
     LlamaCall f{};
     f.m = m; f.cx = cx; f.ws = llama_ws(m, Bn, T, workspace);
     if (f.ws.total > ws_bytes) return fail(cx, -12, "emu_llama_forward: workspace too small");
@@ -1667,6 +1716,7 @@ int emu_llama_forward_chunk(emu_llama* m, void* hidden, int Bn, int T, const int
     if (T < 2 || T > DECODE_CHUNK_MAX || Bn < 1 || Bn * T > 16) return fail(cx, -22, "emu_llama_forward_chunk: T in 2..8 and B * T <= 16");
     if (cx->tp_size > 1 || cx->comm != nullptr || cx->p2p_on) return fail(cx, -22, "emu_llama_forward_chunk: no tensor-parallel form");
     if (m->kv_share_nb > 1) return fail(cx, -22, "emu_llama_forward_chunk: shared-prefix KV rows serve single-token steps only");
+    if (m->prefix_len > 0) return fail(cx, -22, "emu_llama_forward_chunk: a KV prefix serves emu_llama_forward with T > 1 only");
     if (m->decode_fused) return fail(cx, -22, "emu_llama_forward_chunk: the fused decode modes 1-4 are one-row steps (emu_llama_set_decode_fused(m, 0, 0) first)");
     if (!m->kcache || Bn != m->kv_batch) return fail(cx, -22, "emu_llama_forward_chunk: KV cache not set for this batch size");
     if (ctx_upper < 1 || ctx_upper > m->s_max) return fail(cx, -22, "emu_llama_forward_chunk: ctx out of range");
@@ -1862,6 +1912,7 @@ static int llama_token_step(emu_llama* m, int Bn, int32_t* cur_ids, int32_t* pos
                             const emu_sample_params* params, const ScoreSel* score, const emu_token_trie* trie, int32_t* node,
                             int ngram, emu_stream_t s) {
     const emu_llama_cfg& c = m->cfg;
+    if (m->prefix_len > 0) return fail(m->ctx, -22, "token step: a KV prefix serves emu_llama_forward with T > 1 only");   // before the first launch
     TRY(m->ctx, launch_embed_gather(cur_ids, m->embed, B(hidden), Bn, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward(m, hidden, Bn, 1, pos, slot, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, Bn, logits, ld_logits, workspace, ws_bytes, s));
@@ -1963,6 +2014,7 @@ static int llama_lookup_step(emu_llama* m, int T, int32_t* cur, int32_t* amax, i
         hist_cap < 1)
         return -22;                                  // refused before anything is launched
     if (params && (ld_logits < c.vocab || !lookup_sample_ok(c.vocab, params, uniforms, uni_rows))) return -22;       // likewise
+    if (m->prefix_len > 0) return fail(m->ctx, -22, "lookup step: a KV prefix serves emu_llama_forward with T > 1 only");
     TRY(m->ctx, launch_embed_gather(cur, m->embed, B(hidden), T, c.hidden, c.vocab, S(s)));
     TRY(m->ctx, emu_llama_forward_chunk(m, hidden, 1, T, pos0, slot0, kstart, ctx_dev, ctx_upper, workspace, ws_bytes, s));
     TRY(m->ctx, emu_llama_logits(m, hidden, c.hidden, T, logits, ld_logits, workspace, ws_bytes, s));

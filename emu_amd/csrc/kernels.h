@@ -351,6 +351,22 @@ struct FlashArgs {
 };
 int launch_flash_attn(const FlashArgs& a, hipStream_t s);
 
+// Two-segment flash attention (attention_prefix.hip), D = 128: query i of row b attends the prefix keys [kstart, P) -- one K / V^T per
+// head, common to all B rows -- and its row's own keys j <= i + (Sk - Sq).  flash_kernel's tile arithmetic; prefix tiles first.
+struct FlashPrefixArgs {
+    const bf16_t* q; long q_sb, q_sh, q_ss;    // [B, H, Sq, D] by element strides; d contiguous
+    const bf16_t* kp; long kp_sh, kp_ss;       // prefix K [H, P, D]
+    const bf16_t* vtp;                         // prefix V^T [H, D, P_pad], zero padded
+    const bf16_t* ko; long ko_sb, ko_sh, ko_ss; // own K [B, H, Sk, D]
+    const bf16_t* vto;                         // own V^T [B, H, D, Sk_pad], zero padded
+    bf16_t* o; long o_sb, o_sh, o_ss;
+    const int32_t* kstart_dev;                 // device int32 [>= 1] or null: element 0 overrides kstart (the engine's left-pad count)
+    int kstart;                                // prefix keys < kstart are masked; 0 <= kstart < P
+    int B, H, Sq, P, P_pad, Sk, Sk_pad, D;
+    float scale;
+};
+int launch_flash_attn_prefix(const FlashPrefixArgs& a, hipStream_t s);
+
 struct DecodeAttnArgs {
     const bf16_t* q; long q_sb, q_sh;          // [B, H, D] strided
     const bf16_t* kcache;                      // [B, H, S_max, D]

@@ -393,6 +393,48 @@ class EmuModel:
         return self.score_ids(inputs.input_ids, inputs.attention_mask, image, video, cont.input_ids, cont.attention_mask.bool(),
                               via=via, use_graph=use_graph, reference_logits=reference_logits, return_logits=return_logits)
 
+    @torch.no_grad()
+    def score_candidates_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor] = None,
+                             video: Optional[torch.Tensor] = None, cand_ids: Optional[torch.Tensor] = None,
+                             cand_mask: Optional[torch.Tensor] = None, n_segments: int = 1, via: str = "prefill",
+                             share_prefix: bool = False):
+        """Rank N candidate continuations ``cand_ids`` / ``cand_mask`` [N, Tc] (right padded) of ONE prompt ``input_ids`` /
+        ``attention_mask`` [1, S] (``image`` / ``video`` scattered into its placeholder slots as for ``generate_ids``): the
+        per-token log-probabilities of ``LlamaEngine.score_continuations`` with ``generate``'s positions.  The prompt is prefilled
+        once; ``share_prefix=True`` also keeps its cache in one place (no copy per candidate).  Returns (lp [N, Tc] fp32, counted
+        [N, Tc] bool).  The reference's Emu2 has no ranking call (Emu1's is prediction_mixin.py:36-131)."""
+        if cand_ids is None:
+            raise ValueError("score_candidates_ids: cand_ids is required")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError(f"score_candidates_ids: one prompt at a time, input_ids must be [1, S], got {tuple(input_ids.shape)}")
+        S = input_ids.shape[1]
+        x = self._prompt_embeds(input_ids, image, self.n_query, IMAGE_TOKEN_ID)
+        if video is not None:
+            x = self._prompt_embeds(input_ids, video, self.v_query, gIMG_TOKEN_ID, embeds=x)
+        return self.decoder.lm.score_continuations(x.view(1, S, -1), attention_mask, cand_ids, cand_mask, n_segments=n_segments,
+                                                   via=via, hf_generate_positions=True, share_prefix=share_prefix)
+
+    @torch.no_grad()
+    def score_candidates(self, text: str, candidates: List[str], image: Optional[torch.Tensor] = None,
+                         video: Optional[torch.Tensor] = None, image_placeholder: str = DEFAULT_IMG_PLACEHOLDER,
+                         video_placeholder: str = DEFAULT_VID_PLACEHOLDER, n_segments: int = 1, via: str = "prefill",
+                         share_prefix: bool = False):
+        """``score_candidates_ids`` on text: the prompt is tokenised as ``score`` tokenises its prompts, the candidates right padded
+        without special tokens.  Returns a dict of ``lp`` / ``counted`` [N, Tc] and, per candidate, ``sum`` (the log-probability of
+        the whole candidate) and ``mean`` (per counted token) [N]."""
+        tok = self.decoder.tokenizer
+        text = text.replace(image_placeholder, self.image_placeholder).replace(video_placeholder, self.video_placeholder)
+        inputs = tok([text], padding="longest", return_tensors="pt")
+        side, tok.padding_side = tok.padding_side, "right"
+        try:
+            cand = tok(list(candidates), padding="longest", return_tensors="pt", add_special_tokens=False)
+        finally:
+            tok.padding_side = side
+        lp, counted = self.score_candidates_ids(inputs.input_ids, inputs.attention_mask, image, video, cand.input_ids,
+                                                cand.attention_mask.bool(), n_segments=n_segments, via=via, share_prefix=share_prefix)
+        total = torch.where(counted, lp, torch.zeros_like(lp)).sum(dim=-1)
+        return {"lp": lp, "counted": counted, "sum": total, "mean": total / counted.sum(dim=-1).clamp(min=1)}
+
     # ------------------------------------------------------------------ generate_image (emu.py:92-153)
     @torch.no_grad()
     def generate_image_ids(self, prompt_ids: torch.Tensor, image: Optional[torch.Tensor] = None,

@@ -358,13 +358,14 @@ class Emu:
     @torch.no_grad()
     def predict_ids(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, image: Optional[torch.Tensor],
                     cand_ids: torch.Tensor, cand_mask: torch.Tensor, n_segments: int = 1, via: str = "prefill",
-                    return_losses: bool = False):
+                    return_losses: bool = False, share_prefix: bool = False):
         """``_predict`` (prediction_mixin.py:36-131) at the token-id level: ONE prompt ``input_ids`` / ``attention_mask`` [1, S]
         (its <image> slots take the visual tokens of ``image``), candidates ``cand_ids`` / ``cand_mask`` [N, Tc] right padded.  The
         loss of a candidate is the reference's (``scoring.reference_candidate_losses``: mean over ALL shifted positions of its
         segment's padded width); positions are arange, as the reference calls ``lm(...)`` without position ids.  The prompt is
         prefilled once, not once per candidate.  Returns the candidate indices by ascending loss, [1, N] int64 (``return_losses``:
-        also the losses [N] fp32)."""
+        also the losses [N] fp32).  ``share_prefix``: ``LlamaEngine.score_continuations``'s option of that name (no N-fold copy of the
+        prompt's cache; off by default)."""
         if input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError(f"predict_ids: one prompt at a time, input_ids must be [1, S], got {tuple(input_ids.shape)}")
         N = cand_ids.shape[0]
@@ -372,7 +373,8 @@ class Emu:
         S = input_ids.shape[1]
         x = self._prompt_embeds(input_ids, image)
         lp, counted = self.lm.score_continuations(x, attention_mask, cand_ids, cand_mask, n_segments=n_segments, via=via,
-                                                  hf_generate_positions=False)
+                                                  hf_generate_positions=False,
+                                                  **({"share_prefix": True} if share_prefix else {}))      # off: the call as it was
         lp, counted = lp.cpu(), counted.cpu()
         losses = torch.empty(N, dtype=torch.float32)
         for a, b in segments:
@@ -383,10 +385,11 @@ class Emu:
         return (ranks, losses) if return_losses else ranks
 
     @torch.no_grad()
-    def predict(self, samples, candidates, n_segments=1):
+    def predict(self, samples, candidates, n_segments=1, share_prefix=False):
         """prediction_mixin.py:5-34: rank ``candidates`` (strings) as answers to ``samples["prompt"]`` / ``samples["image"]`` by LM
         loss, best first: [1, n_cands] int64.  A list of lists of candidates = one list per sample; the results are concatenated
-        ([n_samples, n_cands]; a plain list of lists when the lists differ in length, as the reference's)."""
+        ([n_samples, n_cands]; a plain list of lists when the lists differ in length, as the reference's).
+        ``share_prefix``: as ``predict_ids``."""
         if self.tokenizer is None:
             raise RuntimeError("set Emu.tokenizer (LlamaTokenizer + [PAD],[IMG],[/IMG],<image>) to use the text API")
         if type(candidates[0]) in (list, tuple):
@@ -395,14 +398,14 @@ class Emu:
                 one = {"image": samples["image"][i].unsqueeze(0)}
                 if "prompt" in samples.keys():
                     one["prompt"] = [samples["prompt"][i]]
-                results.append(self._predict(one, candidates[i], n_segments))
+                results.append(self._predict(one, candidates[i], n_segments, share_prefix))
             try:
                 return torch.cat(results, dim=0)
             except RuntimeError:
                 return [res.tolist()[0] for res in results]
-        return self._predict(samples, candidates, n_segments)
+        return self._predict(samples, candidates, n_segments, share_prefix)
 
-    def _predict(self, samples, candidates, n_segments):
+    def _predict(self, samples, candidates, n_segments, share_prefix=False):
         tok = self.tokenizer
         prompt = samples["prompt"] if "prompt" in samples.keys() else getattr(self, "prompt", None)
         if prompt is None:
@@ -419,4 +422,5 @@ class Emu:
         if pad_id is not None:
             mask = mask & (out.input_ids != pad_id)                      # prediction_mixin.py:110-112
         assert out.input_ids.shape[0] == N
-        return self.predict_ids(enc.input_ids[:1], enc.attention_mask[:1], samples.get("image"), out.input_ids, mask, n_segments)
+        return self.predict_ids(enc.input_ids[:1], enc.attention_mask[:1], samples.get("image"), out.input_ids, mask, n_segments,
+                                share_prefix=share_prefix)

@@ -21,7 +21,7 @@ from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
 from .sampling import beam_draw_margin, beam_reference_select, beam_scorer_step, beam_start_state, beam_topk
-from .scoring import IGNORE_INDEX, split_segments
+from .scoring import IGNORE_INDEX, shared_prefix_plan, split_segments
 from .tp import ShardPlan
 
 BF16 = torch.bfloat16
@@ -713,9 +713,11 @@ class LlamaEngine:
         return cap
 
     def alloc_kv(self, batch: int, s_max: int, zero: bool = True, which: str = "main") -> None:
-        """Make a cache of ``batch`` rows x ``s_max`` slots the engine's current one.  Two caches persist side by side, the
-        "main" one (prefill, greedy / sampling) and the "beam" one (``fan_out_kv``: prompts x beams rows), each re-used while its
-        shape stays the same: the pointers a captured hipGraph holds stay valid from call to call."""
+        """Make a cache of ``batch`` rows x ``s_max`` slots the engine's current one.  Three caches persist side by side, the
+        "main" one (prefill, greedy / sampling), the "beam" one (``fan_out_kv``: prompts x beams rows) and the "suffix" one (the
+        candidates' own few slots behind a shared prompt: ``score_continuations(share_prefix=True)``), each re-used while its
+        shape stays the same: the pointers a captured hipGraph holds stay valid from call to call.  A KV prefix
+        (``set_kv_prefix``) does not survive a change of cache."""
         slots = self.__dict__.setdefault("_kv_slots", {})
         cur = slots.get(which)
         if cur is None or cur[2] != batch or cur[3] != s_max:
@@ -730,19 +732,22 @@ class LlamaEngine:
             self._drop_loop_states()                       # graphs captured on the replaced cache are void
         if self.kcache is cur[0]:
             self.set_kv_share(0, 0)
+            self.set_kv_prefix(None, None, 0, 0)
             return
         self.kcache, self.vcache, self.kv_batch, self.s_max = cur
         check(lib().emu_llama_set_kv(self.handle, self.kcache.data_ptr(), self.vcache.data_ptr(), batch, s_max),
               "emu_llama_set_kv")
         self._kv_share = False
+        self._kv_prefix = None                             # (emu_llama_set_kv switched it off)
 
     KV_SHARE_MAX = 8                                   # DECODE_SHARE_MAX of the decode attention kernel
 
     def release_kv(self, which: Optional[str] = None) -> None:
-        """Free the persistent KV caches (``which`` = "main" / "beam" / None for both): alloc_kv keeps the main and the beam cache
+        """Free the persistent KV caches (``which`` = "main" / "beam" / "suffix" / None for all): alloc_kv keeps its caches
         resident for the life of the engine (several GB per rank after one 5-beam search at 60 layers) so that captured graphs stay
         valid; a server that is done with beam search hands the memory back here.  Captured decode graphs are dropped."""
         slots = self.__dict__.get("_kv_slots", {})
+        self.set_kv_prefix(None, None, 0, 0)               # a prefix may point into the cache that goes
         for k in ([which] if which else list(slots)):
             cur = slots.pop(k, None)
             if cur is not None and self.kcache is cur[0]:      # the engine's current cache goes: the next prefill allocates anew
@@ -759,8 +764,29 @@ class LlamaEngine:
         group's first row only (include/emu_hip.h: emu_llama_set_kv_share); (0, 0) = every row owns its slots."""
         if rows_per_prompt <= 1 and not getattr(self, "_kv_share", False):
             return
+        if rows_per_prompt > 1 and getattr(self, "_kv_prefix", None) is not None:
+            raise ValueError("set_kv_share: not while a KV prefix is set (set_kv_prefix(None, None, 0, 0) first)")
         check(lib().emu_llama_set_kv_share(self.handle, int(rows_per_prompt), int(shared_slots)), "emu_llama_set_kv_share")
         self._kv_share = rows_per_prompt > 1
+
+    def set_kv_prefix(self, kprefix: Optional[torch.Tensor], vprefix: Optional[torch.Tensor], prefix_s_max: int,
+                      prefix_len: int) -> None:
+        """While set, ``forward`` with T > 1 attends slots [kstart, prefix_len) of the read-only caches ``kprefix`` / ``vprefix``
+        [L, 1, Hl, prefix_s_max, D] plus the rows' own slots of the current cache (include/emu_hip.h: emu_llama_set_kv_prefix);
+        ``None`` / 0 switches it off.  One-row, chunk and token steps and ``set_kv_share`` are refused meanwhile."""
+        on = kprefix is not None and vprefix is not None and prefix_len > 0
+        if not on and getattr(self, "_kv_prefix", None) is None:
+            return
+        if on:
+            L, Hl, D = self.cfg.num_hidden_layers, self.plan.heads_local, self.cfg.head_dim
+            want = (L, 1, Hl, int(prefix_s_max), D)
+            if tuple(kprefix.shape) != want or tuple(vprefix.shape) != want or not (kprefix.is_contiguous() and vprefix.is_contiguous()) \
+                    or kprefix.dtype != BF16 or vprefix.dtype != BF16:
+                raise ValueError(f"set_kv_prefix: contiguous bf16 caches of shape {want}, got {tuple(kprefix.shape)}")
+        check(lib().emu_llama_set_kv_prefix(self.handle, ops._p(kprefix) if on else None, ops._p(vprefix) if on else None,
+                                            int(prefix_s_max) if on else 0, int(prefix_len) if on else 0),
+              "emu_llama_set_kv_prefix", self.ctx.handle)
+        self._kv_prefix = (kprefix, vprefix, int(prefix_s_max), int(prefix_len)) if on else None      # (keeps the tensors alive)
 
     def fan_out_kv(self, B: int, n: int, S: int, s_max: int, share: bool = True) -> None:
         """After a prefill of B prompts: a cache of B * n rows (n beams / candidates per prompt) that continue the prompts.
@@ -819,6 +845,8 @@ class LlamaEngine:
             raise ValueError("forward_chunk: no tensor-parallel form")
         if getattr(self, "_kv_share", False):
             raise ValueError("forward_chunk: shared-prefix KV rows serve single-token steps only")
+        if getattr(self, "_kv_prefix", None) is not None:
+            raise ValueError("forward_chunk: a KV prefix serves forward with T > 1 only")
         if getattr(self, "decode_fused", 0):
             raise ValueError("forward_chunk: the fused decode modes 1-4 are one-row steps (set_decode_fused(0) first)")
         assert hidden.is_contiguous() and hidden.dtype == BF16 and hidden.shape == (B * T, self.cfg.hidden_size)
@@ -1318,20 +1346,31 @@ class LlamaEngine:
     @torch.no_grad()
     def score_continuations(self, prefix_embeds: torch.Tensor, prefix_mask: torch.Tensor, cand_ids: torch.Tensor,
                             cand_mask: Optional[torch.Tensor] = None, n_segments: int = 1, via: str = "prefill",
-                            hf_generate_positions: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                            hf_generate_positions: bool = True, share_prefix: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Per-token log-probabilities of N candidate continuations ``cand_ids`` [N, Tc] (right padded, ``cand_mask`` [N, Tc]) of
         ONE prefix ``prefix_embeds`` [1, S, hidden]: what prediction_mixin.py:36-131 ranks candidate answers by.  The reference runs
         prompt + candidate through the model for every candidate; here the prompt is prefilled once, its K / V slots are copied to
         the rows of a segment (``fan_out_kv``'s copy), and ``score`` runs the candidates on top.  The segments are the reference's
         (``scoring.split_segments``); each is scored to the width of its own longest candidate.  ``hf_generate_positions``: as
         ``prefill``'s (False = arange positions, the bare ``lm(...)`` call of the reference's ``predict``).  Returns (lp [N, Tc]
-        fp32, counted [N, Tc] bool)."""
+        fp32, counted [N, Tc] bool).
+
+        ``share_prefix=True`` (opt-in; ``via="prefill"``, one rank, head_dim 128): no copy.  The prompt's K / V stay in the main
+        cache, a segment's candidates write their own few slots into the small "suffix" cache (``scoring.shared_prefix_plan`` has
+        the shapes and bytes of both routes) and the two-segment flash kernel attends both (``set_kv_prefix``).  With S a multiple of
+        64 the result is bit-identical to the copying route's, else it agrees to bf16 rounding (another tile partition)."""
         if prefix_embeds.dim() != 3 or prefix_embeds.shape[0] != 1:
             raise ValueError(f"score_continuations: prefix_embeds must be [1, S, hidden], got {tuple(prefix_embeds.shape)}")
         if cand_ids.dim() != 2 or cand_ids.shape[0] < 1:
             raise ValueError(f"score_continuations: cand_ids must be [N, Tc], got {tuple(cand_ids.shape)}")
         N, Tc = cand_ids.shape
         segments = split_segments(N, n_segments)
+        if share_prefix and via != "prefill":
+            raise ValueError("score_continuations: share_prefix=True runs via='prefill' only (a one-token step has no two-segment form)")
+        if share_prefix and tp_size_of(self) > 1:
+            raise ValueError("score_continuations: share_prefix=True has no tensor-parallel form (no multi-rank run of it exists)")
+        if share_prefix and self.cfg.head_dim != 128:
+            raise ValueError(f"score_continuations: share_prefix=True needs head_dim 128, got {self.cfg.head_dim}")
         for a, b in segments:                                            # every refusal before any device work
             self._score_args(prefix_embeds.expand(b - a, -1, -1), prefix_mask.expand(b - a, -1), cand_ids[a:b],
                              None if cand_mask is None else cand_mask[a:b], via, None)
@@ -1343,6 +1382,24 @@ class LlamaEngine:
         hidden, kstart, next_pos = self.prefill(prefix_embeds, prefix_mask, s_max, hf_generate_positions)
         first_logits = self.logits(hidden[:, -1, :])
         lp = torch.zeros(N, Tc, device=self.device, dtype=torch.float32)
+        if share_prefix:
+            plan = shared_prefix_plan(N, S, widths, self.cfg.num_hidden_layers, self.plan.heads_local, self.cfg.head_dim, self.kv_capacity)
+            kmain, vmain = self.kcache, self.vcache                      # the prompt's cache: the prefix segment, read only from here on
+            try:
+                for (a, b), w, seg in zip(segments, widths, plan["segments"]):
+                    self.alloc_kv(b - a, seg["suffix_capacity"], zero=False, which="suffix")     # every slot read was written first
+                    self.set_kv_prefix(kmain, vmain, s_max, S)
+                    # the rows' own slots start at 0 (S = 0 below).  The engine runs T > 1 rows behind a prefix, so a segment of
+                    # width 2 (ONE fed token) feeds one more, ignored, token: causal attention keeps it out of the rows before it
+                    tg = targets[a:b, :w]
+                    if w == 2:
+                        tg = torch.cat([tg, torch.full_like(tg[:, :1], IGNORE_INDEX)], dim=1)
+                    r = self._score_on_cache(first_logits.expand(b - a, -1).contiguous(), 0, kstart.expand(b - a).contiguous(),
+                                             next_pos.expand(b - a).contiguous(), tg.contiguous(), via, False, None, False)
+                    lp[a:b, :w] = r["lp"][:, :w]
+            finally:
+                self.set_kv_prefix(None, None, 0, 0)
+            return lp, targets >= 0
         for (a, b), w in zip(segments, widths):
             self.alloc_kv(1, s_max)                                      # back to the prefix's cache: the source of the copy
             self.fan_out_kv(1, b - a, S, s_max, share=False)

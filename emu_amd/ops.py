@@ -557,6 +557,24 @@ def flash_attn(q, k, v, causal: bool, scale: float, kstart=None):
     return o
 
 
+def flash_attn_prefix(q, kp, vp, ko, vo, kstart: int, scale: float, out=None):
+    """Two-segment flash attention (emu_flash_attn_prefix_bf16; the specification is ``scoring.two_segment_attention``): q [B,Sq,H,D],
+    the shared prefix kp / vp [P,H,D] of which keys [kstart, P) count, own keys ko / vo [B,Sk,H,D] (any strides with D contiguous),
+    query i sees own keys j <= i + (Sk - Sq) -> o [B,Sq,H,D] (``out`` if given)."""
+    _req(q, "q"); _req(kp, "kp"); _req(vp, "vp"); _req(ko, "ko"); _req(vo, "vo")
+    B, Sq, H, D = q.shape
+    P, Sk = kp.shape[0], ko.shape[1]
+    o = torch.empty(B, Sq, H, D, device=q.device, dtype=BF16) if out is None else out
+    vtp = transpose_v(vp, 1, H, P, D, 0, vp.stride(1), vp.stride(0))
+    vto = transpose_v(vo, B, H, Sk, D, vo.stride(0), vo.stride(2), vo.stride(1))
+    check(lib().emu_flash_attn_prefix_bf16(_p(q), q.stride(0), q.stride(2), q.stride(1), _p(kp), kp.stride(1), kp.stride(0), _p(vtp),
+                                           _p(ko), ko.stride(0), ko.stride(2), ko.stride(1), _p(vto),
+                                           _p(o), o.stride(0), o.stride(2), o.stride(1), int(kstart),
+                                           B, H, Sq, P, vtp.shape[-1], Sk, vto.shape[-1], D, float(scale), stream(q)),
+          "emu_flash_attn_prefix_bf16")
+    return o
+
+
 def decode_attn(q, kcache, vcache, ctx: int, scale: float, kstart=None, ctx_dev=None, ctx_max: int = 0):
     """q [B,H,D]; caches [B,H,S_max,D] -> o [B,H,D]."""
     _req(q, "q"); _req(kcache, "kcache"); _req(vcache, "vcache")

@@ -506,6 +506,17 @@ int emu_flash_attn_bf16(const void* q, long q_sb, long q_sh, long q_ss, const vo
                         long k_ss, const void* vt, void* o, long o_sb, long o_sh, long o_ss,
                         const int32_t* kstart, int B, int H, int Sq, int Sk, int Sk_pad, int D, int causal,
                         float scale, emu_stream_t s);
+/* Two-segment ("cascade") flash attention, D = 128: B rows of Sq queries behind ONE shared prefix -- candidate ranking, where the
+ * reference runs prompt + candidate through the model once per candidate (Emu1/models/prediction_mixin.py:36-131).  Query i of row b
+ * attends the prefix keys [kstart, P) (kprefix [H, P, D] by kp_sh / kp_ss, vtprefix [H, D, P_pad], common to all rows) and its own
+ * keys j <= i + (Sk - Sq) (k [B, H, Sk, D] strided, vt [B, H, D, Sk_pad]): one online softmax over both segments with
+ * emu_flash_attn_bf16's tile arithmetic, prefix tiles first -- for P a multiple of 64 bit-identical to emu_flash_attn_bf16 on the
+ * concatenated keys.  Both V^T pads are zero (emu_transpose_v_bf16).  -22, nothing written: D != 128, P < 1, kstart outside [0, P),
+ * Sk < Sq, pads that are not multiples of 64 covering P / Sk. */
+int emu_flash_attn_prefix_bf16(const void* q, long q_sb, long q_sh, long q_ss, const void* kprefix, long kp_sh, long kp_ss,
+                               const void* vtprefix, const void* k, long k_sb, long k_sh, long k_ss, const void* vt, void* o,
+                               long o_sb, long o_sh, long o_ss, int kstart, int B, int H, int Sq, int P, int P_pad, int Sk,
+                               int Sk_pad, int D, float scale, emu_stream_t s);
 /* one-query attention over the KV cache (decode step).  ctx_dev (device int32, may be NULL) overrides ctx so a
  * captured graph can be replayed while the context grows; ctx_max sizes the launch. */
 size_t emu_decode_attn_ws_bytes(int B, int H, int D, int ctx_max);
@@ -695,6 +706,16 @@ int emu_llama_set_kv(emu_llama* m, void* kcache, void* vcache, int batch, int s_
  * serves all but the first), and only slots >= shared_slots are per-row.  beams <= 1 switches it off
  * (emu_llama_set_kv does too).  -22 for beams > 8, a batch the group size does not divide, or slots beyond the capacity. */
 int emu_llama_set_kv_share(emu_llama* m, int beams, int shared_slots);
+/* Candidate ranking on a shared prompt (Emu1/models/prediction_mixin.py:36-131: one prompt, N candidate answers): the prompt's keys
+ * and values stay where its prefill left them, kprefix / vprefix [layer, 1, Hl, prefix_s_max, D] (read only), of which slots
+ * [kstart, prefix_len) are attended; the engine's current cache (emu_llama_set_kv) holds only the rows' OWN slots.  While set,
+ * emu_llama_forward with T > 1 writes the rows' K / V at slot[] as always and runs emu_flash_attn_prefix_bf16's kernel over the prefix
+ * plus own slots [0, ctx); a layer's prefix V is transposed once (one row), not once per batch row.  kstart[] must hold the same value
+ * for every row (element 0 is used).  The fused RoPE / V^T prefill epilogues are off.  -22 with a message, before any launch: T == 1,
+ * the chunk step, the token / lookup steps, emu_llama_set_kv_share, the fused decode modes, the two-lane tensor-parallel prefill;
+ * head_dim != 128.  prefix_len = 0 or NULL pointers switch it off (emu_llama_set_kv does too).  emu_llama_workspace_bytes accounts
+ * for the prefix V^T. */
+int emu_llama_set_kv_prefix(emu_llama* m, const void* kprefix, const void* vprefix, int prefix_s_max, int prefix_len);
 /* Parity hook: emu_llama_forward runs decoder layers [l0, l1) only (l1 < 0: through the last; default 0, -1 = all), each on the
  * KV-cache plane of its own index.  The full-size tests feed ONE layer the fp32 oracle's input of that layer (a common input per
  * layer instead of 60 layers of accumulated bf16 rounding); production code never calls it. */
