@@ -74,6 +74,11 @@ class GemvFp8ThinPlanC(C.Structure):
     _fields_ = [(n, i32) for n in ("status", "rows", "mb", "kc", "stages", "lds_bytes", "grid", "block")]
 
 
+class GemmFp8wPlanC(C.Structure):
+    """emu_gemm_fp8w_plan_t (include/emu_hip.h)."""
+    _fields_ = [(n, i32) for n in ("status", "form", "bm", "kc", "stages", "lds_bytes", "grid", "block")]
+
+
 class TokenTrieC(C.Structure):
     """emu_token_trie (include/emu_hip.h): the flat tables of emu_amd.constrain.TokenTrie on the device."""
     _fields_ = [("first", vp), ("tok", vp), ("child", vp), ("nodes", i32), ("edges", i32)]
@@ -130,9 +135,11 @@ _PROTOS = {
     "emu_gemv_thin_plan": (i32, [vp, i32, vp]),
     "emu_gemv_pack_thin_plan": (i32, [vp, i32, i32, vp]),
     "emu_gemv_fp8_thin_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_gemm_fp8w_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_linear_fp8w_gemm_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_mxfp4_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
     "emu_linear_fp4w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -13,8 +13,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libemu_hip.so")
-SOURCES = ["gemv.hip", "gemv_pack.hip", "gemv_pack_thin.hip", "bf16_pack.hip", "gemv_fp4.hip", "gemv_fp4_thin.hip", "gemv_fp8_thin.hip", "gemv_merge.hip", "gemv_thin.hip", "gemm_fp4.hip", "decode_layer.hip", "decode_engine.hip", "gemm.hip", "gemm256.hip", "gemm_w4.hip", "attention.hip", "attention_prefix.hip", "beam.hip", "beam_sample.hip", "contrastive.hip", "lookup.hip", "elementwise.hip", "sample.hip", "score.hip", "image.hip", "unet.hip", "p2p.hip", "engine.hip", "unet_engine.hip"]
-HEADERS = ["common.h", "kernels.h", "beam_common.h", "sample_common.h", "trie.h", "ngram.h", "gemm_tile.h", "fp4_tile.h", "l2_warm.h", "bf16_pack.h", "thin_stream.h", os.path.join("..", "..", "include", "emu_hip.h")]
+SOURCES = ["gemv.hip", "gemv_pack.hip", "gemv_pack_thin.hip", "bf16_pack.hip", "gemv_fp4.hip", "gemv_fp4_thin.hip", "gemv_fp8_thin.hip", "gemv_merge.hip", "gemv_thin.hip", "gemm_fp4.hip", "gemm_fp8.hip", "decode_layer.hip", "decode_engine.hip", "gemm.hip", "gemm256.hip", "gemm_w4.hip", "attention.hip", "attention_prefix.hip", "beam.hip", "beam_sample.hip", "contrastive.hip", "lookup.hip", "elementwise.hip", "sample.hip", "score.hip", "image.hip", "unet.hip", "p2p.hip", "engine.hip", "unet_engine.hip"]
+HEADERS = ["common.h", "kernels.h", "beam_common.h", "sample_common.h", "trie.h", "ngram.h", "gemm_tile.h", "fp4_tile.h", "fp8_tile.h", "l2_warm.h", "bf16_pack.h", "thin_stream.h", os.path.join("..", "..", "include", "emu_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

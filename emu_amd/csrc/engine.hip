@@ -99,18 +99,21 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
                  const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr;
                  PackSet pk; int pkN = 0, pkK = 0; };
-enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel, emu_llama_pack_thin_kernel)
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8, Fp8Stream = 9 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel, emu_llama_pack_thin_kernel)
 // The one rule that picks a LLaMA projection's kernel, layers and head alike, from integers only: the modes as emu_llama_use_fp8 /
 // emu_llama_use_fp4 set them (never both), the call's rows, the shard's reduction widths.  1..2 rows: the weight streams with the
 // RMSNorm in front (gemv_fp4.hip, gemv.hip); 3..16: the MXFP4 matrix-core stream (gemv_fp4_thin.hip), or the fp8 one
 // (gemv_fp8_thin.hip; fp8 modes 3 / 4 = 1 / 2 plus this stream, whole 256-element k stages); 17 and more: the 4-bit GEMM
-// (gemm_fp4.hip), or W8A8 GEMMs on the block-scaled MFMA (twice the bf16 rate, BASELINE configs[4]; whole 128-element k tiles)
+// (gemm_fp4.hip), or W8A8 GEMMs on the block-scaled MFMA (twice the bf16 rate, BASELINE configs[4]; whole 128-element k tiles);
+// fp8 modes 5 / 6 = 3 / 4 plus 17..64 rows on the fp8 W8A16 GEMM (gemm_fp8.hip, the same whole 256-element k stages)
 WeightKernel weight_kernel(int fp8_mode, int fp4_mode, int rows, int H, int HD, int Fl) {
     if (rows <= 2) return fp4_mode >= 1 ? WeightKernel::Fp4Rows : fp8_mode >= 1 ? WeightKernel::Fp8Rows : WeightKernel::Bf16;
     if (rows <= 16)
         return fp4_mode >= 2 ? WeightKernel::Fp4Thin
                : fp8_mode >= 3 && !(H & 255) && !(HD & 255) && !(Fl & 255) ? WeightKernel::Fp8Thin : WeightKernel::Bf16;
     if (fp4_mode == 3) return WeightKernel::Fp4Gemm;
+    if (fp8_mode >= 5 && rows <= 64 && !(H & 255) && !(HD & 255) && !(Fl & 255)) return WeightKernel::Fp8Stream;
+    fp8_mode -= fp8_mode >= 5 ? 2 : 0;
     return (fp8_mode == 2 || fp8_mode == 4) && !(H & 127) && !(HD & 127) && !(Fl & 127) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
 }
 // The one further rule: a bf16 projection streams the 13-bit packed set (gemv_pack.hip) instead -- same bits, 13/16 of the bytes --
@@ -138,11 +141,12 @@ WeightKernel pack_thin_kernel(WeightKernel k, int rows, int pack_rows, int set_n
 // Fp4Gemm 17 and more (no fused norm; K >= 256, K % 32 == 0).  Fp8Gemm needs the caller's quantised rows (linear_q8): not served here.
 // Fp8Thin: 1..16 rows of the fp8 set on the matrix cores (no fused norm; K >= 256, K % 256 == 0), priced at its N * K bytes.
 // Fp8Thin and Fp4Thin go through launch_gemv_thin_stream (gemv.hip: shape, gemv_thin_plan, pointer checks, launch), which refuses.
+// Fp8Stream: 17..64 rows of the fp8 set (gemm_fp8.hip; the same requirements and price), through launch_gemm_fp8w_stream, which refuses.
 int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
-    if (k == WeightKernel::Fp8Thin) {
+    if (k == WeightKernel::Fp8Thin || k == WeightKernel::Fp8Stream) {
         if (!w.W8 || !w.s8) return -22;
         g.W = B(w.W8); g.wscale = w.s8;
-        return gemv_profiled((double)g.N * (double)g.K, s, [&] { return launch_gemv_thin_stream(g, s); });
+        return gemv_profiled((double)g.N * (double)g.K, s, [&] { return k == WeightKernel::Fp8Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp8w_stream(g, s); });
     }
     if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows) {
         const bool f8 = k == WeightKernel::Fp8Rows;
@@ -487,6 +491,12 @@ int emu_linear_fp8w_thin_bf16(const void* A, const void* W8, const float* wscale
     return linear_w(WeightKernel::Fp8Thin, {nullptr, U8(W8), wscale},
                     {B(A), nullptr, nullptr, B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, 0.f, epi}, S(s));
 }
+int emu_linear_fp8w_gemm_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s) {
+    if (!A || !W8 || !wscale || !C) return -22;
+    return linear_w(WeightKernel::Fp8Stream, {nullptr, U8(W8), wscale},
+                    {B(A), nullptr, nullptr, B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, 0.f, epi}, S(s));
+}
 // the four MXFP4 entry points name their kernel (the caller's matrix as a weight record, its arguments as the launch block);
 // linear_w refuses a row count outside the kernel's range
 static int linear_fp4w(WeightKernel k, const void* A, const void* W4, const void* scales, const void* bias, const void* res, const void* norm_w,
@@ -724,7 +734,8 @@ struct emu_llama {
     Weights head;                  // lm_head: the fp8 / MXFP4 copies cover the same rows (quantised from the shard)
     bool fp8_decode = false;       // emu_llama_use_fp8(m, 1 | 2): 1..2 rows stream the fp8 set
     bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2 | 4): W8A8 GEMMs for prefill rows as well
-    bool fp8_wide = false;         // emu_llama_use_fp8(m, 3 | 4): steps of 3..16 rows stream the fp8 set too, on the matrix cores
+    bool fp8_wide = false;         // emu_llama_use_fp8(m, 3 .. 6): steps of 3..16 rows stream the fp8 set too, on the matrix cores
+    bool fp8_mid = false;          // emu_llama_use_fp8(m, 5 | 6): and so do steps of 17..64 rows (gemm_fp8.hip)
     // emu_llama_use_fp4 (exclusive with the fp8 stream): 1..2 rows stream the MXFP4 set; fp4_wide (mode 2) steps of 3..16 rows too, on
     // the matrix cores; fp4_all (mode 3) the calls of 17 rows and more run the 4-bit GEMM.  Every other row count keeps the bf16 weights.
     // bf16_released (emu_llama_release_bf16; mode 3 only, which it pins): the records' bf16 pointers are null.
@@ -736,7 +747,7 @@ struct emu_llama {
     bool bf16_pack_wide = false;   // emu_llama_use_bf16_pack_wide: so do their 4..16-row steps (pack_thin_kernel)
     // the kernel of a projection of `rows` rows, layers and head alike: the modes above through weight_kernel
     WeightKernel kernel_for(int rows) const {
-        return weight_kernel(fp8_decode ? 1 + (fp8_prefill ? 1 : 0) + (fp8_wide ? 2 : 0) : 0, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
+        return weight_kernel(fp8_decode ? 1 + (fp8_prefill ? 1 : 0) + (fp8_wide ? 2 : 0) + (fp8_mid ? 2 : 0) : 0, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
                              cfg.heads_local * cfg.head_dim, cfg.ffn_local);
     }
     const bf16_t *final_norm = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
@@ -858,7 +869,7 @@ struct LlamaPlan {
     // fuse_rope      the qkv GEMM's epilogue rotates q / k, appends k / v and writes V^T (demoted for the rest of the call on -95)
     // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
     // kernel         the weight set and kernel of the call's projections (weight_kernel).  Fp8Gemm: in the layers that have fp8
-    //                weights.  Fp4Thin, Fp8Thin: norms stay launches.  Fp4Gemm: norms, RoPE / KV append and V^T stay launches -- fuse_rope and
+    //                weights.  Fp4Thin, Fp8Thin: norms stay launches.  Fp4Gemm, Fp8Stream: norms, RoPE / KV append and V^T stay launches -- fuse_rope and
     //                fuse_norm are off and the call never takes TwoLane
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
@@ -918,13 +929,14 @@ struct LlamaCall {
         // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
         // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
         p.kernel = m->kernel_for(M);
-        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && p.kernel != WeightKernel::Fp4Gemm;
+        const bool byte_gemm = p.kernel == WeightKernel::Fp4Gemm || p.kernel == WeightKernel::Fp8Stream;   // no bf16 GEMM to carry an epilogue fusion
+        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && !byte_gemm;
         // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
         // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
         // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
         // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
         // with B * beams > 16) keep the fused path they had before the promise became one-shot.
-        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && p.kernel != WeightKernel::Fp4Gemm;
+        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && !byte_gemm;
         p.norm_in_gemv = p.kernel == WeightKernel::Fp8Rows || p.kernel == WeightKernel::Fp4Rows || M == 1;
         p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
         // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
@@ -1033,7 +1045,7 @@ struct LlamaCall {
     int layer_kv(const RowWindow& win, int l, const LaneHook& after_norm = nullptr) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        if ((plan.kernel == WeightKernel::Fp8Rows || plan.kernel == WeightKernel::Fp8Thin) && !L.qkv.W8)
+        if ((plan.kernel == WeightKernel::Fp8Rows || plan.kernel == WeightKernel::Fp8Thin || plan.kernel == WeightKernel::Fp8Stream) && !L.qkv.W8)
             return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
         // after emu_llama_release_bf16 the 4-bit set is the layer's weights (mode 3 is pinned: every row count has a 4-bit path)
         if (m->bf16_released ? !L.qkv.W4 || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
@@ -1583,7 +1595,7 @@ int emu_llama_set_tp_overlap(emu_llama* m, int min_rows) {
 long emu_llama_tp_overlap_count(const emu_llama* m) { return m ? m->ov_forwards : -1; }
 int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (!m) return -22;
-    if (enable < 0 || enable > 4) return fail(m->ctx, -22, "emu_llama_use_fp8: modes 0 to 4");
+    if (enable < 0 || enable > 6) return fail(m->ctx, -22, "emu_llama_use_fp8: modes 0 to 6");
     if (enable && m->bf16_released)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
     if (enable && m->fp4_decode)
@@ -1594,13 +1606,14 @@ int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (enable >= 3) {
         const emu_llama_cfg& c = m->cfg;
         if ((c.hidden & 255) || ((c.heads_local * c.head_dim) & 255) || (c.ffn_local & 255))
-            return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 and 4 (steps of 3..16 rows on the fp8 set) need reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
+            return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 to 6 (steps of 3..16 / 17..64 rows on the fp8 set) need reduction widths (hidden, heads_local * head_dim, ffn_local) that are multiples of 256");
         if (std::any_of(m->layers.begin(), m->layers.end(), [](const emu_llama::Layer& l) { return !l.qkv.W8; }))
-            return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 and 4 need the fp8 weights of every layer");
+            return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 to 6 need the fp8 weights of every layer");
     }
     m->fp8_decode = enable != 0;
-    m->fp8_prefill = enable == 2 || enable == 4;
+    m->fp8_prefill = enable == 2 || enable == 4 || enable == 6;
     m->fp8_wide = enable >= 3;
+    m->fp8_mid = enable >= 5;
     return 0;
 }
 int emu_llama_set_head(emu_llama* m, const void* final_norm, const void* lm_head, const void* embed, const void* rope_cos,
@@ -1863,7 +1876,7 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
     const int H = c.hidden;
     const bool ws_fits = ws_bytes >= (size_t)M * H * 2;
     WeightKernel k = m->kernel_for(M);
-    if (k == WeightKernel::Fp8Gemm || ((k == WeightKernel::Fp8Rows || k == WeightKernel::Fp8Thin) && !m->head.W8) ||
+    if (k == WeightKernel::Fp8Gemm || ((k == WeightKernel::Fp8Rows || k == WeightKernel::Fp8Thin || k == WeightKernel::Fp8Stream) && !m->head.W8) ||
         (k == WeightKernel::Fp8Thin && !ws_fits) || (k == WeightKernel::Fp4Thin && !ws_fits && !m->bf16_released)) k = WeightKernel::Bf16;
     const bool fused = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp8Rows || (k == WeightKernel::Bf16 && (M == 1 || (M <= 8 && !ws_fits)));
     if (fused) k = pack_kernel(k, M, m->head.pkN == N && m->head.pkK == H ? m->head.pk.rows : 0, m->bf16_pack, m->decode_fused, m->decode_tail, m->l2_warm,

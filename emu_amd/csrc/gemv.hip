@@ -1062,6 +1062,32 @@ int launch_gemv_thin_stream(const GemvArgs& a, hipStream_t s) {
 }
 bool fp4_mfma_ok(const GemvArgs& a) { return a.M >= 17 && fp4_mfma_shape_ok(gemv_shape_of(a)) && mfma_pointers_ok(a); }
 
+// The fp8 W8A16 GEMM of 17..64 rows (gemm_fp8.hip): 64 weight rows per workgroup, the activation rows in one tile of bm = 32 (narrow,
+// up to 32 rows) or 64, K in whole stages of 256 through a ring of `stages` stages.  What it asks of a shape is what the fp8 few-row
+// stream asks (gemv_thin_plan), the row count aside.  Ring depth: as deep as a CU's 160 KiB of LDS hold for one workgroup (narrow 4 x
+// 32 KiB, one tile 3 x 48 KiB); emu_gemm_tune bit 20 gives the narrow form a ring of 2 (64 KiB: two workgroups per CU), the A/B twin
+// (tools/fp8_mid_time.py --ab, profiles/fp8_mid.md).
+GemmFp8wPlan gemm_fp8w_plan(const GemvShape& sh, int tune) {
+    GemmFp8wPlan refused{};
+    refused.status = -22;
+    if (!sh.fp8 || sh.fp4 || sh.norm || !sh.w_aligned || !sh.x_aligned || sh.M < 17 || sh.M > 64 || sh.N < 1 || sh.K < 256 || (sh.K % 256) ||
+        (sh.ldx & 7) || (sh.ldw & 15) || sh.ldw < sh.K || sh.ldx < sh.K || !epi3_ok(sh))
+        return refused;
+    GemmFp8wPlan p{};
+    p.form = sh.M <= 32 ? 1 : 2;
+    p.bm = sh.M <= 32 ? 32 : 64;
+    p.kc = 256;
+    p.stages = p.form == 2 ? 3 : (tune & (1 << 20)) ? 2 : 4;
+    p.lds_bytes = p.stages * (64 * p.kc + p.bm * p.kc * 2);
+    p.grid = (sh.N + 63) / 64;
+    p.block = 256;
+    return p;
+}
+int launch_gemm_fp8w_stream(const GemvArgs& a, hipStream_t s) {
+    const GemmFp8wPlan p = gemm_fp8w_plan(gemv_shape_of(a), emu_gemm_tune_get());
+    return p.status || !mfma_pointers_ok(a) ? -22 : launch_gemm_fp8w(a, p, s);
+}
+
 // The 13-bit packed twin of the bf16 thin stream (gemv_pack_thin.hip), from the bf16 plan of the same shape: it exists for kch 32.
 // The built tiles, as (weight rows, ring depth: workgroups that share a CU's LDS): up to 8 activation rows (16, 4: 3), (32, 4: 2),
 // (16, 6: 2), (32, 3: 3); up to 16 (16, 3: 3), (32, 3: 2), (16, 5: 2).  The plan is the tile whose grid fills the largest share of its
@@ -1101,6 +1127,12 @@ int emu_gemv_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
 }
 int emu_gemv_thin_plan(const emu_gemv_shape* shape, int tune, emu_gemv_plan_t* out) {
     return shape && out ? (*out = gemv_thin_plan(*shape, tune)).status : -22;
+}
+int emu_gemm_fp8w_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemm_fp8w_plan_t* out) {
+    if (!out) return -22;
+    GemvShape sh{};
+    sh.M = M; sh.N = N; sh.K = K; sh.ldx = ldx; sh.ldw = ldw; sh.epi = epi; sh.fp8 = sh.w_aligned = sh.x_aligned = 1;
+    return (*out = gemm_fp8w_plan(sh, tune)).status;                 // refused: every field but the status is 0
 }
 // the older view of the fp8 few-row plan: row-contiguous or strided operands on aligned buffers, no fused norm
 int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out) {

@@ -36,22 +36,11 @@
 // template arguments, and callers come through gemv.hip::launch_gemv_thin_stream.
 #include "common.h"
 #include "kernels.h"
-#include "fp4_tile.h"
+#include "fp8_tile.h"                                   // F8_* stage constants and cvt8_e4m3, shared with gemm_fp8.hip
 
 using namespace emu_gemm;
 
 namespace {
-
-constexpr int F8_KC = 256, F8_WROW = F8_KC, F8_XROW = F8_KC * 2;     // k per stage; bytes per staged weight / activation row
-
-// two dwords of e4m3 bytes (8 codes, byte j = element j) -> the 8 bf16 of an MFMA fragment
-__device__ __forceinline__ bf16x8_t cvt8_e4m3(uint32_t d0, uint32_t d1) {
-    const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, false);
-    const bf16x2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, 1.0f, true);
-    const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, false);
-    const bf16x2_t p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, 1.0f, true);
-    return bf16x8_t{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-}
 
 template <int EPI, int RN, int MR, int NSTG>
 __global__ __launch_bounds__(256) void fp8_thin_kernel(const GemvArgs a) {

@@ -114,6 +114,14 @@ inline int fp4_scale_stride(int K) { return K % 256 == 0 ? K / 32 : 8 * ((K + 25
 // norm, epi NONE / RESID / SWIGLU -- and the same pointer checks
 bool fp4_mfma_ok(const GemvArgs& a);
 int launch_gemm_fp4(const GemvArgs& a, hipStream_t s);
+// fp8 weights (a.wscale set; W = e4m3 bytes, ldw in bytes) for 17..64 rows on the matrix cores, W8A16 (gemm_fp8.hip: the tile of
+// gemm_fp4.hip fed as gemv_fp8_thin.hip is fed; fp8_tile.h).  gemm_fp8w_plan (gemv.hip): pure host arithmetic from a shape to the form,
+// the ring depth and the grid, or status -22 (the C-ABI test hook emu_gemm_fp8w_plan returns the same); launch_gemm_fp8w: the switch
+// from a plan to template arguments; launch_gemm_fp8w_stream: shape -> plan -> the checks only pointers can answer -> one launch.
+using GemmFp8wPlan = emu_gemm_fp8w_plan_t;
+GemmFp8wPlan gemm_fp8w_plan(const GemvShape& shape, int tune);
+int launch_gemm_fp8w(const GemvArgs& a, const GemmFp8wPlan& p, hipStream_t s);
+int launch_gemm_fp8w_stream(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

@@ -182,6 +182,7 @@ class EmuHipContext:
 class LlamaEngine:
     fp4_all = False            # use_fp4(True, wide=True, all_rows=True) is on: every row count runs the 4-bit set
     bf16_released = False      # release_bf16() was called: the bf16 matrices and lm_head are gone, fp4_all is pinned
+    fp8_mid = False            # use_fp8(True, wide=True, mid=True) is on: steps of 17..64 rows stream the fp8 set too
 
     def __init__(self, cfg: LlamaCfg, vocab: int, ctx: EmuHipContext):
         self.cfg, self.vocab, self.ctx = cfg, vocab, ctx
@@ -554,7 +555,7 @@ class LlamaEngine:
         self._fp8["lm_head"] = (q, sc)
         check(lib().emu_llama_set_head_fp8(self.handle, q.data_ptr(), sc.data_ptr()), "emu_llama_set_head_fp8")
 
-    def use_fp8(self, enable: bool = True, prefill: bool = False, wide: bool = False) -> None:
+    def use_fp8(self, enable: bool = True, prefill: bool = False, wide: bool = False, mid: bool = False) -> None:
         """Switch the decode stream between the bf16 and the fp8 weights (invalidates captured decode graphs).  The matrices are
         quantised on the device first (``quantize_fp8``).  Exclusive with ``use_fp4``.
 
@@ -565,14 +566,21 @@ class LlamaEngine:
         on a few candidates) stream the fp8 set as well, through the matrix-core kernel (csrc/gemv_fp8_thin.hip; weight-only: the
         activations stay bf16, as at 1..2 rows); needs hidden, heads_local * head_dim and ffn_local to be multiples of 256 (the
         library refuses otherwise and says why: every TP = 1 / 2 sharding of the 33B shapes runs, the TP = 4 / 8 shards do not).
-        Without ``wide`` those steps stream bf16, as they always did.  Not a reference feature; quality on a trained checkpoint is
-        unmeasured."""
+        Without ``wide`` those steps stream bf16, as they always did.
+        ``wide=True, mid=True``: steps of 17..64 rows (four prompts x five beams, contrastive search on a batch) stream the fp8 set
+        too, through the W8A16 GEMM (csrc/gemm_fp8.hip; activations bf16; a prompt of 17..64 rows runs without the RoPE and RMSNorm
+        epilogue fusions of the bf16 prefill).  Same width requirement as ``wide``; ``mid`` without ``wide`` is a ``ValueError``.
+        Above 64 rows nothing changes: bf16, or the W8A8 GEMMs with ``prefill=True``.  Not a reference feature; quality on a trained
+        checkpoint is unmeasured."""
+        if mid and not wide:
+            raise ValueError("use_fp8: mid=True needs wide=True (modes 5 / 6 are modes 3 / 4 plus the steps of 17..64 rows)")
         if enable and not self.bf16_released:   # (after release_bf16 the library refuses and says why)
             self.quantize_fp8()
-        mode = ((2 if prefill else 1) + (2 if wide else 0)) if enable else 0
+        mode = ((2 if prefill else 1) + (2 if wide else 0) + (2 if mid else 0)) if enable else 0
         check(lib().emu_llama_use_fp8(self.handle, mode), "emu_llama_use_fp8", self.ctx.handle)
         self.fp8_decode = bool(enable)
         self.fp8_wide = bool(enable and wide)
+        self.fp8_mid = bool(enable and mid)
         self._mode_changed()
 
     def fp8_dequantized(self, key: str) -> torch.Tensor:

@@ -294,55 +294,70 @@ def linear_fp8w(x, w8, wscale, bias=None, res=None, norm_w=None, eps: float = 0.
     return out
 
 
-def linear_fp8w_thin(x, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):
-    """``linear`` over an fp8 weight stream (``quantize_fp8_rows``' bytes and row scales) for 1..16 rows on the matrix cores: K >= 256
-    and K % 256 == 0, no fused norm, epi NONE / RESID / SWIGLU; see emu_linear_fp8w_thin_bf16.  Every argument is checked here, before
-    any device work: a ``ValueError`` says what is wrong, nothing falls back to another kernel."""
+def _linear_fp8w_mfma(fn, symbol, lo, hi, beyond, x, w8, wscale, bias, res, epi, out):
+    """The two W8A16 matrix-core entry points (``fn``: the wrapper's name, ``symbol``: its C function) differ in their row range
+    ``lo..hi`` alone; ``beyond``: where a caller with other row counts should go.  Every argument is checked before any device work."""
     for name, t, dt in (("x", x, BF16), ("w8", w8, torch.uint8), ("wscale", wscale, torch.float32), ("bias", bias, BF16),
                         ("res", res, BF16), ("out", out, BF16)):
         if t is None and name in ("bias", "res", "out"):
             continue
         if not isinstance(t, torch.Tensor):
-            raise ValueError(f"linear_fp8w_thin: {name} must be a tensor, got {type(t).__name__}")
+            raise ValueError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
         if t.dtype != dt or t.dim() < 1 or t.stride(-1) != 1:
-            raise ValueError(f"linear_fp8w_thin: {name} must be {dt} and contiguous in its last dimension, got {t.dtype} "
+            raise ValueError(f"{fn}: {name} must be {dt} and contiguous in its last dimension, got {t.dtype} "
                              f"{tuple(t.shape)} with strides {t.stride()}")
     if x.dim() != 2 or w8.dim() != 2 or x.shape[1] != w8.shape[1]:
-        raise ValueError(f"linear_fp8w_thin: x [M, K] and w8 [N, K] must agree in K, got {tuple(x.shape)} and {tuple(w8.shape)}")
+        raise ValueError(f"{fn}: x [M, K] and w8 [N, K] must agree in K, got {tuple(x.shape)} and {tuple(w8.shape)}")
     M, K = x.shape
     N = w8.shape[0]
-    if not 1 <= M <= 16:
-        raise ValueError(f"linear_fp8w_thin: 1..16 rows, got M = {M} (17 rows and more: the W8A8 GEMM, linear_fp8)")
+    if not lo <= M <= hi:
+        raise ValueError(f"{fn}: {lo}..{hi} rows, got M = {M} ({beyond})")
     if N < 1 or K < 256 or K % 256:
-        raise ValueError(f"linear_fp8w_thin: N >= 1 and K a multiple of 256, at least 256; got N = {N}, K = {K}")
+        raise ValueError(f"{fn}: N >= 1 and K a multiple of 256, at least 256; got N = {N}, K = {K}")
     if epi not in (EPI_NONE, EPI_RESID, EPI_SWIGLU):
-        raise ValueError(f"linear_fp8w_thin: epi must be EPI_NONE, EPI_RESID or EPI_SWIGLU, got {epi}")
+        raise ValueError(f"{fn}: epi must be EPI_NONE, EPI_RESID or EPI_SWIGLU, got {epi}")
     if epi == EPI_SWIGLU and N % 2:
-        raise ValueError(f"linear_fp8w_thin: EPI_SWIGLU needs an even N (interleaved gate / up rows), got {N}")
+        raise ValueError(f"{fn}: EPI_SWIGLU needs an even N (interleaved gate / up rows), got {N}")
     if wscale.dim() != 1 or wscale.numel() != N:
-        raise ValueError(f"linear_fp8w_thin: wscale must be fp32 [{N}], got {tuple(wscale.shape)}")
+        raise ValueError(f"{fn}: wscale must be fp32 [{N}], got {tuple(wscale.shape)}")
     if w8.stride(0) % 16 or w8.stride(0) < K or w8.data_ptr() % 16:
-        raise ValueError(f"linear_fp8w_thin: w8 rows must start on 16-byte boundaries (row stride {w8.stride(0)} bytes, "
+        raise ValueError(f"{fn}: w8 rows must start on 16-byte boundaries (row stride {w8.stride(0)} bytes, "
                          f"offset {w8.data_ptr() % 16})")
     if x.stride(0) % 8 or x.stride(0) < K or x.data_ptr() % 16:
-        raise ValueError(f"linear_fp8w_thin: x rows must start on 16-byte boundaries (row stride {x.stride(0)} elements, "
+        raise ValueError(f"{fn}: x rows must start on 16-byte boundaries (row stride {x.stride(0)} elements, "
                          f"offset {x.data_ptr() % 16} bytes)")
     cols = N // 2 if epi == EPI_SWIGLU else N
     if bias is not None and bias.numel() != N:
-        raise ValueError(f"linear_fp8w_thin: bias must be bf16 [{N}], got {tuple(bias.shape)}")
+        raise ValueError(f"{fn}: bias must be bf16 [{N}], got {tuple(bias.shape)}")
     if epi == EPI_RESID and (res is None or tuple(res.shape) != (M, N)):
-        raise ValueError(f"linear_fp8w_thin: EPI_RESID needs res bf16 [{M}, {N}]")
+        raise ValueError(f"{fn}: EPI_RESID needs res bf16 [{M}, {N}]")
     if out is None:
         out = torch.empty(M, cols, device=x.device, dtype=BF16)
     elif tuple(out.shape) != (M, cols):
-        raise ValueError(f"linear_fp8w_thin: out must be bf16 [{M}, {cols}], got {tuple(out.shape)}")
+        raise ValueError(f"{fn}: out must be bf16 [{M}, {cols}], got {tuple(out.shape)}")
     for name, t in (("x", x), ("w8", w8), ("wscale", wscale), ("bias", bias), ("res", res), ("out", out)):
         if t is not None and (not t.is_cuda or t.device != x.device):
-            raise ValueError(f"linear_fp8w_thin: {name} must be a GPU tensor on x's device (emu_amd has no CPU path)")
-    check(lib().emu_linear_fp8w_thin_bf16(_p(x), _p(w8), _p(wscale), _p(bias), _p(res), _p(out), M, N, K, x.stride(0), w8.stride(0),
-                                          res.stride(0) if res is not None else 0, out.stride(0), int(epi), stream(x)),
-          "emu_linear_fp8w_thin_bf16")
+            raise ValueError(f"{fn}: {name} must be a GPU tensor on x's device (emu_amd has no CPU path)")
+    check(getattr(lib(), symbol)(_p(x), _p(w8), _p(wscale), _p(bias), _p(res), _p(out), M, N, K, x.stride(0), w8.stride(0),
+                                 res.stride(0) if res is not None else 0, out.stride(0), int(epi), stream(x)), symbol)
     return out
+
+
+def linear_fp8w_thin(x, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):
+    """``linear`` over an fp8 weight stream (``quantize_fp8_rows``' bytes and row scales) for 1..16 rows on the matrix cores: K >= 256
+    and K % 256 == 0, no fused norm, epi NONE / RESID / SWIGLU; see emu_linear_fp8w_thin_bf16.  Every argument is checked here, before
+    any device work: a ``ValueError`` says what is wrong, nothing falls back to another kernel."""
+    return _linear_fp8w_mfma("linear_fp8w_thin", "emu_linear_fp8w_thin_bf16", 1, 16, "17 rows and more: the W8A8 GEMM, linear_fp8",
+                             x, w8, wscale, bias, res, epi, out)
+
+
+def linear_fp8w_gemm(x, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):
+    """The same product for 17..64 rows (beams x batch): the W8A16 GEMM of csrc/gemm_fp8.hip, same arguments, requirements, epilogues
+    and rounding points as ``linear_fp8w_thin``; see emu_linear_fp8w_gemm_bf16.  Every argument is checked here, before any device
+    work: a ``ValueError`` says what is wrong, nothing falls back to another kernel."""
+    return _linear_fp8w_mfma("linear_fp8w_gemm", "emu_linear_fp8w_gemm_bf16", 17, 64,
+                             "up to 16 rows: linear_fp8w_thin; 65 and more: linear, or the W8A8 GEMM linear_fp8",
+                             x, w8, wscale, bias, res, epi, out)
 
 
 def rmsnorm(x, w, eps: float, out=None):

@@ -152,6 +152,17 @@ typedef struct {
     int status, rows, mb, kc, stages, lds_bytes, grid, block;
 } emu_gemv_fp8_thin_plan_t;
 int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out);
+/* CPU test hook (tests/test_fp8_mid_host.py): what emu_linear_fp8w_gemm_bf16 and the engine's 17..64-row steps under fp8 modes 5 / 6
+ * launch (gemm_fp8.hip) for M rows over an fp8 matrix [N, K] (ldx in bf16 elements, ldw in bytes) on aligned buffers -- host arithmetic
+ * only.  form: 1 narrow (64 weight rows x 32 activation rows, M 17..32), 2 one tile (64 x 64, M 33..64); bm: activation rows of the
+ * tile (32 / 64); kc = 256: k per stage; stages: depth of the LDS ring (narrow 4, one tile 3; tune bit 20 (emu_gemm_tune): narrow 2,
+ * which lets two workgroups share a CU's LDS); lds_bytes = stages * (64 * kc + bm * kc * 2), at most 160 KiB; grid = ceil(N / 64);
+ * block 256.  Returns 0, or -22 (then the other fields are 0): M outside 17..64, N < 1, K < 256 or K % 256 != 0, ldw % 16 or
+ * ldx % 8 != 0, a stride below K, an epilogue other than NONE / RESID / SWIGLU, an odd N under SWIGLU. */
+typedef struct {
+    int status, form, bm, kc, stages, lds_bytes, grid, block;
+} emu_gemm_fp8w_plan_t;
+int emu_gemm_fp8w_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemm_fp8w_plan_t* out);
 /* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bits 0, 4, 5, 14, 17 and 18: retired,
  * ignored.  Bit 1: the K-slice workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before
  * round 3) instead of the XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip)
@@ -161,7 +172,8 @@ int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int t
  * different XCDs); bit 7: it stores O straight from the accumulator layout; bits 12-13: 1 / 2 = attention always on 4 / 8 waves;
  * bit 15: causal attention launches keep the (head, query block) order instead of walking every XCD's heads from the longest query
  * block down; bits 8-11: variant of the thin stream (tools/thin_ab.py); bit 16: no successor-weight prefetch from inside the GEMM
- * kernels; bit 19 (opt-in): a short tensor-parallel shard's one-row step merges the decode attention's splits in the o_proj
+ * kernels; bit 20: the narrow form of the fp8 W8A16 GEMM (gemm_fp8.hip, 17..32 rows) runs a ring of 2 stages instead of 4, so that
+ * two workgroups share a CU's LDS (tools/fp8_mid_time.py --ab); bit 19 (opt-in): a short tensor-parallel shard's one-row step merges the decode attention's splits in the o_proj
  * launch's prologue instead of a combine launch ahead of it (gemv_merge.hip: bit-identical, measured level);
  * bits 21-23 (round 6, the four-wave 256x256 tile of gemm_w4.hip): 21 = never take it (the eight-wave ping-pong
  * tile everywhere: the same-run A/B twin), 22 = take it wherever it is instantiated (tests: bf16 plain GEMMs and convs of the
@@ -233,6 +245,13 @@ int emu_linear_fp8w_bf16(const void* A, const void* W8, const float* wscale, con
  * lda % 8 == 0, both at least K, A / W8 16-byte aligned, N even under SWIGLU; anything else -22, nothing is launched and nothing
  * falls back.  emu_linear_fp8w_bf16 keeps answering -22 for M > 2.  Not a reference feature. */
 int emu_linear_fp8w_thin_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C,
+                              int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s);
+/* The same product, arguments, epilogues, rounding points and requirements for 17 <= M <= 64 rows (gemm_fp8.hip: a workgroup owns 64
+ * weight rows x 32 / 64 activation rows, every converted weight fragment feeds 2 or 4 MFMAs; ragged M and N; emu_gemm_fp8w_plan names
+ * the launch).  M outside 17..64 and every violated requirement: -22, nothing is launched.  It computes what emu_linear_bf16 computes
+ * on the dequantised weights, up to fp32 summation order.  emu_linear_fp8w_thin_bf16 keeps answering -22 for M > 16.  Not a reference
+ * feature. */
+int emu_linear_fp8w_gemm_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C,
                               int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s);
 /* MXFP4 (OCP microscaling) weights, the 4-bit weight-only stream; emu_amd/mxfp4.py is the definition of the format.
  *   elements  uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j+1 in the high nibble; a code is a sign bit (8) and an
@@ -601,6 +620,11 @@ int emu_llama_set_layer(emu_llama* m, int layer, const void* wqkv, const void* w
  * and the head where it has an fp8 copy (whole or emu_llama_set_head_shard rows); the RMSNorm launches of the bf16 few-row path stay,
  * attention is untouched.  Modes 3 and 4 fail (-22, with a message) unless hidden, heads_local*head_dim and ffn_local are multiples
  * of 256 (every TP = 1 / 2 sharding of the 33B shapes; the TP = 4 / 8 shards are refused).  Modes 0..2 are what they were.
+ * emu_llama_use_fp8(m, 5) is mode 3 and (m, 6) is mode 4 plus: every forward / logits call of 17 <= B*T <= 64 rows (beams x batch,
+ * contrastive search on a batch) streams the fp8 set through emu_linear_fp8w_gemm_bf16's kernel, the same projections and head; the
+ * RMSNorm launches stay in front of the projections and a prompt of 17..64 rows runs the unfused RoPE / KV append and V^T launches
+ * (no RoPE epilogue, no K-slice sum + RMSNorm fusion at those row counts).  Above 64 rows mode 5 is mode 3 (bf16) and mode 6 is
+ * mode 4 (W8A8 GEMMs).  Same width and every-layer requirements as modes 3 and 4.  Modes 0..4 are what they were.
  * Accuracy on a trained checkpoint is unmeasured. */
 int emu_llama_set_layer_fp8(emu_llama* m, int layer, const void* wqkv8, const float* sqkv, const void* wo8,
                             const float* so, const void* wgu8, const float* sgu, const void* wdown8,
@@ -636,12 +660,13 @@ int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_sc
 int emu_llama_use_fp4(emu_llama* m, int enable);
 int emu_llama_release_bf16(emu_llama* m);
 /* CPU test hook (tests/test_llama_weight_kernel.py): the one rule by which emu_llama_forward and emu_llama_logits pick a projection's
- * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..4 / fp4_mode 0..3 as emu_llama_use_fp8 /
+ * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..6 / fp4_mode 0..3 as emu_llama_use_fp8 /
  * emu_llama_use_fp4 take them (never both non-zero), rows = B*T of the call, the shard's hidden, heads_local*head_dim and ffn_local.
  * Returns 0 bf16, 1 the fp8 stream (1..2 rows), 2 W8A8 GEMMs (17 rows and more; in the layers that have fp8 weights), 3 the MXFP4
  * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more), 7 the fp8 matrix-core
- * stream (3..16 rows in fp8 modes 3 / 4 when the three widths are multiples of 256; other widths: 0 there) -- 6 is
- * emu_llama_pack_kernel's.  The head runs 2 as bf16. */
+ * stream (3..16 rows in fp8 modes 3 .. 6 when the three widths are multiples of 256; other widths: 0 there), 9 the fp8 W8A16 GEMM
+ * (17..64 rows in fp8 modes 5 / 6, same widths; other widths: 0 there) -- 6 is emu_llama_pack_kernel's, 8
+ * emu_llama_pack_thin_kernel's.  The head runs 2 as bf16. */
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local);
 /* The 13-bit lossless packing of a bf16 weight matrix for the one-row decode streams; emu_amd/bf16pack.py is the definition of the
  * format and emu_amd/csrc/bf16_pack.h states the layout once for the packer and the kernels.  A weight keeps its low byte and its
