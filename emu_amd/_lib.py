@@ -89,6 +89,14 @@ class Bf16PackSetC(C.Structure):
     _fields_ = [("lo", vp), ("nib", vp), ("sign", vp), ("flags", vp), ("hb", i32), ("rows", i32)]
 
 
+class ProjectionC(C.Structure):
+    """emu_projection (include/emu_hip.h): the facts emu_llama_projection_kernel takes, the mode record first; norm_in_stream is its
+    second answer."""
+    _fields_ = [(n, i32) for n in (
+        "fp8", "fp4", "pack", "pack_wide", "bf16_released", "rows", "hidden", "heads_dim_local", "ffn_local", "N", "K", "norm", "epi",
+        "has_fp8", "pack_rows", "set_n", "set_k", "fused_mode", "tail_mode", "warm_mask", "tune", "head", "ws_fits", "norm_in_stream")]
+
+
 SAMPLE_MAX_VOCAB = 40000   # EMU_SAMPLE_MAX_VOCAB of include/emu_hip.h: emu_sample_bf16 answers -22 above it
 CONTRASTIVE_MAX_K = 8      # EMU_CONTRASTIVE_MAX_K: candidates per prompt of the contrastive-search kernels
 BEAM_MAX_BEAMS = 8         # emu_beam_step_bf16 / emu_beam_sample_step_bf16 (include/emu_hip.h): nb <= 8 ...
@@ -194,6 +202,7 @@ _PROTOS = {
     "emu_llama_set_head_fp4": (i32, [vp, vp, vp]),
     "emu_llama_use_fp4": (i32, [vp, i32]),
     "emu_llama_release_bf16": (i32, [vp]),
+    "emu_llama_projection_kernel": (i32, [C.POINTER(ProjectionC)]),
     "emu_llama_weight_kernel": (i32, [i32, i32, i32, i32, i32, i32]),
     "emu_bf16_pack_rows": (i32, [i32, i32, i32, i32, i32]),
     "emu_bf16_pack": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]),

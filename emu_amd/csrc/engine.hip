@@ -77,6 +77,44 @@ int gemv_profiled(double weight_bytes, hipStream_t s, Launch launch) {
     return st;
 }
 
+// ---- The weight sets of one matrix, any of them null: bf16; fp8 (e4m3) bytes + one fp32 scale per output row; MXFP4 element bytes
+// [N, K/2] + E8M0 block scales [N, K/32] at a row stride of fp4_scale_stride(K); and the 13-bit lossless packing of the bf16 matrix
+// [pkN, pkK] (bf16_pack.h; pk.rows == 0: none), whose flagged row groups read the bf16 rows
+struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
+                 const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr;
+                 PackSet pk; int pkN = 0, pkK = 0; };
+enum class WeightSet { Bf16, Fp8, Fp4, Pack };
+// what a set says of every kernel that reads it: whether the record holds it, K over its weight row stride, and the bytes one pass
+// over an [N, K] matrix is priced at under the weight-stream profiler (R: the rows per group of a packed set, priced at what it stores)
+bool holds(const Weights& w, WeightSet set) { return set == WeightSet::Bf16 ? w.W != nullptr : set == WeightSet::Fp8 ? w.W8 && w.s8 : set == WeightSet::Fp4 ? w.W4 && w.s4 : w.W && w.pk.rows; }
+constexpr int set_kdiv(WeightSet set) { return set == WeightSet::Fp4 ? 2 : 1; }
+double set_bytes(WeightSet set, int N, int K, int R = 0) {
+    if (set == WeightSet::Pack) return (double)(pack_lo_bytes(N, K, R) + pack_nib_bytes(N, K, R) + pack_sign_bytes(N, K, R) + 4 * pack_flag_words(N, R));
+    return set == WeightSet::Fp4 ? (double)N * (double)(K / 2 + K / 32) : (set == WeightSet::Fp8 ? 1.0 : 2.0) * (double)N * (double)K;
+}
+// The kernels of a LLaMA projection (ABI: the values emu_llama_projection_kernel and its three views return), and what each is, said
+// once: the set it reads; the rows it serves; whether it takes the RMSNorm in front; whether a bf16 GEMM runs its calls of 17 rows and
+// more -- the one that carries the RoPE epilogue, the K-slice sum + RMSNorm and the two-lane prefill (Fp8Gemm: the W8A8 GEMM beside
+// it, on the caller's quantised rows through linear_q8, bf16 in a matrix without an fp8 copy; those fusions are off under it anyway).
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8, Fp8Stream = 9 };
+struct KernelFacts { WeightSet set; int lo, hi; bool norm, bf16_gemm; };
+constexpr int ANY_ROWS = 1 << 30;
+constexpr KernelFacts KERNEL_FACTS[] = {
+    {WeightSet::Bf16, 1, ANY_ROWS, true, true},      // Bf16          gemv.hip up to 8 / 16 rows, the GEMMs above (linear)
+    {WeightSet::Fp8, 1, 2, true, false},             // Fp8Rows       gemv.hip
+    {WeightSet::Fp8, 17, ANY_ROWS, false, true},     // Fp8Gemm       block-scaled MFMA, twice the bf16 rate (BASELINE configs[4]); whole 128-element k tiles
+    {WeightSet::Fp4, 1, 2, true, false},             // Fp4Rows       gemv_fp4.hip; K % 32 == 0
+    {WeightSet::Fp4, 1, 16, false, false},           // Fp4Thin       gemv_fp4_thin.hip, matrix cores; K >= 256, K % 32 == 0
+    {WeightSet::Fp4, 17, ANY_ROWS, false, false},    // Fp4Gemm       gemm_fp4.hip; the same
+    {WeightSet::Pack, 1, 1, true, false},            // Bf16Pack      gemv_pack.hip: the bf16 stream's bits at 13/16 of its bytes
+    {WeightSet::Fp8, 1, 16, false, false},           // Fp8Thin       gemv_fp8_thin.hip, matrix cores; whole 256-element k stages
+    {WeightSet::Pack, 4, 16, false, false},          // Bf16PackThin  gemv_pack_thin.hip: the packed twin of the bf16 few-row stream
+    {WeightSet::Fp8, 17, 64, false, false},          // Fp8Stream     gemm_fp8.hip, W8A16; the same whole stages
+};
+constexpr const KernelFacts& facts(WeightKernel k) { return KERNEL_FACTS[(int)k]; }
+constexpr bool serves(WeightKernel k, int rows) { return rows >= facts(k).lo && rows <= facts(k).hi; }
+constexpr bool needs_fp8(WeightKernel k) { return facts(k).set == WeightSet::Fp8 && !facts(k).bf16_gemm; }   // no bf16 to fall back to
+constexpr bool norm_rides(WeightKernel k) { return facts(k).norm && facts(k).set != WeightSet::Bf16 && facts(k).set != WeightSet::Pack; }   // in every call
 int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* res, const bf16_t* norm_w,
            bf16_t* C, int M, int N, int K, int lda, int ldw, int ldres, int ldc, float eps, int epi, hipStream_t s,
            const float* wscale = nullptr, float* splitk = nullptr, size_t splitk_floats = 0, const WarmPlan* warm = nullptr) {
@@ -86,109 +124,84 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
     if (M <= 8 || gemv_rows_9_16_ok(M, K, lda, ldw, norm_w != nullptr, wscale != nullptr, epi)) {
         GemvArgs g{A, W, norm_w, bias, res, C, M, N, K, lda, ldw, ldres, ldc, eps, epi, wscale};
         if (warm && M == 1 && !wscale) g.warm = *warm;
-        return gemv_profiled((wscale ? 1.0 : 2.0) * (double)N * (double)K, s, [&] { return launch_gemv(g, s); });
+        return gemv_profiled(set_bytes(wscale ? WeightSet::Fp8 : WeightSet::Bf16, N, K), s, [&] { return launch_gemv(g, s); });
     }
     if (norm_w) return -22;
     GemmArgs g{A, W, bias, res, C, M, N, K, lda, ldw, ldres, ldc, epi, ConvGeom{0, 0, 0, 0, 0, 0}, nullptr, 0, 0};
     g.partial = splitk; g.partial_floats = splitk_floats;
     return launch_gemm(g, s);
 }
-// ---- The weight sets of one matrix, any of them null: bf16; fp8 (e4m3) bytes + one fp32 scale per output row; MXFP4 element bytes
-// [N, K/2] + E8M0 block scales [N, K/32] at a row stride of fp4_scale_stride(K) -- and the kernel that reads them
-// -- and the 13-bit lossless packing of the bf16 matrix [pkN, pkK] (bf16_pack.h; pk.rows == 0: none)
-struct Weights { const bf16_t* W = nullptr; const uint8_t* W8 = nullptr; const float* s8 = nullptr;
-                 const uint8_t* W4 = nullptr; const uint8_t* s4 = nullptr;
-                 PackSet pk; int pkN = 0, pkK = 0; };
-enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8, Fp8Stream = 9 };   // (ABI: emu_llama_weight_kernel, emu_llama_pack_kernel, emu_llama_pack_thin_kernel)
-// The one rule that picks a LLaMA projection's kernel, layers and head alike, from integers only: the modes as emu_llama_use_fp8 /
-// emu_llama_use_fp4 set them (never both), the call's rows, the shard's reduction widths.  1..2 rows: the weight streams with the
-// RMSNorm in front (gemv_fp4.hip, gemv.hip); 3..16: the MXFP4 matrix-core stream (gemv_fp4_thin.hip), or the fp8 one
-// (gemv_fp8_thin.hip; fp8 modes 3 / 4 = 1 / 2 plus this stream, whole 256-element k stages); 17 and more: the 4-bit GEMM
-// (gemm_fp4.hip), or W8A8 GEMMs on the block-scaled MFMA (twice the bf16 rate, BASELINE configs[4]; whole 128-element k tiles);
-// fp8 modes 5 / 6 = 3 / 4 plus 17..64 rows on the fp8 W8A16 GEMM (gemm_fp8.hip, the same whole 256-element k stages)
-WeightKernel weight_kernel(int fp8_mode, int fp4_mode, int rows, int H, int HD, int Fl) {
-    if (rows <= 2) return fp4_mode >= 1 ? WeightKernel::Fp4Rows : fp8_mode >= 1 ? WeightKernel::Fp8Rows : WeightKernel::Bf16;
-    if (rows <= 16)
-        return fp4_mode >= 2 ? WeightKernel::Fp4Thin
-               : fp8_mode >= 3 && !(H & 255) && !(HD & 255) && !(Fl & 255) ? WeightKernel::Fp8Thin : WeightKernel::Bf16;
-    if (fp4_mode == 3) return WeightKernel::Fp4Gemm;
-    if (fp8_mode >= 5 && rows <= 64 && !(H & 255) && !(HD & 255) && !(Fl & 255)) return WeightKernel::Fp8Stream;
-    fp8_mode -= fp8_mode >= 5 ? 2 : 0;
-    return (fp8_mode == 2 || fp8_mode == 4) && !(H & 127) && !(HD & 127) && !(Fl & 127) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
+// ---- The one rule that picks a projection's kernel from an engine's weight mode (emu_weight_mode: what the setters took), in two pure
+// functions on integers -- no HIP call, no model.  emu_llama_projection_kernel is both; include/emu_hip.h states them in full.
+constexpr bool fp8_prefill(const emu_weight_mode& md) { return md.fp8 == 2 || md.fp8 == 4 || md.fp8 == 6; }   // W8A8 GEMMs on
+constexpr bool quantised(const emu_weight_mode& md) { return md.fp8 != 0 || md.fp4 != 0; }                    // an fp8 / fp4 stream on
+// The call-level rule: the kernel a call of `rows` rows is planned around, from the mode and the shard's reduction widths (fp8 modes
+// 3 / 4 = 1 / 2 plus the few-row stream, 5 / 6 = 3 / 4 plus the W8A16 GEMM; above 2 rows fp8 needs whole k stages / tiles, else bf16)
+WeightKernel call_kernel(const emu_weight_mode& md, int rows, int H, int HD, int Fl) {
+    const auto whole = [&](int k) { return !(H & (k - 1)) && !(HD & (k - 1)) && !(Fl & (k - 1)); };
+    if (serves(WeightKernel::Fp4Rows, rows)) return md.fp4 >= 1 ? WeightKernel::Fp4Rows : md.fp8 >= 1 ? WeightKernel::Fp8Rows : WeightKernel::Bf16;
+    if (serves(WeightKernel::Fp4Thin, rows)) return md.fp4 >= 2 ? WeightKernel::Fp4Thin : md.fp8 >= 3 && whole(256) ? WeightKernel::Fp8Thin : WeightKernel::Bf16;
+    if (md.fp4 == 3) return WeightKernel::Fp4Gemm;
+    if (md.fp8 >= 5 && serves(WeightKernel::Fp8Stream, rows) && whole(256)) return WeightKernel::Fp8Stream;
+    return fp8_prefill(md) && whole(128) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
 }
-// The one further rule: a bf16 projection streams the 13-bit packed set (gemv_pack.hip) instead -- same bits, 13/16 of the bytes --
-// exactly when it is one activation row on the bf16 kernel, the stream is switched on, no fused-layer / decode-tail / L2-warm mode
-// is on, and the matrix has a set (pack_rows: its rows per group) for the form gemv_plan names for the shape.  Integers only.
-WeightKernel pack_kernel(WeightKernel k, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
-                         int norm, int epi, int tune) {
-    if (k != WeightKernel::Bf16 || rows != 1 || !pack_on || pack_rows <= 0 || fused_mode || tail_mode || warm_mask) return k;
-    const GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
-    return gemv_pack_rows(gemv_plan(sh, tune), sh) == pack_rows ? WeightKernel::Bf16Pack : k;
-}
-// And the rule behind it, for the steps of 4..16 rows: a projection the two rules above left on bf16 streams the same packed set through
-// the matrix-core twin (gemv_pack_thin.hip) exactly when the pack stream and its wide switch (emu_llama_use_bf16_pack_wide) are on,
-// the matrix has a set (pack_rows) of its own N and K, and gemv_pack_thin_plan has a twin for the shape.  Integers only.
-WeightKernel pack_thin_kernel(WeightKernel k, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
-                              int epi, int tune) {
-    if (k != WeightKernel::Bf16 || !pack_on || !wide_on || pack_rows <= 0 || set_n != N || set_k != K || rows < 4 || rows > 16) return k;
-    GemvShape sh = gemv_one_row_shape(N, K, norm != 0, epi);
-    sh.M = rows;
-    return gemv_pack_thin_plan(sh, pack_rows, tune).status ? k : WeightKernel::Bf16PackThin;
+// The matrix-level rule: the kernel that launches for ONE matrix at one call site, from the call-level answer k and the facts q
+// (of the call only `rows` is read), and into q.norm_in_stream whether the RMSNorm rides in the weight stream.  A layer projection
+// fuses the norm where its plan asks (q.norm) and runs the W8A8 GEMM as bf16 without an fp8 copy.  The head decides the norm itself; it
+// has no W8A8 GEMM, its fp8 copy is optional, and the 3..16-row byte streams need the workspace for the normalised rows (all: bf16, MXFP4
+// only while there are bf16 weights).  Then a matrix left on bf16 streams its 13-bit packed set instead -- same bits, 13/16 of the bytes
+// -- at one row unless a fused-layer / decode-tail / L2-warm mode inhibits it, at 4..16 rows under the wide switch and no fused norm.
+WeightKernel matrix_kernel(WeightKernel k, emu_projection& q) {
+    const bool no_copy = needs_fp8(k) && !q.has_fp8, no_ws = (k == WeightKernel::Fp8Thin || (k == WeightKernel::Fp4Thin && !q.mode.bf16_released)) && !q.ws_fits;
+    if (k == WeightKernel::Fp8Gemm ? q.head || !q.has_fp8 : q.head && (no_copy || no_ws)) k = WeightKernel::Bf16;
+    const bool fused = q.head ? norm_rides(k) || (k == WeightKernel::Bf16 && (q.rows == 1 || (q.rows <= 8 && !q.ws_fits))) : q.norm != 0;
+    q.norm_in_stream = fused;
+    const int set_rows = q.set_n == q.N && q.set_k == q.K ? q.pack_rows : 0;
+    if (k != WeightKernel::Bf16 || !q.mode.pack || set_rows <= 0) return k;
+    GemvShape sh = gemv_one_row_shape(q.N, q.K, fused, q.epi);
+    if (serves(WeightKernel::Bf16Pack, q.rows))
+        return !q.fused_mode && !q.tail_mode && !q.warm_mask && gemv_pack_rows(gemv_plan(sh, q.tune), sh) == set_rows ? WeightKernel::Bf16Pack : k;
+    if (fused || !q.mode.pack_wide || !serves(WeightKernel::Bf16PackThin, q.rows)) return k;       // (the twin takes no norm: KERNEL_FACTS)
+    sh.M = q.rows;
+    return gemv_pack_thin_plan(sh, set_rows, q.tune).status ? k : WeightKernel::Bf16PackThin;
 }
 // out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
-// pointers, which come from w (ldw in elements of the set k reads).  The MXFP4 kernels run under the GEMV profiler, the 4-bit bytes of
-// the matrix once.  The row range follows from k, a row count outside it is refused: Fp4Rows 1..2 (fused norm allowed), Fp4Thin 1..16,
-// Fp4Gemm 17 and more (no fused norm; K >= 256, K % 32 == 0).  Fp8Gemm needs the caller's quantised rows (linear_q8): not served here.
-// Fp8Thin: 1..16 rows of the fp8 set on the matrix cores (no fused norm; K >= 256, K % 256 == 0), priced at its N * K bytes.
-// Fp8Thin and Fp4Thin go through launch_gemv_thin_stream (gemv.hip: shape, gemv_thin_plan, pointer checks, launch), which refuses.
-// Fp8Stream: 17..64 rows of the fp8 set (gemm_fp8.hip; the same requirements and price), through launch_gemm_fp8w_stream, which refuses.
+// pointers, which come from w (ldw in elements of the set k reads).  Every stream runs under the GEMV profiler at its set's price.
+// Refused (-22): a set the record does not hold, a row count outside the kernel's range, Fp8Gemm (it needs the caller's quantised rows:
+// linear_q8), and whatever the launcher behind the kernel refuses (shape -> plan -> pointer checks -> launch).
 int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
-    if (k == WeightKernel::Fp8Thin || k == WeightKernel::Fp8Stream) {
-        if (!w.W8 || !w.s8) return -22;
+    const WeightSet set = facts(k).set;
+    if (k == WeightKernel::Fp8Gemm || !holds(w, set) || !serves(k, g.M)) return -22;
+    if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows)       // stream or GEMM by the rows, priced where it streams (linear)
+        return linear(g.x, set == WeightSet::Fp8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps,
+                      g.epi, s, set == WeightSet::Fp8 ? w.s8 : nullptr, splitk, splitk_floats, &g.warm);
+    const double bytes = set_bytes(set, g.N, g.K, w.pk.rows);
+    if (set == WeightSet::Fp8) {
         g.W = B(w.W8); g.wscale = w.s8;
-        return gemv_profiled((double)g.N * (double)g.K, s, [&] { return k == WeightKernel::Fp8Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp8w_stream(g, s); });
+        return gemv_profiled(bytes, s, [&] { return k == WeightKernel::Fp8Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp8w_stream(g, s); });
     }
-    if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows) {
-        const bool f8 = k == WeightKernel::Fp8Rows;
-        if (f8 ? !w.W8 || !w.s8 : !w.W) return -22;
-        return linear(g.x, f8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps, g.epi, s,
-                      f8 ? w.s8 : nullptr, splitk, splitk_floats, &g.warm);
-    }
-    if (k == WeightKernel::Bf16Pack) {               // the packed twin of the planned bf16 form, priced at the bytes it streams
-        if (!w.W || !w.pk.rows || g.M != 1 || g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
+    if (set == WeightSet::Pack) {                    // the packed twins of the planned bf16 forms
+        if (g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
+        g.W = w.W;
+        if (k == WeightKernel::Bf16PackThin) {
+            const GemvPlan p = gemv_pack_thin_plan(gemv_shape_of(g), w.pk.rows, emu_gemm_tune_get());
+            return p.status ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv_pack_thin(g, w.pk, p, s); });
+        }
         const GemvShape sh = gemv_one_row_shape(g.N, g.K, g.norm_w != nullptr, g.epi);
         const GemvPlan p = gemv_plan(sh, emu_gemm_tune_get());
-        if (gemv_pack_rows(p, sh) != w.pk.rows) return -22;
-        g.W = w.W;
-        const double bytes = (double)(pack_lo_bytes(g.N, g.K, w.pk.rows) + pack_nib_bytes(g.N, g.K, w.pk.rows) + pack_sign_bytes(g.N, g.K, w.pk.rows) +
-                                      4 * pack_flag_words(g.N, w.pk.rows));
-        return gemv_profiled(bytes, s, [&] { return launch_gemv_pack(g, w.pk, p.form, s); });
+        return gemv_pack_rows(p, sh) != w.pk.rows ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv_pack(g, w.pk, p.form, s); });
     }
-    if (k == WeightKernel::Bf16PackThin) {           // the packed twin of the bf16 thin stream, priced at the bytes it streams
-        if (!w.W || !w.pk.rows || g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
-        g.W = w.W;
-        const GemvPlan p = gemv_pack_thin_plan(gemv_shape_of(g), w.pk.rows, emu_gemm_tune_get());
-        if (p.status) return -22;
-        const double bytes = (double)(pack_lo_bytes(g.N, g.K, w.pk.rows) + pack_nib_bytes(g.N, g.K, w.pk.rows) + pack_sign_bytes(g.N, g.K, w.pk.rows) +
-                                      4 * pack_flag_words(g.N, w.pk.rows));
-        return gemv_profiled(bytes, s, [&] { return launch_gemv_pack_thin(g, w.pk, p, s); });
-    }
-    if (k == WeightKernel::Fp8Gemm || !w.W4 || !w.s4) return -22;
     g.W = B(w.W4); g.w4scale = w.s4;
-    const double bytes = (double)g.N * (double)(g.K / 2 + g.K / 32);
-    if (k == WeightKernel::Fp4Rows)
-        return g.M > 2 || (g.K & 31) ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv(g, s); });
+    if (k == WeightKernel::Fp4Rows) return g.K & 31 ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv(g, s); });
     return gemv_profiled(bytes, s, [&] { return k == WeightKernel::Fp4Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp4(g, s); });
 }
-// linear_w's launch block for a packed [N, K] matrix of the engines (rows of K elements: K bf16 / fp8 bytes, K / 2 MXFP4 bytes, scale
-// rows at fp4_scale_stride(K)), no bias; norm_w: the RMSNorm fused in front (eps), or null
+// linear_w's launch block for a packed [N, K] matrix of the engines (scale rows at fp4_scale_stride(K)), no bias; norm_w: the fused RMSNorm or null
 GemvArgs packed(WeightKernel k, const bf16_t* x, int ldx, const bf16_t* norm_w, float eps, const bf16_t* res, int ldres, bf16_t* out, int ldo, int M, int N, int K, int epi) {
-    const bool fp4 = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp4Thin || k == WeightKernel::Fp4Gemm;
-    return {x, nullptr, norm_w, nullptr, res, out, M, N, K, ldx, fp4 ? K / 2 : K, ldres, ldo, norm_w ? eps : 0.f, epi, nullptr, nullptr, fp4_scale_stride(K)};
+    return {x, nullptr, norm_w, nullptr, res, out, M, N, K, ldx, K / set_kdiv(facts(k).set), ldres, ldo, norm_w ? eps : 0.f, epi, nullptr, nullptr, fp4_scale_stride(K)};
 }
 // the merged o_proj of a short shard (gemv_merge.hip) under the same GEMV launch profiler as linear()
 int gemv_merge_profiled(const GemvMergeArgs& g, hipStream_t s) {
-    return gemv_profiled(2.0 * (double)g.N * (double)g.K, s, [&] { return launch_gemv_merge(g, s); });
+    return gemv_profiled(set_bytes(WeightSet::Bf16, g.N, g.K), s, [&] { return launch_gemv_merge(g, s); });
 }
 // the wait bound and loader waves of a persistent-engine launch (decode_engine.hip): 2 s and the kernel's default, unless the tool
 // switches EMU_ENGINE_TIMEOUT_MS / EMU_ENGINE_LOADERS (tools/README.md) say otherwise
@@ -234,19 +247,25 @@ void emu_prof_end(hipStream_t s, const char* klass, int M, int N, int K, int tag
 extern "C" {
 
 int emu_version(void) { return 6; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
-int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local) {
-    return (int)weight_kernel(fp8_mode, fp4_mode, rows, hidden, heads_dim_local, ffn_local);
+int emu_llama_projection_kernel(emu_projection* q) {
+    if (!q || q->mode.fp8 < 0 || q->mode.fp8 > 6 || q->mode.fp4 < 0 || q->mode.fp4 > 3 || (q->mode.fp8 && q->mode.fp4) || q->rows < 1 ||
+        q->hidden < 1 || q->heads_dim_local < 1 || q->ffn_local < 1 || q->N < 1 || q->K < 1 || q->pack_rows < 0 || q->warm_mask < 0)
+        return -22;
+    return (int)matrix_kernel(call_kernel(q->mode, q->rows, q->hidden, q->heads_dim_local, q->ffn_local), *q);
 }
-
+int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local) {
+    return (int)call_kernel(emu_weight_mode{fp8_mode, fp4_mode, 0, 0, 0}, rows, hidden, heads_dim_local, ffn_local);
+}
+// the two older hooks: the matrix-level rule at a layer projection with an fp8 copy -- the wide switch off; the one-row stream inhibited
 int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
                           int norm, int epi, int tune) {
-    if (kernel < 0 || kernel > (int)WeightKernel::Fp8Thin) return -22;
-    return (int)pack_kernel((WeightKernel)kernel, rows, pack_rows, pack_on, fused_mode, tail_mode, warm_mask, N, K, norm, epi, tune);
+    emu_projection q{{0, 0, pack_on, 0, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, N, K, fused_mode, tail_mode, warm_mask, tune, 0, 0, 0};
+    return kernel < 0 || kernel > (int)WeightKernel::Fp8Thin ? -22 : (int)matrix_kernel((WeightKernel)kernel, q);
 }
 int emu_llama_pack_thin_kernel(int kernel, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
                                int epi, int tune) {
-    if (kernel < 0 || kernel > (int)WeightKernel::Bf16PackThin) return -22;
-    return (int)pack_thin_kernel((WeightKernel)kernel, rows, pack_rows, set_n, set_k, pack_on, wide_on, N, K, norm, epi, tune);
+    emu_projection q{{0, 0, pack_on, wide_on, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, set_n, set_k, 1, 0, 0, tune, 0, 0, 0};
+    return kernel < 0 || kernel > (int)WeightKernel::Bf16PackThin ? -22 : (int)matrix_kernel((WeightKernel)kernel, q);
 }
 int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune) {
     if (N < 1 || K < 8) return 0;
@@ -732,23 +751,15 @@ struct emu_llama {
     struct Layer { Weights qkv, o, gu, down; const bf16_t *ln1 = nullptr, *ln2 = nullptr; };
     std::vector<Layer> layers;
     Weights head;                  // lm_head: the fp8 / MXFP4 copies cover the same rows (quantised from the shard)
-    bool fp8_decode = false;       // emu_llama_use_fp8(m, 1 | 2): 1..2 rows stream the fp8 set
-    bool fp8_prefill = false;      // emu_llama_use_fp8(m, 2 | 4): W8A8 GEMMs for prefill rows as well
-    bool fp8_wide = false;         // emu_llama_use_fp8(m, 3 .. 6): steps of 3..16 rows stream the fp8 set too, on the matrix cores
-    bool fp8_mid = false;          // emu_llama_use_fp8(m, 5 | 6): and so do steps of 17..64 rows (gemm_fp8.hip)
-    // emu_llama_use_fp4 (exclusive with the fp8 stream): 1..2 rows stream the MXFP4 set; fp4_wide (mode 2) steps of 3..16 rows too, on
-    // the matrix cores; fp4_all (mode 3) the calls of 17 rows and more run the 4-bit GEMM.  Every other row count keeps the bf16 weights.
-    // bf16_released (emu_llama_release_bf16; mode 3 only, which it pins): the records' bf16 pointers are null.
-    bool fp4_decode = false;
-    bool fp4_wide = false;
-    bool fp4_all = false;
-    bool bf16_released = false;
-    bool bf16_pack = false;        // emu_llama_use_bf16_pack: one-row bf16 projections stream their 13-bit packed sets (pack_kernel)
-    bool bf16_pack_wide = false;   // emu_llama_use_bf16_pack_wide: so do their 4..16-row steps (pack_thin_kernel)
-    // the kernel of a projection of `rows` rows, layers and head alike: the modes above through weight_kernel
-    WeightKernel kernel_for(int rows) const {
-        return weight_kernel(fp8_decode ? 1 + (fp8_prefill ? 1 : 0) + (fp8_wide ? 2 : 0) + (fp8_mid ? 2 : 0) : 0, fp4_all ? 3 : fp4_wide ? 2 : fp4_decode, rows, cfg.hidden,
-                             cfg.heads_local * cfg.head_dim, cfg.ffn_local);
+    // the weight mode as the setters took it (include/emu_hip.h), fp8 and fp4 never both; what it means for a projection is call_kernel's and
+    // matrix_kernel's to say.  bf16_released (emu_llama_release_bf16; fp4 mode 3 only, which it pins): the records' bf16 pointers are null.
+    emu_weight_mode mode{};
+    // the kernel a call of `rows` rows is planned around, layers and head alike
+    WeightKernel kernel_for(int rows) const { return call_kernel(mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local); }
+    // matrix_kernel's facts for the [N, K] matrix W under `rows` rows at a layer projection; the head sets its own two on top
+    emu_projection site(const Weights& W, int rows, int N, int K, bool norm, int epi, int tail_mode, int warm_mask) const {
+        return {mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local, N, K, norm, epi, W.W8 != nullptr, W.pk.rows, W.pkN, W.pkK,
+                decode_fused, tail_mode, warm_mask, emu_gemm_tune_get(), 0, 0, 0};
     }
     const bf16_t *final_norm = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
     // tensor parallelism: lm_head holds rows [head_row0, head_row0 + head_rows) of the vocabulary only (emu_llama_set_head_shard);
@@ -868,9 +879,9 @@ struct LlamaPlan {
     LlamaPath path;
     // fuse_rope      the qkv GEMM's epilogue rotates q / k, appends k / v and writes V^T (demoted for the rest of the call on -95)
     // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
-    // kernel         the weight set and kernel of the call's projections (weight_kernel).  Fp8Gemm: in the layers that have fp8
-    //                weights.  Fp4Thin, Fp8Thin: norms stay launches.  Fp4Gemm, Fp8Stream: norms, RoPE / KV append and V^T stay launches -- fuse_rope and
-    //                fuse_norm are off and the call never takes TwoLane
+    // kernel         the weight set and kernel of the call's projections (call_kernel).  Fp8Gemm: in the layers that have fp8
+    //                weights.  Fp4Thin, Fp8Thin: norms stay launches.  A kernel without a bf16 GEMM behind it (KERNEL_FACTS: Fp4Gemm,
+    //                Fp8Stream): norms, RoPE / KV append and V^T stay launches -- fuse_rope and fuse_norm are off, never TwoLane
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
@@ -912,7 +923,7 @@ struct LlamaCall {
         p.path = LlamaPath::Launches;
         p.kernel = m->kernel_for(M);
         p.fuse_rope = p.fuse_norm = p.decode_tail = p.merge_o = false;
-        p.norm_in_gemv = p.kernel == WeightKernel::Fp8Rows || p.kernel == WeightKernel::Fp4Rows;
+        p.norm_in_gemv = norm_rides(p.kernel);
     }
 
     // Decides the call's schedule and fusions; launches, zeroes and uploads nothing.  Precedence: the engine, whole layers per launch,
@@ -925,19 +936,20 @@ struct LlamaCall {
         // order, slot[i] = i.  The promise is per call: emu_llama_forward consumed it, so a later forward with rows in another slot
         // order (any caller that did not renew it) runs the unfused sequence, which honours slot[] everywhere.
         // (a KV prefix: the rows are a continuation behind the prefix, whatever T == ctx and slots 0 .. T - 1 look like -- never fused)
-        const bool ordered_prompt = promise && Bn == 1 && T == ctx && !m->fp8_prefill && own_kv && m->prefix_len == 0;
+        const bool ordered_prompt = promise && Bn == 1 && T == ctx && !fp8_prefill(m->mode) && own_kv && m->prefix_len == 0;
         // Prefill of such a prompt: the qkv projection rotates q / k, appends k / v to the cache and writes V^T itself
         // (GemmArgs::rope_*), instead of the rope_kv and transpose_v launches.
         p.kernel = m->kernel_for(M);
-        const bool byte_gemm = p.kernel == WeightKernel::Fp4Gemm || p.kernel == WeightKernel::Fp8Stream;   // no bf16 GEMM to carry an epilogue fusion
-        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && !byte_gemm;
+        // else: no bf16 GEMM to carry an epilogue fusion or the two lanes (which start at 512 rows, where only Fp4Gemm lacks one)
+        const bool bf16_gemm = facts(p.kernel).bf16_gemm;
+        p.fuse_rope = ordered_prompt && T > 16 && D == 128 && !(HD & 255) && bf16_gemm;
         // (prefill fusion, no tensor parallelism: the K-slice sums of o_proj / down_proj apply the RMSNorm that follows them; for
         // down_proj that is the NEXT layer's input norm, so a layer may find its normalised rows in w.xn already)
         // The K-slice sum + RMSNorm fusion does not depend on the slot order: it follows the sticky capability (fuse_norm_on: set with the
         // first promise, cleared by emu_llama_set_prefill_fusion(0)), so M > 16 rows of single-token steps (beam / contrastive search
         // with B * beams > 16) keep the fused path they had before the promise became one-shot.
-        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !m->fp8_prefill && !byte_gemm;
-        p.norm_in_gemv = p.kernel == WeightKernel::Fp8Rows || p.kernel == WeightKernel::Fp4Rows || M == 1;
+        p.fuse_norm = m->fuse_norm_on && !tp && M > 16 && !fp8_prefill(m->mode) && bf16_gemm;
+        p.norm_in_gemv = norm_rides(p.kernel) || M == 1;
         p.decode_tail = T == 1 && m->decode_tail && m->arrive && own_kv && (long)Bn * Hl <= EMU_ARRIVE_INTS;
         // short shards (a TP = 8 rank's 7 heads), opt-in (emu_gemm_tune bit 19): the o_proj launch merges the attention's splits
         // itself, no combine launch (gemv_merge.hip).  Bit-identical and measured LEVEL with the two launches (3.15 vs 3.15-3.18 ms
@@ -950,7 +962,7 @@ struct LlamaCall {
             !(emu_gemm_tune_get() & (1 << 30)))
             p.warm = m->l2_warm;
 
-        const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !m->fp8_decode && !m->fp4_decode && own_kv && some_layers;
+        const bool one_row_bf16 = T == 1 && Bn == 1 && D == 128 && !quantised(m->mode) && own_kv && some_layers;
         // the fence-free peer-to-peer all-reduce is on (which implies tensor parallelism and an opened cx->p2p): what the all-reduces
         // inside a launch build on
         const bool p2p_fence_free = cx->p2p_on && emu_p2p_fenced(cx->p2p) == 0;
@@ -988,7 +1000,7 @@ struct LlamaCall {
         }
         // ---- long prompt under tensor parallelism: two row halves, every all-reduce behind the other half's GEMMs (needs the slot-order
         // promise: the rows of the one batch element are the whole context in order, so the first half never reads the second's keys)
-        if (p.kernel != WeightKernel::Fp4Gemm && tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
+        if (bf16_gemm && tp && m->tp_overlap_rows > 0 && cx->lane_stream && cx->ar_ev[4] && ws.vt2 && ordered_prompt && M >= m->tp_overlap_rows && some_layers)
             p.path = LlamaPath::TwoLane;
     }
 
@@ -998,16 +1010,11 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const Weights& W, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi, const WarmPlan& warm = WarmPlan{}) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
-        WeightKernel k = plan.kernel;
-        if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Gemm) {
-            if (!W.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
-            if (k == WeightKernel::Fp8Gemm && W.W8) return linear_q8(w, A, K, W.W8, W.s8, res, C, rows, N, K, ldres, ldc, epi, s);
-            if (gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
-            k = WeightKernel::Bf16;                      // (Fp8Gemm: a layer without fp8 weights runs bf16)
-        }
-        k = pack_kernel(k, rows, W.pkN == N && W.pkK == K ? W.pk.rows : 0, m->bf16_pack, m->decode_fused, plan.decode_tail, plan.warm | (int)warm.ntouch,
-                        N, K, gain_in != nullptr, epi, emu_gemm_tune_get());
-        k = pack_thin_kernel(k, rows, W.pk.rows, W.pkN, W.pkK, m->bf16_pack, m->bf16_pack_wide, N, K, gain_in != nullptr, epi, emu_gemm_tune_get());
+        if (facts(plan.kernel).bf16_gemm && !W.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
+        emu_projection q = m->site(W, rows, N, K, gain_in != nullptr, epi, plan.decode_tail, plan.warm | (int)warm.ntouch);   // (the call's plan)
+        const WeightKernel k = matrix_kernel(plan.kernel, q);
+        if (k == WeightKernel::Fp8Gemm) return linear_q8(w, A, K, W.W8, W.s8, res, C, rows, N, K, ldres, ldc, epi, s);
+        if (k == WeightKernel::Bf16 && gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
         GemvArgs g = packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi);
         if (warm.ntouch && k == WeightKernel::Bf16) { g.warm = warm; ++m->warm_launches; }
         return linear_w(k, W, g, s, w.splitk, w.splitk_floats);
@@ -1045,10 +1052,10 @@ struct LlamaCall {
     int layer_kv(const RowWindow& win, int l, const LaneHook& after_norm = nullptr) {
         const LlamaWs& w = win.w;
         const emu_llama::Layer& L = m->layers[l];
-        if ((plan.kernel == WeightKernel::Fp8Rows || plan.kernel == WeightKernel::Fp8Thin || plan.kernel == WeightKernel::Fp8Stream) && !L.qkv.W8)
+        if (needs_fp8(plan.kernel) && !L.qkv.W8)
             return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
         // after emu_llama_release_bf16 the 4-bit set is the layer's weights (mode 3 is pinned: every row count has a 4-bit path)
-        if (m->bf16_released ? !L.qkv.W4 || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+        if (m->mode.bf16_released ? !L.qkv.W4 || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
@@ -1408,7 +1415,7 @@ void emu_llama_destroy(emu_llama* m) {
 
 int emu_llama_set_decode_fused(emu_llama* m, int enable, int layers_per_launch) {
     if (!m || layers_per_launch < 0) return -22;
-    if (enable > 0 && m->bf16_released)
+    if (enable > 0 && m->mode.bf16_released)
         return fail(m->ctx, -22, "emu_llama_set_decode_fused: the bf16 weights were released (emu_llama_release_bf16); the fused decode modes read them");
     if (enable && !m->dl_cnt) {
         const emu_llama_cfg& c = m->cfg;
@@ -1488,11 +1495,11 @@ int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_sc
 int emu_llama_use_fp4(emu_llama* m, int enable) {
     if (!m) return -22;
     if (enable < 0 || enable > 3) return fail(m->ctx, -22, "emu_llama_use_fp4: modes 0 to 3");
-    if (m->bf16_released && enable != 3)
+    if (m->mode.bf16_released && enable != 3)
         return fail(m->ctx, -22, "emu_llama_use_fp4: the bf16 weights were released (emu_llama_release_bf16); only mode 3 runs without them");
     if (enable) {
         const emu_llama_cfg& c = m->cfg;
-        if (m->fp8_decode)
+        if (m->mode.fp8)
             return fail(m->ctx, -22, "emu_llama_use_fp4: the fp8 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp8(m, 0) first)");
         if ((c.hidden & 31) || ((c.heads_local * c.head_dim) & 31) || (c.ffn_local & 31))
             return fail(m->ctx, -22, "emu_llama_use_fp4: reduction widths (hidden, heads_local * head_dim, ffn_local) must be multiples of 32");
@@ -1501,9 +1508,7 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
         if (enable >= 2 && (c.hidden < 256 || c.heads_local * c.head_dim < 256 || c.ffn_local < 256))
             return fail(m->ctx, -22, "emu_llama_use_fp4: modes 2 and 3 (steps of 3 rows and more) need reduction widths (hidden, heads_local * head_dim, ffn_local) of at least 256 that are multiples of 32 (they need not be multiples of 256: the last K stage may be partial)");
     }
-    m->fp4_decode = enable != 0;
-    m->fp4_wide = enable >= 2;
-    m->fp4_all = enable == 3;
+    m->mode.fp4 = enable;
     return 0;
 }
 static int set_pack(emu_llama* m, Weights& w, const emu_bf16_pack_set& s, int N, int K, const char* what) {
@@ -1515,7 +1520,7 @@ static int set_pack(emu_llama* m, Weights& w, const emu_bf16_pack_set& s, int N,
 }
 int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_set* sets4) {
     if (!m || !sets4 || layer < 0 || layer >= m->cfg.layers) return -22;
-    if (m->bf16_released) return fail(m->ctx, -22, "emu_llama_set_layer_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    if (m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_set_layer_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
     const emu_llama_cfg& c = m->cfg;
     const int H = c.hidden, HD = c.heads_local * c.head_dim, Fl = c.ffn_local;
     emu_llama::Layer& L = m->layers[layer];
@@ -1527,24 +1532,24 @@ int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_s
 }
 int emu_llama_set_head_bf16_pack(emu_llama* m, const emu_bf16_pack_set* set, int rows_n) {
     if (!m || !set || rows_n < 1) return -22;
-    if (m->bf16_released) return fail(m->ctx, -22, "emu_llama_set_head_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    if (m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_set_head_bf16_pack: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
     return set_pack(m, m->head, *set, rows_n, m->cfg.hidden, "emu_llama_set_head_bf16_pack: a set needs its four pointers, rows 2 or 4, hb 0..112 and K % 32 == 0");
 }
 int emu_llama_use_bf16_pack(emu_llama* m, int on) {
     if (!m) return -22;
-    if (on && m->bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack: the bf16 weights were released (emu_llama_release_bf16)");
-    m->bf16_pack = on != 0;
+    if (on && m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack: the bf16 weights were released (emu_llama_release_bf16)");
+    m->mode.pack = on != 0;
     return 0;
 }
 int emu_llama_use_bf16_pack_wide(emu_llama* m, int on) {
     if (!m) return -22;
-    if (on && m->bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack_wide: the bf16 weights were released (emu_llama_release_bf16)");
-    m->bf16_pack_wide = on != 0;
+    if (on && m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack_wide: the bf16 weights were released (emu_llama_release_bf16)");
+    m->mode.pack_wide = on != 0;
     return 0;
 }
 int emu_llama_release_bf16(emu_llama* m) {
     if (!m) return -22;
-    if (!m->fp4_all) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
+    if (m->mode.fp4 != 3) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
     if (m->decode_fused) return fail(m->ctx, -22, "emu_llama_release_bf16: the fused decode modes read the bf16 weights (emu_llama_set_decode_fused(m, 0, 0) first)");
     for (auto& l : m->layers) {
         l.qkv.W = l.o.W = l.gu.W = l.down.W = nullptr;
@@ -1552,9 +1557,9 @@ int emu_llama_release_bf16(emu_llama* m) {
     }
     m->head.W = nullptr;
     m->head.pk = PackSet{};
-    m->bf16_pack = m->bf16_pack_wide = false;
+    m->mode.pack = m->mode.pack_wide = 0;
     m->dl_dirty = true;
-    m->bf16_released = true;
+    m->mode.bf16_released = 1;
     return 0;
 }
 int emu_llama_set_decode_tail(emu_llama* m, int enable) {
@@ -1596,9 +1601,9 @@ long emu_llama_tp_overlap_count(const emu_llama* m) { return m ? m->ov_forwards 
 int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (!m) return -22;
     if (enable < 0 || enable > 6) return fail(m->ctx, -22, "emu_llama_use_fp8: modes 0 to 6");
-    if (enable && m->bf16_released)
+    if (enable && m->mode.bf16_released)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
-    if (enable && m->fp4_decode)
+    if (enable && m->mode.fp4)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp4(m, 0) first)");
     // (emu_llama_set_layer_fp8 was never called: it sets all of a layer's or refuses, and a model has at least one layer)
     if (enable && std::none_of(m->layers.begin(), m->layers.end(), [](const emu_llama::Layer& l) { return l.qkv.W8; }))
@@ -1610,10 +1615,7 @@ int emu_llama_use_fp8(emu_llama* m, int enable) {
         if (std::any_of(m->layers.begin(), m->layers.end(), [](const emu_llama::Layer& l) { return !l.qkv.W8; }))
             return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 to 6 need the fp8 weights of every layer");
     }
-    m->fp8_decode = enable != 0;
-    m->fp8_prefill = enable == 2 || enable == 4 || enable == 6;
-    m->fp8_wide = enable >= 3;
-    m->fp8_mid = enable >= 5;
+    m->mode.fp8 = enable;
     return 0;
 }
 int emu_llama_set_head(emu_llama* m, const void* final_norm, const void* lm_head, const void* embed, const void* rope_cos,
@@ -1866,24 +1868,20 @@ int emu_llama_final_norm(emu_llama* m, const void* hidden, void* out, int rows, 
                           m->cfg.rms_eps, S(s));
 }
 
-// final RMSNorm + rows of the head (N of them, from the engine's head record) on M hidden rows -> out.  The kernel is the layers'
-// (emu_llama::kernel_for) but for the head's own facts: it has no W8A8 GEMM and its fp8 copy is optional (both: bf16), and the 3..16-row
-// MXFP4 / fp8 stream needs the workspace for the normalised rows (too small: bf16, while there are bf16 weights).  The few-row streams fuse
-// the norm -- bf16 also up to 8 rows when the workspace is too small; every other path runs the norm launch into the workspace first.
+// final RMSNorm + rows of the head (N of them, from the engine's head record) on M hidden rows -> out.  The kernel, and whether
+// the norm rides in its stream or is a launch into the workspace first, is matrix_kernel's answer for the head site.
 static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t* out, int N, int ld, bf16_t* ws, size_t ws_bytes,
                       hipStream_t s) {
     const emu_llama_cfg& c = m->cfg;
     const int H = c.hidden;
     const bool ws_fits = ws_bytes >= (size_t)M * H * 2;
-    WeightKernel k = m->kernel_for(M);
-    if (k == WeightKernel::Fp8Gemm || ((k == WeightKernel::Fp8Rows || k == WeightKernel::Fp8Thin || k == WeightKernel::Fp8Stream) && !m->head.W8) ||
-        (k == WeightKernel::Fp8Thin && !ws_fits) || (k == WeightKernel::Fp4Thin && !ws_fits && !m->bf16_released)) k = WeightKernel::Bf16;
-    const bool fused = k == WeightKernel::Fp4Rows || k == WeightKernel::Fp8Rows || (k == WeightKernel::Bf16 && (M == 1 || (M <= 8 && !ws_fits)));
-    if (fused) k = pack_kernel(k, M, m->head.pkN == N && m->head.pkK == H ? m->head.pk.rows : 0, m->bf16_pack, m->decode_fused, m->decode_tail, m->l2_warm,
-                               N, H, 1, EPI_NONE, emu_gemm_tune_get());
+    // (the tail and warm switches as set; a layer projection passes what its call's plan made of them: kept as found, it looks accidental)
+    emu_projection q = m->site(m->head, M, N, H, true, EPI_NONE, m->decode_tail, m->l2_warm);
+    q.head = 1; q.ws_fits = ws_fits;
+    const WeightKernel k = matrix_kernel(m->kernel_for(M), q);
+    const bool fused = q.norm_in_stream != 0;
     if (!fused) {
         if (!ws_fits) return fail(m->ctx, -12, "emu_llama_logits: workspace too small");
-        k = pack_thin_kernel(k, M, m->head.pk.rows, m->head.pkN, m->head.pkK, m->bf16_pack, m->bf16_pack_wide, N, H, 0, EPI_NONE, emu_gemm_tune_get());
         TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
     }
     return linear_w(k, m->head, packed(k, fused ? hidden : ws, fused ? ldh : H, fused ? m->final_norm : nullptr, c.rms_eps, nullptr, 0, out, ld,
@@ -1894,7 +1892,7 @@ int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* log
                      size_t ws_bytes, emu_stream_t s) {
     if (!m || !m->final_norm) return -22;
     // after emu_llama_release_bf16 the 4-bit head is the head (mode 3 is pinned: every row count has a 4-bit path in llama_head)
-    if (m->bf16_released ? !m->fp4_all || !m->head.W4 : !m->head.W) return -22;
+    if (m->mode.bf16_released ? m->mode.fp4 != 3 || !m->head.W4 : !m->head.W) return -22;
     const emu_llama_cfg& c = m->cfg;
     if (m->head_rows < 0) return llama_head(m, B(hidden), ldh, M, B(logits), c.vocab, ld, B(workspace), ws_bytes, S(s));
     // vocabulary-sharded head (tensor parallelism): this rank streams its rows of lm_head only (4035 of 32 274 at TP = 8:

@@ -180,9 +180,13 @@ class EmuHipContext:
 
 
 class LlamaEngine:
+    # the weight mode as the setters below left it (defaults of the class, so that every engine has them before any setter ran)
+    fp8_decode = fp8_wide = False      # use_fp8(True[, wide=True]): 1..2 [and 3..16] rows stream the fp8 set
+    fp8_mid = False            # use_fp8(True, wide=True, mid=True) is on: steps of 17..64 rows stream the fp8 set too
+    fp4_decode = fp4_wide = False      # use_fp4(True[, wide=True]): the same row ranges on the MXFP4 set
     fp4_all = False            # use_fp4(True, wide=True, all_rows=True) is on: every row count runs the 4-bit set
     bf16_released = False      # release_bf16() was called: the bf16 matrices and lm_head are gone, fp4_all is pinned
-    fp8_mid = False            # use_fp8(True, wide=True, mid=True) is on: steps of 17..64 rows stream the fp8 set too
+    bf16_pack_on = bf16_pack_wide = False      # use_bf16_pack / use_bf16_pack_wide: the 13-bit packed streams at 1 / 4..16 rows
 
     def __init__(self, cfg: LlamaCfg, vocab: int, ctx: EmuHipContext):
         self.cfg, self.vocab, self.ctx = cfg, vocab, ctx
@@ -389,13 +393,13 @@ class LlamaEngine:
         """Algorithmic bytes one decode step of THIS shard must stream (all packed matrices once + lm_head)."""
         if self.bf16_released:          # only the 4-bit tensors are left: their shapes
             return sum(self._fp4_shape(k)[0] * mxfp4.bytes_per_row(self._fp4_shape(k)[1]) for k in self._fp4_keys())
-        if getattr(self, "fp4_decode", False):             # MXFP4: K/2 element bytes + K/32 scale bytes per row
+        if self.fp4_decode:             # MXFP4: K/2 element bytes + K/32 scale bytes per row
             size = lambda v: v.shape[0] * mxfp4.bytes_per_row(v.shape[1])
         else:
-            b = 1 if getattr(self, "fp8_decode", False) else 2
+            b = 1 if self.fp8_decode else 2
             size = lambda v: v.numel() * b
         # the 13-bit packed stream (use_bf16_pack): a matrix that has a set streams its planes and flag words instead
-        pk = getattr(self, "_pack", {}) if getattr(self, "bf16_pack_on", False) and b == 2 and not getattr(self, "fp4_decode", False) else {}
+        pk = getattr(self, "_pack", {}) if self.bf16_pack_on and b == 2 and not self.fp4_decode else {}
         one = lambda k, v: bf16pack.packed_bytes(v.shape[0], v.shape[1], pk[k]["rows"]) if k in pk else size(v)
         per = sum(one(k, v) for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
         return per + (one("lm_head", self.lm_head) if self.lm_head is not None else 0)
@@ -468,7 +472,7 @@ class LlamaEngine:
         """Steps of 4..16 rows (beam search, small batches, contrastive search, the lookup chunk step) stream the packed sets too,
         through the matrix-core twin of the bf16 few-row stream: same bits, 13/16 of the bytes.  Off by default
         (profiles/bf16_pack_wide.md); needs ``use_bf16_pack`` on.  Invalidates captured graphs."""
-        if enable and not self.bf16_released and not getattr(self, "bf16_pack_on", False):
+        if enable and not self.bf16_released and not self.bf16_pack_on:
             raise RuntimeError("use_bf16_pack_wide: switch the packed stream on first (use_bf16_pack)")
         check(lib().emu_llama_use_bf16_pack_wide(self.handle, 1 if enable else 0), "emu_llama_use_bf16_pack_wide", self.ctx.handle)
         self.bf16_pack_wide = bool(enable)
@@ -476,7 +480,7 @@ class LlamaEngine:
 
     def _pack_wide_default(self) -> None:
         """EMU_BF16_PACK_WIDE=1 switches the few-row stream on where the default packing has switched the one-row stream on."""
-        if os.environ.get("EMU_BF16_PACK_WIDE") == "1" and not getattr(self, "bf16_pack_wide", False) and hasattr(lib(), "emu_llama_use_bf16_pack_wide"):
+        if os.environ.get("EMU_BF16_PACK_WIDE") == "1" and not self.bf16_pack_wide and hasattr(lib(), "emu_llama_use_bf16_pack_wide"):
             self.use_bf16_pack_wide(True)
 
     def _auto_pack_bf16(self) -> None:
@@ -653,7 +657,7 @@ class LlamaEngine:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != shape:
                 raise ValueError(f"load_fp4({key!r}): {name} must be uint8 {shape}, got "
                                  f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if getattr(self, "fp4_decode", False):
+        if self.fp4_decode:
             raise RuntimeError("load_fp4: switch the fp4 stream off first (use_fp4(False)); captured graphs hold the old pointers")
         self.__dict__.setdefault("_fp4", {})
         self._fp4[key] = (packed.to(self.device).contiguous(), mxfp4.pad_scales(scales.to(self.device).contiguous(), K))
@@ -675,7 +679,7 @@ class LlamaEngine:
         requirement as ``wide``; ``all_rows`` without ``wide`` is a ``ValueError``."""
         if all_rows and not wide:
             raise ValueError("use_fp4: all_rows=True needs wide=True (mode 3 is mode 2 plus the calls of 17 rows and more)")
-        if enable and not getattr(self, "fp8_decode", False) and not self.bf16_released:
+        if enable and not self.fp8_decode and not self.bf16_released:
             self.quantize_fp4()                                    # (with fp8 on, the library refuses and says why)
         mode = (3 if all_rows else 2 if wide else 1) if enable else 0
         check(lib().emu_llama_use_fp4(self.handle, mode), "emu_llama_use_fp4", self.ctx.handle)

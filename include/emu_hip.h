@@ -659,14 +659,41 @@ int emu_llama_set_layer_fp4(emu_llama* m, int layer, const void* wqkv4, const vo
 int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_scales);
 int emu_llama_use_fp4(emu_llama* m, int enable);
 int emu_llama_release_bf16(emu_llama* m);
-/* CPU test hook (tests/test_llama_weight_kernel.py): the one rule by which emu_llama_forward and emu_llama_logits pick a projection's
- * weight set and kernel -- host arithmetic on integers, no HIP call, no model.  fp8_mode 0..6 / fp4_mode 0..3 as emu_llama_use_fp8 /
- * emu_llama_use_fp4 take them (never both non-zero), rows = B*T of the call, the shard's hidden, heads_local*head_dim and ffn_local.
- * Returns 0 bf16, 1 the fp8 stream (1..2 rows), 2 W8A8 GEMMs (17 rows and more; in the layers that have fp8 weights), 3 the MXFP4
- * stream (1..2 rows), 4 the MXFP4 matrix-core stream (3..16 rows), 5 the MXFP4 GEMM (17 rows and more), 7 the fp8 matrix-core
- * stream (3..16 rows in fp8 modes 3 .. 6 when the three widths are multiples of 256; other widths: 0 there), 9 the fp8 W8A16 GEMM
- * (17..64 rows in fp8 modes 5 / 6, same widths; other widths: 0 there) -- 6 is emu_llama_pack_kernel's, 8
- * emu_llama_pack_thin_kernel's.  The head runs 2 as bf16. */
+/* The one rule by which emu_llama_forward and emu_llama_logits pick the kernel of a projection -- host arithmetic on integers, no HIP
+ * call, no model -- and its CPU test hook (tests/test_projection_rule.py).  The engine asks it with exactly these facts.
+ * The kernels: 0 bf16 (the weight stream up to 8 / 16 rows, GEMMs above); 1 the fp8 stream (1..2 rows); 2 W8A8 GEMMs (17 rows and
+ * more); 3 the MXFP4 stream (1..2 rows); 4 the MXFP4 matrix-core stream (3..16 rows); 5 the MXFP4 GEMM (17 rows and more); 6 the
+ * 13-bit packed bf16 stream (1 row); 7 the fp8 matrix-core stream (3..16 rows); 8 the packed matrix-core stream (4..16 rows); 9 the
+ * fp8 W8A16 GEMM (17..64 rows).  Under the weight-stream profiler a launch over [N, K] is priced at 2NK bytes (0 where it streams),
+ * NK (1, 7, 9), N(K/2 + K/32) (3, 4, 5), the bytes its packed set stores (6, 8), nothing (2 and the bf16 GEMMs).
+ * emu_weight_mode: what the setters took -- fp8 0..6 (emu_llama_use_fp8), fp4 0..3 (emu_llama_use_fp4), never both non-zero; pack,
+ * pack_wide (emu_llama_use_bf16_pack, _wide); bf16_released (emu_llama_release_bf16).
+ * The call-level rule (emu_llama_weight_kernel is this alone): mode, rows = B*T of the call and the shard's hidden, heads_local *
+ * head_dim and ffn_local give the kernel the call is planned around.  1..2 rows: 3 if fp4, 1 if fp8, else 0.  3..16 rows: 4 in fp4
+ * modes 2, 3; 7 in fp8 modes 3..6 when the three widths are multiples of 256; else 0.  17 rows and more: 5 in fp4 mode 3; 9 in fp8
+ * modes 5, 6 up to 64 rows, same widths; 2 in fp8 modes 2, 4, 6 when the widths are multiples of 128; else 0.
+ * The matrix-level rule: that answer and the facts of ONE matrix at one call site give the kernel that launches, and norm_in_stream
+ * (out) = the RMSNorm rides in the weight stream.  [N, K], epi: the projection.  has_fp8: the matrix has an fp8 copy.  pack_rows,
+ * set_n, set_k: the rows per group (0: none) and shape of its registered packed set.  fused_mode, tail_mode, warm_mask: what inhibits
+ * the packed one-row stream -- emu_llama_set_decode_fused as set; a layer projection passes the decode tail its call runs and the
+ * L2-warm boundaries its call and this launch carry, the head emu_llama_set_decode_tail / _l2_warm as set.  tune: the emu_gemm_tune
+ * mask.  head = 0, a layer projection: norm = its call fuses the norm in front (1..2 rows on kernels 1, 3; one row on 0; never in a
+ * chunk step on 0), and norm_in_stream = norm; 2 runs as 0 when !has_fp8.  head = 1 (norm is not read, the head always has one in
+ * front; ws_fits: the caller's workspace holds the normalised rows): 2 runs as 0, and so do 1, 7, 9 when !has_fp8, 7 when !ws_fits,
+ * 4 when !ws_fits && !bf16_released; norm_in_stream = kernels 1, 3, and 0 at one row or, when !ws_fits, up to 8 rows.  Then, either
+ * site, 0 becomes 6 when pack is on, rows == 1, no inhibitor is set and the set is of this [N, K] with emu_bf16_pack_rows(N, K,
+ * norm_in_stream, epi, tune) == pack_rows; and 0 becomes 8 when pack and pack_wide are on, 4 <= rows <= 16, !norm_in_stream, the set
+ * is of this [N, K] and emu_gemv_pack_thin_plan has a plan for the shape.  Every other kernel passes through.
+ * Returns the kernel, or -22: q null, a mode out of range or both non-zero, rows / a width / N / K < 1, pack_rows or warm_mask < 0. */
+typedef struct emu_weight_mode { int fp8, fp4, pack, pack_wide, bf16_released; } emu_weight_mode;
+typedef struct emu_projection {
+    emu_weight_mode mode;
+    int rows, hidden, heads_dim_local, ffn_local;               /* the call */
+    int N, K, norm, epi, has_fp8, pack_rows, set_n, set_k;      /* the matrix */
+    int fused_mode, tail_mode, warm_mask, tune, head, ws_fits;  /* the site */
+    int norm_in_stream;                                         /* out */
+} emu_projection;
+int emu_llama_projection_kernel(emu_projection* q);
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local);
 /* The 13-bit lossless packing of a bf16 weight matrix for the one-row decode streams; emu_amd/bf16pack.py is the definition of the
  * format and emu_amd/csrc/bf16_pack.h states the layout once for the packer and the kernels.  A weight keeps its low byte and its
@@ -688,15 +715,12 @@ int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* s
                         int K, int form, float eps, int epi, emu_stream_t s);
 /* The packed sets of a layer (sets4: qkv, o_proj, gate/up, down; rows == 0: that matrix has none and stays on bf16) and of the head
  * (rows_n: the rows the lm_head pointer holds); refused after emu_llama_release_bf16.  emu_llama_use_bf16_pack(m, 1): projections of
- * ONE activation row on the bf16 kernels stream their set where emu_llama_pack_kernel says so; everything else reads what it read. */
+ * ONE activation row on the bf16 kernels stream their set where emu_llama_projection_kernel says so; everything else reads what it read. */
 int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_set* sets4);
 int emu_llama_set_head_bf16_pack(emu_llama* m, const emu_bf16_pack_set* set, int rows_n);
 int emu_llama_use_bf16_pack(emu_llama* m, int on);
-/* CPU test hook (tests/test_bf16_pack_rule.py): the one further rule, bf16 -> the packed stream (6), on integers.  kernel: the answer
- * of emu_llama_weight_kernel; rows = B*T; pack_rows: the rows per group of the matrix's registered set (0: none); pack_on: the
- * switch; fused_mode / tail_mode / warm_mask: emu_llama_set_decode_fused / _decode_tail / _l2_warm as set; [N, K], norm, epi: the
- * projection; tune: the emu_gemm_tune mask.  Returns 6 only for kernel 0, rows 1, the switch on, all three modes 0 and
- * emu_bf16_pack_rows(N, K, norm, epi, tune) == pack_rows; else `kernel`. */
+/* CPU test hook (tests/test_bf16_pack_rule.py): the matrix-level rule of emu_llama_projection_kernel for `kernel` (0..7, else -22) at
+ * a layer projection with an fp8 copy and a set of pack_rows rows per group for its own [N, K], the wide switch off: 6 or `kernel`. */
 int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
                           int norm, int epi, int tune);
 /* The same sets under steps of 4..16 activation rows: the matrix-core twin of the bf16 few-row stream (gemv_pack_thin.hip), whose
@@ -705,11 +729,10 @@ int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int 
  * bf16 matrix W [N, K] (read for flagged row groups); epi NONE / RESID (res [M, N]) / SWIGLU (C [M, N / 2]).  -22, nothing
  * written, where emu_gemv_pack_thin_plan refuses or a pointer is missing or a plane is off a 16-byte boundary.
  * emu_llama_use_bf16_pack_wide(m, 1): OFF by default; with emu_llama_use_bf16_pack on, projections and the head at 4..16 rows that
- * are on the bf16 kernels stream their set where emu_llama_pack_thin_kernel says so.  Refused after emu_llama_release_bf16.
- * emu_llama_pack_thin_kernel (CPU test hook, tests/test_pack_thin_plan.py): that rule on integers.  kernel: the answer of
- * emu_llama_pack_kernel; rows = B*T; pack_rows, set_n, set_k: the registered set's rows per group (0: none) and shape; pack_on /
- * wide_on: the two switches; [N, K], norm, epi: the projection; tune: the emu_gemm_tune mask.  Returns 8 only for kernel 0, both
- * switches on, a set of this N and K, 4 <= rows <= 16 and a plan from emu_gemv_pack_thin_plan; else `kernel`. */
+ * are on the bf16 kernels stream their set where emu_llama_projection_kernel says so.  Refused after emu_llama_release_bf16.
+ * emu_llama_pack_thin_kernel (CPU test hook, tests/test_pack_thin_plan.py): the matrix-level rule of emu_llama_projection_kernel for
+ * `kernel` (0..8, else -22) at a layer projection with an fp8 copy, a set of pack_rows rows per group for [set_n, set_k], the two
+ * switches as given and the one-row stream inhibited: 8 or `kernel`. */
 int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, void* C, int M, int N, int K,
                              int epi, emu_stream_t s);
 int emu_llama_use_bf16_pack_wide(emu_llama* m, int on);

@@ -1,15 +1,17 @@
 """Bit-for-bit check of emu_llama_forward and emu_llama_logits between two builds of libemu_hip.so: seeded cases over every
 schedule of the forward (per-layer launches for decode / prefill / left-padded batch / beam-shaped steps / fp8, decode tail and
-merged o_proj, the MXFP4 modes 1-3 at every row range and after release_bf16, the fused decode modes 1-4 on the shard-emulation
+merged o_proj, the MXFP4 modes 1-3 at every row range and after release_bf16, the fp8 modes 3, 5 and 6 at 5, 20 and 65 rows with and
+without the head's fp8 copy, the 13-bit packed streams at 1, 5 and 16 rows, the fused decode modes 1-4 on the shard-emulation
 engines, the two-lane tensor-parallel prefill over p2p and 1-rank RCCL) and every kernel of the head (whole, with the workspace too
 small, vocabulary-sharded).  Per case it writes the sha256 of the residual stream forward returned and of the K and V cache it wrote,
-of the logits where the case takes them, plus the path counters (the weight-stream profiler's bytes and launches in the fp4 group),
-as JSON:
+of the logits where the case takes them, plus the path counters (the weight-stream profiler's bytes and launches in the fp4, fp8w
+and pack groups), as JSON:
 
-    python tools/llama_forward_equiv.py new.json [main|merge|fp4|fused|lanes ...]
+    python tools/llama_forward_equiv.py new.json [main|merge|fp4|fp8w|pack|fused|lanes ...]
     EMU_HIP_TOOLS=1 EMU_HIP_LIB=/path/to/other/libemu_hip.so python tools/llama_forward_equiv.py other.json
 
-Equal files = equal bits in every case (profiles/llama_forward_refactor_equivalence.md, profiles/weight_path_refactor_equivalence.md)."""
+Equal files = equal bits in every case (profiles/llama_forward_refactor_equivalence.md, profiles/weight_path_refactor_equivalence.md,
+profiles/projection_rule_equivalence.md)."""
 import ctypes as C
 import hashlib
 import json
@@ -73,13 +75,18 @@ def h(t):
     return hashlib.sha256(t.detach().contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()[:24]
 
 
+def dump():
+    """one case per line"""
+    open(out_path, "w").write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in res.items()) + "\n}\n")
+
+
 def rec(name, hidden, eng, extra=None, kv=None):
     k, v = kv if kv else (eng.kcache, eng.vcache)
     res[name] = {"hidden": h(hidden), "k": h(k), "v": h(v)}
     if extra:
         res[name].update(extra)
     print(name, res[name], flush=True)
-    json.dump(res, open(out_path, "w"), indent=1)
+    dump()
 
 
 def logits_small_ws(eng, rows):
@@ -127,7 +134,7 @@ def step_rows(eng, rows, S, seed, steps=2):
 def rec_logits(name, logits):
     res[name] = {"logits": h(logits)}
     print(name, res[name], flush=True)
-    json.dump(res, open(out_path, "w"), indent=1)
+    dump()
 
 
 def want(n):
@@ -140,6 +147,7 @@ def rand(*shape, seed):
 
 
 def main():
+    from emu_amd import ops
     from emu_amd._lib import check, lib
     from emu_amd.conf.emu_conf import LlamaCfg
     dev = torch.device("cuda", 0)
@@ -262,6 +270,55 @@ def main():
                 for rows in (1, 5, 20):
                     rec_logits(f"k_head_shard_{tag}_{rows}rows", eng.logits(rand(rows, cfg.hidden_size, seed=80 + rows)))
             del eng, real
+            torch.cuda.empty_cache()
+        if want("fp8w"):
+            # (l) the fp8 modes 3, 5 and 6 on a shape whose three widths are multiples of 256: the few-row stream, the W8A16 GEMM and
+            # the bf16 / W8A8 GEMM above it, each followed by the head -- first without its fp8 copy (bf16), then with
+            cfg = LlamaCfg(hidden_size=256, intermediate_size=512, num_attention_heads=2, num_hidden_layers=3)
+            eng, _ = make_engine(cfg, 2050)
+            eng._fp8 = {}                                       # the layers' copies only: quantize_fp8 adds the head's
+            for i in range(cfg.num_hidden_layers):
+                a = []
+                for k in ("wqkv", "wo", "wgu", "wdown"):
+                    eng._fp8[f"{i}.{k}"] = ops.quantize_fp8_rows(eng._keep[f"{i}.{k}"])
+                    a += [t.data_ptr() for t in eng._fp8[f"{i}.{k}"]]
+                check(lib().emu_llama_set_layer_fp8(eng.handle, i, *a), "emu_llama_set_layer_fp8", eng.ctx.handle)
+            for head in ("no_head_copy", "head_copy"):
+                if head == "head_copy":
+                    old, eng._fp8 = eng._fp8, None              # (kept until every pointer is registered anew)
+                    eng.quantize_fp8()
+                    del old
+                for tag, mode in (("mode3", dict(wide=True)), ("mode5", dict(wide=True, mid=True)), ("mode6", dict(prefill=True, wide=True, mid=True))):
+                    eng.use_fp8(True, **mode)
+                    for rows in (5, 20, 65):
+                        hs, lg, counters = step_rows(eng, rows, 40, seed=90 + rows)
+                        if rows == 5:                           # no workspace: the bf16 stream with the norm fused
+                            counters["logits_small_ws"] = h(logits_small_ws(eng, hs[-1]))
+                        rec(f"l_fp8_{head}_{tag}_{rows}rows", hs, eng, {"logits": h(lg), **counters},
+                            kv=(eng.kcache[:, :, :, 40:42], eng.vcache[:, :, :, 40:42]))
+            del eng
+            torch.cuda.empty_cache()
+        if want("pack"):
+            # (m) the 13-bit packed streams on the shape of tests/test_gpu_bf16_pack_wide.py (its sets are made under emu_gemm_tune bit
+            # 17): the one-row and the few-row switch, under the default L2-warm mask, with the decode tail, and with no warming
+            cfg = LlamaCfg(hidden_size=256, intermediate_size=512, num_attention_heads=2, num_hidden_layers=2)
+            eng, _ = make_engine(cfg, 1024)
+            lib().emu_gemm_tune(1 << 17)
+            try:
+                eng.pack_bf16(tune=1 << 17)
+                eng.use_bf16_pack(True)
+                for tag, setup in (("default", lambda: None), ("tail", lambda: eng.set_decode_tail(True)), ("no_warm", lambda: eng.set_l2_warm(0))):
+                    setup()
+                    for wide in (False, True):
+                        eng.use_bf16_pack_wide(wide)
+                        for rows in (1, 5, 16):
+                            hs, lg, counters = step_rows(eng, rows, 24, seed=110 + rows)
+                            rec(f"m_pack_{tag}_wide{int(wide)}_{rows}rows", hs, eng, {"logits": h(lg), **counters},
+                                kv=(eng.kcache[:, :, :, 24:26], eng.vcache[:, :, :, 24:26]))
+                    eng.set_decode_tail(False)
+            finally:
+                lib().emu_gemm_tune(0)
+            del eng
             torch.cuda.empty_cache()
         if want("fused"):
             # (g) modes 1, 2, 3 on the TP = 8 shard emulation, mode 4 on the TP = 4 one
