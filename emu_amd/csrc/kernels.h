@@ -336,7 +336,10 @@ struct RopeKvArgs {
 };
 int launch_rope_kv(const RopeKvArgs& a, hipStream_t s);
 
-// Vt[b, h, d, s] = V[b, h, s, d] for s < S (zero for S <= s < S_pad); strided source
+// Vt[b, h, d, s] = V[b, h, s, d] for s < S (zero for S <= s < S_pad); strided source.
+// Memory contract (tests/test_gpu_flash_kernel.py): V rows >= S are not read; EVERY element of [S, S_pad) is written as zero, whole
+// extra tiles included -- this launch is the producer of the zero pad launch_flash_attn relies on.  -22, nothing written: D not a
+// multiple of 64, S_pad not a multiple of 64 or below S, a stride that is not a multiple of 8.
 struct TransposeVArgs {
     const bf16_t* v; long v_sb, v_sh, v_ss;    // element strides (batch, head, token); d contiguous
     bf16_t* vt;                                // [B, H, D, S_pad]
@@ -344,6 +347,18 @@ struct TransposeVArgs {
 };
 int launch_transpose_v(const TransposeVArgs& a, hipStream_t s);
 
+// softmax(q k^T scale + mask) v; query i of row b sees the keys kstart[b] <= key (and, causal, key <= i + (Sk - Sq)).
+// Memory contract, pinned bit for bit by tests/test_gpu_flash_kernel.py:
+//  - may hold anything (NaN patterns included), because it is either not read or selected away, never multiplied: the K rows of keys
+//    < kstart[b]; Q rows >= Sq and K rows >= Sk (loads are clamped to the last row); V^T columns >= ceil64(Sk) (Sk_pad may be larger:
+//    further tiles are never touched);
+//  - must be FINITE: the V rows of masked keys (key < kstart[b], or behind the causal limit inside a tile that is read).  Their weight
+//    is an exact zero, but the row does reach the P.V MFMA as 0 * v: any finite value gives the bits that zero gives, NaN / Inf do not;
+//  - must be ZERO: the V^T pad [Sk, ceil64(Sk)) inside the last key tile (launch_transpose_v writes it);
+//  - a query row with no visible key comes out as exact zeros (l = 0 -> 1 / l is replaced by 0), in every form;
+//  - nothing outside o[B, Sq, H, D] (by its strides) is written, by staged and by direct stores alike.
+// -22, nothing written: Sq < 1, Sk < 1, Sk_pad not a multiple of 64 or below Sk, D not 64 / 128, a q / k stride that is not a
+// multiple of 8, an o stride that is not a multiple of 4 (a multiple of 4 but not of 8, or an o that is not 16-byte aligned: direct stores).
 struct FlashArgs {
     const bf16_t* q; long q_sb, q_sh, q_ss;    // element strides; d contiguous
     const bf16_t* k; long k_sb, k_sh, k_ss;

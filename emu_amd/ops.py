@@ -557,13 +557,24 @@ def transpose_v(v, B: int, H: int, S: int, D: int, sb: int, sh: int, ss: int, S_
     return vt
 
 
-def flash_attn(q, k, v, causal: bool, scale: float, kstart=None):
-    """q [B,Sq,H,D], k/v [B,Sk,H,D] (any strides with D contiguous) -> o [B,Sq,H,D]."""
-    _req(q, "q"); _req(k, "k"); _req(v, "v")
+def flash_attn(q, k, v, causal: bool, scale: float, kstart=None, out=None, vt=None):
+    """q [B,Sq,H,D], k/v [B,Sk,H,D] (any strides with D contiguous) -> o [B,Sq,H,D] (``out`` if given: any strides that are multiples
+    of 4 with D contiguous).  ``vt``: the caller's V^T [B,H,D,Sk_pad] (``transpose_v``: zero in [Sk, ceil64(Sk))) instead of ``v``."""
+    _req(q, "q"); _req(k, "k")
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
-    vt = transpose_v(v, B, H, Sk, D, v.stride(0), v.stride(2), v.stride(1))
-    o = torch.empty(B, Sq, H, D, device=q.device, dtype=BF16)
+    if vt is None:
+        _req(v, "v")
+        vt = transpose_v(v, B, H, Sk, D, v.stride(0), v.stride(2), v.stride(1))
+    else:
+        _req(vt, "vt")
+        assert v is None and vt.is_contiguous() and vt.shape[:3] == (B, H, D), (vt.shape, vt.stride())
+    if out is None:
+        o = torch.empty(B, Sq, H, D, device=q.device, dtype=BF16)
+    else:
+        _req(out, "out")
+        assert out.shape == (B, Sq, H, D) and out.stride(3) == 1, (out.shape, out.stride())
+        o = out
     check(lib().emu_flash_attn_bf16(_p(q), q.stride(0), q.stride(2), q.stride(1),
                                     _p(k), k.stride(0), k.stride(2), k.stride(1), _p(vt),
                                     _p(o), o.stride(0), o.stride(2), o.stride(1), _p(kstart),
