@@ -79,6 +79,11 @@ class GemmFp8wPlanC(C.Structure):
     _fields_ = [(n, i32) for n in ("status", "form", "bm", "kc", "stages", "lds_bytes", "grid", "block")]
 
 
+class GemmFp8tPlanC(C.Structure):
+    """emu_gemm_fp8t_plan_t (include/emu_hip.h)."""
+    _fields_ = [(n, i32) for n in ("status", "form", "bm", "kc", "stages", "lds_bytes", "grid_x", "grid_y", "block")]
+
+
 class TokenTrieC(C.Structure):
     """emu_token_trie (include/emu_hip.h): the flat tables of emu_amd.constrain.TokenTrie on the device."""
     _fields_ = [("first", vp), ("tok", vp), ("child", vp), ("nodes", i32), ("edges", i32)]
@@ -93,7 +98,7 @@ class ProjectionC(C.Structure):
     """emu_projection (include/emu_hip.h): the facts emu_llama_projection_kernel takes, the mode record first; norm_in_stream is its
     second answer."""
     _fields_ = [(n, i32) for n in (
-        "fp8", "fp4", "pack", "pack_wide", "bf16_released", "rows", "hidden", "heads_dim_local", "ffn_local", "N", "K", "norm", "epi",
+        "fp8", "fp4", "pack", "pack_wide", "bf16_released", "fp8_all", "rows", "hidden", "heads_dim_local", "ffn_local", "N", "K", "norm", "epi",
         "has_fp8", "pack_rows", "set_n", "set_k", "fused_mode", "tail_mode", "warm_mask", "tune", "head", "ws_fits", "norm_in_stream")]
 
 
@@ -144,10 +149,12 @@ _PROTOS = {
     "emu_gemv_pack_thin_plan": (i32, [vp, i32, i32, vp]),
     "emu_gemv_fp8_thin_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_gemm_fp8w_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_gemm_fp8t_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_fp8_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, vp]),
     "emu_linear_fp8w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_linear_fp8w_gemm_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "emu_linear_fp8w_tile_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_quantize_mxfp4_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, vp]),
     "emu_linear_fp4w_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
     "emu_linear_fp8_bf16": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -195,6 +202,7 @@ _PROTOS = {
     "emu_llama_set_layer_fp8": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "emu_llama_set_head_fp8": (i32, [vp, vp, vp]),
     "emu_llama_use_fp8": (i32, [vp, i32]),
+    "emu_llama_use_fp8_all": (i32, [vp, i32]),
     "emu_linear_fp4w_thin_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_linear_fp4w_gemm_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "emu_linear_fp4w_mfma_bf16": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -96,7 +96,7 @@ double set_bytes(WeightSet set, int N, int K, int R = 0) {
 // once: the set it reads; the rows it serves; whether it takes the RMSNorm in front; whether a bf16 GEMM runs its calls of 17 rows and
 // more -- the one that carries the RoPE epilogue, the K-slice sum + RMSNorm and the two-lane prefill (Fp8Gemm: the W8A8 GEMM beside
 // it, on the caller's quantised rows through linear_q8, bf16 in a matrix without an fp8 copy; those fusions are off under it anyway).
-enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8, Fp8Stream = 9 };
+enum class WeightKernel { Bf16 = 0, Fp8Rows = 1, Fp8Gemm = 2, Fp4Rows = 3, Fp4Thin = 4, Fp4Gemm = 5, Bf16Pack = 6, Fp8Thin = 7, Bf16PackThin = 8, Fp8Stream = 9, Fp8Tile = 10 };
 struct KernelFacts { WeightSet set; int lo, hi; bool norm, bf16_gemm; };
 constexpr int ANY_ROWS = 1 << 30;
 constexpr KernelFacts KERNEL_FACTS[] = {
@@ -110,6 +110,7 @@ constexpr KernelFacts KERNEL_FACTS[] = {
     {WeightSet::Fp8, 1, 16, false, false},           // Fp8Thin       gemv_fp8_thin.hip, matrix cores; whole 256-element k stages
     {WeightSet::Pack, 4, 16, false, false},          // Bf16PackThin  gemv_pack_thin.hip: the packed twin of the bf16 few-row stream
     {WeightSet::Fp8, 17, 64, false, false},          // Fp8Stream     gemm_fp8.hip, W8A16; the same whole stages
+    {WeightSet::Fp8, 65, ANY_ROWS, false, false},    // Fp8Tile       gemm_fp8.hip, its 64 x 128 form under the fp8_all switch; the same
 };
 constexpr const KernelFacts& facts(WeightKernel k) { return KERNEL_FACTS[(int)k]; }
 constexpr bool serves(WeightKernel k, int rows) { return rows >= facts(k).lo && rows <= facts(k).hi; }
@@ -136,24 +137,30 @@ int linear(const bf16_t* A, const bf16_t* W, const bf16_t* bias, const bf16_t* r
 constexpr bool fp8_prefill(const emu_weight_mode& md) { return md.fp8 == 2 || md.fp8 == 4 || md.fp8 == 6; }   // W8A8 GEMMs on
 constexpr bool quantised(const emu_weight_mode& md) { return md.fp8 != 0 || md.fp4 != 0; }                    // an fp8 / fp4 stream on
 // The call-level rule: the kernel a call of `rows` rows is planned around, from the mode and the shard's reduction widths (fp8 modes
-// 3 / 4 = 1 / 2 plus the few-row stream, 5 / 6 = 3 / 4 plus the W8A16 GEMM; above 2 rows fp8 needs whole k stages / tiles, else bf16)
+// 3 / 4 = 1 / 2 plus the few-row stream, 5 / 6 = 3 / 4 plus the W8A16 GEMM; above 2 rows fp8 needs whole k stages / tiles, else bf16;
+// the fp8_all switch puts mode 5's calls of 65 rows and more on the W8A16 GEMM's third form, mode 6 keeps the W8A8 GEMMs there)
 WeightKernel call_kernel(const emu_weight_mode& md, int rows, int H, int HD, int Fl) {
     const auto whole = [&](int k) { return !(H & (k - 1)) && !(HD & (k - 1)) && !(Fl & (k - 1)); };
     if (serves(WeightKernel::Fp4Rows, rows)) return md.fp4 >= 1 ? WeightKernel::Fp4Rows : md.fp8 >= 1 ? WeightKernel::Fp8Rows : WeightKernel::Bf16;
     if (serves(WeightKernel::Fp4Thin, rows)) return md.fp4 >= 2 ? WeightKernel::Fp4Thin : md.fp8 >= 3 && whole(256) ? WeightKernel::Fp8Thin : WeightKernel::Bf16;
     if (md.fp4 == 3) return WeightKernel::Fp4Gemm;
     if (md.fp8 >= 5 && serves(WeightKernel::Fp8Stream, rows) && whole(256)) return WeightKernel::Fp8Stream;
+    if (md.fp8 == 5 && md.fp8_all && serves(WeightKernel::Fp8Tile, rows) && whole(256)) return WeightKernel::Fp8Tile;
     return fp8_prefill(md) && whole(128) ? WeightKernel::Fp8Gemm : WeightKernel::Bf16;
 }
 // The matrix-level rule: the kernel that launches for ONE matrix at one call site, from the call-level answer k and the facts q
 // (of the call only `rows` is read), and into q.norm_in_stream whether the RMSNorm rides in the weight stream.  A layer projection
 // fuses the norm where its plan asks (q.norm) and runs the W8A8 GEMM as bf16 without an fp8 copy.  The head decides the norm itself; it
-// has no W8A8 GEMM, its fp8 copy is optional, and the 3..16-row byte streams need the workspace for the normalised rows (all: bf16, MXFP4
-// only while there are bf16 weights).  Then a matrix left on bf16 streams its 13-bit packed set instead -- same bits, 13/16 of the bytes
+// has no W8A8 GEMM (under the fp8_all switch the W8A16 tile runs in its place where the head has an fp8 copy and K is in whole stages),
+// its fp8 copy is optional, and the 3..16-row byte streams need the workspace for the normalised rows (all: bf16; MXFP4, and fp8 under
+// fp8_all, only while there are bf16 weights).  Then a matrix left on bf16 streams its 13-bit packed set instead -- same bits, 13/16 of the bytes
 // -- at one row unless a fused-layer / decode-tail / L2-warm mode inhibits it, at 4..16 rows under the wide switch and no fused norm.
 WeightKernel matrix_kernel(WeightKernel k, emu_projection& q) {
-    const bool no_copy = needs_fp8(k) && !q.has_fp8, no_ws = (k == WeightKernel::Fp8Thin || (k == WeightKernel::Fp4Thin && !q.mode.bf16_released)) && !q.ws_fits;
-    if (k == WeightKernel::Fp8Gemm ? q.head || !q.has_fp8 : q.head && (no_copy || no_ws)) k = WeightKernel::Bf16;
+    const bool released8 = q.mode.bf16_released && q.mode.fp8_all;       // (only the fp8 set is left: nothing to fall back to)
+    const bool no_copy = needs_fp8(k) && !q.has_fp8;
+    const bool no_ws = ((k == WeightKernel::Fp8Thin && !released8) || (k == WeightKernel::Fp4Thin && !q.mode.bf16_released)) && !q.ws_fits;
+    if (k == WeightKernel::Fp8Gemm && q.head && q.mode.fp8_all && q.has_fp8 && serves(WeightKernel::Fp8Tile, q.rows) && !(q.K & 255)) k = WeightKernel::Fp8Tile;
+    else if (k == WeightKernel::Fp8Gemm ? q.head || !q.has_fp8 : q.head && (no_copy || no_ws)) k = WeightKernel::Bf16;
     const bool fused = q.head ? norm_rides(k) || (k == WeightKernel::Bf16 && (q.rows == 1 || (q.rows <= 8 && !q.ws_fits))) : q.norm != 0;
     q.norm_in_stream = fused;
     const int set_rows = q.set_n == q.N && q.set_k == q.K ? q.pack_rows : 0;
@@ -178,7 +185,9 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
     const double bytes = set_bytes(set, g.N, g.K, w.pk.rows);
     if (set == WeightSet::Fp8) {
         g.W = B(w.W8); g.wscale = w.s8;
-        return gemv_profiled(bytes, s, [&] { return k == WeightKernel::Fp8Thin ? launch_gemv_thin_stream(g, s) : launch_gemm_fp8w_stream(g, s); });
+        return gemv_profiled(bytes, s, [&] {
+            return k == WeightKernel::Fp8Thin ? launch_gemv_thin_stream(g, s) : k == WeightKernel::Fp8Tile ? launch_gemm_fp8t_stream(g, s) : launch_gemm_fp8w_stream(g, s);
+        });
     }
     if (set == WeightSet::Pack) {                    // the packed twins of the planned bf16 forms
         if (g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
@@ -249,22 +258,23 @@ extern "C" {
 int emu_version(void) { return 6; }      // ABI version: emu_amd/_lib.py::ABI_VERSION must match
 int emu_llama_projection_kernel(emu_projection* q) {
     if (!q || q->mode.fp8 < 0 || q->mode.fp8 > 6 || q->mode.fp4 < 0 || q->mode.fp4 > 3 || (q->mode.fp8 && q->mode.fp4) || q->rows < 1 ||
+        q->mode.fp8_all < 0 || q->mode.fp8_all > 1 || (q->mode.fp8_all && q->mode.fp8 < 5) ||
         q->hidden < 1 || q->heads_dim_local < 1 || q->ffn_local < 1 || q->N < 1 || q->K < 1 || q->pack_rows < 0 || q->warm_mask < 0)
         return -22;
     return (int)matrix_kernel(call_kernel(q->mode, q->rows, q->hidden, q->heads_dim_local, q->ffn_local), *q);
 }
 int emu_llama_weight_kernel(int fp8_mode, int fp4_mode, int rows, int hidden, int heads_dim_local, int ffn_local) {
-    return (int)call_kernel(emu_weight_mode{fp8_mode, fp4_mode, 0, 0, 0}, rows, hidden, heads_dim_local, ffn_local);
+    return (int)call_kernel(emu_weight_mode{fp8_mode, fp4_mode, 0, 0, 0, 0}, rows, hidden, heads_dim_local, ffn_local);
 }
 // the two older hooks: the matrix-level rule at a layer projection with an fp8 copy -- the wide switch off; the one-row stream inhibited
 int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int fused_mode, int tail_mode, int warm_mask, int N, int K,
                           int norm, int epi, int tune) {
-    emu_projection q{{0, 0, pack_on, 0, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, N, K, fused_mode, tail_mode, warm_mask, tune, 0, 0, 0};
+    emu_projection q{{0, 0, pack_on, 0, 0, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, N, K, fused_mode, tail_mode, warm_mask, tune, 0, 0, 0};
     return kernel < 0 || kernel > (int)WeightKernel::Fp8Thin ? -22 : (int)matrix_kernel((WeightKernel)kernel, q);
 }
 int emu_llama_pack_thin_kernel(int kernel, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
                                int epi, int tune) {
-    emu_projection q{{0, 0, pack_on, wide_on, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, set_n, set_k, 1, 0, 0, tune, 0, 0, 0};
+    emu_projection q{{0, 0, pack_on, wide_on, 0, 0}, rows, 0, 0, 0, N, K, norm, epi, 1, pack_rows, set_n, set_k, 1, 0, 0, tune, 0, 0, 0};
     return kernel < 0 || kernel > (int)WeightKernel::Bf16PackThin ? -22 : (int)matrix_kernel((WeightKernel)kernel, q);
 }
 int emu_bf16_pack_rows(int N, int K, int norm, int epi, int tune) {
@@ -516,6 +526,12 @@ int emu_linear_fp8w_gemm_bf16(const void* A, const void* W8, const float* wscale
     return linear_w(WeightKernel::Fp8Stream, {nullptr, U8(W8), wscale},
                     {B(A), nullptr, nullptr, B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, 0.f, epi}, S(s));
 }
+int emu_linear_fp8w_tile_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C, int M, int N,
+                              int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s) {
+    if (!A || !W8 || !wscale || !C) return -22;
+    return linear_w(WeightKernel::Fp8Tile, {nullptr, U8(W8), wscale},
+                    {B(A), nullptr, nullptr, B(bias), B(res), B(C), M, N, K, lda, ldw, ldres, ldc, 0.f, epi}, S(s));
+}
 // the four MXFP4 entry points name their kernel (the caller's matrix as a weight record, its arguments as the launch block);
 // linear_w refuses a row count outside the kernel's range
 static int linear_fp4w(WeightKernel k, const void* A, const void* W4, const void* scales, const void* bias, const void* res, const void* norm_w,
@@ -752,7 +768,8 @@ struct emu_llama {
     std::vector<Layer> layers;
     Weights head;                  // lm_head: the fp8 / MXFP4 copies cover the same rows (quantised from the shard)
     // the weight mode as the setters took it (include/emu_hip.h), fp8 and fp4 never both; what it means for a projection is call_kernel's and
-    // matrix_kernel's to say.  bf16_released (emu_llama_release_bf16; fp4 mode 3 only, which it pins): the records' bf16 pointers are null.
+    // matrix_kernel's to say.  bf16_released (emu_llama_release_bf16; fp4 mode 3, or fp8 modes 5 / 6 with fp8_all, which it pins): the
+    // records' bf16 pointers are null.
     emu_weight_mode mode{};
     // the kernel a call of `rows` rows is planned around, layers and head alike
     WeightKernel kernel_for(int rows) const { return call_kernel(mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local); }
@@ -881,7 +898,7 @@ struct LlamaPlan {
     // fuse_norm      the K-slice sums of o_proj / down_proj apply the RMSNorm behind them
     // kernel         the weight set and kernel of the call's projections (call_kernel).  Fp8Gemm: in the layers that have fp8
     //                weights.  Fp4Thin, Fp8Thin: norms stay launches.  A kernel without a bf16 GEMM behind it (KERNEL_FACTS: Fp4Gemm,
-    //                Fp8Stream): norms, RoPE / KV append and V^T stay launches -- fuse_rope and fuse_norm are off, never TwoLane
+    //                Fp8Stream, Fp8Tile): norms, RoPE / KV append and V^T stay launches -- fuse_rope and fuse_norm are off, never TwoLane
     // norm_in_gemv   one row, or two with fp8 / fp4 weights: the weight stream applies the RMSNorm in front of it itself
     // decode_tail    decode attention without the combine launch (emu_llama_set_decode_tail)
     // merge_o        the o_proj launch merges the decode attention's splits (emu_gemm_tune bit 19)
@@ -1010,7 +1027,7 @@ struct LlamaCall {
     int project(const LlamaWs& w, hipStream_t s, const bf16_t* A, const Weights& W, const bf16_t* res, const bf16_t* gain_in,
                 const bf16_t* gain_out, bf16_t* C, int rows, int N, int K, int epi, const WarmPlan& warm = WarmPlan{}) {
         const int ldres = res ? N : 0, ldc = epi == EPI_SWIGLU ? N / 2 : N;
-        if (facts(plan.kernel).bf16_gemm && !W.W) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
+        if (facts(plan.kernel).bf16_gemm && !W.W && !(plan.kernel == WeightKernel::Fp8Gemm && W.W8 && m->mode.bf16_released)) return fail(cx, -22, "emu_llama_forward: bf16 layer weights not set (released by emu_llama_release_bf16?)");
         emu_projection q = m->site(W, rows, N, K, gain_in != nullptr, epi, plan.decode_tail, plan.warm | (int)warm.ntouch);   // (the call's plan)
         const WeightKernel k = matrix_kernel(plan.kernel, q);
         if (k == WeightKernel::Fp8Gemm) return linear_q8(w, A, K, W.W8, W.s8, res, C, rows, N, K, ldres, ldc, epi, s);
@@ -1054,8 +1071,9 @@ struct LlamaCall {
         const emu_llama::Layer& L = m->layers[l];
         if (needs_fp8(plan.kernel) && !L.qkv.W8)
             return fail(cx, -22, "emu_llama_forward: fp8 decode enabled but fp8 layer weights not set");
-        // after emu_llama_release_bf16 the 4-bit set is the layer's weights (mode 3 is pinned: every row count has a 4-bit path)
-        if (m->mode.bf16_released ? !L.qkv.W4 || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
+        // after emu_llama_release_bf16 the 4-bit set (mode 3 pinned) or the fp8 set (modes 5 / 6 with fp8_all pinned) is the layer's
+        // weights: every row count has a path on it
+        if (m->mode.bf16_released ? !(m->mode.fp8_all ? L.qkv.W8 : L.qkv.W4) || !L.ln1 : !L.qkv.W) return fail(cx, -22, "emu_llama_forward: layer weights not set");
         const int rows = Bn * win.T;
         bf16_t *kc = m->kcache + l * kv_layer, *vc = m->vcache + l * kv_layer;
         if (!plan.norm_in_gemv) {                        // 2..16 rows: norm once, skinny MFMA stream; more: GEMM
@@ -1495,8 +1513,9 @@ int emu_llama_set_head_fp4(emu_llama* m, const void* lm_head4, const void* lm_sc
 int emu_llama_use_fp4(emu_llama* m, int enable) {
     if (!m) return -22;
     if (enable < 0 || enable > 3) return fail(m->ctx, -22, "emu_llama_use_fp4: modes 0 to 3");
-    if (m->mode.bf16_released && enable != 3)
-        return fail(m->ctx, -22, "emu_llama_use_fp4: the bf16 weights were released (emu_llama_release_bf16); only mode 3 runs without them");
+    if (m->mode.bf16_released && (enable != 3 || m->mode.fp8_all))
+        return fail(m->ctx, -22, m->mode.fp8_all ? "emu_llama_use_fp4: the bf16 weights were released under the fp8 set (emu_llama_release_bf16); only fp8 modes 5 / 6 with emu_llama_use_fp8_all run without them"
+                                                 : "emu_llama_use_fp4: the bf16 weights were released (emu_llama_release_bf16); only mode 3 runs without them");
     if (enable) {
         const emu_llama_cfg& c = m->cfg;
         if (m->mode.fp8)
@@ -1549,7 +1568,8 @@ int emu_llama_use_bf16_pack_wide(emu_llama* m, int on) {
 }
 int emu_llama_release_bf16(emu_llama* m) {
     if (!m) return -22;
-    if (m->mode.fp4 != 3) return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3) is on (every row count on the 4-bit set)");
+    if (m->mode.fp4 != 3 && !(m->mode.fp8 >= 5 && m->mode.fp8_all))
+        return fail(m->ctx, -22, "emu_llama_release_bf16: only while emu_llama_use_fp4(m, 3), or emu_llama_use_fp8(m, 5 | 6) with emu_llama_use_fp8_all(m, 1), is on (every row count on the 4-bit / the fp8 set)");
     if (m->decode_fused) return fail(m->ctx, -22, "emu_llama_release_bf16: the fused decode modes read the bf16 weights (emu_llama_set_decode_fused(m, 0, 0) first)");
     for (auto& l : m->layers) {
         l.qkv.W = l.o.W = l.gu.W = l.down.W = nullptr;
@@ -1601,8 +1621,9 @@ long emu_llama_tp_overlap_count(const emu_llama* m) { return m ? m->ov_forwards 
 int emu_llama_use_fp8(emu_llama* m, int enable) {
     if (!m) return -22;
     if (enable < 0 || enable > 6) return fail(m->ctx, -22, "emu_llama_use_fp8: modes 0 to 6");
-    if (enable && m->mode.bf16_released)
-        return fail(m->ctx, -22, "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
+    if (m->mode.bf16_released && (m->mode.fp8_all ? enable < 5 : enable != 0))
+        return fail(m->ctx, -22, m->mode.fp8_all ? "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only modes 5 and 6 with emu_llama_use_fp8_all run without them"
+                                                 : "emu_llama_use_fp8: the bf16 weights were released (emu_llama_release_bf16); only the fp4 mode 3 runs without them");
     if (enable && m->mode.fp4)
         return fail(m->ctx, -22, "emu_llama_use_fp8: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive (emu_llama_use_fp4(m, 0) first)");
     // (emu_llama_set_layer_fp8 was never called: it sets all of a layer's or refuses, and a model has at least one layer)
@@ -1616,6 +1637,20 @@ int emu_llama_use_fp8(emu_llama* m, int enable) {
             return fail(m->ctx, -22, "emu_llama_use_fp8: modes 3 to 6 need the fp8 weights of every layer");
     }
     m->mode.fp8 = enable;
+    if (enable < 5) m->mode.fp8_all = 0;         // the switch lives beside modes 5 / 6 only
+    return 0;
+}
+int emu_llama_use_fp8_all(emu_llama* m, int on) {
+    if (!m) return -22;
+    if (on != 0 && on != 1) return fail(m->ctx, -22, "emu_llama_use_fp8_all: 0 or 1");
+    if (!on && m->mode.bf16_released && m->mode.fp8_all)
+        return fail(m->ctx, -22, "emu_llama_use_fp8_all: the bf16 weights were released (emu_llama_release_bf16); the switch is pinned");
+    if (on) {
+        if (m->mode.fp4) return fail(m->ctx, -22, "emu_llama_use_fp8_all: the fp4 stream is on; the fp8 and fp4 weight streams are exclusive");
+        if (m->mode.fp8 < 5) return fail(m->ctx, -22, "emu_llama_use_fp8_all: needs emu_llama_use_fp8(m, 5 | 6) (every row count below 65 on the fp8 set)");
+        if (!m->head.W8 || !m->head.s8) return fail(m->ctx, -22, "emu_llama_use_fp8_all: the head's fp8 copy is not set (emu_llama_set_head_fp8)");
+    }
+    m->mode.fp8_all = on;
     return 0;
 }
 int emu_llama_set_head(emu_llama* m, const void* final_norm, const void* lm_head, const void* embed, const void* rope_cos,
@@ -1891,8 +1926,9 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
 int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* logits, int ld, void* workspace,
                      size_t ws_bytes, emu_stream_t s) {
     if (!m || !m->final_norm) return -22;
-    // after emu_llama_release_bf16 the 4-bit head is the head (mode 3 is pinned: every row count has a 4-bit path in llama_head)
-    if (m->mode.bf16_released ? m->mode.fp4 != 3 || !m->head.W4 : !m->head.W) return -22;
+    // after emu_llama_release_bf16 the 4-bit head (mode 3 pinned) or the fp8 head (modes 5 / 6 with fp8_all pinned) is the head: every
+    // row count has a path on it in llama_head
+    if (m->mode.bf16_released ? (m->mode.fp8_all ? m->mode.fp8 < 5 || !m->head.W8 : m->mode.fp4 != 3 || !m->head.W4) : !m->head.W) return -22;
     const emu_llama_cfg& c = m->cfg;
     if (m->head_rows < 0) return llama_head(m, B(hidden), ldh, M, B(logits), c.vocab, ld, B(workspace), ws_bytes, S(s));
     // vocabulary-sharded head (tensor parallelism): this rank streams its rows of lm_head only (4035 of 32 274 at TP = 8:

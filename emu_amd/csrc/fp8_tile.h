@@ -1,5 +1,6 @@
 // Device code shared by the two fp8 (e4m3, W8A16) matrix-core kernels (gemv_fp8_thin.hip: 1..16 rows, k split over the waves;
-// gemm_fp8.hip: 17..64 rows, a two-dimensional tile): the geometry of one K stage in LDS and the e4m3 -> bf16 fragment conversion.
+// gemm_fp8.hip: 17..64 rows, a two-dimensional tile, and 65 rows and more, the same tile at 128 activation rows on a two-dimensional
+// grid): the geometry of one K stage in LDS and the e4m3 -> bf16 fragment conversion.
 // A stage is F8_KC = 256 k: 256 bytes per weight row (16 chunks of 16 bytes), 512 per activation row (32 chunks).  Both arrive by
 // 16-byte LDS-DMA, the LDS image lane-linear, the swizzle carried by the source address: chunk c of staged row r sits in slot
 // c ^ (r & 15).  The epilogue (store_c4) is fp4_tile.h's.

@@ -1067,12 +1067,15 @@ bool fp4_mfma_ok(const GemvArgs& a) { return a.M >= 17 && fp4_mfma_shape_ok(gemv
 // stream asks (gemv_thin_plan), the row count aside.  Ring depth: as deep as a CU's 160 KiB of LDS hold for one workgroup (narrow 4 x
 // 32 KiB, one tile 3 x 48 KiB); emu_gemm_tune bit 20 gives the narrow form a ring of 2 (64 KiB: two workgroups per CU), the A/B twin
 // (tools/fp8_mid_time.py --ab, profiles/fp8_mid.md).
+// what the forms of the W8A16 GEMM ask of a shape, the row count aside
+static bool fp8_gemm_shape_ok(const GemvShape& sh) {
+    return sh.fp8 && !sh.fp4 && !sh.norm && sh.w_aligned && sh.x_aligned && sh.N >= 1 && sh.K >= 256 && !(sh.K % 256) && !(sh.ldx & 7) &&
+           !(sh.ldw & 15) && sh.ldw >= sh.K && sh.ldx >= sh.K && epi3_ok(sh);
+}
 GemmFp8wPlan gemm_fp8w_plan(const GemvShape& sh, int tune) {
     GemmFp8wPlan refused{};
     refused.status = -22;
-    if (!sh.fp8 || sh.fp4 || sh.norm || !sh.w_aligned || !sh.x_aligned || sh.M < 17 || sh.M > 64 || sh.N < 1 || sh.K < 256 || (sh.K % 256) ||
-        (sh.ldx & 7) || (sh.ldw & 15) || sh.ldw < sh.K || sh.ldx < sh.K || !epi3_ok(sh))
-        return refused;
+    if (sh.M < 17 || sh.M > 64 || !fp8_gemm_shape_ok(sh)) return refused;
     GemmFp8wPlan p{};
     p.form = sh.M <= 32 ? 1 : 2;
     p.bm = sh.M <= 32 ? 32 : 64;
@@ -1086,6 +1089,28 @@ GemmFp8wPlan gemm_fp8w_plan(const GemvShape& sh, int tune) {
 int launch_gemm_fp8w_stream(const GemvArgs& a, hipStream_t s) {
     const GemmFp8wPlan p = gemm_fp8w_plan(gemv_shape_of(a), emu_gemm_tune_get());
     return p.status || !mfma_pointers_ok(a) ? -22 : launch_gemm_fp8w(a, p, s);
+}
+// The same kernel for 65 rows and more: 64 weight rows x 128 activation rows per workgroup, grid.x over the row tiles so that the
+// workgroups in flight share weight rows in L2, grid.y (at most 65535) over the column tiles; a ring of two 80 KiB stages is the CU's
+// 160 KiB of LDS.  No tune bit is read.
+GemmFp8tPlan gemm_fp8t_plan(const GemvShape& sh, int) {
+    GemmFp8tPlan refused{};
+    refused.status = -22;
+    if (sh.M < 65 || !fp8_gemm_shape_ok(sh) || (sh.N + 63) / 64 > 65535) return refused;
+    GemmFp8tPlan p{};
+    p.form = 3;
+    p.bm = 128;
+    p.kc = 256;
+    p.stages = 2;
+    p.lds_bytes = p.stages * (64 * p.kc + p.bm * p.kc * 2);
+    p.grid_x = (sh.M + 127) / 128;
+    p.grid_y = (sh.N + 63) / 64;
+    p.block = 256;
+    return p;
+}
+int launch_gemm_fp8t_stream(const GemvArgs& a, hipStream_t s) {
+    const GemmFp8tPlan p = gemm_fp8t_plan(gemv_shape_of(a), emu_gemm_tune_get());
+    return p.status || !mfma_pointers_ok(a) ? -22 : launch_gemm_fp8t(a, p, s);
 }
 
 // The 13-bit packed twin of the bf16 thin stream (gemv_pack_thin.hip), from the bf16 plan of the same shape: it exists for kch 32.
@@ -1133,6 +1158,12 @@ int emu_gemm_fp8w_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune,
     GemvShape sh{};
     sh.M = M; sh.N = N; sh.K = K; sh.ldx = ldx; sh.ldw = ldw; sh.epi = epi; sh.fp8 = sh.w_aligned = sh.x_aligned = 1;
     return (*out = gemm_fp8w_plan(sh, tune)).status;                 // refused: every field but the status is 0
+}
+int emu_gemm_fp8t_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemm_fp8t_plan_t* out) {
+    if (!out) return -22;
+    GemvShape sh{};
+    sh.M = M; sh.N = N; sh.K = K; sh.ldx = ldx; sh.ldw = ldw; sh.epi = epi; sh.fp8 = sh.w_aligned = sh.x_aligned = 1;
+    return (*out = gemm_fp8t_plan(sh, tune)).status;                 // refused: every field but the status is 0
 }
 // the older view of the fp8 few-row plan: row-contiguous or strided operands on aligned buffers, no fused norm
 int emu_gemv_fp8_thin_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemv_fp8_thin_plan_t* out) {

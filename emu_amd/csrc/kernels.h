@@ -122,6 +122,12 @@ using GemmFp8wPlan = emu_gemm_fp8w_plan_t;
 GemmFp8wPlan gemm_fp8w_plan(const GemvShape& shape, int tune);
 int launch_gemm_fp8w(const GemvArgs& a, const GemmFp8wPlan& p, hipStream_t s);
 int launch_gemm_fp8w_stream(const GemvArgs& a, hipStream_t s);
+// The same kernel's form for 65 rows and more (64 weight rows x 128 activation rows, a two-dimensional grid, cached weight loads), with
+// the same three steps: gemm_fp8t_plan (C ABI: emu_gemm_fp8t_plan), launch_gemm_fp8t, launch_gemm_fp8t_stream.
+using GemmFp8tPlan = emu_gemm_fp8t_plan_t;
+GemmFp8tPlan gemm_fp8t_plan(const GemvShape& shape, int tune);
+int launch_gemm_fp8t(const GemvArgs& a, const GemmFp8tPlan& p, hipStream_t s);
+int launch_gemm_fp8t_stream(const GemvArgs& a, hipStream_t s);
 
 // Implicit-GEMM 3x3 convolution over an NHWC activation: A is [B, Hin, Win, Cin], the GEMM row m is the output
 // pixel (b, yo, xo), K = 9*Cin ordered (ky, kx, ci) -- weights repacked to [Cout, 3, 3, Cin].  Cin % 64 == 0.

@@ -183,9 +183,10 @@ class LlamaEngine:
     # the weight mode as the setters below left it (defaults of the class, so that every engine has them before any setter ran)
     fp8_decode = fp8_wide = False      # use_fp8(True[, wide=True]): 1..2 [and 3..16] rows stream the fp8 set
     fp8_mid = False            # use_fp8(True, wide=True, mid=True) is on: steps of 17..64 rows stream the fp8 set too
+    fp8_all = False            # use_fp8(True, wide=True, mid=True, all_rows=True) is on: every row count runs the fp8 set
     fp4_decode = fp4_wide = False      # use_fp4(True[, wide=True]): the same row ranges on the MXFP4 set
     fp4_all = False            # use_fp4(True, wide=True, all_rows=True) is on: every row count runs the 4-bit set
-    bf16_released = False      # release_bf16() was called: the bf16 matrices and lm_head are gone, fp4_all is pinned
+    bf16_released = False      # release_bf16() was called: the bf16 matrices and lm_head are gone, fp4_all / fp8_all is pinned
     bf16_pack_on = bf16_pack_wide = False      # use_bf16_pack / use_bf16_pack_wide: the 13-bit packed streams at 1 / 4..16 rows
 
     def __init__(self, cfg: LlamaCfg, vocab: int, ctx: EmuHipContext):
@@ -391,6 +392,8 @@ class LlamaEngine:
 
     def weight_bytes_per_token(self) -> int:
         """Algorithmic bytes one decode step of THIS shard must stream (all packed matrices once + lm_head)."""
+        if self.bf16_released and self.fp8_all:      # only the fp8 tensors are left: one byte per weight
+            return sum(q.numel() for q, _ in self._fp8.values())
         if self.bf16_released:          # only the 4-bit tensors are left: their shapes
             return sum(self._fp4_shape(k)[0] * mxfp4.bytes_per_row(self._fp4_shape(k)[1]) for k in self._fp4_keys())
         if self.fp4_decode:             # MXFP4: K/2 element bytes + K/32 scale bytes per row
@@ -545,21 +548,43 @@ class LlamaEngine:
             raise RuntimeError("quantize_fp8: load all weights first")
         if self.bf16_released:
             raise RuntimeError("quantize_fp8: the bf16 weights were released (release_bf16); there is nothing left to quantise")
-        if getattr(self, "_fp8", None):
-            return
-        self._fp8 = {}
-        for i in range(self.cfg.num_hidden_layers):
-            a = []
-            for k in ("wqkv", "wo", "wgu", "wdown"):
-                q, sc = ops.quantize_fp8_rows(self._keep[f"{i}.{k}"])
-                self._fp8[f"{i}.{k}"] = (q, sc)
-                a += [q.data_ptr(), sc.data_ptr()]
-            check(lib().emu_llama_set_layer_fp8(self.handle, i, *a), "emu_llama_set_layer_fp8", self.ctx.handle)
-        q, sc = ops.quantize_fp8_rows(self.lm_head)
-        self._fp8["lm_head"] = (q, sc)
-        check(lib().emu_llama_set_head_fp8(self.handle, q.data_ptr(), sc.data_ptr()), "emu_llama_set_head_fp8")
+        self.__dict__.setdefault("_fp8", {})
+        for key in self._fp4_keys():                               # (the same keys; whatever load_fp8 provided is kept)
+            if key not in self._fp8:
+                self._fp8[key] = ops.quantize_fp8_rows(self._fp4_source(key))
+                self._fp8_register(key)
 
-    def use_fp8(self, enable: bool = True, prefill: bool = False, wide: bool = False, mid: bool = False) -> None:
+    def _fp8_register(self, key: str) -> None:
+        """Hand the library the pointers of a layer once its four matrices are here (or of the head)."""
+        if key == "lm_head":
+            q, sc = self._fp8[key]
+            check(lib().emu_llama_set_head_fp8(self.handle, q.data_ptr(), sc.data_ptr()), "emu_llama_set_head_fp8", self.ctx.handle)
+            return
+        i = key.split(".")[0]
+        if all(f"{i}.{k}" in self._fp8 for k in self._FP4_KINDS):
+            a = [t.data_ptr() for k in self._FP4_KINDS for t in self._fp8[f"{i}.{k}"]]
+            check(lib().emu_llama_set_layer_fp8(self.handle, int(i), *a), "emu_llama_set_layer_fp8", self.ctx.handle)
+
+    def load_fp8(self, key: str, q: torch.Tensor, scale: torch.Tensor) -> None:
+        """Register externally prepared fp8 tensors (``ops.quantize_fp8_rows`` or any quantiser that writes e4m3fn bytes and one fp32
+        scale per row) for ``"<layer>.wqkv|wo|wgu|wdown"`` or ``"lm_head"``: ``q`` uint8 [N, K], ``scale`` float32 [N] for the [N, K]
+        packed bf16 matrix of this rank (the tensor-parallel shard; lm_head: the rows this rank holds).  A layer is registered once
+        its four matrices are here; ``quantize_fp8`` fills in whatever was not loaded."""
+        src = self._fp4_source(key)
+        if src is None:
+            raise RuntimeError(f"load_fp8({key!r}): load the bf16 weights first (their packed shapes define the fp8 shapes)")
+        N, K = src.shape
+        for name, t, dt, shape in (("q", q, torch.uint8, (N, K)), ("scale", scale, torch.float32, (N,))):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape:
+                raise ValueError(f"load_fp8({key!r}): {name} must be {dt} {shape}, got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if self.fp8_decode:
+            raise RuntimeError("load_fp8: switch the fp8 stream off first (use_fp8(False)); captured graphs hold the old pointers")
+        self.__dict__.setdefault("_fp8", {})
+        self._fp8[key] = (q.to(self.device).contiguous(), scale.to(self.device).contiguous())
+        self._fp8_register(key)
+
+    def use_fp8(self, enable: bool = True, prefill: bool = False, wide: bool = False, mid: bool = False, all_rows: bool = False) -> None:
         """Switch the decode stream between the bf16 and the fp8 weights (invalidates captured decode graphs).  The matrices are
         quantised on the device first (``quantize_fp8``).  Exclusive with ``use_fp4``.
 
@@ -574,18 +599,33 @@ class LlamaEngine:
         ``wide=True, mid=True``: steps of 17..64 rows (four prompts x five beams, contrastive search on a batch) stream the fp8 set
         too, through the W8A16 GEMM (csrc/gemm_fp8.hip; activations bf16; a prompt of 17..64 rows runs without the RoPE and RMSNorm
         epilogue fusions of the bf16 prefill).  Same width requirement as ``wide``; ``mid`` without ``wide`` is a ``ValueError``.
-        Above 64 rows nothing changes: bf16, or the W8A8 GEMMs with ``prefill=True``.  Not a reference feature; quality on a trained
-        checkpoint is unmeasured."""
+        Above 64 rows nothing changes without ``all_rows``: bf16, or the W8A8 GEMMs with ``prefill=True``.
+        ``wide=True, mid=True, all_rows=True``: calls of 65 rows and more (a prompt, ``score(via="prefill")``, beams x batch) stay on
+        the fp8 set too, through the 64 x 128 form of the W8A16 GEMM (csrc/gemm_fp8.hip; weight-only, bit-identical row by row to
+        the 17..64-row form; the RoPE and RMSNorm epilogue fusions and the two-lane prefill are off).  With ``prefill=True`` the layer
+        projections keep the faster W8A8 GEMMs there and only the head, which has none, runs the new form.  One generation then sees
+        one weight set and ``release_bf16`` may free the bf16 matrices.  Needs the head's fp8 copy; same width requirement as
+        ``wide``; ``all_rows`` without ``mid`` is a ``ValueError``.  Not a reference feature; quality on a trained checkpoint is
+        unmeasured."""
         if mid and not wide:
             raise ValueError("use_fp8: mid=True needs wide=True (modes 5 / 6 are modes 3 / 4 plus the steps of 17..64 rows)")
+        if all_rows and not mid:
+            raise ValueError("use_fp8: all_rows=True needs wide=True, mid=True (the switch sits beside modes 5 / 6: the calls of 65 rows and more)")
         if enable and not self.bf16_released:   # (after release_bf16 the library refuses and says why)
             self.quantize_fp8()
         mode = ((2 if prefill else 1) + (2 if wide else 0) + (2 if mid else 0)) if enable else 0
+        if self.bf16_released and not (enable and all_rows):     # (before the mode moves: the library pins the switch, and says why)
+            check(lib().emu_llama_use_fp8_all(self.handle, 0), "emu_llama_use_fp8_all", self.ctx.handle)
         check(lib().emu_llama_use_fp8(self.handle, mode), "emu_llama_use_fp8", self.ctx.handle)
         self.fp8_decode = bool(enable)
         self.fp8_wide = bool(enable and wide)
         self.fp8_mid = bool(enable and mid)
+        self.fp8_all = False                                     # (a mode below 5 clears the switch in the library)
         self._mode_changed()
+        if mode >= 5:
+            check(lib().emu_llama_use_fp8_all(self.handle, 1 if all_rows else 0), "emu_llama_use_fp8_all", self.ctx.handle)
+            self.fp8_all = bool(all_rows)
+            self._mode_changed()
 
     def fp8_dequantized(self, key: str) -> torch.Tensor:
         """fp32 value of a registered fp8 tensor (tests: feed the oracle the exact weights the stream uses)."""
@@ -607,7 +647,8 @@ class LlamaEngine:
         if key != "lm_head" and (kind not in self._FP4_KINDS or not layer.isdigit() or int(layer) >= self.cfg.num_hidden_layers):
             raise KeyError(f"fp4 key {key!r}: expected '<layer>.wqkv|wo|wgu|wdown' or 'lm_head'")
         if self.bf16_released:
-            return torch.empty(self._fp4_shape(key), dtype=BF16, device="meta")
+            shape = tuple(self._fp8[key][0].shape) if self.fp8_all else self._fp4_shape(key)
+            return torch.empty(shape, dtype=BF16, device="meta")
         return self.lm_head if key == "lm_head" else self._keep[key]
 
     def _fp4_keys(self):
@@ -690,11 +731,15 @@ class LlamaEngine:
 
     def release_bf16(self) -> None:
         """Free the bf16 packed matrices and the bf16 lm_head; needs ``use_fp4(True, wide=True, all_rows=True)``, which it pins (33B:
-        65 GB leave, the 17 GB of 4-bit tensors stay; the norm gains, the embedding and the RoPE tables stay).  Afterwards
-        ``use_fp4(False)``, ``use_fp4(True)`` without ``all_rows``, ``use_fp8`` and ``set_decode_fused(!= 0)`` raise with the
-        library's message; there is no way back short of a new engine.  Invalidates captured decode graphs."""
-        if not self.fp4_all:
-            raise RuntimeError("release_bf16: switch every row count to the 4-bit set first (use_fp4(True, wide=True, all_rows=True))")
+        65 GB leave, the 17 GB of 4-bit tensors stay; the norm gains, the embedding and the RoPE tables stay), or
+        ``use_fp8(True, wide=True, mid=True, all_rows=True)`` with or without ``prefill``, which it pins likewise (the 32 GB of fp8
+        tensors stay).  Afterwards ``use_fp4(False)``, ``use_fp4(True)`` without ``all_rows``, ``use_fp8`` and
+        ``set_decode_fused(!= 0)`` raise with the library's message -- after an fp8 release everything but
+        ``use_fp8(True, wide=True, mid=True, all_rows=True)``, ``use_fp4`` included; there is no way back short of a new engine.
+        Invalidates captured decode graphs."""
+        if not (self.fp4_all or self.fp8_all):
+            raise RuntimeError("release_bf16: switch every row count to one quantised set first (use_fp4(True, wide=True, all_rows=True) "
+                               "or use_fp8(True, wide=True, mid=True, all_rows=True))")
         check(lib().emu_llama_release_bf16(self.handle), "emu_llama_release_bf16", self.ctx.handle)
         self.bf16_released = True
         for key in [k for k in self._keep if k.split(".")[1] in self._FP4_KINDS]:

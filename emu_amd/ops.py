@@ -295,8 +295,8 @@ def linear_fp8w(x, w8, wscale, bias=None, res=None, norm_w=None, eps: float = 0.
 
 
 def _linear_fp8w_mfma(fn, symbol, lo, hi, beyond, x, w8, wscale, bias, res, epi, out):
-    """The two W8A16 matrix-core entry points (``fn``: the wrapper's name, ``symbol``: its C function) differ in their row range
-    ``lo..hi`` alone; ``beyond``: where a caller with other row counts should go.  Every argument is checked before any device work."""
+    """The three W8A16 matrix-core entry points (``fn``: the wrapper's name, ``symbol``: its C function) differ in their row range
+    ``lo..hi`` alone (``hi`` None: no upper end); ``beyond``: where a caller with other row counts should go.  Every argument is checked before any device work."""
     for name, t, dt in (("x", x, BF16), ("w8", w8, torch.uint8), ("wscale", wscale, torch.float32), ("bias", bias, BF16),
                         ("res", res, BF16), ("out", out, BF16)):
         if t is None and name in ("bias", "res", "out"):
@@ -310,8 +310,12 @@ def _linear_fp8w_mfma(fn, symbol, lo, hi, beyond, x, w8, wscale, bias, res, epi,
         raise ValueError(f"{fn}: x [M, K] and w8 [N, K] must agree in K, got {tuple(x.shape)} and {tuple(w8.shape)}")
     M, K = x.shape
     N = w8.shape[0]
-    if not lo <= M <= hi:
+    if hi is None and M < lo:
+        raise ValueError(f"{fn}: {lo} rows and more, got M = {M} ({beyond})")
+    if hi is not None and not lo <= M <= hi:
         raise ValueError(f"{fn}: {lo}..{hi} rows, got M = {M} ({beyond})")
+    if (N + 63) // 64 > 65535 and hi is None:
+        raise ValueError(f"{fn}: at most 65535 column tiles of 64 weight rows, got N = {N}")
     if N < 1 or K < 256 or K % 256:
         raise ValueError(f"{fn}: N >= 1 and K a multiple of 256, at least 256; got N = {N}, K = {K}")
     if epi not in (EPI_NONE, EPI_RESID, EPI_SWIGLU):
@@ -358,6 +362,15 @@ def linear_fp8w_gemm(x, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, ou
     return _linear_fp8w_mfma("linear_fp8w_gemm", "emu_linear_fp8w_gemm_bf16", 17, 64,
                              "up to 16 rows: linear_fp8w_thin; 65 and more: linear, or the W8A8 GEMM linear_fp8",
                              x, w8, wscale, bias, res, epi, out)
+
+
+def linear_fp8w_tile(x, w8, wscale, bias=None, res=None, epi: int = EPI_NONE, out=None):
+    """The same product for 65 rows and more (prompts, scoring prefills, beams x batch): the 64 x 128 form of csrc/gemm_fp8.hip's
+    kernel, same arguments, requirements, epilogues and rounding points as ``linear_fp8w_gemm``, whose results it repeats bit for bit
+    row by row; see emu_linear_fp8w_tile_bf16.  Every argument is checked here, before any device work: a ``ValueError`` says what is
+    wrong, nothing falls back to another kernel."""
+    return _linear_fp8w_mfma("linear_fp8w_tile", "emu_linear_fp8w_tile_bf16", 65, None,
+                             "up to 16 rows: linear_fp8w_thin; 17..64: linear_fp8w_gemm", x, w8, wscale, bias, res, epi, out)
 
 
 def rmsnorm(x, w, eps: float, out=None):

@@ -163,6 +163,17 @@ typedef struct {
     int status, form, bm, kc, stages, lds_bytes, grid, block;
 } emu_gemm_fp8w_plan_t;
 int emu_gemm_fp8w_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemm_fp8w_plan_t* out);
+/* CPU test hook (tests/test_fp8_all_host.py): what emu_linear_fp8w_tile_bf16 and the engine's calls of 65 rows and more under
+ * emu_llama_use_fp8_all launch (gemm_fp8.hip, the third form of the same kernel) -- host arithmetic only.  form 3: a workgroup owns 64
+ * weight rows x bm = 128 activation rows (four waves 2 x 2, a converted weight fragment feeds four MFMAs); kc = 256: k per stage;
+ * stages 2: the LDS ring; lds_bytes = stages * (64 * kc + bm * kc * 2) = 163840, a CU's whole LDS; grid_x = ceil(M / 128) walks the
+ * row tiles (the workgroups in flight share weight rows in L2), grid_y = ceil(N / 64) the column tiles; block 256.  tune: no bit is
+ * read.  Returns 0, or -22 (then the other fields are 0): M < 65, more than 65535 column tiles, and whatever emu_gemm_fp8w_plan
+ * refuses apart from the row count. */
+typedef struct {
+    int status, form, bm, kc, stages, lds_bytes, grid_x, grid_y, block;
+} emu_gemm_fp8t_plan_t;
+int emu_gemm_fp8t_plan(int M, int N, int K, int ldx, int ldw, int epi, int tune, emu_gemm_fp8t_plan_t* out);
 /* Bench hook: A/B switches of single dispatch decisions (0 = the shipped heuristic).  Bits 0, 4, 5, 14, 17 and 18: retired,
  * ignored.  Bit 1: the K-slice workgroups of a split GEMM are dealt tile by tile round-robin over the XCDs (the order before
  * round 3) instead of the XCD-aware slice-major order.  Bit 2: 4..16-row linears skip the LDS-DMA + MFMA stream (gemv_thin.hip)
@@ -252,6 +263,15 @@ int emu_linear_fp8w_thin_bf16(const void* A, const void* W8, const float* wscale
  * on the dequantised weights, up to fp32 summation order.  emu_linear_fp8w_thin_bf16 keeps answering -22 for M > 16.  Not a reference
  * feature. */
 int emu_linear_fp8w_gemm_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C,
+                              int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s);
+/* The same product, arguments, epilogues, rounding points and requirements for M >= 65 rows (the third form of gemm_fp8.hip's kernel:
+ * a workgroup owns 64 weight rows x 128 activation rows, every converted weight fragment feeds four MFMAs, grid = row tiles x column
+ * tiles, at most 65535 of the latter; ragged M and N; emu_gemm_fp8t_plan names the launch).  Every output element sums the same 32-k
+ * products in the same order as in emu_linear_fp8w_gemm_bf16's 64 x 64 form, so a row's result is that call's, bit for bit, and does
+ * not depend on how many rows share the call.  M < 65 and every violated requirement: -22, nothing is launched.
+ * emu_linear_fp8w_gemm_bf16 keeps answering -22 for M > 64.  No fused RMSNorm, no RoPE epilogue, no K-slicing.  Not a reference
+ * feature. */
+int emu_linear_fp8w_tile_bf16(const void* A, const void* W8, const float* wscale, const void* bias, const void* res, void* C,
                               int M, int N, int K, int lda, int ldw, int ldres, int ldc, int epi, emu_stream_t s);
 /* MXFP4 (OCP microscaling) weights, the 4-bit weight-only stream; emu_amd/mxfp4.py is the definition of the format.
  *   elements  uint8 [N, K/2]: element 2j in the low nibble of byte j, 2j+1 in the high nibble; a code is a sign bit (8) and an
@@ -625,12 +645,22 @@ int emu_llama_set_layer(emu_llama* m, int layer, const void* wqkv, const void* w
  * RMSNorm launches stay in front of the projections and a prompt of 17..64 rows runs the unfused RoPE / KV append and V^T launches
  * (no RoPE epilogue, no K-slice sum + RMSNorm fusion at those row counts).  Above 64 rows mode 5 is mode 3 (bf16) and mode 6 is
  * mode 4 (W8A8 GEMMs).  Same width and every-layer requirements as modes 3 and 4.  Modes 0..4 are what they were.
- * Accuracy on a trained checkpoint is unmeasured. */
+ * emu_llama_use_fp8_all(m, 1), a switch beside modes 5 / 6: every call of 65 rows and more (a prompt, a scoring prefill, beams x
+ * batch) stays on the fp8 set too -- under mode 5 qkv, o_proj, gate/up, down and the head run emu_linear_fp8w_tile_bf16's kernel
+ * (RMSNorm, RoPE / KV append and V^T stay launches; no RoPE epilogue, no K-slice sum + RMSNorm fusion, no two-lane prefill); under
+ * mode 6 the layer projections keep the W8A8 GEMMs and the head, which has none, runs that kernel.  It needs mode 5 or 6 (so their
+ * width and every-layer requirements: TP = 1 / 2 shards of the 33B shapes, TP = 4 / 8 refused) and the head's fp8 copy, and is
+ * refused while fp4 is on (-22, with a message).  emu_llama_use_fp8 with a mode below 5 clears it.  With it on emu_llama_release_bf16
+ * is valid (see there): afterwards only emu_llama_use_fp8(m, 5 | 6) is accepted, the switch cannot be cleared, and
+ * emu_llama_use_fp8(m, < 5), emu_llama_use_fp4(m, any), emu_llama_set_decode_fused(m, != 0, ..) and the bf16 pack setters answer
+ * -22 with a message that names the release.  Out of scope: TP = 4 / 8 widths (a partial last K stage), a fused RoPE / RMSNorm
+ * epilogue in the new form, loading a checkpoint straight to fp8.  Accuracy on a trained checkpoint is unmeasured. */
 int emu_llama_set_layer_fp8(emu_llama* m, int layer, const void* wqkv8, const float* sqkv, const void* wo8,
                             const float* so, const void* wgu8, const float* sgu, const void* wdown8,
                             const float* sdown);
 int emu_llama_set_head_fp8(emu_llama* m, const void* lm_head8, const float* lm_scale);
 int emu_llama_use_fp8(emu_llama* m, int enable);
+int emu_llama_use_fp8_all(emu_llama* m, int on);
 /* Optional MXFP4 decode stream (not in the reference; 0.53125 byte per weight, 0.53 of the fp8 stream's bytes).  W4 / scales: the
  * two tensors of emu_quantize_mxfp4_rows over the SAME packed (and, under tensor parallelism, sharded) bf16 matrix -- or prepared
  * offline by any quantiser that writes the format (emu_amd/mxfp4.py), the scale rows of every matrix at the stride that
@@ -650,7 +680,7 @@ int emu_llama_use_fp8(emu_llama* m, int enable);
  * gate/up, down and the head (whole or sharded) through emu_linear_fp4w_gemm_bf16's kernel, so no row count reads a bf16 matrix.
  * The RMSNorm launches stay in front of the projections; RoPE / KV append, V^T and flash attention are the unfused launches (no
  * RoPE epilogue, no K-slice sum + RMSNorm fusion, no two-lane prefill while the mode is on).  Same width requirement as mode 2.
- * emu_llama_release_bf16(m): valid only in mode 3 (else -22).  Forgets every layer's four bf16 matrix pointers and the bf16 lm_head
+ * emu_llama_release_bf16(m): valid only in mode 3, or in fp8 mode 5 / 6 with emu_llama_use_fp8_all on (else -22).  Forgets every layer's four bf16 matrix pointers and the bf16 lm_head
  * pointer, so the caller may free them (33B: 65 GB leave, 17 GB of 4-bit tensors stay); the norm gains, the embedding and the RoPE
  * tables stay.  From then on emu_llama_use_fp4(m, 0 | 1 | 2), emu_llama_use_fp8(m, != 0) and emu_llama_set_decode_fused(m, != 0, ..)
  * answer -22 with a message that names the release; there is no way back. */
@@ -664,14 +694,18 @@ int emu_llama_release_bf16(emu_llama* m);
  * The kernels: 0 bf16 (the weight stream up to 8 / 16 rows, GEMMs above); 1 the fp8 stream (1..2 rows); 2 W8A8 GEMMs (17 rows and
  * more); 3 the MXFP4 stream (1..2 rows); 4 the MXFP4 matrix-core stream (3..16 rows); 5 the MXFP4 GEMM (17 rows and more); 6 the
  * 13-bit packed bf16 stream (1 row); 7 the fp8 matrix-core stream (3..16 rows); 8 the packed matrix-core stream (4..16 rows); 9 the
- * fp8 W8A16 GEMM (17..64 rows).  Under the weight-stream profiler a launch over [N, K] is priced at 2NK bytes (0 where it streams),
- * NK (1, 7, 9), N(K/2 + K/32) (3, 4, 5), the bytes its packed set stores (6, 8), nothing (2 and the bf16 GEMMs).
+ * fp8 W8A16 GEMM (17..64 rows); 10 its form for 65 rows and more (64 weight rows x 128 activation rows; emu_linear_fp8w_tile_bf16).
+ * Under the weight-stream profiler a launch over [N, K] is priced at 2NK bytes (0 where it streams), NK (1, 7, 9, 10), N(K/2 + K/32)
+ * (3, 4, 5), the bytes its packed set stores (6, 8), nothing (2 and the bf16 GEMMs).  10, like 5, has no bf16 GEMM behind it: norms,
+ * RoPE / KV append and V^T stay launches under it and it never runs the two-lane prefill.
  * emu_weight_mode: what the setters took -- fp8 0..6 (emu_llama_use_fp8), fp4 0..3 (emu_llama_use_fp4), never both non-zero; pack,
- * pack_wide (emu_llama_use_bf16_pack, _wide); bf16_released (emu_llama_release_bf16).
+ * pack_wide (emu_llama_use_bf16_pack, _wide); bf16_released (emu_llama_release_bf16); fp8_all 0 / 1 (emu_llama_use_fp8_all: a switch
+ * beside fp8 modes 5 / 6, as pack_wide is beside pack; with it off every answer is what it was).
  * The call-level rule (emu_llama_weight_kernel is this alone): mode, rows = B*T of the call and the shard's hidden, heads_local *
  * head_dim and ffn_local give the kernel the call is planned around.  1..2 rows: 3 if fp4, 1 if fp8, else 0.  3..16 rows: 4 in fp4
  * modes 2, 3; 7 in fp8 modes 3..6 when the three widths are multiples of 256; else 0.  17 rows and more: 5 in fp4 mode 3; 9 in fp8
- * modes 5, 6 up to 64 rows, same widths; 2 in fp8 modes 2, 4, 6 when the widths are multiples of 128; else 0.
+ * modes 5, 6 up to 64 rows, same widths; 10 in fp8 mode 5 under fp8_all at 65 rows and more, same widths; 2 in fp8 modes 2, 4, 6
+ * when the widths are multiples of 128 (mode 6 keeps the faster W8A8 prefill for the layer projections under fp8_all); else 0.
  * The matrix-level rule: that answer and the facts of ONE matrix at one call site give the kernel that launches, and norm_in_stream
  * (out) = the RMSNorm rides in the weight stream.  [N, K], epi: the projection.  has_fp8: the matrix has an fp8 copy.  pack_rows,
  * set_n, set_k: the rows per group (0: none) and shape of its registered packed set.  fused_mode, tail_mode, warm_mask: what inhibits
@@ -679,13 +713,15 @@ int emu_llama_release_bf16(emu_llama* m);
  * L2-warm boundaries its call and this launch carry, the head emu_llama_set_decode_tail / _l2_warm as set.  tune: the emu_gemm_tune
  * mask.  head = 0, a layer projection: norm = its call fuses the norm in front (1..2 rows on kernels 1, 3; one row on 0; never in a
  * chunk step on 0), and norm_in_stream = norm; 2 runs as 0 when !has_fp8.  head = 1 (norm is not read, the head always has one in
- * front; ws_fits: the caller's workspace holds the normalised rows): 2 runs as 0, and so do 1, 7, 9 when !has_fp8, 7 when !ws_fits,
+ * front; ws_fits: the caller's workspace holds the normalised rows): 2 runs as 10 under fp8_all when has_fp8, rows >= 65 and
+ * K % 256 == 0, else as 0, and so do 1, 7, 9, 10 when !has_fp8, 7 when !ws_fits && !(bf16_released && fp8_all),
  * 4 when !ws_fits && !bf16_released; norm_in_stream = kernels 1, 3, and 0 at one row or, when !ws_fits, up to 8 rows.  Then, either
  * site, 0 becomes 6 when pack is on, rows == 1, no inhibitor is set and the set is of this [N, K] with emu_bf16_pack_rows(N, K,
  * norm_in_stream, epi, tune) == pack_rows; and 0 becomes 8 when pack and pack_wide are on, 4 <= rows <= 16, !norm_in_stream, the set
  * is of this [N, K] and emu_gemv_pack_thin_plan has a plan for the shape.  Every other kernel passes through.
- * Returns the kernel, or -22: q null, a mode out of range or both non-zero, rows / a width / N / K < 1, pack_rows or warm_mask < 0. */
-typedef struct emu_weight_mode { int fp8, fp4, pack, pack_wide, bf16_released; } emu_weight_mode;
+ * Returns the kernel, or -22: q null, a mode out of range or both non-zero, fp8_all outside 0 / 1 or set with fp8 below 5 (so with
+ * any fp4 mode), rows / a width / N / K < 1, pack_rows or warm_mask < 0.  emu_llama_weight_kernel answers with fp8_all off. */
+typedef struct emu_weight_mode { int fp8, fp4, pack, pack_wide, bf16_released, fp8_all; } emu_weight_mode;
 typedef struct emu_projection {
     emu_weight_mode mode;
     int rows, hidden, heads_dim_local, ffn_local;               /* the call */

@@ -3,7 +3,7 @@
 decode kernels (``LlamaEngine.score(via="decode")``), bf16 first, then each mode asked for with the bf16 logits as the reference
 (needs a GPU):
 
-    python tools/quant_eval.py [--checkpoint PATH] [--prompts FILE.jsonl] [--modes fp8,fp8-wide,fp4,fp4-wide] [--out profiles/quant_eval.md]
+    python tools/quant_eval.py [--checkpoint PATH] [--prompts FILE.jsonl] [--modes fp8,fp8-wide,fp4,fp4-wide,fp8-all] [--out profiles/quant_eval.md]
 
 Per mode: mean NLL per scored token and its difference from bf16, mean and max KL(bf16 || mode), top-1 agreement with bf16, and
 ms per scored token (hipGraph-replayed steps, host clock between device synchronisations, the second of two runs).
@@ -17,7 +17,9 @@ bf16 run's own greedy choice (tokens a model finds likely), half random ids (tok
 
 Rows per step follow the stream under test: fp8 and fp4 stream one-row steps (``use_fp8`` / ``use_fp4(True)``: 1-2 rows), fp8-wide
 and fp4-wide the 3-16-row steps (``use_fp8(True, wide=True)`` / ``use_fp4(True, wide=True)``), so those modes score ``--wide-rows``
-prompts at a time; bf16 is run at the same row count for each.
+prompts at a time; bf16 is run at the same row count for each.  fp8-all (``use_fp8(True, wide=True, mid=True, all_rows=True)``)
+scores ``via="prefill"``, every prompt in one batch: prefix and continuation rows run through the 65-rows-and-up form of the W8A16
+GEMM (csrc/gemm_fp8.hip) where the batch has 65 rows or more, against bf16 scored the same way.
 """
 import argparse
 import json
@@ -50,8 +52,10 @@ def set_mode(lm, mode):
         lm.use_fp4(True)
     elif mode == "fp4-wide":
         lm.use_fp4(True, wide=True)
+    elif mode == "fp8-all":
+        lm.use_fp8(True, wide=True, mid=True, all_rows=True)
     elif mode != "bf16":
-        raise SystemExit(f"unknown mode {mode!r}: fp8, fp8-wide, fp4, fp4-wide")
+        raise SystemExit(f"unknown mode {mode!r}: fp8, fp8-wide, fp4, fp4-wide, fp8-all")
 
 
 def batches(items, rows):
@@ -67,7 +71,7 @@ def batches(items, rows):
         yield ids, mask, cont, cmask
 
 
-def run(lm, items, rows, refs=None, keep_logits=False):
+def run(lm, items, rows, refs=None, keep_logits=False, via="decode"):
     """Scores every batch twice (the first run warms up and captures); returns the per-batch dicts and ms per scored token."""
     out, tokens, secs = [], 0, 0.0
     for n, (ids, mask, cont, cmask) in enumerate(batches(items, rows)):
@@ -75,7 +79,7 @@ def run(lm, items, rows, refs=None, keep_logits=False):
         for attempt in range(2):
             torch.cuda.synchronize()
             t = time.perf_counter()
-            r = lm.score(x, mask, cont, cmask, via="decode", use_graph=True, reference_logits=None if refs is None else refs[n],
+            r = lm.score(x, mask, cont, cmask, via=via, use_graph=via == "decode", reference_logits=None if refs is None else refs[n],
                          return_logits=keep_logits)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t
@@ -124,7 +128,7 @@ def main():
         weights = f"SYNTHETIC weights (seed 0), {a.layers} layers at the 33B widths"
     if not lm.ready:
         sys.exit("the LLaMA weights are incomplete")
-    if "fp8" in modes or "fp8-wide" in modes:
+    if "fp8" in modes or "fp8-wide" in modes or "fp8-all" in modes:
         lm.quantize_fp8()
 
     if a.prompts:
@@ -153,18 +157,19 @@ def main():
               "|---|---|---|---|---|---|---|---|---|"]
     base = {}
     for mode in modes:
-        rows = a.wide_rows if mode in ("fp8-wide", "fp4-wide") else 1
-        if rows not in base:
+        via = "prefill" if mode == "fp8-all" else "decode"
+        rows = len(items) if via == "prefill" else a.wide_rows if mode in ("fp8-wide", "fp4-wide") else 1
+        if (rows, via) not in base:
             set_mode(lm, "bf16")
-            res, ms = run(lm, items, rows, keep_logits=True)
-            base[rows] = ([r.pop("logits") for r in res], summarise(res), ms)
-            b = base[rows][1]
-            lines.append(f"| bf16 | {rows} | {b['tokens']} | {b['nll']:.4f} | | | | | {ms:.3f} |")
+            res, ms = run(lm, items, rows, keep_logits=True, via=via)
+            base[(rows, via)] = ([r.pop("logits") for r in res], summarise(res), ms)
+            b = base[(rows, via)][1]
+            lines.append(f"| bf16{' (prefill)' if via == 'prefill' else ''} | {rows} | {b['tokens']} | {b['nll']:.4f} | | | | | {ms:.3f} |")
             print(lines[-1], flush=True)
-        refs, b, _ = base[rows]
+        refs, b, _ = base[(rows, via)]
         set_mode(lm, mode)
         try:
-            res, ms = run(lm, items, rows, refs=refs)
+            res, ms = run(lm, items, rows, refs=refs, via=via)
         finally:
             set_mode(lm, "bf16")
         s = summarise(res, b)
@@ -172,7 +177,8 @@ def main():
                      f"{s['kl_max']:.3e} | {s['agree']:.3f} | {ms:.3f} |")
         print(lines[-1], flush=True)
     lines += ["", "KL is KL(bf16 || mode) per scored token; ms/token is per scored token of the second of two runs of each batch (graph replay),",
-              "prefill and the first token's logits included."]
+              "prefill and the first token's logits included.  fp8-all and its bf16 row score via=\"prefill\": rows/step is the batch, every",
+              "prefix and continuation row of it in one forward."]
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
