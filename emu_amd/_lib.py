@@ -94,6 +94,11 @@ class Bf16PackSetC(C.Structure):
     _fields_ = [("lo", vp), ("nib", vp), ("sign", vp), ("flags", vp), ("hb", i32), ("rows", i32)]
 
 
+class Bf16Pack12SetC(C.Structure):
+    """emu_bf16_pack12_set (include/emu_hip.h): one matrix's 12-bit packed set; rows == 0 = none."""
+    _fields_ = [("lo", vp), ("nib", vp), ("patch", vp), ("flags", vp), ("hb", i32), ("rows", i32)]
+
+
 class ProjectionC(C.Structure):
     """emu_projection (include/emu_hip.h): the facts emu_llama_projection_kernel takes, the mode record first; norm_in_stream is its
     second answer."""
@@ -218,6 +223,10 @@ _PROTOS = {
     "emu_llama_set_layer_bf16_pack": (i32, [vp, i32, C.POINTER(Bf16PackSetC)]),
     "emu_llama_set_head_bf16_pack": (i32, [vp, C.POINTER(Bf16PackSetC), i32]),
     "emu_llama_use_bf16_pack": (i32, [vp, i32]),
+    "emu_bf16_pack12": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), vp]),
+    "emu_linear_bf16pack12": (i32, [vp, vp, C.POINTER(Bf16Pack12SetC), vp, vp, vp, i32, i32, i32, f32, i32, vp]),
+    "emu_llama_set_layer_bf16_pack12": (i32, [vp, i32, C.POINTER(Bf16Pack12SetC)]),
+    "emu_llama_set_head_bf16_pack12": (i32, [vp, C.POINTER(Bf16Pack12SetC), i32]),
     "emu_llama_pack_kernel": (i32, [i32] * 12),
     "emu_linear_bf16pack_thin": (i32, [vp, vp, C.POINTER(Bf16PackSetC), vp, vp, i32, i32, i32, i32, vp]),
     "emu_llama_use_bf16_pack_wide": (i32, [vp, i32]),

@@ -1,4 +1,4 @@
-// The 13-bit lossless bf16 weight format of the one-row decode streams: the ONE place that states the layout, shared by the packer
+// The 13-bit and 12-bit lossless bf16 weight formats of the one-row decode streams (the 12-bit one below the 13-bit one): the ONE place that states the layout, shared by the packer
 // (bf16_pack.hip) and the stream kernels (gemv_pack.hip); emu_amd/bf16pack.py restates it with torch on the CPU.
 //
 // A weight matrix uses a handful of binades, so the top 7 bits of a bf16's exponent field fit a 4-bit offset from a per-matrix
@@ -32,6 +32,7 @@ struct PackSet {                    // one matrix's packed set as the kernels ta
     const uint32_t* flags = nullptr;
     int hb = 0;                     // the matrix's exponent base
     int rows = 0;                   // R: rows per group (the rows per workgroup of the planned form), 0 = no set
+    const uint32_t* patch = nullptr;   // the 12-bit format below: its patch records (sign is null then); null = the 13-bit format
 };
 
 constexpr int pack_hb(int emax) { return (emax | 1) < 31 ? 0 : ((emax | 1) - 31) >> 1; }       // (constexpr: host and device)
@@ -40,6 +41,38 @@ inline size_t pack_lo_bytes(int N, int K, int R) { return pack_groups(N, R) * (s
 inline size_t pack_nib_bytes(int N, int K, int R) { return pack_groups(N, R) * (size_t)R * K / 2; }
 inline size_t pack_sign_bytes(int N, int K, int R) { return pack_groups(N, R) * (size_t)R * K / 8; }
 inline size_t pack_flag_words(int N, int R) { return (pack_groups(N, R) + 31) / 32; }
+
+
+// ---- The 12-bit format: the same low plane, and the sign moves into the nibble, so the sign plane goes.  A matrix's weights sit in far
+// fewer than 32 binades, so a window of 8 exponent-pair codes (16 binades) from a per-matrix base hb holds all but a few tiny ones:
+//     nibble     n(w) = (w >> 15) << 3 | code,  code = ((w >> 8) & 0x7f) - hb  in 0..7
+// laid out as the 13-bit nibbles are (byte b of row r = n(w_b) | n(w_{b+4}) << 4).  A weight whose code is outside 0..7 -- any bit
+// pattern: zeros, denormals, Inf and NaN are not special -- is a miss: its low byte stays in the low plane, its nibble is 0 and one
+// slot of the row group's patch record carries its true high byte:
+//     patch      8 slots of 32 bits per row group at patch + g * 32 bytes.  slot = vi << 13 | r << 11 | j << 8 | (w >> 8): vector index
+//                vi (bits 13..31: the owning lane vi & 255 at bits 13..20, its trip vi >> 8 at bits 21..31), row r in the group, element
+//                j of the vector, high byte.  An empty slot is 0xffffffff, whose trip 2047 no kernel runs (KV <= 2304).  The slots in
+//                use are sorted ascending (by vi, r, j), the empty ones behind them.
+//     flags      a group with more than 8 misses is flagged, streams its bf16 rows as in the 13-bit format, and its record is empty
+// Rows that pad the last group are no misses (nibble 0, low byte 0).  hb is the base of the 8-code window that covers the most weights,
+// from the 128-bin histogram of (w >> 8) & 0x7f over the matrix; ties go to the lower base (pack12_window; bf16pack.py: window_rule).
+// 12 bits per weight in two planes: one load instruction fewer per trip than the 13-bit set.
+constexpr int PACK12_SLOTS = 8;
+constexpr uint32_t PACK12_EMPTY = 0xffffffffu;
+constexpr int PACK12_MAX_KV = 1 << 18;             // vi must stay clear of the empty slot's
+inline size_t pack12_patch_bytes(int N, int R) { return pack_groups(N, R) * PACK12_SLOTS * 4; }
+constexpr uint32_t pack12_slot(uint32_t vi, int r, int j, uint32_t high) { return vi << 13 | (uint32_t)r << 11 | (uint32_t)j << 8 | high; }
+inline int pack12_window(const unsigned long long (&hist)[128]) {
+    unsigned long long best = 0, cur = 0;
+    int hb = 0;
+    for (int b = 0; b < 8; ++b) cur += hist[b];
+    best = cur;
+    for (int b = 1; b <= 120; ++b) {
+        cur += hist[b + 7] - hist[b - 1];
+        if (cur > best) { best = cur; hb = b; }
+    }
+    return hb;
+}
 
 #ifdef __HIPCC__
 // the pieces of 8 weights of row r of a group of R (the dwords w.x .. w.w of a 16-byte bf16 vector): low bytes L0 / L1, nibble
@@ -85,5 +118,59 @@ __device__ __forceinline__ void pack_decode_row(uint32_t L0, uint32_t L1, uint32
     w[1] = __builtin_amdgcn_perm(ha, L0, 0x07030602u);
     w[2] = __builtin_amdgcn_perm(hh, L1, 0x05010400u);
     w[3] = __builtin_amdgcn_perm(hh, L1, 0x07030602u);
+}
+
+// ---- the 12-bit format.  Encode: the low bytes and the nibble dword of 8 weights; miss: bit j = weight j is a miss (its nibble 0)
+__device__ __forceinline__ void pack12_encode_row(const uint32_t (&w)[4], int hb, uint32_t& L0, uint32_t& L1, uint32_t& nib, uint32_t& miss) {
+    L0 = L1 = nib = miss = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t v = (w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+        const int d = (int)((v >> 8) & 0x7f) - hb;
+        const bool out = d < 0 || d > 7;
+        if (j < 4) L0 |= (v & 0xff) << (8 * j); else L1 |= (v & 0xff) << (8 * (j - 4));
+        if (out) miss |= 1u << j;
+        else nib |= ((v >> 15) << 3 | (uint32_t)d) << (8 * (j & 3) + 4 * (j >> 2));
+    }
+}
+// Decode: the codes as bytes + hb in every byte, the sign from bit 3 / bit 7 of each nibble pair to bit 7, then pack_decode_row's perms
+__device__ __forceinline__ void pack12_decode_row(uint32_t L0, uint32_t L1, uint32_t nib, uint32_t hb4, uint32_t (&w)[4]) {
+    const uint32_t ha = ((nib & 0x07070707u) + hb4) | ((nib << 4) & 0x80808080u);
+    const uint32_t hh = (((nib >> 4) & 0x07070707u) + hb4) | (nib & 0x80808080u);
+    w[0] = __builtin_amdgcn_perm(ha, L0, 0x05010400u);
+    w[1] = __builtin_amdgcn_perm(ha, L0, 0x07030602u);
+    w[2] = __builtin_amdgcn_perm(hh, L1, 0x05010400u);
+    w[3] = __builtin_amdgcn_perm(hh, L1, 0x07030602u);
+}
+// A row group's patch record in a wave: lane s < 8 holds slot s, and key = the slot's trip and row pair (slot >> 12 with the lane field
+// cleared; no slot's in the lanes from 8 up).  Rows are patched two at a time (the pair h = rows 2h and 2h + 1 of the group): the
+// test "does a slot name trip `trip` and pair h" is workgroup-uniform, one v_cmp of key against a constant and a branch on vcc
+struct Pack12Rec { uint32_t slot, key; };
+__device__ __forceinline__ Pack12Rec pack12_record(const uint32_t* patch, int g, int lane) {
+    Pack12Rec rec;
+    rec.slot = patch[(size_t)g * PACK12_SLOTS + (lane & (PACK12_SLOTS - 1))];
+    rec.key = lane < PACK12_SLOTS ? (rec.slot >> 12) & ~0x1feu : PACK12_EMPTY;
+    return rec;
+}
+// the decoded dwords w[i] of the 8 weights thread tid holds of rows 2h + i of the group in trip `trip` (vi = tid + 256 trip), patched:
+// skipped on the uniform test where no slot names them; else, slot by slot of those that do, the owning lane replaces the high byte
+// of dword j >> 1, half j & 1 of its row (a uniform switch over the eight dwords: no indexed registers).  The ballot sees active lanes
+// only and the record is in lanes 0..7: call with the whole wave, never under a per-lane `vi < KV` (a ragged trip's last wave may
+// hold 4 vectors); a lane past the row matches no slot, so nothing else needs masking.
+__device__ __forceinline__ void pack12_patch(const Pack12Rec& rec, int trip, int h, int tid, uint32_t (&w)[2][4]) {
+    unsigned long long hit = __builtin_amdgcn_ballot_w64(rec.key == ((uint32_t)trip << 9 | (uint32_t)h));
+#pragma nounroll
+    while (hit) {
+        const uint32_t p = __builtin_amdgcn_readlane(rec.slot, __builtin_ctzll(hit));
+        hit &= hit - 1;
+        const uint32_t sh = (p & 0x100u) ? 24u : 8u;
+        const uint32_t m = ((p >> 13) & 255u) == (uint32_t)tid ? 0xffu << sh : 0u, high = (p & 0xffu) << sh;
+        const uint32_t at = (p >> 9) & 7u;                            // 4 (r & 1) + (j >> 1)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+                if (at == (uint32_t)(4 * i + d)) w[i][d] = (w[i][d] & ~m) | (high & m);
+    }
 }
 #endif

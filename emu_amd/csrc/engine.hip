@@ -88,8 +88,9 @@ enum class WeightSet { Bf16, Fp8, Fp4, Pack };
 // over an [N, K] matrix is priced at under the weight-stream profiler (R: the rows per group of a packed set, priced at what it stores)
 bool holds(const Weights& w, WeightSet set) { return set == WeightSet::Bf16 ? w.W != nullptr : set == WeightSet::Fp8 ? w.W8 && w.s8 : set == WeightSet::Fp4 ? w.W4 && w.s4 : w.W && w.pk.rows; }
 constexpr int set_kdiv(WeightSet set) { return set == WeightSet::Fp4 ? 2 : 1; }
-double set_bytes(WeightSet set, int N, int K, int R = 0) {
-    if (set == WeightSet::Pack) return (double)(pack_lo_bytes(N, K, R) + pack_nib_bytes(N, K, R) + pack_sign_bytes(N, K, R) + 4 * pack_flag_words(N, R));
+double set_bytes(WeightSet set, int N, int K, int R = 0, bool twelve = false) {       // twelve: a packed set of the 12-bit format
+    if (set == WeightSet::Pack)
+        return (double)(pack_lo_bytes(N, K, R) + pack_nib_bytes(N, K, R) + (twelve ? pack12_patch_bytes(N, R) : pack_sign_bytes(N, K, R)) + 4 * pack_flag_words(N, R));
     return set == WeightSet::Fp4 ? (double)N * (double)(K / 2 + K / 32) : (set == WeightSet::Fp8 ? 1.0 : 2.0) * (double)N * (double)K;
 }
 // The kernels of a LLaMA projection (ABI: the values emu_llama_projection_kernel and its three views return), and what each is, said
@@ -182,7 +183,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
     if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows)       // stream or GEMM by the rows, priced where it streams (linear)
         return linear(g.x, set == WeightSet::Fp8 ? B(w.W8) : w.W, g.bias, g.res, g.norm_w, g.out, g.M, g.N, g.K, g.ldx, g.ldw, g.ldres, g.ldo, g.eps,
                       g.epi, s, set == WeightSet::Fp8 ? w.s8 : nullptr, splitk, splitk_floats, &g.warm);
-    const double bytes = set_bytes(set, g.N, g.K, w.pk.rows);
+    const double bytes = set_bytes(set, g.N, g.K, w.pk.rows, w.pk.patch != nullptr);
     if (set == WeightSet::Fp8) {
         g.W = B(w.W8); g.wscale = w.s8;
         return gemv_profiled(bytes, s, [&] {
@@ -193,6 +194,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
         if (g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
         g.W = w.W;
         if (k == WeightKernel::Bf16PackThin) {
+            if (w.pk.patch) return -22;                              // (the few-row twin reads 13-bit sets only)
             const GemvPlan p = gemv_pack_thin_plan(gemv_shape_of(g), w.pk.rows, emu_gemm_tune_get());
             return p.status ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv_pack_thin(g, w.pk, p, s); });
         }
@@ -292,6 +294,19 @@ int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* s
     GemvArgs g{B(A), B(W), B(norm_w), nullptr, B(res), B(C), 1, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, eps, epi, nullptr};
     PackSet p;
     p.lo = set->lo; p.nib = set->nib; p.sign = set->sign; p.flags = reinterpret_cast<const uint32_t*>(set->flags); p.hb = set->hb; p.rows = set->rows;
+    return launch_gemv_pack(g, p, form, S(s));
+}
+int emu_bf16_pack12(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* patch, void* flags, int* hb_out,
+                    int* flagged_out, emu_stream_t s) {
+    return launch_bf16_pack12(B(w_bf16), ldw, N, K, rows, lo, nib, patch, reinterpret_cast<uint32_t*>(flags), hb_out, flagged_out, S(s));
+}
+int emu_linear_bf16pack12(const void* A, const void* W, const emu_bf16_pack12_set* set, const void* res, const void* norm_w, void* C,
+                          int N, int K, int form, float eps, int epi, emu_stream_t s) {
+    if (!A || !W || !set || !C || !set->patch) return -22;
+    GemvArgs g{B(A), B(W), B(norm_w), nullptr, B(res), B(C), 1, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, eps, epi, nullptr};
+    PackSet p;
+    p.lo = set->lo; p.nib = set->nib; p.patch = reinterpret_cast<const uint32_t*>(set->patch); p.flags = reinterpret_cast<const uint32_t*>(set->flags);
+    p.hb = set->hb; p.rows = set->rows;
     return launch_gemv_pack(g, p, form, S(s));
 }
 int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, void* C, int M, int N, int K,
@@ -775,7 +790,7 @@ struct emu_llama {
     WeightKernel kernel_for(int rows) const { return call_kernel(mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local); }
     // matrix_kernel's facts for the [N, K] matrix W under `rows` rows at a layer projection; the head sets its own two on top
     emu_projection site(const Weights& W, int rows, int N, int K, bool norm, int epi, int tail_mode, int warm_mask) const {
-        return {mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local, N, K, norm, epi, W.W8 != nullptr, W.pk.rows, W.pkN, W.pkK,
+        return {mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local, N, K, norm, epi, W.W8 != nullptr, W.pk.patch && rows > 1 ? 0 : W.pk.rows, W.pkN, W.pkK,       // (a 12-bit set: the one-row streams only)
                 decode_fused, tail_mode, warm_mask, emu_gemm_tune_get(), 0, 0, 0};
     }
     const bf16_t *final_norm = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
@@ -1533,9 +1548,39 @@ int emu_llama_use_fp4(emu_llama* m, int enable) {
 static int set_pack(emu_llama* m, Weights& w, const emu_bf16_pack_set& s, int N, int K, const char* what) {
     if (!s.rows) { w.pk = PackSet{}; w.pkN = w.pkK = 0; return 0; }       // this matrix stays on bf16
     if (!s.lo || !s.nib || !s.sign || !s.flags || (s.rows != 2 && s.rows != 4) || s.hb < 0 || s.hb > 112 || (K & 31)) return fail(m->ctx, -22, what);
+    w.pk = PackSet{};
     w.pk.lo = s.lo; w.pk.nib = s.nib; w.pk.sign = s.sign; w.pk.flags = reinterpret_cast<const uint32_t*>(s.flags); w.pk.hb = s.hb; w.pk.rows = s.rows;
     w.pkN = N; w.pkK = K;
     return 0;
+}
+static int set_pack12(emu_llama* m, Weights& w, const emu_bf16_pack12_set& s, int N, int K, const char* what) {
+    if (!s.rows) { w.pk = PackSet{}; w.pkN = w.pkK = 0; return 0; }       // this matrix stays on bf16
+    if (!s.lo || !s.nib || !s.patch || !s.flags || (s.rows != 2 && s.rows != 4) || s.hb < 0 || s.hb > 120 || (K & 31) || (K >> 3) >= PACK12_MAX_KV) return fail(m->ctx, -22, what);
+    w.pk = PackSet{};
+    w.pk.lo = s.lo; w.pk.nib = s.nib; w.pk.patch = reinterpret_cast<const uint32_t*>(s.patch); w.pk.flags = reinterpret_cast<const uint32_t*>(s.flags);
+    w.pk.hb = s.hb; w.pk.rows = s.rows;
+    w.pkN = N; w.pkK = K;
+    return 0;
+}
+// the 12-bit setters take a layer's / the head's sets like the 13-bit ones; a matrix whose entry has rows == 0 keeps what it holds
+int emu_llama_set_layer_bf16_pack12(emu_llama* m, int layer, const emu_bf16_pack12_set* sets4) {
+    if (!m || !sets4 || layer < 0 || layer >= m->cfg.layers) return -22;
+    if (m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_set_layer_bf16_pack12: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    const emu_llama_cfg& c = m->cfg;
+    const int H = c.hidden, HD = c.heads_local * c.head_dim, Fl = c.ffn_local;
+    emu_llama::Layer& L = m->layers[layer];
+    const char* what = "emu_llama_set_layer_bf16_pack12: a set needs its four pointers, rows 2 or 4, hb 0..120 and K % 32 == 0";
+    Weights* ws[4] = {&L.qkv, &L.o, &L.gu, &L.down};
+    const int Ns[4] = {3 * HD, H, 2 * Fl, H}, Ks[4] = {H, HD, H, Fl};
+    for (int i = 0; i < 4; ++i)
+        if (sets4[i].rows)
+            if (int st = set_pack12(m, *ws[i], sets4[i], Ns[i], Ks[i], what)) return st;
+    return 0;
+}
+int emu_llama_set_head_bf16_pack12(emu_llama* m, const emu_bf16_pack12_set* set, int rows_n) {
+    if (!m || !set || rows_n < 1) return -22;
+    if (m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_set_head_bf16_pack12: the bf16 weights were released (emu_llama_release_bf16); flagged row groups read them");
+    return set_pack12(m, m->head, *set, rows_n, m->cfg.hidden, "emu_llama_set_head_bf16_pack12: a set needs its four pointers, rows 2 or 4, hb 0..120 and K % 32 == 0");
 }
 int emu_llama_set_layer_bf16_pack(emu_llama* m, int layer, const emu_bf16_pack_set* sets4) {
     if (!m || !sets4 || layer < 0 || layer >= m->cfg.layers) return -22;

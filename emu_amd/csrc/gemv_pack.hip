@@ -1,5 +1,6 @@
-// One-row decode weight streams over the 13-bit lossless bf16 format (bf16_pack.h): the packed twins of the bf16 forms the headline
-// decode step runs (gemv.hip):
+// One-row decode weight streams over the 13-bit and 12-bit lossless bf16 formats (bf16_pack.h; BITS picks the format, the 13-bit
+// instantiations are what they were before the 12-bit ones came): the packed twins of the bf16 forms the headline decode step runs
+// (gemv.hip):
 //   head form, fused RMSNorm      gemv_kernel<4, 1, true, EPI, -1>       qkv, gate/up (SwiGLU), lm_head
 //   preload form                  gemv_kernel<2, 1, false, EPI, 4>       o_proj
 //   single round trip             gemv_rt_kernel<2, 9, false, EPI, false> down_proj
@@ -8,6 +9,8 @@
 // fetch and the in-register decode in front of bf16_dot2 differ, so the outputs are the bf16 kernels' bit for bit.  13/16 of the HBM bytes.  A workgroup whose row group is flagged (a weight outside the matrix's 32-binade window) streams the
 // bf16 rows through the same registers instead; the branch is workgroup-uniform.  The packed loads of the first trip / the preload
 // are requested before the flag word is back, so the flag costs an unflagged workgroup no latency.  No workgroup waits for another.
+// 12 bits: no sign load; the row group's patch record (8 slots, requested at kernel start with the flag word) is applied to the decoded
+// dwords in front of the unchanged bf16_dot2 chain, behind a workgroup-uniform test per trip and row pair; 12/16 of the HBM bytes.
 #include "common.h"
 #include "kernels.h"
 #include "bf16_pack.h"
@@ -43,7 +46,8 @@ __device__ __forceinline__ PackPtrs<R> pack_ptrs(const GemvArgs& a, const PackSe
     return q;
 }
 
-template <int R>
+// BITS: 13, or 12 (no sign load: the sign is in the nibble)
+template <int R, int BITS = 13>
 __device__ __forceinline__ void fetch_packed(const PackPtrs<R>& q, int vi, PackRaw<R>& w) {
 #pragma unroll
     for (int h = 0; h < R / 2; ++h) {
@@ -53,12 +57,23 @@ __device__ __forceinline__ void fetch_packed(const PackPtrs<R>& q, int vi, PackR
     if constexpr (R == 4) {
         const u32x4 n = ld_stream(reinterpret_cast<const u32x4*>(q.nib) + vi);
         w.d[8] = n.x; w.d[9] = n.y; w.d[10] = n.z; w.d[11] = n.w;
-        w.d[12] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(q.sign) + vi);
+        if constexpr (BITS == 13) w.d[12] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(q.sign) + vi);
     } else {
         const u32x2 n = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(q.nib) + vi);
         w.d[4] = n.x; w.d[5] = n.y;
-        w.d[6] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(q.sign) + vi);
+        if constexpr (BITS == 13) w.d[6] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(q.sign) + vi);
     }
+}
+// the 12-bit fetch of the single round trip (R = 2): buffer loads whose range is the row group's KV vectors, so a load past the row
+// returns zeros by itself -- no branch around the load and no zero-initialised registers for it to merge with (with those the
+// compiler waits for each trip's load before it requests the next)
+__device__ __forceinline__ void fetch_packed12_ranged(const PackPtrs<2>& q, int vi, PackRaw<2>& w) {
+    const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(q.lo), 0, (uint32_t)q.KV * 16u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(q.nib), 0, (uint32_t)q.KV * 8u, 0x00020000);
+    const u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rl, (uint32_t)vi * 16u, 0, 2));      // (aux 2: nt)
+    const u32x2 n = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rn, (uint32_t)vi * 8u, 0, 2));
+    w.d[0] = v.x; w.d[1] = v.y; w.d[2] = v.z; w.d[3] = v.w;
+    w.d[4] = n.x; w.d[5] = n.y;
 }
 template <int R>
 __device__ __forceinline__ void fetch_bf16(const PackPtrs<R>& q, int vi, PackRaw<R>& w) {
@@ -68,9 +83,51 @@ __device__ __forceinline__ void fetch_bf16(const PackPtrs<R>& q, int vi, PackRaw
         w.d[4 * r] = v.x; w.d[4 * r + 1] = v.y; w.d[4 * r + 2] = v.z; w.d[4 * r + 3] = v.w;
     }
 }
-// acc[r] += row r . xp, the bf16 kernels' chain: x, y, z, w of the row's vector in order
-template <int R>
-__device__ __forceinline__ void pack_dots(const PackPtrs<R>& q, bool flagged, const PackRaw<R>& w, const u32x4& xp, float (&acc)[R]) {
+// what a 12-bit stream carries beside its planes: the row group's patch record (nothing at 13 bits)
+template <int BITS> struct PackPatch {};
+template <> struct PackPatch<12> { Pack12Rec rec; };
+template <int BITS>
+__device__ __forceinline__ PackPatch<BITS> pack_patch(const PackSet& p, int g, int lane) {
+    if constexpr (BITS == 12) return {pack12_record(p.patch, g, lane)};
+    else return {};
+}
+// acc[r] += row r . xp, the bf16 kernels' chain: x, y, z, w of the row's vector in order (12 bits: the patches of trip `trip` first).
+// 12 bits: called by EVERY lane of the wave, `active` = this lane holds a vector of the trip.  The record sits in lanes 0..7 and the
+// patch test is a ballot, which sees active lanes only, so the decode and the patches run with the whole wave (the last wave of a
+// ragged trip may hold 4 vectors: lanes 4..7 must still show their slots) and only the sums are the active lanes'; the packed
+// registers of an inactive lane must be loaded (a clamped vector) all the same.  A wave with no active lane skips everything.
+template <int R, int BITS = 13>
+__device__ __forceinline__ void pack_dots(const PackPtrs<R>& q, bool flagged, const PackRaw<R>& w, const u32x4& xp, float (&acc)[R],
+                                          const PackPatch<BITS>& pp = {}, int trip = 0, int tid = 0, bool active = true) {
+    if constexpr (BITS == 12) {
+        if (!__builtin_amdgcn_ballot_w64(active)) return;
+        // two rows at a time: decoded, patched behind one uniform test, summed -- straight-line code but for that test.  The empty
+        // asm pins each sum where it is made: without it the compiler sinks the chains of a whole trip below the next fetch and
+        // keeps every decoded dword alive across it (the head form then needs 147 VGPRs: 3 waves per SIMD).
+#pragma unroll
+        for (int h = 0; h < R / 2; ++h) {
+            uint32_t v[2][4];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int r = 2 * h + i;
+                if (flagged) { v[i][0] = w.d[4 * r]; v[i][1] = w.d[4 * r + 1]; v[i][2] = w.d[4 * r + 2]; v[i][3] = w.d[4 * r + 3]; }
+                else pack12_decode_row(w.d[2 * r], w.d[2 * r + 1], w.d[2 * R + r], q.hb4, v[i]);
+            }
+            if (!flagged) pack12_patch(pp.rec, trip, h, tid, v);
+            if (!active) continue;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                float t = acc[2 * h + i];
+                t = bf16_dot2(v[i][0], xp.x, t);
+                t = bf16_dot2(v[i][1], xp.y, t);
+                t = bf16_dot2(v[i][2], xp.z, t);
+                t = bf16_dot2(v[i][3], xp.w, t);
+                asm volatile("" : "+v"(t));
+                acc[2 * h + i] = t;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         uint32_t v[4];
@@ -135,7 +192,7 @@ __device__ __forceinline__ void pack_reduce(float (&acc)[R], float (*red)[R], fl
 // x differs, so the outputs stay the bf16 kernel's bits.  A group past the last one (an odd group count) is clamped to the last group
 // for every load and its rows fail the epilogue's n < N.  G = 2: a workgroup with a flagged group streams the bf16 rows of all 8, one
 // trip at a time through the registers of both sets (8 rows x 4 dwords do not fit one); rare, it only has to be exact.
-template <int EPI, int G>
+template <int EPI, int G, int BITS>
 __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, const PackSet p, const int groups) {
     constexpr int R = 4;
     __shared__ float red[4][R * G];
@@ -150,6 +207,9 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
     PackPtrs<R> q[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) q[j] = pack_ptrs<R>(a, p, g0 + j < groups ? g0 + j : groups - 1);
+    PackPatch<BITS> pp[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) pp[j] = pack_patch<BITS>(p, g0 + j < groups ? g0 + j : groups - 1, lane);
 
     u32x4 hx[4], hg[4];
     PackRaw<R> hw[G], w1[G];
@@ -162,7 +222,7 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
     }
     const int v0 = tid < KV ? tid : KV - 1;                            // short rows (K < 2048): clamped, against a zero operand
 #pragma unroll
-    for (int j = 0; j < G; ++j) fetch_packed<R>(q[j], v0, hw[j]);
+    for (int j = 0; j < G; ++j) fetch_packed<R, BITS>(q[j], v0, hw[j]);
     bool flagged = false;
 #pragma unroll
     for (int j = 0; j < G; ++j) flagged = flagged || (g0 + j < groups && ((fw >> ((g0 + j) & 31)) & 1u));
@@ -199,38 +259,46 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
     for (int j = 0; j < G; ++j)
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[j][r] = 0.f;
-    auto dots = [&](bool fl, const PackRaw<R> (&w)[G], const u32x4& xp) {
+    auto dots = [&](bool fl, const PackRaw<R> (&w)[G], const u32x4& xp, int trip, bool active = true) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) pack_dots<R>(q[j], fl, w[j], xp, acc[j]);
+        for (int j = 0; j < G; ++j) pack_dots<R, BITS>(q[j], fl, w[j], xp, acc[j], pp[j], trip, tid, active);
     };
     if (flagged) {
-        dots(true, hw, hx[0]);
+        dots(true, hw, hx[0], 0);
 #pragma unroll
         for (int c = 1; c < 4; ++c) {
             const int vi = tid + 256 * c;
             if (vi < KV) {
 #pragma unroll
                 for (int j = 0; j < G; ++j) fetch_bf16<R>(q[j], vi, hw[j]);
-                dots(true, hw, hx[c]);
+                dots(true, hw, hx[c], c);
             }
         }
     } else {
+        // (12 bits: a wave that holds any vector of the trip fetches with all its lanes, the lanes past the row a clamped vector,
+        // and every lane calls dots -- pack_dots says why)
         auto fetch = [&](PackRaw<R> (&w)[G], int c) {
             const int vi = tid + 256 * c;
-            if (vi < KV) {
+            if (BITS == 12 ? __builtin_amdgcn_ballot_w64(vi < KV) != 0 : vi < KV) {
 #pragma unroll
-                for (int j = 0; j < G; ++j) fetch_packed<R>(q[j], vi, w[j]);
+                for (int j = 0; j < G; ++j) fetch_packed<R, BITS>(q[j], BITS == 12 && vi >= KV ? KV - 1 : vi, w[j]);
             }
         };
         fetch(w1, 1);
-        dots(false, hw, hx[0]);
+        dots(false, hw, hx[0], 0);
         __builtin_amdgcn_sched_barrier(0);
         fetch(hw, 2);
-        if (tid + 256 < KV) dots(false, w1, hx[1]);
+        if constexpr (BITS == 12) dots(false, w1, hx[1], 1, tid + 256 < KV);
+        else if (tid + 256 < KV) dots(false, w1, hx[1], 1);
         __builtin_amdgcn_sched_barrier(0);
         fetch(w1, 3);
-        if (tid + 512 < KV) dots(false, hw, hx[2]);
-        if (tid + 768 < KV) dots(false, w1, hx[3]);
+        if constexpr (BITS == 12) {
+            dots(false, hw, hx[2], 2, tid + 512 < KV);
+            dots(false, w1, hx[3], 3, tid + 768 < KV);
+        } else {
+            if (tid + 512 < KV) dots(false, hw, hx[2], 2);
+            if (tid + 768 < KV) dots(false, w1, hx[3], 3);
+        }
     }
 
     float accf[R * G];
@@ -245,7 +313,7 @@ __global__ __launch_bounds__(256) void gemv_pack_head_kernel(const GemvArgs a, c
 // ---- the two plain forms of two rows per workgroup, every load requested up front.  CLAMP: the preload form (gemv_kernel<2, 1, false,
 // EPI, 4>: loads past the row clamped, their trips skipped); else the single round trip (gemv_rt_kernel<2, 9, false, EPI, false>:
 // loads past the row not issued, zero registers against a zero activation)
-template <int KIT, bool CLAMP, int EPI>
+template <int KIT, bool CLAMP, int EPI, int BITS>
 __global__ __launch_bounds__(256) void gemv_pack_rows2_kernel(const GemvArgs a, const PackSet p) {
     constexpr int R = 2;
     __shared__ float red[4][R];
@@ -255,6 +323,7 @@ __global__ __launch_bounds__(256) void gemv_pack_rows2_kernel(const GemvArgs a, 
     const int n0 = blockIdx.x * R;
     const uint32_t fw = p.flags[blockIdx.x >> 5];
     const PackPtrs<R> q = pack_ptrs<R>(a, p, blockIdx.x);
+    const PackPatch<BITS> pp = pack_patch<BITS>(p, blockIdx.x, tid & 63);
 
     u32x4 xv[KIT];
     PackRaw<R> wv[KIT];
@@ -267,11 +336,14 @@ __global__ __launch_bounds__(256) void gemv_pack_rows2_kernel(const GemvArgs a, 
     for (int it = 0; it < KIT; ++it) {
         const int vi = tid + 256 * it;
         if constexpr (CLAMP) {
-            fetch_packed<R>(q, vi < KV ? vi : KV - 1, wv[it]);
+            fetch_packed<R, BITS>(q, vi < KV ? vi : KV - 1, wv[it]);
+        } else if constexpr (BITS == 12) {
+            fetch_packed12_ranged(q, vi, wv[it]);
+            __builtin_amdgcn_sched_barrier(0);                       // trip by trip, so the first trip's planes are back first
         } else {
 #pragma unroll
             for (int d = 0; d < 4 * R; ++d) wv[it].d[d] = 0u;
-            if (vi < KV) fetch_packed<R>(q, vi, wv[it]);
+            if (vi < KV) fetch_packed<R, BITS>(q, vi, wv[it]);
         }
     }
     const bool flagged = (fw >> (blockIdx.x & 31)) & 1u;
@@ -292,9 +364,19 @@ __global__ __launch_bounds__(256) void gemv_pack_rows2_kernel(const GemvArgs a, 
     float acc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) acc[r] = 0.f;
+    if constexpr (BITS == 12) {          // two copies of the chain, so no register of the packed fetch waits to merge with the bf16 one
+        auto dots = [&](bool fl) {
 #pragma unroll
-    for (int it = 0; it < KIT; ++it) {
-        if (!CLAMP || tid + 256 * it < KV) pack_dots<R>(q, flagged, wv[it], xv[it], acc);
+            for (int it = 0; it < KIT; ++it) {
+                pack_dots<R, BITS>(q, fl, wv[it], xv[it], acc, pp, it, tid, !CLAMP || tid + 256 * it < KV);       // (every lane calls)
+            }
+        };
+        if (flagged) dots(true); else dots(false);
+    } else {
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            if (!CLAMP || tid + 256 * it < KV) pack_dots<R>(q, flagged, wv[it], xv[it], acc);
+        }
     }
 
     pack_reduce<R>(acc, red, fin, tid);
@@ -313,39 +395,47 @@ int gemv_pack_rows(const GemvPlan& p, const GemvShape& sh) {
     return 0;
 }
 
+// the twin of the set's format: p.patch set = the 12-bit set (no sign plane), else the 13-bit one.  Which kinds have a 12-bit twin is
+// what profiles/bf16_pack12.md measured faster than the 13-bit one; a 12-bit set of another form is refused.
 int launch_gemv_pack(const GemvArgs& a, const PackSet& p, int form, hipStream_t s) {
-    if (!a.x || !a.W || !a.out || !p.lo || !p.nib || !p.sign || !p.flags || a.M != 1 || a.N < 1 || a.K < 32 || (a.K & 31)) return -22;
-    if (a.ldw < a.K || (a.ldw & 7) || p.hb < 0 || p.hb > 112 || (a.epi == EPI_RESID && !a.res)) return -22;
+    const bool b12 = p.patch != nullptr;
+    if (!a.x || !a.W || !a.out || !p.lo || !p.nib || (!b12 && !p.sign) || !p.flags || a.M != 1 || a.N < 1 || a.K < 32 || (a.K & 31)) return -22;
+    if (a.ldw < a.K || (a.ldw & 7) || p.hb < 0 || p.hb > (b12 ? 120 : 112) || (a.epi == EPI_RESID && !a.res)) return -22;
     const int KV = a.K >> 3;
 #define EMU_PACK_LAUNCH(KERNEL, R)                                                                                   \
     hipLaunchKernelGGL(KERNEL, dim3((a.N + R - 1) / R), dim3(256), 0, s, a, p);                                      \
     EMU_CHECK_LAUNCH();                                                                                              \
     return 0;
+#define EMU_PACK_ROWS2(KIT, CLAMP, EPI)                                                                              \
+    if (b12) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<KIT, CLAMP, EPI, 12>), 2) }                                   \
+    EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<KIT, CLAMP, EPI, 13>), 2)
     if (form == GEMV_FORM_HEAD) {
         if (p.rows != 4 || !a.norm_w || KV > 1024) return -22;
         if (a.epi != EPI_NONE && (a.epi != EPI_SWIGLU || (a.N & 1))) return -22;
         const int groups = (int)pack_groups(a.N, 4);                 // two groups (8 rows) per workgroup
-#define EMU_PACK_HEAD(EPI)                                                                                           \
-    hipLaunchKernelGGL((gemv_pack_head_kernel<EPI, 2>), dim3((groups + 1) / 2), dim3(256), 0, s, a, p, groups);      \
+#define EMU_PACK_HEAD(EPI, BITS)                                                                                     \
+    hipLaunchKernelGGL((gemv_pack_head_kernel<EPI, 2, BITS>), dim3((groups + 1) / 2), dim3(256), 0, s, a, p, groups); \
     EMU_CHECK_LAUNCH();                                                                                              \
     return 0;
-        if (a.epi == EPI_NONE) { EMU_PACK_HEAD(EPI_NONE) }
-        EMU_PACK_HEAD(EPI_SWIGLU)
+        if (a.epi == EPI_NONE) { if (b12) { EMU_PACK_HEAD(EPI_NONE, 12) } EMU_PACK_HEAD(EPI_NONE, 13) }
+        if (b12) { EMU_PACK_HEAD(EPI_SWIGLU, 12) }
+        EMU_PACK_HEAD(EPI_SWIGLU, 13)
 #undef EMU_PACK_HEAD
     }
     if (p.rows != 2 || a.norm_w) return -22;
     if (form == GEMV_FORM_PRELOAD) {
         if (KV > 1024) return -22;
-        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<4, true, EPI_NONE>), 2) }
-        if (a.epi == EPI_RESID) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<4, true, EPI_RESID>), 2) }
+        if (a.epi == EPI_NONE) { EMU_PACK_ROWS2(4, true, EPI_NONE) }
+        if (a.epi == EPI_RESID) { EMU_PACK_ROWS2(4, true, EPI_RESID) }
         return -22;
     }
     if (form == GEMV_FORM_RT) {
         if (KV > 9 * 256) return -22;
-        if (a.epi == EPI_NONE) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<9, false, EPI_NONE>), 2) }
-        if (a.epi == EPI_RESID) { EMU_PACK_LAUNCH((gemv_pack_rows2_kernel<9, false, EPI_RESID>), 2) }
+        if (a.epi == EPI_NONE) { EMU_PACK_ROWS2(9, false, EPI_NONE) }
+        if (a.epi == EPI_RESID) { EMU_PACK_ROWS2(9, false, EPI_RESID) }
         return -22;
     }
+#undef EMU_PACK_ROWS2
 #undef EMU_PACK_LAUNCH
     return -22;
 }

@@ -78,6 +78,11 @@ void plan_fp4(int KB, int* threads_per_row_set, int* row_sets);
 // bf16 matrix (flagged row groups read it), form = the plan's GemvForm; bit-identical to launch_gemv on the bf16 matrix
 int launch_bf16_pack(const bf16_t* W, int ldw, int N, int K, int rows, void* lo, void* nib, void* sign, uint32_t* flags, int* hb_out,
                      hipStream_t s);
+// the 12-bit format's packer: planes, patch records (8 slots of 32 bits per row group) and flags; *hb_out = the base of the matrix's
+// 8-code window, *flagged_out = the flagged row groups (what the rule that picks a matrix's format reads).  launch_gemv_pack takes
+// either format's set (PackSet::patch set = 12 bits)
+int launch_bf16_pack12(const bf16_t* W, int ldw, int N, int K, int rows, void* lo, void* nib, void* patch, uint32_t* flags, int* hb_out,
+                       int* flagged_out, hipStream_t s);
 int gemv_pack_rows(const GemvPlan& p, const GemvShape& sh);
 int launch_gemv_pack(const GemvArgs& a, const struct PackSet& p, int form, hipStream_t s);
 // the few-row (4..16) twin (gemv_pack_thin.hip): the same sets through the bf16 thin stream's arithmetic at kch 32.  gemv_pack_thin_plan

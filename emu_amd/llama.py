@@ -16,7 +16,7 @@ from typing import Dict, Iterable, Optional, Tuple
 import torch
 
 from . import bf16pack, genroute, mxfp4, ops, speculate
-from ._lib import SAMPLE_MAX_VOCAB, Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
+from ._lib import SAMPLE_MAX_VOCAB, Bf16Pack12SetC, Bf16PackSetC, EmuHipError, LlamaCfgC, SampleParamsC, check, lib
 from .conf.emu_conf import LlamaCfg
 from .constrain import TokenTrie
 from .device_loop import CapturedStep, run_polled, warn_once
@@ -403,7 +403,7 @@ class LlamaEngine:
             size = lambda v: v.numel() * b
         # the 13-bit packed stream (use_bf16_pack): a matrix that has a set streams its planes and flag words instead
         pk = getattr(self, "_pack", {}) if self.bf16_pack_on and b == 2 and not self.fp4_decode else {}
-        one = lambda k, v: bf16pack.packed_bytes(v.shape[0], v.shape[1], pk[k]["rows"]) if k in pk else size(v)
+        one = lambda k, v: self._set_bytes(pk[k]) if k in pk else size(v)
         per = sum(one(k, v) for k, v in self._keep.items() if k.split(".")[1] in ("wqkv", "wo", "wgu", "wdown"))
         return per + (one("lm_head", self.lm_head) if self.lm_head is not None else 0)
 
@@ -423,15 +423,40 @@ class LlamaEngine:
         rows = 0 if K % 32 else int(lib().emu_bf16_pack_rows(N, K, norm, epi, tune))
         return rows if rows == 2 or head_form else 0
 
+    @staticmethod
+    def _set_bytes(p) -> int:
+        """Bytes one pass over a packed set streams: its planes, its flag words and (12 bits) its patch records."""
+        return (bf16pack.packed_bytes12 if "patch" in p else bf16pack.packed_bytes)(*p["shape"], p["rows"])
+
+    def _pack12_default(self) -> bool:
+        """Whether the default packing may give a matrix a 12-bit set (``bf16pack.set_bits`` then decides matrix by matrix):
+        EMU_BF16_PACK12=0 forces 13 bits everywhere, tensor-parallel shards keep the 13-bit sets (nothing at TP has been timed),
+        EMU_BF16_PACK_WIDE=1 keeps them too (the 4..16-row twin reads 13-bit sets only), and a library that predates the format has no
+        packer for it."""
+        return (os.environ.get("EMU_BF16_PACK12", "1") != "0" and os.environ.get("EMU_BF16_PACK_WIDE") != "1" and self.ctx.tp_size == 1
+                and hasattr(lib(), "emu_bf16_pack12"))
+
     def _register_bf16_pack(self, keys) -> None:
+        """Hand the sets of the layers / the head named in ``keys`` to the library: the 13-bit setter takes a layer's four entries
+        (an empty one clears that matrix's set), then the 12-bit setter overrides the matrices that hold a 12-bit set."""
         pk = self.__dict__.setdefault("_pack", {})
+        is12 = lambda k: "patch" in pk.get(k, ())
         for i in sorted({int(k.split(".")[0]) for k in keys if k != "lm_head"}):
-            sets = (Bf16PackSetC * 4)(*[ops.pack_set_c(pk.get(f"{i}.{k}")) for k in self._PACK_KINDS])
+            names = [f"{i}.{k}" for k in self._PACK_KINDS]
+            sets = (Bf16PackSetC * 4)(*[ops.pack_set_c(pk.get(k)) for k in names])
             check(lib().emu_llama_set_layer_bf16_pack(self.handle, i, sets), "emu_llama_set_layer_bf16_pack", self.ctx.handle)
+            if any(is12(k) for k in names):
+                sets12 = (Bf16Pack12SetC * 4)(*[ops.pack12_set_c(pk.get(k)) for k in names])
+                check(lib().emu_llama_set_layer_bf16_pack12(self.handle, i, sets12), "emu_llama_set_layer_bf16_pack12", self.ctx.handle)
         if "lm_head" in keys and self.lm_head is not None:
-            one = ops.pack_set_c(pk.get("lm_head"))
-            check(lib().emu_llama_set_head_bf16_pack(self.handle, C.byref(one), int(self.lm_head.shape[0])), "emu_llama_set_head_bf16_pack",
-                  self.ctx.handle)
+            if is12("lm_head"):
+                one = ops.pack12_set_c(pk["lm_head"])
+                check(lib().emu_llama_set_head_bf16_pack12(self.handle, C.byref(one), int(self.lm_head.shape[0])),
+                      "emu_llama_set_head_bf16_pack12", self.ctx.handle)
+            else:
+                one = ops.pack_set_c(pk.get("lm_head"))
+                check(lib().emu_llama_set_head_bf16_pack(self.handle, C.byref(one), int(self.lm_head.shape[0])),
+                      "emu_llama_set_head_bf16_pack", self.ctx.handle)
 
     def _drop_bf16_pack(self, keys) -> None:
         pk = getattr(self, "_pack", None)
@@ -442,11 +467,22 @@ class LlamaEngine:
             self._register_bf16_pack(hit)
             self._mode_changed()
 
-    def pack_bf16(self, tune: int = 0, head_form: bool = False) -> Tuple[int, int]:
-        """Build and register the 13-bit packed set (``emu_amd.bf16pack``) of every matrix whose one-row stream has a packed twin and
+    def _pack_one(self, w: torch.Tensor, kind: str, rows: int, bits12: bool):
+        """The packed set of one matrix: 12 bits where ``bits12`` allows, the kind has a 12-bit twin (``bf16pack.PACK12_KINDS``) and
+        ``bf16pack.set_bits`` picks it from the flagged share the 12-bit pack reports; else 13 bits.  One set per matrix."""
+        if bits12 and kind in bf16pack.PACK12_KINDS:
+            p = ops.pack12_bf16_rows(w, rows)
+            if bf16pack.set_bits(p["flagged"], (w.shape[0] + rows - 1) // rows, rows, w.shape[1], True) == 12:
+                return p
+            del p
+        return ops.pack_bf16_rows(w, rows)
+
+    def pack_bf16(self, tune: int = 0, head_form: bool = False, bits12: bool = False) -> Tuple[int, int]:
+        """Build and register the packed set (``emu_amd.bf16pack``) of every matrix whose one-row stream has a packed twin and
         that has none yet; ``tune``: the emu_gemm_tune mask the streams will run under; ``head_form``: also the matrices behind a fused
-        RMSNorm (``_pack_rows``).  Returns (matrices packed, bytes of their sets).  The bf16 matrices stay: prefill, steps of more
-        rows and flagged row groups read them."""
+        RMSNorm (``_pack_rows``); ``bits12``: 12-bit sets where ``_pack_one`` picks them (the default packing asks for them), else 13
+        bits.  Returns (matrices packed, bytes of their sets).  The bf16 matrices stay: prefill, steps of more rows and flagged row
+        groups read them."""
         if not self.ready:
             raise RuntimeError("pack_bf16: load all weights first")
         if self.bf16_released:
@@ -456,9 +492,9 @@ class LlamaEngine:
         for key in self._pack_keys():
             rows = 0 if key in pk else self._pack_rows(key, tune, head_form)
             if rows:
-                pk[key] = ops.pack_bf16_rows(self.lm_head if key == "lm_head" else self._keep[key], rows)
+                pk[key] = self._pack_one(self.lm_head if key == "lm_head" else self._keep[key], key.split(".")[-1], rows, bits12)
                 new.append(key)
-                nbytes += bf16pack.packed_bytes(*pk[key]["shape"], rows)
+                nbytes += self._set_bytes(pk[key])
         if new:
             self._register_bf16_pack(new)
             self._mode_changed()
@@ -477,9 +513,23 @@ class LlamaEngine:
         (profiles/bf16_pack_wide.md); needs ``use_bf16_pack`` on.  Invalidates captured graphs."""
         if enable and not self.bf16_released and not self.bf16_pack_on:
             raise RuntimeError("use_bf16_pack_wide: switch the packed stream on first (use_bf16_pack)")
+        if enable:
+            self._repack_13()
         check(lib().emu_llama_use_bf16_pack_wide(self.handle, 1 if enable else 0), "emu_llama_use_bf16_pack_wide", self.ctx.handle)
         self.bf16_pack_wide = bool(enable)
         self._mode_changed()
+
+    def _repack_13(self) -> None:
+        """The few-row twin reads 13-bit sets only: give every matrix that holds a 12-bit set a 13-bit one in its place (the one-row
+        steps then stream 13 bits too; a matrix holds one set).  Nothing to do where the sets are 13-bit already."""
+        pk = getattr(self, "_pack", {})
+        k12 = [k for k, v in pk.items() if "patch" in v]
+        for k in k12:
+            pk[k] = ops.pack_bf16_rows(self.lm_head if k == "lm_head" else self._keep[k], pk[k]["rows"])
+        if k12:
+            self._register_bf16_pack(k12)
+            self._mode_changed()
+            print(f"emu_amd: bf16 pack stream: {len(k12)} sets repacked from 12 to 13 bits per weight for the 4..16-row stream", file=sys.stderr)
 
     def _pack_wide_default(self) -> None:
         """EMU_BF16_PACK_WIDE=1 switches the few-row stream on where the default packing has switched the one-row stream on."""
@@ -504,12 +554,13 @@ class LlamaEngine:
             print(f"emu_amd: bf16 pack stream off: its sets need {need / 2**30:.1f} GiB, {free / 2**30:.1f} GiB are free", file=sys.stderr)
             return
         t0 = time.time()
-        n, nbytes = self.pack_bf16(head_form=head_form)
+        n, nbytes = self.pack_bf16(head_form=head_form, bits12=self._pack12_default())
         torch.cuda.synchronize(self.device)
         self.use_bf16_pack(True)
         self._pack_wide_default()
-        print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s",
-              file=sys.stderr)
+        n12 = sum("patch" in v for v in self._pack.values())
+        print(f"emu_amd: bf16 pack stream on: {n} matrices packed ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s; "
+              f"{n12} of {len(self._pack)} sets at 12 bits per weight, the rest at 13", file=sys.stderr)
 
     def pack_bf16_default(self) -> str:
         """The model-level default (``EmuModel.load_weights`` / ``Emu.load_state_dict`` call it once the engine is ready): on top of
@@ -530,13 +581,14 @@ class LlamaEngine:
                       "qkv, gate/up and lm_head stay bf16", file=sys.stderr)
             return rule
         t0 = time.time()
-        n, nbytes = self.pack_bf16(head_form=True)
+        n, nbytes = self.pack_bf16(head_form=True, bits12=self._pack12_default())
         torch.cuda.synchronize(self.device)
         self.use_bf16_pack(True)
         self._pack_wide_default()
-        total = sum(bf16pack.packed_bytes(*v["shape"], v["rows"]) for v in self._pack.values())
-        print(f"emu_amd: bf16 pack stream on: {n} matrices packed to 13 bits per weight ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s"
-              f"; {len(self._pack)} matrices, {total / 2**30:.2f} GiB of sets in all", file=sys.stderr)
+        total = sum(self._set_bytes(v) for v in self._pack.values())
+        n12 = sum("patch" in v for v in self._pack.values())
+        print(f"emu_amd: bf16 pack stream on: {n} matrices packed ({nbytes / 2**30:.2f} GiB) in {time.time() - t0:.2f} s"
+              f"; {len(self._pack)} matrices, {total / 2**30:.2f} GiB of sets in all, {n12} of them at 12 bits per weight", file=sys.stderr)
         return rule
 
     # ------------------------------------------------------------------ optional fp8 decode stream

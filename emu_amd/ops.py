@@ -148,12 +148,38 @@ def pack_bf16_rows(w, rows: int):
     return p
 
 
+def pack12_bf16_rows(w, rows: int):
+    """The 12-bit lossless packing of a bf16 weight [N, K] (K % 32 == 0) on the device, for row groups of ``rows`` (2 or 4) rows: the
+    dict of ``emu_amd.bf16pack.pack12`` (planes, patch records and flags on the device), byte for byte; see emu_bf16_pack12."""
+    _req(w, "w")
+    assert w.dim() == 2 and rows in (2, 4)
+    N, K = w.shape
+    G, KV = (N + rows - 1) // rows, K // 8
+    u8 = dict(device=w.device, dtype=torch.uint8)
+    i32 = dict(device=w.device, dtype=torch.int32)
+    p = {"lo": torch.empty(G, rows // 2, KV, 16, **u8), "nib": torch.empty(G, KV, rows, 4, **u8), "patch": torch.empty(G, 8, **i32),
+         "flags": torch.empty((G + 31) // 32, **i32), "rows": rows, "shape": (N, K), "bits": 12}
+    hb, flagged = C.c_int(0), C.c_int(0)
+    check(lib().emu_bf16_pack12(_p(w), w.stride(0), N, K, rows, _p(p["lo"]), _p(p["nib"]), _p(p["patch"]), _p(p["flags"]), C.byref(hb),
+                                C.byref(flagged), stream(w)), "emu_bf16_pack12")
+    p["hb"], p["flagged"] = int(hb.value), int(flagged.value)
+    return p
+
+
 def pack_set_c(p):
-    """The emu_bf16_pack_set of a packed dict (None: the empty set, rows 0)."""
+    """The emu_bf16_pack_set of a 13-bit packed dict (None, or a 12-bit dict: the empty set, rows 0)."""
     from ._lib import Bf16PackSetC
-    if p is None:
+    if p is None or "patch" in p:
         return Bf16PackSetC(None, None, None, None, 0, 0)
     return Bf16PackSetC(_p(p["lo"]), _p(p["nib"]), _p(p["sign"]), _p(p["flags"]), p["hb"], p["rows"])
+
+
+def pack12_set_c(p):
+    """The emu_bf16_pack12_set of a 12-bit packed dict (None, or a 13-bit dict: the empty set, rows 0)."""
+    from ._lib import Bf16Pack12SetC
+    if p is None or "patch" not in p:
+        return Bf16Pack12SetC(None, None, None, None, 0, 0)
+    return Bf16Pack12SetC(_p(p["lo"]), _p(p["nib"]), _p(p["patch"]), _p(p["flags"]), p["hb"], p["rows"])
 
 
 def linear_bf16pack(x, w, p, form: int, res=None, norm_w=None, eps: float = 0.0, epi: int = EPI_NONE, out=None):
@@ -163,6 +189,11 @@ def linear_bf16pack(x, w, p, form: int, res=None, norm_w=None, eps: float = 0.0,
     N, K = w.shape
     if out is None:
         out = torch.empty(1, N // 2 if epi == EPI_SWIGLU else N, device=x.device, dtype=BF16)
+    if "patch" in p:                                 # a 12-bit set: its own entry point
+        s = pack12_set_c(p)
+        check(lib().emu_linear_bf16pack12(_p(x), _p(w), C.byref(s), _p(res), _p(norm_w), _p(out), N, K, form, eps, epi, stream(x)),
+              "emu_linear_bf16pack12")
+        return out
     s = pack_set_c(p)
     check(lib().emu_linear_bf16pack(_p(x), _p(w), C.byref(s), _p(res), _p(norm_w), _p(out), N, K, form, eps, epi, stream(x)),
           "emu_linear_bf16pack")

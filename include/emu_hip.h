@@ -749,6 +749,23 @@ int emu_bf16_pack(const void* w_bf16, int ldw, int N, int K, int rows, void* lo,
                   emu_stream_t s);
 int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, const void* norm_w, void* C, int N,
                         int K, int form, float eps, int epi, emu_stream_t s);
+/* The 12-bit format of the same streams (emu_amd/csrc/bf16_pack.h, emu_amd/bf16pack.py: pack12): the sign moves into the nibble
+ * beside a 3-bit exponent code (a window of 8 codes from the base hb that covers the most weights), the sign plane goes, and the few
+ * weights a row group has outside the window travel in its patch record (8 slots of 32 bits at patch + 32 g bytes); a row group with
+ * more than 8 of them is flagged.  Lossless like the 13-bit format; a matrix holds a set of one format or the other.
+ * emu_bf16_pack12: packs bf16 [N, ldw] (K % 32 == 0, K < 2^21, rows 2 or 4) on the device: lo and nib as emu_bf16_pack, patch
+ * 32 * ceil(N/rows) bytes, flags as there; *hb_out = hb, *flagged_out = the number of flagged row groups.  Waits for its own results.
+ * emu_linear_bf16pack12 (tests): emu_linear_bf16pack over a 12-bit set; bit-identical to emu_linear_bf16 on W.
+ * emu_llama_set_layer_bf16_pack12 / emu_llama_set_head_bf16_pack12: the 12-bit counterparts of the two setters below (a matrix's set
+ * of either format replaces the one it had).  The one-row streams read a 12-bit set; the 4..16-row twin has none and leaves such a
+ * matrix on the bf16 kernel. */
+typedef struct emu_bf16_pack12_set { const void *lo, *nib, *patch, *flags; int hb, rows; } emu_bf16_pack12_set;
+int emu_bf16_pack12(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* patch, void* flags, int* hb_out,
+                    int* flagged_out, emu_stream_t s);
+int emu_linear_bf16pack12(const void* A, const void* W, const emu_bf16_pack12_set* set, const void* res, const void* norm_w, void* C,
+                          int N, int K, int form, float eps, int epi, emu_stream_t s);
+int emu_llama_set_layer_bf16_pack12(emu_llama* m, int layer, const emu_bf16_pack12_set* sets4);
+int emu_llama_set_head_bf16_pack12(emu_llama* m, const emu_bf16_pack12_set* set, int rows_n);
 /* The packed sets of a layer (sets4: qkv, o_proj, gate/up, down; rows == 0: that matrix has none and stays on bf16) and of the head
  * (rows_n: the rows the lm_head pointer holds); refused after emu_llama_release_bf16.  emu_llama_use_bf16_pack(m, 1): projections of
  * ONE activation row on the bf16 kernels stream their set where emu_llama_projection_kernel says so; everything else reads what it read. */
