@@ -229,6 +229,7 @@ _PROTOS = {
     "emu_llama_set_head_bf16_pack12": (i32, [vp, C.POINTER(Bf16Pack12SetC), i32]),
     "emu_llama_pack_kernel": (i32, [i32] * 12),
     "emu_linear_bf16pack_thin": (i32, [vp, vp, C.POINTER(Bf16PackSetC), vp, vp, i32, i32, i32, i32, vp]),
+    "emu_linear_bf16pack12_thin": (i32, [vp, vp, C.POINTER(Bf16Pack12SetC), vp, vp, i32, i32, i32, i32, vp]),
     "emu_llama_use_bf16_pack_wide": (i32, [vp, i32]),
     "emu_llama_pack_thin_kernel": (i32, [i32] * 12),
     "emu_llama_set_head": (i32, [vp, vp, vp, vp, vp, vp]),

@@ -1,5 +1,5 @@
 // The 13-bit and 12-bit lossless bf16 weight formats of the one-row decode streams (the 12-bit one below the 13-bit one): the ONE place that states the layout, shared by the packer
-// (bf16_pack.hip) and the stream kernels (gemv_pack.hip); emu_amd/bf16pack.py restates it with torch on the CPU.
+// (bf16_pack.hip) and the stream kernels (gemv_pack.hip; gemv_pack_thin.hip at 4..16 rows, both formats); emu_amd/bf16pack.py restates it with torch on the CPU.
 //
 // A weight matrix uses a handful of binades, so the top 7 bits of a bf16's exponent field fit a 4-bit offset from a per-matrix
 // base hb.  A weight w (16 bits: s, e8, m7) is kept as three pieces:

@@ -176,8 +176,9 @@ WeightKernel matrix_kernel(WeightKernel k, emu_projection& q) {
 // out = epi(x W^T [+ bias] [+ res]) from a weight record through the kernel k names: g is the launch block but for the weight
 // pointers, which come from w (ldw in elements of the set k reads).  Every stream runs under the GEMV profiler at its set's price.
 // Refused (-22): a set the record does not hold, a row count outside the kernel's range, Fp8Gemm (it needs the caller's quantised rows:
-// linear_q8), and whatever the launcher behind the kernel refuses (shape -> plan -> pointer checks -> launch).
-int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0) {
+// linear_q8), and whatever the launcher behind the kernel refuses (shape -> plan -> pointer checks -> launch).  pack_wide: the engine's
+// few-row switch (emu_llama_use_bf16_pack_wide); below 2, Bf16PackThin over a 12-bit set is refused.
+int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float* splitk = nullptr, size_t splitk_floats = 0, int pack_wide = 0) {
     const WeightSet set = facts(k).set;
     if (k == WeightKernel::Fp8Gemm || !holds(w, set) || !serves(k, g.M)) return -22;
     if (k == WeightKernel::Bf16 || k == WeightKernel::Fp8Rows)       // stream or GEMM by the rows, priced where it streams (linear)
@@ -194,7 +195,7 @@ int linear_w(WeightKernel k, const Weights& w, GemvArgs g, hipStream_t s, float*
         if (g.N != w.pkN || g.K != w.pkK || g.ldw != g.K) return -22;
         g.W = w.W;
         if (k == WeightKernel::Bf16PackThin) {
-            if (w.pk.patch) return -22;                              // (the few-row twin reads 13-bit sets only)
+            if (w.pk.patch && pack_wide < 2) return -22;             // (a 12-bit set goes to its twin under switch value 2 only)
             const GemvPlan p = gemv_pack_thin_plan(gemv_shape_of(g), w.pk.rows, emu_gemm_tune_get());
             return p.status ? -22 : gemv_profiled(bytes, s, [&] { return launch_gemv_pack_thin(g, w.pk, p, s); });
         }
@@ -315,6 +316,16 @@ int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_s
     GemvArgs g{B(A), B(W), nullptr, nullptr, B(res), B(C), M, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, 0.f, epi, nullptr};
     PackSet p;
     p.lo = set->lo; p.nib = set->nib; p.sign = set->sign; p.flags = reinterpret_cast<const uint32_t*>(set->flags); p.hb = set->hb; p.rows = set->rows;
+    const GemvPlan pl = gemv_pack_thin_plan(gemv_shape_of(g), p.rows, emu_gemm_tune_get());
+    return pl.status ? -22 : launch_gemv_pack_thin(g, p, pl, S(s));
+}
+int emu_linear_bf16pack12_thin(const void* A, const void* W, const emu_bf16_pack12_set* set, const void* res, void* C, int M, int N, int K,
+                               int epi, emu_stream_t s) {
+    if (!A || !W || !set || !C || !set->patch) return -22;
+    GemvArgs g{B(A), B(W), nullptr, nullptr, B(res), B(C), M, N, K, K, K, res ? N : 0, epi == EPI_SWIGLU ? N / 2 : N, 0.f, epi, nullptr};
+    PackSet p;
+    p.lo = set->lo; p.nib = set->nib; p.patch = reinterpret_cast<const uint32_t*>(set->patch); p.flags = reinterpret_cast<const uint32_t*>(set->flags);
+    p.hb = set->hb; p.rows = set->rows;
     const GemvPlan pl = gemv_pack_thin_plan(gemv_shape_of(g), p.rows, emu_gemm_tune_get());
     return pl.status ? -22 : launch_gemv_pack_thin(g, p, pl, S(s));
 }
@@ -790,7 +801,7 @@ struct emu_llama {
     WeightKernel kernel_for(int rows) const { return call_kernel(mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local); }
     // matrix_kernel's facts for the [N, K] matrix W under `rows` rows at a layer projection; the head sets its own two on top
     emu_projection site(const Weights& W, int rows, int N, int K, bool norm, int epi, int tail_mode, int warm_mask) const {
-        return {mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local, N, K, norm, epi, W.W8 != nullptr, W.pk.patch && rows > 1 ? 0 : W.pk.rows, W.pkN, W.pkK,       // (a 12-bit set: the one-row streams only)
+        return {mode, rows, cfg.hidden, cfg.heads_local * cfg.head_dim, cfg.ffn_local, N, K, norm, epi, W.W8 != nullptr, W.pk.patch && rows > 1 && mode.pack_wide < 2 ? 0 : W.pk.rows, W.pkN, W.pkK,       // (a 12-bit set: the one-row streams only, below switch value 2)
                 decode_fused, tail_mode, warm_mask, emu_gemm_tune_get(), 0, 0, 0};
     }
     const bf16_t *final_norm = nullptr, *embed = nullptr, *cos = nullptr, *sin = nullptr;
@@ -1049,7 +1060,7 @@ struct LlamaCall {
         if (k == WeightKernel::Bf16 && gain_out) return linear_then_rmsnorm(w, A, W.W, res, C, rows, N, K, epi, gain_out, w.xn, eps, true, s);
         GemvArgs g = packed(k, A, K, gain_in, eps, res, ldres, C, ldc, rows, N, K, epi);
         if (warm.ntouch && k == WeightKernel::Bf16) { g.warm = warm; ++m->warm_launches; }
-        return linear_w(k, W, g, s, w.splitk, w.splitk_floats);
+        return linear_w(k, W, g, s, w.splitk, w.splitk_floats, m->mode.pack_wide);
     }
 
     // ---- L2 warming (l2_warm.h).  The budget and the head's shape ride in the mask (include/emu_hip.h: emu_llama_set_l2_warm).
@@ -1608,7 +1619,7 @@ int emu_llama_use_bf16_pack(emu_llama* m, int on) {
 int emu_llama_use_bf16_pack_wide(emu_llama* m, int on) {
     if (!m) return -22;
     if (on && m->mode.bf16_released) return fail(m->ctx, -22, "emu_llama_use_bf16_pack_wide: the bf16 weights were released (emu_llama_release_bf16)");
-    m->mode.pack_wide = on != 0;
+    m->mode.pack_wide = on == 2 ? 2 : on != 0;          // 2: 12-bit sets go to the few-row twin too; 1: 13-bit sets only
     return 0;
 }
 int emu_llama_release_bf16(emu_llama* m) {
@@ -1965,7 +1976,7 @@ static int llama_head(emu_llama* m, const bf16_t* hidden, int ldh, int M, bf16_t
         TRY(m->ctx, launch_rmsnorm(hidden, m->final_norm, ws, M, H, ldh, H, c.rms_eps, s));
     }
     return linear_w(k, m->head, packed(k, fused ? hidden : ws, fused ? ldh : H, fused ? m->final_norm : nullptr, c.rms_eps, nullptr, 0, out, ld,
-                                       M, N, H, EPI_NONE), s);
+                                       M, N, H, EPI_NONE), s, nullptr, 0, m->mode.pack_wide);
 }
 
 int emu_llama_logits(emu_llama* m, const void* hidden, int ldh, int M, void* logits, int ld, void* workspace,

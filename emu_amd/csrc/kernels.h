@@ -89,7 +89,8 @@ int launch_gemv_pack(const GemvArgs& a, const struct PackSet& p, int form, hipSt
 // (gemv.hip): family GEMV_FAM_PACK_THIN with rows, mb, stages, kch, grid, block exactly when gemv_plan sends the bf16 shape (no fused
 // norm) to GEMV_FAM_THIN with a kch that has a twin, set_rows is 2 or 4, 4 <= M <= 16 and the epilogue is NONE / RESID / SWIGLU; else
 // status -22 and every other field 0.  launch_gemv_pack_thin: that plan's launch; a.W = the bf16 matrix (flagged workgroups stream
-// it); bit-identical to launch_gemv on the bf16 matrix
+// it); bit-identical to launch_gemv on the bf16 matrix.  It takes either format's set under the same plan (PackSet::patch set = the
+// 12-bit twin: sign null, 16-byte aligned records, hb 0..120, K / 8 < PACK12_MAX_KV)
 GemvPlan gemv_pack_thin_plan(const GemvShape& shape, int set_rows, int tune);
 int launch_gemv_pack_thin(const GemvArgs& a, const struct PackSet& p, const GemvPlan& plan, hipStream_t s);
 // o_proj of a tensor-parallel shard's one-row step with the decode attention's split merge in its prologue (gemv_merge.hip):

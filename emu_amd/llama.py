@@ -431,8 +431,8 @@ class LlamaEngine:
     def _pack12_default(self) -> bool:
         """Whether the default packing may give a matrix a 12-bit set (``bf16pack.set_bits`` then decides matrix by matrix):
         EMU_BF16_PACK12=0 forces 13 bits everywhere, tensor-parallel shards keep the 13-bit sets (nothing at TP has been timed),
-        EMU_BF16_PACK_WIDE=1 keeps them too (the 4..16-row twin reads 13-bit sets only), and a library that predates the format has no
-        packer for it."""
+        EMU_BF16_PACK_WIDE=1 keeps them too (the request for the 13-bit few-row twin; =12 asks for the 12-bit one and keeps the 12-bit
+        sets), and a library that predates the format has no packer for it."""
         return (os.environ.get("EMU_BF16_PACK12", "1") != "0" and os.environ.get("EMU_BF16_PACK_WIDE") != "1" and self.ctx.tp_size == 1
                 and hasattr(lib(), "emu_bf16_pack12"))
 
@@ -507,20 +507,26 @@ class LlamaEngine:
         self.bf16_pack_on = bool(enable)
         self._mode_changed()
 
-    def use_bf16_pack_wide(self, enable: bool = True) -> None:
+    def use_bf16_pack_wide(self, enable: bool = True, keep12: bool = False) -> None:
         """Steps of 4..16 rows (beam search, small batches, contrastive search, the lookup chunk step) stream the packed sets too,
         through the matrix-core twin of the bf16 few-row stream: same bits, 13/16 of the bytes.  Off by default
-        (profiles/bf16_pack_wide.md); needs ``use_bf16_pack`` on.  Invalidates captured graphs."""
+        (profiles/bf16_pack_wide.md); needs ``use_bf16_pack`` on.  Invalidates captured graphs.  Without ``keep12`` every 12-bit set
+        is repacked to 13 bits first (the one-row steps then stream 13 bits too); with it the sets stay as they are and a matrix that
+        holds a 12-bit set goes to the twin's 12-bit form (the library's switch value 2, profiles/bf16_pack12_wide.md): one resident
+        set serves both the one-row and the few-row step.  Tensor-parallel shards hold 13-bit sets either way."""
         if enable and not self.bf16_released and not self.bf16_pack_on:
             raise RuntimeError("use_bf16_pack_wide: switch the packed stream on first (use_bf16_pack)")
-        if enable:
+        if enable and keep12 and not hasattr(lib(), "emu_linear_bf16pack12_thin"):
+            raise RuntimeError("use_bf16_pack_wide: this library has no 12-bit few-row stream (keep12)")
+        if enable and not keep12:
             self._repack_13()
-        check(lib().emu_llama_use_bf16_pack_wide(self.handle, 1 if enable else 0), "emu_llama_use_bf16_pack_wide", self.ctx.handle)
+        check(lib().emu_llama_use_bf16_pack_wide(self.handle, (2 if keep12 else 1) if enable else 0), "emu_llama_use_bf16_pack_wide",
+              self.ctx.handle)
         self.bf16_pack_wide = bool(enable)
         self._mode_changed()
 
     def _repack_13(self) -> None:
-        """The few-row twin reads 13-bit sets only: give every matrix that holds a 12-bit set a 13-bit one in its place (the one-row
+        """``use_bf16_pack_wide`` without ``keep12``: give every matrix that holds a 12-bit set a 13-bit one in its place (the one-row
         steps then stream 13 bits too; a matrix holds one set).  Nothing to do where the sets are 13-bit already."""
         pk = getattr(self, "_pack", {})
         k12 = [k for k, v in pk.items() if "patch" in v]
@@ -532,9 +538,13 @@ class LlamaEngine:
             print(f"emu_amd: bf16 pack stream: {len(k12)} sets repacked from 12 to 13 bits per weight for the 4..16-row stream", file=sys.stderr)
 
     def _pack_wide_default(self) -> None:
-        """EMU_BF16_PACK_WIDE=1 switches the few-row stream on where the default packing has switched the one-row stream on."""
-        if os.environ.get("EMU_BF16_PACK_WIDE") == "1" and not self.bf16_pack_wide and hasattr(lib(), "emu_llama_use_bf16_pack_wide"):
+        """EMU_BF16_PACK_WIDE=1 switches the few-row stream on where the default packing has switched the one-row stream on (on
+        13-bit sets); =12 does so with ``keep12``, on the sets the default packing made."""
+        want = os.environ.get("EMU_BF16_PACK_WIDE")
+        if want == "1" and not self.bf16_pack_wide and hasattr(lib(), "emu_llama_use_bf16_pack_wide"):
             self.use_bf16_pack_wide(True)
+        elif want == "12" and not self.bf16_pack_wide and hasattr(lib(), "emu_linear_bf16pack12_thin"):
+            self.use_bf16_pack_wide(True, keep12=True)
 
     def _auto_pack_bf16(self) -> None:
         """The default: when the engine is ready, pack and switch the stream on -- unless EMU_BF16_PACK=0, the library predates the

@@ -202,7 +202,7 @@ def linear_bf16pack(x, w, p, form: int, res=None, norm_w=None, eps: float = 0.0,
 
 def linear_bf16pack_thin(x, w, p, res=None, epi: int = EPI_NONE, out=None):
     """4..16 activation rows over the packed set ``p`` of ``w`` on the matrix cores, the bits of ``linear(x, w)``; the library
-    refuses (-22) what has no packed twin; see emu_linear_bf16pack_thin."""
+    refuses (-22) what has no packed twin; see emu_linear_bf16pack_thin (a 12-bit set: emu_linear_bf16pack12_thin)."""
     _req(x, "x"); _req(w, "w")
     assert x.dim() == 2 and x.is_contiguous() and w.is_contiguous() and tuple(w.shape) == tuple(p["shape"]) and x.shape[1] == w.shape[1]
     M, (N, K) = x.shape[0], w.shape
@@ -210,6 +210,11 @@ def linear_bf16pack_thin(x, w, p, res=None, epi: int = EPI_NONE, out=None):
         out = torch.empty(M, N // 2 if epi == EPI_SWIGLU else N, device=x.device, dtype=BF16)
     _req(out, "out")
     assert out.is_contiguous() and (res is None or (res.is_contiguous() and tuple(res.shape) == (M, N)))
+    if "patch" in p:                                 # a 12-bit set: its own entry point
+        s = pack12_set_c(p)
+        check(lib().emu_linear_bf16pack12_thin(_p(x), _p(w), C.byref(s), _p(res), _p(out), M, N, K, int(epi), stream(x)),
+              "emu_linear_bf16pack12_thin")
+        return out
     s = pack_set_c(p)
     check(lib().emu_linear_bf16pack_thin(_p(x), _p(w), C.byref(s), _p(res), _p(out), M, N, K, int(epi), stream(x)),
           "emu_linear_bf16pack_thin")

@@ -757,8 +757,8 @@ int emu_linear_bf16pack(const void* A, const void* W, const emu_bf16_pack_set* s
  * 32 * ceil(N/rows) bytes, flags as there; *hb_out = hb, *flagged_out = the number of flagged row groups.  Waits for its own results.
  * emu_linear_bf16pack12 (tests): emu_linear_bf16pack over a 12-bit set; bit-identical to emu_linear_bf16 on W.
  * emu_llama_set_layer_bf16_pack12 / emu_llama_set_head_bf16_pack12: the 12-bit counterparts of the two setters below (a matrix's set
- * of either format replaces the one it had).  The one-row streams read a 12-bit set; the 4..16-row twin has none and leaves such a
- * matrix on the bf16 kernel. */
+ * of either format replaces the one it had).  The one-row streams read a 12-bit set; the 4..16-row twin reads one only under
+ * emu_llama_use_bf16_pack_wide(m, 2) and otherwise leaves such a matrix on the bf16 kernel. */
 typedef struct emu_bf16_pack12_set { const void *lo, *nib, *patch, *flags; int hb, rows; } emu_bf16_pack12_set;
 int emu_bf16_pack12(const void* w_bf16, int ldw, int N, int K, int rows, void* lo, void* nib, void* patch, void* flags, int* hb_out,
                     int* flagged_out, emu_stream_t s);
@@ -781,13 +781,21 @@ int emu_llama_pack_kernel(int kernel, int rows, int pack_rows, int pack_on, int 
  * emu_linear_bf16pack_thin (tests): C[M, N] = epi(A W^T [+ res]) for 4 <= M <= 16 rows of K contiguous elements over the set of the
  * bf16 matrix W [N, K] (read for flagged row groups); epi NONE / RESID (res [M, N]) / SWIGLU (C [M, N / 2]).  -22, nothing
  * written, where emu_gemv_pack_thin_plan refuses or a pointer is missing or a plane is off a 16-byte boundary.
- * emu_llama_use_bf16_pack_wide(m, 1): OFF by default; with emu_llama_use_bf16_pack on, projections and the head at 4..16 rows that
- * are on the bf16 kernels stream their set where emu_llama_projection_kernel says so.  Refused after emu_llama_release_bf16.
+ * emu_linear_bf16pack12_thin (tests): the same over a 12-bit set (the kernel's 12-bit twin: no sign piece in a stage, the row groups'
+ * patch records applied to the decoded fragments); the same bits.  Also -22: a set without its patch pointer, records off a 16-byte
+ * boundary, hb outside 0..120, K / 8 >= 2^18.
+ * emu_llama_use_bf16_pack_wide(m, on): OFF (0) by default; with emu_llama_use_bf16_pack on, projections and the head at 4..16 rows that
+ * are on the bf16 kernels stream their set where emu_llama_projection_kernel says so.  on = 1: matrices with a 13-bit set only -- one
+ * that holds a 12-bit set is not offered to the rule at more than one row (pack_rows 0) and stays on the bf16 kernel there.  on = 2:
+ * 12-bit sets are offered too, so one resident set serves a matrix's one-row and 4..16-row steps (13-bit sets go to the 13-bit twin
+ * as under 1).  Any other non-zero value counts as 1.  Refused after emu_llama_release_bf16.
  * emu_llama_pack_thin_kernel (CPU test hook, tests/test_pack_thin_plan.py): the matrix-level rule of emu_llama_projection_kernel for
  * `kernel` (0..8, else -22) at a layer projection with an fp8 copy, a set of pack_rows rows per group for [set_n, set_k], the two
  * switches as given and the one-row stream inhibited: 8 or `kernel`. */
 int emu_linear_bf16pack_thin(const void* A, const void* W, const emu_bf16_pack_set* set, const void* res, void* C, int M, int N, int K,
                              int epi, emu_stream_t s);
+int emu_linear_bf16pack12_thin(const void* A, const void* W, const emu_bf16_pack12_set* set, const void* res, void* C, int M, int N, int K,
+                               int epi, emu_stream_t s);
 int emu_llama_use_bf16_pack_wide(emu_llama* m, int on);
 int emu_llama_pack_thin_kernel(int kernel, int rows, int pack_rows, int set_n, int set_k, int pack_on, int wide_on, int N, int K, int norm,
                                int epi, int tune);
